@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the planning hot path on MI355X (contract: see the task statement / DESIGN.md §Measurement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload uct|opd|vi|vi_dense] [--roots R]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload uct|opd|vi|vi_dense] [--roots R] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`metric`, `value`, `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` = wall milliseconds of one timed step); with --dump-outputs DIR it also writes what the last timed step
+returned to its caller as DIR/<name>.npy (float32 / float64; the inputs are seeded, so runs with the same arguments compare
+output for output).  Everything else below -- the CPU baselines, the other workloads' slices, the oracle replay of a sample,
+kernel times, roofline and counter figures, latency and host-inclusive forms, the multi-GPU cross-check -- runs with --full.
 
 Default workload = the BASELINE.json headline: MCTS/UCT on a highway-shaped finite MDP
 (S = 10 000, |A| = 5), budget 1000 as 33 episodes x horizon 30, 262 144 independent roots per GPU (the saturated batch;
@@ -20,9 +27,9 @@ in the line prices it: pack + collective + unpack in ms, and whether it ran unde
 mp_unpack_rows, nothing through the host), cross-checked inside the run: rank 0 re-plans a sample of ANOTHER rank's roots
 and compares it with what the gather delivered (`ranks.cross_check`).
 
-With N > 1 the default run also shards BASELINE configs C4 (OPD, 1024 roots per GPU) and C5 (dense robust VI, one 25 GB row
+With N > 1 the --full run also shards BASELINE configs C4 (OPD, 1024 roots per GPU) and C5 (dense robust VI, one 25 GB row
 block per GPU with the per-sweep all_gather of V) and attaches them under `workloads`.
-The default run (headline workload, one GPU) also runs every other workload of the path for a bounded slice and attaches
+The --full run (headline workload, one GPU) also runs every other workload of the path for a bounded slice and attaches
 `workloads: {name: {value, kernel_ms, frac, traffic_frac, parity_sample}}` to the one JSON line; `parity_sample` replays a
 sample of the timed launch's own roots (or three sweeps) through the CPU oracle.
 
@@ -63,7 +70,41 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=4.0)
     ap.add_argument("--headline-only", action="store_true", help="skip the bounded slices of the other workloads")
     ap.add_argument("--no-parity-sample", action="store_true", help="skip the oracle replay of a sample of the timed launch")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (CPU baselines, the other workloads, "
+                         "oracle replay, kernel / roofline / counter figures); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if not args.full:
+        args.headline_only = args.no_cpu_baseline = args.no_parity_sample = True
+    return args
+
+
+DUMP_LIMIT = 64 << 20       # bytes of --dump-outputs in all
+
+
+def dump_outputs(directory, outputs):
+    """outputs {name: array} -> directory/<name>.npy: float32 arrays as they are, everything else in float64 (exact for
+    integers below 2**53).  Beyond DUMP_LIMIT a fixed, seeded sample of the leading axis is written (the same rows for every
+    array of that length) and its indices go to directory/sample_rows.npy."""
+    arrays = {}
+    for name, a in outputs.items():
+        a = np.asarray(a)
+        arrays[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        n = max(len(a) for a in arrays.values() if a.ndim)
+        rows = [k for k, a in arrays.items() if a.ndim and len(a) == n]
+        row_bytes = sum(arrays[k].nbytes // n for k in rows) + 8
+        fixed = total - sum(arrays[k].nbytes for k in rows) + 4096 * (len(arrays) + 1)      # (+ the .npy headers)
+        size = max(1, (DUMP_LIMIT - fixed) // row_bytes)
+        keep = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, size=size, replace=False))
+        arrays = {k: (a[keep] if k in rows else a) for k, a in arrays.items()}
+        arrays["sample_rows"] = keep.astype(np.float64)
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def self_launch(args):
@@ -180,6 +221,7 @@ def run_slices(args, rank, world, local, slices=None):
         # (every slice carries its own bounded CPU baseline -- the C port on this host's cores for about a second -- and the
         # unmodified Python reference's committed timing of the same workload beside it: VERDICT r4)
         sub.workload, sub.steps, sub.warmup, sub.roots = workload, steps, 1, roots
+        sub.dump_outputs = None                                   # (--dump-outputs is the headline's)
         sub.no_cpu_baseline, sub.cpu_seconds = args.no_cpu_baseline or world > 1, 1.0
         sub.dense_mode = mode[0] if mode and mode[0] else ("mfma" if workload == "rvi_dense_shard" else None)
         if len(mode) > 1:
@@ -247,6 +289,12 @@ def main():
             # the other two BASELINE configurations that are sharded over the GPUs of a node, in the same launch the driver
             # times: C4 (OPD, 1024 roots per GPU) and C5 (dense robust VI, one row block per GPU, all_gather of V per sweep)
             res["workloads"] = run_slices(args, rank, world, local, slices=SLICES_MULTI_GPU)
+    outputs = res.pop("_outputs", None)
+    if args.dump_outputs and rank == 0:
+        if outputs is None:
+            print("bench.py: --dump-outputs is not available for --workload {}".format(args.workload), file=sys.stderr)
+            sys.exit(2)
+        dump_outputs(args.dump_outputs, outputs)
     res.setdefault("cpu_baseline", None)
     if isinstance(res["cpu_baseline"], dict):
         # the reference's own (pure Python) CPU path on the same tables: it cannot travel to the GPU box, so its timing is
@@ -259,14 +307,15 @@ def main():
         # the long form first (one JSON object per workload, also written to bench_detail.json), then the ONE compact line the
         # driver parses: <= 4 KB, strict JSON (benchmarks/report.py; tests/test_bench_line.py)
         from benchmarks.report import compact_line, detail_lines
-        detail = detail_lines(res)
+        detail = detail_lines(res) if args.full else []       # (a plain run has no long form)
         for ln in detail:
             print(ln)
+        side = os.environ.get("BENCH_DETAIL_FILE") or os.path.join(REPO, "bench_detail.json")
         try:
-            side = os.environ.get("BENCH_DETAIL_FILE") or os.path.join(REPO, "gpurun_out", "bench_detail.json")
-            os.makedirs(os.path.dirname(side), exist_ok=True)
-            with open(side, "w") as f:
-                f.write("\n".join(detail) + "\n")
+            if detail:
+                os.makedirs(os.path.dirname(side), exist_ok=True)
+                with open(side, "w") as f:
+                    f.write("\n".join(detail) + "\n")
         except OSError:
             pass
         sys.stdout.flush()

@@ -92,7 +92,7 @@ def compact(res):
               "mfma_frac_of_f64_peak"):
         if k in roof:
             r[k] = sig(roof[k], 5)
-    out["roofline"] = r
+    out["roofline"] = r if roof else None                      # (a plain run measures no kernel time: no roofline)
     cpu = res.get("cpu_baseline")
     if isinstance(cpu, dict):
         b = dict(value=sig(cpu.get("value"), 5), unit=cpu.get("unit"), cores=cpu.get("cores"), kind=cpu.get("kind"),
@@ -131,7 +131,8 @@ def compact(res):
     if isinstance(w, dict):
         out["workloads"] = {name: slice_summary(rec) for name, rec in w.items()}
         out["workloads_key"] = "v=value ms=ms/step kms=kernel ms frac=algorithmic/peak tfrac=PMC bytes/peak par=oracle replay"
-    out["detail"] = "earlier stdout lines (one JSON object per workload) and bench_detail.json"
+    if roof:
+        out["detail"] = "earlier stdout lines (one JSON object per workload) and bench_detail.json"
     return out
 
 

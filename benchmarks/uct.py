@@ -55,6 +55,7 @@ def bench_uct(args, rank, world, local, with_prior=False):
             ctx.uct_plan_device(model, n_roots, d_s0, episodes, horizon, gamma, temperature, p, p, d_rng, mpl,
                                 plans=d_plans, plan_len=d_len, root_value=d_val, env_steps=d_steps, policy=policy)
             d_total.add_(d_steps.sum())
+            return dict(plans=d_plans, plan_len=d_len, value=d_val, env_steps=d_steps)
     else:
         from rl_agents_amd.agents.common.factory import agent_factory
         from rl_agents_amd.distributed import ShardedDevicePlan
@@ -75,7 +76,7 @@ def bench_uct(args, rank, world, local, with_prior=False):
         d_rng = sp.d_rng
         # ---- cross-check inside the run: what the gather delivered for ANOTHER rank's roots == rank 0's own re-plan
         first = sp.wait(sp.plan(d_s0))
-        if rank == 0:
+        if rank == 0 and args.full:
             other = 1 % world
             k = min(256, n_roots)
             lo_o = other * n_roots + (n_roots - k) // 2            # a block from the middle of that rank's shard
@@ -97,8 +98,9 @@ def bench_uct(args, rank, world, local, with_prior=False):
         d_plans, d_len, d_val, d_steps = loc["plans"], loc["plan_len"], loc["value"], loc["env_steps"]
 
         def step():
-            sp.plan(d_s0)
+            out = sp.plan(d_s0)
             d_total.add_(sp.local[(sp.turn - 1) % len(sp.local)]["env_steps"].sum())
+            return out
 
     for _ in range(args.warmup):
         step()
@@ -109,10 +111,34 @@ def bench_uct(args, rank, world, local, with_prior=False):
     barrier(world)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     barrier(world)
     dt = time.perf_counter() - t0
     timed_env_steps = int(d_total.item())
+    metric = "rollout env-steps/sec (UCT plan(), budget=1000)"
+    workload = "{}_highway_shaped_S{}_A{}_budget1000_e{}xh{}_roots{}_per_gpu".format(
+        "uct_with_vi_boltzmann_prior" if with_prior else "uct", s_, a_, episodes, horizon, n_roots)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path received from its last step, copied to the host before anything else runs
+        if sp is not None:
+            sp.wait(last)
+        outputs = {k: last[k].cpu().numpy() for k in ("plans", "plan_len", "value", "env_steps", "status") if k in last}
+    if not args.full:
+        # a plain run: the headline figure and nothing else (everything below is measured with --full only)
+        dt = max_over_ranks(dt, world)
+        total_env_steps = sum_over_ranks(float(timed_env_steps), world) / args.steps
+        res = dict(metric=metric, unit="env-steps/s", value=total_env_steps * args.steps / dt, ms_per_step=1e3 * dt / args.steps,
+                   dtype="f64",
+                   config=dict(workload=workload, n_roots_per_gpu=n_roots, n_roots_total=n_roots * world, states=s_, actions=a_,
+                               episodes=episodes, horizon=horizon, gamma=gamma, env_steps_per_step=total_env_steps,
+                               plan_ms_per_root=1e3 * dt / args.steps / n_roots,
+                               value_definition_short="device-resident: roots, generator records and results stay in HBM",
+                               parallelism="roots sharded over {} GPU(s)".format(world)))
+        if outputs is not None:
+            res["_outputs"] = outputs
+        ctx.synchronize()
+        return res
     # per-launch kernel time from HIP events on the kernel's stream (separate short pass so that the
     # event synchronisation does not sit inside the timed region above)
     def last_buffers():
@@ -235,7 +261,7 @@ def bench_uct(args, rank, world, local, with_prior=False):
     k_ms = float(np.mean(kernel_ms))
     nl4 = min(4096, n_roots)
     res = dict(
-        metric="rollout env-steps/sec (UCT plan(), budget=1000)", unit="env-steps/s",
+        metric=metric, unit="env-steps/s",
         value=total_env_steps * args.steps / dt, ms_per_step=1e3 * dt / args.steps,
         # the same metric on SURVEY.md 8(d)'s own terms: host arrays in / out (PCIe inclusive) and the 4096-root batch
         value_host_inclusive=sum_over_ranks(hi_val, world), host_inclusive_ms_per_step=hi_ms,
@@ -249,8 +275,7 @@ def bench_uct(args, rank, world, local, with_prior=False):
         host_inclusive_pageable_all_outputs_ms={str(k): v for k, v in pageable_ms.items()},
         host_inclusive_kernel_ms={str(k): v for k, v in host_kernel_ms.items()},
         dtype="f64",
-        config=dict(workload="{}_highway_shaped_S{}_A{}_budget1000_e{}xh{}_roots{}_per_gpu".format(
-            "uct_with_vi_boltzmann_prior" if with_prior else "uct", s_, a_, episodes, horizon, n_roots), n_roots_per_gpu=n_roots, n_roots_total=n_roots * world,
+        config=dict(workload=workload, n_roots_per_gpu=n_roots, n_roots_total=n_roots * world,
             states=s_, actions=a_, episodes=episodes, horizon=horizon, gamma=gamma,
             env_steps_per_step=total_env_steps, plan_ms_per_root=1e3 * dt / args.steps / n_roots, latency=latency,
             value_definition="`value` = device-resident: roots, generator records and results stay in HBM (this tier's "
@@ -338,6 +363,8 @@ def bench_uct(args, rank, world, local, with_prior=False):
                   and np.array_equal(got["value"], ref["root_value"]) and np.array_equal(got["env_steps"], ref["env_steps"]))
             res["parity_sample"] = parity_record(ok, "{} roots of a {}-root launch vs oracle.uct_plan_batch: plans, plan_len, root "
                                                  "value, env_steps bit for bit".format(len(idx), n_roots))
+    if outputs is not None:
+        res["_outputs"] = outputs
     if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the host baseline is an N = 1 figure
         from oracle import oracle
         cores = host_cores()

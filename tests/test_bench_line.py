@@ -84,3 +84,55 @@ def test_line_degrades_instead_of_growing():
     line = report.compact_line(res)
     assert len(line) <= report.LINE_LIMIT
     assert len(_strict(line)["workloads"]) == len(res["workloads"])
+
+
+def test_plain_run_line_carries_the_headline_only():
+    """A plain run (no --full) has no roofline, baseline or slices: its line still carries the contract's headline keys."""
+    res = dict(metric="rollout env-steps/sec (UCT plan(), budget=1000)", unit="env-steps/s", value=1.5e11, ms_per_step=0.79,
+               dtype="f64", n_gpus=1, steps=20, warmup=3, higher_is_better=True, scaling="weak", vs_baseline=None,
+               config=dict(workload="uct_highway_shaped", value_definition_short="device-resident"), cpu_baseline=None)
+    out = _strict(report.compact_line(res))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert out[k] == res[k], k
+    assert out["roofline"] is None and out["cpu_baseline"] is None and "workloads" not in out and "detail" not in out
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_driver", os.path.join(REPO, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_full_is_off_by_default(monkeypatch):
+    bench = _bench_module()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "7", "--warmup", "2"])
+    args = bench.parse()
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    assert args.headline_only and args.no_cpu_baseline and args.no_parity_sample
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full and args.dump_outputs == "d" and not (args.headline_only or args.no_cpu_baseline or args.no_parity_sample)
+
+
+def test_dump_outputs_float_files_within_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    bench = _bench_module()
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 1 << 20)          # (the sampling path, on small arrays)
+    plans = np.arange(40, dtype=np.int32).reshape(10, 4)
+    bench.dump_outputs(str(tmp_path / "small"), dict(plans=plans, value=np.linspace(0, 1, 10), f=np.ones(3, np.float32)))
+    got = {p.stem: np.load(p) for p in (tmp_path / "small").iterdir()}
+    assert set(got) == {"plans", "value", "f"} and got["plans"].dtype == np.float64 and got["f"].dtype == np.float32
+    assert np.array_equal(got["plans"], plans) and np.array_equal(got["value"], np.linspace(0, 1, 10))
+    # beyond the limit: the same seeded rows of every array of the batch's length, and their indices
+    n = 3 * bench.DUMP_LIMIT // 16
+    big = dict(a=np.arange(n, dtype=np.int64), b=np.arange(n, dtype=np.float64) * 0.5, c=np.ones(5))
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = list((tmp_path / "big1").iterdir())
+    assert sum(p.stat().st_size for p in files) <= bench.DUMP_LIMIT
+    rows = np.load(tmp_path / "big1" / "sample_rows.npy").astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "big1" / "a.npy"), rows) and np.array_equal(np.load(tmp_path / "big1" / "b.npy"), rows * 0.5)
+    assert np.array_equal(rows, np.load(tmp_path / "big2" / "sample_rows.npy").astype(np.int64))
+    assert np.load(tmp_path / "big1" / "c.npy").shape == (5,)

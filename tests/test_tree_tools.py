@@ -1,16 +1,13 @@
 """Consumers of an exported tree, CPU only: the Node API of this package -- breadth_first_search,
 get_trajectories, get_obs_visits, path / sequence, TreePlot -- on trees rebuilt from the reference's own plans, against
 what the UNMODIFIED reference returned for those trees (tests/golden/tree_tools.npz, tests/golden/gen/make_golden_trees.py),
-and, in the build container, the reference's TreePlot drawing this package's Node tree."""
+and the segments the reference's TreePlot drew for this package's Node tree (tests/golden/reference_tree_plot.json)."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 
 @pytest.fixture(scope="module")
@@ -110,37 +107,19 @@ def test_tree_plot_segments(trees):
     assert writer.images == [("Expanded_tree", image.shape, 3)] and image.shape[0] == 3 and image.dtype == np.uint8
 
 
-SCRIPT = r'''
-import os, sys, types
-sys.dont_write_bytecode = True
-repo, ref = sys.argv[1], sys.argv[2]
-sys.path[:0] = [os.path.join(repo, "tests", "golden", "gen", "stubs"), ref, repo]
-import matplotlib
-matplotlib.use("Agg")
-import matplotlib.pyplot as plt
-import numpy as np
-from rl_agents.agents.tree_search.graphics import TreePlot as RefTreePlot          # the REFERENCE's plot
-from rl_agents_amd.agents.tree_search.graphics import TreePlot
-sys.path.insert(0, os.path.join(repo, "tests"))
-from test_tree_tools import rebuild
-z = np.load(os.path.join(repo, "tests", "golden", "tree_tools.npz"))
-for name, n_actions in (("uct_highway_small", 5), ("opd_grid_c1", 4)):
-    root = rebuild(z, name)
-    planner = types.SimpleNamespace(root=root, env=types.SimpleNamespace(action_space=types.SimpleNamespace(n=n_actions)))
-    fig, ax = plt.subplots()
-    RefTreePlot(planner, max_depth=6).plot(filename=None, ax=ax)                    # reads planner.root / children / count
-    theirs = sorted((round(float(l.get_xdata()[0]), 9), round(float(l.get_ydata()[0]), 9), round(float(l.get_xdata()[1]), 9),
-                     round(float(l.get_ydata()[1]), 9), round(float(l.get_linewidth()), 9)) for l in ax.lines)
-    ours = sorted(tuple(round(float(v), 9) for v in s) for s in TreePlot(planner, max_depth=6).segments())
-    assert len(theirs) > 10 and theirs == ours, (name, len(theirs), len(ours))
-print("ok")
-'''
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference only exists in the build container")
-def test_reference_tree_plot_draws_this_packages_tree():
+def test_reference_tree_plot_draws_this_packages_tree(trees):
     """The reference's TreePlot (tree_search/graphics.py:115-147) takes the exported Node tree as it is, and draws the very
-    segments this package's TreePlot lists."""
-    out = subprocess.run([sys.executable, "-c", SCRIPT, REPO, REF], capture_output=True, text=True, timeout=300,
-                         env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
+    segments this package's TreePlot lists (tests/golden/reference_tree_plot.json: the segments the unmodified reference
+    drew for these trees, tests/golden/gen/make_golden_dropin.py)."""
+    import json
+    import types
+    from rl_agents_amd.agents.tree_search.graphics import TreePlot
+    with open(os.path.join(REPO, "tests", "golden", "reference_tree_plot.json")) as f:
+        record = json.load(f)
+    assert set(record["trees"]) == {"uct_highway_small", "opd_grid_c1"}
+    for name, rec in record["trees"].items():
+        planner = types.SimpleNamespace(root=rebuild(trees, name),
+                                        env=types.SimpleNamespace(action_space=types.SimpleNamespace(n=rec["n_actions"])))
+        theirs = [tuple(s) for s in rec["segments"]]
+        ours = sorted(tuple(round(float(v), 9) for v in s) for s in TreePlot(planner, max_depth=record["max_depth"]).segments())
+        assert len(theirs) > 10 and theirs == ours, (name, len(theirs), len(ours))

@@ -10,9 +10,9 @@ timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu_full.log 2>&1
 echo "pytest rc=$?" >> $O/pytest_gpu_full.log
 tail -8 $O/pytest_gpu_full.log | cut -c1-250
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1 | cut -c1-160
-( time timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
+( time timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time
 tail -3 $O/bench_default.time
-( time timeout 900 python bench.py --gpus 2 --steps 5 --warmup 2 --roots 65536 > $O/bench_2rank.json 2> $O/bench_2rank.err ) 2> $O/bench_2rank.time
+( time timeout 900 python bench.py --full --gpus 2 --steps 5 --warmup 2 --roots 65536 > $O/bench_2rank.json 2> $O/bench_2rank.err ) 2> $O/bench_2rank.time
 python - $O <<'PY'
 import json, sys
 o = sys.argv[1]

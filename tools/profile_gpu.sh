@@ -5,6 +5,7 @@
 #   usage: tools/profile_gpu.sh r01
 set -u
 TAG=${1:-r05}
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 OUT=/root/repo/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
@@ -25,14 +26,14 @@ args_of() {
 # (TRACE_WLS / PMC_WLS: re-collect a subset after a kernel changed; summarize_profiles.py reads whatever is there)
 for wl in ${TRACE_WLS:-uct uct4096 uct1024 uct256 uct1 uct_per_root_model uct_prior uct_cartpole uct_stoch opd opd8192 ropd saopd vi rvi vi_batch vi_batch_s10000 vi_batch_s10000_256 vi_dense vi_dense_exact rvi_dense_shard rvi_dense_shard_exact}; do
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$wl -o $wl -- \
-      python /root/repo/bench.py $(args_of $wl) --steps 5 --warmup 1 --no-cpu-baseline --headline-only --no-parity-sample > $OUT/trace_$wl.log 2>&1
+      python $BENCH $(args_of $wl) --steps 5 --warmup 1 --full --no-cpu-baseline --headline-only --no-parity-sample > $OUT/trace_$wl.log 2>&1
 done
 # HBM traffic: FETCH_SIZE and WRITE_SIZE cannot share a pass (TCC slots) -> two runs each; counters only,
 # no tracing domains besides the kernel trace
 for wl in ${PMC_WLS:-uct uct4096 uct_per_root_model uct_prior uct_cartpole uct_stoch vi rvi vi_batch vi_batch_s10000 vi_batch_s10000_256 vi_dense vi_dense_exact rvi_dense_shard rvi_dense_shard_exact opd opd8192 ropd saopd}; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     timeout 300 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $OUT/pmc_${wl}_$ctr -o $wl -- \
-        python /root/repo/bench.py $(args_of $wl) --steps 3 --warmup 1 --no-cpu-baseline --headline-only --no-parity-sample > $OUT/pmc_${wl}_$ctr.log 2>&1
+        python $BENCH $(args_of $wl) --steps 3 --warmup 1 --full --no-cpu-baseline --headline-only --no-parity-sample > $OUT/pmc_${wl}_$ctr.log 2>&1
   done
 done
 find $OUT -name "*.csv" | head -50

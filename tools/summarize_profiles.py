@@ -49,7 +49,7 @@ def main():
     os.makedirs(dst, exist_ok=True)
     lines = ["# rocprofv3 --kernel-trace --stats summaries ({})".format(tag), "",
              "Command per workload: `rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py "
-             "--workload <wl> --steps 5 --warmup 1 --no-cpu-baseline --headline-only --no-parity-sample` on one MI355X (tools/profile_gpu.sh; BENCH_NO_LIVE_PMC unset is harmless: --headline-only skips it).", ""]
+             "--workload <wl> --steps 5 --warmup 1 --full --no-cpu-baseline --headline-only --no-parity-sample` on one MI355X (tools/profile_gpu.sh; BENCH_NO_LIVE_PMC unset is harmless: --headline-only skips it).", ""]
     for wl in ("uct", "uct4096", "uct1024", "uct256", "uct1", "uct_per_root_model", "uct_prior", "uct_cartpole", "uct_stoch", "opd", "opd8192", "ropd", "saopd", "vi", "rvi",
                "vi_batch", "vi_batch_s10000", "vi_batch_s10000_256", "vi_dense", "vi_dense_exact", "rvi_dense_shard", "rvi_dense_shard_exact"):
         f = os.path.join(src, "trace_" + wl, wl + "_kernel_stats.csv")
