@@ -255,9 +255,13 @@ int mp_vi_solve(mp_ctx *ctx, mp_model *model, double gamma, int32_t iterations, 
  * one workgroup per MDP -- the fixed-point iteration of each MDP runs to ITS OWN allclose exit, exactly as N
  * ValueIterationAgent objects would (value_iteration.py:42-45,65-73 per agent; trainer/evaluation.py:139-194 runs one
  * agent per process).  Bit-exact with N mp_vi_solve calls on the N tables.
- *   Q_out double [N,S,A] (= [N*S, A] over global states: what mp_greedy_actions takes), sweeps_out int32 [N].
+ *   Q_out double [N,S,A] (= [N*S, A] over global states: what mp_greedy_actions takes), sweeps_out int32 [N];
+ *   either may be NULL (that output is not written).
  * mem = MP_MEM_DEVICE only enqueues.  Rows of an MDP live in registers and its value vector in LDS when
  * S <= 4096 (any such S), else the value vector is double-buffered in LDS (S <= 10 200) or kept in global memory.
+ * Batches of few large MDPs run K = 2 / 4 / 8 workgroups per MDP that must all be resident at once; on a GPU shared with
+ * other work a cluster that does not meet gives up (bounded spins, no hang) and the MDP is solved again by a follow-up
+ * launch of the same call -- in both memory modes the caller receives the exact result, never a failure report.
  */
 int mp_vi_solve_batch(mp_ctx *ctx, mp_model *model, double gamma, int32_t iterations, double rtol, double atol,
                       double *Q_out, int32_t *sweeps_out, int32_t mem);

@@ -260,6 +260,7 @@ struct ViPersistArgs {
     unsigned *sync;   // [0] timeout flag, [1 + k] arrivals (low 16 bits) + moved count (high bits) of sweep k
     double *Q_out, *V_out;
     int32_t *sweeps_out;
+    int give_wg, give_sweep; // test hook (give_wg >= 0): that workgroup's gather at that sweep counts as timed out
 };
 
 constexpr int kLag = 2, kRing = kLag + 2;
@@ -338,6 +339,7 @@ __global__ __launch_bounds__(1024) void vi_det_persist(ViPersistArgs q)
                 if (m == 0 || qm < qn[a]) qn[a] = qm;       // robust_value_iteration.py:46-48 (MT = 1: plain VI)
             }
         }
+        if (k == q.give_sweep && (int)blockIdx.x == q.give_wg) ok = false;  // (test hook: what a spin that ran out leaves)
         bool nc = false;
         double vmax = qn[0];
 #pragma unroll
@@ -354,7 +356,9 @@ __global__ __launch_bounds__(1024) void vi_det_persist(ViPersistArgs q)
         }
         // ---- per-workgroup: aggregate "moved" (bit 0) and "timed out" (bit 1), arrive for sweep k, publish the verdict
         // of sweep k - kLag to the other waves
-        const int agg = __syncthreads_or((own && nc ? 1 : 0) | (ok ? 0 : 2));
+        // (a bitwise OR over the workgroup: __syncthreads_or is a predicate -- it reduces !!x, which folded "timed out" into
+        // "moved", so a workgroup whose gather timed out went on without publishing and its partners spun out sweep after sweep)
+        const int agg = __ockl_wgred_or_i32((own && nc ? 1 : 0) | (ok ? 0 : 2));
         unsigned *bc = bcast + 2 * (k & 1);                 // double-buffered: one barrier per sweep
         if (tid == 0) {
             unsigned bad = (agg & 2) ? 1u : 0u, verdict = 1u;
@@ -1215,6 +1219,11 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
         MP_HIP(hipMemsetAsync(q.sync, 0, ((size_t)iterations + 4) * sizeof(unsigned), st));
         // test hook: a raised timeout word is what a grid that is not co-resident ends in (after its bounded spins)
         if (getenv("MP_VI_PERSIST_INJECT_TIMEOUT")) MP_HIP(hipMemsetAsync(q.sync, 1, 1, st));
+        // test hook MP_VI_PERSIST_GIVE_UP=wg,sweep: only that workgroup gives up, at that sweep (raises the timeout word, does
+        // not publish, does not arrive); the others run on until they notice or finish
+        q.give_wg = q.give_sweep = -1;
+        if (const char *e = getenv("MP_VI_PERSIST_GIVE_UP"))
+            if (sscanf(e, "%d,%d", &q.give_wg, &q.give_sweep) != 2) q.give_wg = q.give_sweep = -1;
         persist_sync = q.sync;
         MP_TRY(kernels_begin(ctx));
         if (!vi_persist_dispatch(q, A, M, st)) return fail(MP_ERR_ARG, "vi: no persistent kernel for |A| = %d, M = %d", A, M);
@@ -1358,7 +1367,8 @@ struct ViBatchArgs {
     double *Q_out;        // [N*Sb*A]
     int32_t *sweeps_out;  // [N]
     double *Vglobal;      // VGLOBAL form: [N][3][Sb]
-    int only_failed;      // VGLOBAL form as the cluster form's fallback: solve only the MDPs whose sweeps_out says -1
+    int only_failed;      // VGLOBAL form as the cluster form's fallback: solve only the MDPs whose gave_up word is set
+    unsigned *gave_up;    // cluster form: [N], raised by any workgroup of the MDP's cluster that left by the give-up exit
 };
 
 // REGISTER form (Sb <= OWN * BLOCK): a thread keeps the rows of its OWN states -- transitions, rewards and the last Q row,
@@ -1443,17 +1453,22 @@ __global__ __launch_bounds__(BLOCK) void vi_det_batch_reg(ViBatchArgs p)
 // copy with L1-bypassing (sc1) loads (cdna_hip_programming.md Guideline 16: sc1 stores -> s_waitcnt vmcnt(0) -> barrier ->
 // relaxed agent fetch_add; relaxed polls; sc1 reads).  A cluster's workgroups are block ids 8 apart: the dispatcher places block
 // b on XCD b % 8, so they share an L2 (a speed choice only; any placement is correct).  They must be co-resident: the host
-// launches at most one workgroup per CU, and a spin limit turns a cluster that never met into sweeps_out = -1, which the
-// follow-up launch (the global-memory workgroup form with only_failed) solves again.
+// launches at most one workgroup per CU, and a spin limit turns a cluster that never met into a raised gave_up[b], which the
+// follow-up launch (the global-memory workgroup form with only_failed) reads to solve the MDP again.  ANY workgroup that gives
+// up raises it: the one that gives up has already arrived, so its partners may see a complete word, finish the MDP's last sweep
+// and write their slices and a real sweep count -- the MDP is still incomplete (the failed slice is never written).
+// Test hook (give_part >= 0): workgroup give_part of MDP give_mdp (every MDP when < 0) arrives at sweep give_sweep and then takes
+// the give-up exit instead of polling, as a partner that never became resident makes the others do.
 template <int AT, int OWN>
 __global__ __launch_bounds__(1024) void vi_det_batch_cluster(ViBatchArgs p, int K, double *__restrict__ Vx, unsigned *__restrict__ words_all,
-                                                             unsigned need, unsigned spin_limit)
+                                                             unsigned need, unsigned spin_limit, int give_part, int give_sweep, int give_mdp)
 {
     extern __shared__ __attribute__((aligned(16))) double lds_v[];
     constexpr int NT = 1024;
     const int bid = blockIdx.x, xcd = bid & 7, slot = bid >> 3;
     const int b = (slot / K) * 8 + xcd, part = slot % K, tid = threadIdx.x, S = p.Sb;
     if (b >= p.N) return;
+    const int give_at = part == give_part && (give_mdp < 0 || b == give_mdp) ? give_sweep : -1;   // (test hook; -1: never)
     const int Sp = (S + K - 1) / K, s_lo = part * Sp, s_hi = min(S, s_lo + Sp), n_mine = max(s_hi - s_lo, 0);
     const long base = (long)b * S;
     double *V0 = lds_v, *V1 = lds_v + S;
@@ -1509,8 +1524,8 @@ __global__ __launch_bounds__(1024) void vi_det_batch_cluster(ViBatchArgs p, int 
         unsigned *bck = bc + 2 * (k & 1);
         if (tid == 0) {
             __hip_atomic_fetch_add(words + k, 1u + (agg ? 0x10000u : 0u), MP_RLX_AGENT);
-            unsigned spins = 0, w, bad = 0;
-            while (((w = __hip_atomic_load(words + k, MP_RLX_AGENT)) & 0xffffu) < need) {   // (need = K)
+            unsigned spins = 0, w = 0, bad = k == give_at ? 1u : 0u;
+            while (!bad && ((w = __hip_atomic_load(words + k, MP_RLX_AGENT)) & 0xffffu) < need) {   // (need = K)
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > spin_limit) { bad = 1; break; }
             }
@@ -1532,6 +1547,7 @@ __global__ __launch_bounds__(1024) void vi_det_batch_cluster(ViBatchArgs p, int 
         }
         __syncthreads();
     }
+    if (tid == 0 && sweeps < 0) __hip_atomic_store((gu32_t *)(p.gave_up + b), 1u, MP_RLX_AGENT); // (read after the kernel boundary)
     if (tid == 0 && part == 0 && p.sweeps_out) p.sweeps_out[b] = sweeps;
     if (p.Q_out && sweeps >= 0)
 #pragma unroll
@@ -1552,7 +1568,7 @@ __global__ __launch_bounds__(1024) void vi_det_batch_wg(ViBatchArgs p)
 {
     extern __shared__ __attribute__((aligned(16))) double lds_v[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, S = p.Sb, A = AT > 0 ? AT : p.A;
-    if (p.only_failed && p.sweeps_out[b] != -1) return;      // (uniform: before any barrier)
+    if (p.only_failed && p.gave_up[b] == 0) return;          // (uniform: before any barrier; the kernel boundary orders the word)
     const long base = (long)b * S;
     double *Vb = VLDS ? lds_v : p.Vglobal + (long)b * 3 * S; // VLDS: [2][S]; global: [3][S]
     constexpr int NB = VLDS ? 2 : 3;
@@ -1808,26 +1824,37 @@ static int vi_batch_launch(mp_ctx *ctx, ViBatchArgs &q, hipStream_t st, const ch
         while (K < 8 && (long)q.N * (K * 2) <= cus) K *= 2;
         if (const char *e = getenv("MP_VI_BATCH_CLUSTER")) K = atoi(e);    // 0 / 1: off; 2, 4, 8: forced
         const int own = K > 1 ? ((S + K - 1) / K + 1023) / 1024 : 99;
+        // (the kernel's static LDS -- __syncthreads_or's scratch, 256 bytes -- comes on top of the dynamic size: the same margin as
+        // the other LDS forms; without it S = 10 224 .. 10 239 failed in hipFuncSetAttribute instead of taking another form)
         const size_t lds = (size_t)2 * S * sizeof(double) + 16;
-        if (K > 1 && K <= 8 && own <= 3 && lds <= kLdsBytes && q.iterations > 0) {
+        if (K > 1 && K <= 8 && own <= 3 && lds <= kLdsBytes - 512 && q.iterations > 0) {
             double *Vx = nullptr;
             unsigned *words = nullptr;
             MP_TRY(ws_get(ctx, WS_VI1, (size_t)q.N * 3 * S, &Vx));          // (the cluster uses [N][2][S]; the fallback [N][3][S])
-            MP_TRY(ws_get(ctx, WS_VI3, (size_t)q.N * q.iterations, &words));
-            MP_HIP(hipMemsetAsync(words, 0, (size_t)q.N * q.iterations * sizeof(unsigned), st));
+            // one word per (MDP, sweep), then one give-up word per MDP: all cleared by every call
+            MP_TRY(ws_get(ctx, WS_VI3, (size_t)q.N * q.iterations + q.N, &words));
+            MP_HIP(hipMemsetAsync(words, 0, ((size_t)q.N * q.iterations + q.N) * sizeof(unsigned), st));
+            q.gave_up = words + (size_t)q.N * q.iterations;
             const unsigned cgrid = (unsigned)((q.N + 7) / 8) * 8 * K;
-            // (test hook MP_VI_BATCH_CLUSTER_NEVER_MEETS=1: a cluster waits for one arrival too many and gives up after a short spin)
+            // test hooks: MP_VI_BATCH_CLUSTER_NEVER_MEETS=1: every cluster waits for one arrival too many and gives up after a
+            // short spin; MP_VI_BATCH_CLUSTER_GIVE_UP=part,sweep[,mdp]: that one workgroup of the cluster gives up after its
+            // arrival at that sweep (short spins for every workgroup, so that its partners' later waits end soon)
             const bool hook = getenv("MP_VI_BATCH_CLUSTER_NEVER_MEETS") != nullptr;
-            const unsigned need = (unsigned)K + (hook ? 1u : 0u), spin = hook ? 2000u : kSpinLimit;
+            int give_part = -1, give_sweep = -1, give_mdp = -1;
+            if (const char *e = getenv("MP_VI_BATCH_CLUSTER_GIVE_UP"))
+                if (sscanf(e, "%d,%d,%d", &give_part, &give_sweep, &give_mdp) < 2) give_part = -1;
+            const unsigned need = (unsigned)K + (hook ? 1u : 0u), spin = hook || give_part >= 0 ? 2000u : kSpinLimit;
 #define MP_VC(o)                                                                                                            \
     {                                                                                                                       \
         MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vi_det_batch_cluster<AT, o>),                             \
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
-        hipLaunchKernelGGL((vi_det_batch_cluster<AT, o>), dim3(cgrid), dim3(1024), lds, st, q, K, Vx, words, need, spin);  \
+        hipLaunchKernelGGL((vi_det_batch_cluster<AT, o>), dim3(cgrid), dim3(1024), lds, st, q, K, Vx, words, need, spin,   \
+                           give_part, give_sweep, give_mdp);                                                                \
     }
             if (own == 1) MP_VC(1) else if (own == 2) MP_VC(2) else MP_VC(3)
 #undef MP_VC
-            // clusters that never met (a busy device): solved again by the global-memory workgroup form (returns at once otherwise)
+            // clusters with a raised give-up word (a busy device): solved again, Q and sweep count, by the global-memory workgroup
+            // form (which returns at once for every other MDP)
             ViBatchArgs f = q;
             f.only_failed = 1; f.Vglobal = Vx;
             hipLaunchKernelGGL((vi_det_batch_wg<AT, false>), dim3(grid), dim3(1024), 0, st, f);
