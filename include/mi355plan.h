@@ -36,6 +36,7 @@ extern "C" {
 #define MP_ERR_ALLOC (-3)
 #define MP_ERR_ARG (-4)          /* invalid argument / unsupported configuration                  */
 #define MP_ERR_MODE (-5)         /* model kind not valid for this call ("Unknown mode")           */
+#define MP_ERR_OLOP_KEY (-6)     /* OLOP status: the "zeros" continuation's action is not a child (olop.py:89 KeyError) */
 
 #define MP_MEM_HOST 0
 #define MP_MEM_DEVICE 1
@@ -477,6 +478,37 @@ int mp_opd_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int3
 int mp_opd_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *action,
                        int32_t *state, int32_t *depth, double *reward, double *lower, double *upper, uint8_t *done,
                        int64_t *count, int32_t *first_child, int32_t *n_children);
+
+/* ---------------------------------------------------------------- OLOP ---------------------- */
+/*
+ * OLOP.plan (tree_search/olop.py:94-100) for n_roots independent roots of a deterministic table model: `episodes` times
+ * OLOP.run (:64-92) -- one generator draw (state.seed(np_random.randint(2**30)), :73), then exactly `horizon` model steps
+ * (the reference does not stop at done): OLOPNode.expand (:165-180, the available actions in listing order) at a childless
+ * node followed by the continuation action, else the first child of maximal value_upper (:84); OLOPNode.update (:132-142,
+ * done sticky per node, reward range checked); compute_reward_ucb (:144-163); backup_to_root (:182-193) -- then get_plan
+ * (abstract.py:143-156) with OLOPNode.selection_rule (:126-130).  Replaces the reference's per-episode safe_deepcopy_env.
+ *   bound_type: 1 = "kullback-leibler" (kl_upper_bound, utils.py:123-203), anything else = mu_ucb stays inf (the reference
+ *     logs "Unknown upper-bound type").
+ *   continuation: < 0 = "uniform" (np_random.choice over the new children); >= 0 = the action label taken after an expansion
+ *     ("zeros": action 0 of the environment); status MP_ERR_OLOP_KEY where it is not among the children.
+ *   thresholds double [episodes]: the bound's threshold per episode (eval of the config string; read with bound_type 1 only).
+ *   value_upper_init double [horizon + 1]: (1 - gamma ** (horizon + 1 - depth)) / (1 - gamma) by depth (olop.py:113).
+ *   Both are host pointers: the host evaluates them with the reference's own Python operations.
+ *   rng_state [n_roots][6], advanced; plans int32 [n_roots, max_plan_len] (-1 padded), plan_len, root_value = the root's
+ *   value_upper, env_steps (= episodes * horizon without an error), status (MP_OK / MP_ERR_REWARD_RANGE / MP_ERR_OLOP_KEY).
+ * The step limit of the model plays no part: the reference folds a step's 5-tuple with done = terminated.
+ */
+int mp_olop_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
+                 double gamma, int32_t bound_type, int32_t continuation, const double *thresholds,
+                 const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len,
+                 double *root_value, int64_t *env_steps, int32_t *status, int32_t mem);
+/* Tree of root `root` after the last mp_olop_plan, in the reference's creation order (children contiguous, listing order):
+ * per node parent (-1 at the root), action, depth, count, cumulative_reward, mu_ucb, value_upper, done, state (olop.py:102-116);
+ * host arrays of capacity `cap` (at most 1 + episodes * horizon * |A| nodes).  When a batch's trees do not all fit the
+ * workspace only root 0's is kept (MP_ERR_ARG for the others). */
+int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *action,
+                        int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *value_upper,
+                        uint8_t *done, int32_t *state);
 
 /* ---------------------------------------------------------------- discrete robust OPD ------- */
 /*

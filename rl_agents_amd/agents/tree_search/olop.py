@@ -1,10 +1,194 @@
-"""Budget allocation used by MCTS when no horizon is configured (reference ``tree_search/olop.py:42-62``).
-Only these two functions of the reference's OLOP class are on the planning path."""
-from rl_agents_amd import native
+"""Open-Loop Optimistic Planning, OLOP / KL-OLOP, on the MI355X planning core (reference
+``rl_agents/agents/tree_search/olop.py``); the episodes run in ``mp_olop_plan`` (rl_agents_amd/csrc/olop.hip).
+
+Same class names, config keys and results as the reference on deterministic finite-MDP tables.  What the host computes:
+the budget split (``allocation``, also used by MCTS), the initial upper bounds by depth (Python ``**``) and the bound's
+threshold per episode (``eval`` of the config string) -- every constant that is not a basic IEEE operation.  The
+device computes the KL bound's Newton iteration with its own ``log``: bounds agree with the reference within 1e-12 and
+every discrete output is identical.
+"""
+import logging
+
+import numpy as np
+
+from rl_agents_amd import device_model, native
+from rl_agents_amd.agents.tree_search.abstract import AbstractPlanner, AbstractTreeSearchAgent, Node
+
+logger = logging.getLogger(__name__)
 
 
-class OLOP(object):
+class OLOP(AbstractPlanner):
+    """OLOP planner (olop.py:11-100) for one or many roots of one deterministic finite MDP."""
+
+    def __init__(self, env, config=None):
+        self.env = env
+        super(OLOP, self).__init__(config)
+
+    @classmethod
+    def default_config(cls):
+        cfg = super(OLOP, cls).default_config()
+        cfg["upper_bound"] = dict(type="hoeffding", time="global", threshold="4*np.log(time)")
+        cfg["continuation_type"] = "zeros"
+        return cfg
+
+    def reset(self):
+        """olop.py:36-40.  The reference builds its root here, so what that raises is raised here: a non-mapping
+        ``upper_bound`` (TypeError), ``gamma == 1`` (ValueError from the allocation, ZeroDivisionError with a given horizon)."""
+        super(OLOP, self).reset()
+        if self.config["step_strategy"] == "subtree":
+            # on a kept subtree the reference walks past the horizon and fails the assert of olop.py:190
+            raise NotImplementedError("step_strategy 'subtree' is not available for OLOP")
+        if "horizon" not in self.config:
+            self.allocate_budget()
+        bound = self.config["upper_bound"]
+        bound["type"]                                   # olop.py:107 reads it: TypeError for "upper_bound": "hoeffding"
+        self._value_upper_init = self.value_upper_init(self.config["gamma"], self.config["horizon"])
+
+    @staticmethod
+    def horizon(episodes, gamma):
+        """L(M) = max(1, ceil(log M / (2 log(1 / gamma)))) in numpy arithmetic (olop.py:42-44): gamma == 1 gives int(nan)."""
+        denominator = 2 * np.log(1 / gamma)
+        length = np.ceil(np.log(episodes) / denominator)
+        return max(int(length), 1)
+
+    def allocate_budget(self):
+        """olop.py:46-48: the budget is at least the number of actions."""
+        n_actions = self.env.action_space.n
+        budget = self.config["budget"] if self.config["budget"] > n_actions else n_actions
+        # the reference's first horizon(1, gamma) raises for gamma == 1 (int(nan): ValueError) and gamma == 0 (1 / 0:
+        # ZeroDivisionError); checked here, before the C loop sees a NaN horizon.  (Not in `allocation`: MCTS calls that,
+        # and its errors stay as they were.)
+        self.horizon(1, self.config["gamma"])
+        self.config["episodes"], self.config["horizon"] = self.allocation(budget, self.config["gamma"])
+
     @staticmethod
     def allocation(budget, gamma):
-        """Largest number of episodes e with e * horizon(e) <= budget, and that horizon."""
+        """Largest number of episodes e with e * horizon(e) <= budget, and that horizon (olop.py:50-62)."""
         return native.olop_allocation(budget, gamma)
+
+    @staticmethod
+    def value_upper_init(gamma, horizon):
+        """A new node's value_upper by depth 0..horizon (olop.py:113), in Python arithmetic."""
+        out = np.empty(int(horizon) + 1, np.float64)
+        for depth in range(int(horizon) + 1):
+            out[depth] = (1 - gamma ** (horizon + 1 - depth)) / (1 - gamma)
+        return out
+
+    def thresholds(self):
+        """The bound's threshold for every episode (olop.py:145-158): the config string evaluated with ``time`` = the
+        number of episodes ("global") or episode + 1 ("local")."""
+        bound = self.config["upper_bound"]
+        episodes = int(self.config["episodes"])
+        out = np.zeros(episodes, np.float64)
+        for episode in range(episodes):
+            time = {"global": self.config["episodes"], "local": episode + 1}.get(bound["time"], np.nan)
+            out[episode] = float(eval(bound["threshold"], {"np": np}, {"time": time}))
+        return out
+
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
+        """``root_steps`` is accepted for the common interface: the step limit ends no OLOP episode (done = terminated)."""
+        cfg = self.config
+        episodes, horizon = int(cfg["episodes"]), int(cfg["horizon"])        # KeyError without "episodes" (olop.py:95)
+        model = self.model_for(state)
+        self.about_to_plan()
+        n = len(root_states)
+        if rng_states is None:
+            rng_states = self.batch_rng_states(n)
+        kl = cfg["upper_bound"]["type"] == "kullback-leibler"
+        if kl:
+            if cfg["upper_bound"]["time"] not in ("global", "local"):
+                logger.error("Unknown upper-bound time reference")
+            thresholds = self.thresholds()
+        else:
+            logger.error("Unknown upper-bound type")
+            thresholds = np.zeros(0, np.float64)
+        # "uniform": a random new child; anything else: action 0 of the environment, in the device's labels
+        continuation = -1 if cfg["continuation_type"] == "uniform" else int(self.device_actions([0], model)[0])
+        out = self.models.ctx.olop_plan(model, root_states, episodes, horizon, cfg["gamma"], kl, continuation, thresholds,
+                                        self._value_upper_init, rng_states, max_plan_len=max(horizon, 1))
+        # the reference's observations and generator draws up to the failing step are taken before it raises: the step
+        # count is booked, and the records in `rng_states` are advanced, also on an error
+        self.env_steps += int(out["env_steps"].sum())
+        failed = np.flatnonzero(out["status"] != native.MP_OK)
+        if failed.size:
+            if out["status"][failed[0]] == native.ERR_OLOP_KEY:
+                raise KeyError(0)                                                           # olop.py:89
+            raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # olop.py:133-134
+        out["rng_states"] = rng_states
+        self.relabel(out, model)
+        self.last, self._root, self._last_model, self._last_actions = out, None, model, model.A
+        self.claim_device_tree()
+        return out
+
+    def plan(self, state, observation):
+        """AbstractPlanner.plan, with the planner's generator written back also when the plan raises (the reference's
+        generator has made the draws of the episodes run before the error)."""
+        s0, steps0 = device_model.env_root_state(state)
+        rng = native.rng_state_from_generator(self.np_random).reshape(1, 6)
+        try:
+            out = self.plan_batch(state, [s0], [steps0], rng_states=rng)
+        finally:
+            native.generator_set_state(self.np_random, rng[0])
+        n = int(out["plan_len"][0])
+        return [int(a) for a in out["plans"][0, :n]]
+
+    def export_tree(self, root=0):
+        self.require_device_tree()
+        cfg = self.config
+        cap = 1 + int(cfg["episodes"]) * int(cfg["horizon"]) * self._last_actions
+        arrays = self.relabel_tree(self.models.ctx.olop_tree(root, cap), self._last_model)
+        return build_olop_tree(arrays, self)
+
+    def get_visits(self):
+        """Observations stepped through (abstract.py:163-167).  On a deterministic model a node stands for one state and
+        was stepped into ``count`` times, so the counts come from the exported tree (the last plan, as for OPD)."""
+        from collections import defaultdict
+        visits = defaultdict(int)
+        if self.root is not None:
+            for node, _ in self.root.breadth_first_search(self.root):
+                if node.parent is not None and node.count > 0:
+                    visits[str(node.state)] += node.count
+        return visits
+
+
+class OLOPNode(Node):
+    """A node of an exported OLOP tree (olop.py:102-193): ``count``, ``cumulative_reward``, ``mu_ucb``, ``value_upper``,
+    ``done``, ``state``."""
+    STOP_ON_ANY_TERMINAL_STATE = False
+
+    def get_value(self):
+        return self.value_upper
+
+    def selection_rule(self):
+        """olop.py:126-130: the most visited children; among them the first whose value_upper nothing later exceeds."""
+        labels = list(self.children)
+        visits = [self.children[a].count for a in labels]
+        most = max(visits)
+        best = None
+        for a, c in zip(labels, visits):
+            if c == most and (best is None or self.children[a].value_upper > self.children[best].value_upper):
+                best = a
+        return best
+
+
+def build_olop_tree(arrays, planner=None):
+    """Creation-order arrays of mp_olop_tree_export -> linked :class:`OLOPNode` objects (children in creation order)."""
+    nodes = []
+    for i in range(len(arrays["parent"])):
+        par = nodes[arrays["parent"][i]] if arrays["parent"][i] >= 0 else None
+        node = OLOPNode(par, int(arrays["action"][i]), int(arrays["count"][i]), float(arrays["vu"][i]),
+                        int(arrays["depth"][i]), planner)
+        node.value_upper = float(arrays["vu"][i])
+        node.mu_ucb = float(arrays["mu"][i])
+        node.cumulative_reward = float(arrays["cum"][i])
+        node.done = bool(arrays["done"][i])
+        node.state = int(arrays["state"][i])
+        if par is not None:
+            par.children[node.action] = node
+        nodes.append(node)
+    return nodes[0]
+
+
+class OLOPAgent(AbstractTreeSearchAgent):
+    """Drop-in for ``rl_agents.agents.tree_search.olop.OLOPAgent``."""
+    PLANNER_TYPE = OLOP

@@ -50,7 +50,7 @@ struct DevBuf {
 
 // what the last tree-search call left on the device (for the *_tree_export entry points)
 struct TreeMeta {
-    int kind = 0; // 0 none, 1 uct, 2 opd, 3 robust opd
+    int kind = 0; // 0 none, 1 uct, 2 opd, 3 robust opd, 4 stochastic uct (mp_uct_plan_stochastic), 5 olop
     int n_roots = 0, A = 0, cap = 0, K = 0, M = 1;
     double gamma = 0.0; // robust opd: the export recomputes leaf upper-bound vectors
     int buf = 0;        // UCT: which of the two tree workspaces (WS_TREE0 / WS_TREE2) holds the current trees

@@ -1,0 +1,392 @@
+// olop.hip -- Open-Loop Optimistic Planning, OLOP / KL-OLOP (tree_search/olop.py, utils.py:89-203).
+//
+// Mapping: ONE ROOT PER WAVEFRONT (one 64-lane workgroup), the workgroups striding over the roots.  An OLOP plan is M episodes
+// of exactly L model steps down a tree of action sequences that grows only where it is walked (olop.py:64-92):
+//   * the walk is the serial chain: one model step per depth, every lane holding the same (wave-uniform) state;
+//   * the lanes cover a node's children -- their creation at an expansion (one 16-byte model gather each, listing order by a
+//     ballot prefix count), the selection argmax (Python max with `>`, olop.py:84) and the backup's np.amax (olop.py:188, NaN
+//     propagating) -- 64 at a time when |A| > 64;
+//   * the L bounds of an episode's path are independent (each node appears once on the path and only the backup reads them),
+//     so the lanes cover the L path nodes and run their Newton iterations (utils.py:123-203) at the same time, after the walk.
+// Nodes live in a global workspace, children contiguous in creation order (the reference's order of dict insertion): at most
+// 1 + M * L * |A| nodes per tree.  The workspace has one tree per root while the batch's trees fit kOlopKeepBytes (every tree
+// exportable), else one per workgroup (plus one for root 0, the tree an agent exports).  Everything that is not a basic IEEE
+// operation -- the initial upper bounds (Python **), the thresholds (eval of the config string, np.log) -- comes from host
+// tables.  The Newton step's log is the device's (parity of the bounds is 1e-12, not bit-exact).
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "common.hpp"
+#include "pcg64.hpp"
+
+namespace mp {
+
+constexpr size_t kOlopKeepBytes = (size_t)1 << 30; // trees of every root kept while they fit
+
+struct OlopNode {
+    double cum, mu;                  // cumulative_reward, mu_ucb (olop.py:102-108)
+    int32_t count, state, parent, first_child;
+    int32_t n_children, action, depth, done;
+};
+static_assert(sizeof(OlopNode) == 48, "OlopNode layout");
+
+struct OlopArgs {
+    int n_roots, A, M, L, cap, done_on_next, kl, cont, keep, grid, max_plan_len;
+    double gamma;
+    const Rec *rec;
+    const int32_t *root_state;
+    const double *thr;   // [M]     threshold of episode e
+    const double *vinit; // [L + 1] (1 - gamma ** (L + 1 - d)) / (1 - gamma)
+    uint64_t *rng;
+    OlopNode *nodes;     // [slots][cap]
+    double *vu;          // [slots][cap] value_upper
+    int32_t *n_nodes_out;
+    int32_t *plans, *plan_len, *status;
+    double *root_value;
+    int64_t *env_steps;
+};
+
+// utils.py:89-109 bernoulli_kullback_leibler
+__device__ __forceinline__ double bernoulli_kl(double p, double q)
+{
+    double kl1 = 0.0, kl2 = INFINITY;
+    if (p > 0 && q > 0) kl1 = p * log(p / q);
+    if (q < 1) kl2 = p < 1 ? (1 - p) * log((1 - p) / (1 - q)) : 0.0;
+    return kl1 + kl2;
+}
+
+// utils.py:123-146 kl_upper_bound with newton_iteration (:149-203): eps 1e-2, weight 0.9, 100 iterations, the in-loop clamps,
+// the final clamp.  `py` follows whether the iterate is still a Python float: only then does the derivative raise
+// ZeroDivisionError (and the finite difference of :183 replace it); numpy scalars give inf / nan instead.
+__device__ double kl_upper_bound(double total, int count, double threshold)
+{
+    if (count == 0) return 1.0;
+    const double mu = total / (double)count, max_div = threshold / (double)count;
+    const double a = mu, b = 1.0, eps = 1e-2, w = 0.9, wc = 1.0 - 0.9;
+    const double x0 = (a + b) / 2;
+    if (a == b) return a;
+    double x = INFINITY, xn = x0;
+    bool pyn = true;
+    for (int it = 0; fabs(x - xn) > eps && it < 100; ++it) {
+        x = xn;
+        const bool px = pyn;
+        const double fx = bernoulli_kl(mu, x) - max_div;
+        double dfx;
+        if (px && (1 - x == 0 || x == 0)) dfx = (fx - (bernoulli_kl(mu, x - eps) - max_div)) / eps;
+        else dfx = (1 - mu) / (1 - x) - mu / x;
+        if (dfx != 0) { xn = x - fx / dfx; pyn = false; }
+        if (xn < a) { xn = w * a + wc * x; pyn = px; }
+        else if (xn > b) { xn = w * b + wc * x; pyn = px; }
+    }
+    if (xn < a) xn = a;
+    if (xn > b) xn = b;
+    return xn;
+}
+
+__device__ __forceinline__ unsigned long long olop_ballot(bool p) { return __ballot(p); }
+
+// Python max over children [0, k) in order with `>` (olop.py:84, and the tie-break of selection_rule :126-130 when `in_set`
+// restricts it): the first element stays unless something is strictly greater, so a NaN first element wins and later NaNs
+// never do.  Returns the index (wave-uniform).
+__device__ int olop_first_max(const double *V, const OlopNode *C, int k, int lane, int count_eq)
+{
+    // first element of the set
+    int first = 0x7fffffff;
+    for (int i0 = 0; i0 < k && first == 0x7fffffff; i0 += 64) {
+        const int i = i0 + lane;
+        const bool in = i < k && (count_eq < 0 || C[i].count == count_eq);
+        const unsigned long long bal = olop_ballot(in);
+        if (bal) first = i0 + __ffsll((long long)bal) - 1;
+    }
+    if (isnan(V[first])) return first;
+    double bv = 0.0;
+    int bi = 0x7fffffff;
+    bool have = false;
+    for (int i = lane; i < k; i += 64) {
+        if (count_eq >= 0 && C[i].count != count_eq) continue;
+        const double v = V[i];
+        if (!isnan(v) && (!have || v > bv)) { bv = v; bi = i; have = true; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        const int oh = __shfl_xor((int)have, off);
+        if (oh && (!have || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; have = true; }
+    }
+    return bi;
+}
+
+// np.amax over children [0, k): NaN if any is NaN (olop.py:188)
+__device__ double olop_amax(const double *V, int k, int lane)
+{
+    double m = -INFINITY;
+    bool nan_seen = false;
+    for (int i = lane; i < k; i += 64) {
+        const double v = V[i];
+        if (isnan(v)) nan_seen = true;
+        else if (v > m) m = v;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(m, off);
+        m = o > m ? o : m;
+    }
+    return olop_ballot(nan_seen) ? (double)NAN : m;
+}
+
+__global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
+{
+    extern __shared__ int32_t path[]; // [L + 1] node ids of the episode's walk
+    const int lane = threadIdx.x, A = p.A, L = p.L;
+    const uint32_t done_bit = p.done_on_next ? 2u : 1u;
+    const double mu0 = p.kl ? 1.0 : (double)INFINITY; // olop.py:105-108
+    for (int root = blockIdx.x; root < p.n_roots; root += p.grid) {
+        const long slot = p.keep ? root : (root == 0 ? p.grid : blockIdx.x);
+        OlopNode *N = p.nodes + slot * p.cap;
+        double *V = p.vu + slot * p.cap;
+        if (lane == 0) {
+            OlopNode r;
+            r.cum = 0.0; r.mu = mu0; r.count = 0; r.state = p.root_state[root]; r.parent = -1; r.first_child = -1;
+            r.n_children = 0; r.action = -1; r.depth = 0; r.done = 0;
+            N[0] = r;
+            V[0] = p.vinit[0];
+        }
+        __syncthreads();
+        Pcg64 gen;
+        gen.load(p.rng + (long)root * 6);
+        int n_nodes = 1, status = MP_OK;
+        long steps = 0;
+        for (int e = 0; e < p.M && status == MP_OK; ++e) {
+            gen.below(1u << 30); // state.seed(self.np_random.randint(2**30)), olop.py:73
+            int node = 0;
+            if (lane == 0) path[0] = 0;
+            for (int h = 0; h < L; ++h) {
+                const OlopNode nd = N[node];
+                int fc = nd.first_child, k = nd.n_children, j, act;
+                if (k == 0) {
+                    // OLOPNode.expand (olop.py:165-180): the available actions in listing order
+                    const Rec *row = p.rec + (long)nd.state * A;
+                    int rank0 = -1, base = 0;
+                    fc = n_nodes;
+                    for (int a0 = 0; a0 < A; a0 += 64) {
+                        const int a = a0 + lane;
+                        Rec rc;
+                        bool av = false;
+                        if (a < A) { rc = row[a]; av = (rc.flags & 4u) != 0; }
+                        const unsigned long long bal = olop_ballot(av);
+                        const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+                        if (av) {
+                            OlopNode c;
+                            c.cum = 0.0; c.mu = mu0; c.count = 0; c.state = rc.next; c.parent = node; c.first_child = -1;
+                            c.n_children = 0; c.action = a; c.depth = nd.depth + 1; c.done = 0;
+                            N[fc + pos] = c;
+                            V[fc + pos] = p.vinit[nd.depth + 1];
+                        }
+                        if (p.cont >= a0 && p.cont < a0 + 64 && ((bal >> (p.cont - a0)) & 1ull))
+                            rank0 = base + __popcll(bal & ((1ull << (p.cont - a0)) - 1ull));
+                        base += __popcll(bal);
+                    }
+                    k = base;
+                    if (lane == 0) { N[node].first_child = fc; N[node].n_children = k; }
+                    n_nodes += k;
+                    __syncthreads();
+                    if (p.cont < 0) { // np_random.choice(list(children))
+                        j = (int)gen.below((uint32_t)k);
+                        act = N[fc + j].action;
+                    } else { // action 0 (in the env's numbering): KeyError when it is not a child
+                        j = rank0;
+                        act = p.cont;
+                    }
+                } else {
+                    j = olop_first_max(V + fc, N + fc, k, lane, -1);
+                    act = N[fc + j].action;
+                }
+                // the model step (every step is taken: the reference does not stop at done)
+                const Rec rc = p.rec[(long)nd.state * A + act];
+                ++steps;
+                if (j < 0) { status = MP_ERR_OLOP_KEY; break; }
+                const double r = rc.reward;
+                if (!(0.0 <= r && r <= 1.0)) { status = MP_ERR_REWARD_RANGE; break; } // olop.py:133-134
+                const int child = fc + j;
+                if (lane == 0) { // OLOPNode.update (olop.py:132-142)
+                    OlopNode c = N[child];
+                    if (rc.flags & done_bit) c.done = 1;
+                    c.cum += c.done ? 0.0 : r;
+                    c.count += 1;
+                    N[child] = c;
+                    path[h + 1] = child;
+                }
+                node = child;
+                __syncthreads();
+            }
+            if (status != MP_OK) break;
+            // compute_reward_ucb (olop.py:144-163) of the path nodes, one lane each; other bound types keep mu_ucb = inf
+            if (p.kl) {
+                const double thr = p.thr[e];
+                for (int i = 1 + lane; i <= L; i += 64) {
+                    OlopNode *c = N + path[i];
+                    c->mu = kl_upper_bound(c->cum, c->count, thr);
+                }
+            }
+            __syncthreads();
+            // backup_to_root (olop.py:182-193), from the depth-L node up
+            for (int h = L; h >= 0; --h) {
+                const OlopNode nd = N[path[h]];
+                double v;
+                if (nd.n_children > 0) v = nd.mu + p.gamma * olop_amax(V + nd.first_child, nd.n_children, lane);
+                else v = nd.mu;
+                if (lane == 0) V[path[h]] = v;
+                __syncthreads();
+            }
+        }
+        // get_plan (abstract.py:143-156) with OLOPNode.selection_rule (olop.py:126-130)
+        int len = 0;
+        if (status == MP_OK) {
+            int node = 0;
+            for (;;) {
+                const OlopNode nd = N[node];
+                if (nd.n_children == 0) break;
+                int cmax = -1;
+                for (int i = lane; i < nd.n_children; i += 64) cmax = max(cmax, N[nd.first_child + i].count);
+                for (int off = 32; off > 0; off >>= 1) cmax = max(cmax, __shfl_xor(cmax, off));
+                const int j = olop_first_max(V + nd.first_child, N + nd.first_child, nd.n_children, lane, cmax);
+                node = nd.first_child + j;
+                if (lane == 0 && p.plans && len < p.max_plan_len) p.plans[(long)root * p.max_plan_len + len] = N[node].action;
+                ++len;
+            }
+        }
+        if (lane == 0) {
+            gen.store(p.rng + (long)root * 6);
+            if (p.plans)
+                for (int i = len; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
+            if (p.plan_len) p.plan_len[root] = len;
+            if (p.status) p.status[root] = status;
+            if (p.env_steps) p.env_steps[root] = steps;
+            if (p.root_value) p.root_value[root] = V[0];
+            p.n_nodes_out[root] = n_nodes;
+        }
+        __syncthreads();
+    }
+}
+
+} // namespace mp
+
+using namespace mp;
+
+extern "C" {
+
+int mp_olop_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
+                 double gamma, int32_t bound_type, int32_t continuation, const double *thresholds,
+                 const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len,
+                 double *root_value, int64_t *env_steps, int32_t *status, int32_t mem)
+{
+    if (!ctx || !model || !root_state || !rng_state || !value_upper_init) return fail(MP_ERR_ARG, "mp_olop_plan: NULL argument");
+    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_olop_plan: unknown mem flags %d", mem);
+    const int rmem = mem_rng(mem);
+    mem = mem_arrays(mem);
+    if (model->mode != MP_MODE_DETERMINISTIC)
+        return fail(MP_ERR_MODE, "mp_olop_plan: model mode %d is not a deterministic table", model->mode);
+    const int A = model->A;
+    if (n_roots < 1 || episodes < 0 || horizon < 0 || horizon > 16384 || max_plan_len < 0)
+        return fail(MP_ERR_ARG, "mp_olop_plan: bad sizes");
+    if (bound_type == 1 && episodes > 0 && !thresholds) return fail(MP_ERR_ARG, "mp_olop_plan: thresholds are NULL");
+    if (continuation >= A) return fail(MP_ERR_ARG, "mp_olop_plan: continuation action %d out of range", continuation);
+    if (mem == MP_MEM_HOST && !pinned_alias(ctx, root_state, (size_t)n_roots * sizeof(int32_t)))
+        for (int i = 0; i < n_roots; ++i)
+            if (root_state[i] < 0 || root_state[i] >= model->S) return fail(MP_ERR_ARG, "mp_olop_plan: root state %d out of range", root_state[i]);
+    const long cap = 1 + (long)episodes * horizon * A;
+    if (cap > (1L << 30)) return fail(MP_ERR_ARG, "mp_olop_plan: %ld nodes per tree", cap);
+    MP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+
+    // one table: thresholds [M] then value_upper_init [L + 1] (host pointers; the values the reference's Python computes)
+    std::vector<double> tab((size_t)episodes + horizon + 1);
+    for (int e = 0; e < episodes; ++e) tab[e] = bound_type == 1 ? thresholds[e] : 0.0;
+    for (int d = 0; d <= horizon; ++d) tab[(size_t)episodes + d] = value_upper_init[d];
+    double *d_tab = nullptr;
+    MP_TRY(upload_tables(ctx, 40, tab, &d_tab));
+
+    OlopArgs a;
+    const long waves = (long)ctx->prop.multiProcessorCount * 32;
+    a.grid = (int)(n_roots < waves ? n_roots : waves);
+    const size_t per_tree = (size_t)cap * (sizeof(OlopNode) + sizeof(double));
+    a.keep = (size_t)n_roots * per_tree <= kOlopKeepBytes;
+    const size_t slots = a.keep ? (size_t)n_roots : (size_t)a.grid + 1;
+    a.n_roots = n_roots; a.A = A; a.M = episodes; a.L = horizon; a.cap = (int)cap; a.done_on_next = model->done_on_next;
+    a.kl = bound_type == 1; a.cont = continuation; a.max_plan_len = max_plan_len; a.gamma = gamma;
+    a.rec = model->rec;
+    a.thr = d_tab; a.vinit = d_tab + episodes;
+    MP_TRY(ws_get(ctx, WS_TREE0, slots * cap * (sizeof(OlopNode) / sizeof(double)), reinterpret_cast<double **>(&a.nodes)));
+    MP_TRY(ws_get(ctx, WS_TREE1, slots * cap, &a.vu));
+    MP_TRY(ws_get(ctx, WS_TREE7, (size_t)n_roots, &a.n_nodes_out));
+    ctx->tree.kind = 5; ctx->tree.armed = false; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap;
+    ctx->tree.K = a.keep ? -1 : a.grid; // which slot holds a root's tree: its own (-1), else root 0 only, in slot `grid`
+
+    int32_t *d_rs = nullptr;
+    MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n_roots, mem, &d_rs));
+    a.root_state = d_rs;
+    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n_roots * 6, rmem, &a.rng));
+    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n_roots * max_plan_len, mem, &a.plans));
+    MP_TRY(stage_out_alloc(ctx, WS_IO4, plan_len, (size_t)n_roots, mem, &a.plan_len));
+    MP_TRY(stage_out_alloc(ctx, WS_IO5, root_value, (size_t)n_roots, mem, &a.root_value));
+    MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
+    MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, mem, &a.env_steps));
+
+    snprintf(ctx->last_variant, sizeof(ctx->last_variant), "%s", a.keep ? "olop_global" : "olop_global_slots");
+    MP_TRY(kernels_begin(ctx));
+    hipLaunchKernelGGL(olop_kernel, dim3((unsigned)a.grid), dim3(64), (size_t)(horizon + 1) * sizeof(int32_t), st, a);
+    MP_TRY(kernels_end(ctx, 1));
+    MP_HIP(hipGetLastError());
+
+    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n_roots * 6, rmem));
+    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n_roots * max_plan_len, mem));
+    MP_TRY(stage_out_copy(ctx, plan_len, a.plan_len, (size_t)n_roots, mem));
+    MP_TRY(stage_out_copy(ctx, root_value, a.root_value, (size_t)n_roots, mem));
+    MP_TRY(stage_out_copy(ctx, status, a.status, (size_t)n_roots, mem));
+    MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n_roots, mem));
+    if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
+    return MP_OK;
+}
+
+int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *action,
+                        int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *value_upper,
+                        uint8_t *done, int32_t *state)
+{
+    if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
+    if (ctx->tree.kind != 5) return fail(MP_ERR_ARG, "mp_olop_tree_export: no tree of mp_olop_plan on this ctx");
+    if (root < 0 || root >= ctx->tree.n_roots) return fail(MP_ERR_ARG, "mp_olop_tree_export: root %d out of range", root);
+    const bool keep = ctx->tree.K < 0;
+    if (!keep && root != 0)
+        return fail(MP_ERR_ARG, "mp_olop_tree_export: the batch's trees did not all fit the workspace; only root 0's was kept");
+    const long slot = keep ? root : ctx->tree.K;
+    const long tcap = ctx->tree.cap;
+    MP_HIP(hipSetDevice(ctx->device));
+    MP_HIP(hipStreamSynchronize(ctx->stream));
+    int32_t n = 0;
+    MP_HIP(hipMemcpy(&n, (const int32_t *)ctx->ws[WS_TREE7].p + root, sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (n < 1 || n > tcap) return fail(MP_ERR_ARG, "mp_olop_tree_export: bad node count %d", n);
+    if (n > cap) return fail(MP_ERR_ARG, "mp_olop_tree_export: capacity %d < %d nodes", cap, n);
+    std::vector<OlopNode> na((size_t)n);
+    std::vector<double> vu((size_t)n);
+    MP_HIP(hipMemcpy(na.data(), (const OlopNode *)ctx->ws[WS_TREE0].p + slot * tcap, (size_t)n * sizeof(OlopNode),
+                     hipMemcpyDeviceToHost));
+    MP_HIP(hipMemcpy(vu.data(), (const double *)ctx->ws[WS_TREE1].p + slot * tcap, (size_t)n * sizeof(double),
+                     hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+        if (parent) parent[i] = na[i].parent;
+        if (action) action[i] = na[i].action;
+        if (depth) depth[i] = na[i].depth;
+        if (count) count[i] = na[i].count;
+        if (cumulative_reward) cumulative_reward[i] = na[i].cum;
+        if (mu_ucb) mu_ucb[i] = na[i].mu;
+        if (value_upper) value_upper[i] = vu[i];
+        if (done) done[i] = (uint8_t)na[i].done;
+        if (state) state[i] = na[i].state;
+    }
+    if (n_nodes) *n_nodes = n;
+    return MP_OK;
+}
+
+} // extern "C"

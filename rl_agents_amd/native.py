@@ -16,6 +16,7 @@ MP_MEM_HOST, MP_MEM_DEVICE, MP_MEM_RNG_DEVICE = 0, 1, 2
 MP_OK, MP_ERR_HIP, MP_ERR_REWARD_RANGE, MP_ERR_ALLOC, MP_ERR_ARG, MP_ERR_MODE = 0, -1, -2, -3, -4, -5
 MODE_DETERMINISTIC, MODE_STOCHASTIC, MODE_SPARSE, MODE_CARTPOLE = 0, 1, 2, 3
 ERR_REWARD_RANGE, ERR_ARG, ERR_MODE = -2, -4, -5
+ERR_OLOP_KEY = -6          # mp_olop_plan status: the "zeros" continuation's action is not a child (olop.py:89 KeyError)
 
 _LIB = None
 
@@ -102,6 +103,9 @@ SIGNATURES = {
     "mp_saopd_info": (C.c_int, [_vp, P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
     "mp_saopd_export": (C.c_int, [_vp, c_i32, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_olop_allocation": (C.c_int, [c_i32, c_f64, P(c_i32), P(c_i32)]),
+    "mp_olop_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp, _vp,
+                               _vp, _vp, c_i32]),
+    "mp_olop_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_last_kernel_ms": (C.c_int, [_vp, P(c_f64), P(c_i32)]),
     "mp_last_kernel_variant": (C.c_char_p, [_vp]),
     "mp_selftest_lds_atomic_order": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
@@ -1013,6 +1017,40 @@ class Context(object):
                                              _ptr(t["action"]), _ptr(t["state"]), _ptr(t["depth"]), _ptr(t["reward"]),
                                              _ptr(t["lower"]), _ptr(t["upper"]), _ptr(t["done"]), _ptr(t["count"]),
                                              _ptr(t["first_child"]), _ptr(t["n_children"])))
+        return {k: v[:n.value].copy() for k, v in t.items()}
+
+    def olop_plan(self, model, root_state, episodes, horizon, gamma, kl, continuation, thresholds, value_upper_init, rng_state,
+                  max_plan_len=None):
+        """OLOP.plan for a batch of roots (host arrays): mp_olop_plan.  ``kl``: the kullback-leibler bound (else mu_ucb stays
+        inf); ``continuation``: < 0 = uniform, else the action label taken after an expansion; ``thresholds`` float64
+        [episodes], ``value_upper_init`` float64 [horizon + 1] from the host."""
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        n = rs.shape[0]
+        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
+                and rng_state.size == n * 6):
+            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
+        mpl = max(int(horizon), 1) if max_plan_len is None else int(max_plan_len)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        vin = np.ascontiguousarray(value_upper_init, dtype=np.float64).reshape(-1)
+        if vin.size != int(horizon) + 1 or (kl and thr.size < int(episodes)):
+            raise ValueError("olop_plan: thresholds [episodes] and value_upper_init [horizon + 1] expected")
+        out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32), root_value=np.zeros(n, np.float64),
+                   env_steps=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
+        _check(self._lib.mp_olop_plan(self._h, model._h, n, _ptr(rs), int(episodes), int(horizon), float(gamma), 1 if kl else 0,
+                                      int(continuation), _ptr(thr) if thr.size else None, _ptr(vin), _ptr(rng_state), mpl,
+                                      _ptr(out["plans"]), _ptr(out["plan_len"]), _ptr(out["root_value"]), _ptr(out["env_steps"]),
+                                      _ptr(out["status"]), MP_MEM_HOST))
+        return out
+
+    def olop_tree(self, root, cap):
+        """Creation-order arrays of root ``root``'s tree after the last olop_plan (mp_olop_tree_export)."""
+        t = dict(parent=np.zeros(cap, np.int32), action=np.zeros(cap, np.int32), depth=np.zeros(cap, np.int32),
+                 count=np.zeros(cap, np.int64), cum=np.zeros(cap, np.float64), mu=np.zeros(cap, np.float64),
+                 vu=np.zeros(cap, np.float64), done=np.zeros(cap, np.uint8), state=np.zeros(cap, np.int32))
+        n = c_i32()
+        _check(self._lib.mp_olop_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]), _ptr(t["action"]),
+                                             _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["cum"]), _ptr(t["mu"]), _ptr(t["vu"]),
+                                             _ptr(t["done"]), _ptr(t["state"])))
         return {k: v[:n.value].copy() for k, v in t.items()}
 
     def opd_tree(self, root, cap):
