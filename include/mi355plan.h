@@ -662,11 +662,20 @@ int mp_comm_destroy(mp_ctx *ctx);
 /* ---------------------------------------------------------------- helpers ------------------- */
 /* OLOP.allocation (tree_search/olop.py:50-62) with OLOP.horizon (:42-44); host arithmetic. */
 int mp_olop_allocation(int32_t budget, double gamma, int32_t *episodes, int32_t *horizon);
+/* The kernel form mp_uct_plan* chooses for a call of this description, on the host alone (no device, no ctx: tests pin the choice
+ * without a GPU).  The MP_UCT_* knobs are read from the environment as the plan reads them.
+ *   call[14]: n_roots, episodes, horizon, |A|, the model's S, NB and Sb (batch models: MDPs, states per MDP), compact transitions
+ *             (0 / 1), compact reward index (0 / 1), distinct rewards, CartPole (0 / 1), policy (0 none, 1 per-state, 2 listed),
+ *             the layout of the kept tree the plan continues (-1: fresh trees), compute units.
+ *   out[7]:   tree layout, lanes, waves, rep_shift (the kernel arguments), roots and threads per workgroup, dynamic LDS bytes.
+ *   *name:    the form, as mp_last_kernel_variant names it.
+ * A call the plan refuses for its shape gets the plan's MP_ERR_ARG. */
+int mp_uct_choose_form(const int64_t *call, int64_t *out, const char **name);
 /* Timing of the last kernel batch enqueued by a plan / solve call, from HIP events recorded on
  * the ctx stream around the kernel launches only (no copies).  Synchronises the stream. */
 int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
 /* Name of the kernel variant the last mp_uct_plan* / mp_vi_solve_batch call launched -- "uct_global", "uct_ldsr" (model resident
- * in LDS), "uct_lds", "uct_quad" (four lanes per root), "uct_lone" (one root per workgroup), "uct_lone_mw" (2 / 4 / 8 roots per workgroup, a
+ * in LDS), "uct_quad" (four lanes per root), "uct_lone" (one root per workgroup), "uct_lone_mw" (2 / 4 / 8 roots per workgroup, a
  * wavefront each, around one copy of the transitions), "uct_row_shared" / "uct_row_each" /
  * "uct_lone_each" (four roots per wavefront on DPP rows, trees in LDS: a shared model / one MDP per root; a wavefront per root),
  * "uct_policy", "uct_cartpole", "uct_global_spill"; "vi_batch_reg<own,block>", "vi_batch_cluster2|4|8" (K workgroups per MDP),

@@ -7,12 +7,10 @@
 // long as its slowest lane's dependency chain, so the kernel is built to shorten that chain:
 //
 //   model   default: one 16-byte record {next, flags, reward} per (s,a), a single dwordx4 gather per
-//           env step (any S).  MP_UCT_MODEL=lds (S < 32768 and S*A*2 B fits): the transition table is
-//           staged once per workgroup into LDS as uint16 {bit15 = terminal[next], next state} and the
-//           step's reward is fetched off the chain, added one step later in the reference's order.
-//           Measured slower (0.376 vs 0.338 ms at 4096 roots): the chain is instruction-bound.
+//           env step (any S).
 //           ENV_TABLE_LDSR (round 4, the default wherever the model fits): the WHOLE model lives in LDS -- uint16
-//           transitions, a uint8 index per (s,a) into the table of the model's distinct rewards (<= 256 of them) and that
+//           transitions {bit15 = terminal[next], next state}, a uint8 index per (s,a) into the table of the model's
+//           distinct rewards (<= 256 of them) and that
 //           table -- 3 B per (s,a): the headline's S*A = 50 000 takes 150 of the CU's 160 KB.  An env step then makes
 //           no global-memory request at all; the path stack moves from LDS to registers (depths 1..5) with a global
 //           spill beyond.  One workgroup of up to 16 waves per CU shares the tables.
@@ -31,10 +29,12 @@
 //           saturated kernel is bound by L2/HBM requests, and these remove a third of them.
 //   path    per-lane stack of visited node ids in LDS ([depth][lane], conflict-free): the backup
 //           walks known addresses, not parent pointers.
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <new>
 #include <vector>
 
@@ -57,9 +57,7 @@ static_assert(sizeof(UctNode) == 16, "UctNode must be one dwordx4");
 // One root's tree inside the batch buffer.  LAY selects the layout (A/B: profiles/r02_uct_tree_layout.md):
 //   0 root-major       Node[n_roots][cap]: a root's nodes contiguous -- the |A| children of a node share one or two
 //                      cache lines, but neighbouring lanes are a whole tree apart: nothing a wave does coalesces.
-//   1 interleaved      Node[n_roots / 64][cap][64]: the same node id of a wavefront's 64 roots contiguous -- accesses
-//                      that hit the same id in every lane (expansions: ids advance in lock-step) fill whole lines, but a
-//                      node's |A| children now lie in |A| different lines.
+//                      Generic |A| and CartPole.
 //   2 group-interleaved Node[n_roots / 64][groups][64][|A|]: node ids come in groups of |A| siblings (1 + g|A| .. ;
 //                      the root fills the last slot of group 0); a lane's sibling group stays contiguous (one or two
 //                      lines per scored level, as root-major) AND the same group of the 64 lanes is contiguous
@@ -69,18 +67,17 @@ template <int LAY, int AT>
 struct TreeRef {
     UctNode *base;
     int A; // runtime |A| (generic ids only)
-    __device__ __forceinline__ static unsigned idx01(int n) { return LAY == 1 ? (unsigned)n << 6 : (unsigned)n; }
     // node fc + a where fc is the first child of some node (fc = 1 mod |A|)
     __device__ __forceinline__ int handle(int fc, int a) const { return LAY == 2 ? ((fc - 1 + AT) << 6) + a : fc + a; }
     __device__ __forceinline__ int root_handle() const { return LAY == 2 ? AT - 1 : 0; }
-    __device__ __forceinline__ UctNode &at(int h) const { return base[LAY == 2 ? (unsigned)h : idx01(h)]; }
+    __device__ __forceinline__ UctNode &at(int h) const { return base[(unsigned)h]; }
     __device__ __forceinline__ UctNode &child(int fc, int a) const { return at(handle(fc, a)); }
     // sibling a of a group whose first node is *first (= &child(fc, 0)): one address computation per group, the siblings
     // at constant offsets (the compiler cannot derive that from 32-bit handles: it re-materialises a 64-bit address each)
-    __device__ __forceinline__ static UctNode &sibling(UctNode *first, int a) { return first[LAY == 1 ? a << 6 : a]; }
+    __device__ __forceinline__ static UctNode &sibling(UctNode *first, int a) { return first[a]; }
     __device__ __forceinline__ UctNode &operator[](int n) const
     {
-        if (LAY != 2) return base[idx01(n)];
+        if (LAY != 2) return base[(unsigned)n];
         const int x = n + A - 1, q = x / A;          // group q (root: group 0, last slot), slot x - q|A|
         return base[(unsigned)(q * A * 64 + (x - q * A))];
     }
@@ -91,7 +88,6 @@ __device__ __forceinline__ TreeRef<LAY, AT> tree_of(UctNode *trees, int r, int c
     TreeRef<LAY, AT> t;
     t.A = A;
     if (LAY == 2) t.base = trees + ((long)(r >> 6) * (cap + A) * 64 + (long)(r & 63) * A);
-    else if (LAY == 1) t.base = trees + ((long)(r >> 6) * cap * 64 + (r & 63));
     else t.base = trees + (long)r * cap;
     return t;
 }
@@ -101,7 +97,7 @@ static inline size_t tree_stride_alloc(int lay, long cap, int A) { return (size_
 struct UctArgs {
     int n_roots, S, A, episodes, horizon, cap;
     int table_n; // counts with entries in the quotient tables of `tab` (TE below): min(episodes, what 16 KB of LDS hold)
-    int tree_il; // tree layout (TreeRef): 0 root-major, 1 interleaved, 2 group-interleaved
+    int tree_il; // tree layout (TreeRef): 0 root-major, 2 group-interleaved
     int done_on_next, max_steps, max_plan_len;
     int lanes; // roots per wavefront (64 = dense; fewer spreads a small batch over more SIMDs)
     int rep_shift; // CartPole: a root is replicated over 2^rep_shift lanes (see the launch code: wavefronts of few ACTIVE lanes run slow)
@@ -196,7 +192,7 @@ __device__ __forceinline__ bool cartpole_step(const mp_cartpole_params &c, doubl
     return x < -c.x_threshold || x > c.x_threshold || theta < -c.theta_threshold || theta > c.theta_threshold;
 }
 
-enum { ENV_TABLE = 0, ENV_TABLE_LDS = 1, ENV_CARTPOLE = 2, ENV_TABLE_LDSR = 3, ENV_TABLE_SPILL = 4 };
+enum { ENV_TABLE = 0, ENV_CARTPOLE = 2, ENV_TABLE_LDSR = 3, ENV_TABLE_SPILL = 4 };
 // ENV_TABLE_SPILL: ENV_TABLE with the path stack in registers + a global spill array instead of LDS -- for horizons whose
 // [H + 1][64] stack would not fit (the reference has no horizon limit: tree_search/mcts.py:116-118)
 
@@ -229,8 +225,8 @@ enum { ENV_TABLE = 0, ENV_TABLE_LDS = 1, ENV_CARTPOLE = 2, ENV_TABLE_LDSR = 3, E
 template <int AT, int ENV, bool SP = false, bool MK = false, int IL = 0, bool QD = false>
 // Per-state-policy kernels with |A| <= 5 are held to the registers of 4 waves per SIMD (they would take 134-140 VGPRs = 3
 // waves; TA 52 %, VALU 45 %, L1 28 % busy: latency-bound -- 2.14 -> 1.91 ms at 262 144 roots with the fourth wave).
-__global__ __launch_bounds__((ENV == ENV_TABLE_LDS || ENV == ENV_TABLE_LDSR) ? 1024 : (ENV == ENV_CARTPOLE ? 256 : 64),
-                             (ENV == ENV_TABLE_LDS || ENV == ENV_TABLE_LDSR) ? 1 : (SP && AT > 0 && AT <= 5 && MP_UCT_MIN_WAVES < 4 ? 4 : MP_UCT_MIN_WAVES))
+__global__ __launch_bounds__(ENV == ENV_TABLE_LDSR ? 1024 : (ENV == ENV_CARTPOLE ? 256 : 64),
+                             ENV == ENV_TABLE_LDSR ? 1 : (SP && AT > 0 && AT <= 5 && MP_UCT_MIN_WAVES < 4 ? 4 : MP_UCT_MIN_WAVES))
 void uct_kernel(UctArgs p)
 {
     static_assert(!SP || (AT > 0 && ENV == ENV_TABLE), "per-state policies: table env, |A| known at compile time");
@@ -238,8 +234,8 @@ void uct_kernel(UctArgs p)
     constexpr int NTH = AT > 1 ? AT - 1 : 1; // thresholds that can be reached (the last one is 2^53: never)
     constexpr int NQ = (NTH + 1) / 2;        // 16-byte chunks of a row of exact (uint64) thresholds
     constexpr int NQ32 = (NTH + 3) / 4;      // 16-byte chunks of the fused record's 32-bit thresholds
-    constexpr bool LDSR = ENV == ENV_TABLE_LDSR;             // transitions AND rewards in LDS, path stack in registers
-    constexpr bool LDSM = ENV == ENV_TABLE_LDS || LDSR;      // transitions in LDS (reward one step behind the state chain)
+    constexpr bool LDSR = ENV == ENV_TABLE_LDSR;             // transitions AND rewards in LDS (the reward one step behind the
+                                                             // state chain), path stack in registers
     static_assert(!LDSR || (AT > 0 && !SP), "the LDS-resident variant: |A| at compile time, state-independent policies");
     static_assert(!QD || LDSR, "four lanes per root: the LDS-resident model");
     constexpr bool PREG = LDSR || ENV == ENV_TABLE_SPILL;    // path stack in registers + global spill, not in LDS
@@ -268,8 +264,7 @@ void uct_kernel(UctArgs p)
     int32_t *path_all = reinterpret_cast<int32_t *>(lds_d + ntab); // [H + 1][waves * 64]  (not in the LDS-resident variant)
     const int ntab2 = (ntab + 1) & ~1;                             // (16-byte alignment of what follows)
     const double *rdict = lds_d + ntab2;                           // LDSR: [n_rdict] distinct rewards
-    uint16_t *t16 = LDSR ? reinterpret_cast<uint16_t *>(lds_d + ntab2 + ((p.n_rdict + 1) & ~1))
-                         : reinterpret_cast<uint16_t *>(path_all + (H + 1) * nthreads);
+    uint16_t *t16 = reinterpret_cast<uint16_t *>(lds_d + ntab2 + ((p.n_rdict + 1) & ~1)); // LDSR: [S*A] transitions
     uint8_t *r8 = reinterpret_cast<uint8_t *>(t16 + ((p.S * A + 7) & ~7)); // LDSR: [S*A]
     uint32_t *jump = reinterpret_cast<uint32_t *>(r8 + ((p.S * A + 15) & ~15)); // QD: [H + 5][8]
     if (QD)
@@ -291,7 +286,7 @@ void uct_kernel(UctArgs p)
         uint4 *dst = reinterpret_cast<uint4 *>(r8);
         for (int i = tid; i < n16; i += nthreads) dst[i] = src[i];
     }
-    if (LDSM) {
+    if (LDSR) {
         // S*A uint16 entries, staged with 16-byte loads where the tail allows
         const int n = p.S * A;
         const int n8 = n >> 3;
@@ -507,9 +502,9 @@ void uct_kernel(UctArgs p)
             if (CART) {
                 terminal = cartpole_step(p.cp, x4, act, p.cp_sincos, sctab);
                 reward = 1.0;
-            } else if (LDSM) {
+            } else if (LDSR) {
                 const uint32_t e = t16[idx];
-                reward = LDSR ? rdict[r8[idx]] : rec[idx].reward;
+                reward = rdict[r8[idx]];
                 const bool next_term = (e & 0x8000u) != 0;
                 terminal = p.done_on_next ? next_term : cur_term;
                 cur_term = next_term;
@@ -1037,10 +1032,10 @@ void uct_kernel(UctArgs p)
                     unext = gspec.next64() >> USH;
                     term_h = cartpole_step(p.cp, x4, act, p.cp_sincos, sctab);
                     total += g_mine * 1.0;
-                } else if (LDSM) {
+                } else if (LDSR) {
                     const unsigned idx = ridx;
                     const uint32_t e = t16[idx];
-                    r_mine = LDSR ? rdict[r8[idx]] : rec[idx].reward;
+                    r_mine = rdict[r8[idx]];
                     gspec = gcur;
                     unext = gspec.next64() >> USH;
                     // (the first step of a rollout has no previous reward: r_prev = g_prev = 0.0 then, and adding +0.0 changes no bit
@@ -1105,7 +1100,7 @@ void uct_kernel(UctArgs p)
                 if (step(r_b, g_b, r_a, g_a, true, gb, ga, un)) { stopped_in_a = false; break; }
                 u = un;
             }
-            if (LDSM) total += stopped_in_a ? g_a * r_a : g_b * r_b;
+            if (LDSR) total += stopped_in_a ? g_a * r_a : g_b * r_b;
             g = stopped_in_a ? ga : gb; // the generator whose draw was consumed last
             st += h - depth; steps_taken += h - depth;
         }
@@ -2070,82 +2065,6 @@ __global__ __launch_bounds__(64) void uct_reroot_kernel(int n_roots, int A, int 
     n_new[r] = tail;
 }
 
-// Roots per wavefront for the global-table variant.  A root's episodes are one long dependency
-// chain, so a batch takes as long as its slowest wavefront; measured on MI355X (4096 roots,
-// highway table) dense waves are fastest: 64 lanes 0.41 ms, 16 lanes 0.44 ms, 4 lanes 0.70 ms.
-static int uct_lanes_per_wave()
-{
-    if (const char *e = getenv("MP_UCT_LANES")) {
-        const int v = atoi(e);
-        if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) return v;
-    }
-    return 64;
-}
-
-// whether the LDS-resident model is used when nothing is forced (MP_UCT_MODEL unset)
-// Measured on MI355X (headline table, 33 x 30; profiles/r04_uct_ldsr.md): kernel ms global / LDS-resident at 8 192 roots
-// 0.342 / 0.357, 32 768 0.376 / 0.383, 65 536 0.412 / 0.369, 131 072 0.564 / 0.473, 262 144 1.049 / 0.781, 524 288
-// 2.050 / 1.545 -- staging 150 KB per workgroup costs ~25 us and a lone wave per SIMD hides the gather anyway, so the
-// variant is the default from one wave per SIMD (four per CU) upwards.
-static bool uct_ldsr_default(bool forced, long n_roots, int cus)
-{
-    if (forced) return true;
-    return (n_roots + 63) / 64 >= 4L * (cus > 0 ? cus : 256);
-}
-
-template <int AT>
-static int uct_launch(const UctArgs &a, bool ldsm, size_t lds, hipStream_t st, bool sp, bool listed, bool ldsr = false, bool spill = false,
-                      bool quad = false)
-{
-    const int roots_per_block = a.waves * a.lanes;
-    const dim3 grid((unsigned)((a.n_roots + roots_per_block - 1) / roots_per_block)), block((unsigned)a.waves * 64);
-    if (spill) {
-        if (a.tree_il == 2) {
-            if constexpr (AT > 0) hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE_SPILL, false, false, 2>), grid, block, lds, st, a);
-        } else {
-            hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE_SPILL, false, false, 0>), grid, block, lds, st, a);
-        }
-    } else if (ldsr && quad) {
-        if constexpr (AT > 0) {
-            if (lds > 64 * 1024)
-                MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, true>), grid, block, lds, st, a);
-        }
-    } else if (ldsr) {
-        if constexpr (AT > 0) {
-            if (lds > 64 * 1024)
-                MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2>), grid, block, lds, st, a);
-        }
-    } else if (sp && listed) {
-        if constexpr (AT > 0) {
-            if (a.tree_il == 2) hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE, true, true, 2>), grid, block, lds, st, a);
-            else if (a.tree_il == 1) hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE, true, true, 1>), grid, block, lds, st, a);
-            else hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE, true, true, 0>), grid, block, lds, st, a);
-        }
-    } else if (sp) {
-        if constexpr (AT > 0) {
-            if (a.tree_il == 2) hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE, true, false, 2>), grid, block, lds, st, a);
-            else if (a.tree_il == 1) hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE, true, false, 1>), grid, block, lds, st, a);
-            else hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE, true, false, 0>), grid, block, lds, st, a);
-        }
-    } else if (ldsm) {
-        if (lds > 64 * 1024)
-            MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_kernel<AT, ENV_TABLE_LDS>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE_LDS>), grid, block, lds, st, a);
-    } else if (a.tree_il == 2) {
-        if constexpr (AT > 0) hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE, false, false, 2>), grid, block, lds, st, a);
-    } else if (a.tree_il == 1) {
-        hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE, false, false, 1>), grid, block, lds, st, a);
-    } else {
-        hipLaunchKernelGGL((uct_kernel<AT, ENV_TABLE>), grid, block, lds, st, a);
-    }
-    return MP_OK;
-}
-
 // ---- per-state policies fused ON THE DEVICE (round 6).  mp_policy_load's host loops (download the model's records, S * |A|
 // thresholds and fused records in C++, six hipMalloc'ed arrays uploaded) cost 90 ms per call on the batch model of 4096
 // highway episodes (491 520 global states) -- per step of the per-episode evaluation loop, whose tables change at every step.
@@ -2256,8 +2175,6 @@ static int uct_reroot_now(mp_ctx *ctx, long cap_new)
     const UctNode *od = (const UctNode *)ctx->ws[old_slot].p;
     if (ctx->tree.il == 2)
         hipLaunchKernelGGL(uct_reroot_kernel<2>, rgrid, dim3(64), 0, ctx->stream, n_roots, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, acts, sizes);
-    else if (ctx->tree.il == 1)
-        hipLaunchKernelGGL(uct_reroot_kernel<1>, rgrid, dim3(64), 0, ctx->stream, n_roots, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, acts, sizes);
     else
         hipLaunchKernelGGL(uct_reroot_kernel<0>, rgrid, dim3(64), 0, ctx->stream, n_roots, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, acts, sizes);
     MP_HIP(hipGetLastError());
@@ -2265,6 +2182,280 @@ static int uct_reroot_now(mp_ctx *ctx, long cap_new)
     ctx->tree.cap = (int)cap_new;
     ctx->tree.armed = false;
     return MP_OK;
+}
+
+// ---- which kernel form a plan takes, and its geometry: a pure host function of the call's shape, the model's and the
+// policy's facts, the kept tree and the MP_UCT_* knobs.  No HIP call, no ctx: mp_uct_choose_form runs it without a device.
+// DESIGN.md §4.1 tabulates the forms, their defaults and the knobs that force them.
+enum UctForm { UF_GLOBAL, UF_GLOBAL_SPILL, UF_LDSR, UF_QUAD, UF_LONE, UF_LONE_MW, UF_LONE_EACH, UF_ROW_EACH, UF_ROW_SHARED,
+               UF_CARTPOLE, UF_POLICY, UF_COUNT };
+static const char *const kUctFormName[UF_COUNT] = {"uct_global", "uct_global_spill", "uct_ldsr", "uct_quad", "uct_lone",
+                                                   "uct_lone_mw", "uct_lone_each", "uct_row_each", "uct_row_shared",
+                                                   "uct_cartpole", "uct_policy"};
+
+constexpr int kUnset = INT_MIN;
+// the knobs that pick a form or its geometry (kUnset: not set), read once per call -- tests change them between calls
+struct UctKnobs {
+    int model;        // MP_UCT_MODEL: 1 "ldsr" (the LDS-resident form), 0 any other value (the gather form)
+    int quad, lone, each, row, rows;   // MP_UCT_QUAD / LONE / EACH / ROW / ROWS: their atoi
+    int lone_waves;   // MP_UCT_LONE_WAVES: 1 / 2 / 4 / 8, any other value 0 (off)
+    int row_waves, row_roots, lanes, cart_rep, cart_waves;   // MP_UCT_ROW_WAVES / ROW_ROOTS / LANES / CART_REP / CART_WAVES
+    int path;         // MP_UCT_PATH: 1 "spill" (the register / global path stack, a test hook), 0 any other value
+    long ldsr_waves;  // MP_UCT_LDSR_WAVES (LONG_MIN: not set)
+};
+static int uct_knob(const char *name)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : kUnset;
+}
+static UctKnobs uct_knobs_read()
+{
+    UctKnobs k;
+    const char *model = getenv("MP_UCT_MODEL"), *path = getenv("MP_UCT_PATH"), *ldsr_waves = getenv("MP_UCT_LDSR_WAVES");
+    k.model = model ? !strcmp(model, "ldsr") : kUnset;
+    k.path = path ? path[0] == 's' : kUnset;
+    k.ldsr_waves = ldsr_waves ? atol(ldsr_waves) : LONG_MIN;
+    k.quad = uct_knob("MP_UCT_QUAD"); k.lone = uct_knob("MP_UCT_LONE"); k.each = uct_knob("MP_UCT_EACH");
+    k.row = uct_knob("MP_UCT_ROW"); k.rows = uct_knob("MP_UCT_ROWS");
+    k.lone_waves = uct_knob("MP_UCT_LONE_WAVES");
+    if (k.lone_waves != kUnset && k.lone_waves != 1 && k.lone_waves != 2 && k.lone_waves != 4 && k.lone_waves != 8) k.lone_waves = 0;
+    k.row_waves = uct_knob("MP_UCT_ROW_WAVES"); k.row_roots = uct_knob("MP_UCT_ROW_ROOTS"); k.lanes = uct_knob("MP_UCT_LANES");
+    k.cart_rep = uct_knob("MP_UCT_CART_REP"); k.cart_waves = uct_knob("MP_UCT_CART_WAVES");
+    return k;
+}
+
+// what the chooser needs to know of a call
+struct UctCall {
+    int n_roots, episodes, horizon, A, S, NB, Sb;   // (NB, Sb: the model's MDPs and states per MDP)
+    bool t16, r8;   // the model has compact transitions / a compact reward index (then n_rdict distinct rewards)
+    int n_rdict;
+    bool cart, pol, listed;
+    int kept_il;    // the layout of the kept tree this plan continues; -1: fresh trees
+    int cus;        // compute units (<= 0: taken as 256)
+};
+// the choice: the form, the tree layout, the kernel arguments lanes / waves / rep_shift, the launch's roots and threads per
+// workgroup and its dynamic LDS bytes
+struct UctChoice {
+    UctForm form;
+    int tree_il, lanes, waves, rep_shift, roots_per_wg, threads;
+    size_t lds;
+};
+
+static int uct_choose(const UctCall &c, const UctKnobs &k, UctChoice *out)
+{
+    const int A = c.A, H = c.horizon, E = c.episodes;
+    const long n = c.n_roots, cus = c.cus > 0 ? c.cus : 256, cap = 1 + (long)E * A;
+    const bool at_known = A >= 2 && A <= 8, fresh = c.kept_il < 0, forced = k.model != kUnset;
+    // LDS bytes.  The per-call tables (their quotient tables hold 16 KB at most), arrays 16-byte aligned, transitions as uint16,
+    // the generator's jump table (n = 0 .. H and the lanes' 1 .. 4), a path stack of [H + 1][64] per wavefront.
+    const int te_max = (int)(16384 / (sizeof(double) * (size_t)(A + 1))), TE = E < te_max ? E : te_max;
+    const size_t ntab = (size_t)(H + 1) + 2 * (size_t)A + (TE + 1) + (size_t)A * (TE + 2), tabs = ntab * sizeof(double);
+    auto dbl16 = [](size_t m) { return ((m + 1) & ~(size_t)1) * sizeof(double); };
+    auto t16_bytes = [](size_t m) { return ((m + 7) & ~(size_t)7) * 2; };
+    const size_t sa = (size_t)c.S * A, sa_each = (size_t)(c.NB > 1 && c.Sb > 0 ? c.Sb : c.S) * A;
+    const size_t jump = (size_t)(H + 5) * 32, path_stack = (size_t)(H + 1) * 64 * sizeof(int32_t);
+    const size_t tree_lds = (size_t)cap * (sizeof(UctNode) + sizeof(double)) + (size_t)(H + 1) * sizeof(int32_t) + 16;
+    const size_t lds_ldsr = dbl16(ntab) + dbl16(c.n_rdict) + t16_bytes(sa) + ((sa + 15) & ~(size_t)15);
+    const size_t lds_quad = lds_ldsr + jump, lds_lone = lds_quad + tree_lds;
+    const size_t lds_each = dbl16(ntab) + dbl16(sa_each) + t16_bytes(sa_each) + jump + tree_lds;
+    auto lds_lone_mw = [&](int w) {     // tables + the transitions + w x (jump table + tree + exploration terms)
+        return dbl16(ntab) + t16_bytes(sa) + (size_t)w * ((((size_t)(H + 5) * 8 + (size_t)cap * 6 + 3) & ~(size_t)3) * 4) + 16;
+    };
+    const size_t row_tree = (size_t)cap * sizeof(UctNode) + (size_t)((H + 4) & ~3) * sizeof(int32_t);
+    auto lds_row_each = [&](int rows) { return dbl16(ntab) + jump + rows * (row_tree + dbl16(sa_each) + t16_bytes(sa_each)); };
+    auto lds_row_shared = [&](int rows) { return dbl16(ntab) + jump + rows * row_tree + t16_bytes(sa); };
+
+    // Which forms the call can take.  The LDS forms plan state-independent policies on table models with |A| in 2..8, and all
+    // but the LDS-resident one and its four-lanes-per-root form start from fresh trees.
+    const bool table = !c.cart && !c.pol && at_known;
+    const bool resident = table && c.t16 && c.r8;                                // the whole model in 3 B per (s, a)
+    const bool shared = table && c.t16 && c.NB <= 1 && fresh;                    // one model's transitions
+    const bool batch = table && c.NB > 1 && c.Sb > 0 && c.Sb < 32768 && fresh;   // one MDP per root
+    // LDS-RESIDENT model (transitions + reward indices + reward table in LDS, nothing of an env step in global memory).
+    // Measured (headline table, 33 x 30; profiles/r04_uct_ldsr.md): kernel ms global / LDS-resident at 8 192 roots 0.342 / 0.357,
+    // 32 768 0.376 / 0.383, 65 536 0.412 / 0.369, 131 072 0.564 / 0.473, 262 144 1.049 / 0.781, 524 288 2.050 / 1.545 -- staging
+    // 150 KB per workgroup costs ~25 us and a lone wave per SIMD hides the gather anyway, so it is the default from one wave per
+    // SIMD (four per CU) upwards.
+    bool ldsr = resident && k.model != 0 && (forced || (n + 63) / 64 >= 4 * cus);
+    if (ldsr && lds_ldsr > kLdsBytes) {
+        if (forced) return fail(MP_ERR_ARG, "mp_uct_plan: model does not fit LDS (%zu B)", lds_ldsr);
+        ldsr = false;
+    }
+    // FOUR LANES PER ROOT: at most one wave per SIMD's worth of roots (16 per wave: 16 384 roots on 256 CUs).  Measured
+    // (profiles/r05_uct_small_batch.md): 64 .. 16 384 roots 1.2-1.25x faster than the one-lane-per-root gather kernel, a single
+    // root level with it (0.186 against 0.183 ms: its chain is selection + backup in global memory).
+    const bool quad = resident && H >= 1 && H <= 255 && lds_quad <= kLdsBytes &&
+                      (k.quad != kUnset ? k.quad != 0 : !forced && n >= 16 && (n + 15) / 16 <= 4 * cus);
+    // ONE ROOT PER WORKGROUP: batches of at most one root per CU -- a single agent's act() above all: model, tables AND tree in
+    // LDS, the whole wavefront working for the root.  One workgroup per CU for a model that fills its LDS (the headline table:
+    // 256 roots 0.088 ms); for smaller models as many as fit a CU's LDS together, up to two planning wavefronts per SIMD
+    // (tools/uct_small_batch.py with UCT_SB_SHAPE, round 6: S = 1 000: 1 024 roots 0.068 ms against the row kernel's 0.090;
+    // S = 250: 2 048 roots 0.083 / 0.094; S = 3 000: 512 roots 0.088 / 0.128 -- and slower than the rows as soon as the
+    // workgroups need a second round).
+    bool lone = resident && fresh && H >= 1 && H <= 63 && lds_lone <= kLdsBytes &&
+                (k.lone != kUnset ? k.lone != 0 : !forced && k.quad == kUnset && n <= cus * std::min(std::max((long)(kLdsBytes / lds_lone), 1L), 8L));
+    // ... and SEVERAL planning wavefronts per workgroup around one copy of the transitions, the rewards from the records in L2:
+    // for a model that fills the LDS, batches of up to 8 roots per CU (two wavefronts per SIMD) -- and, with ONE planning
+    // wavefront, small batches of a model the plain form cannot take (more than 256 distinct rewards, or transitions + reward
+    // indices beyond the LDS; the transitions alone may still fit).
+    int lone_w = 0;
+    if (shared && H >= 1 && H <= 63 && (!lone || k.lone_waves > 0) && k.lone != 0) {
+        if (k.lone_waves != kUnset) lone_w = k.lone_waves;
+        else if (!forced && k.quad == kUnset && k.rows == kUnset && k.path == kUnset && n <= 8 * cus)
+            lone_w = n <= cus ? 1 : (n <= 2 * cus ? 2 : (n <= 4 * cus ? 4 : 8));
+        if (lone_w && lds_lone_mw(lone_w) <= kLdsBytes) lone = true;
+        else lone_w = 0;
+    }
+    // ONE MDP PER ROOT: a batch model, every root's own MDP staged into its workgroup's LDS from the 16-byte records (10 B per
+    // (s, a)), whatever the batch size ...
+    const bool each = batch && H >= 1 && H <= 63 && lds_each <= kLdsBytes && !forced && k.each != 0;
+    // ... and FOUR such roots per wavefront, a DPP row each, with four waves per workgroup (one per SIMD) while their MDPs + trees
+    // fit the LDS, else two / one.  Measured (tools/each_ab.sh, S = 120, 33 x 30): a wavefront per root against four roots per
+    // wavefront -- 256 roots 0.062 ms (lone), 512: 0.065 / 0.091, 1024: 0.067 / 0.090, 2048: 0.077 / 0.090, 4096: 0.143 / 0.098.
+    // Up to two wavefronts per SIMD (and while their workgroups' LDS fits the CU together) a root is served best by a whole
+    // wavefront; beyond, the rows win (the SIMD is 16 lanes wide: four lone waves run at a quarter each).
+    int row_waves = k.row_waves == 1 || k.row_waves == 2 || k.row_waves == 4 ? k.row_waves : 4;
+    while (row_waves > 1 && lds_row_each(kRowRoots * row_waves) > kLdsBytes) row_waves >>= 1;
+    const bool rowk = batch && H >= 1 && H <= 255 && lds_row_each(kRowRoots * row_waves) <= kLdsBytes && !forced && k.each != 0 &&
+                      k.row != 0 && (k.row != kUnset || !each || n > cus * std::min(std::max((long)(kLdsBytes / lds_each), 1L), 8L));
+    // ... and the SHARED-model row form: batches between one root per CU and sixteen (one round of four-wave workgroups) of a model
+    // whose transitions + the workgroup's trees fit the LDS.  Two roots per wavefront (rows 2 and 3 idle) while that still fits
+    // one wave per SIMD: a wave's rounds then run to the slower of 2 roots instead of 4 (2048 roots 0.197 -> 0.187 ms, 1024 roots
+    // 0.195 -> 0.184); two such waves per SIMD for 4096 roots measure the same as one wave of four (0.201 against 0.197).  As few
+    // waves per workgroup as still put the batch on the chip in one round (fewer roots behind one staged copy).
+    const int rpw = n <= 2L * 4 * cus ? 2 : kRowRoots;
+    int rowsh_waves = 4;
+    while (rowsh_waves > 1 && (n + rpw * (rowsh_waves / 2) - 1) / (rpw * (rowsh_waves / 2)) <= cus) rowsh_waves >>= 1;
+    if (k.row_waves == 1 || k.row_waves == 2 || k.row_waves == 4 || k.row_waves == 8) rowsh_waves = k.row_waves;
+    const int rowsh_rpw = k.row_roots == 2 || k.row_roots == 4 ? k.row_roots : rpw;
+    while (rowsh_waves > 1 && lds_row_shared(rowsh_rpw * rowsh_waves) > kLdsBytes) rowsh_waves >>= 1;
+    const bool rowsh = shared && H >= 1 && H <= 255 && lds_row_shared(rowsh_rpw * rowsh_waves) <= kLdsBytes && !forced && !rowk && !each &&
+                       (k.rows != kUnset ? k.rows != 0 : !lone && k.quad == kUnset && k.path == kUnset && n >= 16 && n <= 4L * kRowRoots * cus);
+
+    UctChoice o;
+    o.form = c.cart ? UF_CARTPOLE : c.pol ? UF_POLICY : rowsh ? UF_ROW_SHARED : rowk ? UF_ROW_EACH : each ? UF_LONE_EACH
+           : lone ? (lone_w ? UF_LONE_MW : UF_LONE) : quad ? UF_QUAD : ldsr ? UF_LDSR : UF_GLOBAL;
+    o.tree_il = fresh ? (c.cart || !at_known ? 0 : 2) : c.kept_il;
+    // a kept tree in another layout than the LDS-resident forms': the default kernel with its LDS budget (MP_UCT_PATH aside)
+    const bool fallback = (o.form == UF_LDSR || o.form == UF_QUAD) && o.tree_il != 2;
+    if (fallback) o.form = UF_GLOBAL;
+    // Roots per wavefront of the other forms.  A root's episodes are one long dependency chain, so a batch takes as long as its
+    // slowest wavefront; measured on MI355X (4096 roots, highway table) dense waves are fastest: 64 lanes 0.41 ms, 16 lanes
+    // 0.44 ms, 4 lanes 0.70 ms.
+    o.lanes = k.lanes == 1 || k.lanes == 2 || k.lanes == 4 || k.lanes == 8 || k.lanes == 16 || k.lanes == 32 ? k.lanes : 64;
+    o.waves = 1; o.rep_shift = 0;
+    o.roots_per_wg = 1; o.threads = 1024;
+    switch (o.form) {
+    case UF_LDSR:
+    case UF_QUAD: {
+        // one workgroup per CU shares the tables: as many waves per workgroup as it takes to put the batch on the chip's CUs (a
+        // power of two <= 16, so that chunk boundaries -- multiples of 1024 roots -- are workgroup boundaries)
+        o.lanes = o.form == UF_QUAD ? 16 : 64;
+        const long w = k.ldsr_waves != LONG_MIN ? k.ldsr_waves : ((n + o.lanes - 1) / o.lanes + cus - 1) / cus;
+        while (o.waves < w && o.waves < 16) o.waves <<= 1;
+        o.lds = o.form == UF_QUAD ? lds_quad : lds_ldsr;
+        break;
+    }
+    case UF_LONE: o.lds = lds_lone; break;
+    case UF_LONE_MW: o.waves = o.roots_per_wg = lone_w; o.lds = lds_lone_mw(lone_w); break;
+    case UF_LONE_EACH: o.threads = sa_each <= 4096 ? 64 : 256; o.lds = lds_each; break;   // (one wave while it stages its MDP in a few trips)
+    case UF_ROW_EACH: o.roots_per_wg = kRowRoots * row_waves; o.threads = 64 * row_waves; o.lds = lds_row_each(o.roots_per_wg); break;
+    case UF_ROW_SHARED:   // (the wavefronts of a workgroup that plan; the workgroup's other waves help stage the model)
+        o.lanes = rowsh_rpw; o.waves = rowsh_waves; o.roots_per_wg = rowsh_rpw * rowsh_waves; o.lds = lds_row_shared(o.roots_per_wg);
+        break;
+    case UF_CARTPOLE: {
+        // CartPole (round 6): a root is one lane, and a wavefront takes as long as its SLOWEST root's episodes -- rollouts end when
+        // the pole falls, at very different lengths -- so a small batch is spread over more wavefronts of FEWER roots: 16 per
+        // wave (4096 roots: 256 waves; 0.564 -> 0.550 ms).  Not fewer: wavefronts with 2 .. 8 active lanes run 1.6 - 3x SLOWER per
+        // instruction when the whole chip is busy with them (tools/exec_rate.hip: an f64 division chain 180 -> 527 cycles at 4
+        // active lanes x 1024 waves, unchanged at 16 or 64 lanes or on a single wave; the kernel itself 0.56 -> 1.16 ms at 4 roots
+        // per wave although each wave then executes a third fewer instructions: profiles/r06_cartpole.md).
+        if (k.lanes == kUnset)
+            for (o.lanes = 1; o.lanes < (n + 4 * cus - 1) / (4 * cus) && o.lanes < 64;) o.lanes <<= 1;
+        // Later in round 6: the slow mode is a matter of how many lanes are ACTIVE, not of how many roots a wave serves
+        // (exec_rate.hip with strides: <= 8 active lanes anywhere in the wave are slow about every other run, >= 16 never).  So a
+        // root is REPLICATED over 2^rep_shift lanes that all compute its plan -- 4 roots x 16 lanes at 4096 roots: 1024
+        // wavefronts, one per SIMD, 669 rollout trips per wave instead of 891 -- and the replicas share the generator work (the
+        // rollout block of uct_kernel).
+        while ((o.lanes << (o.rep_shift + 1)) <= 64) ++o.rep_shift;
+        if (k.cart_rep != kUnset)
+            for (o.rep_shift = k.cart_rep; o.rep_shift > 0 && (o.lanes << o.rep_shift) > 64;) --o.rep_shift;
+        if (o.rep_shift < 2) o.rep_shift = 0;      // (the replicated form works on quads)
+        o.waves = k.cart_waves == 1 || k.cart_waves == 2 || k.cart_waves == 4 ? k.cart_waves : 4;
+        // the per-lane path stack, then the sin / cos table of libm_sincos.hpp and the jump table: fewer waves per workgroup where
+        // four would not fit the CU's LDS -- horizons beyond ~150; one wave reaches ~600 steps
+        const size_t sincos = 8 + (size_t)MP_SINCOS_ENTRIES * sizeof(double) + jump;
+        while (o.waves > 1 && tabs + o.waves * path_stack + sincos > kLdsBytes) o.waves >>= 1;
+        o.lds = tabs + o.waves * path_stack + sincos;
+        if (o.lds > kLdsBytes) return fail(MP_ERR_ARG, "mp_uct_plan: horizon %d / episodes %d need %zu B of LDS tables (> 64 KiB)", H, E, o.lds);
+        break;
+    }
+    default:    // the gather forms: a path stack that does not fit 64 KB of LDS (horizon >~ 180) moves to registers + a global
+                // spill array; MP_UCT_PATH=spill forces that
+        o.lds = tabs + path_stack;
+        if (o.lds > 64 * 1024 && !fallback && (c.pol || tabs > 64 * 1024))
+            return fail(MP_ERR_ARG, "mp_uct_plan: horizon %d / episodes %d need %zu B of LDS tables (> 64 KiB)", H, E, o.lds);
+        if (o.lds > 64 * 1024 || (k.path == 1 && !fallback && !c.pol)) {
+            o.form = UF_GLOBAL_SPILL;
+            o.lds = tabs;
+        }
+        break;
+    }
+    if (o.form != UF_LONE && o.form != UF_LONE_MW && o.form != UF_LONE_EACH && o.form != UF_ROW_EACH && o.form != UF_ROW_SHARED) {
+        o.roots_per_wg = o.waves * o.lanes;   // uct_kernel: a lane per root (QD: four)
+        o.threads = o.waves * 64;
+    }
+    if (c.pol && !c.cart && !at_known)
+        return fail(MP_ERR_ARG, "mp_uct_plan_policy: |A| = %d is not in 2..8: per-state policies over more actions plan through "
+                                "mp_uct_plan_stochastic_policy (it takes deterministic tables too)", A);
+    *out = o;
+    return MP_OK;
+}
+
+// one launch of the chosen form: the grid and workgroup of the choice, the kernel's LDS limit raised past the default 64 KiB
+template <typename Kernel>
+static int uct_go(Kernel kernel, const UctChoice &ch, const UctArgs &a, hipStream_t st)
+{
+    if (ch.lds > 64 * 1024)
+        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ch.lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n_roots + ch.roots_per_wg - 1) / ch.roots_per_wg)), dim3((unsigned)ch.threads), ch.lds,
+                       st, a);
+    return MP_OK;
+}
+
+// the kernel of a form for |A| = AT (0: any |A|), in the tree layout a.tree_il
+template <int AT>
+static int uct_launch(const UctChoice &ch, bool listed, const UctArgs &a, hipStream_t st)
+{
+    const bool il2 = a.tree_il == 2;
+    if constexpr (AT > 0) {
+        switch (ch.form) {
+        case UF_LDSR: return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2>, ch, a, st);
+        case UF_QUAD: return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, true>, ch, a, st);
+        case UF_LONE: return uct_go(uct_lone_kernel<AT>, ch, a, st);
+        case UF_LONE_MW: return uct_go(uct_lone_kernel<AT, false, true>, ch, a, st);
+        case UF_LONE_EACH: return uct_go(uct_lone_kernel<AT, true>, ch, a, st);
+        case UF_ROW_EACH: return uct_go(uct_row_kernel<AT>, ch, a, st);
+        case UF_ROW_SHARED: return uct_go(uct_row_kernel<AT, true>, ch, a, st);
+        case UF_POLICY:
+            if (listed)
+                return il2 ? uct_go(uct_kernel<AT, ENV_TABLE, true, true, 2>, ch, a, st) : uct_go(uct_kernel<AT, ENV_TABLE, true, true, 0>, ch, a, st);
+            return il2 ? uct_go(uct_kernel<AT, ENV_TABLE, true, false, 2>, ch, a, st) : uct_go(uct_kernel<AT, ENV_TABLE, true, false, 0>, ch, a, st);
+        case UF_GLOBAL:
+            if (il2) return uct_go(uct_kernel<AT, ENV_TABLE, false, false, 2>, ch, a, st);
+            break;
+        case UF_GLOBAL_SPILL:
+            if (il2) return uct_go(uct_kernel<AT, ENV_TABLE_SPILL, false, false, 2>, ch, a, st);
+            break;
+        default: break;
+        }
+    }
+    if constexpr (AT == 2)   // (CartPole's two actions)
+        if (ch.form == UF_CARTPOLE) return uct_go(uct_kernel<2, ENV_CARTPOLE>, ch, a, st);
+    // root-major trees: generic |A|, and a kept CartPole tree continued by a table plan
+    if (ch.form == UF_GLOBAL && !il2) return uct_go(uct_kernel<AT, ENV_TABLE>, ch, a, st);
+    if (ch.form == UF_GLOBAL_SPILL && !il2) return uct_go(uct_kernel<AT, ENV_TABLE_SPILL>, ch, a, st);
+    return fail(MP_ERR_ARG, "mp_uct_plan: no %s kernel for |A| = %d in tree layout %d", kUctFormName[ch.form], a.A, a.tree_il);
 }
 
 static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int32_t n_roots, const void *root_state,
@@ -2373,159 +2564,21 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
     a.TA = temperature * (double)A;
     a.temperature = temperature;
 
-    // variant and geometry
-    // Measured on MI355X (highway table, 4096 roots): global-record variant 0.338 ms, LDS-table variant 0.376 ms --
-    // the per-step chain is instruction-bound (PCG64's 128-bit multiply), not gather-latency bound, so the
-    // single-gather variant is the default; MP_UCT_MODEL=lds selects the LDS-resident transition table.
-    const char *force = getenv("MP_UCT_MODEL"); // "global" (default) / "lds"
-    const char *lay = getenv("MP_UCT_TREE"); // "rootmajor" / "interleaved" / "group": tree layout (TreeRef)
-    const bool at_known = A >= 2 && A <= 8;
-    // default: group-interleaved wherever |A| has a compile-time specialisation (262 144 roots: 1.05-1.07 ms against
-    // 1.16 ms root-major and 1.09 ms interleaved; 4 096 roots and single roots: no difference)
-    const int want_il = !lay ? (at_known ? 2 : 0) : (lay[0] == 'i' ? 1 : (lay[0] == 'g' && at_known ? 2 : 0));
-    bool ldsm = !cart && !pol && model->t16 != nullptr && force && !strcmp(force, "lds"); // (the LDS variant keeps root-major trees)
-    // LDS-RESIDENT model (transitions + reward indices + reward table in LDS, nothing of an env step in global memory):
-    // table models with S < 32768, at most 256 distinct rewards, |A| with a specialisation, whose 3 B per (s,a) fit the
-    // CU's LDS next to the per-call tables.  MP_UCT_MODEL=ldsr forces it on, =global off.
-    bool ldsr = !cart && !pol && at_known && model->t16 != nullptr && model->r8 != nullptr && want_il == 2 &&
-                !(force && strcmp(force, "ldsr") != 0) && uct_ldsr_default(force != nullptr, n_roots, ctx->prop.multiProcessorCount);
-    const size_t sa16 = ((size_t)model->S * A + 15) & ~(size_t)15;
-    const size_t lds_ldsr = (((ntab + 1) & ~(size_t)1) + (((size_t)model->n_rdict + 1) & ~(size_t)1)) * sizeof(double) +
-                            (((size_t)model->S * A + 7) & ~(size_t)7) * 2 + sa16;
-    if (ldsr && lds_ldsr > kLdsBytes) {
-        if (force && !strcmp(force, "ldsr")) return fail(MP_ERR_ARG, "mp_uct_plan: model does not fit LDS (%zu B)", lds_ldsr);
-        ldsr = false;
-    }
-    if (ldsr) ldsm = false;
-    // FOUR LANES PER ROOT (uct_kernel<..., QD>): small batches of an LDS-resident model -- at most one wave per SIMD's worth of
-    // roots (16 roots per wave: 16 384 roots on 256 CUs).  MP_UCT_QUAD=1 / 0 forces it on / off.
-    bool quad = false;
-    const size_t lds_quad = lds_ldsr + (size_t)(H + 5) * 32;   // jump table: n = 0 .. H (and the lanes' 1 .. 4)
-    if (!cart && !pol && at_known && model->t16 != nullptr && model->r8 != nullptr && want_il == 2 && H >= 1 && H <= 255 &&
-        lds_quad <= kLdsBytes) {
-        const long cus_q = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        const char *qe = getenv("MP_UCT_QUAD");
-        // measured (profiles/r05_uct_small_batch.md): 64 .. 16 384 roots 1.2-1.25x faster than the one-lane-per-root gather
-        // kernel, a single root level with it (0.186 against 0.183 ms: its chain is selection + backup in global memory)
-        quad = qe ? atoi(qe) != 0 : (!force && n_roots >= 16 && ((long)n_roots + 15) / 16 <= 4 * cus_q);
-    }
-    if (quad) { ldsr = true; ldsm = false; }
-    // ONE ROOT PER WORKGROUP (uct_lone_kernel): batches of at most one root per CU -- a single agent's act() above all -- on fresh
-    // trees: model, tables AND tree in LDS, the whole wavefront working for the root.  MP_UCT_LONE=1 / 0 forces it on (any batch) / off.
-    bool lone = false;
-    int lone_w = 0;                 // > 0: the multi-wavefront form (MW), that many planning wavefronts per workgroup
-    const size_t lds_lone = lds_quad + (size_t)cap * (sizeof(UctNode) + sizeof(double)) + (size_t)(H + 1) * sizeof(int32_t) + 16;
-    auto lds_lone_mw_of = [&](int w) {     // tables + the transitions + w x (jump table + tree + exploration terms)
-        return ((ntab + 1) & ~(size_t)1) * sizeof(double) + (((size_t)model->S * A + 7) & ~(size_t)7) * 2 +
-               (size_t)w * ((((size_t)(H + 5) * 8 + (size_t)cap * 6 + 3) & ~(size_t)3) * 4) + 16;
-    };
-    {
-        const bool will_continue = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
-        if (!cart && !pol && at_known && model->t16 != nullptr && model->r8 != nullptr && want_il == 2 && H >= 1 && H <= 63 &&
-            lds_lone <= kLdsBytes && !will_continue) {
-            const char *le = getenv("MP_UCT_LONE");
-            const long cus_l = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-            // One workgroup per CU for a model that fills its LDS (the headline table: 256 roots 0.088 ms); for smaller models as many
-            // as fit a CU's LDS together, up to two planning wavefronts per SIMD (tools/uct_small_batch.py with UCT_SB_SHAPE, round 6:
-            // S = 1 000: 1 024 roots 0.068 ms against the row kernel's 0.090; S = 250: 2 048 roots 0.083 / 0.094; S = 3 000: 512
-            // roots 0.088 / 0.128 -- and slower than the rows as soon as the workgroups need a second round)
-            const long fit_l = (long)(kLdsBytes / lds_lone);
-            lone = le ? atoi(le) != 0 : (!force && !getenv("MP_UCT_QUAD") && n_roots <= cus_l * (fit_l < 1 ? 1 : (fit_l > 8 ? 8 : fit_l)));
-        }
-        // ... and for a model that fills the LDS (the headline table: one such workgroup per CU), SEVERAL planning wavefronts per
-        // workgroup around one copy of the transitions, the rewards from the records in L2 (uct_lone_kernel<.., MW>): batches of up
-        // to 8 roots per CU (two wavefronts per SIMD) -- and, with ONE planning wavefront, small batches of a model the plain form cannot
-        // take.  MP_UCT_LONE_WAVES=1 / 2 / 4 / 8 forces the form (any batch), 0 turns it off.
-        const char *we = getenv("MP_UCT_LONE_WAVES");
-        const bool we_on = we && (atoi(we) == 1 || atoi(we) == 2 || atoi(we) == 4 || atoi(we) == 8);
-        if (!cart && !pol && at_known && model->t16 != nullptr && model->NB <= 1 && want_il == 2 && H >= 1 && H <= 63 && !will_continue &&
-            (!lone || we_on) && !(getenv("MP_UCT_LONE") && atoi(getenv("MP_UCT_LONE")) == 0)) {
-            const long cus_l = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-            int w = 0;
-            if (we) { if (we_on) w = atoi(we); }
-            else if (!force && !getenv("MP_UCT_QUAD") && !getenv("MP_UCT_ROWS") && !getenv("MP_UCT_PATH") && n_roots <= 8 * cus_l)
-                // (at most one root per CU gets here when the plain form is not to be had: no compact reward index -- more than 256
-                // distinct rewards -- or transitions + reward indices beyond the LDS; the transitions alone may still fit)
-                w = n_roots <= cus_l ? 1 : (n_roots <= 2 * cus_l ? 2 : (n_roots <= 4 * cus_l ? 4 : 8));
-            if (w && lds_lone_mw_of(w) <= kLdsBytes) { lone = true; lone_w = w; }
-        }
-    }
-    // ONE MDP PER ROOT (uct_lone_kernel<.., EACH>): a batch model -- every root's own MDP staged into its workgroup's LDS from the
-    // 16-byte records (10 B per (s, a)), whatever the batch size.  MP_UCT_EACH=0 keeps the one-lane-per-root gather kernel.
-    bool each = false;
-    const int Sb = model->NB > 1 && model->Sb > 0 ? model->Sb : model->S;
-    const size_t sa_each = (size_t)Sb * A;
-    const size_t lds_each = (((ntab + 1) & ~(size_t)1) + ((sa_each + 1) & ~(size_t)1)) * sizeof(double) + ((sa_each + 7) & ~(size_t)7) * 2 +
-                            (size_t)(H + 5) * 32 + (size_t)cap * (sizeof(UctNode) + sizeof(double)) + (size_t)(H + 1) * sizeof(int32_t) + 16;
-    {
-        const bool will_continue = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
-        const char *ee = getenv("MP_UCT_EACH");
-        if (!cart && !pol && at_known && model->NB > 1 && model->Sb > 0 && model->Sb < 32768 && want_il == 2 && H >= 1 && H <= 63 &&
-            lds_each <= kLdsBytes && !will_continue && !force && !(ee && atoi(ee) == 0))
-            each = true;
-    }
-    // ... and FOUR such roots per wavefront, a DPP row each (uct_row_kernel): the default wherever four MDPs + trees fit the LDS of
-    // a workgroup.  MP_UCT_ROW=0 keeps a wavefront per root.
-    bool rowk = false;
-    // waves per workgroup: four (one per SIMD of the CU) while their MDPs + trees fit the LDS, else two / one
-    auto lds_row_of = [&](int rows_wg) {
-        return (((ntab + 1) & ~(size_t)1) + rows_wg * ((sa_each + 1) & ~(size_t)1)) * sizeof(double) + rows_wg * (size_t)cap * sizeof(UctNode) +
-               (size_t)(H + 5) * 32 + rows_wg * (size_t)((H + 4) & ~3) * sizeof(int32_t) + rows_wg * ((sa_each + 7) & ~(size_t)7) * 2;
-    };
-    int row_waves = 4;
-    if (const char *e = getenv("MP_UCT_ROW_WAVES")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) row_waves = v; }
-    while (row_waves > 1 && lds_row_of(kRowRoots * row_waves) > kLdsBytes) row_waves >>= 1;
-    const size_t lds_row = lds_row_of(kRowRoots * row_waves);
-    {
-        const char *re = getenv("MP_UCT_ROW");
-        const bool will_continue = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
-        if (!cart && !pol && at_known && model->NB > 1 && model->Sb > 0 && model->Sb < 32768 && want_il == 2 && H >= 1 && H <= 255 &&
-            lds_row <= kLdsBytes && !will_continue && !force && !(getenv("MP_UCT_EACH") && atoi(getenv("MP_UCT_EACH")) == 0) &&
-            !(re && atoi(re) == 0)) {
-            // measured (tools/each_ab.sh, S = 120, 33 x 30, after the lone kernel's rebuild in round 6): a wavefront per root against
-            // four roots per wavefront -- 256 roots 0.062 ms (lone), 512: 0.065 / 0.091, 1024: 0.067 / 0.090, 2048: 0.077 / 0.090,
-            // 4096: 0.143 / 0.098.  Up to two wavefronts per SIMD (and while their workgroups' LDS fits the CU together) a root is
-            // served best by a whole wavefront; beyond, the rows win (the SIMD is 16 lanes wide: four lone waves run at a quarter each).
-            const long cus_r = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-            const long fit_cu = lds_each > 0 ? (long)(kLdsBytes / lds_each) : 1;
-            const long lone_roots = cus_r * (fit_cu < 1 ? 1 : (fit_cu > 8 ? 8 : fit_cu));
-            rowk = (re && atoi(re) != 0) || !each || n_roots > lone_roots;
-        }
-    }
-    if (rowk) each = false;
-    // ... and the SHARED-model form of the row kernel (uct_row_kernel<.., true>): batches between one root per CU (uct_lone_kernel)
-    // and sixteen (one round of four-wave workgroups) of a model whose transitions + the workgroup's trees fit the LDS.
-    // MP_UCT_ROWS=1 / 0 forces it on (any batch size) / off.
-    bool rowsh = false;
-    int rowsh_waves = 4, rowsh_rpw = kRowRoots;   // planning wavefronts per workgroup, roots per wavefront
-    size_t lds_rowsh = 0;
-    {
-        auto lds_rowsh_of = [&](int rows_wg) {
-            return ((ntab + 1) & ~(size_t)1) * sizeof(double) + rows_wg * (size_t)cap * sizeof(UctNode) + (size_t)(H + 5) * 32 +
-                   rows_wg * (size_t)((H + 4) & ~3) * sizeof(int32_t) + (((size_t)model->S * A + 7) & ~(size_t)7) * 2;
-        };
-        const long cus_s = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        // two roots per wavefront (rows 2 and 3 idle) while that still fits one wave per SIMD: a wave's rounds then run to the slower
-        // of 2 roots instead of 4 (2048 roots 0.197 -> 0.187 ms, 1024 roots 0.195 -> 0.184); two such waves per SIMD for 4096 roots
-        // measure the same as one wave of four (0.201 against 0.197)
-        if ((long)n_roots <= 2L * 4 * cus_s) rowsh_rpw = 2;
-        // as few waves per workgroup as still put the batch on the chip in one round (fewer roots behind one staged copy)
-        while (rowsh_waves > 1 && ((long)n_roots + rowsh_rpw * (rowsh_waves / 2) - 1) / (rowsh_rpw * (rowsh_waves / 2)) <= cus_s) rowsh_waves >>= 1;
-        if (const char *e = getenv("MP_UCT_ROW_WAVES")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) rowsh_waves = v; }
-        if (const char *e = getenv("MP_UCT_ROW_ROOTS")) { const int v = atoi(e); if (v == 2 || v == 4) rowsh_rpw = v; }
-        while (rowsh_waves > 1 && lds_rowsh_of(rowsh_rpw * rowsh_waves) > kLdsBytes) rowsh_waves >>= 1;
-        lds_rowsh = lds_rowsh_of(rowsh_rpw * rowsh_waves);
-        const char *se = getenv("MP_UCT_ROWS");
-        const bool will_continue = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
-        if (!cart && !pol && at_known && model->t16 != nullptr && model->NB <= 1 && want_il == 2 && H >= 1 && H <= 255 &&
-            lds_rowsh <= kLdsBytes && !will_continue && !force && !rowk && !each)
-            rowsh = se ? atoi(se) != 0 : (!lone && !getenv("MP_UCT_QUAD") && !getenv("MP_UCT_PATH") && n_roots >= 16 && n_roots <= 4L * kRowRoots * cus_s);
-    }
-    if (each || rowk || rowsh) lone = true;
-    if (lone) { quad = false; ldsr = false; ldsm = false; }
-    a.Sb = Sb;
+    // the kernel form and its geometry: nothing below changes them
+    const bool cont = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
+    UctCall call;
+    call.n_roots = n_roots; call.episodes = E; call.horizon = H; call.A = A; call.S = model->S; call.NB = model->NB; call.Sb = model->Sb;
+    call.t16 = model->t16 != nullptr; call.r8 = model->r8 != nullptr; call.n_rdict = model->n_rdict;
+    call.cart = cart; call.pol = pol != nullptr; call.listed = listed;
+    call.kept_il = cont ? ctx->tree.il : -1;
+    call.cus = ctx->prop.multiProcessorCount;
+    UctChoice ch;
+    MP_TRY(uct_choose(call, uct_knobs_read(), &ch));
+    const UctForm form = ch.form;
+    a.Sb = model->NB > 1 && model->Sb > 0 ? model->Sb : model->S;
     a.jump = nullptr;
-    if (quad || lone || cart) {
+    if (form == UF_QUAD || form == UF_LONE || form == UF_LONE_MW || form == UF_LONE_EACH || form == UF_ROW_EACH || form == UF_ROW_SHARED ||
+        form == UF_CARTPOLE) {
         // limbs of A^n and G_n = 1 + A + ... + A^(n-1) (mod 2^128), n = 0..H: the generator after n draws is A^n state + inc G_n
         if (ctx->jump_entries < H + 5) {
             typedef unsigned __int128 u128;
@@ -2550,68 +2603,7 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
         a.jump = static_cast<const uint32_t *>(ctx->ws[WS_JUMP].p);
     }
     a.r8 = model->r8; a.rdict = model->rdict; a.n_rdict = model->n_rdict; a.path_spill = nullptr; a.spill_stride = 0;
-    a.lanes = quad ? 16 : ((ldsm || ldsr) ? 64 : uct_lanes_per_wave());
-    // LDS variant: few roots -> 4 waves per workgroup (one per SIMD); big batches -> 16
-    a.waves = ldsm ? ((long)n_roots >= 64L * 16 * ctx->prop.multiProcessorCount ? 16 : 4) : 1;
-    if (rowsh) { a.waves = rowsh_waves; a.lanes = rowsh_rpw; }   // (the wavefronts of a workgroup that plan; the launch adds staging waves)
-    if (cart) {
-        // CartPole (round 6): a root is one lane, and a wavefront takes as long as its SLOWEST root's episodes -- rollouts end when
-        // the pole falls, at very different lengths -- so a small batch is spread over more wavefronts of FEWER roots: 16 per
-        // wave (4096 roots: 256 waves; 0.564 -> 0.550 ms).  Not fewer: wavefronts with 2 .. 8 active lanes run 1.6 - 3x SLOWER per
-        // instruction when the whole chip is busy with them (tools/exec_rate.hip: an f64 division chain 180 -> 527 cycles at 4 active
-        // lanes x 1024 waves, unchanged at 16 or 64 lanes or on a single wave; the kernel itself 0.56 -> 1.16 ms at 4 roots per
-        // wave although each wave then executes a third fewer instructions: profiles/r06_cartpole.md).
-        const long cus_c = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        // Later in round 6: the slow mode is a matter of how many lanes are ACTIVE, not of how many roots a wave serves (exec_rate.hip
-        // with strides: <= 8 active lanes anywhere in the wave are slow about every other run, >= 16 never).  So a root is REPLICATED
-        // over 2^rep_shift lanes that all compute its plan -- 4 roots x 16 lanes at 4096 roots: 1024 wavefronts, one per SIMD, 669
-        // rollout trips per wave instead of 891 -- and the replicas share the generator work (the rollout block of uct_kernel).
-        if (!getenv("MP_UCT_LANES")) {
-            long per = ((long)n_roots + 4 * cus_c - 1) / (4 * cus_c);
-            a.lanes = 1;
-            while (a.lanes < per && a.lanes < 64) a.lanes <<= 1;
-        }
-        a.waves = 4;
-        a.rep_shift = 0;
-        while ((a.lanes << (a.rep_shift + 1)) <= 64) ++a.rep_shift;
-        if (const char *e = getenv("MP_UCT_CART_REP")) { a.rep_shift = atoi(e); while (a.rep_shift > 0 && (a.lanes << a.rep_shift) > 64) --a.rep_shift; }
-        if (a.rep_shift < 2) a.rep_shift = 0;      // (the replicated form works on quads)
-        if (const char *e = getenv("MP_UCT_CART_WAVES")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) a.waves = v; }
-        // (the per-lane path stack is [H + 1][waves * 64] in LDS: fewer waves per workgroup where four would not fit the CU's LDS --
-        // horizons beyond ~150; one wave reaches ~600 steps)
-        while (a.waves > 1 && ntab * sizeof(double) + (size_t)(H + 1) * a.waves * 64 * sizeof(int32_t) + 8 + (size_t)MP_SINCOS_ENTRIES * sizeof(double) +
-                                      (size_t)(H + 5) * 32 > kLdsBytes)
-            a.waves >>= 1;
-    }
-    if (ldsr) {
-        // one workgroup per CU shares the tables: as many waves per workgroup as it takes to put the batch on the chip's
-        // CUs (a power of two <= 16, so that chunk boundaries -- multiples of 1024 roots -- are workgroup boundaries)
-        const long total_waves = ((long)n_roots + a.lanes - 1) / a.lanes, cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        long w = (total_waves + cus - 1) / cus;
-        if (const char *e = getenv("MP_UCT_LDSR_WAVES")) w = atol(e);
-        a.waves = 1;
-        while (a.waves < w && a.waves < 16) a.waves <<= 1;
-    }
-    const size_t lds_base = ntab * sizeof(double) + (size_t)(H + 1) * a.waves * 64 * sizeof(int32_t);
-    size_t lds = rowsh ? lds_rowsh : rowk ? lds_row : each ? lds_each : lone ? (lone_w ? lds_lone_mw_of(lone_w) : lds_lone) : quad ? lds_quad : (ldsr ? lds_ldsr : lds_base + (ldsm ? (((size_t)model->S * A * 2 + 15) & ~(size_t)15) + 16 : 0));
-    if (cart) lds += 8 + (size_t)MP_SINCOS_ENTRIES * sizeof(double) + (size_t)(H + 5) * 32; // the sin / cos table of libm_sincos.hpp behind the path stack, then the jump table
-    if (ldsm && lds > kLdsBytes) {
-        if (force && force[0] == 'l') return fail(MP_ERR_ARG, "mp_uct_plan: model does not fit LDS (%zu B)", lds);
-        ldsm = false;
-        a.lanes = uct_lanes_per_wave(); a.waves = 1;
-        lds = ntab * sizeof(double) + (size_t)(H + 1) * 64 * sizeof(int32_t);
-    }
-    // a path stack that does not fit 64 KB of LDS (horizon >~ 180): registers + the global spill array instead
-    bool spill = false;
-    if (!lone && !ldsm && !ldsr && lds > 64 * 1024 && !(cart && lds <= kLdsBytes)) {   // (CartPole: the launch raises the kernel's LDS limit)
-        const char *lay_now = getenv("MP_UCT_TREE");
-        if (cart || pol || (lay_now && lay_now[0] == 'i') || ntab * sizeof(double) > 64 * 1024)
-            return fail(MP_ERR_ARG, "mp_uct_plan: horizon %d / episodes %d need %zu B of LDS tables (> 64 KiB)", H, E, lds);
-        spill = true;
-        lds = ntab * sizeof(double);
-    }
-    if (const char *e = getenv("MP_UCT_PATH")) // "spill": force the register / global path stack (test hook)
-        if (e[0] == 's' && !lone && !ldsm && !ldsr && !cart && !pol && want_il != 1) { spill = true; lds = ntab * sizeof(double); }
+    a.lanes = ch.lanes; a.waves = ch.waves; a.rep_shift = ch.rep_shift;
 
     // trees: fresh ones, or (step_strategy "subtree") the kept ones re-rooted into the other buffer with room
     // for this plan's expansions
@@ -2620,7 +2612,6 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
     a.n_nodes_in = nullptr;
     a.n_nodes_out = d_nn;
     long cap_use = cap;
-    const bool cont = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
     if (cont) {
         // a kept subtree only holds nodes created by the last `horizon` plans (a node at depth d survives d re-rootings
         // and d <= horizon), so the stride stays O(horizon * episodes * |A|) however long the episode runs
@@ -2636,21 +2627,13 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
         ctx->tree.armed = false;
         ctx->tree.buf = 0;
         ctx->tree.kept_bound = 1 + (long)horizon * episodes * A;
-        ctx->tree.il = (!cart && !ldsm) ? want_il : 0;   // (ldsr implies want_il == 2)
+        ctx->tree.il = ch.tree_il;
         MP_TRY(ws_get(ctx, WS_TREE0, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_use, A), &a.tree));
     }
     a.cap = (int)cap_use;
     a.tree_il = ctx->tree.il;
-    if (ldsr && ctx->tree.il != 2) { // (a kept tree in another layout: the default kernel and its LDS budget)
-        ldsr = false; ldsm = false; quad = false;
-        a.lanes = uct_lanes_per_wave();
-        a.waves = 1;
-        lds = ntab * sizeof(double) + (size_t)(H + 1) * 64 * sizeof(int32_t);
-        if (lds > 64 * 1024) { spill = true; lds = ntab * sizeof(double); }
-    }
-    if (spill && ctx->tree.il == 1) return fail(MP_ERR_ARG, "mp_uct_plan: horizon %d needs the spilled path stack, which the interleaved tree layout does not have", H);
-    snprintf(ctx->last_variant, sizeof(ctx->last_variant), "%s", cart ? "uct_cartpole" : (pol ? "uct_policy" : (rowsh ? "uct_row_shared" : rowk ? "uct_row_each" : each ? "uct_lone_each" : lone ? (lone_w ? "uct_lone_mw" : "uct_lone") : quad ? "uct_quad" : ldsr ? "uct_ldsr" : (ldsm ? "uct_lds" : (spill ? "uct_global_spill" : "uct_global")))));
-    if (ldsr || spill) {
+    snprintf(ctx->last_variant, sizeof(ctx->last_variant), "%s", kUctFormName[form]);
+    if (form == UF_LDSR || form == UF_QUAD || form == UF_GLOBAL_SPILL) {
         a.spill_stride = ((long)n_roots + 63) & ~63L;
         MP_TRY(ws_get(ctx, WS_TREE4, (size_t)(H + 1) * (size_t)a.spill_stride, &a.path_spill));
     }
@@ -2724,7 +2707,7 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
     // ---- one chunk of roots [r0, r1): copies in, the kernel, copies out, all on stream `s`.  A chunk is the same launch
     // on shifted pointers (r0 is a multiple of 1024: whole wavefront blocks of the interleaved tree layouts and whole
     // workgroups of every variant), so chunked and unchunked calls leave identical trees and results.
-    const long tree_off_per_block = ctx->tree.il == 2 ? (cap_use + A) * 64 : (ctx->tree.il == 1 ? cap_use * 64 : cap_use * 64);
+    const long tree_off_per_block = ctx->tree.il == 2 ? (cap_use + A) * 64 : cap_use * 64;
     auto run_chunk = [&](int r0, int r1, hipStream_t s) -> int {
         const size_t cnt = (size_t)(r1 - r0);
         if (host) {
@@ -2749,79 +2732,15 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
         if (c.root_child_count) c.root_child_count += (size_t)r0 * A;
         if (c.root_child_value) c.root_child_value += (size_t)r0 * A;
         if (c.env_steps) c.env_steps += r0;
-        if (cart) {
-            const int per_block = c.lanes * c.waves;
-            const dim3 grid((unsigned)((c.n_roots + per_block - 1) / per_block)), block(64u * c.waves);
-            if (lds > 64 * 1024)
-                MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_kernel<2, ENV_CARTPOLE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL((uct_kernel<2, ENV_CARTPOLE>), grid, block, lds, s, c);
-        } else if (rowsh) {
-#define MP_ROWS(k)                                                                                                                 \
-    case k:                                                                                                                        \
-        if (lds > 64 * 1024)                                                                                                       \
-            MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_row_kernel<k, true>),                                   \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                    \
-        hipLaunchKernelGGL((uct_row_kernel<k, true>), dim3((unsigned)((c.n_roots + rowsh_rpw * rowsh_waves - 1) / (rowsh_rpw * rowsh_waves))), \
-                           dim3(1024u), lds, s, c);                                                                                \
-        break;
-            switch (A) { MP_ROWS(2) MP_ROWS(3) MP_ROWS(4) MP_ROWS(5) MP_ROWS(6) MP_ROWS(7) MP_ROWS(8) default: break; }
-#undef MP_ROWS
-        } else if (rowk) {
-#define MP_ROWK(k)                                                                                                                 \
-    case k:                                                                                                                        \
-        if (lds > 64 * 1024)                                                                                                       \
-            MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_row_kernel<k>),                                         \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                    \
-        hipLaunchKernelGGL((uct_row_kernel<k>), dim3((unsigned)((c.n_roots + kRowRoots * row_waves - 1) / (kRowRoots * row_waves))),  \
-                           dim3(64u * row_waves), lds, s, c);                                                                      \
-        break;
-            switch (A) { MP_ROWK(2) MP_ROWK(3) MP_ROWK(4) MP_ROWK(5) MP_ROWK(6) MP_ROWK(7) MP_ROWK(8) default: break; }
-#undef MP_ROWK
-        } else if (each) {
-            // one wave per workgroup while a wave stages its MDP in a few trips; four for larger ones
-            const unsigned threads = sa_each <= 4096 ? 64u : 256u;
-#define MP_LONE(k)                                                                                                                 \
-    case k:                                                                                                                        \
-        if (lds > 64 * 1024)                                                                                                       \
-            MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_lone_kernel<k, true>),                                  \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                    \
-        hipLaunchKernelGGL((uct_lone_kernel<k, true>), dim3((unsigned)c.n_roots), dim3(threads), lds, s, c);                      \
-        break;
-            switch (A) { MP_LONE(2) MP_LONE(3) MP_LONE(4) MP_LONE(5) MP_LONE(6) MP_LONE(7) MP_LONE(8) default: break; }
-#undef MP_LONE
-        } else if (lone && lone_w) {
-            c.waves = lone_w;          // the planning wavefronts of a workgroup (its sixteen stage the model first)
-#define MP_LONE(k)                                                                                                                 \
-    case k:                                                                                                                        \
-        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_lone_kernel<k, false, true>),                               \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                        \
-        hipLaunchKernelGGL((uct_lone_kernel<k, false, true>), dim3((unsigned)((c.n_roots + lone_w - 1) / lone_w)), dim3(1024), lds, s, c); \
-        break;
-            switch (A) { MP_LONE(2) MP_LONE(3) MP_LONE(4) MP_LONE(5) MP_LONE(6) MP_LONE(7) MP_LONE(8) default: break; }
-#undef MP_LONE
-        } else if (lone) {
-#define MP_LONE(k)                                                                                                                 \
-    case k:                                                                                                                        \
-        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(uct_lone_kernel<k>), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)lds));                                                                                    \
-        hipLaunchKernelGGL((uct_lone_kernel<k>), dim3((unsigned)c.n_roots), dim3(1024), lds, s, c);                               \
-        break;
-            switch (A) { MP_LONE(2) MP_LONE(3) MP_LONE(4) MP_LONE(5) MP_LONE(6) MP_LONE(7) MP_LONE(8) default: break; }
-#undef MP_LONE
-        } else
         switch (A) {
-        case 2: MP_TRY(uct_launch<2>(c, ldsm, lds, s, pol != nullptr, listed, ldsr, spill, quad)); break;
-        case 3: MP_TRY(uct_launch<3>(c, ldsm, lds, s, pol != nullptr, listed, ldsr, spill, quad)); break;
-        case 4: MP_TRY(uct_launch<4>(c, ldsm, lds, s, pol != nullptr, listed, ldsr, spill, quad)); break;
-        case 5: MP_TRY(uct_launch<5>(c, ldsm, lds, s, pol != nullptr, listed, ldsr, spill, quad)); break;
-        case 6: MP_TRY(uct_launch<6>(c, ldsm, lds, s, pol != nullptr, listed, ldsr, spill, quad)); break;
-        case 7: MP_TRY(uct_launch<7>(c, ldsm, lds, s, pol != nullptr, listed, ldsr, spill, quad)); break;
-        case 8: MP_TRY(uct_launch<8>(c, ldsm, lds, s, pol != nullptr, listed, ldsr, spill, quad)); break;
-        default:
-            if (pol) return fail(MP_ERR_ARG, "mp_uct_plan_policy: |A| = %d is not in 2..8: per-state policies over more actions plan through "
-                                             "mp_uct_plan_stochastic_policy (it takes deterministic tables too)", A);
-            MP_TRY(uct_launch<0>(c, ldsm, lds, s, false, false, false, spill));
-            break;
+        case 2: MP_TRY(uct_launch<2>(ch, listed, c, s)); break;
+        case 3: MP_TRY(uct_launch<3>(ch, listed, c, s)); break;
+        case 4: MP_TRY(uct_launch<4>(ch, listed, c, s)); break;
+        case 5: MP_TRY(uct_launch<5>(ch, listed, c, s)); break;
+        case 6: MP_TRY(uct_launch<6>(ch, listed, c, s)); break;
+        case 7: MP_TRY(uct_launch<7>(ch, listed, c, s)); break;
+        case 8: MP_TRY(uct_launch<8>(ch, listed, c, s)); break;
+        default: MP_TRY(uct_launch<0>(ch, listed, c, s)); break;
         }
         if (rmem == MP_MEM_HOST) MP_HIP(hipMemcpyAsync(rng_state + (size_t)r0 * 6, c.rng, cnt * 48, hipMemcpyDeviceToHost, s));
         if (host) {
@@ -2906,6 +2825,21 @@ int mp_uct_plan_policy(mp_ctx *ctx, mp_model *model, mp_policy *policy, int32_t 
 
 // mcts_with_prior.py:47-62 as tables: per state, the prior row and the integer sampling thresholds of the rollout row
 // (computed exactly as mp_uct_plan computes them for one distribution), plus one fused record per (s, a).
+int mp_uct_choose_form(const int64_t *call, int64_t *out, const char **name)
+{
+    if (!call || !out || !name) return fail(MP_ERR_ARG, "mp_uct_choose_form: NULL argument");
+    UctCall c;
+    c.n_roots = (int)call[0]; c.episodes = (int)call[1]; c.horizon = (int)call[2]; c.A = (int)call[3]; c.S = (int)call[4];
+    c.NB = (int)call[5]; c.Sb = (int)call[6]; c.t16 = call[7] != 0; c.r8 = call[8] != 0; c.n_rdict = (int)call[9];
+    c.cart = call[10] != 0; c.pol = call[11] != 0; c.listed = call[11] == 2; c.kept_il = (int)call[12]; c.cus = (int)call[13];
+    UctChoice ch;
+    MP_TRY(uct_choose(c, uct_knobs_read(), &ch));
+    out[0] = ch.tree_il; out[1] = ch.lanes; out[2] = ch.waves; out[3] = ch.rep_shift; out[4] = ch.roots_per_wg; out[5] = ch.threads;
+    out[6] = (int64_t)ch.lds;
+    *name = kUctFormName[ch.form];
+    return MP_OK;
+}
+
 int mp_policy_load(mp_ctx *ctx, mp_model *model, const double *prior, const double *rollout, mp_policy **out)
 {
     return mp_policy_load_listed(ctx, model, prior, rollout, nullptr, out);
@@ -3259,7 +3193,6 @@ int mp_uct_path_count(mp_ctx *ctx, int32_t root, const int32_t *actions, int32_t
     if (n > 0) MP_HIP(hipMemcpyAsync(d_act, actions, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
     const int tcap = ctx->tree.cap, A = ctx->tree.A;
     if (ctx->tree.il == 2) hipLaunchKernelGGL(uct_path_count_kernel<2>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out);
-    else if (ctx->tree.il == 1) hipLaunchKernelGGL(uct_path_count_kernel<1>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out);
     else hipLaunchKernelGGL(uct_path_count_kernel<0>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out);
     MP_HIP(hipGetLastError());
     MP_HIP(hipMemcpyAsync(count, d_out, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -3285,10 +3218,7 @@ int mp_uct_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes,
         MP_HIP(hipMemcpy2D(g.data(), (size_t)A * sizeof(UctNode), trees + ((long)(root >> 6) * (tcap + A) * 64 + (long)(root & 63) * A),
                            (size_t)64 * A * sizeof(UctNode), (size_t)A * sizeof(UctNode), (size_t)groups, hipMemcpyDeviceToHost));
         for (int i = 0; i < tcap; ++i) h[i] = g[(size_t)(i + A - 1)];
-    } else if (ctx->tree.il == 1) // node i of root r sits at [(r / 64) * cap + i][r % 64]: a strided column
-        MP_HIP(hipMemcpy2D(h.data(), sizeof(UctNode), trees + ((long)(root >> 6) * tcap * 64 + (root & 63)), 64 * sizeof(UctNode),
-                           sizeof(UctNode), (size_t)tcap, hipMemcpyDeviceToHost));
-    else
+    } else
         MP_HIP(hipMemcpy(h.data(), trees + (long)root * tcap, (size_t)tcap * sizeof(UctNode), hipMemcpyDeviceToHost));
     // node slots are appended A at a time; the tree in use is the closure of first_child links.  Slots with
     // count < 0 are the phantoms of actions a listed policy did not list (uct_kernel<.., MK>): they are not nodes.

@@ -106,6 +106,7 @@ SIGNATURES = {
     "mp_olop_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp, _vp,
                                _vp, _vp, c_i32]),
     "mp_olop_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_uct_choose_form": (C.c_int, [_vp, _vp, P(C.c_char_p)]),
     "mp_last_kernel_ms": (C.c_int, [_vp, P(c_f64), P(c_i32)]),
     "mp_last_kernel_variant": (C.c_char_p, [_vp]),
     "mp_selftest_lds_atomic_order": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
@@ -259,6 +260,23 @@ def olop_allocation(budget, gamma):
     if rc != 0:
         raise ValueError("Could not split budget {} with gamma {}".format(budget, gamma))
     return e.value, h.value
+
+
+UCT_CALL_FIELDS = ("n_roots", "episodes", "horizon", "A", "S", "NB", "Sb", "t16", "r8", "n_rdict", "cart", "policy", "kept_il",
+                   "cus")
+UCT_FORM_FIELDS = ("tree_il", "lanes", "waves", "rep_shift", "roots_per_wg", "threads", "lds")
+
+
+def uct_choose_form(call):
+    """The kernel form mp_uct_plan* chooses for a call (mp_uct_choose_form; host only): ``call`` holds the UCT_CALL_FIELDS in
+    order, the MP_UCT_* knobs come from the environment -> (name, int64 array of the UCT_FORM_FIELDS).  A shape the plan
+    refuses raises its NativeError."""
+    c = np.ascontiguousarray(call, dtype=np.int64)
+    assert c.shape == (len(UCT_CALL_FIELDS),), c.shape
+    out = np.zeros(len(UCT_FORM_FIELDS), dtype=np.int64)
+    name = C.c_char_p()
+    _check(load().mp_uct_choose_form(_ptr(c), _ptr(out), C.byref(name)))
+    return name.value.decode(), out
 
 
 def vi_exact_plan(n):

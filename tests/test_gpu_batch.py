@@ -44,11 +44,11 @@ def _cmp_uct(ctx, cfg, n_roots, episodes, horizon, gamma, temperature, prior, ro
     return out
 
 
-@pytest.mark.parametrize("variant", ["global", "lds", "ldsr"])
+@pytest.mark.parametrize("variant", ["global", "ldsr"])
 def test_uct_batch_highway_headline_shape(ctx, variant, monkeypatch):
     """Headline configuration (highway-shaped S=10 000, A=5, 33 episodes x horizon 30), 1536 ragged roots,
-    with the model gathered from HBM/L2 records (default at this size), with the transition table staged in LDS, and with
-    the whole model resident in LDS (round 4: the default from 65 536 roots upwards)."""
+    with the model gathered from HBM/L2 records (default at this size) and with the whole model resident in LDS (round 4:
+    the default from 65 536 roots upwards)."""
     from rl_agents_amd.envs import generators
     monkeypatch.setenv("MP_UCT_MODEL", variant)
     cfg = generators.highway_shaped(10, 10, 100, seed=0)
@@ -138,10 +138,10 @@ def test_uct_lds_resident_model_falls_back(ctx, monkeypatch):
     model.close()
 
 
-@pytest.mark.parametrize("variant", ["global", "lds"])
+@pytest.mark.parametrize("variant", ["global"])
 @pytest.mark.parametrize("n_actions", [2, 3, 4, 5, 6, 7, 8, 11])
 def test_uct_batch_action_counts(ctx, n_actions, variant, monkeypatch):
-    """Every compile-time |A| specialisation and the generic-|A| kernel, both model placements."""
+    """Every compile-time |A| specialisation and the generic-|A| kernel, the model gathered from its records."""
     from rl_agents_amd.envs import generators
     monkeypatch.setenv("MP_UCT_MODEL", variant)
     cfg = generators.random_deterministic(257, n_actions, seed=n_actions, terminal_rate=0.05)
@@ -494,7 +494,7 @@ def test_limits_and_error_codes(ctx):
 
 
 def test_uct_large_state_space_without_compact_table(ctx):
-    """S >= 32768: no uint16 transition table exists; the record-gather kernel handles it (also with MP_UCT_MODEL=lds)."""
+    """S >= 32768: no uint16 transition table exists; the record-gather kernel handles it."""
     from rl_agents_amd.envs import generators
     cfg = generators.random_deterministic(40000, 4, seed=12, terminal_rate=0.02)
     p = np.ones(4) / 4
