@@ -28,6 +28,8 @@
 // moves (TA busy 72-84 % at 8192 roots), so an expansion issues as few as possible: one record store per child
 // instead of four, gamma tables through the scalar cache (the depth is wave-uniform)
 // = 37 B/node; LDS per root: 8 B/node (+ 4 B per expansion for the parent map).
+// The host side (choice of kernel form, tables, staging, export skeleton: opd_host.hpp) and the tie draws of the plan descents
+// (opd_closing.hpp) are shared with ropd.hip.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -38,6 +40,7 @@
 #include "pcg64.hpp"
 #include "wave.hpp"
 #include "opd_closing.hpp"
+#include "opd_host.hpp"
 
 // The selected leaf's 16-byte node record, read by a SCALAR load past the scalar cache (glc).  The record was written by this
 // wave's vector stores of an EARLIER expansion; `s_waitcnt vmcnt(N)` with N = the vector-memory operations THIS expansion has
@@ -72,11 +75,7 @@ struct OpdArgs {
     double *L; // OpdNode records {L, state, depth}, 16 B per node
     double *U, *reward;
     double *leaf_global; // [n_roots][64 * T]: the upper-bound array of the high-occupancy variant (else nullptr)
-    int32_t *expanded; // [n_roots][K] node expanded at step k (= parent of nodes 1 + kA .. 1 + kA + A - 1)
-    int32_t *n_nodes_out;
-    int32_t *plans, *plan_len, *status;
-    double *root_lower, *root_upper;
-    int64_t *env_steps;
+    OpdOut out; // (the wide kernel reads it from the kernel-argument segment: the layout is part of its code)
 };
 
 struct alignas(16) OpdNode {
@@ -85,6 +84,7 @@ struct alignas(16) OpdNode {
     int32_t depth;
 };
 static_assert(sizeof(OpdNode) == 16, "OpdNode must be one dwordx4");
+static_assert(offsetof(OpdArgs, out) == 128 && sizeof(OpdArgs) == 192, "OpdArgs: the kernel-argument layout changed");
 
 // LDS layout of the upper-bound array: node id -> (id & 63) * T + (id >> 6).  Lane l owns the ids
 // congruent to l mod 64 ("class" l), stored contiguously, and caches the best leaf of its class in
@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64) void opd_kernel(OpdArgs p)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int T = p.T;                                                // odd, >= ceil(cap / 64)
     double *leafU = lds;                                                        // [64 * T]
-    int32_t *exp_lds = EXPG ? p.expanded + (long)blockIdx.x * (p.K > 0 ? p.K : 1) // parent map in HBM
+    int32_t *exp_lds = EXPG ? p.out.expanded + (long)blockIdx.x * (p.K > 0 ? p.K : 1) // parent map in HBM
                             : reinterpret_cast<int32_t *>(lds + 64 * T);        // [K]
 #define LU(id) leafU[((id) & 63) * T + ((id) >> 6)]
     const int lane = threadIdx.x;
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(64) void opd_kernel(OpdArgs p)
             // pointer jumping over the expansion tree + a prepared plan walk (opd_closing.hpp)
             len = closing_compact(lds, p.K, k_done, n_nodes, A, exp_lds, [&](int id) { return NA[id].L; },
                                   [&](int id, double v) { NA[id].L = v; }, gen,
-                                  p.plans ? p.plans + (long)root * p.max_plan_len : nullptr, p.max_plan_len, root_lower);
+                                  p.out.plans ? p.out.plans + (long)root * p.max_plan_len : nullptr, p.max_plan_len, root_lower);
             PROF_T(cf2); PROF_T(cf3); PROF_T(cf4);
 #ifdef MP_PROFILE
             t_f[0] = cf1 - cf0; t_f[1] = cf2 - cf1; t_f[2] = cf3 - cf2; t_f[3] = cf4 - cf3; t_f[4] = cf4;
@@ -447,13 +447,8 @@ __global__ __launch_bounds__(64) void opd_kernel(OpdArgs p)
                 const double l = lane < A ? NA[fc + lane].L : ninf;
                 const double slot = lane < A ? LU(fc + lane) : 0.0;
                 const double m = A <= 16 ? row0_max(l) : wave_max(l);
-                const unsigned long long ties = ballot64(lane < A && l == m);
-                const int nt = __popcll(ties);
-                int pick = (int)gen.below((uint32_t)nt); // uniform across lanes (same state, same draws)
-                unsigned long long t = ties;
-                while (pick-- > 0) t &= t - 1;
-                const int a = __ffsll((long long)t) - 1;
-                if (lane == 0 && p.plans && len < p.max_plan_len) p.plans[(long)root * p.max_plan_len + len] = a;
+                const int a = draw_tie(ballot64(lane < A && l == m), gen);
+                if (lane == 0 && p.out.plans && len < p.max_plan_len) p.out.plans[(long)root * p.max_plan_len + len] = a;
                 ++len;
                 const int shi = __builtin_amdgcn_readlane(__double2hiint(slot), a), slo = __builtin_amdgcn_readlane(__double2loint(slot), a);
                 kcur = ((unsigned)shi == 0xFFF80000u) ? slo : -1; // expanded: its k; a leaf: the plan ends
@@ -464,16 +459,16 @@ __global__ __launch_bounds__(64) void opd_kernel(OpdArgs p)
 #endif
         if (lane == 0) {
             gen.store(p.rng + (long)root * 6);
-            if (p.plans)
-                for (int i = len; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
-            if (p.plan_len) p.plan_len[root] = len;
-            if (p.root_lower) p.root_lower[root] = root_lower;
-            if (p.root_upper) p.root_upper[root] = root_upper;
+            if (p.out.plans)
+                for (int i = len; i < p.max_plan_len; ++i) p.out.plans[(long)root * p.max_plan_len + i] = -1;
+            if (p.out.plan_len) p.out.plan_len[root] = len;
+            if (p.out.root_lower) p.out.root_lower[root] = root_lower;
+            if (p.out.root_upper) p.out.root_upper[root] = root_upper;
         }
     } else if (lane == 0) {
-        if (p.plans)
-            for (int i = 0; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
-        if (p.plan_len) p.plan_len[root] = 0;
+        if (p.out.plans)
+            for (int i = 0; i < p.max_plan_len; ++i) p.out.plans[(long)root * p.max_plan_len + i] = -1;
+        if (p.out.plan_len) p.out.plan_len[root] = 0;
     }
 #ifdef MP_PROFILE
     if (root == 0 && lane == 0)
@@ -490,14 +485,14 @@ __global__ __launch_bounds__(64) void opd_kernel(OpdArgs p)
     int n_real = real_mine;
     for (int off = 32; off > 0; off >>= 1) n_real += __shfl_xor(n_real, off);
     if (lane == 0) {
-        if (p.status) p.status[root] = status;
-        if (p.env_steps) p.env_steps[root] = (int64_t)n_real;
-        p.n_nodes_out[root] = n_nodes;
+        if (p.out.status) p.out.status[root] = status;
+        if (p.out.env_steps) p.out.env_steps[root] = (int64_t)n_real;
+        p.out.n_nodes_out[root] = n_nodes;
     }
     if (EXPG) {
-        for (int k = k_done + lane; k < p.K; k += 64) p.expanded[(long)root * p.K + k] = -1;
+        for (int k = k_done + lane; k < p.K; k += 64) p.out.expanded[(long)root * p.K + k] = -1;
     } else {
-        for (int k = lane; k < p.K; k += 64) p.expanded[(long)root * p.K + k] = k < k_done ? exp_lds[k] : -1;
+        for (int k = lane; k < p.K; k += 64) p.out.expanded[(long)root * p.K + k] = k < k_done ? exp_lds[k] : -1;
     }
 #undef LU
 }
@@ -747,18 +742,10 @@ __global__ __launch_bounds__(64, 8) void opd_wide_kernel(OpdArgs p)
     }
     __syncthreads();
 
-    // Everything only the closing passes need is read from the kernel-argument segment HERE: loaded at entry (as the
-    // compiler does with by-value arguments) those twelve pointers sit in SGPRs through the main loop, which at the 80
-    // SGPRs of 8 waves per SIMD meant 17 spill reloads per expansion (a tenth of its VALU instructions).
-    const OpdArgs __attribute__((address_space(4))) *q;
-    {
-        unsigned long long ka = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ka)); // the loads below cannot move above this point
-        q = (const OpdArgs __attribute__((address_space(4))) *)ka;
-    }
+    const auto *q = kernargs_after_loop<OpdArgs>(); // what only the closing passes need (opd_closing.hpp)
     double *U = q->U + base;
-    int32_t *exp_map = q->expanded + (long)root * (q->K > 0 ? q->K : 1);
-    int32_t *const plans = q->plans, *const plan_len = q->plan_len;
+    int32_t *exp_map = q->out.expanded + (long)root * (q->K > 0 ? q->K : 1);
+    int32_t *const plans = q->out.plans, *const plan_len = q->out.plan_len;
     const int max_plan_len = q->max_plan_len;
 
     // closing pass over the bounds array: leaf upper bounds out, the root's upper bound, and the parent map scattered from
@@ -852,12 +839,7 @@ __global__ __launch_bounds__(64, 8) void opd_wide_kernel(OpdArgs p)
             const double l = lane < A ? NA[fc + lane].L : ninf;
             const double slot = lane >= A ? 0.0 : SIB ? leafU[((kcur + 1) & 63) * T + ((kcur + 1) >> 6) * A + lane] : LU(fc + lane);
             const double m = A <= 16 ? row0_max(l) : wave_max(l);
-            const unsigned long long ties = ballot64(lane < A && l == m);
-            const int nt = __popcll(ties);
-            int pick = (int)gen.below((uint32_t)nt);
-            unsigned long long t = ties;
-            while (pick-- > 0) t &= t - 1;
-            const int a = __ffsll((long long)t) - 1;
+            const int a = draw_tie(ballot64(lane < A && l == m), gen);
             if (lane == 0 && plans && len < max_plan_len) plans[(long)root * max_plan_len + len] = a;
             ++len;
             const int shi = __builtin_amdgcn_readlane(__double2hiint(slot), a), slo = __builtin_amdgcn_readlane(__double2loint(slot), a);
@@ -868,8 +850,8 @@ __global__ __launch_bounds__(64, 8) void opd_wide_kernel(OpdArgs p)
             if (plans)
                 for (int i = len; i < max_plan_len; ++i) plans[(long)root * max_plan_len + i] = -1;
             if (plan_len) plan_len[root] = len;
-            if (q->root_lower) q->root_lower[root] = NA[0].L;
-            if (q->root_upper) q->root_upper[root] = root_upper;
+            if (q->out.root_lower) q->out.root_lower[root] = NA[0].L;
+            if (q->out.root_upper) q->out.root_upper[root] = root_upper;
         }
     } else if (lane == 0) {
         if (plans)
@@ -879,9 +861,9 @@ __global__ __launch_bounds__(64, 8) void opd_wide_kernel(OpdArgs p)
     int n_real = real_mine;
     for (int off = 32; off > 0; off >>= 1) n_real += __shfl_xor(n_real, off);
     if (lane == 0) {
-        if (q->status) q->status[root] = status;
-        if (q->env_steps) q->env_steps[root] = (int64_t)n_real;
-        q->n_nodes_out[root] = n_nodes;
+        if (q->out.status) q->out.status[root] = status;
+        if (q->out.env_steps) q->out.env_steps[root] = (int64_t)n_real;
+        q->out.n_nodes_out[root] = n_nodes;
     }
     for (int k = k_done + lane; k < q->K; k += 64) exp_map[k] = -1;
 #undef LU
@@ -897,7 +879,7 @@ __global__ __launch_bounds__(64) void opd_any_kernel(OpdArgs p)
     const long base = (long)root * p.cap;
     OpdNode *NA = reinterpret_cast<OpdNode *>(p.L) + base;
     double *U = p.U + base, *RW = p.reward + base;
-    int32_t *EXP = p.expanded + (long)root * (p.K > 0 ? p.K : 1);
+    int32_t *EXP = p.out.expanded + (long)root * (p.K > 0 ? p.K : 1);
     constexpr int32_t DONE_FLAG = 1 << 30;
     const uint32_t done_bit = p.done_on_next ? 2u : 1u;
     const double ninf = -INFINITY;
@@ -989,42 +971,30 @@ __global__ __launch_bounds__(64) void opd_any_kernel(OpdArgs p)
                 m = l > m ? l : m;
             }
             m = wave_max(m);
-            int nt = 0;
-            for (int a0 = 0; a0 < A; a0 += 64) nt += __popcll(ballot64(a0 + lane < A && NA[fc + a0 + lane].L == m));
-            int pick = (int)gen.below((uint32_t)nt), act = 0;
-            for (int a0 = 0; a0 < A; a0 += 64) {
-                unsigned long long t = ballot64(a0 + lane < A && NA[fc + a0 + lane].L == m);
-                const int c = __popcll(t);
-                if (pick < c) {
-                    while (pick-- > 0) t &= t - 1;
-                    act = a0 + __ffsll((long long)t) - 1;
-                    break;
-                }
-                pick -= c;
-            }
-            if (lane == 0 && p.plans && len < p.max_plan_len) p.plans[(long)root * p.max_plan_len + len] = act;
+            const int act = draw_tie_chunks(A, [&](int a) { return NA[fc + a].L == m; }, gen);
+            if (lane == 0 && p.out.plans && len < p.max_plan_len) p.out.plans[(long)root * p.max_plan_len + len] = act;
             ++len;
             node = fc + act;
         }
         if (lane == 0) {
             gen.store(p.rng + (long)root * 6);
-            if (p.plans)
-                for (int i = len; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
-            if (p.plan_len) p.plan_len[root] = len;
-            if (p.root_lower) p.root_lower[root] = NA[0].L;
-            if (p.root_upper) p.root_upper[root] = root_upper;
+            if (p.out.plans)
+                for (int i = len; i < p.max_plan_len; ++i) p.out.plans[(long)root * p.max_plan_len + i] = -1;
+            if (p.out.plan_len) p.out.plan_len[root] = len;
+            if (p.out.root_lower) p.out.root_lower[root] = NA[0].L;
+            if (p.out.root_upper) p.out.root_upper[root] = root_upper;
         }
     } else if (lane == 0) {
-        if (p.plans)
-            for (int i = 0; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
-        if (p.plan_len) p.plan_len[root] = 0;
+        if (p.out.plans)
+            for (int i = 0; i < p.max_plan_len; ++i) p.out.plans[(long)root * p.max_plan_len + i] = -1;
+        if (p.out.plan_len) p.out.plan_len[root] = 0;
     }
     int n_real = real_mine;
     for (int off = 32; off > 0; off >>= 1) n_real += __shfl_xor(n_real, off);
     if (lane == 0) {
-        if (p.status) p.status[root] = status;
-        if (p.env_steps) p.env_steps[root] = (int64_t)n_real;
-        p.n_nodes_out[root] = n_nodes;
+        if (p.out.status) p.out.status[root] = status;
+        if (p.out.env_steps) p.out.env_steps[root] = (int64_t)n_real;
+        p.out.n_nodes_out[root] = n_nodes;
     }
     for (int k = k_done + lane; k < p.K; k += 64) EXP[k] = -1;
 }
@@ -1065,114 +1035,51 @@ int mp_opd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *ro
     if (model->mode != MP_MODE_DETERMINISTIC)
         return fail(MP_ERR_MODE, "mp_opd_plan: model mode %d is not a deterministic table", model->mode);
     const int A = model->A;
-    const bool any_a = A > 64; // more actions than lanes: the plain kernel (opd_any_kernel)
     if (n_roots < 1 || budget < 0 || max_plan_len < 0) return fail(MP_ERR_ARG, "mp_opd_plan: bad sizes");
-    const int K = budget / A; // deterministic.py:118
-    if (K > 0 && !(gamma != 1.0))
+    const OpdShape s = opd_shape(ctx, A, budget, n_roots, gamma, terminal_reward);
+    if (s.K > 0 && !(gamma != 1.0))
         return fail(MP_ERR_ARG, "mp_opd_plan: gamma = 1 (the reference divides by 1 - gamma, deterministic.py:53: ZeroDivisionError)");
-    const long cap = 1 + (long)K * A;
-    const int T = (int)((cap + 63) / 64) | 1;
-    const size_t lds_full = (size_t)64 * T * sizeof(double) + (size_t)(K > 0 ? K : 1) * sizeof(int32_t);
-        const size_t lds_bounds = (size_t)64 * T * sizeof(double); // bounds only, parent map in HBM (EXPG)
-    // high-occupancy variant: LDS only holds the window of the closing lower-bound pass, `chunk` expansions x |A| doubles
-    int chunk = 64;
-    while (chunk > 1 && (size_t)chunk * A * sizeof(double) > 4096) chunk >>= 1;
-    const size_t lds_win = (size_t)chunk * A * sizeof(double);
-    // variant: LDS-resident bounds while every root of the batch fits on the chip that way, else high occupancy
-    const char *force = getenv("MP_OPD_MODEL"); // "lds" / "global": test hook
-    const long cus = ctx->prop.multiProcessorCount;
-    const long lds_roots = cus * (long)((kLdsBytes - 1024) / (lds_full ? lds_full : 1));
-    const long expg_roots = cus * (long)((kLdsBytes - 1024) / (lds_bounds ? lds_bounds : 1));
-    bool glb = lds_bounds > kLdsBytes - 1024 || n_roots > expg_roots;
-    if (force && force[0] == 'g') glb = true;
-    if (force && force[0] == 'l' && lds_bounds <= kLdsBytes - 1024) glb = false;
-    // bounds in LDS: keep the parent map there too while that costs no residency
-    bool expg = !glb && (lds_full > kLdsBytes - 1024 || n_roots > lds_roots);
-    if (force && !glb && force[1] == 'd' && force[2] == 's' && force[3] == 'x') expg = true; // "ldsx": test hook
-    const size_t lds = glb ? lds_win : (expg ? lds_bounds : lds_full);
     MP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-
-    // gamma-power tables, host libm (bit-equal to Python's float **); depth <= K + 1
-    const int D = K + 2;
-    std::vector<double> tab((size_t)3 * D);
-    for (int d = 0; d < D; ++d) {
-        tab[d] = d >= 1 ? pow(gamma, (double)(d - 1)) : 0.0;
-        tab[D + d] = pow(gamma, (double)d) / (1 - gamma);
-        tab[2 * D + d] = terminal_reward * pow(gamma, (double)d) / (1 - gamma);
-    }
-    double *d_tab = nullptr;
-    MP_TRY(upload_tables(ctx, 2, tab, &d_tab));
 
     OpdArgs a;
-    // high-occupancy variant, sibling layout (default; MP_OPD_WIDE=cls: the residue-class layout): groups of |A| slots,
-    // ceil((K + 1) / 64) groups per row, one cache line of padding so that rows do not all start in the same channels
-    int lgP = 0;
-    while ((1 << lgP) < A) ++lgP;
-    const int groups = (K + 1 + 63) / 64;
-    const int Tsib = groups * A + 16;
-    const char *wide_env = getenv("MP_OPD_WIDE");
-    const bool sib = !(wide_env && wide_env[0] == 'c');
-    a.n_roots = n_roots; a.S = model->S; a.A = A; a.K = K; a.cap = (int)cap; a.T = T; a.chunk = chunk; a.Tsib = Tsib; a.lgP = lgP;
-    { const char *cl = getenv("MP_OPD_CLOSING"); a.closing_chain = cl && cl[0] == 'c'; }
+    a.n_roots = n_roots; a.S = model->S; a.A = A; a.K = s.K; a.cap = s.cap; a.T = s.T; a.chunk = s.chunk; a.Tsib = s.Tsib; a.lgP = s.lgP;
+    a.closing_chain = s.closing_chain;
     a.done_on_next = model->done_on_next; a.max_plan_len = max_plan_len;
     a.rec = model->rec;
-    a.g1 = d_tab; a.gdiv = d_tab + D; a.tdiv = d_tab + 2 * D;
-    const size_t nn = (size_t)n_roots * cap;
+    MP_TRY(opd_gamma_tables(ctx, s.K, gamma, terminal_reward, &a.g1, &a.gdiv, &a.tdiv));
+    // the form: more actions than lanes -> the plain kernel; else LDS-resident or wide (opd_shape), the wide one with at most
+    // two slots per lane in a re-scan (SMALLT) or any number
+    typedef void (*kernel_t)(OpdArgs);
+    static const kernel_t lds_form[2][2] = {{opd_kernel<false, false>, opd_kernel<false, true>}, // [expg][nonneg]
+                                            {opd_kernel<true, false>, opd_kernel<true, true>}};
+    static const kernel_t wide_form[2][2][2] = {                                                 // [sib][nonneg][small]
+        {{opd_wide_kernel<false, false, false>, opd_wide_kernel<false, true, false>}, {opd_wide_kernel<true, false, false>, opd_wide_kernel<true, true, false>}},
+        {{opd_wide_kernel<false, false, true>, opd_wide_kernel<false, true, true>}, {opd_wide_kernel<true, false, true>, opd_wide_kernel<true, true, true>}}};
+    const bool any_a = A > 64, small = (s.sib ? s.Tsib - 16 : s.T) <= 128;
+    const kernel_t kfn = any_a ? opd_any_kernel : s.glb ? wide_form[s.sib][s.nonneg][small] : lds_form[s.expg][s.nonneg];
+    const size_t lds = any_a ? 0 : s.lds();
+
+    const size_t nn = (size_t)n_roots * s.cap;
     MP_TRY(ws_get(ctx, WS_TREE0, 2 * nn, &a.L)); // OpdNode records, 16 B each
     MP_TRY(ws_get(ctx, WS_TREE1, nn, &a.U));
     MP_TRY(ws_get(ctx, WS_TREE2, nn, &a.reward));
     a.leaf_global = nullptr;
-    if (glb && !any_a) MP_TRY(ws_get(ctx, WS_TREE3, (size_t)n_roots * 64 * (sib ? Tsib : T), &a.leaf_global));
-    MP_TRY(ws_get(ctx, WS_TREE7, (size_t)n_roots * (K > 0 ? K : 1) + n_roots, &a.expanded));
-    a.n_nodes_out = a.expanded + (size_t)n_roots * (K > 0 ? K : 1);
-    ctx->tree.kind = 2; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap; ctx->tree.K = K;
+    if (s.glb && !any_a) MP_TRY(ws_get(ctx, WS_TREE3, (size_t)n_roots * 64 * (s.sib ? s.Tsib : s.T), &a.leaf_global));
+    ctx->tree.kind = 2; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = s.cap; ctx->tree.K = s.K;
 
+    const OpdResults res = {rng_state, plans, plan_len, root_lower, root_upper, env_steps, status};
     int32_t *d_rs = nullptr;
     MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n_roots, mem, &d_rs));
     a.root_state = d_rs;
-    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n_roots * 6, rmem, &a.rng));
-    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n_roots * max_plan_len, mem, &a.plans));
-    MP_TRY(stage_out_alloc(ctx, WS_IO4, plan_len, (size_t)n_roots, mem, &a.plan_len));
-    MP_TRY(stage_out_alloc(ctx, WS_IO5, root_lower, (size_t)n_roots, mem, &a.root_lower));
-    MP_TRY(stage_out_alloc(ctx, WS_IO6, root_upper, (size_t)n_roots, mem, &a.root_upper));
-    MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
-    MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, mem, &a.env_steps));
+    MP_TRY(opd_stage(ctx, s, n_roots, max_plan_len, mem, rmem, res, &a.rng, &a.out));
 
-    // every finite bound is >= +0.0 (rewards are range-checked, gamma in [0, 1), terminal reward >= 0): the cheaper cross-lane
-    // maxima (wave.hpp); MP_OPD_LOOP=0: the general ones always -- test hook, shared with mp_ropd_plan
-    const char *nn_env = getenv("MP_OPD_LOOP");
-    const bool nonneg = gamma >= 0 && gamma < 1 && terminal_reward >= 0 && !(nn_env && nn_env[0] == '0');
-    const void *kfn = expg ? (nonneg ? (const void *)opd_kernel<true, true> : (const void *)opd_kernel<true, false>)
-                           : (nonneg ? (const void *)opd_kernel<false, true> : (const void *)opd_kernel<false, false>);
-    if (!any_a && lds > 64 * 1024) MP_HIP(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 64 * 1024)
+        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     MP_TRY(kernels_begin(ctx));
-    if (any_a) hipLaunchKernelGGL(opd_any_kernel, dim3((unsigned)n_roots), dim3(64), 0, st, a);
-    else if (glb) {
-        const bool small = sib ? groups * A <= 128 : a.T <= 128; // at most two slots per lane in a re-scan
-        void (*kw)(OpdArgs) =
-            sib ? (nonneg ? (small ? opd_wide_kernel<true, true, true> : opd_wide_kernel<true, false, true>)
-                          : (small ? opd_wide_kernel<false, true, true> : opd_wide_kernel<false, false, true>))
-                : (nonneg ? (small ? opd_wide_kernel<true, true, false> : opd_wide_kernel<true, false, false>)
-                          : (small ? opd_wide_kernel<false, true, false> : opd_wide_kernel<false, false, false>));
-        hipLaunchKernelGGL(kw, dim3((unsigned)n_roots), dim3(64), lds, st, a);
-    }
-    else if (expg && nonneg) hipLaunchKernelGGL((opd_kernel<true, true>), dim3((unsigned)n_roots), dim3(64), lds, st, a);
-    else if (expg) hipLaunchKernelGGL((opd_kernel<true, false>), dim3((unsigned)n_roots), dim3(64), lds, st, a);
-    else if (nonneg) hipLaunchKernelGGL((opd_kernel<false, true>), dim3((unsigned)n_roots), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL((opd_kernel<false, false>), dim3((unsigned)n_roots), dim3(64), lds, st, a);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)n_roots), dim3(64), lds, ctx->stream, a);
     MP_TRY(kernels_end(ctx, 1));
     MP_HIP(hipGetLastError());
-
-    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n_roots * 6, rmem));
-    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n_roots * max_plan_len, mem));
-    MP_TRY(stage_out_copy(ctx, plan_len, a.plan_len, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, root_lower, a.root_lower, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, root_upper, a.root_upper, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, status, a.status, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n_roots, mem));
-    if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
-    return MP_OK;
+    return opd_unstage(ctx, n_roots, max_plan_len, mem, rmem, res, a.rng, a.out);
 }
 
 int mp_opd_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *action,
@@ -1182,78 +1089,30 @@ int mp_opd_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes,
     if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
     if (ctx->tree.kind != 2) return fail(MP_ERR_ARG, "mp_opd_tree_export: no OPD tree on this ctx");
     if (root < 0 || root >= ctx->tree.n_roots) return fail(MP_ERR_ARG, "mp_opd_tree_export: root %d out of range", root);
-    const int tcap = ctx->tree.cap, A = ctx->tree.A, K = ctx->tree.K, NR = ctx->tree.n_roots;
-    MP_HIP(hipSetDevice(ctx->device));
-    MP_HIP(hipStreamSynchronize(ctx->stream));
-    const int32_t *d_exp = (const int32_t *)ctx->ws[WS_TREE7].p;
+    const int A = ctx->tree.A;
     int32_t n = 0;
-    MP_HIP(hipMemcpy(&n, d_exp + (size_t)NR * (K > 0 ? K : 1) + root, sizeof(int32_t), hipMemcpyDeviceToHost));
-    const long base = (long)root * tcap;
-    auto pull = [&](void *dst, int slot, size_t elt) -> int {
-        MP_HIP(hipMemcpy(dst, (const char *)ctx->ws[slot].p + base * elt, (size_t)n * elt, hipMemcpyDeviceToHost));
-        return MP_OK;
-    };
-    std::vector<int32_t> fc((size_t)n, -1), exp((size_t)(K > 0 ? K : 1));
-    MP_HIP(hipMemcpy(exp.data(), d_exp + (size_t)root * (K > 0 ? K : 1), (size_t)(K > 0 ? K : 1) * sizeof(int32_t),
-                     hipMemcpyDeviceToHost));
-    // the k-th expansion created node slots 1 + kA .. 1 + kA + A - 1 under exp[k]
-    for (int k = 0; k < K && 1 + (k + 1) * A <= n; ++k)
-        if (exp[k] >= 0 && exp[k] < n) fc[exp[k]] = 1 + k * A;
+    std::vector<int32_t> exp;
+    MP_TRY(opd_pull_expanded(ctx, root, &n, exp));
     std::vector<double> up((size_t)n), rw((size_t)n);
     std::vector<OpdNode> na((size_t)n);
-    MP_TRY(pull(up.data(), WS_TREE1, sizeof(double)));
-    MP_TRY(pull(rw.data(), WS_TREE2, sizeof(double)));
-    MP_TRY(pull(na.data(), WS_TREE0, sizeof(OpdNode)));
-    std::vector<int32_t> par((size_t)n);
-    par[0] = -1;
-    for (int i = 1; i < n; ++i) par[i] = exp[(i - 1) / A];
-    // the kernel stores leaf upper bounds only (-inf marks an expanded node): U[n] = max over children,
-    // bottom-up in reverse creation order (children have larger ids than their parent)
-    for (int i = n - 1; i >= 0; --i)
-        if (fc[i] >= 0) {
-            double m = up[fc[i]];
-            for (int a = 1; a < A; ++a)
-                if (up[fc[i] + a] > m) m = up[fc[i] + a];
-            up[i] = m;
-        }
-    // slots of unavailable actions (deterministic.py:32-35) are phantoms with L = -inf: not nodes of the tree
-    std::vector<int32_t> id((size_t)n, -1);
-    int kept = 0;
-    for (int i = 0; i < n; ++i)
-        if (!(na[i].L == -INFINITY)) id[i] = kept++;
-    if (kept > cap) return fail(MP_ERR_ARG, "mp_opd_tree_export: capacity %d < %d nodes", cap, kept);
-    // deterministic.py:62-63: every node on the root..child sequence gets +1 per created child;
-    // count = 1 (initial) + size of own subtree for non-root nodes, root: 1 + #descendants
-    std::vector<int64_t> sz((size_t)n, 0);
-    for (int i = n - 1; i >= 0; --i) {
-        if (id[i] < 0) continue;
-        sz[i] += 1;
-        if (i > 0) sz[par[i]] += sz[i];
-    }
+    MP_TRY(opd_pull(ctx, WS_TREE1, root, n, sizeof(double), up.data()));
+    MP_TRY(opd_pull(ctx, WS_TREE2, root, n, sizeof(double), rw.data()));
+    MP_TRY(opd_pull(ctx, WS_TREE0, root, n, sizeof(OpdNode), na.data()));
+    // (a phantom has L = -inf)
+    const OpdSkeleton t = opd_skeleton(exp, n, A, ctx->tree.K, [&](int i) { return na[i].L == -INFINITY; }, up.data());
+    if (t.kept > cap) return fail(MP_ERR_ARG, "mp_opd_tree_export: capacity %d < %d nodes", cap, t.kept);
     for (int i = 0; i < n; ++i) {
-        if (id[i] < 0) continue;
-        const int o = id[i];
+        if (t.id[i] < 0) continue;
+        const int o = t.id[i];
         if (lower) lower[o] = na[i].L;
         if (state) state[o] = na[i].state;
         if (depth) depth[o] = na[i].depth & ((1 << 30) - 1);
         if (done) done[o] = (uint8_t)((na[i].depth >> 30) & 1);
         if (upper) upper[o] = up[i];
         if (reward) reward[o] = rw[i];
-        if (parent) parent[o] = i == 0 ? -1 : id[par[i]];
-        if (action) action[o] = i == 0 ? -1 : (i - 1) % A;
-        if (count) count[o] = i == 0 ? sz[0] : 1 + sz[i];
-        int first = -1, nc = 0;
-        if (fc[i] >= 0)
-            for (int a = 0; a < A; ++a) {
-                const int c = id[fc[i] + a];
-                if (c < 0) continue;
-                if (first < 0) first = c;
-                ++nc;
-            }
-        if (first_child) first_child[o] = first;
-        if (n_children) n_children[o] = nc;
+        t.links(i, A, parent, action, count, first_child, n_children);
     }
-    if (n_nodes) *n_nodes = kept;
+    if (n_nodes) *n_nodes = t.kept;
     return MP_OK;
 }
 

@@ -1,5 +1,7 @@
 // opd_closing.hpp -- the closing passes of the LDS-resident optimistic planners (opd_kernel, ropd_kernel): every
 // backup_to_root of the plan at once (deterministic.py:67-79) and get_plan (abstract.py:143-156), on the EXPANSION tree.
+// Also what ALL kernels of opd.hip and ropd.hip share: the struct of their output pointers (OpdOut), the tie draw of every
+// plan descent (draw_tie, draw_tie_chunks) and the wide kernels' late read of their arguments (kernargs_after_loop).
 //
 // After K expansions the final lower bound of an expanded node is the maximum of the creation-time lower bounds of the
 // LEAVES below it.  With s_k = max over the leaf children of expansion k and up(k) = the expansion that created k's node,
@@ -16,10 +18,51 @@
 //
 // LDS use (the bounds array of the main loop is dead by now): val f64[K] | link i32[K] | link' i32[K] | node->k i32[cap].
 #pragma once
+#include <stddef.h>
+
+#include "common.hpp"
 #include "pcg64.hpp"
 #include "wave.hpp"
 
 namespace mp {
+
+// The output pointers of a plan call: the tail of both argument structs (OpdArgs, ROpdArgs), each array per root.
+struct OpdOut {
+    int32_t *expanded; // [n_roots][K] node expanded at step k (= parent of nodes 1 + kA .. 1 + kA + A - 1)
+    int32_t *n_nodes_out;
+    int32_t *plans, *plan_len, *status; // (plans .. env_steps may be null: not wanted)
+    double *root_lower, *root_upper;
+    int64_t *env_steps;
+};
+
+// Node.random_argmax (abstract.py:304-311) over the set bits of `ties`: the bit the generator picks (one bounded draw for
+// two or more ties, none for one -- the ORDER of these draws is what makes plans bit-exact).  Uniform across lanes (same
+// state, same draws).
+__device__ __forceinline__ int draw_tie(unsigned long long ties, Pcg64 &gen)
+{
+    int pick = (int)gen.below((uint32_t)__popcll(ties));
+    while (pick-- > 0) ties &= ties - 1;
+    return __ffsll((long long)ties) - 1;
+}
+// the same over any number of actions, 64 at a time: tied(a) for a < n (evaluated twice per action)
+template <class Tied>
+__device__ __forceinline__ int draw_tie_chunks(int n, Tied tied, Pcg64 &gen)
+{
+    const int lane = threadIdx.x;
+    int nt = 0;
+    for (int a0 = 0; a0 < n; a0 += 64) nt += __popcll(ballot64(a0 + lane < n && tied(a0 + lane)));
+    int pick = (int)gen.below((uint32_t)nt);
+    for (int a0 = 0; a0 < n; a0 += 64) {
+        unsigned long long t = ballot64(a0 + lane < n && tied(a0 + lane));
+        const int c = __popcll(t);
+        if (pick < c) {
+            while (pick-- > 0) t &= t - 1;
+            return a0 + __ffsll((long long)t) - 1;
+        }
+        pick -= c;
+    }
+    return 0;
+}
 
 __host__ __device__ inline bool closing_compact_fits(long K, long A, long cap, long lds_bytes)
 {
@@ -163,12 +206,7 @@ __device__ __forceinline__ int closing_compact(void *lds, int K, int k_done, int
                 l = kc >= 0 ? val[kc] : loadL(fc + lane);
             }
             const double m = A <= 16 ? row0_max(l) : wave_max(l);
-            const unsigned long long ties = ballot64(lane < A && l == m);
-            const int nt = __popcll(ties);
-            int pick = (int)gen.below((uint32_t)nt); // uniform across lanes (same state, same draws)
-            unsigned long long t = ties;
-            while (pick-- > 0) t &= t - 1;
-            a = __ffsll((long long)t) - 1;
+            a = draw_tie(ballot64(lane < A && l == m), gen);
             knext = __builtin_amdgcn_readlane(kc, a);
         }
         if (lane == 0 && plan_row && len < max_plan_len) plan_row[len] = a;
@@ -183,6 +221,19 @@ __device__ __forceinline__ int closing_compact(void *lds, int K, int k_done, int
 #endif
 #undef CT
     return len;
+}
+
+// ---- the high-occupancy kernels (opd_wide_kernel, ropd_wide_kernel).  Everything only the closing passes need is read from
+// the kernel-argument segment AFTER the main loop: loaded at entry (as the compiler does with by-value arguments) those
+// pointers sit in SGPRs through the loop, which at the 80 SGPRs of 8 waves per SIMD meant 17 spill reloads per expansion (a
+// tenth of its VALU instructions).  Returns the segment as a pointer to the kernel's argument struct: every field is loaded
+// where it is first read.
+template <class Args>
+__device__ __forceinline__ const Args __attribute__((address_space(4))) *kernargs_after_loop()
+{
+    unsigned long long ka = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka)); // the loads through the result cannot move above this point
+    return (const Args __attribute__((address_space(4))) *)ka;
 }
 
 } // namespace mp

@@ -17,6 +17,7 @@
 // deferred to one bottom-up pass at the end exactly as in opd.hip -- no planning decision reads an expanded node's
 // bounds, children start from their parent's CREATION-TIME vector, and max is exact.
 // HBM per node: M x {L f64, state i32, reward f64} + {min_m L, min_m U, depth, done bits}.
+// The host side (opd_host.hpp) and the tie draws of the plan descents (opd_closing.hpp) are shared with opd.hip.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -27,6 +28,7 @@
 #include "pcg64.hpp"
 #include "wave.hpp"
 #include "opd_closing.hpp"
+#include "opd_host.hpp"
 
 namespace mp {
 
@@ -58,9 +60,6 @@ __host__ __device__ __forceinline__ double reward_plain(double r)
 }
 
 
-// (one terminal flag per model in a 32-bit word of the node; from the 33rd model on the flag rides in the sign bit of the
-// stored reward -- rewards are range-checked to [0, 1], and 0. with the flag is -0. -- so the number of models is not bounded)
-
 struct ROpdArgs {
     int n_roots, M, S, A, K, cap, done_on_next, max_plan_len;
     int T; // row length of a residue class in the upper-bound array: odd, >= ceil(cap / 64)
@@ -78,12 +77,9 @@ struct ROpdArgs {
     double *Umin;      // [n_roots][cap]    min_m U of leaves, -inf for expanded nodes (export fills those in)
     int32_t *meta;     // [n_roots][cap][2] depth, done bits
     double *leaf_global; // [n_roots][64 * T] upper-bound array of the high-occupancy variant (else nullptr)
-    int32_t *expanded; // [n_roots][K]
-    int32_t *n_nodes_out;
-    int32_t *plans, *plan_len, *status;
-    double *root_lower, *root_upper;
-    int64_t *env_steps;
+    OpdOut out; // (the wide kernel reads it from the kernel-argument segment: the layout is part of its code)
 };
+static_assert(offsetof(ROpdArgs, out) == 160 && sizeof(ROpdArgs) == 224, "ROpdArgs: the kernel-argument layout changed");
 
 // ropd_kernel<EXPG = false>: upper-bound array and parent map in LDS (44 KB per root at budget 5000: 3 roots per CU);
 // ropd_kernel<EXPG = true>: the parent map in HBM (40 448 B: 4 roots per CU, so a 1024-root batch stays on this
@@ -94,7 +90,7 @@ __global__ __launch_bounds__(64) void ropd_kernel(ROpdArgs p)
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int T = p.T;
     double *leafU = lds;
-    int32_t *exp_lds = EXPG ? p.expanded + (long)blockIdx.x * (p.K > 0 ? p.K : 1) : reinterpret_cast<int32_t *>(lds + 64 * T);
+    int32_t *exp_lds = EXPG ? p.out.expanded + (long)blockIdx.x * (p.K > 0 ? p.K : 1) : reinterpret_cast<int32_t *>(lds + 64 * T);
 #define LU(id) leafU[((id) & 63) * T + ((id) >> 6)]
     const int lane = threadIdx.x, root = blockIdx.x, A = p.A, M = p.M;
     const long base = (long)root * p.cap, SA = (long)p.S * A;
@@ -356,7 +352,7 @@ __global__ __launch_bounds__(64) void ropd_kernel(ROpdArgs p)
             // pointer jumping over the expansion tree + a prepared plan walk, on the scalars min_m L (opd_closing.hpp)
             len = closing_compact(lds, p.K, k_done, n_nodes, A, exp_lds, [&](int id) { return Lmin[id]; },
                                   [&](int id, double v) { Lmin[id] = v; }, gen,
-                                  p.plans ? p.plans + (long)root * p.max_plan_len : nullptr, p.max_plan_len, root_lower);
+                                  p.out.plans ? p.out.plans + (long)root * p.max_plan_len : nullptr, p.max_plan_len, root_lower);
         } else {
             for (int i = lane; i < n_nodes; i += 64) LU(i) = Lmin[i];
             __syncthreads();
@@ -401,13 +397,8 @@ __global__ __launch_bounds__(64) void ropd_kernel(ROpdArgs p)
                 const double l = lane < A ? Lmin[fc + lane] : ninf;
                 const double slot = lane < A ? LU(fc + lane) : 0.0;
                 const double m = A <= 16 ? row0_max(l) : wave_max(l);
-                const unsigned long long ties = ballot64(lane < A && l == m);
-                const int nt = __popcll(ties);
-                int pick = (int)gen.below((uint32_t)nt);
-                unsigned long long t = ties;
-                while (pick-- > 0) t &= t - 1;
-                const int a = __ffsll((long long)t) - 1;
-                if (lane == 0 && p.plans && len < p.max_plan_len) p.plans[(long)root * p.max_plan_len + len] = a;
+                const int a = draw_tie(ballot64(lane < A && l == m), gen);
+                if (lane == 0 && p.out.plans && len < p.max_plan_len) p.out.plans[(long)root * p.max_plan_len + len] = a;
                 ++len;
                 const int shi = __builtin_amdgcn_readlane(__double2hiint(slot), a), slo = __builtin_amdgcn_readlane(__double2loint(slot), a);
                 kcur = ((unsigned)shi == 0xFFF80000u) ? slo : -1; // expanded: its k; a leaf: the plan ends
@@ -415,26 +406,26 @@ __global__ __launch_bounds__(64) void ropd_kernel(ROpdArgs p)
         }
         if (lane == 0) {
             gen.store(p.rng + (long)root * 6);
-            if (p.plans)
-                for (int i = len; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
-            if (p.plan_len) p.plan_len[root] = len;
-            if (p.root_lower) p.root_lower[root] = root_lower;
-            if (p.root_upper) p.root_upper[root] = root_upper;
+            if (p.out.plans)
+                for (int i = len; i < p.max_plan_len; ++i) p.out.plans[(long)root * p.max_plan_len + i] = -1;
+            if (p.out.plan_len) p.out.plan_len[root] = len;
+            if (p.out.root_lower) p.out.root_lower[root] = root_lower;
+            if (p.out.root_upper) p.out.root_upper[root] = root_upper;
         }
     } else if (lane == 0) {
-        if (p.plans)
-            for (int i = 0; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
-        if (p.plan_len) p.plan_len[root] = 0;
+        if (p.out.plans)
+            for (int i = 0; i < p.max_plan_len; ++i) p.out.plans[(long)root * p.max_plan_len + i] = -1;
+        if (p.out.plan_len) p.out.plan_len[root] = 0;
     }
     if (lane == 0) {
-        if (p.status) p.status[root] = status;
-        if (p.env_steps) p.env_steps[root] = (int64_t)real_steps; // one joint step per (real) child (deterministic.py:41)
-        p.n_nodes_out[root] = n_nodes;
+        if (p.out.status) p.out.status[root] = status;
+        if (p.out.env_steps) p.out.env_steps[root] = (int64_t)real_steps; // one joint step per (real) child (deterministic.py:41)
+        p.out.n_nodes_out[root] = n_nodes;
     }
     if (EXPG) {
-        for (int k = k_done + lane; k < p.K; k += 64) p.expanded[(long)root * p.K + k] = -1;
+        for (int k = k_done + lane; k < p.K; k += 64) p.out.expanded[(long)root * p.K + k] = -1;
     } else {
-        for (int k = lane; k < p.K; k += 64) p.expanded[(long)root * p.K + k] = k < k_done ? exp_lds[k] : -1;
+        for (int k = lane; k < p.K; k += 64) p.out.expanded[(long)root * p.K + k] = k < k_done ? exp_lds[k] : -1;
     }
 #undef LU
 }
@@ -583,15 +574,10 @@ __global__ __launch_bounds__(64, 8) void ropd_wide_kernel(ROpdArgs p)
     }
     __syncthreads();
 
-    const ROpdArgs __attribute__((address_space(4))) *q; // closing-only arguments: read here, not held through the loop
-    {
-        unsigned long long ka = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ka));
-        q = (const ROpdArgs __attribute__((address_space(4))) *)ka;
-    }
+    const auto *q = kernargs_after_loop<ROpdArgs>(); // what only the closing passes need (opd_closing.hpp)
     double *Umin = q->Umin + base;
-    int32_t *exp_map = q->expanded + (long)root * (q->K > 0 ? q->K : 1);
-    int32_t *const plans = q->plans, *const plan_len = q->plan_len;
+    int32_t *exp_map = q->out.expanded + (long)root * (q->K > 0 ? q->K : 1);
+    int32_t *const plans = q->out.plans, *const plan_len = q->out.plan_len;
     const int max_plan_len = q->max_plan_len;
 
     double root_upper = ninf;
@@ -653,12 +639,7 @@ __global__ __launch_bounds__(64, 8) void ropd_wide_kernel(ROpdArgs p)
             const double l = lane < A ? Lmin[fc + lane] : ninf;
             const double slot = lane >= A ? 0.0 : SIB ? leafU[((kcur + 1) & 63) * T + ((kcur + 1) >> 6) * A + lane] : LU(fc + lane);
             const double m = A <= 16 ? row0_max(l) : wave_max(l);
-            const unsigned long long ties = ballot64(lane < A && l == m);
-            const int nt = __popcll(ties);
-            int pick = (int)gen.below((uint32_t)nt);
-            unsigned long long t = ties;
-            while (pick-- > 0) t &= t - 1;
-            const int a = __ffsll((long long)t) - 1;
+            const int a = draw_tie(ballot64(lane < A && l == m), gen);
             if (lane == 0 && plans && len < max_plan_len) plans[(long)root * max_plan_len + len] = a;
             ++len;
             const int shi = __builtin_amdgcn_readlane(__double2hiint(slot), a), slo = __builtin_amdgcn_readlane(__double2loint(slot), a);
@@ -669,8 +650,8 @@ __global__ __launch_bounds__(64, 8) void ropd_wide_kernel(ROpdArgs p)
             if (plans)
                 for (int i = len; i < max_plan_len; ++i) plans[(long)root * max_plan_len + i] = -1;
             if (plan_len) plan_len[root] = len;
-            if (q->root_lower) q->root_lower[root] = Lmin[0];
-            if (q->root_upper) q->root_upper[root] = root_upper;
+            if (q->out.root_lower) q->out.root_lower[root] = Lmin[0];
+            if (q->out.root_upper) q->out.root_upper[root] = root_upper;
         }
     } else if (lane == 0) {
         if (plans)
@@ -678,9 +659,9 @@ __global__ __launch_bounds__(64, 8) void ropd_wide_kernel(ROpdArgs p)
         if (plan_len) plan_len[root] = 0;
     }
     if (lane == 0) {
-        if (q->status) q->status[root] = status;
-        if (q->env_steps) q->env_steps[root] = (int64_t)real_steps;
-        q->n_nodes_out[root] = n_nodes;
+        if (q->out.status) q->out.status[root] = status;
+        if (q->out.env_steps) q->out.env_steps[root] = (int64_t)real_steps;
+        q->out.n_nodes_out[root] = n_nodes;
     }
     for (int k = k_done + lane; k < q->K; k += 64) exp_map[k] = -1;
 #undef LU
@@ -694,7 +675,7 @@ __global__ __launch_bounds__(64) void ropd_any_kernel(ROpdArgs p)
     const long base = (long)root * p.cap, SA = (long)p.S * A;
     double *Lv = p.Lv + base * M, *Rv = p.Rv + base * M, *Lmin = p.Lmin + base, *Umin = p.Umin + base;
     int32_t *Sv = p.Sv + base * M, *meta = p.meta + base * 2;
-    int32_t *EXP = p.expanded + (long)root * (p.K > 0 ? p.K : 1);
+    int32_t *EXP = p.out.expanded + (long)root * (p.K > 0 ? p.K : 1);
     const uint32_t done_bit = p.done_on_next ? 2u : 1u;
     const double ninf = -INFINITY;
     if (lane == 0) {
@@ -796,40 +777,28 @@ __global__ __launch_bounds__(64) void ropd_any_kernel(ROpdArgs p)
                 m = l > m ? l : m;
             }
             m = wave_max(m);
-            int nt = 0;
-            for (int a0 = 0; a0 < A; a0 += 64) nt += __popcll(ballot64(a0 + lane < A && Lmin[fc + a0 + lane] == m));
-            int pick = (int)gen.below((uint32_t)nt), act = 0;
-            for (int a0 = 0; a0 < A; a0 += 64) {
-                unsigned long long t = ballot64(a0 + lane < A && Lmin[fc + a0 + lane] == m);
-                const int c = __popcll(t);
-                if (pick < c) {
-                    while (pick-- > 0) t &= t - 1;
-                    act = a0 + __ffsll((long long)t) - 1;
-                    break;
-                }
-                pick -= c;
-            }
-            if (lane == 0 && p.plans && len < p.max_plan_len) p.plans[(long)root * p.max_plan_len + len] = act;
+            const int act = draw_tie_chunks(A, [&](int a) { return Lmin[fc + a] == m; }, gen);
+            if (lane == 0 && p.out.plans && len < p.max_plan_len) p.out.plans[(long)root * p.max_plan_len + len] = act;
             ++len;
             node = fc + act;
         }
         if (lane == 0) {
             gen.store(p.rng + (long)root * 6);
-            if (p.plans)
-                for (int i = len; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
-            if (p.plan_len) p.plan_len[root] = len;
-            if (p.root_lower) p.root_lower[root] = Lmin[0];
-            if (p.root_upper) p.root_upper[root] = root_upper;
+            if (p.out.plans)
+                for (int i = len; i < p.max_plan_len; ++i) p.out.plans[(long)root * p.max_plan_len + i] = -1;
+            if (p.out.plan_len) p.out.plan_len[root] = len;
+            if (p.out.root_lower) p.out.root_lower[root] = Lmin[0];
+            if (p.out.root_upper) p.out.root_upper[root] = root_upper;
         }
     } else if (lane == 0) {
-        if (p.plans)
-            for (int i = 0; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = -1;
-        if (p.plan_len) p.plan_len[root] = 0;
+        if (p.out.plans)
+            for (int i = 0; i < p.max_plan_len; ++i) p.out.plans[(long)root * p.max_plan_len + i] = -1;
+        if (p.out.plan_len) p.out.plan_len[root] = 0;
     }
     if (lane == 0) {
-        if (p.status) p.status[root] = status;
-        if (p.env_steps) p.env_steps[root] = (int64_t)real_steps;
-        p.n_nodes_out[root] = n_nodes;
+        if (p.out.status) p.out.status[root] = status;
+        if (p.out.env_steps) p.out.env_steps[root] = (int64_t)real_steps;
+        p.out.n_nodes_out[root] = n_nodes;
     }
     for (int k = k_done + lane; k < p.K; k += 64) EXP[k] = -1;
 }
@@ -851,54 +820,31 @@ int mp_ropd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     if (model->mode != MP_MODE_DETERMINISTIC || !model->rec_all)
         return fail(MP_ERR_MODE, "mp_ropd_plan: needs a joint model (mp_model_load_joint)");
     const int A = model->A, M = model->M;
-    const bool any_a = A > 64; // more actions than lanes: the plain kernel (ropd_any_kernel)
     if (n_roots < 1 || budget < 0 || max_plan_len < 0) return fail(MP_ERR_ARG, "mp_ropd_plan: bad sizes");
-    const int K = budget / A; // deterministic.py:118
-    if (K > 0 && !(gamma != 1.0))
+    const OpdShape s = opd_shape(ctx, A, budget, n_roots, gamma, terminal_reward); // (the forms and test hooks of mp_opd_plan)
+    if (s.K > 0 && !(gamma != 1.0))
         return fail(MP_ERR_ARG, "mp_ropd_plan: gamma = 1 (the reference divides by 1 - gamma, deterministic.py:53)");
-    const long cap = 1 + (long)K * A;
-    const int T = (int)((cap + 63) / 64) | 1;
-    const size_t lds_bounds = (size_t)64 * T * sizeof(double); // bounds only, parent map in HBM (EXPG)
-    const size_t lds_full = lds_bounds + (size_t)(K > 0 ? K : 1) * sizeof(int32_t);
-    int chunk = 64; // high-occupancy variant: LDS only holds the window of the closing pass
-    while (chunk > 1 && (size_t)chunk * A * sizeof(double) > 4096) chunk >>= 1;
-    const size_t lds_win = (size_t)chunk * A * sizeof(double);
-    const char *force = getenv("MP_OPD_MODEL"); // "lds" / "ldsx" / "global": test hook (shared with mp_opd_plan)
-    const long cus = ctx->prop.multiProcessorCount;
-    const long lds_roots = cus * (long)((kLdsBytes - 1024) / lds_full);
-    const long expg_roots = cus * (long)((kLdsBytes - 1024) / lds_bounds);
-    bool glb = lds_bounds > kLdsBytes - 1024 || n_roots > expg_roots;
-    if (force && force[0] == 'g') glb = true;
-    if (force && force[0] == 'l' && lds_bounds <= kLdsBytes - 1024) glb = false;
-    bool expg = !glb && (lds_full > kLdsBytes - 1024 || n_roots > lds_roots);
-    if (force && !glb && force[1] == 'd' && force[2] == 's' && force[3] == 'x') expg = true;
-    const size_t lds = glb ? lds_win : (expg ? lds_bounds : lds_full);
     MP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-
-    const int D = K + 2;
-    std::vector<double> tab((size_t)3 * D);
-    for (int d = 0; d < D; ++d) { // host libm, bit-equal to Python's float ** (as in mp_opd_plan)
-        tab[d] = d >= 1 ? pow(gamma, (double)(d - 1)) : 0.0;
-        tab[D + d] = pow(gamma, (double)d) / (1 - gamma);
-        tab[2 * D + d] = terminal_reward * pow(gamma, (double)d) / (1 - gamma);
-    }
-    double *d_tab = nullptr;
-    MP_TRY(upload_tables(ctx, 2, tab, &d_tab));
 
     ROpdArgs a;
-    // high-occupancy variant: the sibling layout of its bounds array (default; MP_OPD_WIDE=cls: the residue-class layout), see opd.hip
-    int lgP = 0;
-    while ((1 << lgP) < A) ++lgP;
-    const int Tsib = ((K + 1 + 63) / 64) * A + 16;
-    const char *wide_env = getenv("MP_OPD_WIDE");
-    const bool sib = !(wide_env && wide_env[0] == 'c');
-    a.n_roots = n_roots; a.M = M; a.S = model->S; a.A = A; a.K = K; a.cap = (int)cap; a.T = T; a.chunk = chunk; a.Tsib = Tsib; a.lgP = lgP;
-    { const char *cl = getenv("MP_OPD_CLOSING"); a.closing_chain = cl && cl[0] == 'c'; }
+    a.n_roots = n_roots; a.M = M; a.S = model->S; a.A = A; a.K = s.K; a.cap = s.cap; a.T = s.T; a.chunk = s.chunk; a.Tsib = s.Tsib; a.lgP = s.lgP;
+    a.closing_chain = s.closing_chain;
     a.done_on_next = model->done_on_next; a.max_plan_len = max_plan_len;
     a.rec = model->rec_all;
-    a.g1 = d_tab; a.gdiv = d_tab + D; a.tdiv = d_tab + 2 * D;
-    const size_t nn = (size_t)n_roots * cap;
+    MP_TRY(opd_gamma_tables(ctx, s.K, gamma, terminal_reward, &a.g1, &a.gdiv, &a.tdiv));
+    // the form: more actions than lanes -> the plain kernel; else LDS-resident or wide (opd_shape); the LDS-resident main loop in
+    // its batched-load form for <= 2 / <= 4 models when every finite bound is >= +0.0, else the generic one
+    typedef void (*kernel_t)(ROpdArgs);
+    static const kernel_t lds_form[2][3] = {{ropd_kernel<false, 0>, ropd_kernel<false, 2>, ropd_kernel<false, 4>}, // [expg][models]
+                                            {ropd_kernel<true, 0>, ropd_kernel<true, 2>, ropd_kernel<true, 4>}};
+    static const kernel_t wide_form[2][2] = {{ropd_wide_kernel<false, false>, ropd_wide_kernel<true, false>},      // [sib][nonneg]
+                                             {ropd_wide_kernel<false, true>, ropd_wide_kernel<true, true>}};
+    const bool any_a = A > 64;
+    const int mb = !s.nonneg || M > 4 ? 0 : M <= 2 ? 1 : 2;
+    const kernel_t kfn = any_a ? ropd_any_kernel : s.glb ? wide_form[s.sib][s.nonneg] : lds_form[s.expg][mb];
+    const size_t lds = any_a ? 0 : s.lds();
+
+    const size_t nn = (size_t)n_roots * s.cap;
     MP_TRY(ws_get(ctx, WS_TREE0, nn * M, &a.Lv));
     MP_TRY(ws_get(ctx, WS_TREE1, nn * M, &a.Sv));
     MP_TRY(ws_get(ctx, WS_TREE2, nn, &a.Lmin));
@@ -906,53 +852,23 @@ int mp_ropd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(ws_get(ctx, WS_TREE4, nn * M, &a.Rv));
     MP_TRY(ws_get(ctx, WS_TREE5, nn * 2, &a.meta));
     a.leaf_global = nullptr;
-    if (glb && !any_a) MP_TRY(ws_get(ctx, WS_TREE6, (size_t)n_roots * 64 * (sib ? Tsib : T), &a.leaf_global));
-    MP_TRY(ws_get(ctx, WS_TREE7, (size_t)n_roots * (K > 0 ? K : 1) + n_roots, &a.expanded));
-    a.n_nodes_out = a.expanded + (size_t)n_roots * (K > 0 ? K : 1);
-    ctx->tree.kind = 3; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap; ctx->tree.K = K;
+    if (s.glb && !any_a) MP_TRY(ws_get(ctx, WS_TREE6, (size_t)n_roots * 64 * (s.sib ? s.Tsib : s.T), &a.leaf_global));
+    ctx->tree.kind = 3; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = s.cap; ctx->tree.K = s.K;
     ctx->tree.M = M; ctx->tree.gamma = gamma;
 
+    const OpdResults res = {rng_state, plans, plan_len, root_lower, root_upper, env_steps, status};
     int32_t *d_rs = nullptr;
     MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n_roots * M, mem, &d_rs));
     a.root_state = d_rs;
-    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n_roots * 6, rmem, &a.rng));
-    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n_roots * max_plan_len, mem, &a.plans));
-    MP_TRY(stage_out_alloc(ctx, WS_IO4, plan_len, (size_t)n_roots, mem, &a.plan_len));
-    MP_TRY(stage_out_alloc(ctx, WS_IO5, root_lower, (size_t)n_roots, mem, &a.root_lower));
-    MP_TRY(stage_out_alloc(ctx, WS_IO6, root_upper, (size_t)n_roots, mem, &a.root_upper));
-    MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
-    MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, mem, &a.env_steps));
+    MP_TRY(opd_stage(ctx, s, n_roots, max_plan_len, mem, rmem, res, &a.rng, &a.out));
 
-    // main loop: the batched-load form for <= 2 / <= 4 models when every finite bound is >= +0.0, else the generic one
-    // (MP_OPD_LOOP=0: the generic one always -- test hook, shared with mp_opd_plan)
-    const char *mode_env = getenv("MP_OPD_LOOP");
-    int mb = gamma >= 0 && gamma < 1 && terminal_reward >= 0 && !(mode_env && mode_env[0] == '0') ? (M <= 2 ? 2 : M <= 4 ? 4 : 0) : 0;
-    typedef void (*kernel_t)(ROpdArgs);
-    const kernel_t kfn = expg ? (mb == 2 ? ropd_kernel<true, 2> : mb == 4 ? ropd_kernel<true, 4> : ropd_kernel<true, 0>)
-                              : (mb == 2 ? ropd_kernel<false, 2> : mb == 4 ? ropd_kernel<false, 4> : ropd_kernel<false, 0>);
-    if (!any_a && lds > 64 * 1024)
+    if (lds > 64 * 1024)
         MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     MP_TRY(kernels_begin(ctx));
-    const bool nonneg = gamma >= 0 && gamma < 1 && terminal_reward >= 0 && !(mode_env && mode_env[0] == '0');
-    if (any_a) hipLaunchKernelGGL(ropd_any_kernel, dim3((unsigned)n_roots), dim3(64), 0, st, a);
-    else if (glb) {
-        const kernel_t kw = sib ? (nonneg ? ropd_wide_kernel<true, true> : ropd_wide_kernel<false, true>)
-                                : (nonneg ? ropd_wide_kernel<true, false> : ropd_wide_kernel<false, false>);
-        hipLaunchKernelGGL(kw, dim3((unsigned)n_roots), dim3(64), lds, st, a);
-    }
-    else hipLaunchKernelGGL(kfn, dim3((unsigned)n_roots), dim3(64), lds, st, a);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)n_roots), dim3(64), lds, ctx->stream, a);
     MP_TRY(kernels_end(ctx, 1));
     MP_HIP(hipGetLastError());
-
-    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n_roots * 6, rmem));
-    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n_roots * max_plan_len, mem));
-    MP_TRY(stage_out_copy(ctx, plan_len, a.plan_len, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, root_lower, a.root_lower, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, root_upper, a.root_upper, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, status, a.status, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n_roots, mem));
-    if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
-    return MP_OK;
+    return opd_unstage(ctx, n_roots, max_plan_len, mem, rmem, res, a.rng, a.out);
 }
 
 int mp_ropd_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *action,
@@ -962,70 +878,30 @@ int mp_ropd_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
     if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
     if (ctx->tree.kind != 3) return fail(MP_ERR_ARG, "mp_ropd_tree_export: no robust OPD tree on this ctx");
     if (root < 0 || root >= ctx->tree.n_roots) return fail(MP_ERR_ARG, "mp_ropd_tree_export: root %d out of range", root);
-    const int tcap = ctx->tree.cap, A = ctx->tree.A, K = ctx->tree.K, NR = ctx->tree.n_roots, M = ctx->tree.M;
+    const int A = ctx->tree.A, M = ctx->tree.M;
     const double gamma = ctx->tree.gamma;
-    MP_HIP(hipSetDevice(ctx->device));
-    MP_HIP(hipStreamSynchronize(ctx->stream));
-    const int32_t *d_exp = (const int32_t *)ctx->ws[WS_TREE7].p;
     int32_t n = 0;
-    MP_HIP(hipMemcpy(&n, d_exp + (size_t)NR * (K > 0 ? K : 1) + root, sizeof(int32_t), hipMemcpyDeviceToHost));
-    const long base = (long)root * tcap;
-    auto pull = [&](void *dst, int slot, size_t elt) -> int {
-        MP_HIP(hipMemcpy(dst, (const char *)ctx->ws[slot].p + base * elt, (size_t)n * elt, hipMemcpyDeviceToHost));
-        return MP_OK;
-    };
+    std::vector<int32_t> exp;
+    MP_TRY(opd_pull_expanded(ctx, root, &n, exp));
     std::vector<double> lv((size_t)n * M), rv((size_t)n * M), lmin((size_t)n), umin((size_t)n);
-    std::vector<int32_t> sv((size_t)n * M), meta((size_t)n * 2), fc((size_t)n, -1), exp((size_t)(K > 0 ? K : 1)), par((size_t)n);
-    MP_TRY(pull(lv.data(), WS_TREE0, sizeof(double) * M));
-    MP_TRY(pull(sv.data(), WS_TREE1, sizeof(int32_t) * M));
-    MP_TRY(pull(lmin.data(), WS_TREE2, sizeof(double)));
-    MP_TRY(pull(umin.data(), WS_TREE3, sizeof(double)));
-    MP_TRY(pull(rv.data(), WS_TREE4, sizeof(double) * M));
-    MP_TRY(pull(meta.data(), WS_TREE5, sizeof(int32_t) * 2));
-    MP_HIP(hipMemcpy(exp.data(), d_exp + (size_t)root * (K > 0 ? K : 1), (size_t)(K > 0 ? K : 1) * sizeof(int32_t),
-                     hipMemcpyDeviceToHost));
-    for (int k = 0; k < K && 1 + (k + 1) * A <= n; ++k)
-        if (exp[k] >= 0 && exp[k] < n) fc[exp[k]] = 1 + k * A;
-    par[0] = -1;
-    for (int i = 1; i < n; ++i) par[i] = exp[(i - 1) / A];
-    for (int i = n - 1; i >= 0; --i) // expanded nodes: U = max over children of their scalar (bottom-up)
-        if (fc[i] >= 0) {
-            double m = umin[fc[i]];
-            for (int a = 1; a < A; ++a)
-                if (umin[fc[i] + a] > m) m = umin[fc[i] + a];
-            umin[i] = m;
-        }
-    // slots of actions no model lists (deterministic.py:32-35 over JointEnv.get_available_actions) are phantoms with
-    // min L = -inf: not nodes of the tree
-    std::vector<int32_t> id((size_t)n, -1);
-    int kept = 0;
-    for (int i = 0; i < n; ++i)
-        if (!(lmin[i] == -INFINITY)) id[i] = kept++;
-    if (kept > cap) return fail(MP_ERR_ARG, "mp_ropd_tree_export: capacity %d < %d nodes", cap, kept);
-    std::vector<int64_t> sz((size_t)n, 0);
-    for (int i = n - 1; i >= 0; --i) {
-        if (id[i] < 0) continue;
-        sz[i] += 1;
-        if (i > 0) sz[par[i]] += sz[i];
-    }
+    std::vector<int32_t> sv((size_t)n * M), meta((size_t)n * 2);
+    MP_TRY(opd_pull(ctx, WS_TREE0, root, n, sizeof(double) * M, lv.data()));
+    MP_TRY(opd_pull(ctx, WS_TREE1, root, n, sizeof(int32_t) * M, sv.data()));
+    MP_TRY(opd_pull(ctx, WS_TREE2, root, n, sizeof(double), lmin.data()));
+    MP_TRY(opd_pull(ctx, WS_TREE3, root, n, sizeof(double), umin.data()));
+    MP_TRY(opd_pull(ctx, WS_TREE4, root, n, sizeof(double) * M, rv.data()));
+    MP_TRY(opd_pull(ctx, WS_TREE5, root, n, sizeof(int32_t) * 2, meta.data()));
+    // (a phantom -- an action no model lists, JointEnv.get_available_actions -- has min L = -inf; an expanded node's U is
+    // the max over its children's scalars)
+    const OpdSkeleton t = opd_skeleton(exp, n, A, ctx->tree.K, [&](int i) { return lmin[i] == -INFINITY; }, umin.data());
+    if (t.kept > cap) return fail(MP_ERR_ARG, "mp_ropd_tree_export: capacity %d < %d nodes", cap, t.kept);
     for (int i = 0; i < n; ++i) {
-        if (id[i] < 0) continue;
-        const int o = id[i];
+        if (t.id[i] < 0) continue;
+        const int o = t.id[i];
         const int d = meta[2 * i];
-        if (parent) parent[o] = i == 0 ? -1 : id[par[i]];
-        if (action) action[o] = i == 0 ? -1 : (i - 1) % A;
+        const bool expanded = t.fc[i] >= 0;
         if (depth) depth[o] = d;
-        if (count) count[o] = i == 0 ? sz[0] : 1 + sz[i];
-        int first = -1, nc = 0;
-        if (fc[i] >= 0)
-            for (int a = 0; a < A; ++a) {
-                const int c = id[fc[i] + a];
-                if (c < 0) continue;
-                if (first < 0) first = c;
-                ++nc;
-            }
-        if (first_child) first_child[o] = first;
-        if (n_children) n_children[o] = nc;
+        t.links(i, A, parent, action, count, first_child, n_children);
         for (int m = 0; m < M; ++m) {
             const size_t j = (size_t)i * M + m, jo = (size_t)o * M + m;
             const bool dn = m < 32 ? (((uint32_t)meta[2 * i + 1] >> m) & 1u) != 0 : reward_done(rv[j]);
@@ -1034,11 +910,11 @@ int mp_ropd_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
             if (done) done[jo] = (uint8_t)dn;
             // a leaf keeps its vectors (U recomputed as update() computed it, deterministic.py:51-59: same host
             // operations as the planning tables); an expanded node holds the backed-up scalars
-            if (lower) lower[jo] = fc[i] >= 0 ? lmin[i] : lv[j];
-            if (upper) upper[jo] = fc[i] >= 0 ? umin[i] : (i == 0 ? 0.0 : (dn ? lv[j] : lv[j] + pow(gamma, (double)d) / (1 - gamma)));
+            if (lower) lower[jo] = expanded ? lmin[i] : lv[j];
+            if (upper) upper[jo] = expanded ? umin[i] : (i == 0 ? 0.0 : (dn ? lv[j] : lv[j] + pow(gamma, (double)d) / (1 - gamma)));
         }
     }
-    if (n_nodes) *n_nodes = kept;
+    if (n_nodes) *n_nodes = t.kept;
     return MP_OK;
 }
 

@@ -2,6 +2,7 @@
 """Build-time check of hand-counted `s_waitcnt vmcnt(N)` sites (rl_agents_amd/csrc/opd.hip: OPD_LEAF_SLOAD).
 
     python tools/check_isa.py rl_agents_amd/lib/opd.o
+    python tools/check_isa.py --diff old.o new.o      (what a change did to every kernel's code: see diff())
 
 Every `s_waitcnt vmcnt(N)` that is directly followed by `s_load_dwordx4 ... glc` must be preceded -- walking the listing
 backwards -- by exactly N - 1 `global_load_dwordx2` (the row loads of this expansion) and then one `global_store_dwordx2` (the
@@ -19,7 +20,7 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 VMEM = re.compile(r"^\s*(global_|buffer_|flat_|scratch_)(load|store|atomic)\w*")
 
 
-def device_listing(obj):
+def device_listing(obj, flags=()):
     """Disassembly of the gfx950 code object bundled in a hipcc object file."""
     with tempfile.TemporaryDirectory() as tmp:
         local = os.path.join(tmp, os.path.basename(obj))
@@ -28,7 +29,7 @@ def device_listing(obj):
         dev = [f for f in os.listdir(tmp) if "amdgcn" in f]
         if not dev:
             raise RuntimeError("no device code object in " + obj)
-        return subprocess.run([OBJDUMP, "-d", os.path.join(tmp, dev[0])], stdout=subprocess.PIPE, check=True).stdout.decode()
+        return subprocess.run([OBJDUMP, "-d", *flags, os.path.join(tmp, dev[0])], stdout=subprocess.PIPE, check=True).stdout.decode()
 
 
 def check(obj, min_sites=1):
@@ -59,5 +60,42 @@ def check(obj, min_sites=1):
     return sites
 
 
+def kernels(obj):
+    """{symbol: [instruction, ...]} of an object's device code, without addresses, encodings and branch targets."""
+    out, cur = {}, None
+    for ln in device_listing(obj, ["--no-show-raw-insn"]).splitlines():
+        m = re.match(r"[0-9a-f]+ <(\w+)>:$", ln)
+        ln = ln.split("//")[0].strip()
+        if m:
+            cur = out.setdefault(m.group(1), [])
+        elif cur is not None and ln and ln not in ("s_code_end", "..."):   # ("...": objdump's mark for zero padding)
+            cur.append(re.sub(r"^(s_c?branch\w*) .*", r"\1", ln))
+    return out
+
+
+def blank(insn):
+    """The instruction with its register numbers blanked (v12 -> v, s[4:5] -> s[])."""
+    return re.sub(r"\b([vsa])(\d+|\[\d+:\d+\])", lambda m: m.group(1) + ("[]" if "[" in m.group(2) else ""), insn)
+
+
+def diff(old, new):
+    """Per kernel symbol of two objects: the instruction counts and "identical", or the index of the first differing
+    instruction as printed and with register numbers blanked ("-" = none: only the register allocation differs)."""
+    a, b = kernels(old), kernels(new)
+
+    def first(x, y):
+        i = next((i for i, (p, q) in enumerate(zip(x, y)) if p != q), min(len(x), len(y)))
+        return "-" if i == len(x) == len(y) else str(i)
+    rows = ["{:<72} {:>6} {:>6}  {}".format("kernel", "old", "new", "first difference (as printed / registers blanked)")]
+    for sym in sorted(set(a) | set(b)):
+        x, y = a.get(sym, []), b.get(sym, [])
+        what = "identical" if x == y else first(x, y) + " / " + first([blank(i) for i in x], [blank(i) for i in y])
+        rows.append("{:<72} {:>6} {:>6}  {}".format(sym, len(x), len(y), what))
+    return "\n".join(rows)
+
+
 if __name__ == "__main__":
-    print("{} site(s) ok".format(check(sys.argv[1])))
+    if sys.argv[1] == "--diff":
+        print(diff(sys.argv[2], sys.argv[3]))
+    else:
+        print("{} site(s) ok".format(check(sys.argv[1])))

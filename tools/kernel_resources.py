@@ -25,11 +25,11 @@ def main():
         m = re.search(r"remark:\s+([^:]+?): (\d+)", line)
         if m and cur is not None:
             cur[m.group(1).strip()] = int(m.group(2))
-    print("{:<90} {:>5} {:>5} {:>7} {:>7} {:>4} {:>7}".format("kernel", "VGPR", "AGPR", "spillV", "scratch", "occ", "LDS"))
+    print("{:<90} {:>5} {:>5} {:>5} {:>7} {:>7} {:>7} {:>4} {:>7}".format("kernel", "VGPR", "AGPR", "SGPR", "spillV", "spillS", "scratch", "occ", "LDS"))
     for r in rows:
         if flt in r["name"]:
-            print("{:<90} {:>5} {:>5} {:>7} {:>7} {:>4} {:>7}".format(
-                r["name"][:90], r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("VGPRs Spill", -1),
+            print("{:<90} {:>5} {:>5} {:>5} {:>7} {:>7} {:>7} {:>4} {:>7}".format(
+                r["name"][:90], r.get("VGPRs", -1), r.get("AGPRs", -1), r.get("TotalSGPRs", r.get("SGPRs", -1)), r.get("VGPRs Spill", -1), r.get("SGPRs Spill", -1),
                 r.get("ScratchSize [bytes/lane]", -1), r.get("Occupancy [waves/SIMD]", -1), r.get("LDS Size [bytes/block]", -1)))
 
 
