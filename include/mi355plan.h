@@ -510,6 +510,35 @@ int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
                         int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *value_upper,
                         uint8_t *done, int32_t *state);
 
+/* ---------------------------------------------------------------- BRUE ---------------------- */
+/*
+ * BRUE.plan (tree_search/brue.py:66-71) for n_roots independent roots of a deterministic table, dense or sparse model: while
+ * the budget lasts, one rollout (:24-33) -- one generator draw state.seed(np_random.randint(2**30)) (:25, made for every
+ * model), then up to `horizon` steps of a uniformly random action (np_random.randint(|A|), :27: every action, whatever the
+ * env lists as available), each spending one unit of budget, until a step reports done (= terminated, by the model's done
+ * rule; the step limit plays no part) -- and `update` (:35-50): DecisionNode / ChanceNode.get_child (:93-96, :113-116,
+ * children in creation order), then from the last step up the running means of DecisionNode.update (:84-86) and
+ * ChanceNode.update (:106-108) on reward + gamma * estimate(next) (:52-64: the first chance child of maximal value, an outcome
+ * drawn with np_random.choice(..., p=counts / counts.sum()), one double even for a single child).  A dense / sparse model's
+ * step draws one double from the clone's own generator, Generator(PCG64(SeedSequence(x))) of the rollout's 30-bit draw x
+ * (FiniteMDPEnv.seed); a deterministic table draws nothing.  Then get_plan (:73-75): DecisionNode.selection_rule (:88-91),
+ * Node.random_argmax (abstract.py:296-311) over the root's chance children.  Replaces the reference's per-rollout
+ * safe_deepcopy_env.  Bit-exact with the reference (+ - * / on f64, integer counts).
+ *   gpow double [horizon + 1]: gamma ** d (a host pointer: the host's Python `**`).  1 <= horizon <= 4096.
+ *   rng_state [n_roots][6], advanced; plans int32 [n_roots] the ONE planned action (-1: no rollout was made, budget <= 0 --
+ *   the reference raises ValueError from np.amax([])); root_value = the value of the chosen chance child; env_steps = model
+ *   steps taken (the last rollout may overshoot the budget); status MP_OK.
+ */
+int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t budget, int32_t horizon,
+                 double gamma, const double *gpow, uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *env_steps,
+                 int32_t *status, int32_t mem);
+/* Tree of root `root` after the last mp_brue_plan, in the reference's creation order: per node parent (-1 at the root), key
+ * (the action of a chance node, the observed state of a decision node, -1 at the root), is_chance, depth (brue.py:81,103),
+ * count, stat (DecisionNode.reward / ChanceNode.value); host arrays of capacity `cap` (at most 1 + 2 * (budget + horizon)
+ * nodes).  When a batch's trees do not all fit the workspace only root 0's is kept (MP_ERR_ARG for the others). */
+int mp_brue_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *key,
+                        uint8_t *is_chance, int32_t *depth, int64_t *count, double *stat);
+
 /* ---------------------------------------------------------------- discrete robust OPD ------- */
 /*
  * A joint environment of M models of one decision problem stepped together (agents/robust/robust.py:9-26 JointEnv): the

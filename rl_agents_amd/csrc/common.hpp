@@ -50,7 +50,7 @@ struct DevBuf {
 
 // what the last tree-search call left on the device (for the *_tree_export entry points)
 struct TreeMeta {
-    int kind = 0; // 0 none, 1 uct, 2 opd, 3 robust opd, 4 stochastic uct (mp_uct_plan_stochastic), 5 olop
+    int kind = 0; // 0 none, 1 uct, 2 opd, 3 robust opd, 4 stochastic uct (mp_uct_plan_stochastic), 5 olop, 6 brue
     int n_roots = 0, A = 0, cap = 0, K = 0, M = 1;
     double gamma = 0.0; // robust opd: the export recomputes leaf upper-bound vectors
     int buf = 0;        // UCT: which of the two tree workspaces (WS_TREE0 / WS_TREE2) holds the current trees
@@ -297,6 +297,8 @@ inline bool mem_valid(int mem) { return mem >= 0 && mem <= 3; }
 // uct_stoch.hip: apply a pending re-rooting of the open-loop stochastic trees (mp_uct_step_tree arms it)
 } // namespace mp
 int uct_stoch_reroot_now(mp_ctx *ctx, long cap_new);
+// uct_stoch.hip: the sampling thresholds ceil(cdf * 2^53) of a dense / sparse model's rows (model->thr), built once per model
+int ensure_thresholds(mp_ctx *ctx, mp_model *model);
 namespace mp {
 
 // (model_index, local root state) pairs of a batch model -> global root states for the planners: `host_tmp` backs *out for

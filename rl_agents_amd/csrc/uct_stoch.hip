@@ -709,7 +709,7 @@ __global__ void env_step_stoch_kernel(int n, int A, int sparse, int W, const uin
 using namespace mp;
 
 // sampling thresholds of a stochastic / sparse model's rows, built once per model on the device (numpy's cumsum / division order)
-static int ensure_thresholds(mp_ctx *ctx, mp_model *model)
+int ensure_thresholds(mp_ctx *ctx, mp_model *model)
 {
     if (model->thr) return MP_OK;
     const long rows = (long)model->S * model->A;

@@ -106,6 +106,8 @@ SIGNATURES = {
     "mp_olop_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp, _vp,
                                _vp, _vp, c_i32]),
     "mp_olop_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_brue_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_brue_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_uct_choose_form": (C.c_int, [_vp, _vp, P(C.c_char_p)]),
     "mp_last_kernel_ms": (C.c_int, [_vp, P(c_f64), P(c_i32)]),
     "mp_last_kernel_variant": (C.c_char_p, [_vp]),
@@ -1069,6 +1071,33 @@ class Context(object):
         _check(self._lib.mp_olop_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]), _ptr(t["action"]),
                                              _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["cum"]), _ptr(t["mu"]), _ptr(t["vu"]),
                                              _ptr(t["done"]), _ptr(t["state"])))
+        return {k: v[:n.value].copy() for k, v in t.items()}
+
+    def brue_plan(self, model, root_state, budget, horizon, gamma, gpow, rng_state):
+        """BRUE.plan for a batch of roots (host arrays): mp_brue_plan.  ``gpow`` float64 [horizon + 1]: gamma ** d from the
+        host.  ``plans`` [n]: the one planned action per root (-1 where no rollout was made)."""
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        n = rs.shape[0]
+        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
+                and rng_state.size == n * 6):
+            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
+        gp = np.ascontiguousarray(gpow, dtype=np.float64).reshape(-1)
+        if gp.size != int(horizon) + 1:
+            raise ValueError("brue_plan: gpow [horizon + 1] expected")
+        out = dict(plans=np.full(n, -1, np.int32), root_value=np.zeros(n, np.float64), env_steps=np.zeros(n, np.int64),
+                   status=np.zeros(n, np.int32))
+        _check(self._lib.mp_brue_plan(self._h, model._h, n, _ptr(rs), int(budget), int(horizon), float(gamma), _ptr(gp),
+                                      _ptr(rng_state), _ptr(out["plans"]), _ptr(out["root_value"]), _ptr(out["env_steps"]),
+                                      _ptr(out["status"]), MP_MEM_HOST))
+        return out
+
+    def brue_tree(self, root, cap):
+        """Creation-order arrays of root ``root``'s tree after the last brue_plan (mp_brue_tree_export)."""
+        t = dict(parent=np.zeros(cap, np.int32), key=np.zeros(cap, np.int32), is_chance=np.zeros(cap, np.uint8),
+                 depth=np.zeros(cap, np.int32), count=np.zeros(cap, np.int64), stat=np.zeros(cap, np.float64))
+        n = c_i32()
+        _check(self._lib.mp_brue_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]), _ptr(t["key"]),
+                                             _ptr(t["is_chance"]), _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["stat"])))
         return {k: v[:n.value].copy() for k, v in t.items()}
 
     def opd_tree(self, root, cap):
