@@ -37,6 +37,8 @@ extern "C" {
 #define MP_ERR_ARG (-4)          /* invalid argument / unsupported configuration                  */
 #define MP_ERR_MODE (-5)         /* model kind not valid for this call ("Unknown mode")           */
 #define MP_ERR_OLOP_KEY (-6)     /* OLOP status: the "zeros" continuation's action is not a child (olop.py:89 KeyError) */
+#define MP_ERR_GBOPD_DIVERGED (-7)  /* GBOP-D status: a plan made more than 2^22 queue pops (bounds that cycle, never converge) */
+#define MP_ERR_GBOPD_NO_ACTION (-8) /* GBOP-D status: a node no action is listed for (graph_based.py:74, np.amax([]) ValueError) */
 
 #define MP_MEM_HOST 0
 #define MP_MEM_DEVICE 1
@@ -619,6 +621,53 @@ int mp_saopd_info(mp_saopd *planners, int32_t *n_planners, int32_t *n_nodes, int
 int mp_saopd_export(mp_saopd *planners, int32_t planner, int32_t cap, int32_t *parent, int32_t *action, int32_t *state,
                     int32_t *depth, double *reward, double *lower, uint8_t *done, int64_t *count, int32_t *first_child,
                     uint8_t *alive, double *state_values);
+
+/* ---------------------------------------------------------------- GBOP-D -------------------- */
+/*
+ * GraphBasedPlanner / GraphNode (tree_search/graph_based.py:12-151): optimistic planning on the GRAPH of observed states
+ * -- one node per state, a lower and an upper bound of V per node, tightened after every expansion by a partial value
+ * iteration that runs backwards through the graph (a first-in-first-out queue with duplicates, :66-78).
+ * An mp_gbopd handle holds, for n_planners independent planners of one deterministic table model (with or without an
+ * availability table and listing order; any other model kind answers MP_ERR_MODE), what a reference planner OBJECT holds
+ * across plan() calls: planner.nodes (bounds, children, parents), updates_count and observations -- reset() (:93-94) only
+ * replaces `root`, so every later plan continues on the same graph.  queue_cap: entries of a planner's backup queue
+ * (rounded up to a power of two; <= 0: MP_GBOPD_QUEUE in the environment, else 65 536, less for batches whose rings would
+ * exceed 4 GiB: such a batch should name its capacity).
+ * mp_gbopd_plan = GraphBasedPlanner.plan (:118-124) for every planner: root = get_node(root_state), budget // |A| epochs
+ * of run() (:96-108; |A| is the model's action count), then get_plan (:126-135).
+ *   value_max = 1 / (1 - gamma) as the host computes it (:18); accuracy and sampling_timeout as in the config (:148-149).
+ *   -1 < gamma < 1 and accuracy >= 0 are required (MP_ERR_ARG): outside them the reference's queue never empties.
+ *   rng_state uint64 [n,6]: the tie draws of sampling_rule (:22-30); a single maximum does not advance the generator.
+ *   plans int32 [n,sampling_timeout] (-1 padded; actions are the model's slots = the listing order), plan_len int32 [n],
+ *   value_lower / value_upper double [n] (the root's bounds), env_steps / updates int64 [n] (observations appended /
+ *   queue pops of this call), status int32 [n]: MP_OK, MP_ERR_ALLOC (the planner's queue filled up: its graph is half
+ *   updated and it stays failed -- every later call reports MP_ERR_ALLOC for it again; the other planners are unaffected)
+ *   MP_ERR_ARG (root state out of range in a device array), MP_ERR_GBOPD_NO_ACTION (a node no action is listed for: the
+ *   reference raises ValueError) or MP_ERR_GBOPD_DIVERGED (more than 2^22 pops in one plan: with accuracy 0 and rewards
+ *   outside [0, 1] the bounds can cycle for ever and the reference never returns); a planner that reported either stays
+ *   failed, as with MP_ERR_ALLOC.  Tables or action sets that changed under a kept graph (mp_model_update_tables / _rows,
+ *   mp_model_set_available after mp_gbopd_create): mp_gbopd_plan and mp_gbopd_export RETURN MP_ERR_ARG with the reason.
+ *   mem = MP_MEM_HOST synchronises; MP_MEM_DEVICE is one asynchronous launch on the context's stream.
+ * The parents of a node are kept and appended in INSERTION order (the reference iterates a set hashed by address there).
+ * mp_gbopd_export: one planner's graph in creation order, arrays of capacity cap >= n_nodes (at most n_states):
+ *   state, lower, upper, expanded [cap]; child int32 / reward double [cap, n_actions]: per slot the creation index of the
+ *   child (-1: not listed, or the node is not expanded) and its reward; parent_ptr int32 [cap + 1] and parent_idx int32
+ *   [n_edges (mp_gbopd_info)]: the parents' creation indices in order; visits / updates int64 [n_states]: the lifetime
+ *   counters by state (get_visits, abstract.py:163-167; get_updates); n_observations = len(planner.observations);
+ *   root = creation index of the last root.
+ * The model must outlive the planners and keep its tables.
+ */
+typedef struct mp_gbopd mp_gbopd;
+int mp_gbopd_create(mp_ctx *ctx, mp_model *model, int32_t n_planners, int32_t queue_cap, mp_gbopd **out);
+int mp_gbopd_free(mp_gbopd *planners);
+int mp_gbopd_plan(mp_ctx *ctx, mp_gbopd *planners, const int32_t *root_state, int32_t budget, double gamma, double value_max,
+                  double accuracy, int32_t sampling_timeout, uint64_t *rng_state, int32_t *plans, int32_t *plan_len,
+                  double *value_lower, double *value_upper, int64_t *env_steps, int64_t *updates, int32_t *status, int32_t mem);
+int mp_gbopd_info(mp_gbopd *planners, int32_t *n_planners, int32_t *n_states, int32_t *n_actions, int32_t *queue_cap,
+                  int64_t *n_edges);
+int mp_gbopd_export(mp_gbopd *planners, int32_t planner, int32_t cap, int32_t *n_nodes, int32_t *state, double *lower,
+                    double *upper, uint8_t *expanded, int32_t *child, double *reward, int32_t *parent_ptr, int32_t *parent_idx,
+                    int64_t *visits, int64_t *updates, int64_t *n_observations, int32_t *root);
 
 /* ---------------------------------------------------------------- batched evaluation -------- */
 /*

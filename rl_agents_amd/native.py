@@ -16,6 +16,7 @@ MP_MEM_HOST, MP_MEM_DEVICE, MP_MEM_RNG_DEVICE = 0, 1, 2
 MP_OK, MP_ERR_HIP, MP_ERR_REWARD_RANGE, MP_ERR_ALLOC, MP_ERR_ARG, MP_ERR_MODE = 0, -1, -2, -3, -4, -5
 MODE_DETERMINISTIC, MODE_STOCHASTIC, MODE_SPARSE, MODE_CARTPOLE = 0, 1, 2, 3
 ERR_REWARD_RANGE, ERR_ARG, ERR_MODE = -2, -4, -5
+MP_ERR_GBOPD_DIVERGED, MP_ERR_GBOPD_NO_ACTION = -7, -8
 ERR_OLOP_KEY = -6          # mp_olop_plan status: the "zeros" continuation's action is not a child (olop.py:89 KeyError)
 
 _LIB = None
@@ -102,6 +103,11 @@ SIGNATURES = {
                                 _vp, c_i32]),
     "mp_saopd_info": (C.c_int, [_vp, P(c_i32), P(c_i32), P(c_i32), P(c_i32)]),
     "mp_saopd_export": (C.c_int, [_vp, c_i32, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_gbopd_create": (C.c_int, [_vp, _vp, c_i32, c_i32, P(_vp)]),
+    "mp_gbopd_free": (C.c_int, [_vp]),
+    "mp_gbopd_plan": (C.c_int, [_vp, _vp, _vp, c_i32, c_f64, c_f64, c_f64, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_gbopd_info": (C.c_int, [_vp, P(c_i32), P(c_i32), P(c_i32), P(c_i32), P(c_i64)]),
+    "mp_gbopd_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, P(c_i64), P(c_i32)]),
     "mp_olop_allocation": (C.c_int, [c_i32, c_f64, P(c_i32), P(c_i32)]),
     "mp_olop_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp, _vp,
                                _vp, _vp, c_i32]),
@@ -1328,6 +1334,90 @@ class StateAwarePlanners(object):
     def close(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
             self.ctx._lib.mp_saopd_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GraphBasedPlanners(object):
+    """A batch of device-resident GraphBasedPlanner objects (mp_gbopd): the graph of observed states with both bounds, the
+    parents in insertion order and the lifetime visit / update counters persist across plan() calls, as in the reference
+    (tree_search/graph_based.py:87-94).  ``queue_cap``: entries of a planner's backup queue (None: the library's default)."""
+
+    def __init__(self, ctx, model, n_planners, queue_cap=None):
+        self.ctx, self.model, self.n = ctx, model, int(n_planners)
+        self._h = _vp()
+        _check(ctx._lib.mp_gbopd_create(ctx._h, model._h, self.n, int(queue_cap or 0), C.byref(self._h)))
+
+    def plan(self, root_state, budget, gamma, value_max, accuracy, sampling_timeout, rng_state):
+        """GraphBasedPlanner.plan for every planner (host arrays).  ``value_max``: the host's ``1 / (1 - gamma)``."""
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        if rs.shape[0] != self.n:
+            raise ValueError("one root state per planner ({}), got {}".format(self.n, rs.shape[0]))
+        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
+                and rng_state.size == self.n * 6):
+            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_planners, 6]")
+        t = int(sampling_timeout)
+        out = dict(plans=np.full((self.n, t), -1, np.int32), plan_len=np.zeros(self.n, np.int32),
+                   value_lower=np.zeros(self.n, np.float64), value_upper=np.zeros(self.n, np.float64),
+                   env_steps=np.zeros(self.n, np.int64), updates=np.zeros(self.n, np.int64),
+                   status=np.zeros(self.n, np.int32))
+        _check(self.ctx._lib.mp_gbopd_plan(self.ctx._h, self._h, _ptr(rs), int(budget), float(gamma), float(value_max),
+                                           float(accuracy), t, _ptr(rng_state), _ptr(out["plans"]), _ptr(out["plan_len"]),
+                                           _ptr(out["value_lower"]), _ptr(out["value_upper"]), _ptr(out["env_steps"]),
+                                           _ptr(out["updates"]), _ptr(out["status"]), MP_MEM_HOST))
+        return out
+
+    def plan_device(self, root_state, budget, gamma, value_max, accuracy, sampling_timeout, rng_state, plans=None,
+                    plan_len=None, value_lower=None, value_upper=None, env_steps=None, updates=None, status=None):
+        """Asynchronous form: every array is a device buffer (torch tensors on the context's device: root_state int32 [n],
+        rng_state uint64-as-int64 [n, 6], plans int32 [n, sampling_timeout], plan_len / status int32 [n], value_lower /
+        value_upper float64 [n], env_steps / updates int64 [n]); one launch on the context's stream, nothing read back."""
+        _check(self.ctx._lib.mp_gbopd_plan(self.ctx._h, self._h, _ptr(root_state), int(budget), float(gamma), float(value_max),
+                                           float(accuracy), int(sampling_timeout), _ptr(rng_state), _ptr(plans), _ptr(plan_len),
+                                           _ptr(value_lower), _ptr(value_upper), _ptr(env_steps), _ptr(updates), _ptr(status),
+                                           MP_MEM_DEVICE))
+
+    def info(self):
+        n, s, a, q, e = c_i32(), c_i32(), c_i32(), c_i32(), c_i64()
+        _check(self.ctx._lib.mp_gbopd_info(self._h, C.byref(n), C.byref(s), C.byref(a), C.byref(q), C.byref(e)))
+        return dict(n_planners=n.value, n_states=s.value, n_actions=a.value, queue_cap=q.value, n_edges=e.value)
+
+    def export(self, planner=0):
+        """One planner's graph in creation order, in the fields of the goldens' listing: state, lower, upper, expanded,
+        n_children, child_action / child_node / child_reward [n, A] (the listed actions first, in the model's slot order,
+        -1 / 0 padded), parent_ptr / parent_idx, visits / updates [S], n_observations, root."""
+        inf = self.info()
+        S, A = inf["n_states"], inf["n_actions"]
+        nn, nobs, root = c_i32(), c_i64(), c_i32()
+        state, lower, upper = np.zeros(S, np.int32), np.zeros(S, np.float64), np.zeros(S, np.float64)
+        expanded, child, reward = np.zeros(S, np.uint8), np.full((S, A), -1, np.int32), np.zeros((S, A), np.float64)
+        pptr, pidx = np.zeros(S + 1, np.int32), np.zeros(max(inf["n_edges"], 1), np.int32)
+        visits, updates = np.zeros(S, np.int64), np.zeros(S, np.int64)
+        _check(self.ctx._lib.mp_gbopd_export(self._h, int(planner), S, C.byref(nn), _ptr(state), _ptr(lower), _ptr(upper),
+                                             _ptr(expanded), _ptr(child), _ptr(reward), _ptr(pptr), _ptr(pidx), _ptr(visits),
+                                             _ptr(updates), C.byref(nobs), C.byref(root)))
+        n = nn.value
+        child, reward = child[:n], reward[:n]
+        listed = child >= 0
+        rank = np.argsort(~listed, axis=1, kind="stable")                  # the listed slots first, in slot order
+        n_children = listed.sum(axis=1).astype(np.int32)
+        keep = np.arange(A)[None, :] < n_children[:, None]
+        take = lambda x, fill: np.where(keep, np.take_along_axis(x, rank, axis=1), fill)  # noqa: E731
+        slots = np.broadcast_to(np.arange(A, dtype=np.int32), (n, A))
+        return dict(state=state[:n].copy(), lower=lower[:n].copy(), upper=upper[:n].copy(), expanded=expanded[:n].copy(),
+                    n_children=n_children, child_action=take(slots, -1).astype(np.int32),
+                    child_node=take(child, -1).astype(np.int32), child_reward=take(reward, 0.0),
+                    parent_ptr=pptr[:n + 1].copy(), parent_idx=pidx[:pptr[n]].copy(), visits=visits, updates=updates,
+                    n_observations=np.asarray(nobs.value), root=np.asarray(root.value))
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            self.ctx._lib.mp_gbopd_free(self._h)
         self._h = None
 
     def __del__(self):

@@ -69,6 +69,9 @@ class PerEpisodeEvaluation(object):
         self.max_steps = int(max_steps or device_model.env_max_steps(self.envs[0]) or 100)
         self.vi = not hasattr(agent, "planner")
         planner = None if self.vi else agent.planner
+        if not getattr(planner, "supports_per_episode_tables", True):
+            raise NotImplementedError("per-episode tables: {} keeps its planner state (graph, bounds, state values) from plan to "
+                                      "plan, and a kept state was built on the previous step's table".format(type(planner).__name__))
         self.kind = "vi" if self.vi else ("uct" if hasattr(planner, "prior_policy") else "opd")
         if not self.vi:
             cfg = planner.config
