@@ -239,3 +239,81 @@ def first_result(queue, procs, seconds):
         if p.is_alive():
             p.kill()
     pytest.fail("the process group produced no result (exit codes {}; still running ones were killed)".format(codes))
+
+
+# ---- shared by the forged-draw tests (tests/test_forge_host.py, tests/test_gpu_forged_draws.py) and tests/test_host_logic.py
+M64 = (1 << 64) - 1
+
+
+def scalar_mulhi(a, b):
+    a0, a1, b0, b1 = a & 0xffffffff, a >> 32, b & 0xffffffff, b >> 32
+    p00, p01, p10, p11 = a0 * b0, a0 * b1, a1 * b0, a1 * b1
+    mid = (p00 >> 32) + (p01 & 0xffffffff) + (p10 & 0xffffffff)
+    return (p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32)) & M64
+
+
+def scalar_step(s_hi, s_lo, inc_hi, inc_lo):
+    """Pcg64U::advance of csrc/pcg64.hpp on Python integers masked to 64 bits (tests/test_host_logic.py checks it against numpy,
+    tests/test_forge_host.py steps it on forged records)."""
+    m_lo, m_hi = 0x4385DF649FCCF645, 0x2360ED051FC65DA4
+    lo = (s_lo * m_lo) & M64
+    hi = (scalar_mulhi(s_lo, m_lo) + s_lo * m_hi + s_hi * m_lo) & M64
+    lo2 = (lo + inc_lo) & M64
+    carry = ((lo & inc_lo) | ((lo | inc_lo) & (~lo2 & M64))) >> 63
+    return (hi + inc_hi + carry) & M64, lo2
+
+
+def scalar_output(s_hi, s_lo):
+    x, rot = s_hi ^ s_lo, s_hi >> 58
+    return ((x >> rot) | (x << ((64 - rot) & 63))) & M64
+
+
+def generator_from(rec):
+    """A numpy Generator(PCG64) standing at the six-word record ``rec``."""
+    from rl_agents_amd import native
+    gen = np.random.Generator(np.random.PCG64(0))
+    native.generator_set_state(gen, rec)
+    return gen
+
+
+def zero_table(n_states, n_actions, k):
+    """All rewards zero, no terminal state, no self-loop: every first decision is a tie among the ``k`` listed actions."""
+    t = (np.arange(n_states)[:, None] + 1 + np.arange(n_actions)[None, :] % (n_states - 1)) % n_states
+    avail = np.zeros((n_states, n_actions), bool)
+    avail[:, :k] = True
+    return t.astype(np.int64), np.zeros((n_states, n_actions)), np.zeros(n_states, bool), avail
+
+
+def value_table(n_states, n_actions):
+    """No terminal state; rewards on a grid of 17 values, different for every action of a state: the first rollout action shows
+    in every statistic."""
+    s, a = np.arange(n_states)[:, None], np.arange(n_actions)[None, :]
+    return ((s * 5 + a * 3 + 1) % n_states).astype(np.int64), ((s * 7 + a * 11) % 17) / 16.0, np.zeros(n_states, bool)
+
+
+def stochastic_model(kind, n_states, n_actions, zero_rewards, width=3):
+    """A dense ("stochastic") or sparse model whose rows depend on the state alone (every action of a state samples the same
+    row, with a zero entry in it), so that the env generator's first draw meets the row of the root state whatever the first
+    action is.  No terminal state."""
+    g = np.random.Generator(np.random.PCG64(100 + n_actions + width))
+    reward = np.zeros((n_states, n_actions)) if zero_rewards else value_table(n_states, n_actions)[1]
+    if kind == "sparse":
+        w = g.random((n_states, 1, width)) + 0.05
+        if width >= 3:
+            w[:, :, 1] = 0.0
+        p = np.repeat(w / w.sum(axis=2, keepdims=True), n_actions, axis=1)
+        nxt = g.integers(0, n_states, size=(n_states, n_actions, width)).astype(np.int64)
+        return dict(mode="sparse", transition=p, next=nxt, reward=reward)
+    w = g.random((n_states, 1, n_states)) + 0.05
+    w[:, :, 2::3] = 0.0
+    p = np.repeat(w / w.sum(axis=2, keepdims=True), n_actions, axis=1)
+    return dict(mode="stochastic", transition=p, next=None, reward=reward)
+
+
+# rows whose inverse-CDF thresholds the forged-draw tests meet exactly
+CDF_ROWS = {
+    "uniform2": np.ones(2) / 2, "uniform3": np.ones(3) / 3, "uniform5": np.ones(5) / 5, "uniform8": np.ones(8) / 8,
+    "uniform9": np.ones(9) / 9,
+    "zeros": np.array([0.25, 0.0, 0.5, 0.25, 0.0, 0.0]),          # a zero in the middle (a repeated threshold), trailing zeros
+    "lead_zero": np.array([0.0, 0.3, 0.0, 0.7]),                  # a threshold of 0: no k is below it
+}
