@@ -752,14 +752,32 @@ int mp_uct_choose_form(const int64_t *call, int64_t *out, const char **name);
 /* Timing of the last kernel batch enqueued by a plan / solve call, from HIP events recorded on
  * the ctx stream around the kernel launches only (no copies).  Synchronises the stream. */
 int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
-/* Name of the kernel variant the last mp_uct_plan* / mp_vi_solve_batch call launched -- "uct_global", "uct_ldsr" (model resident
- * in LDS), "uct_quad" (four lanes per root), "uct_lone" (one root per workgroup), "uct_lone_mw" (2 / 4 / 8 roots per workgroup, a
- * wavefront each, around one copy of the transitions), "uct_row_shared" / "uct_row_each" /
- * "uct_lone_each" (four roots per wavefront on DPP rows, trees in LDS: a shared model / one MDP per root; a wavefront per root),
- * "uct_policy", "uct_cartpole", "uct_global_spill"; "vi_batch_reg<own,block>", "vi_batch_cluster2|4|8" (K workgroups per MDP),
- * "vi_batch_wg_stream", "vi_batch_wg_lds", "vi_batch_wg_global": the host picks by model and batch size; reports and tests name
- * what ran.  Results do not depend on the variant. */
+/* Name of the kernel form the last plan call of any planner, or the last mp_vi_solve_batch, launched on this ctx: every selector
+ * that changes which device code runs, after all overrides and fallbacks.
+ *   UCT           "uct_global", "uct_ldsr" (model resident in LDS), "uct_quad" (four lanes per root), "uct_lone" (one root per
+ *                 workgroup), "uct_lone_mw" (2 / 4 / 8 roots per workgroup, a wavefront each, around one copy of the
+ *                 transitions), "uct_row_shared" / "uct_row_each" / "uct_lone_each" (four roots per wavefront on DPP rows, trees
+ *                 in LDS: a shared model / one MDP per root; a wavefront per root), "uct_policy", "uct_cartpole",
+ *                 "uct_global_spill"
+ *   batched VI    "vi_batch_reg<own,block>", "vi_batch_cluster2|4|8" (K workgroups per MDP), "vi_batch_wg_stream|lds|global"
+ *   OLOP, BRUE    "olop_global", "brue_global" (a tree per root, kept for the export), "..._slots" (slots shared by the waves)
+ *   GBOP-D        "gbopd_wave_lds", "gbopd_wave_global"
+ *   OPD           "opd_any" (more than 64 actions); "opd_lds" / "opd_ldsx" (bounds in LDS / the parent map in HBM), then "_gen"
+ *                 (the main loop for arbitrary bounds), then "_chain" (the closing pass on the node array);
+ *                 "opd_wide_sib" / "opd_wide_cls" (bounds in HBM, sibling / residue-class layout), then "_small" (at most two
+ *                 slots per lane in a re-scan), then "_gen"
+ *   robust OPD    "ropd_any"; "ropd_lds" / "ropd_ldsx", then "_m2" / "_m4" (batched loads for up to two / four models) or "_gen",
+ *                 then "_chain"; "ropd_wide_sib" / "ropd_wide_cls", then "_gen"
+ *   state-aware   "saopd_lane" (a planner per lane), "saopd_wave" (per wavefront), "saopd_wave_dict" (dictionaries in LDS),
+ *                 "saopd_wave_lds" (the arena in LDS too): the kernel of the call's LAST launch; then "_ordered" (the dispatch
+ *                 order was sorted), then "_retry" (the call rolled back and ran again)
+ *   stochastic    "uct_stoch_r{0,2,4,1}_p{16,32}_a{any,2..8}", then "_policy": step records (0 rows and thresholds, 2 / 4 fused
+ *   UCT           records of that many successors, 1 compact 16-byte records), bits of a path entry, the unrolled |A|
+ * The host picks by model, batch size and the MP_* test hooks; reports and tests name what ran.  Results do not depend on the form. */
 const char *mp_last_kernel_variant(mp_ctx *ctx);
+/* Every name mp_last_kernel_variant can return, one per line, built by the functions that name the launches (host only, no
+ * device): a test table that is to cover every form is compared with this list. */
+const char *mp_kernel_form_names(void);
 /* Hardware self-test (no reference counterpart): LDS atomics of ONE wavefront instruction that hit the same address apply
  * in LANE ORDER on this device -- the state-aware OPD kernel's grouped backup relies on it (one ds_min_rtn_f64 of the group
  * leaders hands every leader the running minimum the reference's turn-by-turn loop would have read).  Runs `waves` wave

@@ -737,6 +737,12 @@ int mp_ctx_device_info(mp_ctx *ctx, int32_t *n_cu, int32_t *wave_size, int64_t *
 
 const char *mp_last_kernel_variant(mp_ctx *ctx) { return ctx ? ctx->last_variant : ""; }
 
+const char *mp_kernel_form_names(void)
+{
+    static const std::string names = mp::all_form_names();
+    return names.c_str();
+}
+
 // ---- self-test: lane order of same-address LDS atomics within one wave instruction (see mi355plan.h) ----------------------
 namespace mp {
 __device__ __forceinline__ uint32_t st_hash(uint32_t x)

@@ -364,7 +364,7 @@ int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
     MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, mem, &a.env_steps));
 
-    snprintf(ctx->last_variant, sizeof(ctx->last_variant), "%s", a.keep ? "brue_global" : "brue_global_slots");
+    form_record(ctx->last_variant, brue_form_name(a.keep));
     MP_TRY(kernels_begin(ctx));
     hipLaunchKernelGGL(brue_kernel, dim3((unsigned)a.grid), dim3(64), (size_t)horizon * (sizeof(double) + sizeof(int2)), st, a);
     MP_TRY(kernels_end(ctx, 1));

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mi355plan.h"
+#include "form_names.hpp"
 
 namespace mp {
 
@@ -80,7 +81,7 @@ struct mp_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     int n_launches = 0;
-    char last_variant[48] = ""; // which kernel variant the last tree-search call launched (mp_last_kernel_variant)
+    char last_variant[mp::kFormNameBytes] = ""; // which kernel form the last plan / batched VI call launched (mp_last_kernel_variant)
     hipDeviceProp_t prop;
     mp::DevBuf ws[mp::WS_COUNT];
     mp::TreeMeta tree;

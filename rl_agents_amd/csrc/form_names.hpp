@@ -1,0 +1,186 @@
+// form_names.hpp -- the names mp_last_kernel_variant reports, one small function per planner.  An entry point passes the
+// selectors it launched with, after every override and fallback, to its function; mp_kernel_form_names (api.hip) loops the
+// same functions over their selector ranges.  Host only.  A name fits mp_ctx::last_variant (kFormNameBytes with the NUL).
+#pragma once
+#include <stdio.h>
+
+#include <string>
+
+namespace mp {
+
+constexpr int kFormNameBytes = 48;
+
+struct FormName {
+    char s[kFormNameBytes];
+    const char *c_str() const { return s; }
+};
+
+inline void form_record(char (&dst)[kFormNameBytes], const FormName &n) { snprintf(dst, sizeof(dst), "%s", n.s); }
+
+// ---- UCT (uct.hip: the index is its UctForm), batched VI (vi.hip), OLOP, BRUE, GBOP-D
+constexpr int kUctForms = 11;
+inline FormName uct_form_name(int form)
+{
+    static const char *const name[kUctForms] = {"global", "global_spill", "ldsr", "quad", "lone", "lone_mw", "lone_each", "row_each",
+                                                "row_shared", "cartpole", "policy"};
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "uct_%s", name[form]);
+    return n;
+}
+// (the same name in static storage: mp_uct_choose_form hands out a pointer)
+inline const char *uct_form_name_static(int form)
+{
+    static const struct Names {
+        FormName n[kUctForms];
+        Names() { for (int f = 0; f < kUctForms; ++f) n[f] = uct_form_name(f); }
+    } names;
+    return names.n[form].s;
+}
+
+// the register forms of the batched VI: states per thread, threads per workgroup
+constexpr int kViBatchRegForms = 7;
+constexpr int kViBatchReg[kViBatchRegForms][2] = {{1, 64}, {2, 64}, {2, 128}, {2, 256}, {4, 256}, {4, 512}, {4, 1024}};
+inline FormName vi_batch_reg_name(int own, int block)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "vi_batch_reg<%d,%d>", own, block);
+    return n;
+}
+inline FormName vi_batch_cluster_name(int k) // 2, 4 or 8 workgroups per MDP
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "vi_batch_cluster%d", k);
+    return n;
+}
+enum ViBatchWg { VB_WG_STREAM, VB_WG_LDS, VB_WG_GLOBAL, VB_WG_COUNT };
+inline FormName vi_batch_wg_name(int kind)
+{
+    static const char *const name[VB_WG_COUNT] = {"stream", "lds", "global"};
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "vi_batch_wg_%s", name[kind]);
+    return n;
+}
+
+inline FormName slots_form_name(const char *planner, bool keep) // OLOP, BRUE: the trees kept for export, or slots shared by waves
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "%s_global%s", planner, keep ? "" : "_slots");
+    return n;
+}
+inline FormName olop_form_name(bool keep) { return slots_form_name("olop", keep); }
+inline FormName brue_form_name(bool keep) { return slots_form_name("brue", keep); }
+inline FormName gbopd_form_name(bool use_lds)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "gbopd_wave_%s", use_lds ? "lds" : "global");
+    return n;
+}
+
+// ---- OPD (opd.hip) and robust OPD (ropd.hip).  any_a: |A| > 64, the plain kernel.  Else glb: the wide kernel in its sibling
+// (sib) or residue-class layout; !glb: the LDS-resident kernel, the parent map in HBM with expg, the closing pass on the node
+// array with chain.  nonneg picks the cheaper main loops everywhere.
+// OPD only: small = the wide kernel's two-slots-per-lane re-scan.  Robust OPD only: mb = the batched-load main loop of the
+// LDS-resident kernel (0 the generic one, 1 up to two models, 2 up to four).
+struct OpdForm {
+    bool any_a, glb, expg, sib, small, nonneg, chain;
+    int mb;
+};
+inline FormName opd_form_name(const OpdForm &f)
+{
+    FormName n;
+    if (f.any_a) snprintf(n.s, sizeof(n.s), "opd_any");
+    else if (f.glb) snprintf(n.s, sizeof(n.s), "opd_wide_%s%s%s", f.sib ? "sib" : "cls", f.small ? "_small" : "", f.nonneg ? "" : "_gen");
+    else snprintf(n.s, sizeof(n.s), "opd_%s%s%s", f.expg ? "ldsx" : "lds", f.nonneg ? "" : "_gen", f.chain ? "_chain" : "");
+    return n;
+}
+inline FormName ropd_form_name(const OpdForm &f)
+{
+    FormName n;
+    if (f.any_a) snprintf(n.s, sizeof(n.s), "ropd_any");
+    else if (f.glb) snprintf(n.s, sizeof(n.s), "ropd_wide_%s%s", f.sib ? "sib" : "cls", f.nonneg ? "" : "_gen");
+    else snprintf(n.s, sizeof(n.s), "ropd_%s%s%s", f.expg ? "ldsx" : "lds", f.mb == 1 ? "_m2" : f.mb == 2 ? "_m4" : "_gen", f.chain ? "_chain" : "");
+    return n;
+}
+
+// ---- state-aware OPD (saopd.hip): the kernel of the LAST launch of the call.  One planner per lane, or per wavefront with
+// everything in global memory, with the dictionaries in LDS (dict) or with the arena in LDS too (lds); ordered: the dispatch
+// order was sorted (saopd_order_kernel ran); retry: the call rolled back and ran again.
+struct SaopdForm {
+    bool wave, dict, lds, ordered, retry;
+};
+// (the lane kernel takes no dispatch order; a retry of the all-in-LDS form runs on another form)
+inline bool saopd_form_possible(const SaopdForm &f)
+{
+    return !(f.lds && f.dict) && (f.wave || !(f.dict || f.lds || f.ordered)) && !(f.lds && f.retry);
+}
+inline FormName saopd_form_name(const SaopdForm &f)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "saopd_%s%s%s", !f.wave ? "lane" : f.lds ? "wave_lds" : f.dict ? "wave_dict" : "wave", f.ordered ? "_ordered" : "",
+             f.retry ? "_retry" : "");
+    return n;
+}
+
+// ---- UCT on stochastic models (uct_stoch.hip).  wbk: the form the step records really have (0 rows + thresholds, 2 / 4 fused
+// records of that many successors, 1 the compact 16-byte records); p16: 16-bit path entries; at: the unrolled |A| in 2..8 or
+// 0, the loop form; pol: per-state policies (32-bit path entries only)
+inline bool uct_stoch_form_possible(int wbk, bool p16, int at, bool pol)
+{
+    return (wbk == 0 || wbk == 1 || wbk == 2 || wbk == 4) && (at == 0 || (at >= 2 && at <= 8)) && !(pol && p16);
+}
+inline FormName uct_stoch_form_name(int wbk, bool p16, int at, bool pol)
+{
+    FormName n;
+    char a[8];
+    if (at) snprintf(a, sizeof(a), "%d", at);
+    else snprintf(a, sizeof(a), "any");
+    snprintf(n.s, sizeof(n.s), "uct_stoch_r%d_p%d_a%s%s", wbk, p16 ? 16 : 32, a, pol ? "_policy" : "");
+    return n;
+}
+
+// every name an entry point can record, one per line
+inline std::string all_form_names()
+{
+    std::string out;
+    auto add = [&](const FormName &n) { out += n.s; out += '\n'; };
+    for (int f = 0; f < kUctForms; ++f) add(uct_form_name(f));
+    for (int i = 0; i < kViBatchRegForms; ++i) add(vi_batch_reg_name(kViBatchReg[i][0], kViBatchReg[i][1]));
+    for (int k = 2; k <= 8; k *= 2) add(vi_batch_cluster_name(k));
+    for (int k = 0; k < VB_WG_COUNT; ++k) add(vi_batch_wg_name(k));
+    for (int keep = 1; keep >= 0; --keep) { add(olop_form_name(keep)); add(brue_form_name(keep)); }
+    for (int l = 1; l >= 0; --l) add(gbopd_form_name(l));
+    for (int robust = 0; robust < 2; ++robust) {
+        OpdForm f = {};
+        f.any_a = true;
+        add(robust ? ropd_form_name(f) : opd_form_name(f));
+        f.any_a = false;
+        for (int expg = 0; expg < 2; ++expg)
+            for (int v = 0; v < (robust ? 3 : 2); ++v)
+                for (int chain = 0; chain < 2; ++chain) {
+                    f.glb = false; f.expg = expg; f.chain = chain;
+                    f.nonneg = robust ? v != 0 : v == 0; f.mb = robust ? v : 0;
+                    add(robust ? ropd_form_name(f) : opd_form_name(f));
+                }
+        for (int sib = 1; sib >= 0; --sib)
+            for (int small = robust ? 0 : 1; small >= 0; --small)
+                for (int nonneg = 1; nonneg >= 0; --nonneg) {
+                    f.glb = true; f.sib = sib; f.small = small; f.nonneg = nonneg;
+                    add(robust ? ropd_form_name(f) : opd_form_name(f));
+                }
+    }
+    for (int kind = 0; kind < 4; ++kind)
+        for (int ordered = 0; ordered < 2; ++ordered)
+            for (int retry = 0; retry < 2; ++retry) {
+                const SaopdForm f = {kind != 0, kind == 2, kind == 3, ordered != 0, retry != 0};
+                if (saopd_form_possible(f)) add(saopd_form_name(f));
+            }
+    static const int wbks[4] = {0, 2, 4, 1};
+    for (int pol = 0; pol < 2; ++pol)
+        for (int w = 0; w < 4; ++w)
+            for (int p16 = 1; p16 >= 0; --p16)
+                for (int at = 0; at <= 8; ++at)
+                    if (at != 1 && uct_stoch_form_possible(wbks[w], p16, at, pol)) add(uct_stoch_form_name(wbks[w], p16, at, pol));
+    return out;
+}
+
+} // namespace mp

@@ -496,7 +496,7 @@ int mp_gbopd_plan(mp_ctx *ctx, mp_gbopd *pl, const int32_t *root_state, int32_t 
     if (lds_limit > 64 * 1024) lds_limit = 64 * 1024;
     const size_t lds = (size_t)S * 16;
     const bool use_lds = lds <= lds_limit;
-    snprintf(ctx->last_variant, sizeof(ctx->last_variant), "%s", use_lds ? "gbopd_wave_lds" : "gbopd_wave_global");
+    form_record(ctx->last_variant, gbopd_form_name(use_lds));
     MP_TRY(kernels_begin(ctx));
     if (use_lds) hipLaunchKernelGGL(gbopd_kernel<true>, dim3((unsigned)n), dim3(64), lds, st, a);
     else hipLaunchKernelGGL(gbopd_kernel<false>, dim3((unsigned)n), dim3(64), 0, st, a);

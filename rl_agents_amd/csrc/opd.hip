@@ -1058,6 +1058,7 @@ int mp_opd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *ro
     const bool any_a = A > 64, small = (s.sib ? s.Tsib - 16 : s.T) <= 128;
     const kernel_t kfn = any_a ? opd_any_kernel : s.glb ? wide_form[s.sib][s.nonneg][small] : lds_form[s.expg][s.nonneg];
     const size_t lds = any_a ? 0 : s.lds();
+    const OpdForm form = {any_a, s.glb, s.expg, s.sib, small, s.nonneg, opd_closing_on_nodes(s, A), 0};
 
     const size_t nn = (size_t)n_roots * s.cap;
     MP_TRY(ws_get(ctx, WS_TREE0, 2 * nn, &a.L)); // OpdNode records, 16 B each
@@ -1075,6 +1076,7 @@ int mp_opd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *ro
 
     if (lds > 64 * 1024)
         MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    form_record(ctx->last_variant, opd_form_name(form));
     MP_TRY(kernels_begin(ctx));
     hipLaunchKernelGGL(kfn, dim3((unsigned)n_roots), dim3(64), lds, ctx->stream, a);
     MP_TRY(kernels_end(ctx, 1));

@@ -67,6 +67,13 @@ inline OpdShape opd_shape(const mp_ctx *ctx, int A, int budget, int n_roots, dou
     return s;
 }
 
+// the LDS-resident kernels (opd_kernel, ropd_kernel) close on the node array when told to, or when the tables of
+// opd_closing.hpp do not fit the bounds array they reuse: the kernels' own test, asked from the host for the form's name
+inline bool opd_closing_on_nodes(const OpdShape &s, int A)
+{
+    return s.closing_chain || !closing_compact_fits(s.K, A, s.cap, 64L * s.T * 8);
+}
+
 // ---- gamma-power tables for depths <= K + 1, host libm (bit-equal to Python's float **):
 // g1[d] = gamma ** (d - 1) (d >= 1), gdiv[d] = gamma ** d / (1 - gamma), tdiv[d] = terminal_reward * gamma ** d / (1 - gamma)
 inline int opd_gamma_tables(mp_ctx *ctx, int K, double gamma, double terminal_reward, const double **g1, const double **gdiv,

@@ -843,6 +843,7 @@ int mp_ropd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     const int mb = !s.nonneg || M > 4 ? 0 : M <= 2 ? 1 : 2;
     const kernel_t kfn = any_a ? ropd_any_kernel : s.glb ? wide_form[s.sib][s.nonneg] : lds_form[s.expg][mb];
     const size_t lds = any_a ? 0 : s.lds();
+    const OpdForm form = {any_a, s.glb, s.expg, s.sib, false, s.nonneg, opd_closing_on_nodes(s, A), mb};
 
     const size_t nn = (size_t)n_roots * s.cap;
     MP_TRY(ws_get(ctx, WS_TREE0, nn * M, &a.Lv));
@@ -864,6 +865,7 @@ int mp_ropd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
 
     if (lds > 64 * 1024)
         MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    form_record(ctx->last_variant, ropd_form_name(form));
     MP_TRY(kernels_begin(ctx));
     hipLaunchKernelGGL(kfn, dim3((unsigned)n_roots), dim3(64), lds, ctx->stream, a);
     MP_TRY(kernels_end(ctx, 1));

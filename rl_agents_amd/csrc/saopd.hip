@@ -1891,6 +1891,7 @@ int mp_saopd_plan(mp_ctx *ctx, mp_saopd *pl, const int32_t *root_state, int32_t 
         a.order = pl->order;
         ++launches;
     }
+    bool retried = false;
     for (;;) {
         MP_HIP(hipMemsetAsync(pl->overflow, 0, 4, st));
         if (fresh) {
@@ -1908,6 +1909,7 @@ int mp_saopd_plan(mp_ctx *ctx, mp_saopd *pl, const int32_t *root_state, int32_t 
         else if (pl->wave) hipLaunchKernelGGL(saopd_wave_kernel<false>, dim3((unsigned)n), dim3(64), lds, st, a);
         else hipLaunchKernelGGL(saopd_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st, a);
         ++launches;
+        form_record(ctx->last_variant, saopd_form_name({pl->wave != 0, pl->wave && !use_lds && use_dict, pl->wave && use_lds, a.order != nullptr, retried}));
         if (async) break;
         int32_t ovf = 0;
         MP_HIP(hipMemcpyAsync(&ovf, pl->overflow, 4, hipMemcpyDeviceToHost, st));
@@ -1945,6 +1947,7 @@ int mp_saopd_plan(mp_ctx *ctx, mp_saopd *pl, const int32_t *root_state, int32_t 
             ++launches;
         }
         MP_HIP(hipMemcpyAsync(a.rng, pl->snap_rng, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
+        retried = true;
     }
     if (pl->wave) {
         pl->cost_valid = true;

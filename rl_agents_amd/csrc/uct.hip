@@ -2189,9 +2189,7 @@ static int uct_reroot_now(mp_ctx *ctx, long cap_new)
 // DESIGN.md §4.1 tabulates the forms, their defaults and the knobs that force them.
 enum UctForm { UF_GLOBAL, UF_GLOBAL_SPILL, UF_LDSR, UF_QUAD, UF_LONE, UF_LONE_MW, UF_LONE_EACH, UF_ROW_EACH, UF_ROW_SHARED,
                UF_CARTPOLE, UF_POLICY, UF_COUNT };
-static const char *const kUctFormName[UF_COUNT] = {"uct_global", "uct_global_spill", "uct_ldsr", "uct_quad", "uct_lone",
-                                                   "uct_lone_mw", "uct_lone_each", "uct_row_each", "uct_row_shared",
-                                                   "uct_cartpole", "uct_policy"};
+static_assert(UF_COUNT == kUctForms, "uct_form_name (form_names.hpp) names the forms in this order");
 
 constexpr int kUnset = INT_MIN;
 // the knobs that pick a form or its geometry (kUnset: not set), read once per call -- tests change them between calls
@@ -2455,7 +2453,7 @@ static int uct_launch(const UctChoice &ch, bool listed, const UctArgs &a, hipStr
     // root-major trees: generic |A|, and a kept CartPole tree continued by a table plan
     if (ch.form == UF_GLOBAL && !il2) return uct_go(uct_kernel<AT, ENV_TABLE>, ch, a, st);
     if (ch.form == UF_GLOBAL_SPILL && !il2) return uct_go(uct_kernel<AT, ENV_TABLE_SPILL>, ch, a, st);
-    return fail(MP_ERR_ARG, "mp_uct_plan: no %s kernel for |A| = %d in tree layout %d", kUctFormName[ch.form], a.A, a.tree_il);
+    return fail(MP_ERR_ARG, "mp_uct_plan: no %s kernel for |A| = %d in tree layout %d", uct_form_name(ch.form).c_str(), a.A, a.tree_il);
 }
 
 static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int32_t n_roots, const void *root_state,
@@ -2632,7 +2630,7 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
     }
     a.cap = (int)cap_use;
     a.tree_il = ctx->tree.il;
-    snprintf(ctx->last_variant, sizeof(ctx->last_variant), "%s", kUctFormName[form]);
+    form_record(ctx->last_variant, uct_form_name(form));
     if (form == UF_LDSR || form == UF_QUAD || form == UF_GLOBAL_SPILL) {
         a.spill_stride = ((long)n_roots + 63) & ~63L;
         MP_TRY(ws_get(ctx, WS_TREE4, (size_t)(H + 1) * (size_t)a.spill_stride, &a.path_spill));
@@ -2836,7 +2834,7 @@ int mp_uct_choose_form(const int64_t *call, int64_t *out, const char **name)
     MP_TRY(uct_choose(c, uct_knobs_read(), &ch));
     out[0] = ch.tree_il; out[1] = ch.lanes; out[2] = ch.waves; out[3] = ch.rep_shift; out[4] = ch.roots_per_wg; out[5] = ch.threads;
     out[6] = (int64_t)ch.lds;
-    *name = kUctFormName[ch.form];
+    *name = uct_form_name_static(ch.form);
     return MP_OK;
 }
 

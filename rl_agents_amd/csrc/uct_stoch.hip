@@ -990,6 +990,7 @@ static int uct_stoch_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *po
         const char *ag = getenv("MP_UCT_STOCH_GENERIC_A"); // "1": the loop form of the selection for any |A| -- test hook
         const int at = A >= 2 && A <= 8 && !(ag && ag[0] == '1') ? A : 0;
         const int wrow = wbk == 2 ? 1 : wbk == 4 ? 2 : wbk == 1 ? 3 : 0;
+        form_record(ctx->last_variant, uct_stoch_form_name(wbk, p16, at, pol != nullptr));
         if (pol) {
             static const kernel_t any_sp[4] = {uct_stoch_kernel<0, 0, int32_t, true>, uct_stoch_kernel<2, 0, int32_t, true>,
                                                uct_stoch_kernel<4, 0, int32_t, true>, uct_stoch_kernel<1, 0, int32_t, true>};

@@ -1798,7 +1798,7 @@ __global__ __launch_bounds__(1024) void vi_det_batch_wgr(ViBatchArgs p, const ui
 }
 
 template <int AT>
-static int vi_batch_launch(mp_ctx *ctx, ViBatchArgs &q, hipStream_t st, const char **variant)
+static int vi_batch_launch(mp_ctx *ctx, ViBatchArgs &q, hipStream_t st, FormName *variant)
 {
     const int S = q.Sb;
     const unsigned grid = (unsigned)q.N;
@@ -1807,7 +1807,7 @@ static int vi_batch_launch(mp_ctx *ctx, ViBatchArgs &q, hipStream_t st, const ch
 #define MP_VB(own, block)                                                                                              \
     if (S <= (own) * (block)) {                                                                                        \
         hipLaunchKernelGGL((vi_det_batch_reg<AT, own, block>), dim3(grid), dim3(block), lds, st, q);                   \
-        *variant = "vi_batch_reg<" #own "," #block ">";                                                                \
+        *variant = vi_batch_reg_name(own, block);                                                                   \
         return MP_OK;                                                                                                  \
     }
         if (!getenv("MP_VI_BATCH_NO_REG")) {
@@ -1858,7 +1858,7 @@ static int vi_batch_launch(mp_ctx *ctx, ViBatchArgs &q, hipStream_t st, const ch
             ViBatchArgs f = q;
             f.only_failed = 1; f.Vglobal = Vx;
             hipLaunchKernelGGL((vi_det_batch_wg<AT, false>), dim3(grid), dim3(1024), 0, st, f);
-            *variant = K == 2 ? "vi_batch_cluster2" : (K == 4 ? "vi_batch_cluster4" : "vi_batch_cluster8");
+            *variant = vi_batch_cluster_name(K);
             return MP_OK;
         }
     }
@@ -1878,7 +1878,7 @@ static int vi_batch_launch(mp_ctx *ctx, ViBatchArgs &q, hipStream_t st, const ch
             MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vi_det_batch_wgr<AT>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds));
             hipLaunchKernelGGL((vi_det_batch_wgr<AT>), dim3(grid), dim3(1024), lds, st, q, (const uint16_t *)Tt, (const double *)Rt);
-            *variant = "vi_batch_wg_stream";
+            *variant = vi_batch_wg_name(VB_WG_STREAM);
             return MP_OK;
         }
     }
@@ -1888,12 +1888,12 @@ static int vi_batch_launch(mp_ctx *ctx, ViBatchArgs &q, hipStream_t st, const ch
             MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vi_det_batch_wg<AT, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)lds));
         hipLaunchKernelGGL((vi_det_batch_wg<AT, true>), dim3(grid), dim3(1024), lds, st, q);
-        *variant = "vi_batch_wg_lds";
+        *variant = vi_batch_wg_name(VB_WG_LDS);
         return MP_OK;
     }
     MP_TRY(ws_get(ctx, WS_VI1, (size_t)q.N * 3 * S, &q.Vglobal));
     hipLaunchKernelGGL((vi_det_batch_wg<AT, false>), dim3(grid), dim3(1024), 0, st, q);
-    *variant = "vi_batch_wg_global";
+    *variant = vi_batch_wg_name(VB_WG_GLOBAL);
     return MP_OK;
 }
 
@@ -1917,7 +1917,7 @@ static int vi_solve_batch(mp_ctx *ctx, mp_model *m, double gamma, int iterations
     memset(&q, 0, sizeof(q));
     q.N = N; q.Sb = Sb; q.A = A; q.iterations = iterations; q.T = m->T; q.R = m->R; q.term = m->term;
     q.gamma = gamma; q.rtol = rtol; q.atol = atol; q.Q_out = dQ; q.sweeps_out = dSw;
-    const char *variant = "";
+    FormName variant = {""};
     MP_TRY(kernels_begin(ctx));
     switch (A) {
     case 2: MP_TRY(vi_batch_launch<2>(ctx, q, st, &variant)); break;
@@ -1929,7 +1929,7 @@ static int vi_solve_batch(mp_ctx *ctx, mp_model *m, double gamma, int iterations
     default: MP_TRY(vi_batch_launch<0>(ctx, q, st, &variant)); break;
     }
     MP_TRY(kernels_end(ctx, 1));
-    snprintf(ctx->last_variant, sizeof(ctx->last_variant), "%s", variant);
+    form_record(ctx->last_variant, variant);
     MP_HIP(hipGetLastError());
     MP_TRY(stage_out_copy(ctx, Q_out, dQ, nq, mem));
     MP_TRY(stage_out_copy(ctx, sweeps_out, dSw, (size_t)N, mem));

@@ -117,6 +117,7 @@ SIGNATURES = {
     "mp_uct_choose_form": (C.c_int, [_vp, _vp, P(C.c_char_p)]),
     "mp_last_kernel_ms": (C.c_int, [_vp, P(c_f64), P(c_i32)]),
     "mp_last_kernel_variant": (C.c_char_p, [_vp]),
+    "mp_kernel_form_names": (C.c_char_p, []),
     "mp_selftest_lds_atomic_order": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
     "mp_env_step": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, _vp, _vp, c_i32, c_i32, _vp, _vp, _vp, _vp, c_i32, _vp, c_i32]),
     "mp_greedy_actions": (C.c_int, [_vp, c_i32, c_i32, c_i32, _vp, _vp, _vp, c_i32, c_i32]),
@@ -287,6 +288,11 @@ def uct_choose_form(call):
     return name.value.decode(), out
 
 
+def kernel_form_names():
+    """Every name Context.last_kernel_variant() can return (mp_kernel_form_names; host only), in the library's order."""
+    return load().mp_kernel_form_names().decode().split()
+
+
 def vi_exact_plan(n):
     """The tables the bit-exact dense backup sums a row of ``n`` elements by (numpy's pairwise recursion; host only):
     -> (leaves int32 [L,2] {offset, length}, nodes int32 [K,2] {left slot, right slot} by height, hoff int32 [H+1],
@@ -370,7 +376,8 @@ class Context(object):
         return ms.value, n.value
 
     def last_kernel_variant(self):
-        """Which kernel variant the last UCT plan launched ("uct_global", "uct_ldsr", ...)."""
+        """Which kernel form the last plan / batched VI call launched ("uct_ldsr", "opd_wide_sib_small", "saopd_wave_dict", ...:
+        every name in kernel_form_names())."""
         return self._lib.mp_last_kernel_variant(self._h).decode()
 
     # ---- the collective of the C ABI (RCCL resolved at run time): what a consumer without torch.distributed calls ------------

@@ -317,3 +317,99 @@ CDF_ROWS = {
     "zeros": np.array([0.25, 0.0, 0.5, 0.25, 0.0, 0.0]),          # a zero in the middle (a repeated threshold), trailing zeros
     "lead_zero": np.array([0.0, 0.3, 0.0, 0.7]),                  # a threshold of 0: no k is below it
 }
+
+
+# ---- kernel forms (Context.last_kernel_variant()): what a test means to run, asserted after the call.  opd_form and saopd_form
+# restate the host's choice (csrc/opd_host.hpp opd_shape, csrc/saopd.hip mp_saopd_plan) from the shape of a call and the knobs
+# the test set, so that a test says "the knob I set took effect" without hard-coding a name per shape.
+LDS_AVAIL = 160 * 1024 - 1024
+
+
+def assert_form(ctx, name):
+    """The last plan / batched VI call on ``ctx`` launched the kernel form ``name``."""
+    got = ctx.last_kernel_variant()
+    assert got == name, "kernel form {!r} ran where the test means {!r}".format(got, name)
+
+
+def opd_closing_fits(n_actions, budget):
+    """closing_compact_fits (csrc/opd_closing.hpp) at the sizes opd_shape derives from |A| and the budget."""
+    k = budget // n_actions
+    cap = 1 + k * n_actions
+    t = ((cap + 63) // 64) | 1
+    return n_actions <= 255 and k < (1 << 22) and 16 * k + 4 * cap <= 64 * t * 8
+
+
+def opd_form(ctx, n_actions, budget, n_roots, model=None, wide=None, closing=None, general=False, models=0):
+    """The form mp_opd_plan (``models`` = 0) or mp_ropd_plan (``models`` = M) records: ``model`` / ``wide`` / ``closing`` are the
+    values of MP_OPD_MODEL / MP_OPD_WIDE / MP_OPD_CLOSING (None: unset), ``general``: MP_OPD_LOOP=0, a negative terminal reward
+    or gamma outside [0, 1)."""
+    prefix = "ropd" if models else "opd"
+    if n_actions > 64:
+        return prefix + "_any"
+    cus = ctx.device_info()["n_cu"]
+    k = budget // n_actions
+    cap = 1 + k * n_actions
+    t = ((cap + 63) // 64) | 1
+    lds_bounds = 64 * t * 8
+    lds_full = lds_bounds + max(k, 1) * 4
+    glb = lds_bounds > LDS_AVAIL or n_roots > cus * (LDS_AVAIL // lds_bounds)
+    if model == "global":
+        glb = True
+    if model in ("lds", "ldsx") and lds_bounds <= LDS_AVAIL:
+        glb = False
+    if glb:
+        sib = wide != "cls"
+        small = (((k + 64) // 64) * n_actions if sib else t) <= 128
+        return "{}_wide_{}{}{}".format(prefix, "sib" if sib else "cls", "_small" if small and not models else "",
+                                       "_gen" if general else "")
+    expg = lds_full > LDS_AVAIL or n_roots > cus * (LDS_AVAIL // lds_full) or model == "ldsx"
+    chain = closing == "chain" or not opd_closing_fits(n_actions, budget)
+    if models:
+        loop = "_gen" if general or models > 4 else "_m2" if models <= 2 else "_m4"
+    else:
+        loop = "_gen" if general else ""
+    return "{}_{}{}{}".format(prefix, "ldsx" if expg else "lds", loop, "_chain" if chain else "")
+
+
+def saopd_form(ctx, n_states, n_actions, budget, n_planners, nodes_before=0, model=None, lds=None, dictionary=None, order=None,
+               have_cost=False, queue=None, retry=False, device_arrays=False):
+    """The form mp_saopd_plan records for one plan of a planner batch that holds ``nodes_before`` nodes per planner: ``model`` /
+    ``lds`` / ``dictionary`` / ``order`` / ``queue`` are the values of MP_SAOPD_MODEL / _LDS / _DICT / _ORDER / _QUEUE (None:
+    unset); ``have_cost``: the planners have planned before, or -- fresh ones -- an earlier wave batch planned on the model;
+    ``retry``: the test expects the call to roll back (the all-in-LDS form then gives way to the next one)."""
+    cus = ctx.device_info()["n_cu"]
+    wave = model != "lane" and n_actions <= 64
+    if not wave:
+        return "saopd_lane" + ("_retry" if retry else "")
+    k = budget // n_actions
+    need = nodes_before + 1 + k * n_actions
+    tables = 3 * min(k + 3, 2560) * 8 + 128 * 4
+    lds_qcap = 4096
+    while lds_qcap < 2 * (1 + k * n_actions) and lds_qcap < (1 << 20):
+        lds_qcap <<= 1
+    if queue is not None:
+        qcap = 2
+        while qcap < queue:
+            qcap <<= 1
+        lds_qcap = min(lds_qcap, qcap)      # (a kept planner's queue only grows: the caller passes the size it has reached)
+    lds_res = ((tables + 15) & ~15) + 16 + need * 36 + n_states * 20 + lds_qcap * 4
+    fits = lds_res <= LDS_AVAIL
+    use_lds = fits and (n_planners <= cus if lds is None else lds == "1")
+    tab_lds = min(k + 3, (5 * 1024 - 32 - n_states * 40) // 24)
+    use_dict = tab_lds >= 16 and (dictionary is None or dictionary == "1")
+    if use_dict and lds is None:
+        use_lds = False
+    if device_arrays:
+        use_lds = False
+    if retry:
+        use_lds = False
+    ordered = (n_planners > 32 * cus if order is None else order == "1") and have_cost
+    return "saopd_wave{}{}{}".format("_lds" if use_lds else "_dict" if use_dict else "", "_ordered" if ordered else "",
+                                     "_retry" if retry else "")
+
+
+def uct_stoch_form(records, path_bits, n_actions, policy=False, generic=False):
+    """``records``: 0 rows and thresholds, 2 / 4 fused records, 1 compact records; ``path_bits`` 16 or 32; ``generic``:
+    MP_UCT_STOCH_GENERIC_A=1."""
+    unrolled = 2 <= n_actions <= 8 and not generic
+    return "uct_stoch_r{}_p{}_a{}{}".format(records, path_bits, n_actions if unrolled else "any", "_policy" if policy else "")

@@ -3,6 +3,8 @@ plus size-independent properties at the BASELINE.json sizes."""
 import numpy as np
 import pytest
 
+from tests.helpers import assert_form, opd_form, saopd_form
+
 pytestmark = pytest.mark.gpu
 
 
@@ -214,7 +216,8 @@ def test_uct_stream_continues_across_calls(ctx):
         s0 = t[s0, np.maximum(out["plans"][:, 0], 0)].astype(np.int32)
 
 
-def _cmp_opd(ctx, cfg, n_roots, budget, gamma, terminal_reward=0.0, seed=0, done_rule="source"):
+def _cmp_opd(ctx, cfg, n_roots, budget, gamma, terminal_reward=0.0, seed=0, done_rule="source", form=None, **knobs):
+    """``form``: the kernel form the test means, or ``knobs``: what it set, as tests.helpers.opd_form takes them."""
     from oracle import oracle
     t, r, term = cfg["transition"], cfg["reward"], cfg["terminal"]
     model = ctx.load_table(t, r, term, done_rule=done_rule)
@@ -223,6 +226,7 @@ def _cmp_opd(ctx, cfg, n_roots, budget, gamma, terminal_reward=0.0, seed=0, done
     rng_ref, rng0 = rng.copy(), rng.copy()
     mpl = budget // r.shape[1] + 2
     out = ctx.opd_plan(model, s0, budget, gamma, terminal_reward, rng, max_plan_len=mpl)
+    assert_form(ctx, form or opd_form(ctx, r.shape[1], budget, n_roots, general=terminal_reward < 0 or knobs.pop("general", False), **knobs))
     ref = oracle.opd_plan_batch(t, r, term, s0, budget, gamma, terminal_reward, rng_ref, done_rule=done_rule,
                                 max_plan_len=mpl, n_threads=8)
     np.testing.assert_array_equal(out["status"], ref["status"])
@@ -247,10 +251,11 @@ def _cmp_opd(ctx, cfg, n_roots, budget, gamma, terminal_reward=0.0, seed=0, done
 
 def _opd_variant(monkeypatch, variant):
     """MP_OPD_MODEL = lds | ldsx | global; "global_cls": the high-occupancy kernel with the residue-class layout of its
-    bounds array (MP_OPD_WIDE=cls; the default is the sibling layout, round 5)."""
+    bounds array (MP_OPD_WIDE=cls; the default is the sibling layout, round 5).  -> the knobs, as opd_form takes them."""
     monkeypatch.setenv("MP_OPD_MODEL", variant.split("_")[0])
     if variant.endswith("_cls"):
         monkeypatch.setenv("MP_OPD_WIDE", "cls")
+    return dict(model=variant.split("_")[0], wide="cls" if variant.endswith("_cls") else None)
 
 
 @pytest.mark.parametrize("variant", ["lds", "ldsx", "global", "global_cls"])
@@ -261,14 +266,15 @@ def test_opd_batch_highway_budget5000(ctx, variant, monkeypatch):
     from rl_agents_amd.envs import generators
     _opd_variant(monkeypatch, variant)
     cfg = generators.highway_shaped(10, 10, 100, seed=0)
-    _cmp_opd(ctx, cfg, 96, 5000, 0.8, seed=5)
+    _cmp_opd(ctx, cfg, 96, 5000, 0.8, seed=5, form={"lds": "opd_lds", "ldsx": "opd_ldsx", "global": "opd_wide_sib_small",
+                                                      "global_cls": "opd_wide_cls_small"}[variant])
 
 
 def test_opd_budget_beyond_lds(ctx):
-    """budget 25 000 (40 K of LDS would be 200 KB): only the HBM-resident bounds array can hold it."""
+    """budget 25 000 (40 K of LDS would be 200 KB): only the HBM-resident bounds array can hold it, in rows of 395 slots."""
     from rl_agents_amd.envs import generators
     cfg = generators.random_deterministic(500, 5, seed=77, terminal_rate=0.02)
-    _cmp_opd(ctx, cfg, 6, 25000, 0.9, seed=6)
+    _cmp_opd(ctx, cfg, 6, 25000, 0.9, seed=6, form="opd_wide_sib")
 
 
 @pytest.mark.parametrize("variant", ["lds", "ldsx", "global", "global_cls"])
@@ -276,9 +282,16 @@ def test_opd_budget_beyond_lds(ctx):
                                               (64, 640), (5, 10000)])     # (the last: more than 128 entries per class)
 def test_opd_batch_action_counts(ctx, n_actions, budget, variant, monkeypatch):
     from rl_agents_amd.envs import generators
-    _opd_variant(monkeypatch, variant)
+    """The wide kernels re-scan at most two slots per lane up to rows of 128 ("_small"); (5, 10000) has longer rows in both
+    layouts.  Every shape here fits the compact closing tables, (2, 101) and (3, 200) too: the node-array closing that |A| < 4
+    falls back to at other budgets is reached by tests/test_gpu_forms_reached.py (|A| = 2, budget 44)."""
+    knobs = _opd_variant(monkeypatch, variant)
     cfg = generators.random_deterministic(300, n_actions, seed=40 + n_actions, terminal_rate=0.05)
-    _cmp_opd(ctx, cfg, 70, budget, 0.9, terminal_reward=0.25, seed=n_actions)
+    form = opd_form(ctx, n_actions, budget, 70, **knobs)
+    assert form.startswith({"lds": "opd_lds", "ldsx": "opd_ldsx", "global": "opd_wide_sib", "global_cls": "opd_wide_cls"}[variant])
+    assert form.endswith("_small") == (variant.startswith("global") and budget != 10000)
+    assert not form.endswith("_chain")
+    _cmp_opd(ctx, cfg, 70, budget, 0.9, terminal_reward=0.25, seed=n_actions, form=form)
 
 
 @pytest.mark.parametrize("variant", ["lds", "global", "global_cls"])
@@ -290,11 +303,12 @@ def test_opd_children_an_ulp_above_their_parent(ctx, gamma, variant, monkeypatch
     maximum across expansions and must notice; plans, bounds, generator states and whole trees vs the oracle."""
     from rl_agents_amd.envs import generators
     _opd_variant(monkeypatch, variant)
+    form = {"lds": "opd_lds", "global": "opd_wide_sib_small", "global_cls": "opd_wide_cls_small"}[variant]
     cfg = generators.random_deterministic(200, 5, seed=310, terminal_rate=0.02)
     ones = dict(cfg, reward=np.ones_like(cfg["reward"]))
-    _cmp_opd(ctx, ones, 40, 1500, gamma, seed=int(gamma * 100))
+    _cmp_opd(ctx, ones, 40, 1500, gamma, seed=int(gamma * 100), form=form)
     two = dict(cfg, reward=np.where(cfg["reward"] > 0.5, 1.0, 0.5))
-    _cmp_opd(ctx, two, 40, 1500, gamma, terminal_reward=0.5, seed=int(gamma * 100) + 1)
+    _cmp_opd(ctx, two, 40, 1500, gamma, terminal_reward=0.5, seed=int(gamma * 100) + 1, form=form)
 
 
 @pytest.mark.parametrize("n_actions,budget", [(65, 650), (100, 1999), (130, 1300), (257, 2000)])
@@ -304,13 +318,13 @@ def test_opd_more_actions_than_lanes(ctx, n_actions, budget):
     from rl_agents_amd.envs import generators
     cfg = generators.random_deterministic(120, n_actions, seed=90 + n_actions, terminal_rate=0.05)
     cfg = dict(cfg, reward=np.round(cfg["reward"], 1))
-    _cmp_opd(ctx, cfg, 40, budget, 0.9, terminal_reward=0.25, seed=n_actions)
-    _cmp_opd(ctx, cfg, 5, budget, 0.7, terminal_reward=-0.5, seed=n_actions + 1, done_rule="next")
+    _cmp_opd(ctx, cfg, 40, budget, 0.9, terminal_reward=0.25, seed=n_actions, form="opd_any")
+    _cmp_opd(ctx, cfg, 5, budget, 0.7, terminal_reward=-0.5, seed=n_actions + 1, done_rule="next", form="opd_any")
     # more than 64 children tie for the plan's choice (constant rewards; gamma = 0 makes whole levels tie): the fuzz sweep found
     # the ORACLE capping its tie list at 64 entries there -- random_argmax draws among all of them (abstract.py:304-311)
     flat = dict(cfg, reward=np.full_like(cfg["reward"], 0.5))
-    _cmp_opd(ctx, flat, 6, budget, 0.9, seed=n_actions + 2)
-    _cmp_opd(ctx, cfg, 6, budget, 0.0, seed=n_actions + 3)
+    _cmp_opd(ctx, flat, 6, budget, 0.9, seed=n_actions + 2, form="opd_any")
+    _cmp_opd(ctx, cfg, 6, budget, 0.0, seed=n_actions + 3, form="opd_any")
 
 
 @pytest.mark.parametrize("variant", ["lds", "ldsx"])
@@ -322,10 +336,11 @@ def test_opd_closing_passes_on_the_node_array(ctx, n_actions, budget, variant, m
     monkeypatch.setenv("MP_OPD_MODEL", variant)
     monkeypatch.setenv("MP_OPD_CLOSING", "chain")
     cfg = generators.random_deterministic(300, n_actions, seed=140 + n_actions, terminal_rate=0.05)
-    _cmp_opd(ctx, cfg, 70, budget, 0.9, terminal_reward=0.25, seed=n_actions)
+    form = "opd_{}_chain".format(variant)
+    _cmp_opd(ctx, cfg, 70, budget, 0.9, terminal_reward=0.25, seed=n_actions, form=form)
     cfg = generators.highway_shaped(6, 8, 40, seed=2)
     if n_actions == 5:
-        _cmp_opd(ctx, cfg, 70, budget, 0.95, seed=3)
+        _cmp_opd(ctx, cfg, 70, budget, 0.95, seed=3, form=form)
 
 
 @pytest.mark.parametrize("variant", ["lds", "ldsx", "global", "global_cls"])
@@ -335,8 +350,10 @@ def test_opd_general_main_loop_where_the_fast_one_applies(ctx, variant, monkeypa
     from rl_agents_amd.envs import generators
     _opd_variant(monkeypatch, variant)
     monkeypatch.setenv("MP_OPD_LOOP", "0")
-    _cmp_opd(ctx, generators.highway_shaped(6, 8, 40, seed=2), 70, 2500, 0.95, seed=3)
-    _cmp_opd(ctx, generators.random_deterministic(300, 7, seed=11, terminal_rate=0.05), 70, 700, 0.9, terminal_reward=0.25, seed=5)
+    form = {"lds": "opd_lds_gen", "ldsx": "opd_ldsx_gen", "global": "opd_wide_sib_small_gen", "global_cls": "opd_wide_cls_small_gen"}[variant]
+    _cmp_opd(ctx, generators.highway_shaped(6, 8, 40, seed=2), 70, 2500, 0.95, seed=3, form=form)
+    _cmp_opd(ctx, generators.random_deterministic(300, 7, seed=11, terminal_rate=0.05), 70, 700, 0.9, terminal_reward=0.25, seed=5,
+             form=form)
 
 
 def test_opd_negative_terminal_reward_lowers_an_expanded_node(ctx):
@@ -643,12 +660,15 @@ def test_lds_atomics_apply_in_lane_order(ctx):
     assert ctx.selftest_lds_atomic_order(131072) == 0
 
 
-@pytest.mark.parametrize("mapping", ["wave", "wave-serial-prune", "wave-par-backup", "wave-seq-backup", "wave-global", "wave-ordered",
-                                     "wave-flat", "wave-buckets", "lane"])
+@pytest.mark.parametrize("mapping", ["wave", "wave-serial-prune", "wave-par-backup", "wave-seq-backup", "wave-global", "wave-plain",
+                                     "wave-ordered", "wave-flat", "wave-buckets", "lane"])
 @pytest.mark.parametrize("shape", ["grid", "garnet", "highway"])
 def test_state_aware_batch_vs_oracle(ctx, shape, mapping, monkeypatch):
     """200 planners per launch, three consecutive plans each (planner state kept on the device), vs the oracle run
-    planner by planner; ragged outcomes included (planners whose leaves all get pruned report MP_ERR_ARG)."""
+    planner by planner; ragged outcomes included (planners whose leaves all get pruned report MP_ERR_ARG).
+    The forms: grid and garnet keep their dictionaries in LDS (saopd_wave_dict).  The highway's 120 states leave no room for them
+    beside the depth tables, and "wave-global" switches them off: 200 planners are fewer than the compute units, so the whole
+    arena goes to LDS there (saopd_wave_lds); "wave-plain" keeps that off too and runs everything from global memory."""
     from oracle import oracle
     from rl_agents_amd import native
     from rl_agents_amd.envs import generators
@@ -659,8 +679,10 @@ def test_state_aware_batch_vs_oracle(ctx, shape, mapping, monkeypatch):
         monkeypatch.setenv("MP_SAOPD_PAR_BACKUP", "1")   # chunked lists are rebuilt from the linked ones by the later plans
     if mapping == "wave-seq-backup":        # ... and in none: the element-by-element loop
         monkeypatch.setenv("MP_SAOPD_PAR_BACKUP", "0")
-    if mapping == "wave-global":            # round 4: the dictionaries stay in global memory (default: LDS where they fit)
+    if mapping in ("wave-global", "wave-plain"):    # round 4: the dictionaries stay in global memory (default: LDS where they fit)
         monkeypatch.setenv("MP_SAOPD_DICT", "0")
+    if mapping == "wave-plain":             # ... and so does the arena
+        monkeypatch.setenv("MP_SAOPD_LDS", "0")
     if mapping == "wave-ordered":           # round 4: dispatch by expected cost also for this small batch (default: > 32 per CU)
         monkeypatch.setenv("MP_SAOPD_ORDER", "1")
     if mapping == "wave-flat":              # round 4: the earlier plans' rows as one flat list in every plan ...
@@ -684,8 +706,19 @@ def test_state_aware_batch_vs_oracle(ctx, shape, mapping, monkeypatch):
     ref_rng = rng.copy()
     ref_planner = [None] * n
     dead = np.zeros(n, bool)
+    knobs = dict(model=mapping.split("-")[0], dictionary="0" if mapping in ("wave-global", "wave-plain") else None,
+                 lds="0" if mapping == "wave-plain" else None, order="1" if mapping == "wave-ordered" else None)
+    n_states, n_actions = r.shape
     for step in range(3):
         out = planners.plan(states, budget, gamma, 0.0, rng)
+        form = saopd_form(ctx, n_states, n_actions, budget, n, nodes_before=step * (1 + budget // n_actions * n_actions),
+                          have_cost=step > 0 or mapping == "wave-ordered", **knobs)
+        assert_form(ctx, form)
+        assert form.startswith("saopd_lane" if mapping == "lane" else "saopd_wave")
+        assert form.endswith("_ordered") == (mapping == "wave-ordered")
+        if mapping != "lane":
+            assert form.split("_")[2:3] == (["lds"] if mapping == "wave-global" else [] if mapping == "wave-plain" else
+                                            ["lds"] if shape == "highway" else ["dict"])
         for i in range(n):
             if dead[i]:
                 continue
@@ -735,6 +768,9 @@ def test_state_aware_many_actions_vs_oracle(ctx, n_actions):
     compared = 0
     for step in range(3):
         out = planners.plan(states, budget, 0.85, 0.0, rng)
+        # (12 expansions: fewer depth entries than the 16 the LDS dictionaries are for -- the arena goes to LDS instead)
+        assert_form(ctx, saopd_form(ctx, n_states, n_actions, budget, n, nodes_before=step * (1 + budget)))
+        assert ctx.last_kernel_variant() == ("saopd_lane" if n_actions > 64 else "saopd_wave_lds")
         for i in range(n):
             if dead[i]:
                 continue
@@ -780,6 +816,7 @@ def test_state_aware_large_budgets_vs_oracle(ctx, shape, dict_lds, monkeypatch):
     rng = _rng_states(n, base=77)
     ref_rng = rng.copy()
     out = planners.plan(states, budget, 0.8, 0.0, rng, max_plan_len=budget + 1)
+    assert_form(ctx, "saopd_wave_dict" if dict_lds == "1" else "saopd_wave")     # (neither arena fits the LDS)
     for i in range(n):
         o = oracle.saopd_plan(t, r, term, int(states[i]), budget, 0.8, rng_state=ref_rng[i], max_plan_len=budget + 1)
         assert out["status"][i] == 0
@@ -820,6 +857,7 @@ def test_state_aware_long_lists_vs_oracle(ctx, n_states, n_actions, budget, prun
     compared = 0
     for step in range(5):
         out = planners.plan(states, budget, 0.9, 0.0, rng)
+        assert_form(ctx, "saopd_wave_dict")
         for i in range(n):
             if dead[i]:
                 continue
@@ -858,6 +896,7 @@ def test_state_aware_queue_overflow_is_reported(ctx, monkeypatch):
     planners = native.StateAwarePlanners(ctx, model, 64)
     rng = _rng_states(64, base=5)
     out = planners.plan(np.arange(64, dtype=np.int32), 400, 0.8, 0.0, rng, max_plan_len=4)
+    assert_form(ctx, "saopd_wave_dict")      # (no "_retry": there is no room to run again)
     assert (out["status"] == native.MP_ERR_ALLOC).any() and set(np.unique(out["status"])) <= {0, native.MP_ERR_ALLOC}
     # a planner left with a full queue has lost backups: it stays failed, loudly, in every later call
     again = planners.plan(np.arange(64, dtype=np.int32), 8, 0.8, 0.0, rng, max_plan_len=4)
@@ -888,6 +927,9 @@ def test_state_aware_device_mode_is_asynchronous_and_loud(ctx, monkeypatch):
         torch.cuda.synchronize()  # (the uploads ran on torch's stream, the plan runs on the context's)
         planners.plan_device(d["root"], b, 0.8, 0.0, d["rng"], mpl, plans=d["plans"], plan_len=d["plan_len"],
                              env_steps=d["env_steps"], updates=d["updates"], status=d["status"])
+        # (device arrays: never the all-in-LDS form, never a retry; the two expansions of budget 8 leave the dictionaries no use)
+        assert_form(ctx, saopd_form(ctx, 100, 4, b, n, device_arrays=True))
+        assert ctx.last_kernel_variant() == ("saopd_wave_dict" if b == budget else "saopd_wave")
         ctx.synchronize()
         return {k: v.cpu().numpy() for k, v in d.items()}
 
@@ -949,7 +991,9 @@ def test_results_do_not_depend_on_batch_composition(ctx):
 
     def opd(idx):
         rng = np.ascontiguousarray(rng0[idx])
-        return ctx.opd_plan(model, s0[idx], 400, 0.8, 0.0, rng, max_plan_len=81)
+        out = ctx.opd_plan(model, s0[idx], 400, 0.8, 0.0, rng, max_plan_len=81)
+        assert_form(ctx, "opd_lds")
+        return out
     full, part = opd(np.arange(4000)), opd(np.arange(0, 4000, 7))
     for k in ("plans", "env_steps", "status"):
         np.testing.assert_array_equal(full[k][::7], part[k], err_msg=k)
@@ -962,6 +1006,7 @@ def test_results_do_not_depend_on_batch_composition(ctx):
         planners = native.StateAwarePlanners(ctx, gmodel, len(idx))
         rng = np.ascontiguousarray(rng0[idx])
         out = planners.plan((s0[idx] % 100).astype(np.int32), 200, 0.8, 0.0, rng, max_plan_len=8)
+        assert_form(ctx, "saopd_wave_dict")
         planners.close()
         return out
     full, part = sa(np.arange(3000)), sa(np.arange(0, 3000, 7))
@@ -969,6 +1014,9 @@ def test_results_do_not_depend_on_batch_composition(ctx):
         np.testing.assert_array_equal(full[k][::7], part[k], err_msg=k)
     for x in (policy, model, gmodel):
         x.close()
+
+
+ROLLED_BACK = {"wave": (False, True, False), "lane": (False, True, False)}     # which of the three plans fill the queue they find
 
 
 @pytest.mark.parametrize("mapping", ["wave", "lane"])
@@ -994,6 +1042,9 @@ def test_state_aware_queue_grows_by_rollback(ctx, mapping, monkeypatch):
     most = 0
     for step, budget in enumerate((8, 120, 120)):   # the small first plan leaves state behind: the next one rolls back non-fresh planners
         out = planners.plan(states, budget, 0.9, 0.0, rng)
+        # (two expansions need fewer depth entries than the LDS dictionaries are for: the first plan asks for the arena in LDS)
+        assert_form(ctx, saopd_form(ctx, 3, 4, budget, n, nodes_before=(0, 9, 130)[step], model=mapping, queue=256,
+                                    retry=ROLLED_BACK[mapping][step], have_cost=step > 0))
         assert (out["status"] == 0).all(), out["status"]
         most = max(most, int(out["updates"].max()))
         for i in range(n):

@@ -21,17 +21,22 @@ middle); a masked table where k < |A|.
   UCT one model per root: uct_lone_each, uct_row_each, uct_global / uct_global      3, 6, 7 / 70, 150     same
   UCT uct_cartpole, replicas of 64 (the default at this batch), 16, 4 and 1 lanes   2 (never rejects)     buffered half on entry only
   mp_uct_plan_stochastic open / closed loop, dense / sparse                         3, 6, 7, 70, 150      2nd episode's root tie
-  OPD lds, ldsx, global, global_cls / the plain kernel; mp_opd_plan_models          3, 6, 7 / 3, 70, 150  the plan's first choice
-  robust OPD; state-aware OPD, wave and lane                                        3, 6, 7, 70, 150      the plan's first choice
+  OPD opd_lds, opd_ldsx, opd_wide_sib_small, opd_wide_cls_small / opd_any;
+      mp_opd_plan_models (opd_lds / opd_any)                                        3, 6, 7 / 3, 70, 150  the plan's first choice
+  robust OPD ropd_lds_m2 / ropd_any                                                 3, 6, 7 / 70, 150     the plan's first choice
+  state-aware OPD saopd_lane; "wave": saopd_wave_lds (three expansions leave the
+      LDS dictionaries no use, 28 planners take the arena to LDS)                   3, 6, 7, 70, 150      the plan's first choice
+      / saopd_lane (more actions than lanes, whatever the mapping asked for)        (wave: 70, 150)
+      saopd_wave ("wave-plain"), saopd_wave_dict ("wave-dict": 13 expansions;
+      saopd_wave_dict_retry at k = 6 and 7, whose backups fill the queue once)      3, 6, 7               the plan's first choice
   OLOP (uniform continuation)                                                       3, 6, 7, 70, 150      first continuation draw (after
                                                                                                           the episode's seed word)
   BRUE (the rollout's integers(|A|))                                                3, 6, 7, 70, 150      first action draw (same)
   GBOP-D                                                                            3, 6, 7, 70, 150      the sampling rule's first tie
 
-The variant is asserted by name for every UCT form; OLOP, BRUE and GBOP-D name two variants each (kept / slot trees, LDS /
-global graph) that the library chooses by the batch's memory, and the test asserts that one of the two ran.  OPD, robust OPD,
-state-aware OPD and mp_uct_plan_stochastic record no variant name: their forms are selected by the knobs their own tests use
-and cannot be asserted.  SKIPPED_FORMS lists what could not be selected at these shapes.
+The form is asserted by name in every test: mp_uct_plan_stochastic runs uct_stoch_r0 (dense rows), r4 (sparse rows of 3 and 4),
+r1 / r2 (sparse rows of 2: compact records / kept at 32 bytes) with 16-bit path entries; these small batches run olop_global,
+brue_global and gbopd_wave_lds.  SKIPPED_FORMS lists what could not be selected at these shapes.
 
 The quad, row and CartPole forms share generator work by jump-ahead: reject3 and buffered_plain hand them has_uint32 = 1.
 (OLOP and BRUE draw a seed word first, which leaves room for two forged rejections: their batches hold no reject3.)
@@ -55,7 +60,7 @@ import pytest
 
 from tests import forge
 from tests.helpers import CDF_ROWS as ROWS
-from tests.helpers import bfs_by_parent, generator_from, stochastic_model, value_table, zero_table
+from tests.helpers import assert_form, bfs_by_parent, generator_from, stochastic_model, uct_stoch_form, value_table, zero_table
 
 pytestmark = pytest.mark.gpu
 
@@ -66,7 +71,7 @@ N_TIE = 4 * len(forge.TIE_CASES)          # 28 roots: every case with four diffe
 UCT_KNOBS = ("MP_UCT_MODEL", "MP_UCT_QUAD", "MP_UCT_LONE", "MP_UCT_LONE_WAVES", "MP_UCT_EACH", "MP_UCT_ROW", "MP_UCT_ROWS",
              "MP_UCT_ROW_WAVES", "MP_UCT_ROW_ROOTS", "MP_UCT_PATH", "MP_UCT_LANES", "MP_UCT_LDSR_WAVES", "MP_UCT_CART_REP",
              "MP_UCT_CART_WAVES", "MP_UCT_POLICY_RECORD", "MP_UCT_COARSE_BITS", "MP_UCT_STOCH_FUSED", "MP_UCT_STOCH_GENERIC_A",
-             "MP_OPD_MODEL", "MP_OPD_WIDE", "MP_SAOPD_MODEL")
+             "MP_OPD_MODEL", "MP_OPD_WIDE", "MP_SAOPD_MODEL", "MP_SAOPD_DICT", "MP_SAOPD_LDS")
 UCT_TABLE_FORMS = [("uct_global", "MP_UCT_MODEL=global"), ("uct_global_spill", "MP_UCT_MODEL=global MP_UCT_PATH=spill"),
                    ("uct_ldsr", "MP_UCT_MODEL=ldsr"), ("uct_quad", "MP_UCT_QUAD=1"), ("uct_row_shared", "MP_UCT_ROWS=1"),
                    ("uct_row_shared", "MP_UCT_ROWS=1 MP_UCT_ROW_ROOTS=4 MP_UCT_ROW_WAVES=2"), ("uct_lone", ""),
@@ -348,7 +353,8 @@ def same_parent_tree(tree, ref, keys):
         assert np.array_equal(np.asarray(tree[k])[oa], np.asarray(ref[k])[ob]), k
 
 
-def check_stochastic(ctx, cfg, s0, episodes, horizon, prior, rollout, rng, erng, closed, trees=()):
+def check_stochastic(ctx, cfg, s0, episodes, horizon, prior, rollout, rng, erng, closed, records, trees=()):
+    """``records``: the form of the model's step records (tests.helpers.uct_stoch_form)."""
     from oracle import oracle
     if cfg["mode"] == "sparse":
         model = ctx.load_sparse(cfg["transition"], cfg["next"], cfg["reward"], None)
@@ -358,6 +364,7 @@ def check_stochastic(ctx, cfg, s0, episodes, horizon, prior, rollout, rng, erng,
     mpl = (2 if closed else 1) * horizon
     out = ctx.uct_plan_stochastic(model, s0, episodes, horizon, GAMMA, TEMPERATURE, prior, rollout, rng, env_rng_state=erng,
                                   closed_loop=closed, max_plan_len=mpl)
+    assert_form(ctx, uct_stoch_form(records, 16, len(prior)))
     ref = oracle.uct_plan_stoch_batch(cfg["mode"], cfg["transition"], cfg["reward"], None, s0, episodes, horizon, GAMMA, TEMPERATURE,
                                       prior, rollout, rng_ref, erng, next_states=cfg["next"], closed_loop=closed, max_plan_len=mpl)
     for k in ("plans", "plan_len", "env_steps"):
@@ -383,7 +390,8 @@ def test_stochastic_uct_tie_draws(ctx, monkeypatch, kind, closed, k):
     rng, names = forge.tie_batch(k, N_TIE, skip=horizon)
     erng = native.seed_sequence_states((), 900 + k, N_TIE)
     p = np.ones(k) / k
-    check_stochastic(ctx, cfg, tie_roots(), 5, horizon, p, p, rng, erng, closed, trees=case_roots(names, "reject3", "reject2"))
+    check_stochastic(ctx, cfg, tie_roots(), 5, horizon, p, p, rng, erng, closed, 0 if kind == "stochastic" else 4,
+                     trees=case_roots(names, "reject3", "reject2"))
 
 
 @pytest.mark.parametrize("row", ["uniform2", "uniform3", "uniform5", "uniform8", "uniform9", "zeros"])
@@ -397,7 +405,7 @@ def test_stochastic_uct_first_rollout_draw_on_every_threshold(ctx, monkeypatch, 
     s0 = (np.arange(len(draws)) * 5 % S).astype(np.int32)
     erng = native.seed_sequence_states((), 77, len(draws))
     check_stochastic(ctx, stochastic_model(kind, S, a, zero_rewards=False), s0, 4, 5, np.ones(a) / a, rollout, cdf_records(draws), erng,
-                     closed=(a % 2 == 0), trees=(0, len(draws) - 1))
+                     closed=(a % 2 == 0), records=0 if kind == "stochastic" else 4, trees=(0, len(draws) - 1))
 
 
 @pytest.mark.parametrize("kind,width,knobs", [("stochastic", 0, ""), ("sparse", 2, ""), ("sparse", 2, "MP_UCT_STOCH_FUSED=2"),
@@ -411,6 +419,8 @@ def test_stochastic_uct_model_rows_on_every_threshold(ctx, monkeypatch, kind, wi
     from rl_agents_amd import native
     set_knobs(monkeypatch, knobs)
     a = 3
+    records = {("stochastic", 0, ""): 0, ("sparse", 2, ""): 1, ("sparse", 2, "MP_UCT_STOCH_FUSED=2"): 2, ("sparse", 3, ""): 4,
+               ("sparse", 4, ""): 4, ("sparse", 5, ""): 0, ("sparse", 3, "MP_UCT_STOCH_FUSED=0"): 0}[(kind, width, knobs)]
     cfg = stochastic_model(kind, S, a, zero_rewards=False, width=width)
     draws = []
     for s in range(S):
@@ -424,7 +434,7 @@ def test_stochastic_uct_model_rows_on_every_threshold(ctx, monkeypatch, kind, wi
         erng = cdf_records([d for _, d in part])
         rng = native.seed_sequence_states((), 55 + lo, len(part))
         p = np.ones(a) / a
-        check_stochastic(ctx, cfg, s0, 4, 4, p, p, rng, erng, closed=True, trees=(0,))
+        check_stochastic(ctx, cfg, s0, 4, 4, p, p, rng, erng, closed=True, records=records, trees=(0,))
 
 
 # ---- mp_env_step_stochastic: one draw per call ---------------------------------------------------------------------------------
@@ -501,6 +511,8 @@ def test_opd_tie_draws(ctx, monkeypatch, variant, k):
     rng0, rng_ref = rng.copy(), rng.copy()
     budget, s0 = 3 * n_actions, tie_roots()
     out = ctx.opd_plan(model, s0, budget, 0.8, 0.0, rng, max_plan_len=8)
+    assert_form(ctx, "opd_any" if n_actions > 64 else {"lds": "opd_lds", "ldsx": "opd_ldsx", "global": "opd_wide_sib_small",
+                                                        "global_cls": "opd_wide_cls_small", "default": "opd_lds"}[variant])
     ref = oracle.opd_plan_batch(t, r, term, s0, budget, 0.8, 0.0, rng_ref, max_plan_len=8, available=avail)
     for key in ("status", "plans", "plan_len", "env_steps"):
         np.testing.assert_array_equal(out[key], ref[key], err_msg=key)
@@ -528,6 +540,7 @@ def test_opd_tie_draws_one_model_per_root(ctx, monkeypatch, k):
     rng, _ = forge.tie_batch(k, N_TIE)
     rng0, rng_ref = rng.copy(), rng.copy()
     out = ctx.opd_plan(model, tie_roots(), 3 * k, 0.8, 0.0, rng, max_plan_len=8, model_index=mi)
+    assert_form(ctx, "opd_any" if k > 64 else "opd_lds")
     ref = oracle.opd_plan_each(tr, rw, tm, mi, tie_roots(), 3 * k, 0.8, 0.0, rng_ref, max_plan_len=8)
     for key in ("status", "plans", "plan_len", "env_steps"):
         np.testing.assert_array_equal(out[key], ref[key], err_msg=key)
@@ -550,6 +563,7 @@ def test_robust_opd_tie_draws(ctx, monkeypatch, k):
     rng0, rng_ref = rng.copy(), rng.copy()
     budget, s0 = 3 * n_actions, tie_roots()
     out = ctx.ropd_plan(joint, s0, budget, 0.8, 0.0, rng, max_plan_len=8)
+    assert_form(ctx, "ropd_any" if n_actions > 64 else "ropd_lds_m2")
     ref = oracle.ropd_plan_batch(tm, rm, None, np.repeat(s0[:, None], 2, axis=1), budget, 0.8, 0.0, rng_ref, max_plan_len=8, available=av)
     for key in ("status", "plans", "plan_len", "env_steps"):
         np.testing.assert_array_equal(out[key], ref[key], err_msg=key)
@@ -565,22 +579,32 @@ def test_robust_opd_tie_draws(ctx, monkeypatch, k):
     joint.close()
 
 
-@pytest.mark.parametrize("k", [3, 6, 7, 70, 150])
-@pytest.mark.parametrize("mapping", ["wave", "lane"])
+SAOPD_MAPPINGS = {"wave": ("MP_SAOPD_MODEL=wave", "saopd_wave_lds", 3), "lane": ("MP_SAOPD_MODEL=lane", "saopd_lane", 3),
+                  "wave-plain": ("MP_SAOPD_MODEL=wave MP_SAOPD_DICT=0 MP_SAOPD_LDS=0", "saopd_wave", 3),
+                  "wave-dict": ("MP_SAOPD_MODEL=wave", "saopd_wave_dict", 13)}     # mapping -> knobs, form, expansions
+
+
+@pytest.mark.parametrize("mapping,k", [(m, k) for m in ("wave", "lane") for k in (3, 6, 7, 70, 150)] +
+                         [(m, k) for m in ("wave-plain", "wave-dict") for k in (3, 6, 7)])
 def test_state_aware_opd_tie_draws(ctx, monkeypatch, mapping, k):
     """(get_plan runs twice per plan and the second descent is returned: the forged tie is the first one's, seen in the record
-    after the plan and in everything the second descent draws.)"""
+    after the plan and in everything the second descent draws.)  More than 64 actions plan on the lane kernel whatever the
+    mapping asks for.  Three expansions need fewer depth entries than the LDS dictionaries are for, so "wave" keeps the whole
+    arena of these 28 planners in LDS; "wave-dict" plans 13 expansions."""
     from oracle import oracle
     from rl_agents_amd import native
-    set_knobs(monkeypatch, "MP_SAOPD_MODEL=" + mapping)
+    knobs, form, expansions = SAOPD_MAPPINGS[mapping]
+    set_knobs(monkeypatch, knobs)
     n_actions, k = masked_shape(k)
     t, r, term, avail = zero_table(S, n_actions, k)
     model = ctx.load_table(t, r, term, available=avail)
     planners = native.StateAwarePlanners(ctx, model, N_TIE)
     rng, _ = forge.tie_batch(k, N_TIE)
     rng0 = rng.copy()
-    budget, s0 = 3 * n_actions, tie_roots()
+    budget, s0 = expansions * n_actions, tie_roots()
     out = planners.plan(s0, budget, 0.8, 0.0, rng)
+    # (zero rewards keep the backups going: 13 expansions of 6 or 7 tied actions fill the queue once, and the plan runs again)
+    assert_form(ctx, "saopd_lane" if n_actions > 64 else form + ("_retry" if mapping == "wave-dict" and k in (6, 7) else ""))
     for i in range(N_TIE):
         o = oracle.saopd_plan(t, r, term, int(s0[i]), budget, 0.8, rng_state=rng0[i], max_plan_len=budget + 1, available=avail)
         assert out["status"][i] == 0, i
@@ -612,7 +636,7 @@ def test_olop_tie_draws(monkeypatch, k):
     rng, names = forge.tie_batch(k, N_TIE, lead=1)
     rng0, roots = rng.copy(), tie_roots()
     out = planner.plan_batch(env, roots, rng_states=rng)
-    assert planner.models.ctx.last_kernel_variant() in ("olop_global", "olop_global_slots")
+    assert_form(planner.models.ctx, "olop_global")
     for i in range(N_TIE):
         res, rng_after = restated_root(t, r, term, roots[i], dict(planner.config), rng0[i], avail if k < n_actions else None)
         n = int(out["plan_len"][i])
@@ -640,7 +664,7 @@ def test_brue_action_draws(monkeypatch, k):
     rng0, roots = rng.copy(), tie_roots()
     out = planner.plan_batch(env, roots, rng_states=rng)
     assert (out["status"] == 0).all()
-    assert planner.models.ctx.last_kernel_variant() in ("brue_global", "brue_global_slots")
+    assert_form(planner.models.ctx, "brue_global")
     for i in range(N_TIE):
         res, rng_after = restated_root(tab, roots[i], planner.config, rng0[i])
         assert out["plans"][i].tolist() == res["plan"].tolist(), i
@@ -665,7 +689,7 @@ def test_gbopd_tie_draws(ctx, monkeypatch, k):
     rng0, roots = rng.copy(), tie_roots()
     budget, gamma = 4 * n_actions, 0.9
     out = planners.plan(roots, budget, gamma, 1 / (1 - gamma), 1e-2, 5, rng)
-    assert ctx.last_kernel_variant() in ("gbopd_wave_lds", "gbopd_wave_global")
+    assert_form(ctx, "gbopd_wave_lds")
     assert (out["status"] == 0).all()
     for i in range(N_TIE):
         gen = generator_from(rng0[i])

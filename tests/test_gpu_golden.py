@@ -232,16 +232,24 @@ def test_uct_state_policies_subtree_golden(ctx, golden):
     model.close()
 
 
-@pytest.mark.parametrize("mapping", ["wave", "wave-global", "lane"])
+@pytest.mark.parametrize("mapping", ["wave", "wave-global", "wave-plain", "lane"])
 def test_state_aware_planner_golden_episodes(ctx, golden, mapping, monkeypatch):
     """(one planner per wavefront / per lane) mp_saopd_plan vs the unmodified StateAwarePlannerAgent over multi-plan episodes: plans, trees, leaves sets,
     state-value tables, env-step counts and generator state, with the planner state carried across plans; where
-    the reference raises (every leaf pruned) the planner reports MP_ERR_ARG."""
+    the reference raises (every leaf pruned) the planner reports MP_ERR_ARG.
+    One planner is fewer than the compute units: without the dictionaries ("wave-global", and "wave" on the highway's 120 states
+    or at a budget of fewer than 13 expansions) its whole arena sits in LDS; "wave-plain" plans from global memory."""
     from rl_agents_amd import native
-    from tests.helpers import replay_state_aware_episode
+    from tests.helpers import assert_form, replay_state_aware_episode, saopd_form
     monkeypatch.setenv("MP_SAOPD_MODEL", mapping.split("-")[0])
-    if mapping == "wave-global":    # (round 4: the default wave kernel keeps the per-state dictionaries in LDS; this one does not)
+    if mapping in ("wave-global", "wave-plain"):    # (round 4: the default wave kernel keeps the per-state dictionaries in LDS)
         monkeypatch.setenv("MP_SAOPD_DICT", "0")
+    if mapping == "wave-plain":
+        monkeypatch.setenv("MP_SAOPD_LDS", "0")
+    knobs = dict(model=mapping.split("-")[0], dictionary=None if mapping in ("wave", "lane") else "0",
+                 lds="0" if mapping == "wave-plain" else None)
+    want = {"wave-global": ("saopd_wave_lds",), "wave-plain": ("saopd_wave",), "lane": ("saopd_lane",),
+            "wave": ("saopd_wave_dict", "saopd_wave_lds")}[mapping]
     z = golden["state_aware"]
     for name in [str(n) for n in z["sa/names"]]:
         cfg = mdp_from_golden(z, "sa/{}/mdp".format(name))
@@ -250,9 +258,13 @@ def test_state_aware_planner_golden_episodes(ctx, golden, mapping, monkeypatch):
 
         def plan_fn(cfg, s0, params, rng, planner_state):
             rng = np.array(rng, dtype=np.uint64).reshape(1, 6)
+            before = planners.info()["n_nodes"]
             out = planners.plan([s0], params["budget"], params["gamma"], params["terminal_reward"], rng,
                                 accuracy=params["accuracy"], backup_aggregated_nodes=params["backup_aggregated_nodes"],
                                 prune_suboptimal_leaves=params["prune_suboptimal_leaves"])
+            form = saopd_form(ctx, cfg["reward"].shape[0], cfg["reward"].shape[1], params["budget"], 1, nodes_before=before, **knobs)
+            assert_form(ctx, form)
+            assert form in want
             if out["status"][0] == native.MP_ERR_ARG:
                 raise ValueError("max() arg is an empty sequence")
             assert out["status"][0] == 0

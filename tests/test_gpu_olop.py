@@ -10,6 +10,7 @@ from rl_agents_amd import native
 from rl_agents_amd.agents.common.factory import agent_factory
 from rl_agents_amd.envs import FiniteMDPEnv, MaskedFiniteMDPEnv, OrderedMaskedFiniteMDPEnv, generators
 from tests import olop_restatement as olr
+from tests.helpers import assert_form
 from tests.test_olop_host import GOLDEN, OLOP_AGENT, generator_from, golden_case, names
 
 pytestmark = pytest.mark.gpu
@@ -134,12 +135,13 @@ def restated_root(tr, rw, term, s0, cfg, rng6, available=None, order=None):
     return res, native.rng_state_from_generator(gen)
 
 
-def check_batch(env, cfg, roots, sample, available=None, order=None, tree_roots=()):
+def check_batch(env, cfg, roots, sample, available=None, order=None, tree_roots=(), form="olop_global"):
     agent = agent_factory(env, dict(cfg, __class__=OLOP_AGENT))
     pc = agent.planner.config
     rng = agent.planner.batch_rng_states(len(roots))
     rng0 = rng.copy()
     out = agent.planner.plan_batch(env, roots, rng_states=rng)
+    assert_form(agent.planner.models.ctx, form)
     mdp = env.mdp
     ref_cfg = dict(pc)
     for i in sample:
@@ -161,12 +163,15 @@ def check_batch(env, cfg, roots, sample, available=None, order=None, tree_roots=
 
 @pytest.mark.parametrize("n", [1, 256, 4096, 65536])
 def test_batches_against_the_restatement(n):
+    """A tree per root, kept for the export, while the batch's trees fit 1 GiB (olop_global); 65 536 roots share the slots of the
+    resident wavefronts (olop_global_slots: only root 0's tree is kept)."""
     grid = generators.gridworld()
     env = env_of(grid["transition"], grid["reward"], grid["terminal"], 0)
     cfg = {"gamma": 0.8, "budget": 500, "upper_bound": {"type": "kullback-leibler"}, "continuation_type": "uniform"}
     roots = (np.arange(n) * 37 % 100).astype(np.int32)
     sample = sorted({0, n - 1, n // 2, n // 3, (7 * n) // 9})
-    check_batch(env, cfg, roots, sample, tree_roots=(0, n - 1) if n <= 4096 else (0,))
+    check_batch(env, cfg, roots, sample, tree_roots=(0, n - 1) if n <= 4096 else (0,),
+                form="olop_global" if n <= 4096 else "olop_global_slots")
 
 
 def test_highway_shaped_batch_with_restricted_actions():

@@ -119,6 +119,28 @@ def test_vi_batch_vs_sequential_oracle(ctx, shape, n, gamma, iters):
     model.close()
 
 
+@pytest.mark.parametrize("n_states,n_actions,own,block", [(64, 3, 1, 64), (65, 2, 2, 64), (128, 4, 2, 64), (129, 5, 2, 128),
+                                                          (257, 3, 2, 256), (513, 4, 4, 256), (1025, 6, 4, 512),
+                                                          (2048, 8, 4, 512), (2049, 3, 4, 1024), (4096, 4, 4, 1024)])
+def test_vi_batch_register_forms(ctx, n_states, n_actions, own, block):
+    """The register-resident forms by name, at the first and the last state count of their ranges: ``own`` states per thread of
+    a workgroup of ``block`` threads (the last form for at most four actions only) -- Q and sweeps of sequential oracle solves."""
+    from oracle import oracle
+    from tests.helpers import assert_form
+    g = np.random.Generator(np.random.PCG64(n_states))
+    n = 3
+    tr = g.integers(0, n_states, size=(n, n_states, n_actions))
+    rw = g.random((n, n_states, n_actions)) * np.array([1.0, 1e-2, 1e-4])[:, None, None]
+    tm = g.random((n, n_states)) < 0.05
+    model = ctx.load_table_batch(tr, rw, tm)
+    q, sweeps = ctx.vi_solve_batch(model, 0.9, 40)
+    assert_form(ctx, "vi_batch_reg<{},{}>".format(own, block))
+    q_ref, sw_ref = oracle.vi_solve_each(tr, rw, tm, gamma=0.9, iterations=40)
+    np.testing.assert_array_equal(sweeps, sw_ref)
+    assert np.array_equal(q, q_ref)
+    model.close()
+
+
 @pytest.mark.parametrize("knob,variant", [(None, "vi_batch_wg_stream"), ("MP_VI_BATCH_NO_WGR", "vi_batch_wg_lds"),
                                           ("MP_VI_BATCH_NO_VLDS", "vi_batch_wg_global")])
 def test_vi_batch_workgroup_forms(ctx, monkeypatch, knob, variant):

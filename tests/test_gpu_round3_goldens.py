@@ -6,7 +6,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.helpers import assert_keyed_tree_equal, mdp_from_golden
+from tests.helpers import assert_form, assert_keyed_tree_equal, mdp_from_golden, opd_form, saopd_form, uct_stoch_form
 from tests.test_oracle_round3 import names, robust_models
 
 pytestmark = pytest.mark.gpu
@@ -77,6 +77,7 @@ def test_robust_planner_restricted_actions_goldens(ctx, z, variant, monkeypatch)
     monkeypatch.setenv("MP_OPD_MODEL", variant.split("_")[0])      # "global_cls": the wide kernels' residue-class layout
     if variant.endswith("_cls"):
         monkeypatch.setenv("MP_OPD_WIDE", "cls")
+    knobs = dict(model=variant.split("_")[0], wide="cls" if variant.endswith("_cls") else None)
     for name in names(z, "robust_masked"):
         p = "robust_masked/" + name
         t, r, term = robust_models(z, p)
@@ -86,6 +87,9 @@ def test_robust_planner_restricted_actions_goldens(ctx, z, variant, monkeypatch)
         rng = np.array(z[p + "/rng_before"], dtype=np.uint64).reshape(1, 6)
         out = ctx.ropd_plan(model, [int(z[p + "/s0"])], budget, float(z[p + "/gamma"]), float(z[p + "/terminal_reward"]), rng,
                             max_plan_len=budget // a + 1)
+        form = opd_form(ctx, a, budget, 1, models=m, general=not (0 <= float(z[p + "/gamma"]) < 1 and float(z[p + "/terminal_reward"]) >= 0), **knobs)
+        assert_form(ctx, form)
+        assert form.startswith({"lds": "ropd_lds_", "ldsx": "ropd_ldsx_", "global": "ropd_wide_sib", "global_cls": "ropd_wide_cls"}[variant])
         n = int(out["plan_len"][0])
         np.testing.assert_array_equal(out["plans"][0, :n], z[p + "/plan"], err_msg=name)
         assert out["root_lower"][0] == float(z[p + "/root_lower"]) and out["root_upper"][0] == float(z[p + "/root_upper"]), name
@@ -135,6 +139,7 @@ def test_robust_planner_restricted_actions_batch_vs_oracle(ctx, n_models, n_acti
     monkeypatch.setenv("MP_OPD_MODEL", variant.split("_")[0])      # "global_cls": the wide kernels' residue-class layout
     if variant.endswith("_cls"):
         monkeypatch.setenv("MP_OPD_WIDE", "cls")
+    knobs = dict(model=variant.split("_")[0], wide="cls" if variant.endswith("_cls") else None)
     s_ = 200
     cfgs = [generators.random_deterministic(s_, n_actions, seed=60 + i, terminal_rate=0.05) for i in range(n_models)]
     t, r = np.stack([c["transition"] for c in cfgs]), np.stack([c["reward"] for c in cfgs])
@@ -150,6 +155,10 @@ def test_robust_planner_restricted_actions_batch_vs_oracle(ctx, n_models, n_acti
     rng_ref = rng.copy()
     mpl = budget // n_actions + 2
     out = ctx.ropd_plan(model, s0, budget, 0.9, 0.25, rng, max_plan_len=mpl)
+    form = opd_form(ctx, n_actions, budget, n, models=n_models, **knobs)
+    assert_form(ctx, form)
+    assert form.startswith("ropd_any" if n_actions > 64 else {"lds": "ropd_lds_", "ldsx": "ropd_ldsx_", "global": "ropd_wide_sib",
+                                                              "global_cls": "ropd_wide_cls"}[variant])
     ref = oracle.ropd_plan_batch(t, r, term, s0, budget, 0.9, 0.25, rng_ref, max_plan_len=mpl, n_threads=8, available=avail)
     for k in ("status", "plans", "plan_len", "env_steps"):
         np.testing.assert_array_equal(out[k], ref[k], err_msg=k)
@@ -168,6 +177,7 @@ def test_robust_planner_more_than_32_models_tree_export(ctx, n_models, variant, 
     monkeypatch.setenv("MP_OPD_MODEL", variant.split("_")[0])      # "global_cls": the wide kernels' residue-class layout
     if variant.endswith("_cls"):
         monkeypatch.setenv("MP_OPD_WIDE", "cls")
+    knobs = dict(model=variant.split("_")[0], wide="cls" if variant.endswith("_cls") else None)
     s_, a_, budget = 120, 3, 90
     cfgs = [generators.random_deterministic(s_, a_, seed=300 + i, terminal_rate=0.15) for i in range(n_models)]
     t, r = np.stack([c["transition"] for c in cfgs]), np.stack([c["reward"] for c in cfgs])
@@ -178,6 +188,7 @@ def test_robust_planner_more_than_32_models_tree_export(ctx, n_models, variant, 
     s0 = g.integers(0, s_, size=(1, n_models)).astype(np.int32)
     rng = np.array([[5, 7, 0, 9, 0, 0]], dtype=np.uint64)
     out = ctx.ropd_plan(model, s0, budget, 0.85, 0.5, rng.copy(), max_plan_len=budget)
+    assert_form(ctx, {"lds": "ropd_lds_gen", "global": "ropd_wide_sib", "global_cls": "ropd_wide_cls"}[variant])
     ref = oracle.ropd_plan(t, r, term, s0[0], budget, 0.85, 0.5, rng_state=rng[0].copy(), max_plan_len=budget)
     n = int(out["plan_len"][0])
     assert np.array_equal(out["plans"][0, :n], ref["plan"]) and out["root_lower"][0] == ref["root_lower"]
@@ -284,6 +295,10 @@ def test_uct_on_stochastic_models_batch_vs_oracle(ctx, mode, closed, monkeypatch
     from oracle import oracle
     from rl_agents_amd.envs import generators
     few_rewards = "few-rewards" in mode     # at most 256 distinct rewards + two successors: the 16-byte records
+    step_records = {"stochastic": 0, "sparse": 4, "deterministic": 0, "sparse2": 2, "sparse6": 0, "sparse-unfused": 0, "sparse-many-actions": 2,
+               "sparse-generic-a": 2, "dense-few2": 2, "dense-few4": 4, "sparse2-few-rewards": 1, "dense-few2-few-rewards": 1,
+               "sparse2-few-rewards-32": 2}[mode]
+    generic = mode == "sparse-generic-a"
     if mode.endswith("-32"):
         monkeypatch.setenv("MP_UCT_STOCH_FUSED", "2")       # ... kept at 32 bytes
         mode = mode[:-3]
@@ -342,6 +357,7 @@ def test_uct_on_stochastic_models_batch_vs_oracle(ctx, mode, closed, monkeypatch
         model.set_episode_rules(rule, 25)
         out = ctx.uct_plan_stochastic(model, s0, 24, 9, 0.9, 4.5, prior, roll, rng, env_rng_state=erng, closed_loop=closed,
                                       root_steps=steps0, max_plan_len=18)
+        assert_form(ctx, uct_stoch_form(step_records, 16, a, generic=generic))
         ref = oracle.uct_plan_stoch_batch(mode, cfg["transition"], cfg["reward"], cfg["terminal"], s0, 24, 9, 0.9, 4.5, prior,
                                           roll, rng_ref, erng, next_states=cfg.get("next"), closed_loop=closed, steps0=steps0,
                                           max_steps=25, done_rule=rule, max_plan_len=18, n_threads=8)
@@ -355,8 +371,9 @@ def test_uct_on_stochastic_models_batch_vs_oracle(ctx, mode, closed, monkeypatch
 
 @pytest.mark.parametrize("closed", [False, True])
 def test_uct_on_stochastic_models_long_plans(ctx, closed):
-    """2 300 episodes: more nodes than a 16-bit path entry can name (the int32 path stack) and visit counts beyond the
-    quotient tables (the kernel's own IEEE divisions) -- against the oracle."""
+    """2 300 episodes: visit counts beyond the quotient tables (the kernel's own IEEE divisions) -- against the oracle.
+    (The trees hold at most 1 + 2 300 x 5 = 11 501 nodes, which 16-bit path entries still name: the int32 path stack starts
+    beyond 65 535 node slots -- tests/test_gpu_forms_reached.py, the node-count edges.)"""
     from oracle import oracle
     from rl_agents_amd.envs import generators
     cfg = generators.random_sparse(120, 4, 2, seed=5, terminal_rate=0.03)
@@ -375,6 +392,7 @@ def test_uct_on_stochastic_models_long_plans(ctx, closed):
     model = ctx.load_sparse(cfg["transition"], cfg["next"], cfg["reward"], cfg["terminal"])
     out = ctx.uct_plan_stochastic(model, s0, episodes, horizon, 0.9, 3.0, p, p, rng, env_rng_state=erng, closed_loop=closed,
                                   max_plan_len=2 * horizon)
+    assert_form(ctx, "uct_stoch_r2_p16_a4")
     ref = oracle.uct_plan_stoch_batch("sparse", cfg["transition"], cfg["reward"], cfg["terminal"], s0, episodes, horizon, 0.9, 3.0,
                                       p, p, rng_ref, erng, next_states=cfg["next"], closed_loop=closed, max_plan_len=2 * horizon,
                                       n_threads=8)
@@ -417,14 +435,17 @@ SAOPD = "<class 'rl_agents_amd.agents.tree_search.state_aware.StateAwarePlannerA
 def test_state_aware_restricted_actions_goldens_c_abi(ctx, z, mapping, monkeypatch):
     """mp_saopd_plan on models carrying an availability table: the reference's StateAwarePlannerAgent episodes on
     MaskedFiniteMDPEnv (ascending listing) and on the highway-like env (IDLE first: planned in the permuted action space)
-    -- plans, keyed trees, leaves, state values, env steps, generator -- in every kernel mapping."""
+    -- plans, keyed trees, leaves, state values, env steps, generator -- in every kernel mapping.  At these budgets (at most
+    four plans of 500) the arena of the "lds" mapping stays in LDS to the last plan, but for the fresh plan of grid_walls_b500:
+    its backups fill the 4 096 entries of the LDS queue, and the plan runs again with the dictionaries alone in LDS.  The
+    "wave" mapping keeps the dictionaries there, but the arena on the two highway tables, whose 120 states leave them no room."""
     from rl_agents_amd import native
     from tests.helpers import replay_state_aware_masked_episode
     if mapping == "lane":
         monkeypatch.setenv("MP_SAOPD_MODEL", "lane")
     if mapping == "lds":
         monkeypatch.setenv("MP_SAOPD_LDS", "1")
-    held = {}
+    held, episode, step = {}, [None], [0]
 
     def plan_fn(cfg, available, order, s0, params, rng, planner):
         t, r, av = cfg["transition"], cfg["reward"], np.asarray(available)
@@ -436,10 +457,18 @@ def test_state_aware_restricted_actions_goldens_c_abi(ctx, z, mapping, monkeypat
                 x.close()
             held["model"] = ctx.load_table(t, r, cfg["terminal"], available=av)
             held["planners"] = native.StateAwarePlanners(ctx, held["model"], 1)
+            step[0] = 0
         rs = np.array(rng, dtype=np.uint64).reshape(1, 6)
+        before = held["planners"].info()["n_nodes"]
         out = held["planners"].plan([s0], params["budget"], params["gamma"], params["terminal_reward"], rs,
                                     accuracy=params["accuracy"], backup_aggregated_nodes=params["backup_aggregated_nodes"],
                                     prune_suboptimal_leaves=params["prune_suboptimal_leaves"])
+        form = saopd_form(ctx, r.shape[0], r.shape[1], params["budget"], 1, nodes_before=before,
+                          model="lane" if mapping == "lane" else None, lds="1" if mapping == "lds" else None)
+        assert_form(ctx, "saopd_wave_dict_retry" if mapping == "lds" and (episode[0], step[0]) == ("grid_walls_b500", 0) else form)
+        assert form == {"lane": "saopd_lane", "lds": "saopd_wave_lds",
+                        "wave": "saopd_wave_lds" if r.shape[0] == 120 else "saopd_wave_dict"}[mapping]
+        step[0] += 1
         if out["status"][0] == native.MP_ERR_ARG:
             raise ValueError("max() arg is an empty sequence")
         assert out["status"][0] == 0
@@ -450,6 +479,7 @@ def test_state_aware_restricted_actions_goldens_c_abi(ctx, z, mapping, monkeypat
             tree["action"] = np.where(tree["action"] >= 0, o[np.maximum(tree["action"], 0)], -1)
         return dict(plan=plan, env_steps=int(out["env_steps"][0]), rng_after=rs[0], tree=tree, state_values=sv, planner=True)
     for name in names(z, "sa_masked"):
+        episode[0] = name
         replay_state_aware_masked_episode(z, name, plan_fn)
     for x in held.values():
         x.close()
@@ -527,6 +557,10 @@ def test_state_aware_restricted_actions_batch_vs_oracle(ctx, shape, mapping, mon
     for step in range(3):
         rng_ref = rng.copy()
         out = planners.plan(states, budget, gamma, 0.25, rng, max_plan_len=budget // a_ + 1)
+        # (200 planners are fewer than the compute units: on the highway's 120 states, no room for the dictionaries, the arena is in LDS)
+        assert_form(ctx, saopd_form(ctx, s_, a_, budget, n, nodes_before=step * (1 + budget // a_ * a_),
+                                    model="lane" if mapping == "lane" else None))
+        assert ctx.last_kernel_variant() == ("saopd_lane" if mapping == "lane" else "saopd_wave_lds" if shape == "highway" else "saopd_wave_dict")
         for i in range(n):
             if out["status"][i] != 0:
                 with pytest.raises(ValueError):

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.helpers import (assert_keyed_tree_equal, mdp_from_golden, reference_policy_lists,
+from tests.helpers import (assert_form, assert_keyed_tree_equal, opd_form, mdp_from_golden, reference_policy_lists,
                            restricted_agent_policy_lists)
 
 pytestmark = pytest.mark.gpu
@@ -288,6 +288,7 @@ def test_opd_restricted_actions_batch_vs_oracle(ctx, n_actions, budget, variant,
     monkeypatch.setenv("MP_OPD_MODEL", variant.split("_")[0])      # "global_cls": the wide kernels' residue-class layout
     if variant.endswith("_cls"):
         monkeypatch.setenv("MP_OPD_WIDE", "cls")
+    knobs = dict(model=variant.split("_")[0], wide="cls" if variant.endswith("_cls") else None)
     cfg = generators.random_deterministic(300, n_actions, seed=90 + n_actions, terminal_rate=0.05)
     t, r, term = cfg["transition"], cfg["reward"], cfg["terminal"]
     avail = generators.random_available(300, n_actions, seed=n_actions, rate=0.45)
@@ -301,6 +302,9 @@ def test_opd_restricted_actions_batch_vs_oracle(ctx, n_actions, budget, variant,
     rng_ref = rng.copy()
     mpl = budget // n_actions + 2
     out = ctx.opd_plan(model, s0, budget, 0.9, 0.25, rng, max_plan_len=mpl)
+    assert_form(ctx, opd_form(ctx, n_actions, budget, n, **knobs))
+    assert ctx.last_kernel_variant() == {"lds": "opd_lds", "ldsx": "opd_ldsx", "global": "opd_wide_sib_small",
+                                         "global_cls": "opd_wide_cls_small"}[variant]
     ref = oracle.opd_plan_batch(t, r, term, s0, budget, 0.9, 0.25, rng_ref, max_plan_len=mpl, n_threads=8, available=avail)
     for k in ("status", "plans", "plan_len", "env_steps"):
         np.testing.assert_array_equal(out[k], ref[k], err_msg=k)
@@ -328,6 +332,7 @@ def test_discrete_robust_planner_goldens(ctx, z, variant, monkeypatch):
     monkeypatch.setenv("MP_OPD_MODEL", variant.split("_")[0])      # "global_cls": the wide kernels' residue-class layout
     if variant.endswith("_cls"):
         monkeypatch.setenv("MP_OPD_WIDE", "cls")
+    knobs = dict(model=variant.split("_")[0], wide="cls" if variant.endswith("_cls") else None)
     for name in names(z, "robust"):
         p = "robust/" + name
         cfgs, (t, r, term) = _robust_models(z, p)
@@ -337,6 +342,9 @@ def test_discrete_robust_planner_goldens(ctx, z, variant, monkeypatch):
         rng = np.array(z[p + "/rng_before"], dtype=np.uint64).reshape(1, 6)
         out = ctx.ropd_plan(model, [int(z[p + "/s0"])], budget, float(z[p + "/gamma"]), float(z[p + "/terminal_reward"]), rng,
                             max_plan_len=budget // a_ + 1)
+        form = opd_form(ctx, a_, budget, 1, models=m, general=not (0 <= float(z[p + "/gamma"]) < 1 and float(z[p + "/terminal_reward"]) >= 0), **knobs)
+        assert_form(ctx, form)
+        assert form.startswith({"lds": "ropd_lds_", "ldsx": "ropd_ldsx_", "global": "ropd_wide_sib", "global_cls": "ropd_wide_cls"}[variant])
         n = int(out["plan_len"][0])
         np.testing.assert_array_equal(out["plans"][0, :n], z[p + "/plan"], err_msg=name)
         assert out["root_lower"][0] == float(z[p + "/root_lower"]) and out["root_upper"][0] == float(z[p + "/root_upper"])
@@ -392,6 +400,7 @@ def test_discrete_robust_planner_batch_vs_oracle(ctx, n_models, n_actions, budge
     monkeypatch.setenv("MP_OPD_MODEL", variant.split("_")[0])      # "global_cls": the wide kernels' residue-class layout
     if variant.endswith("_cls"):
         monkeypatch.setenv("MP_OPD_WIDE", "cls")
+    knobs = dict(model=variant.split("_")[0], wide="cls" if variant.endswith("_cls") else None)
     cfgs = [generators.random_deterministic(300, n_actions, seed=100 * n_models + i, terminal_rate=0.05) for i in range(n_models)]
     t = np.stack([c["transition"] for c in cfgs])
     r = np.stack([c["reward"] for c in cfgs])
@@ -406,6 +415,10 @@ def test_discrete_robust_planner_batch_vs_oracle(ctx, n_models, n_actions, budge
     rng_ref = rng.copy()
     mpl = budget // n_actions + 2
     out = ctx.ropd_plan(model, s0, budget, 0.9, 0.25, rng, max_plan_len=mpl)
+    # (one or two models: the main loop with batched loads for two; three: for four; five and sixteen: the generic one)
+    loop = {1: "_m2", 2: "_m2", 3: "_m4", 5: "_gen", 16: "_gen"}[n_models]
+    assert_form(ctx, {"lds": "ropd_lds" + loop, "ldsx": "ropd_ldsx" + loop, "global": "ropd_wide_sib", "global_cls": "ropd_wide_cls"}[variant])
+    assert ctx.last_kernel_variant() == opd_form(ctx, n_actions, budget, n, models=n_models, **knobs)
     ref = oracle.ropd_plan_batch(t, r, term, s0, budget, 0.9, 0.25, rng_ref, max_plan_len=mpl, n_threads=8)
     for k in ("status", "plans", "plan_len", "env_steps"):
         np.testing.assert_array_equal(out[k], ref[k], err_msg=k)
