@@ -183,7 +183,8 @@ int mp_model_update_rows(mp_model *model, int32_t n_rows, const int32_t *rows, c
  *   available uint8 [S,A], non-zero = action a is listed in state s; every state needs at least one (else MP_ERR_ARG).
  * Host pointer.  Applies to the deterministic table model it is called on; mp_opd_plan then expands the available
  * actions only.  Policies loaded earlier for the model become invalid.  (MCTS reads availability through its POLICIES,
- * mcts.py:59-97: see mp_policy_load_listed.)
+ * mcts.py:59-97: see mp_policy_load_listed.)  A whole dense or sparse model takes the table too and only keeps it: Sparse
+ * Sampling reads it (sparse_sampling.py:40-43); the stochastic UCT entry points go on refusing a restricted model without a policy.
  */
 int mp_model_set_available(mp_model *model, const uint8_t *available);
 /*
@@ -530,6 +531,7 @@ int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
  *   rng_state [n_roots][6], advanced; plans int32 [n_roots] the ONE planned action (-1: no rollout was made, budget <= 0 --
  *   the reference raises ValueError from np.amax([])); root_value = the value of the chosen chance child; env_steps = model
  *   steps taken (the last rollout may overshoot the budget); status MP_OK.
+ * An availability table on the model (mp_model_set_available) is not read: BRUE draws among all actions (:27).
  */
 int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t budget, int32_t horizon,
                  double gamma, const double *gpow, uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *env_steps,
@@ -540,6 +542,43 @@ int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
  * nodes).  When a batch's trees do not all fit the workspace only root 0's is kept (MP_ERR_ARG for the others). */
 int mp_brue_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *key,
                         uint8_t *is_chance, int32_t *depth, int64_t *count, double *stat);
+
+/* ---------------------------------------------------------------- Sparse Sampling ----------- */
+/*
+ * SparseSampling.plan (tree_search/sparse_sampling.py:21-24) for n_roots independent roots of a deterministic table, dense or
+ * sparse model: DecisionNode.estimateV (:38-51) visits the actions the env lists (the model's availability table, in column
+ * order; every action without one), ChanceNode.estimateQ (:71-88) takes C samples -- each one generator draw
+ * np_random.randint(2**30) (:79, made for every model kind), a clone seeded with it, Generator(PCG64(SeedSequence(x))), and one
+ * step, which draws one double on a dense / sparse model and nothing on a table -- lists the outcomes in first-occurrence
+ * order with their counts (:83, :93-96), recurses into them in that order down to depth `horizon` and backs up
+ * reward + gamma * sum(value * count) / C (:87-88) with the LAST sample's reward; `done` is never read (:81).  Then get_plan
+ * (:26-28): DecisionNode.selection_rule (:53-56), Node.random_argmax (abstract.py:296-311) over the root's chance children.
+ * Replaces the reference's per-sample safe_deepcopy_env.  Bit-exact with the reference (+ * / on f64, integer counts).
+ *   1 <= horizon <= 16, 1 <= C <= 1024 (else MP_ERR_ARG; the reference raises ValueError at horizon 0 and UnboundLocalError
+ *   at C 0); MP_ERR_ARG too for a tree whose node bound -- D_0 = 1 decision node, |A| D_d chance nodes at depth d,
+ *   D_(d+1) <= |A| D_d min(C, W), W the most outcomes one (state, action) can give -- exceeds int32 indices or the workspace.
+ *   MP_ERR_MODE for joint, batch and row-block models.
+ *   rng_state [n_roots][6], advanced; plans int32 [n_roots] the ONE planned action (a column of the model); root_value = the
+ *   value of the chosen chance child; samples = model steps taken (the reference's own step count, len(planner.observations),
+ *   stays 0: the samples step the clone directly); status MP_OK.
+ * The frames of the recursion sit in LDS ("ss_wave_lds") or, when horizon * min(C, W) list entries exceed 16 KiB, in a global
+ * workspace ("ss_wave_global"); MP_SS_FRAMES=lds|global in the environment forces either where it is legal.
+ */
+int mp_ss_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t horizon, int32_t C, double gamma,
+               uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *samples, int32_t *status, int32_t mem);
+/* Tree of root `root` after the last call of the plan above, in the reference's creation order: per node parent (-1 at the
+ * root), key (the action of a chance node, the observed state of a decision node, -1 at the root), is_chance, depth
+ * (sparse_sampling.py:34,68), count (:83; 0 for chance nodes), value (:51, :87; the int 0 of a node at depth `horizon` is 0.0);
+ * host arrays of capacity `cap` (*n_nodes is set even when `cap` is too small).  Trees are kept for every root while the
+ * batch's node bounds fit the workspace (1 GiB, or MP_SS_KEEP_BYTES if smaller), else only root 0's (MP_ERR_ARG for the others). */
+int mp_ss_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *key, uint8_t *is_chance,
+                      int32_t *depth, int64_t *count, double *value);
+/* Host arithmetic of the plan above (no device): out[5] = { L = min(C, W) entries of an outcome list, bytes of a wave's frames,
+ * the node bound of a tree (-1: beyond int32), the most frame bytes kept in LDS by default, 1 if this call's frames go to LDS
+ * (MP_SS_FRAMES is read) else 0 }. */
+int mp_ss_geometry(int32_t n_actions, int32_t horizon, int32_t C, int32_t W, int64_t *out);
+/* The two names the plan above records for mp_last_kernel_variant, one per line (they are not part of mp_kernel_form_names). */
+const char *mp_ss_form_names(void);
 
 /* ---------------------------------------------------------------- discrete robust OPD ------- */
 /*
@@ -762,6 +801,8 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
  *   batched VI    "vi_batch_reg<own,block>", "vi_batch_cluster2|4|8" (K workgroups per MDP), "vi_batch_wg_stream|lds|global"
  *   OLOP, BRUE    "olop_global", "brue_global" (a tree per root, kept for the export), "..._slots" (slots shared by the waves)
  *   GBOP-D        "gbopd_wave_lds", "gbopd_wave_global"
+ *   Sparse        "ss_wave_lds", "ss_wave_global" (the frames of the recursion in LDS / in a global workspace)
+ *   Sampling
  *   OPD           "opd_any" (more than 64 actions); "opd_lds" / "opd_ldsx" (bounds in LDS / the parent map in HBM), then "_gen"
  *                 (the main loop for arbitrary bounds), then "_chain" (the closing pass on the node array);
  *                 "opd_wide_sib" / "opd_wide_cls" (bounds in HBM, sibling / residue-class layout), then "_small" (at most two
@@ -776,7 +817,8 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
  * The host picks by model, batch size and the MP_* test hooks; reports and tests name what ran.  Results do not depend on the form. */
 const char *mp_last_kernel_variant(mp_ctx *ctx);
 /* Every name mp_last_kernel_variant can return, one per line, built by the functions that name the launches (host only, no
- * device): a test table that is to cover every form is compared with this list. */
+ * device): a test table that is to cover every form is compared with this list.  (Sparse Sampling's two names are listed by
+ * its own mp_ss_form_names.) */
 const char *mp_kernel_form_names(void);
 /* Hardware self-test (no reference counterpart): LDS atomics of ONE wavefront instruction that hit the same address apply
  * in LANE ORDER on this device -- the state-aware OPD kernel's grouped backup relies on it (one ds_min_rtn_f64 of the group

@@ -1174,7 +1174,11 @@ int mp_model_load_joint(mp_ctx *ctx, int32_t M, int32_t S, int32_t A, const int6
 int mp_model_set_available(mp_model *m, const uint8_t *available)
 {
     if (!m || !available) return fail(MP_ERR_ARG, "mp_model_set_available: NULL argument");
-    if (m->mode != MP_MODE_DETERMINISTIC || !m->rec) return fail(MP_ERR_MODE, "mp_model_set_available: deterministic table models only");
+    // a whole dense / sparse model keeps the flags only (the planner that asks the env which actions it lists reads them)
+    const bool table = m->mode == MP_MODE_DETERMINISTIC && m->rec;
+    const bool finite = (m->mode == MP_MODE_STOCHASTIC && m->Sc == m->S) || m->mode == MP_MODE_SPARSE;
+    if (!table && !(finite && m->M == 1 && m->NB == 1))
+        return fail(MP_ERR_MODE, "mp_model_set_available: deterministic tables and whole dense / sparse models only");
     mp_ctx *ctx = m->ctx;
     const int S = m->S, A = m->A;
     for (int s = 0; s < S; ++s) {
@@ -1186,10 +1190,12 @@ int mp_model_set_available(mp_model *m, const uint8_t *available)
     MP_HIP(hipStreamSynchronize(ctx->stream));
     if (!m->avail && hipMalloc(&m->avail, (size_t)S * A) != hipSuccess) return fail(MP_ERR_ALLOC, "mp_model_set_available: hipMalloc failed");
     MP_HIP(hipMemcpy(m->avail, available, (size_t)S * A, hipMemcpyHostToDevice));
-    const long sa = (long)S * A;
-    hipLaunchKernelGGL(pack_records, dim3((unsigned)((sa + 255) / 256)), dim3(256), 0, ctx->stream, S, A, m->T, m->R, m->term,
-                       (const uint8_t *)m->avail, m->rec);
-    MP_HIP(hipStreamSynchronize(ctx->stream));
+    if (table) {
+        const long sa = (long)S * A;
+        hipLaunchKernelGGL(pack_records, dim3((unsigned)((sa + 255) / 256)), dim3(256), 0, ctx->stream, S, A, m->T, m->R, m->term,
+                           (const uint8_t *)m->avail, m->rec);
+        MP_HIP(hipStreamSynchronize(ctx->stream));
+    }
     m->masked = true;
     m->serial = mp::next_model_serial(); // policies fused from the old records no longer belong to this model
     return MP_OK;

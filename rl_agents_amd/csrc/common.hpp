@@ -51,7 +51,7 @@ struct DevBuf {
 
 // what the last tree-search call left on the device (for the *_tree_export entry points)
 struct TreeMeta {
-    int kind = 0; // 0 none, 1 uct, 2 opd, 3 robust opd, 4 stochastic uct (mp_uct_plan_stochastic), 5 olop, 6 brue
+    int kind = 0; // 0 none, 1 uct, 2 opd, 3 robust opd, 4 stochastic uct (mp_uct_plan_stochastic), 5 olop, 6 brue, 7 sparse sampling
     int n_roots = 0, A = 0, cap = 0, K = 0, M = 1;
     double gamma = 0.0; // robust opd: the export recomputes leaf upper-bound vectors
     int buf = 0;        // UCT: which of the two tree workspaces (WS_TREE0 / WS_TREE2) holds the current trees
@@ -242,6 +242,8 @@ struct mp_model {
     double *srec_rtab = nullptr; // srec_wb == 1: the distinct reward values [256] a record's 8-bit index points into
     mp_cartpole_params cp;
     int cp_sincos = 0;       // CartPole: which restated form of the host libm's sin / cos the kernel evaluates (libm_sincos.hpp)
+    int ss_w = 0;            // dense models: the most outcomes one row can give (sparse_sampling.hip counts them once), 0 = not yet
+    uint64_t ss_w_serial = 0; // ... and the serial it was counted under
 };
 
 // per-state prior / rollout policies of one model (mcts_with_prior.py:47-62), device

@@ -76,6 +76,16 @@ inline FormName gbopd_form_name(bool use_lds)
     return n;
 }
 
+// Sparse Sampling (sparse_sampling.hip): the frames in LDS or in a global workspace.  Reported by mp_last_kernel_variant after a
+// call and listed by the planner's own mp_ss_form_names -- NOT by all_form_names below, whose list is pinned name for name
+// by a table of the planners it covers.
+inline FormName ss_form_name(bool use_lds)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "ss_wave_%s", use_lds ? "lds" : "global");
+    return n;
+}
+
 // ---- OPD (opd.hip) and robust OPD (ropd.hip).  any_a: |A| > 64, the plain kernel.  Else glb: the wide kernel in its sibling
 // (sib) or residue-class layout; !glb: the LDS-resident kernel, the parent map in HBM with expg, the closing pass on the node
 // array with chain.  nonneg picks the cheaper main loops everywhere.
@@ -138,7 +148,7 @@ inline FormName uct_stoch_form_name(int wbk, bool p16, int at, bool pol)
     return n;
 }
 
-// every name an entry point can record, one per line
+// every name an entry point can record, one per line (Sparse Sampling's two are listed by mp_ss_form_names)
 inline std::string all_form_names()
 {
     std::string out;

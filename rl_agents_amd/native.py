@@ -114,6 +114,10 @@ SIGNATURES = {
     "mp_olop_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_brue_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_brue_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_ss_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_ss_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_ss_geometry": (C.c_int, [c_i32, c_i32, c_i32, c_i32, _vp]),
+    "mp_ss_form_names": (C.c_char_p, []),
     "mp_uct_choose_form": (C.c_int, [_vp, _vp, P(C.c_char_p)]),
     "mp_last_kernel_ms": (C.c_int, [_vp, P(c_f64), P(c_i32)]),
     "mp_last_kernel_variant": (C.c_char_p, [_vp]),
@@ -293,6 +297,23 @@ def kernel_form_names():
     return load().mp_kernel_form_names().decode().split()
 
 
+def ss_form_names():
+    """The names a Sparse Sampling plan records for Context.last_kernel_variant() (mp_ss_form_names; host only).  They are
+    not part of kernel_form_names()."""
+    return load().mp_ss_form_names().decode().split()
+
+
+def ss_geometry(n_actions, horizon, C, W):
+    """Host arithmetic of a Sparse Sampling plan (mp_ss_geometry; no device): ``W`` = the most outcomes one (state, action) can
+    give -- 1 for deterministic tables, B for sparse models, the fullest row's non-zeros for dense ones.  -> dict with the
+    entries of an outcome list, the bytes of a wave's frames, the node bound of a tree (-1: beyond int32 indices), the LDS
+    share the frames may take by default and whether this call's frames go to LDS (MP_SS_FRAMES is read)."""
+    out = np.zeros(5, np.int64)
+    _check(load().mp_ss_geometry(int(n_actions), int(horizon), int(C), int(W), _ptr(out)))
+    return dict(list_entries=int(out[0]), frame_bytes=int(out[1]), node_bound=int(out[2]), lds_limit=int(out[3]),
+                lds=bool(out[4]))
+
+
 def vi_exact_plan(n):
     """The tables the bit-exact dense backup sums a row of ``n`` elements by (numpy's pairwise recursion; host only):
     -> (leaves int32 [L,2] {offset, length}, nodes int32 [K,2] {left slot, right slot} by height, hoff int32 [H+1],
@@ -377,7 +398,7 @@ class Context(object):
 
     def last_kernel_variant(self):
         """Which kernel form the last plan / batched VI call launched ("uct_ldsr", "opd_wide_sib_small", "saopd_wave_dict", ...:
-        every name in kernel_form_names())."""
+        every name in kernel_form_names(); after a Sparse Sampling plan one of ss_form_names(), which that list does not hold)."""
         return self._lib.mp_last_kernel_variant(self._h).decode()
 
     # ---- the collective of the C ABI (RCCL resolved at run time): what a consumer without torch.distributed calls ------------
@@ -1111,6 +1132,36 @@ class Context(object):
         n = c_i32()
         _check(self._lib.mp_brue_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]), _ptr(t["key"]),
                                              _ptr(t["is_chance"]), _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["stat"])))
+        return {k: v[:n.value].copy() for k, v in t.items()}
+
+    def ss_plan(self, model, root_state, horizon, C, gamma, rng_state):
+        """SparseSampling.plan for a batch of roots (host arrays): mp_ss_plan.  ``plans`` [n]: the one planned action per
+        root (a column of the model); ``samples`` [n]: model steps taken."""
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        n = rs.shape[0]
+        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
+                and rng_state.size == n * 6):
+            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
+        out = dict(plans=np.full(n, -1, np.int32), root_value=np.zeros(n, np.float64), samples=np.zeros(n, np.int64),
+                   status=np.zeros(n, np.int32))
+        _check(self._lib.mp_ss_plan(self._h, model._h, n, _ptr(rs), int(horizon), int(C), float(gamma), _ptr(rng_state),
+                                    _ptr(out["plans"]), _ptr(out["root_value"]), _ptr(out["samples"]), _ptr(out["status"]),
+                                    MP_MEM_HOST))
+        return out
+
+    def ss_tree(self, root, cap=None):
+        """Creation-order arrays of root ``root``'s tree after the last ss_plan (mp_ss_tree_export).  ``cap`` None: the
+        tree's own node count is asked first."""
+        n = c_i32()
+        if cap is None:
+            rc = self._lib.mp_ss_tree_export(self._h, int(root), 0, C.byref(n), None, None, None, None, None, None)
+            if n.value < 1:                                     # (no tree to size: the refusal itself)
+                _check(rc)
+            cap = n.value
+        t = dict(parent=np.zeros(cap, np.int32), key=np.zeros(cap, np.int32), is_chance=np.zeros(cap, np.uint8),
+                 depth=np.zeros(cap, np.int32), count=np.zeros(cap, np.int64), value=np.zeros(cap, np.float64))
+        _check(self._lib.mp_ss_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]), _ptr(t["key"]),
+                                           _ptr(t["is_chance"]), _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["value"])))
         return {k: v[:n.value].copy() for k, v in t.items()}
 
     def opd_tree(self, root, cap):

@@ -72,6 +72,9 @@ class PerEpisodeEvaluation(object):
         if not getattr(planner, "supports_per_episode_tables", True):
             raise NotImplementedError("per-episode tables: {} keeps its planner state (graph, bounds, state values) from plan to "
                                       "plan, and a kept state was built on the previous step's table".format(type(planner).__name__))
+        if getattr(planner, "per_episode_entry_point", True) is None:
+            raise NotImplementedError("per-episode tables: {} has no entry point that plans a batch on one model per episode, "
+                                      "and this loop would run the optimistic planner in its place".format(type(planner).__name__))
         self.kind = "vi" if self.vi else ("uct" if hasattr(planner, "prior_policy") else "opd")
         if not self.vi:
             cfg = planner.config
