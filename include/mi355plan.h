@@ -306,6 +306,35 @@ int mp_vi_exact_plan(int32_t n, int32_t cap_leaves, int32_t *leaves, int32_t cap
                      int32_t *hoff, int32_t *counts);
 /* Timing hook: run exactly `sweeps` Bellman sweeps (no early exit), Q left on the device. */
 int mp_vi_sweeps(mp_ctx *ctx, mp_model *model, double gamma, int32_t sweeps, int32_t robust);
+/* The names the single-model entry points above (solve, solve_v, solve_v_robust, sweeps, backup) record for
+ * mp_last_kernel_variant, one per line (host only; they are not part of mp_kernel_form_names): the form of the launch that
+ * produced the returned values -- after the persistent kernel's host-mode fallback the chained one.
+ *   vi_det_small_a{2,3,4,5,6,8,any}             deterministic tables, one workgroup, everything in LDS
+ *   vi_det_persist_a{A}_m{M}                    ... one persistent grid (19 pairs of |A| and models)
+ *   vi_det_chain_a{2,3,4,5,6,8,any}[_graph]     ... a launch per sweep; _graph: replayed from the captured graph
+ *   vi_sparse, vi_sparse_big                    sparse models with up to / more than 128 next states
+ *   vi_dense_exact_n{8,10,12,14,16}_{lds,pieces,global}   dense rows in numpy's order: unrolled steps of a leaf, where V is read from
+ *   vi_dense_mfma, vi_dense_mfma_split          dense rows on the matrix cores, the columns in one / several segments
+ * A solve of 0 iterations on the chained, dense or sparse path launches no sweep and records the empty name. */
+const char *mp_vi_form_names(void);
+/* How many times this context has captured a chain of deterministic sweeps into a graph (vi_det_chain_*_graph).  The context
+ * keeps the executable graph of its last chain, keyed by everything baked into the kernel arguments (model, table and
+ * workspace pointers, sizes, iterations, gamma, tolerances, Q or V form): a call with that key replays it and leaves the
+ * count alone, any other captures anew.  The tables are read through their pointers, so a replay after an in-place
+ * mp_model_update_tables solves the new tables.  Host only; 0 for a NULL context. */
+int64_t mp_vi_graph_captures(mp_ctx *ctx);
+/* Host arithmetic of those launches (no device; the launch code calls the same functions), on a device of `cus` compute units.
+ * The MP_VI_* and MP_DENSE_NO_SPLIT knobs are read from the environment.  out int64 [14]:
+ *   mode = MP_MODE_DETERMINISTIC, M models of S states and A actions (Sc ignored):
+ *     [0] LDS bytes of the single-workgroup kernel's tables, [1] 1 if they fit, [2] 1 if that kernel is taken (MP_VI_NO_SMALL),
+ *     [3] threads per workgroup and [4] workgroups of the persistent grid, [5] 1 if the persistent kernel is admitted
+ *     (it is taken when [2] is 0);
+ *   mode = MP_MODE_STOCHASTIC, rows of Sc columns (S, A, M ignored):
+ *     [6] most 8-element steps in a leaf (nb) and [7] the unrolled form NBT it selects, [8] waves per workgroup, [9] LDS bytes
+ *     of the summation tables, [10] where V goes by default and [11] with the knobs: 0 read through L2, 1 all of it in LDS,
+ *     2 in pieces of 8192; [12] column segments of the matrix-core form, [13] columns per segment.
+ * The other half of `out` is zero. */
+int mp_vi_geometry(int32_t mode, int32_t S, int32_t A, int32_t M, int32_t Sc, int32_t cus, int64_t *out);
 
 /* ---------------------------------------------------------------- UCT ----------------------- */
 /*
@@ -818,7 +847,7 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
 const char *mp_last_kernel_variant(mp_ctx *ctx);
 /* Every name mp_last_kernel_variant can return, one per line, built by the functions that name the launches (host only, no
  * device): a test table that is to cover every form is compared with this list.  (Sparse Sampling's two names are listed by
- * its own mp_ss_form_names.) */
+ * its own mp_ss_form_names, single-model value iteration's by mp_vi_form_names.) */
 const char *mp_kernel_form_names(void);
 /* Hardware self-test (no reference counterpart): LDS atomics of ONE wavefront instruction that hit the same address apply
  * in LANE ORDER on this device -- the state-aware OPD kernel's grouped backup relies on it (one ds_min_rtn_f64 of the group

@@ -92,6 +92,7 @@ struct mp_ctx {
     // cached hipGraphExec of the last deterministic VI sweep chain
     void *vi_graph_exec = nullptr;
     mp::ViGraphKey vi_graph_key;
+    long vi_graph_captures = 0; // times a chain was captured (a call that finds its key cached replays and leaves it alone)
     // dense value iteration: 1 = contract in numpy's summation order (vi_dense_exact_q, bit-exact with the reference),
     // 0 = on the f64 matrix cores (vi_dense_q); -1 = not set yet (MP_VI_DENSE in the environment, else the default)
     int vi_dense_exact = -1;

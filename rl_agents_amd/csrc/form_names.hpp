@@ -86,6 +86,91 @@ inline FormName ss_form_name(bool use_lds)
     return n;
 }
 
+// ---- single-model value iteration (vi.hip: mp_vi_solve, mp_vi_solve_v, mp_vi_solve_v_robust, mp_vi_sweeps, mp_vi_backup):
+// the form of the launch that produced the returned values.  Reported by mp_last_kernel_variant after a call and listed by
+// mp_vi_form_names -- NOT by all_form_names below, as for Sparse Sampling.
+// Deterministic tables: one workgroup with everything in LDS (VD_SMALL), one persistent grid (VD_PERSIST: `at` x `models` is
+// one of kViPersistForms) or a launch per sweep (VD_CHAIN; graph: replayed from the captured graph).  at: the unrolled |A|,
+// 0 = the loop form.
+enum ViDetKind { VD_SMALL, VD_PERSIST, VD_CHAIN };
+struct ViDetForm {
+    int kind, at, models;
+    bool graph;
+};
+constexpr int kViDetUnrolled[6] = {2, 3, 4, 5, 6, 8};
+inline int vi_det_unrolled(int A)
+{
+    for (int a : kViDetUnrolled)
+        if (a == A) return A;
+    return 0;
+}
+constexpr int kViPersistForms = 19;
+constexpr int kViPersist[kViPersistForms][2] = {{2, 1}, {3, 1}, {4, 1}, {5, 1}, {6, 1}, {8, 1}, {2, 2}, {3, 2}, {4, 2}, {5, 2},
+                                                {6, 2}, {8, 2}, {2, 3}, {3, 3}, {4, 3}, {5, 3}, {2, 4}, {3, 4}, {4, 4}};
+inline bool vi_persist_form_exists(int A, int M)
+{
+    for (const auto &f : kViPersist)
+        if (f[0] == A && f[1] == M) return true;
+    return false;
+}
+inline FormName vi_det_form_name(const ViDetForm &f)
+{
+    FormName n;
+    char a[8];
+    if (f.at) snprintf(a, sizeof(a), "%d", f.at);
+    else snprintf(a, sizeof(a), "any");
+    if (f.kind == VD_SMALL) snprintf(n.s, sizeof(n.s), "vi_det_small_a%s", a);
+    else if (f.kind == VD_PERSIST) snprintf(n.s, sizeof(n.s), "vi_det_persist_a%s_m%d", a, f.models);
+    else snprintf(n.s, sizeof(n.s), "vi_det_chain_a%s%s", a, f.graph ? "_graph" : "");
+    return n;
+}
+inline FormName vi_sparse_form_name(bool big) // more than 128 next states per (s, a): the pairwise recursion
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "vi_sparse%s", big ? "_big" : "");
+    return n;
+}
+// Dense rows: numpy's order (exact: nbt = the unrolled 8-element steps of a leaf, place = where the lanes read V from, in the
+// order of vi.hip's VI_V_* values) or the matrix cores (split: the columns cut into segments).
+constexpr int kViExactNbt[5] = {8, 10, 12, 14, 16};
+inline int vi_exact_nbt(int nb)
+{
+    for (int t : kViExactNbt)
+        if (nb <= t) return t;
+    return kViExactNbt[4];
+}
+struct ViDenseForm {
+    bool exact;
+    int nbt, place;
+    bool split;
+};
+inline FormName vi_dense_form_name(const ViDenseForm &f)
+{
+    static const char *const place[3] = {"global", "lds", "pieces"};
+    FormName n;
+    if (f.exact) snprintf(n.s, sizeof(n.s), "vi_dense_exact_n%d_%s", f.nbt, place[f.place]);
+    else snprintf(n.s, sizeof(n.s), "vi_dense_mfma%s", f.split ? "_split" : "");
+    return n;
+}
+inline std::string vi_form_names()
+{
+    std::string out;
+    auto add = [&](const FormName &n) { out += n.s; out += '\n'; };
+    for (int kind = VD_SMALL; kind <= VD_CHAIN; kind += 2)
+        for (int graph = 0; graph <= (kind == VD_CHAIN ? 1 : 0); ++graph) {
+            for (int a : kViDetUnrolled) add(vi_det_form_name({kind, a, 1, graph != 0}));
+            add(vi_det_form_name({kind, 0, 1, graph != 0}));
+        }
+    for (const auto &f : kViPersist) add(vi_det_form_name({VD_PERSIST, f[0], f[1], false}));
+    add(vi_sparse_form_name(false));
+    add(vi_sparse_form_name(true));
+    for (int t : kViExactNbt)
+        for (int place = 1; place <= 3; ++place) add(vi_dense_form_name({true, t, place % 3, false}));
+    add(vi_dense_form_name({false, 0, 0, false}));
+    add(vi_dense_form_name({false, 0, 0, true}));
+    return out;
+}
+
 // ---- OPD (opd.hip) and robust OPD (ropd.hip).  any_a: |A| > 64, the plain kernel.  Else glb: the wide kernel in its sibling
 // (sib) or residue-class layout; !glb: the LDS-resident kernel, the parent map in HBM with expg, the closing pass on the node
 // array with chain.  nonneg picks the cheaper main loops everywhere.
@@ -148,7 +233,8 @@ inline FormName uct_stoch_form_name(int wbk, bool p16, int at, bool pol)
     return n;
 }
 
-// every name an entry point can record, one per line (Sparse Sampling's two are listed by mp_ss_form_names)
+// every name an entry point can record, one per line (Sparse Sampling's two are listed by mp_ss_form_names, single-model
+// value iteration's by mp_vi_form_names)
 inline std::string all_form_names()
 {
     std::string out;

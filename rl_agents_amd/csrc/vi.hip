@@ -20,6 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -670,7 +671,7 @@ __global__ __launch_bounds__(256) void vi_dense_combine(ViGenArgs p)
 // value); leaf results go to LDS and the recursion's additions are done level by level from a table the host derives
 // from the row length -- including what the ufunc machinery adds: the reduction's iterator hands the inner loop at most
 // numpy.getbufsize() = 8192 elements at a time, so a longer row is the running sum, from the identity 0., of the pairwise
-// sums of its 8192-element pieces.  V is staged in LDS: all of it where it fits beside the tables (S <= ~14 000), else the
+// sums of its 8192-element pieces.  V is staged in LDS: all of it where it fits beside the tables (vi_exact_geometry; mp_vi_geometry reports it), else the
 // piece being summed (VM below).  The kernel streams T once, as the matrix-core kernel does: it is bound by HBM, not by the
 // order of its additions.
 struct ViExactPlan {
@@ -683,8 +684,8 @@ struct ViExactPlan {
 
 enum { VI_V_GLOBAL = 0, VI_V_LDS = 1, VI_V_PIECES = 2 };
 
-// VM: where the lanes read V from.  VI_V_LDS: all of it staged once per workgroup (it fits beside the tables up to ~14 000
-// states).  VI_V_PIECES: longer rows -- the 8192-element piece the workgroup's waves are summing, staged between two
+// VM: where the lanes read V from.  VI_V_LDS: all of it staged once per workgroup (where it fits beside the tables:
+// vi_exact_geometry).  VI_V_PIECES: longer rows -- the 8192-element piece the workgroup's waves are summing, staged between two
 // barriers (the waves of a workgroup then walk their rows in step; read through L2 instead, every wave-load of T is
 // matched by one of V that misses the 32 KB L1: 5.45 against 4.0 ms per sweep on a 25 GB row block).  VI_V_GLOBAL: no staging.
 template <int NBT, int VM>
@@ -940,7 +941,39 @@ static int vi_dense_exact_launch_nb(const ViGenArgs &a, const ViExactPlan &pl, i
     return vi_dense_exact_launch_vm<NBT, VI_V_GLOBAL>(a, pl, grid, block, lds, st);
 }
 
-static int vi_dense_exact_launch(mp_ctx *ctx, ViGenArgs &a, hipStream_t st, int *launches)
+// What a launch of vi_dense_exact_q derives from the row length and its summation tables (vi_exact_plan_host), shared with
+// mp_vi_geometry: waves per workgroup, the LDS bytes of the tables, where V goes by default and with the knobs, the unrolled
+// steps of a leaf.  MP_VI_EXACT_WAVES, MP_VI_EXACT_V and MP_VI_EXACT_NO_VLDS are read here.
+struct ViExactGeom {
+    int nw, nbt, vm_default, vm;
+    size_t fixed, lds;
+};
+static ViExactGeom vi_exact_geometry(int Sc, int nleaf, int nnode, int nh, int npiece, int nb)
+{
+    ViExactGeom g;
+    const int nslot = nleaf + nnode;
+    // Eight waves per workgroup: measured 0.669 ms per sweep at S = 10 000 against 0.700 with sixteen (50 000 rows over 2 048
+    // waves leave a shorter tail than over 4 096) -- each wave keeps up to sixteen 512-byte loads in flight.
+    int nw = 8;
+    if (const char *e = getenv("MP_VI_EXACT_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 8) nw = v; } // (launch bounds: 512 threads)
+    const size_t tab = (size_t)nslot + (size_t)(nh + npiece + 3) / 2;
+    while (nw > 1 && (tab + (size_t)nw * nslot) * sizeof(double) > kLdsBytes / 2) nw >>= 1;
+    const size_t fixed = (tab + (size_t)nw * nslot) * sizeof(double);
+    int vm = VI_V_GLOBAL;
+    if (fixed + (size_t)Sc * sizeof(double) <= kLdsBytes - 1024) vm = VI_V_LDS;
+    else if (fixed + (size_t)kViPiece * sizeof(double) <= kLdsBytes - 1024) vm = VI_V_PIECES;
+    g.vm_default = vm;
+    if (const char *e = getenv("MP_VI_EXACT_V")) { // test / measurement knob: global | pieces (whole-V staging only where it fits)
+        if (!strcmp(e, "global")) vm = VI_V_GLOBAL;
+        else if (!strcmp(e, "pieces") && fixed + (size_t)kViPiece * sizeof(double) <= kLdsBytes - 1024) vm = VI_V_PIECES;
+    }
+    if (getenv("MP_VI_EXACT_NO_VLDS")) vm = VI_V_GLOBAL;
+    const size_t vbytes = vm == VI_V_LDS ? (size_t)Sc * sizeof(double) : (vm == VI_V_PIECES ? (size_t)kViPiece * sizeof(double) : 0);
+    g.nw = nw; g.nbt = vi_exact_nbt(nb); g.vm = vm; g.fixed = fixed; g.lds = fixed + vbytes;
+    return g;
+}
+
+static int vi_dense_exact_launch(mp_ctx *ctx, ViGenArgs &a, hipStream_t st, int *launches, FormName *form)
 {
     if (ctx->vi_exact_cols != a.Sc) { // the summation tables of this row length (a few KB, uploaded once)
         std::vector<int> leaves, nodes, hoff, piece;
@@ -967,25 +1000,10 @@ static int vi_dense_exact_launch(mp_ctx *ctx, ViGenArgs &a, hipStream_t st, int 
     pl.hoff = d + 2 * pl.nleaf + 2 * pl.nnode;
     pl.piece = pl.hoff + pl.nh + 1;
     const long SA = (long)a.S * a.A;
-    const int nslot = pl.nleaf + pl.nnode;
-    // Eight waves per workgroup: measured 0.669 ms per sweep at S = 10 000 against 0.700 with sixteen (50 000 rows over 2 048
-    // waves leave a shorter tail than over 4 096) -- each wave keeps up to sixteen 512-byte loads in flight.
-    int nw = 8;
-    if (const char *e = getenv("MP_VI_EXACT_WAVES")) { const int v = atoi(e); if (v >= 1 && v <= 8) nw = v; } // (launch bounds: 512 threads)
-    const size_t tab = (size_t)nslot + (size_t)(pl.nh + pl.npiece + 3) / 2;
-    while (nw > 1 && (tab + (size_t)nw * nslot) * sizeof(double) > kLdsBytes / 2) nw >>= 1;
-    const size_t fixed = (tab + (size_t)nw * nslot) * sizeof(double);
-    if (fixed > kLdsBytes - 1024) return fail(MP_ERR_ARG, "vi: rows of %d columns need %zu bytes of LDS for the summation tables", a.Sc, fixed);
-    int vm = VI_V_GLOBAL;
-    if (fixed + (size_t)a.Sc * sizeof(double) <= kLdsBytes - 1024) vm = VI_V_LDS;
-    else if (fixed + (size_t)kViPiece * sizeof(double) <= kLdsBytes - 1024) vm = VI_V_PIECES;
-    if (const char *e = getenv("MP_VI_EXACT_V")) { // test / measurement knob: global | pieces (whole-V staging only where it fits)
-        if (!strcmp(e, "global")) vm = VI_V_GLOBAL;
-        else if (!strcmp(e, "pieces") && fixed + (size_t)kViPiece * sizeof(double) <= kLdsBytes - 1024) vm = VI_V_PIECES;
-    }
-    if (getenv("MP_VI_EXACT_NO_VLDS")) vm = VI_V_GLOBAL;
-    const size_t vbytes = vm == VI_V_LDS ? (size_t)a.Sc * sizeof(double) : (vm == VI_V_PIECES ? (size_t)kViPiece * sizeof(double) : 0);
-    const size_t lds = fixed + vbytes;
+    const ViExactGeom g = vi_exact_geometry(a.Sc, pl.nleaf, pl.nnode, pl.nh, pl.npiece, ctx->vi_exact_nb);
+    if (g.fixed > kLdsBytes - 1024) return fail(MP_ERR_ARG, "vi: rows of %d columns need %zu bytes of LDS for the summation tables", a.Sc, g.fixed);
+    const int nw = g.nw, vm = g.vm;
+    const size_t lds = g.lds;
     const long groups = (SA + nw - 1) / nw;
     int wg_per_cu = (int)((kLdsBytes - 1024) / (lds > 0 ? lds : 1));
     if (wg_per_cu > 2048 / (64 * nw)) wg_per_cu = 2048 / (64 * nw);
@@ -994,26 +1012,35 @@ static int vi_dense_exact_launch(mp_ctx *ctx, ViGenArgs &a, hipStream_t st, int 
     const long cap = (long)ctx->prop.multiProcessorCount * wg_per_cu;
     const unsigned grid = (unsigned)(groups < cap ? groups : cap);
     const unsigned block = 64u * (unsigned)nw;
-    const int nb = ctx->vi_exact_nb;
     int rc;
-    if (nb <= 8) rc = vi_dense_exact_launch_nb<8>(a, pl, vm, grid, block, lds, st);
-    else if (nb <= 10) rc = vi_dense_exact_launch_nb<10>(a, pl, vm, grid, block, lds, st);
-    else if (nb <= 12) rc = vi_dense_exact_launch_nb<12>(a, pl, vm, grid, block, lds, st);
-    else if (nb <= 14) rc = vi_dense_exact_launch_nb<14>(a, pl, vm, grid, block, lds, st);
-    else rc = vi_dense_exact_launch_nb<16>(a, pl, vm, grid, block, lds, st);
+    switch (g.nbt) {
+    case 8: rc = vi_dense_exact_launch_nb<8>(a, pl, vm, grid, block, lds, st); break;
+    case 10: rc = vi_dense_exact_launch_nb<10>(a, pl, vm, grid, block, lds, st); break;
+    case 12: rc = vi_dense_exact_launch_nb<12>(a, pl, vm, grid, block, lds, st); break;
+    case 14: rc = vi_dense_exact_launch_nb<14>(a, pl, vm, grid, block, lds, st); break;
+    default: rc = vi_dense_exact_launch_nb<16>(a, pl, vm, grid, block, lds, st); break;
+    }
+    if (form) *form = vi_dense_form_name({true, g.nbt, vm, false});
     if (rc != MP_OK) return rc;
     if (launches) ++*launches;
     return MP_OK;
 }
 
-// launch the dense backup (split by column segments when the rows are long)
-static int vi_dense_launch(mp_ctx *ctx, ViGenArgs &a, hipStream_t st, int *launches)
+// column segments of the matrix-core form for rows of Sc columns (MP_DENSE_NO_SPLIT=1: never split); shared with mp_vi_geometry
+static int vi_dense_segments(int Sc)
 {
-    if (vi_dense_exact_on(ctx)) return vi_dense_exact_launch(ctx, a, st, launches);
+    return Sc > kDenseSegCols && !getenv("MP_DENSE_NO_SPLIT") ? (Sc + kDenseSegCols - 1) / kDenseSegCols : 1;
+}
+
+// launch the dense backup (split by column segments when the rows are long); form: the name of what was launched
+static int vi_dense_launch(mp_ctx *ctx, ViGenArgs &a, hipStream_t st, int *launches, FormName *form)
+{
+    if (vi_dense_exact_on(ctx)) return vi_dense_exact_launch(ctx, a, st, launches, form);
     const long SA = (long)a.S * a.A;
     a.seg_cols = kDenseSegCols;
-    a.nseg = a.Sc > kDenseSegCols && !getenv("MP_DENSE_NO_SPLIT") ? (a.Sc + kDenseSegCols - 1) / kDenseSegCols : 1;
+    a.nseg = vi_dense_segments(a.Sc);
     if (a.nseg == 1) a.seg_cols = a.Sc;
+    if (form) *form = vi_dense_form_name({false, 0, 0, a.nseg > 1});
     a.partial = nullptr;
     if (a.nseg > 1) MP_TRY(ws_get(ctx, WS_VI4, (size_t)a.M * a.nseg * SA, &a.partial));
     hipLaunchKernelGGL(vi_dense_q, dim3((unsigned)((SA + 63) / 64), (unsigned)a.nseg), dim3(256), kDenseChunk * sizeof(double), st, a);
@@ -1132,20 +1159,37 @@ static int vi_persist_block(int S)
     return 256;
 }
 
-static bool vi_persist_ok(mp_ctx *ctx, int S, int A, int M)
+static bool vi_persist_ok(int cus, int S, int A, int M)
 {
     if (getenv("MP_VI_NO_PERSIST")) return false;
     const int n_wg = (S + vi_persist_block(S) - 1) / vi_persist_block(S);
-    if (n_wg > ctx->prop.multiProcessorCount) return false;
+    if (n_wg > cus) return false;
     // Measured on MI355X (tools/micro_vi_persist.py): 40 workgroups (S = 10 000) 2.6 us per sweep against
     // 3.0 us for the chained launches, and the early exit really ends the solve; 196 workgroups (S = 50 000, M = 2)
     // 5.4 us against 4.2 us -- the per-sweep arrivals serialise on one word and the hand-offs queue behind each other.
     if (n_wg > 64 && !getenv("MP_VI_PERSIST_BLOCK")) return false;
-    const bool at = A == 2 || A == 3 || A == 4 || A == 5 || A == 6 || A == 8;
-    if (!at || M < 1 || M > 4) return false;
-    if (M == 3 && A > 5) return false;
-    if (M == 4 && A > 4) return false;
-    return true;
+    return vi_persist_form_exists(A, M); // (what vi_persist_dispatch is instantiated for)
+}
+
+// Which kernel family a deterministic solve of M models of S states and A actions takes on a device of `cus` compute units,
+// shared with mp_vi_geometry.  MP_VI_NO_SMALL, MP_VI_NO_PERSIST and MP_VI_PERSIST_BLOCK are read here.
+struct ViDetGeom {
+    size_t small_lds;            // LDS bytes of the single-workgroup kernel: three V iterates and the tables
+    bool small_fits, small;      // they fit / that kernel is taken (MP_VI_NO_SMALL unset)
+    int block, n_wg;             // the persistent grid
+    bool persist;                // ... is admitted (and taken, unless `small`)
+};
+static ViDetGeom vi_det_geometry(int cus, int S, int A, int M)
+{
+    ViDetGeom g;
+    const long SA = (long)S * A;
+    g.small_lds = (size_t)3 * S * sizeof(double) + (size_t)M * SA * (sizeof(double) + sizeof(int32_t));
+    g.small_fits = g.small_lds <= kLdsBytes - 2048 && A <= 64;
+    g.small = g.small_fits && !getenv("MP_VI_NO_SMALL");
+    g.block = vi_persist_block(S);
+    g.n_wg = (S + g.block - 1) / g.block;
+    g.persist = vi_persist_ok(cus, S, A, M);
+    return g;
 }
 
 static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, double rtol, double atol, int robust,
@@ -1179,8 +1223,10 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
     int launches = 0;
     bool persisted = false;
     unsigned *persist_sync = nullptr;
-    const size_t small_lds = (size_t)3 * S * sizeof(double) + (size_t)M * SA * (sizeof(double) + sizeof(int32_t));
-    if (m->mode == MP_MODE_DETERMINISTIC && small_lds <= kLdsBytes - 2048 && A <= 64 && !getenv("MP_VI_NO_SMALL")) {
+    const ViDetGeom dg = vi_det_geometry(ctx->prop.multiProcessorCount, S, A, M);
+    const size_t small_lds = dg.small_lds;
+    FormName form = {""};
+    if (m->mode == MP_MODE_DETERMINISTIC && dg.small) {
         ViSmallArgs q;
         memset(&q, 0, sizeof(q));
         q.d.M = M; q.d.S = S; q.d.A = A; q.d.robust = robust; q.d.vform = vform;
@@ -1201,7 +1247,8 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
             break;
         }
         MP_TRY(kernels_end(ctx, 1));
-    } else if (m->mode == MP_MODE_DETERMINISTIC && allow_persist && vi_persist_ok(ctx, S, A, M)) {
+        form = vi_det_form_name({VD_SMALL, vi_det_unrolled(A), M, false});
+    } else if (m->mode == MP_MODE_DETERMINISTIC && allow_persist && dg.persist) {
         // one persistent launch: every state owns a thread of a co-resident grid (see vi_det_persist)
         persisted = true;
         ViPersistArgs q;
@@ -1209,8 +1256,8 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
         q.d.M = M; q.d.S = S; q.d.A = A; q.d.robust = robust; q.d.vform = vform;
         q.d.T = m->T; q.d.R = m->R; q.d.term = m->term; q.d.gamma = gamma; q.d.rtol = rtol; q.d.atol = atol;
         q.iterations = iterations;
-        q.block = vi_persist_block(S);
-        q.n_wg = (S + q.block - 1) / q.block;
+        q.block = dg.block;
+        q.n_wg = dg.n_wg;
         q.Q_out = dQ; q.V_out = dV; q.sweeps_out = dSw;
         MP_TRY(ws_get(ctx, WS_VI1, (size_t)kRing * S * 2, &q.Vring));
         MP_TRY(ws_get(ctx, WS_VI3, (size_t)iterations + 4, &q.sync));
@@ -1228,6 +1275,7 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
         MP_TRY(kernels_begin(ctx));
         if (!vi_persist_dispatch(q, A, M, st)) return fail(MP_ERR_ARG, "vi: no persistent kernel for |A| = %d, M = %d", A, M);
         MP_TRY(kernels_end(ctx, 1));
+        form = vi_det_form_name({VD_PERSIST, A, M, false});
         hipLaunchKernelGGL(vi_persist_status, dim3(1), dim3(1), 0, st, q.sync, dSw);
     } else if (m->mode == MP_MODE_DETERMINISTIC) {
         double *Vb = nullptr;
@@ -1268,6 +1316,7 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
                 MP_HIP(hipGraphDestroy(graph));
                 ctx->vi_graph_exec = exec;
                 memcpy(&ctx->vi_graph_key, &key, sizeof(key));
+                ++ctx->vi_graph_captures;
             }
             MP_HIP(hipGraphLaunch((hipGraphExec_t)ctx->vi_graph_exec, st));
             launches = iterations;
@@ -1282,6 +1331,7 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
             }
         }
         MP_TRY(kernels_end(ctx, launches));
+        if (iterations > 0) form = vi_det_form_name({VD_CHAIN, vi_det_unrolled(A), M, use_graph});
         a.k = 0;
         hipLaunchKernelGGL(vi_find_stop, dim3(1), dim3(64), 0, st, iterations, notclose, result);
         ViEmitArgs e;
@@ -1306,8 +1356,9 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
             a.Qcur = Qb + (long)(k & 1) * SA;
             a.Qnext = Qb + (long)((k + 1) & 1) * SA;
             if (m->mode == MP_MODE_STOCHASTIC) {
-                MP_TRY(vi_dense_launch(ctx, a, st, &launches));
+                MP_TRY(vi_dense_launch(ctx, a, st, &launches, &form));
             } else {
+                form = vi_sparse_form_name(a.B > 128);
                 if (a.B > 128) hipLaunchKernelGGL(vi_sparse_q<true>, dim3(gq_sparse), dim3(256), 0, st, a);
                 else hipLaunchKernelGGL(vi_sparse_q<false>, dim3(gq_sparse), dim3(256), 0, st, a);
                 ++launches;
@@ -1321,6 +1372,7 @@ static int vi_run_impl(mp_ctx *ctx, mp_model *m, double gamma, int iterations, d
         e.S = S; e.A = A; e.Qbuf = Qb; e.Vbuf = Vb; e.result = result; e.Q_out = dQ; e.V_out = dV; e.sweeps_out = dSw;
         hipLaunchKernelGGL(vi_gen_emit, dim3((unsigned)((SA + 255) / 256)), dim3(256), 0, st, e);
     }
+    form_record(ctx->last_variant, form); // (0 sweeps on the chained, dense or sparse path: no sweep is launched, "")
     MP_HIP(hipGetLastError());
     MP_TRY(stage_out_copy(ctx, Q_out, dQ, (size_t)SA, mem));
     MP_TRY(stage_out_copy(ctx, V_out, dV, (size_t)S, mem));
@@ -1956,8 +2008,10 @@ static int vi_backup(mp_ctx *ctx, mp_model *m, double gamma, int robust, const d
     a.P = m->P; a.R = m->R; a.term = m->term; a.gamma = gamma; a.Vcur = dV; a.Qnext = dQ; a.notclose = flag;
     MP_TRY(kernels_begin(ctx));
     int launches = 0;
-    MP_TRY(vi_dense_launch(ctx, a, st, &launches));
+    FormName form = {""};
+    MP_TRY(vi_dense_launch(ctx, a, st, &launches, &form));
     MP_TRY(kernels_end(ctx, launches));
+    form_record(ctx->last_variant, form);
     MP_HIP(hipGetLastError());
     MP_TRY(stage_out_copy(ctx, Q, dQ, (size_t)SA, mem));
     if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
@@ -2018,6 +2072,35 @@ int mp_vi_exact_plan(int32_t n, int32_t cap_leaves, int32_t *leaves, int32_t cap
     if (hoff && (size_t)cap_heights + 1 >= ho.size()) memcpy(hoff, ho.data(), ho.size() * sizeof(int));
     return MP_OK;
 }
+
+const char *mp_vi_form_names(void)
+{
+    static const std::string names = mp::vi_form_names();
+    return names.c_str();
+}
+
+int mp_vi_geometry(int32_t mode, int32_t S, int32_t A, int32_t M, int32_t Sc, int32_t cus, int64_t *out)
+{
+    if (!out) return mp::fail(MP_ERR_ARG, "mp_vi_geometry: NULL argument");
+    if (S < 1 || A < 1 || M < 1 || Sc < 1 || cus < 1) return mp::fail(MP_ERR_ARG, "mp_vi_geometry: sizes must be positive");
+    if (mode != MP_MODE_DETERMINISTIC && mode != MP_MODE_STOCHASTIC)
+        return mp::fail(MP_ERR_MODE, "mp_vi_geometry: deterministic tables or dense rows (mode %d)", (int)mode);
+    for (int i = 0; i < 14; ++i) out[i] = 0;
+    if (mode == MP_MODE_DETERMINISTIC) {
+        const mp::ViDetGeom g = mp::vi_det_geometry(cus, S, A, M);
+        out[0] = (int64_t)g.small_lds; out[1] = g.small_fits; out[2] = g.small; out[3] = g.block; out[4] = g.n_wg; out[5] = g.persist;
+        return MP_OK;
+    }
+    std::vector<int> lv, nd, ho, pc;
+    int nb = 1;
+    mp::vi_exact_plan_host(Sc, lv, nd, ho, pc, &nb);
+    const mp::ViExactGeom g = mp::vi_exact_geometry(Sc, (int)lv.size() / 2, (int)nd.size() / 2, (int)ho.size() - 1, (int)pc.size() - 1, nb);
+    out[6] = nb; out[7] = g.nbt; out[8] = g.nw; out[9] = (int64_t)g.fixed; out[10] = g.vm_default; out[11] = g.vm;
+    out[12] = mp::vi_dense_segments(Sc); out[13] = out[12] > 1 ? mp::kDenseSegCols : Sc;
+    return MP_OK;
+}
+
+int64_t mp_vi_graph_captures(mp_ctx *ctx) { return ctx ? ctx->vi_graph_captures : 0; }
 
 int mp_vi_sweeps(mp_ctx *ctx, mp_model *model, double gamma, int32_t sweeps, int32_t robust)
 {

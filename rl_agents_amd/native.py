@@ -64,6 +64,9 @@ SIGNATURES = {
     "mp_vi_solve_v": (C.c_int, [_vp, _vp, c_f64, c_i32, c_f64, c_f64, _vp, c_i32]),
     "mp_vi_solve_v_robust": (C.c_int, [_vp, _vp, c_f64, c_i32, c_f64, c_f64, _vp, c_i32]),
     "mp_vi_sweeps": (C.c_int, [_vp, _vp, c_f64, c_i32, c_i32]),
+    "mp_vi_form_names": (C.c_char_p, []),
+    "mp_vi_graph_captures": (c_i64, [_vp]),
+    "mp_vi_geometry": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _vp]),
     "mp_vi_dense_mode": (C.c_int, [_vp, c_i32]),
     "mp_uct_record_visits": (C.c_int, [_vp, _vp]),
     "mp_vi_exact_plan": (C.c_int, [c_i32, c_i32, _vp, c_i32, _vp, c_i32, _vp, _vp]),
@@ -314,6 +317,30 @@ def ss_geometry(n_actions, horizon, C, W):
                 lds=bool(out[4]))
 
 
+def vi_form_names():
+    """The names the single-model value-iteration calls (vi_solve, vi_solve_v, vi_sweeps, vi_backup) record for
+    Context.last_kernel_variant() (mp_vi_form_names; host only).  They are not part of kernel_form_names()."""
+    return load().mp_vi_form_names().decode().split()
+
+
+VI_V_PLACEMENT = ("global", "lds", "pieces")
+
+
+def vi_geometry(mode, S=1, A=1, M=1, Sc=None, cus=256):
+    """Host arithmetic of a single-model value-iteration launch (mp_vi_geometry; no device) on a device of ``cus`` compute
+    units; the MP_VI_* knobs are read from the environment.  ``mode`` "deterministic": M models of S states and A actions ->
+    dict(small_lds, small_fits, small, persist_block, persist_wgs, persist); ``mode`` "stochastic": dense rows of ``Sc`` columns
+    -> dict(nb, nbt, waves, fixed_lds, v_default, v, nseg, seg_cols), the V placements as "lds" | "pieces" | "global"."""
+    out = np.zeros(14, np.int64)
+    code = {"deterministic": MODE_DETERMINISTIC, "stochastic": MODE_STOCHASTIC}[mode]
+    _check(load().mp_vi_geometry(code, int(S), int(A), int(M), int(S if Sc is None else Sc), int(cus), _ptr(out)))
+    if mode == "deterministic":
+        return dict(small_lds=int(out[0]), small_fits=bool(out[1]), small=bool(out[2]), persist_block=int(out[3]),
+                    persist_wgs=int(out[4]), persist=bool(out[5]))
+    return dict(nb=int(out[6]), nbt=int(out[7]), waves=int(out[8]), fixed_lds=int(out[9]), v_default=VI_V_PLACEMENT[out[10]],
+                v=VI_V_PLACEMENT[out[11]], nseg=int(out[12]), seg_cols=int(out[13]))
+
+
 def vi_exact_plan(n):
     """The tables the bit-exact dense backup sums a row of ``n`` elements by (numpy's pairwise recursion; host only):
     -> (leaves int32 [L,2] {offset, length}, nodes int32 [K,2] {left slot, right slot} by height, hoff int32 [H+1],
@@ -397,9 +424,17 @@ class Context(object):
         return ms.value, n.value
 
     def last_kernel_variant(self):
-        """Which kernel form the last plan / batched VI call launched ("uct_ldsr", "opd_wide_sib_small", "saopd_wave_dict", ...:
-        every name in kernel_form_names(); after a Sparse Sampling plan one of ss_form_names(), which that list does not hold)."""
+        """Which kernel form the last plan / value-iteration call launched ("uct_ldsr", "opd_wide_sib_small", "saopd_wave_dict", ...:
+        every name in kernel_form_names(); after a Sparse Sampling plan one of ss_form_names(), after a single-model
+        value-iteration call (vi_solve, vi_solve_v, vi_sweeps, vi_backup) one of vi_form_names() -- the launch that produced the
+        returned values -- neither of which that list holds)."""
         return self._lib.mp_last_kernel_variant(self._h).decode()
+
+    def vi_graph_captures(self):
+        """How many times this context has captured a chain of deterministic value-iteration sweeps into a graph
+        (mp_vi_graph_captures): a "vi_det_chain_*_graph" call whose key -- model, pointers, sizes, iterations, gamma, tolerances,
+        Q or V form -- is the cached one replays the graph and leaves the count alone."""
+        return int(self._lib.mp_vi_graph_captures(self._h))
 
     # ---- the collective of the C ABI (RCCL resolved at run time): what a consumer without torch.distributed calls ------------
     @staticmethod

@@ -2,6 +2,8 @@
 import numpy as np
 import pytest
 
+from tests.helpers import assert_form
+
 pytestmark = pytest.mark.gpu
 
 
@@ -29,10 +31,13 @@ def test_persistent_vi_gives_up_and_the_call_solves_again(ctx, robust, monkeypat
     q_ref, sweeps_ref = oracle.vi_solve("deterministic", t, r, term, gamma=0.95, iterations=200, robust=robust)
     q, sweeps = ctx.vi_solve(model, 0.95, 200, robust=robust)
     assert ctx.last_kernel_ms()[1] == 1, "C2 is expected to run on the single persistent launch"
+    persist = "vi_det_persist_a5_m{}".format(2 if robust else 1)
+    assert_form(ctx, persist)
     assert sweeps == sweeps_ref and np.array_equal(q, q_ref)
     monkeypatch.setenv("MP_VI_PERSIST_INJECT_TIMEOUT", "1")
     q2, sweeps2 = ctx.vi_solve(model, 0.95, 200, robust=robust)
     assert ctx.last_kernel_ms()[1] > 1, "the fallback runs the chained launches"
+    assert_form(ctx, "vi_det_chain_a5_graph")       # (the form that produced what the caller received)
     assert sweeps2 == sweeps_ref and np.array_equal(q2, q_ref)
     v = ctx.vi_solve_v(model, 0.95, 200) if not robust else None
     if v is not None:
@@ -49,6 +54,7 @@ def test_persistent_vi_gives_up_and_the_call_solves_again(ctx, robust, monkeypat
     monkeypatch.delenv("MP_VI_PERSIST_INJECT_TIMEOUT")
     ctx.vi_solve_device(model, 0.95, 200, d_q, d_sw, robust=robust)
     ctx.synchronize()
+    assert_form(ctx, persist)
     assert native.check_device_sweeps(d_sw) == sweeps_ref and np.array_equal(d_q.cpu().numpy(), q_ref)
     model.close()
 

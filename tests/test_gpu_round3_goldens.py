@@ -64,9 +64,12 @@ def test_robust_state_value_all_device_paths_vs_oracle(ctx, n_states, n_models, 
     want = oracle.vi_solve("deterministic", t, r, None, gamma=0.9, iterations=150, robust=True, state_value=True)
     model = ctx.load_table(t, r)
     assert np.array_equal(ctx.vi_solve_v(model, 0.9, 150, robust=True), want)
+    # (M = 3 at S = 700: the tables fit one workgroup's LDS; S = 20 000 is past the persistent grid's 64 workgroups)
+    assert_form(ctx, {10000: "vi_det_persist_a4_m2", 700: "vi_det_small_a4", 20000: "vi_det_chain_a4_graph"}[n_states])
     monkeypatch.setenv("MP_VI_NO_PERSIST", "1")
     monkeypatch.setenv("MP_VI_NO_SMALL", "1")
     assert np.array_equal(ctx.vi_solve_v(model, 0.9, 150, robust=True), want)
+    assert_form(ctx, "vi_det_chain_a4_graph")
     model.close()
 
 

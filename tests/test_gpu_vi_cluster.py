@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from rl_agents_amd import native
+from tests.helpers import assert_form
 
 pytestmark = pytest.mark.gpu
 
@@ -292,16 +293,20 @@ def test_persistent_one_workgroup_gives_up(ctx, monkeypatch, c2_problems, robust
     monkeypatch.setenv("MP_VI_PERSIST_GIVE_UP", "{},{}".format(0 if wg == "first" else n_wg - 1, sweep))
     q, sweeps = ctx.vi_solve(model, 0.95, 200, robust=robust)
     fired = when != "past"
+    persist = "vi_det_persist_a5_m{}".format(2 if robust else 1)
     if fired:
         assert ctx.last_kernel_ms()[1] > 1, "the fallback runs the chained launches"
+        assert_form(ctx, "vi_det_chain_a5_graph")
     else:
         assert ctx.last_kernel_ms()[1] == 1, "C2 is expected to run on the single persistent launch"
+        assert_form(ctx, persist)
     assert sweeps == sw_ref and np.array_equal(q, q_ref)
     d_q = torch.full((model.S, model.A), float("nan"), dtype=torch.float64, device="cuda")
     d_sw = torch.full((1,), -7, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     ctx.vi_solve_device(model, 0.95, 200, d_q, d_sw, robust=robust)
     ctx.synchronize()
+    assert_form(ctx, persist)                                    # (device arrays: no fallback, the failure is reported)
     if fired:
         with pytest.raises(native.NativeError):
             native.check_device_sweeps(d_sw)

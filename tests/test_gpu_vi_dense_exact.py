@@ -10,7 +10,7 @@ halves, several levels, a remainder in the last block only.
 import numpy as np
 import pytest
 
-from tests.helpers import mdp_from_golden
+from tests.helpers import assert_form, mdp_from_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -126,26 +126,35 @@ def test_v_through_l2_and_mode_switch(ctx, monkeypatch):
     model = ctx.load_dense(cfg["transition"], cfg["reward"], cfg["terminal"])
     q_ref, sweeps_ref = oracle.vi_solve("stochastic", cfg["transition"], cfg["reward"], cfg["terminal"], gamma=0.9,
                                         iterations=30)
+    from rl_agents_amd import native
+    nbt = native.vi_geometry("stochastic", Sc=700)["nbt"]
     monkeypatch.setenv("MP_VI_EXACT_NO_VLDS", "1")
     q, sweeps = ctx.vi_solve(model, 0.9, 30)
+    assert_form(ctx, "vi_dense_exact_n{}_global".format(nbt))
     assert sweeps == sweeps_ref and np.array_equal(q, q_ref)
     monkeypatch.delenv("MP_VI_EXACT_NO_VLDS")
     monkeypatch.setenv("MP_VI_EXACT_V", "pieces")
     q, sweeps = ctx.vi_solve(model, 0.9, 30)
+    assert_form(ctx, "vi_dense_exact_n{}_pieces".format(nbt))
     assert sweeps == sweeps_ref and np.array_equal(q, q_ref)
     monkeypatch.delenv("MP_VI_EXACT_V")
     monkeypatch.setenv("MP_VI_EXACT_WAVES", "4")
+    assert native.vi_geometry("stochastic", Sc=700)["waves"] == 4
     q, sweeps = ctx.vi_solve(model, 0.9, 30)
+    assert_form(ctx, "vi_dense_exact_n{}_lds".format(nbt))
     assert sweeps == sweeps_ref and np.array_equal(q, q_ref)
     monkeypatch.delenv("MP_VI_EXACT_WAVES")
+    assert native.vi_geometry("stochastic", Sc=700)["waves"] == 8
     ctx.vi_dense_mode("mfma")
     try:
         q_m, sweeps_m = ctx.vi_solve(model, 0.9, 30)
+        assert_form(ctx, "vi_dense_mfma")
         np.testing.assert_allclose(q_m, q_ref, rtol=1e-12, atol=1e-12)
         assert abs(sweeps_m - sweeps_ref) <= 1
     finally:
         ctx.vi_dense_mode("exact")
     q, sweeps = ctx.vi_solve(model, 0.9, 30)
+    assert_form(ctx, "vi_dense_exact_n{}_lds".format(nbt))
     assert sweeps == sweeps_ref and np.array_equal(q, q_ref)
     model.close()
 
@@ -154,8 +163,9 @@ def test_v_through_l2_and_mode_switch(ctx, monkeypatch):
 def test_rows_longer_than_numpys_reduction_buffer(ctx, monkeypatch, s_cols, v_mode):
     """Rows of more than 8192 next states: numpy's add.reduce is the running sum of the pairwise sums of 8192-element
     pieces (tests/test_oracle_vi_long_rows.py pins the oracle on numpy for it).  A block of source rows of such a model
-    (the unit of the row-sharded solve), two models, against numpy's own expression and the oracle; 16 385 and 50 000
-    columns take the kernel form that stages V piece by piece (it no longer fits LDS), forced on 10 000 as well."""
+    (the unit of the row-sharded solve), two models, against numpy's own expression and the oracle; 50 000 columns take
+    the kernel form that stages V piece by piece (it no longer fits LDS beside the tables: native.vi_geometry), forced on
+    10 000 as well, where reading V through L2 is forced too; the form of each is asserted."""
     from oracle import oracle
     g = np.random.Generator(np.random.PCG64(s_cols))
     rows, a = 37, 2
@@ -165,8 +175,13 @@ def test_rows_longer_than_numpys_reduction_buffer(ctx, monkeypatch, s_cols, v_mo
     v = g.standard_normal(s_cols) * 3
     if v_mode:
         monkeypatch.setenv("MP_VI_EXACT_V", v_mode)
+    from rl_agents_amd import native
+    geo = native.vi_geometry("stochastic", Sc=s_cols)       # (read with the knob set: the placement the launch takes)
+    assert geo["v"] == (v_mode or geo["v_default"]) and geo["v_default"] == ("pieces" if s_cols == 50000 else "lds")
+    form = "vi_dense_exact_n{}_{}".format(geo["nbt"], geo["v"])
     blk = ctx.load_dense_rows(t, r, None)
     q = ctx.vi_backup(blk, 0.95, v, robust=True)
+    assert_form(ctx, form)
     ref = np.min(r + 0.95 * (t * v.reshape((1, 1, 1, v.size))).sum(axis=-1), axis=0)   # robust_value_iteration.py:46-58
     assert np.array_equal(q, ref)
     assert np.array_equal(q, oracle.dense_backup_rows(t, r, None, v, 0.95, robust=True))
@@ -174,6 +189,7 @@ def test_rows_longer_than_numpys_reduction_buffer(ctx, monkeypatch, s_cols, v_mo
     term = g.random(rows) < 0.3
     one = ctx.load_dense_rows(t[0], r[0], term)
     q1 = ctx.vi_backup(one, 0.95, v)
+    assert_form(ctx, form)
     next_v = (t[0] * v.reshape((1, 1, v.size))).sum(axis=-1)
     next_v[term] = 0
     assert np.array_equal(q1, r[0] + 0.95 * next_v)
