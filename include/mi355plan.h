@@ -542,6 +542,19 @@ int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
                         int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *value_upper,
                         uint8_t *done, int32_t *state);
 
+/* mp_olop_plan on a batch model with one MDP per root (see mp_uct_plan_models): root i plans on MDP model_index[i] from its
+ * LOCAL state root_state[i]; several roots may share an MDP.  Everything else as mp_olop_plan, and equal to it with
+ * root_state = model_index * S_each + root_state; validation, MP_MEM_HOST / MP_MEM_DEVICE and the clamp-and-count of
+ * out-of-range device arrays as mp_opd_plan_models; MP_ERR_MODE for a model that is not a deterministic table.  Replaces what
+ * mp_olop_plan replaces (olop.py:64-100, the per-episode safe_deepcopy_env of :72) for a batch of agents that each hold their
+ * own environment (trainer/evaluation.py:139-194, one process each).  The kernel either reads the batch model's records from
+ * global memory ("olop_each_global") or copies the root's own S_each * |A| records into LDS first ("olop_each_lds"):
+ * mp_each_form_info.  Nodes store GLOBAL states, and mp_olop_tree_export serves the trees afterwards. */
+int mp_olop_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                        int32_t episodes, int32_t horizon, double gamma, int32_t bound_type, int32_t continuation,
+                        const double *thresholds, const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len,
+                        int32_t *plans, int32_t *plan_len, double *root_value, int64_t *env_steps, int32_t *status, int32_t mem);
+
 /* ---------------------------------------------------------------- BRUE ---------------------- */
 /*
  * BRUE.plan (tree_search/brue.py:66-71) for n_roots independent roots of a deterministic table, dense or sparse model: while
@@ -571,6 +584,30 @@ int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
  * nodes).  When a batch's trees do not all fit the workspace only root 0's is kept (MP_ERR_ARG for the others). */
 int mp_brue_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *key,
                         uint8_t *is_chance, int32_t *depth, int64_t *count, double *stat);
+
+/* mp_brue_plan on a batch model of deterministic tables with one MDP per root (see mp_uct_plan_models / mp_olop_plan_models):
+ * model_index int32 [n_roots], root_state LOCAL; equal to BRUE.plan (brue.py:66-71, the per-rollout safe_deepcopy_env of :24)
+ * of one agent per MDP.  This entry accepts batch models (mp_brue_plan itself refuses them); MP_ERR_MODE for a dense / sparse
+ * or joint model.  Decision nodes' keys are GLOBAL states; mp_brue_tree_export serves the trees afterwards.  Forms
+ * "brue_each_global" / "brue_each_lds": mp_each_form_info. */
+int mp_brue_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                        int32_t budget, int32_t horizon, double gamma, const double *gpow, uint64_t *rng_state, int32_t *plans,
+                        double *root_value, int64_t *env_steps, int32_t *status, int32_t mem);
+/* The form mp_olop_plan_models (planner 0) / mp_brue_plan_models (planner 1) choose for a call of this description, on the host
+ * alone (no device, no ctx; the function the launch code calls).  A root of these calls reads only its own MDP -- the
+ * reference's agent only its own env (olop.py:72, brue.py:24) -- so its S_each * |A| 16-byte records can sit in LDS behind the
+ * kernel's own arrays (OLOP: path[horizon + 1] int32; BRUE: 16 bytes per step of the horizon; rounded up to 16 bytes).
+ * The LDS form is the default where it was measured faster: a workgroup of at most 160 KiB / 16 bytes (16 wavefronts stay
+ * resident on a CU); OLOP at any batch size, BRUE while all its roots' workgroups are resident at once.  MP_EACH_MODEL=lds|global
+ * in the environment forces a form ("lds" for any table that fits the 160 KiB of a CU, and only those).
+ *   out[6]: LDS bytes a workgroup of the LDS form takes (the arrays + S_each * |A| * 16), 1 if this call takes the LDS form else
+ *           0, the grid = min(n_roots, cus * min(32, floor(160 KiB / those bytes))) of the LDS form, min(n_roots, cus * 32) of the
+ *           global form, dynamic LDS bytes of the launch, the most bytes that take the LDS form by default, the most that fit. */
+int mp_each_form_info(int32_t planner, int32_t S_each, int32_t A, int32_t horizon, int32_t n_roots, int32_t cus, int64_t *out);
+/* The eight names the two entries above record for mp_last_kernel_variant, one per line: "olop_each_lds", "olop_each_global",
+ * "brue_each_lds", "brue_each_global", each also with "_slots" (see mp_last_kernel_variant).  They are not part of
+ * mp_kernel_form_names. */
+const char *mp_each_form_names(void);
 
 /* ---------------------------------------------------------------- Sparse Sampling ----------- */
 /*
@@ -828,7 +865,9 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
  *                 in LDS: a shared model / one MDP per root; a wavefront per root), "uct_policy", "uct_cartpole",
  *                 "uct_global_spill"
  *   batched VI    "vi_batch_reg<own,block>", "vi_batch_cluster2|4|8" (K workgroups per MDP), "vi_batch_wg_stream|lds|global"
- *   OLOP, BRUE    "olop_global", "brue_global" (a tree per root, kept for the export), "..._slots" (slots shared by the waves)
+ *   OLOP, BRUE    "olop_global", "brue_global" (a tree per root, kept for the export), "..._slots" (slots shared by the waves);
+ *                 one MDP per root (mp_olop_plan_models / mp_brue_plan_models): "olop_each_lds" / "olop_each_global",
+ *                 "brue_each_lds" / "brue_each_global", then "_slots"
  *   GBOP-D        "gbopd_wave_lds", "gbopd_wave_global"
  *   Sparse        "ss_wave_lds", "ss_wave_global" (the frames of the recursion in LDS / in a global workspace)
  *   Sampling
@@ -847,7 +886,8 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
 const char *mp_last_kernel_variant(mp_ctx *ctx);
 /* Every name mp_last_kernel_variant can return, one per line, built by the functions that name the launches (host only, no
  * device): a test table that is to cover every form is compared with this list.  (Sparse Sampling's two names are listed by
- * its own mp_ss_form_names, single-model value iteration's by mp_vi_form_names.) */
+ * its own mp_ss_form_names, single-model value iteration's by mp_vi_form_names, the one-MDP-per-root forms of OLOP and BRUE by
+ * mp_each_form_names.) */
 const char *mp_kernel_form_names(void);
 /* Hardware self-test (no reference counterpart): LDS atomics of ONE wavefront instruction that hit the same address apply
  * in LANE ORDER on this device -- the state-aware OPD kernel's grouped backup relies on it (one ds_min_rtn_f64 of the group

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "each_host.hpp"
 #include "pcg64.hpp"
 #include "seed_sequence.hpp"
 
@@ -61,6 +62,7 @@ struct BrueArgs {
     int32_t *plans, *status;
     double *root_value;
     int64_t *env_steps;
+    int Sb;                  // LDS_MODEL: states per MDP of the batch model (a root's MDP starts at global state (s / Sb) * Sb)
 };
 
 // First maximum of `stat` over the chance children of decision node `node` in creation order (Python max, brue.py:58; also the
@@ -96,17 +98,29 @@ __device__ __forceinline__ void brue_capture(const BrueNode *N, int &o, int m, i
     }
 }
 
+// LDS_MODEL (mp_brue_plan_models, one MDP per root, deterministic tables): the root's own Sb * |A| records sit in LDS behind
+// rew[] and po[] (16 bytes a step: the records stay 16-byte aligned), copied before its first rollout, and the rollout's step --
+// the only model read of a plan: `estimate` walks the tree -- is served from there.
+template <bool LDS_MODEL>
 __global__ __launch_bounds__(64) void brue_kernel(BrueArgs p)
 {
     extern __shared__ __attribute__((aligned(16))) char brue_smem[];
     double *rew = reinterpret_cast<double *>(brue_smem);           // [H] reward of the rollout's step
     int2 *po = reinterpret_cast<int2 *>(rew + p.H);                // [H] {chance node, decision node it led to}
+    Rec *lrec = reinterpret_cast<Rec *>(po + p.H);                 // [Sb * A] LDS_MODEL: the root's table
     const int lane = threadIdx.x, A = p.A, H = p.H;
     for (int root = blockIdx.x; root < p.n_roots; root += p.grid) {
         const long slot = p.keep ? root : (root == 0 ? p.grid : blockIdx.x);
         BrueNode *N = p.nodes + slot * p.cap;
         int32_t *C = p.ctab + slot * p.cap * A;
         const int s_root = p.root_state[root];
+        int base = 0;
+        if constexpr (LDS_MODEL) {                                 // (the previous root's reads ended at the barrier closing its iteration)
+            base = s_root / p.Sb * p.Sb;
+            const uint4 *src = reinterpret_cast<const uint4 *>(p.rec + (long)base * A);
+            uint4 *dst = reinterpret_cast<uint4 *>(lrec);
+            for (int i = lane; i < p.Sb * A; i += 64) dst[i] = src[i];
+        }
         if (lane == 0) {                                           // DecisionNode(parent=None), brue.py:22
             BrueNode r;
             r.stat = 0.0; r.count = 0; r.key = -1; r.parent = -1; r.link = 0; r.next = -1; r.depthc = 0;
@@ -123,7 +137,7 @@ __global__ __launch_bounds__(64) void brue_kernel(BrueArgs p)
             const uint32_t x = gen.below(1u << 30);                // state.seed(self.np_random.randint(2**30)), :25
             Pcg64U eg;
             eg.s_hi = eg.s_lo = eg.inc_hi = eg.inc_lo = 0; eg.has_uint32 = eg.uinteger = 0;
-            if (p.mode != MP_MODE_DETERMINISTIC) {                 // Generator(PCG64(SeedSequence(x))) of the clone
+            if (!LDS_MODEL && p.mode != MP_MODE_DETERMINISTIC) {   // Generator(PCG64(SeedSequence(x))) of the clone
                 uint64_t rec6[6];
                 seed_sequence_record(&x, 1, rec6);
                 eg.s_hi = Pcg64U::uni(rec6[0]); eg.s_lo = Pcg64U::uni(rec6[1]);
@@ -137,8 +151,8 @@ __global__ __launch_bounds__(64) void brue_kernel(BrueArgs p)
                 int sn;
                 double r;
                 bool done;
-                if (p.mode == MP_MODE_DETERMINISTIC) {
-                    const Rec rc = p.rec[sa];
+                if (LDS_MODEL || p.mode == MP_MODE_DETERMINISTIC) {
+                    const Rec rc = LDS_MODEL ? lrec[(s - base) * A + a] : p.rec[sa];
                     sn = rc.next; r = rc.reward;
                     done = (rc.flags & (p.done_on_next ? 2u : 1u)) != 0;
                 } else {
@@ -310,9 +324,14 @@ using namespace mp;
 
 extern "C" {
 
-int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t budget, int32_t horizon,
-                 double gamma, const double *gpow, uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *env_steps,
-                 int32_t *status, int32_t mem)
+extern "C++" {
+namespace {
+// mp_brue_plan (each = false: `root_state` holds states of the one model) and mp_brue_plan_models (each = true: a batch model
+// of deterministic tables; it holds the GLOBAL states globalize_roots_arg made of the (model_index, local state) pairs and the
+// form is each_form's)
+int brue_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t budget, int32_t horizon,
+                   double gamma, const double *gpow, uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *env_steps,
+                   int32_t *status, int32_t mem, bool each)
 {
     if (!ctx || !model || !root_state || !rng_state || !gpow) return fail(MP_ERR_ARG, "mp_brue_plan: NULL argument");
     if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_brue_plan: unknown mem flags %d", mem);
@@ -320,7 +339,7 @@ int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     mem = mem_arrays(mem);
     if (model->mode != MP_MODE_DETERMINISTIC && model->mode != MP_MODE_STOCHASTIC && model->mode != MP_MODE_SPARSE)
         return fail(MP_ERR_MODE, "mp_brue_plan: model mode %d is not a finite MDP", model->mode);
-    if (model->M != 1 || model->NB != 1 || (model->mode == MP_MODE_STOCHASTIC && model->Sc != model->S))
+    if (model->M != 1 || (!each && model->NB != 1) || (model->mode == MP_MODE_STOCHASTIC && model->Sc != model->S))
         return fail(MP_ERR_MODE, "mp_brue_plan: one whole model expected (no joint, batch or row-block model)");
     const int A = model->A;
     // (a rollout of no step never spends the budget: the reference loops for ever with horizon 0)
@@ -341,8 +360,11 @@ int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(upload_tables(ctx, 41, tab, &d_tab));
 
     BrueArgs a;
-    const long waves = (long)ctx->prop.multiProcessorCount * 32;
-    a.grid = (int)(n_roots < waves ? n_roots : waves);
+    a.Sb = model->Sb > 0 ? model->Sb : model->S;
+    // (the global form is the launch mp_brue_plan always made: CUs * 32 wavefronts at most, rew[] and po[] in LDS)
+    const int cus = ctx->prop.multiProcessorCount;
+    const EachForm form = each ? each_form(EACH_BRUE, a.Sb, A, horizon, n_roots, cus) : each_form_global(EACH_BRUE, horizon, n_roots, cus);
+    a.grid = form.grid;
     const size_t per_tree = (size_t)cap * (sizeof(BrueNode) + (size_t)A * sizeof(int32_t));
     a.keep = (size_t)n_roots * per_tree <= kBrueKeepBytes;
     const size_t slots = a.keep ? (size_t)n_roots : (size_t)a.grid + 1;
@@ -364,9 +386,12 @@ int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
     MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, mem, &a.env_steps));
 
-    form_record(ctx->last_variant, brue_form_name(a.keep));
+    void (*const kfn)(BrueArgs) = form.lds ? brue_kernel<true> : brue_kernel<false>;
+    if (form.lds_bytes() > 64 * 1024)
+        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)form.lds_bytes()));
+    form_record(ctx->last_variant, each ? each_form_name(EACH_BRUE, form.lds, a.keep) : brue_form_name(a.keep));
     MP_TRY(kernels_begin(ctx));
-    hipLaunchKernelGGL(brue_kernel, dim3((unsigned)a.grid), dim3(64), (size_t)horizon * (sizeof(double) + sizeof(int2)), st, a);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)a.grid), dim3(64), form.lds_bytes(), st, a);
     MP_TRY(kernels_end(ctx, 1));
     MP_HIP(hipGetLastError());
 
@@ -377,6 +402,28 @@ int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n_roots, mem));
     if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
     return MP_OK;
+}
+} // namespace
+} // extern "C++"
+
+int mp_brue_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t budget, int32_t horizon,
+                 double gamma, const double *gpow, uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *env_steps,
+                 int32_t *status, int32_t mem)
+{
+    return brue_plan_impl(ctx, model, n_roots, root_state, budget, horizon, gamma, gpow, rng_state, plans, root_value, env_steps,
+                          status, mem, false);
+}
+
+int mp_brue_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                        int32_t budget, int32_t horizon, double gamma, const double *gpow, uint64_t *rng_state, int32_t *plans,
+                        double *root_value, int64_t *env_steps, int32_t *status, int32_t mem)
+{
+    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_brue_plan_models: unknown mem flags %d", mem);
+    std::vector<int32_t> tmp;
+    const int32_t *global = nullptr;
+    MP_TRY(globalize_roots_arg(ctx, model, n_roots, model_index, root_state, mem, tmp, &global));
+    return brue_plan_impl(ctx, model, n_roots, global, budget, horizon, gamma, gpow, rng_state, plans, root_value, env_steps,
+                          status, mem, true);
 }
 
 int mp_brue_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *key,

@@ -1,0 +1,71 @@
+// each_host.hpp -- OLOP and BRUE on a batch model with one MDP per root (mp_olop_plan_models / mp_brue_plan_models): the ONE
+// host function that picks the kernel form, its grid and its LDS bytes.  The launch code (olop.hip, brue.hip) and
+// mp_each_form_info (api.hip, no device) call the same function, as opd_shape / mp_uct_choose_form do for their planners.
+//
+// A root of such a call only ever reads ITS MDP's S_each * |A| records.  The "lds" form copies them into the workgroup's LDS
+// behind the arrays the kernel already keeps there and serves every model read of the root from LDS; the "global" form is the
+// kernel of mp_olop_plan / mp_brue_plan on the batch model's global states.
+//   MP_EACH_MODEL=lds|global   forces a form where it fits ("lds" is ignored for a table that does not fit LDS)
+#pragma once
+#include <stdlib.h>
+#include <string.h>
+
+#include "common.hpp"
+
+namespace mp {
+
+enum { EACH_OLOP = 0, EACH_BRUE = 1 };
+
+// Where the LDS form is the DEFAULT: only where it was measured to beat the global form by more than the spread between
+// repeated medians (tools/micro_each.py -> profiles/each_model_ab.json; the highway shape, 120 states x
+// 5 actions = 9.6 KB a table, 1 to 65 536 roots):
+//   * a workgroup of at most kLdsBytes / 16 bytes, the footprint measured: 16 wavefronts stay resident on a CU.  A larger table
+//     leaves fewer, and its copy costs more than the few hundred records a plan reads of it: not measured, not the default;
+//   * OLOP at every batch size (0.3 - 6.6 % faster); BRUE (0.7 - 3.3 %) only while every root's workgroup is resident at once --
+//     at 65 536 roots, where the LDS form halves the resident wavefronts, the difference was inside the spread.
+// MP_EACH_MODEL=lds takes the LDS form for any table that fits the CU's LDS.
+constexpr size_t kEachLdsDefaultBytes = kLdsBytes / 16;
+
+struct EachForm {
+    size_t arrays;   // bytes of the kernel's own LDS arrays (OLOP: path[L + 1] int32, BRUE: rew[H] f64 + po[H] int2), 16-byte rounded
+    size_t lds_need; // arrays + S_each * |A| * 16: what a workgroup of the LDS form takes
+    bool lds;        // the form of this call
+    int grid;        // workgroups launched (one wavefront each): what is resident, at most n_roots
+    size_t lds_bytes() const { return lds ? lds_need : arrays; } // dynamic LDS of the launch
+};
+
+inline size_t each_kernel_arrays(int planner, int horizon)
+{
+    const size_t raw = planner == EACH_OLOP ? (size_t)(horizon + 1) * sizeof(int32_t) : (size_t)horizon * (sizeof(double) + 2 * sizeof(int32_t));
+    return (raw + 15) & ~(size_t)15;
+}
+
+inline EachForm each_form(int planner, int S_each, int A, int horizon, int n_roots, int cus)
+{
+    EachForm f;
+    f.arrays = each_kernel_arrays(planner, horizon);
+    f.lds_need = f.arrays + (size_t)S_each * A * sizeof(Rec);
+    const bool fits = f.lds_need <= kLdsBytes;
+    const long lds_per_cu = fits ? (long)(kLdsBytes / f.lds_need < 32 ? kLdsBytes / f.lds_need : 32) : 0;
+    f.lds = fits && f.lds_need <= kEachLdsDefaultBytes && (planner == EACH_OLOP || (long)n_roots <= (long)cus * lds_per_cu);
+    if (const char *force = getenv("MP_EACH_MODEL")) {
+        if (!strcmp(force, "lds")) f.lds = fits;
+        else if (!strcmp(force, "global")) f.lds = false;
+    }
+    const long resident = (long)cus * (f.lds ? lds_per_cu : 32);
+    f.grid = (int)(n_roots < resident ? n_roots : resident);
+    return f;
+}
+
+// the global form whatever the table and the knob: the launch of mp_olop_plan / mp_brue_plan themselves
+inline EachForm each_form_global(int planner, int horizon, int n_roots, int cus)
+{
+    EachForm f;
+    f.arrays = f.lds_need = each_kernel_arrays(planner, horizon);
+    f.lds = false;
+    const long resident = (long)cus * 32;
+    f.grid = (int)(n_roots < resident ? n_roots : resident);
+    return f;
+}
+
+} // namespace mp

@@ -86,6 +86,24 @@ inline FormName ss_form_name(bool use_lds)
     return n;
 }
 
+// OLOP and BRUE on a batch model with one MDP per root (mp_olop_plan_models / mp_brue_plan_models, each_host.hpp): the root's
+// table in LDS or read from global memory, with the `_slots` suffix of slots_form_name.  planner: 0 = OLOP, 1 = BRUE.  Listed by
+// mp_each_form_names -- NOT by all_form_names below, as for Sparse Sampling.
+inline FormName each_form_name(int planner, bool lds, bool keep)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "%s_each_%s%s", planner == 0 ? "olop" : "brue", lds ? "lds" : "global", keep ? "" : "_slots");
+    return n;
+}
+inline std::string each_form_names()
+{
+    std::string out;
+    for (int planner = 0; planner < 2; ++planner)
+        for (int lds = 1; lds >= 0; --lds)
+            for (int keep = 1; keep >= 0; --keep) { out += each_form_name(planner, lds != 0, keep != 0).s; out += '\n'; }
+    return out;
+}
+
 // ---- single-model value iteration (vi.hip: mp_vi_solve, mp_vi_solve_v, mp_vi_solve_v_robust, mp_vi_sweeps, mp_vi_backup):
 // the form of the launch that produced the returned values.  Reported by mp_last_kernel_variant after a call and listed by
 // mp_vi_form_names -- NOT by all_form_names below, as for Sparse Sampling.
@@ -234,7 +252,7 @@ inline FormName uct_stoch_form_name(int wbk, bool p16, int at, bool pol)
 }
 
 // every name an entry point can record, one per line (Sparse Sampling's two are listed by mp_ss_form_names, single-model
-// value iteration's by mp_vi_form_names)
+// value iteration's by mp_vi_form_names, the one-MDP-per-root forms of OLOP and BRUE by mp_each_form_names)
 inline std::string all_form_names()
 {
     std::string out;

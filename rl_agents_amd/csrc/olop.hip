@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "each_host.hpp"
 #include "pcg64.hpp"
 
 namespace mp {
@@ -47,6 +48,7 @@ struct OlopArgs {
     int32_t *plans, *plan_len, *status;
     double *root_value;
     int64_t *env_steps;
+    int Sb;              // LDS_MODEL: states per MDP of the batch model (a root's MDP starts at global state (s / Sb) * Sb)
 };
 
 // utils.py:89-109 bernoulli_kullback_leibler
@@ -136,19 +138,37 @@ __device__ double olop_amax(const double *V, int k, int lane)
     return olop_ballot(nan_seen) ? (double)NAN : m;
 }
 
+// LDS_MODEL (mp_olop_plan_models, one MDP per root): the root's own Sb * |A| records sit in LDS behind path[], copied before
+// its first episode, and every model read -- the expansion's gather, the step -- is served from there.  The `false`
+// instantiation is the kernel of mp_olop_plan as it was: everything the LDS form adds sits under `if constexpr`, and the two
+// compile to the same instructions (profiles/each_kernel_resources.txt).
+template <bool LDS_MODEL>
 __global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
 {
     extern __shared__ int32_t path[]; // [L + 1] node ids of the episode's walk
     const int lane = threadIdx.x, A = p.A, L = p.L;
+    Rec *lrec = nullptr;              // [Sb * A] LDS_MODEL: the root's table, 16-byte aligned behind path[]
+    if constexpr (LDS_MODEL)
+        lrec = static_cast<Rec *>(__builtin_assume_aligned(path + ((L + 1 + 3) & ~3), 16));
     const uint32_t done_bit = p.done_on_next ? 2u : 1u;
     const double mu0 = p.kl ? 1.0 : (double)INFINITY; // olop.py:105-108
     for (int root = blockIdx.x; root < p.n_roots; root += p.grid) {
         const long slot = p.keep ? root : (root == 0 ? p.grid : blockIdx.x);
         OlopNode *N = p.nodes + slot * p.cap;
         double *V = p.vu + slot * p.cap;
+        // LDS_MODEL: the root's table into LDS (the previous root's reads ended at the barrier that closes its iteration; this
+        // root's begin after the one below)
+        int s_root = 0, base = 0;
+        if constexpr (LDS_MODEL) {
+            s_root = p.root_state[root];
+            base = s_root / p.Sb * p.Sb;
+            const uint4 *src = reinterpret_cast<const uint4 *>(p.rec + (long)base * A);
+            uint4 *dst = reinterpret_cast<uint4 *>(lrec);
+            for (int i = lane; i < p.Sb * A; i += 64) dst[i] = src[i];
+        }
         if (lane == 0) {
             OlopNode r;
-            r.cum = 0.0; r.mu = mu0; r.count = 0; r.state = p.root_state[root]; r.parent = -1; r.first_child = -1;
+            r.cum = 0.0; r.mu = mu0; r.count = 0; r.state = LDS_MODEL ? s_root : p.root_state[root]; r.parent = -1; r.first_child = -1;
             r.n_children = 0; r.action = -1; r.depth = 0; r.done = 0;
             N[0] = r;
             V[0] = p.vinit[0];
@@ -167,8 +187,8 @@ __global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
                 int fc = nd.first_child, k = nd.n_children, j, act;
                 if (k == 0) {
                     // OLOPNode.expand (olop.py:165-180): the available actions in listing order
-                    const Rec *row = p.rec + (long)nd.state * A;
-                    int rank0 = -1, base = 0;
+                    const Rec *row = LDS_MODEL ? lrec + (nd.state - base) * A : p.rec + (long)nd.state * A;
+                    int rank0 = -1, pos0 = 0;
                     fc = n_nodes;
                     for (int a0 = 0; a0 < A; a0 += 64) {
                         const int a = a0 + lane;
@@ -176,7 +196,7 @@ __global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
                         bool av = false;
                         if (a < A) { rc = row[a]; av = (rc.flags & 4u) != 0; }
                         const unsigned long long bal = olop_ballot(av);
-                        const int pos = base + __popcll(bal & ((1ull << lane) - 1ull));
+                        const int pos = pos0 + __popcll(bal & ((1ull << lane) - 1ull));
                         if (av) {
                             OlopNode c;
                             c.cum = 0.0; c.mu = mu0; c.count = 0; c.state = rc.next; c.parent = node; c.first_child = -1;
@@ -185,10 +205,10 @@ __global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
                             V[fc + pos] = p.vinit[nd.depth + 1];
                         }
                         if (p.cont >= a0 && p.cont < a0 + 64 && ((bal >> (p.cont - a0)) & 1ull))
-                            rank0 = base + __popcll(bal & ((1ull << (p.cont - a0)) - 1ull));
-                        base += __popcll(bal);
+                            rank0 = pos0 + __popcll(bal & ((1ull << (p.cont - a0)) - 1ull));
+                        pos0 += __popcll(bal);
                     }
-                    k = base;
+                    k = pos0;
                     if (lane == 0) { N[node].first_child = fc; N[node].n_children = k; }
                     n_nodes += k;
                     __syncthreads();
@@ -204,7 +224,7 @@ __global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
                     act = N[fc + j].action;
                 }
                 // the model step (every step is taken: the reference does not stop at done)
-                const Rec rc = p.rec[(long)nd.state * A + act];
+                const Rec rc = LDS_MODEL ? lrec[(nd.state - base) * A + act] : p.rec[(long)nd.state * A + act];
                 ++steps;
                 if (j < 0) { status = MP_ERR_OLOP_KEY; break; }
                 const double r = rc.reward;
@@ -277,10 +297,14 @@ using namespace mp;
 
 extern "C" {
 
-int mp_olop_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
-                 double gamma, int32_t bound_type, int32_t continuation, const double *thresholds,
-                 const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len,
-                 double *root_value, int64_t *env_steps, int32_t *status, int32_t mem)
+extern "C++" {
+namespace {
+// mp_olop_plan (each = false: `root_state` holds states of the model) and mp_olop_plan_models (each = true: it holds the GLOBAL
+// states globalize_roots_arg made of the (model_index, local state) pairs; the form is each_form's)
+int olop_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
+                   double gamma, int32_t bound_type, int32_t continuation, const double *thresholds,
+                   const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len,
+                   double *root_value, int64_t *env_steps, int32_t *status, int32_t mem, bool each)
 {
     if (!ctx || !model || !root_state || !rng_state || !value_upper_init) return fail(MP_ERR_ARG, "mp_olop_plan: NULL argument");
     if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_olop_plan: unknown mem flags %d", mem);
@@ -309,8 +333,11 @@ int mp_olop_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(upload_tables(ctx, 40, tab, &d_tab));
 
     OlopArgs a;
-    const long waves = (long)ctx->prop.multiProcessorCount * 32;
-    a.grid = (int)(n_roots < waves ? n_roots : waves);
+    a.Sb = model->Sb > 0 ? model->Sb : model->S;
+    // (the global form is the launch mp_olop_plan always made: CUs * 32 wavefronts at most, path[] in LDS)
+    const int cus = ctx->prop.multiProcessorCount;
+    const EachForm form = each ? each_form(EACH_OLOP, a.Sb, A, horizon, n_roots, cus) : each_form_global(EACH_OLOP, horizon, n_roots, cus);
+    a.grid = form.grid;
     const size_t per_tree = (size_t)cap * (sizeof(OlopNode) + sizeof(double));
     a.keep = (size_t)n_roots * per_tree <= kOlopKeepBytes;
     const size_t slots = a.keep ? (size_t)n_roots : (size_t)a.grid + 1;
@@ -334,9 +361,12 @@ int mp_olop_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
     MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, mem, &a.env_steps));
 
-    form_record(ctx->last_variant, olop_form_name(a.keep));
+    void (*const kfn)(OlopArgs) = form.lds ? olop_kernel<true> : olop_kernel<false>;
+    if (form.lds_bytes() > 64 * 1024)
+        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)form.lds_bytes()));
+    form_record(ctx->last_variant, each ? each_form_name(EACH_OLOP, form.lds, a.keep) : olop_form_name(a.keep));
     MP_TRY(kernels_begin(ctx));
-    hipLaunchKernelGGL(olop_kernel, dim3((unsigned)a.grid), dim3(64), (size_t)(horizon + 1) * sizeof(int32_t), st, a);
+    hipLaunchKernelGGL(kfn, dim3((unsigned)a.grid), dim3(64), form.lds_bytes(), st, a);
     MP_TRY(kernels_end(ctx, 1));
     MP_HIP(hipGetLastError());
 
@@ -348,6 +378,30 @@ int mp_olop_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n_roots, mem));
     if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
     return MP_OK;
+}
+} // namespace
+} // extern "C++"
+
+int mp_olop_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
+                 double gamma, int32_t bound_type, int32_t continuation, const double *thresholds,
+                 const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len,
+                 double *root_value, int64_t *env_steps, int32_t *status, int32_t mem)
+{
+    return olop_plan_impl(ctx, model, n_roots, root_state, episodes, horizon, gamma, bound_type, continuation, thresholds,
+                          value_upper_init, rng_state, max_plan_len, plans, plan_len, root_value, env_steps, status, mem, false);
+}
+
+int mp_olop_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                        int32_t episodes, int32_t horizon, double gamma, int32_t bound_type, int32_t continuation,
+                        const double *thresholds, const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len,
+                        int32_t *plans, int32_t *plan_len, double *root_value, int64_t *env_steps, int32_t *status, int32_t mem)
+{
+    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_olop_plan_models: unknown mem flags %d", mem);
+    std::vector<int32_t> tmp;
+    const int32_t *global = nullptr;
+    MP_TRY(globalize_roots_arg(ctx, model, n_roots, model_index, root_state, mem, tmp, &global));
+    return olop_plan_impl(ctx, model, n_roots, global, episodes, horizon, gamma, bound_type, continuation, thresholds,
+                          value_upper_init, rng_state, max_plan_len, plans, plan_len, root_value, env_steps, status, mem, true);
 }
 
 int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *action,

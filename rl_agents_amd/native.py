@@ -117,6 +117,11 @@ SIGNATURES = {
     "mp_olop_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_brue_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_brue_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_olop_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp,
+                                      _vp, _vp, _vp, c_i32]),
+    "mp_brue_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_each_form_info": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _vp]),
+    "mp_each_form_names": (C.c_char_p, []),
     "mp_ss_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_ss_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_ss_geometry": (C.c_int, [c_i32, c_i32, c_i32, c_i32, _vp]),
@@ -298,6 +303,27 @@ def uct_choose_form(call):
 def kernel_form_names():
     """Every name Context.last_kernel_variant() can return (mp_kernel_form_names; host only), in the library's order."""
     return load().mp_kernel_form_names().decode().split()
+
+
+def each_form_names():
+    """The names OLOP and BRUE plans on one MDP per root (``olop_plan`` / ``brue_plan`` with ``model_index``) record for
+    Context.last_kernel_variant() (mp_each_form_names; host only).  They are not part of kernel_form_names()."""
+    return load().mp_each_form_names().decode().split()
+
+
+EACH_PLANNERS = {"olop": 0, "brue": 1}
+
+
+def each_form_info(planner, s_each, n_actions, horizon, n_roots, cus=256):
+    """The form ``olop_plan`` / ``brue_plan`` with ``model_index`` take for a call of this description (mp_each_form_info; host
+    only, MP_EACH_MODEL is read): dict(lds_bytes = what a workgroup of the LDS form takes, lds = the call takes it, grid,
+    launch_lds_bytes, default_limit = the most bytes that take the LDS form by default, fit_limit = the most that fit a compute
+    unit's LDS and can be forced).  ``planner``: "olop" or "brue"."""
+    out = np.zeros(6, np.int64)
+    _check(load().mp_each_form_info(EACH_PLANNERS[planner], int(s_each), int(n_actions), int(horizon), int(n_roots), int(cus),
+                                    _ptr(out)))
+    return dict(lds_bytes=int(out[0]), lds=bool(out[1]), grid=int(out[2]), launch_lds_bytes=int(out[3]), default_limit=int(out[4]),
+                fit_limit=int(out[5]))
 
 
 def ss_form_names():
@@ -1109,10 +1135,11 @@ class Context(object):
         return {k: v[:n.value].copy() for k, v in t.items()}
 
     def olop_plan(self, model, root_state, episodes, horizon, gamma, kl, continuation, thresholds, value_upper_init, rng_state,
-                  max_plan_len=None):
+                  max_plan_len=None, model_index=None):
         """OLOP.plan for a batch of roots (host arrays): mp_olop_plan.  ``kl``: the kullback-leibler bound (else mu_ucb stays
         inf); ``continuation``: < 0 = uniform, else the action label taken after an expansion; ``thresholds`` float64
-        [episodes], ``value_upper_init`` float64 [horizon + 1] from the host."""
+        [episodes], ``value_upper_init`` float64 [horizon + 1] from the host.  ``model_index`` int [n]: a batch model with one
+        MDP per root, ``root_state`` local (mp_olop_plan_models)."""
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
         n = rs.shape[0]
         if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
@@ -1125,6 +1152,13 @@ class Context(object):
             raise ValueError("olop_plan: thresholds [episodes] and value_upper_init [horizon + 1] expected")
         out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32), root_value=np.zeros(n, np.float64),
                    env_steps=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
+        if model_index is not None:
+            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
+            _check(self._lib.mp_olop_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(episodes), int(horizon), float(gamma),
+                                                 1 if kl else 0, int(continuation), _ptr(thr) if thr.size else None, _ptr(vin),
+                                                 _ptr(rng_state), mpl, _ptr(out["plans"]), _ptr(out["plan_len"]),
+                                                 _ptr(out["root_value"]), _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
+            return out
         _check(self._lib.mp_olop_plan(self._h, model._h, n, _ptr(rs), int(episodes), int(horizon), float(gamma), 1 if kl else 0,
                                       int(continuation), _ptr(thr) if thr.size else None, _ptr(vin), _ptr(rng_state), mpl,
                                       _ptr(out["plans"]), _ptr(out["plan_len"]), _ptr(out["root_value"]), _ptr(out["env_steps"]),
@@ -1142,9 +1176,10 @@ class Context(object):
                                              _ptr(t["done"]), _ptr(t["state"])))
         return {k: v[:n.value].copy() for k, v in t.items()}
 
-    def brue_plan(self, model, root_state, budget, horizon, gamma, gpow, rng_state):
+    def brue_plan(self, model, root_state, budget, horizon, gamma, gpow, rng_state, model_index=None):
         """BRUE.plan for a batch of roots (host arrays): mp_brue_plan.  ``gpow`` float64 [horizon + 1]: gamma ** d from the
-        host.  ``plans`` [n]: the one planned action per root (-1 where no rollout was made)."""
+        host.  ``plans`` [n]: the one planned action per root (-1 where no rollout was made).  ``model_index`` int [n]: a batch
+        model with one MDP per root, ``root_state`` local (mp_brue_plan_models)."""
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
         n = rs.shape[0]
         if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
@@ -1155,6 +1190,12 @@ class Context(object):
             raise ValueError("brue_plan: gpow [horizon + 1] expected")
         out = dict(plans=np.full(n, -1, np.int32), root_value=np.zeros(n, np.float64), env_steps=np.zeros(n, np.int64),
                    status=np.zeros(n, np.int32))
+        if model_index is not None:
+            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
+            _check(self._lib.mp_brue_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(budget), int(horizon), float(gamma),
+                                                 _ptr(gp), _ptr(rng_state), _ptr(out["plans"]), _ptr(out["root_value"]),
+                                                 _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
+            return out
         _check(self._lib.mp_brue_plan(self._h, model._h, n, _ptr(rs), int(budget), int(horizon), float(gamma), _ptr(gp),
                                       _ptr(rng_state), _ptr(out["plans"]), _ptr(out["root_value"]), _ptr(out["env_steps"]),
                                       _ptr(out["status"]), MP_MEM_HOST))

@@ -12,7 +12,8 @@ Here N environments advance in lock-step and share ONE launch per step:
                                        batch model <- the tables that changed        (mp_model_update_tables: the delta of
                                                                                       a batch is each episode's own table)
                                        ONE batched plan, one MDP per root            (mp_vi_solve_batch + argmax /
-                                                                                      mp_uct_plan_models / mp_opd_plan_models)
+                                                                                      mp_uct_plan_models / mp_opd_plan_models /
+                                                                                      mp_olop_plan_models / mp_brue_plan_models)
                                        env_i.step(action_i)                          (host: the environments are host objects)
 
 Episode i draws from the generator a sequential ``Evaluation`` would give agent i (``np_random(sim_seed + i)``,
@@ -24,7 +25,9 @@ Supported agents of this package: ``ValueIterationAgent``, ``MCTSAgent`` (open l
 for EVERY episode's table at every step, as mcts_with_prior.py:47-54 does through ``prior_agent.act``: ``mp_vi_solve_batch``,
 the Boltzmann rows with numpy on the host -- the reference's distribution is numpy's ``exp``, whose SIMD implementation no
 device restatement can be checked against -- and ``mp_policy_load`` over the batch model's global states),
-``DeterministicPlannerAgent``; environments: deterministic finite MDPs of one (S, A) shape, with or without restricted /
+``DeterministicPlannerAgent``, ``OLOPAgent`` (OLOP / KL-OLOP: the planner's own thresholds and initial bounds, its
+continuation and its exceptions, as ``OLOP.plan_batch``) and ``BRUEAgent`` (which draws over ALL actions, brue.py:27: its
+batch model carries neither the availability table nor the listing order, as ``BRUE.model_for`` loads it); environments: deterministic finite MDPs of one (S, A) shape, with or without restricted /
 re-ordered action sets (``get_available_actions``: the restriction must be the same table for every episode, as it is for
 grids of one shape -- device_model.availability_of).
 """
@@ -75,7 +78,11 @@ class PerEpisodeEvaluation(object):
         if getattr(planner, "per_episode_entry_point", True) is None:
             raise NotImplementedError("per-episode tables: {} has no entry point that plans a batch on one model per episode, "
                                       "and this loop would run the optimistic planner in its place".format(type(planner).__name__))
-        self.kind = "vi" if self.vi else ("uct" if hasattr(planner, "prior_policy") else "opd")
+        from rl_agents_amd.agents.tree_search.brue import BRUE
+        from rl_agents_amd.agents.tree_search.olop import OLOP
+        # (BRUE first: it subclasses OLOP; both before the fallback, which runs the optimistic deterministic planner)
+        self.kind = "vi" if self.vi else "brue" if isinstance(planner, BRUE) else "olop" if isinstance(planner, OLOP) else \
+            ("uct" if hasattr(planner, "prior_policy") else "opd")
         if not self.vi:
             cfg = planner.config
             if cfg.get("step_strategy", "reset") != "reset":
@@ -107,7 +114,8 @@ class PerEpisodeEvaluation(object):
         version = getattr(mdp, "tables_version", None)
         if version is not None and (not isinstance(version, tuple) or version[0] is None):
             version = None
-        available, order = (None, None) if self.vi else device_model.availability_of(env, mdp)   # (cross-checks the env's listing)
+        # (availability_of cross-checks the env's listing; BRUE never asks the environment: brue.py:27 draws over action_space.n)
+        available, order = (None, None) if self.vi or self.kind == "brue" else device_model.availability_of(env, mdp)
         if self.model is not None and version is not None and self._versions[i] == version:
             return None, state, steps
         if self.kind == "uct":
@@ -141,7 +149,7 @@ class PerEpisodeEvaluation(object):
                                                    done_rule=first_spec.done_rule, max_steps=first_spec.max_steps)
             self.model.action_order = first_spec.action_order
             self._available = None if first_spec.available is None else first_spec.available.astype(bool)
-            if self._available is not None and self.kind == "opd":
+            if self._available is not None and self.kind in ("opd", "olop"):
                 # (MCTS reads availability through its policies, mcts.py:59-97: see _uct_policy)
                 self.model.set_available(np.tile(self._available, (n, 1)))
             self.uploads += len(live)
@@ -260,6 +268,30 @@ class PerEpisodeEvaluation(object):
                 pp, rp = policy_probabilities(planner.prior_policy, model.A), policy_probabilities(planner.rollout_policy, model.A)
                 out = self.ctx.uct_plan(model, states[idx], cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], pp, rp,
                                         rng, root_steps=steps[idx], max_plan_len=1, model_index=idx)
+        elif self.kind == "olop":
+            episodes, horizon = int(cfg["episodes"]), int(cfg["horizon"])    # KeyError without "episodes" (olop.py:95)
+            kl = cfg["upper_bound"]["type"] == "kullback-leibler"
+            thresholds = planner.thresholds() if kl else np.zeros(0, np.float64)
+            # "uniform": a random new child; anything else: action 0 of the environment, in the device's labels
+            continuation = -1 if cfg["continuation_type"] == "uniform" else int(planner.device_actions([0], model)[0])
+            out = self.ctx.olop_plan(model, states[idx], episodes, horizon, cfg["gamma"], kl, continuation, thresholds,
+                                     planner._value_upper_init, rng, max_plan_len=1, model_index=idx)
+            self.rng[idx] = rng                         # (the draws made before a failing step are made: OLOP.plan_batch)
+            failed = np.flatnonzero(out["status"] != native.MP_OK)
+            if failed.size:
+                if out["status"][failed[0]] == native.ERR_OLOP_KEY:
+                    raise KeyError(0)                                                           # olop.py:89
+                raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # olop.py:133-134
+        elif self.kind == "brue":
+            horizon = int(cfg["horizon"])
+            out = self.ctx.brue_plan(model, states[idx], int(cfg["budget"]), horizon, cfg["gamma"],
+                                     planner.gamma_powers(cfg["gamma"], horizon), rng, model_index=idx)
+            self.rng[idx] = rng
+            if (out["plans"] < 0).any():
+                # no rollout was made (budget <= 0): the reference's np.amax([]) of the root's selection raises (brue.py:75)
+                raise ValueError("zero-size array to reduction operation maximum which has no identity")
+            out["plans"] = out["plans"].reshape(len(idx), 1)
+            out["plan_len"] = np.ones(len(idx), np.int32)
         else:
             budget = int(cfg["budget"])
             if cfg["gamma"] == 1 and budget >= model.A:
