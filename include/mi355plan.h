@@ -555,6 +555,20 @@ int mp_olop_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int
                         const double *thresholds, const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len,
                         int32_t *plans, int32_t *plan_len, double *root_value, int64_t *env_steps, int32_t *status, int32_t mem);
 
+/* Test hook: what the DEVICE computes for the three functions behind mu_ucb, the only planner outputs that are held to a
+ * tolerance (1e-12) and not to bits.  Host arrays of n elements in and out, one input per lane of 64-lane workgroups (the lanes
+ * of a wave run different iteration counts, as the path nodes of an episode do); the kernel calls the very __device__ functions
+ * olop_kernel calls.
+ *   what 0: out[i] = kl_upper_bound(x[i] = cumulative reward, count[i], y[i] = threshold) (utils.py:123-203), with
+ *     iterations[i] = the Newton iterations run and decisions[i] = the branches taken, as a bit mask: 1 = the in-loop upper
+ *     clamp (utils.py:195), 2 = the in-loop lower clamp (:193), 4 = the finite difference that replaces the derivative after a
+ *     ZeroDivisionError (:188), 8 / 16 = the final lower / upper clamp (:198-201);
+ *   what 1: out[i] = bernoulli_kullback_leibler(p = x[i], q = y[i]) (utils.py:89-107);
+ *   what 2: out[i] = log(x[i]), the device's.
+ * count, iterations and decisions are read and written with what 0 only; y with what 0 and 1. */
+int mp_selftest_olop_bound(mp_ctx *ctx, int32_t what, int32_t n, const double *x, const double *y, const int32_t *count,
+                           double *out, int32_t *iterations, int32_t *decisions);
+
 /* ---------------------------------------------------------------- BRUE ---------------------- */
 /*
  * BRUE.plan (tree_search/brue.py:66-71) for n_roots independent roots of a deterministic table, dense or sparse model: while

@@ -63,8 +63,15 @@ __device__ __forceinline__ double bernoulli_kl(double p, double q)
 // utils.py:123-146 kl_upper_bound with newton_iteration (:149-203): eps 1e-2, weight 0.9, 100 iterations, the in-loop clamps,
 // the final clamp.  `py` follows whether the iterate is still a Python float: only then does the derivative raise
 // ZeroDivisionError (and the finite difference of :183 replace it); numpy scalars give inf / nan instead.
-__device__ double kl_upper_bound(double total, int count, double threshold)
+// TRACE (mp_selftest_olop_bound only; the planner's instantiation is <false> and holds none of it): the number of iterations
+// and the decisions taken, KL_* below, so that a test can hold them against the reference's, point by point.
+enum { KL_CLAMP_UPPER = 1, KL_CLAMP_LOWER = 2, KL_FINITE_DIFFERENCE = 4, KL_FINAL_LOWER = 8, KL_FINAL_UPPER = 16 };
+
+template <bool TRACE>
+__device__ double kl_upper_bound(double total, int count, double threshold, int *iterations = nullptr, int *decisions = nullptr)
 {
+    int mask = 0, its = 0;
+    if constexpr (TRACE) { *iterations = 0; *decisions = 0; }
     if (count == 0) return 1.0;
     const double mu = total / (double)count, max_div = threshold / (double)count;
     const double a = mu, b = 1.0, eps = 1e-2, w = 0.9, wc = 1.0 - 0.9;
@@ -77,14 +84,29 @@ __device__ double kl_upper_bound(double total, int count, double threshold)
         const bool px = pyn;
         const double fx = bernoulli_kl(mu, x) - max_div;
         double dfx;
-        if (px && (1 - x == 0 || x == 0)) dfx = (fx - (bernoulli_kl(mu, x - eps) - max_div)) / eps;
-        else dfx = (1 - mu) / (1 - x) - mu / x;
+        if (px && (1 - x == 0 || x == 0)) {
+            dfx = (fx - (bernoulli_kl(mu, x - eps) - max_div)) / eps;
+            if constexpr (TRACE) mask |= KL_FINITE_DIFFERENCE;
+        } else dfx = (1 - mu) / (1 - x) - mu / x;
         if (dfx != 0) { xn = x - fx / dfx; pyn = false; }
-        if (xn < a) { xn = w * a + wc * x; pyn = px; }
-        else if (xn > b) { xn = w * b + wc * x; pyn = px; }
+        if (xn < a) {
+            xn = w * a + wc * x; pyn = px;
+            if constexpr (TRACE) mask |= KL_CLAMP_LOWER;
+        } else if (xn > b) {
+            xn = w * b + wc * x; pyn = px;
+            if constexpr (TRACE) mask |= KL_CLAMP_UPPER;
+        }
+        if constexpr (TRACE) ++its;
     }
-    if (xn < a) xn = a;
-    if (xn > b) xn = b;
+    if (xn < a) {
+        xn = a;
+        if constexpr (TRACE) mask |= KL_FINAL_LOWER;
+    }
+    if (xn > b) {
+        xn = b;
+        if constexpr (TRACE) mask |= KL_FINAL_UPPER;
+    }
+    if constexpr (TRACE) { *iterations = its; *decisions = mask; }
     return xn;
 }
 
@@ -247,7 +269,7 @@ __global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
                 const double thr = p.thr[e];
                 for (int i = 1 + lane; i <= L; i += 64) {
                     OlopNode *c = N + path[i];
-                    c->mu = kl_upper_bound(c->cum, c->count, thr);
+                    c->mu = kl_upper_bound<false>(c->cum, c->count, thr);
                 }
             }
             __syncthreads();
@@ -289,6 +311,24 @@ __global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
         }
         __syncthreads();
     }
+}
+
+// mp_selftest_olop_bound: what the device computes for the three functions above, one input per lane of 64-lane workgroups --
+// the lanes of a wave run different iteration counts, as the path nodes of an episode do in olop_kernel.
+__global__ __launch_bounds__(64) void olop_bound_selftest_kernel(int n, int what, const double *__restrict__ x,
+                                                                 const double *__restrict__ y, const int32_t *__restrict__ count,
+                                                                 double *__restrict__ out, int32_t *__restrict__ iterations,
+                                                                 int32_t *__restrict__ decisions)
+{
+    const long i = (long)blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    if (what == 0) {
+        int its, mask;
+        out[i] = kl_upper_bound<true>(x[i], count[i], y[i], &its, &mask);
+        iterations[i] = its;
+        decisions[i] = mask;
+    } else if (what == 1) out[i] = bernoulli_kl(x[i], y[i]);
+    else out[i] = log(x[i]);
 }
 
 } // namespace mp
@@ -440,6 +480,35 @@ int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
         if (state) state[i] = na[i].state;
     }
     if (n_nodes) *n_nodes = n;
+    return MP_OK;
+}
+
+int mp_selftest_olop_bound(mp_ctx *ctx, int32_t what, int32_t n, const double *x, const double *y, const int32_t *count,
+                           double *out, int32_t *iterations, int32_t *decisions)
+{
+    if (!ctx || n < 1 || what < 0 || what > 2 || !x || !out || (what < 2 && !y) || (what == 0 && (!count || !iterations || !decisions)))
+        return fail(MP_ERR_ARG, "mp_selftest_olop_bound: bad argument");
+    MP_HIP(hipSetDevice(ctx->device));
+    const size_t N = (size_t)n;
+    double *d = nullptr; // x, y, out [n] doubles, then count, iterations, decisions [n] int32
+    MP_HIP(hipMalloc(&d, N * 3 * sizeof(double) + N * 3 * sizeof(int32_t)));
+    int32_t *di = reinterpret_cast<int32_t *>(d + 3 * N);
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMemcpyAsync(d, x, N * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && what < 2) e = hipMemcpyAsync(d + N, y, N * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && what == 0) e = hipMemcpyAsync(di, count, N * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(mp::olop_bound_selftest_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, n, what, d, d + N, di,
+                           d + 2 * N, di + N, di + 2 * N);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + 2 * N, N * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && what == 0) e = hipMemcpyAsync(iterations, di + N, N * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && what == 0) e = hipMemcpyAsync(decisions, di + 2 * N, N * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(d);
+    MP_HIP(e);
+    MP_HIP(e2);
     return MP_OK;
 }
 

@@ -53,6 +53,7 @@ SIGNATURES = {
     "mp_libm_sincos_variant": (C.c_int, []),
     "mp_libm_sincos": (C.c_int, [c_i32, _vp, c_i32, _vp, _vp]),
     "mp_selftest_sincos": (C.c_int, [_vp, c_i32, _vp, c_i32, _vp, _vp]),
+    "mp_selftest_olop_bound": (C.c_int, [_vp, c_i32, c_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_model_load_dense": (C.c_int, [_vp, c_i32, c_i32, c_i32, _vp, _vp, _vp, c_i32, P(_vp)]),
     "mp_model_load_dense_rows": (C.c_int, [_vp, c_i32, c_i32, c_i32, c_i32, _vp, _vp, _vp, c_i32, P(_vp)]),
     "mp_vi_backup": (C.c_int, [_vp, _vp, c_f64, c_i32, _vp, _vp, c_i32]),
@@ -488,6 +489,31 @@ class Context(object):
         s, c = np.zeros_like(x), np.zeros_like(x)
         _check(self._lib.mp_selftest_sincos(self._h, int(x.size), _ptr(x), int(variant), _ptr(s), _ptr(c)))
         return s, c
+
+    def selftest_olop_bound(self, what, x, y=None, count=None):
+        """What the DEVICE's OLOP code computes, one input per lane (mp_selftest_olop_bound).  ``what``: "kl_upper_bound"
+        (x = cumulative rewards, count, y = thresholds) -> (bounds, Newton iterations, decision masks: 1 / 2 the in-loop upper /
+        lower clamp, 4 the finite difference, 8 / 16 the final lower / upper clamp); "bernoulli_kl" (p = x, q = y) -> values;
+        "log" -> values."""
+        code = {"kl_upper_bound": 0, "bernoulli_kl": 1, "log": 2}[what]
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        n = x.size
+        out = np.zeros(n, np.float64)
+        if code == 2:
+            _check(self._lib.mp_selftest_olop_bound(self._h, code, n, _ptr(x), None, None, _ptr(out), None, None))
+            return out
+        y = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if y.size != n:
+            raise ValueError("selftest_olop_bound: x and y differ in length")
+        if code == 1:
+            _check(self._lib.mp_selftest_olop_bound(self._h, code, n, _ptr(x), _ptr(y), None, _ptr(out), None, None))
+            return out
+        count = np.ascontiguousarray(count, dtype=np.int32).reshape(-1)
+        if count.size != n:
+            raise ValueError("selftest_olop_bound: x and count differ in length")
+        its, mask = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        _check(self._lib.mp_selftest_olop_bound(self._h, code, n, _ptr(x), _ptr(y), _ptr(count), _ptr(out), _ptr(its), _ptr(mask)))
+        return out, its, mask
 
     def selftest_lds_atomic_order(self, waves=65536):
         """Violations of "same-address LDS atomics of one wave instruction apply in lane order" (0 on a conforming device)."""

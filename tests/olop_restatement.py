@@ -3,7 +3,8 @@
 Reference: ``rl_agents/agents/tree_search/olop.py:64-193`` (run, OLOPNode.update / compute_reward_ucb / expand /
 backup_to_root, selection_rule) and ``rl_agents/utils.py:89-203`` (kl_upper_bound, newton_iteration), on a deterministic
 finite-MDP table.  Its job is to let GPU tests check random cases and sampled roots of big batches against something
-other than the kernel; it is itself pinned on the reference's own outputs (tests/golden/olop.npz, tests/test_olop_host.py).
+other than the kernel; it is itself pinned on the reference's own outputs (tests/golden/olop.npz, tests/test_olop_host.py;
+the bound alone on tests/golden/kl_bound.npz and plans with NaN bounds on tests/golden/olop_nan.npz, tests/test_olop_bound_host.py).
 
 The tree is kept as creation-order arrays, the layout of ``mp_olop_tree_export``.
 """
@@ -16,36 +17,44 @@ KL_WEIGHT = 0.9
 KL_MAX_ITERATIONS = 100
 
 
-def _bernoulli_kl(p, q):
+# decisions of one kl_upper_bound evaluation, the bit mask of mp_selftest_olop_bound
+KL_CLAMP_UPPER, KL_CLAMP_LOWER, KL_FINITE_DIFFERENCE, KL_FINAL_LOWER, KL_FINAL_UPPER = 1, 2, 4, 8, 16
+
+
+def _bernoulli_kl(p, q, log=np.log):
     """KL(B(p) || B(q)) with the case analysis of utils.py:89-109 (numpy's log on the host)."""
-    head = p * np.log(p / q) if (p > 0 and q > 0) else 0.0
+    head = p * log(p / q) if (p > 0 and q > 0) else 0.0
     if not q < 1:
         tail = math.inf
     else:
-        tail = (1 - p) * np.log((1 - p) / (1 - q)) if p < 1 else 0.0
+        tail = (1 - p) * log((1 - p) / (1 - q)) if p < 1 else 0.0
     return float(head + tail)
 
 
-def kl_upper_bound(total, count, threshold):
+def kl_upper_bound_traced(total, count, threshold, log=np.log):
     """utils.py:123-146 with newton_iteration (:149-203), eps 1e-2, weight 0.9, 100 iterations.  ``py_x`` tracks whether
-    the iterate is still a Python float (the first derivative then raises ZeroDivisionError instead of giving inf)."""
+    the iterate is still a Python float (the first derivative then raises ZeroDivisionError instead of giving inf).
+    Returns (bound, Newton iterations, mask of the decisions taken: KL_* above); ``log`` replaces numpy's, for tests that
+    move it by an ulp or record its arguments."""
     if count == 0:
-        return 1.0
+        return 1.0, 0, 0
     mu = total / count
     max_div = threshold / count
     a, b = mu, 1.0
     x0 = (a + b) / 2
     if a == b:
-        return a
+        return a, 0, 0
+    decisions = 0
     with np.errstate(all="ignore"):
         x, x_next, py_next = math.inf, x0, True
         iterations = 0
         while abs(x - x_next) > KL_EPS and iterations < KL_MAX_ITERATIONS:
             iterations += 1
             x, py_x = x_next, py_next
-            f_x = _bernoulli_kl(mu, x) - max_div
+            f_x = _bernoulli_kl(mu, x, log) - max_div
             if py_x and (1 - x == 0 or x == 0):
-                df_x = (f_x - (_bernoulli_kl(mu, x - KL_EPS) - max_div)) / KL_EPS
+                df_x = (f_x - (_bernoulli_kl(mu, x - KL_EPS, log) - max_div)) / KL_EPS
+                decisions |= KL_FINITE_DIFFERENCE
             else:
                 df_x = float(np.float64(1 - mu) / np.float64(1 - x) - np.float64(mu) / np.float64(x))
             if df_x != 0:
@@ -53,13 +62,21 @@ def kl_upper_bound(total, count, threshold):
                 py_next = False
             if x_next < a:
                 x_next, py_next = KL_WEIGHT * a + (1 - KL_WEIGHT) * x, py_x
+                decisions |= KL_CLAMP_LOWER
             elif x_next > b:
                 x_next, py_next = KL_WEIGHT * b + (1 - KL_WEIGHT) * x, py_x
+                decisions |= KL_CLAMP_UPPER
     if x_next < a:
         x_next = a
+        decisions |= KL_FINAL_LOWER
     if x_next > b:
         x_next = b
-    return x_next
+        decisions |= KL_FINAL_UPPER
+    return x_next, iterations, decisions
+
+
+def kl_upper_bound(total, count, threshold):
+    return kl_upper_bound_traced(total, count, threshold)[0]
 
 
 def thresholds(expression, time_ref, episodes):
@@ -86,10 +103,13 @@ def _first_max(values):
 
 
 def olop_plan(transition, reward, terminal, s0, episodes, horizon, gamma, kl, thr, continuation, rng,
-              available=None, order=None, done_rule="source"):
+              available=None, order=None, done_rule="source", first_max=None, amax=np.amax):
     """One OLOP.plan from state ``s0``.  ``rng``: a numpy Generator (advanced in place).  ``thr``: per-episode thresholds.
     ``available`` [S, A] bool and ``order`` (listing order of the action ids) as ``get_available_actions`` lists them.
+    ``first_max`` / ``amax``: other rules in place of Python's ``max`` (olop.py:84, :126-130) and ``np.amax`` (:188), for tests
+    that show which cases tell a wrong NaN rule from the right one.
     Returns dict(plan, parent, action, depth, count, cum, mu, vu, done, state, env_steps, error)."""
+    first_max = first_max or _first_max
     transition = np.asarray(transition)
     reward = np.asarray(reward, np.float64)
     term = np.zeros(reward.shape[0], bool) if terminal is None else np.asarray(terminal).astype(bool).reshape(-1)
@@ -121,7 +141,7 @@ def olop_plan(transition, reward, terminal, s0, episodes, horizon, gamma, kl, th
                     act = 0
             else:
                 kids = children[node]
-                act = action[kids[_first_max([vu[c] for c in kids])]]
+                act = action[kids[first_max([vu[c] for c in kids])]]
             r = float(reward[s, act])
             s_next = int(transition[s, act])
             d = bool(term[s] if done_rule == "source" else term[s_next])
@@ -147,7 +167,7 @@ def olop_plan(transition, reward, terminal, s0, episodes, horizon, gamma, kl, th
             break
         for n in reversed(path):
             if children[n]:
-                m = np.amax([vu[c] for c in children[n]])
+                m = amax([vu[c] for c in children[n]])
                 vu[n] = float(mu[n] + gamma * m)
             else:
                 vu[n] = mu[n]
@@ -158,7 +178,7 @@ def olop_plan(transition, reward, terminal, s0, episodes, horizon, gamma, kl, th
             kids = children[node]
             cnt = np.array([count[c] for c in kids])
             tops = np.flatnonzero(cnt == cnt.max())
-            pick = kids[tops[_first_max([vu[kids[i]] for i in tops])]]
+            pick = kids[tops[first_max([vu[kids[i]] for i in tops])]]
             plan.append(action[pick])
             node = pick
     return dict(plan=np.asarray(plan, np.int32), parent=np.asarray(parent, np.int32), action=np.asarray(action, np.int32),

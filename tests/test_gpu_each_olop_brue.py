@@ -89,8 +89,9 @@ def bits(x):
 
 def assert_bound(got, want, what):
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    fin = np.isfinite(want)
-    assert np.array_equal(bits(got[~fin]), bits(want[~fin])), what
+    fin, inf = np.isfinite(want), np.isinf(want)
+    assert np.array_equal(np.isnan(got), np.isnan(want)), what        # (a NaN by position: its sign and payload are no one's contract)
+    assert np.array_equal(bits(got[inf]), bits(want[inf])), what
     assert np.all(np.abs(got[fin] - want[fin]) <= BOUND_TOL), (what, np.abs(got[fin] - want[fin]).max())
 
 

@@ -80,7 +80,8 @@ def export_arrays(planner):
                 vu=np.asarray([n.value_upper for n in nodes]), done=np.asarray([n.done for n in nodes], np.uint8))
 
 
-def test_every_golden_case(z):
+def golden_cases_through_the_agent(z):
+    """Every case of a golden file in the layout of olop.npz through OLOPAgent; returns how many plans were compared."""
     checked = 0
     for name in names(z):
         case = golden_case(z, name)
@@ -106,7 +107,11 @@ def test_every_golden_case(z):
         assert sorted(visits) == [str(k) for k in case["visit_keys"]], name
         assert [visits[str(k)] for k in case["visit_keys"]] == case["visit_counts"].tolist(), name
         checked += 1
-    assert checked >= 15
+    return checked
+
+
+def test_every_golden_case(z):
+    assert golden_cases_through_the_agent(z) >= 15
 
 
 def test_act_episode_through_agent_factory(z):
@@ -150,8 +155,8 @@ def check_batch(env, cfg, roots, sample, available=None, order=None, tree_roots=
         assert out["plans"][i, :n].tolist() == res["plan"].tolist(), i
         assert np.array_equal(rng[i], rng_after), i
         assert int(out["env_steps"][i]) == res["env_steps"] == pc["episodes"] * pc["horizon"], i
-        if np.isinf(res["vu"][0]):
-            assert out["root_value"][i] == res["vu"][0], i
+        if not np.isfinite(res["vu"][0]):
+            assert np.array_equal(out["root_value"][i], res["vu"][0], equal_nan=True), i
         else:
             assert abs(out["root_value"][i] - res["vu"][0]) <= BOUND_TOL, i
         if i in tree_roots:

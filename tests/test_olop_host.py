@@ -33,7 +33,7 @@ def generator_from(state6):
     return gen
 
 
-def restate(case):
+def restate(case, **rules):
     """Run the restatement on one golden case's inputs; returns (result, generator after)."""
     kl = str(case["bound_type"]) == "kullback-leibler"
     episodes, horizon = int(case["episodes"]), int(case["horizon"])
@@ -41,7 +41,7 @@ def restate(case):
     gen = generator_from(case["rng_before"])
     res = olr.olop_plan(case["mdp/transition"], case["mdp/reward"], case["mdp/terminal"], int(case["s0"]), episodes, horizon,
                         float(case["gamma"]), kl, thr, str(case["continuation"]), gen, available=case["available"],
-                        order=case["order"], done_rule="next" if bool(case["done_on_next"]) else "source")
+                        order=case["order"], done_rule="next" if bool(case["done_on_next"]) else "source", **rules)
     return res, gen
 
 
@@ -49,7 +49,8 @@ def names(z):
     return [str(n) for n in z["olop/names"]]
 
 
-def test_restatement_equals_reference_goldens(z):
+def restatement_equals_golden_cases(z):
+    """The restatement on every case of a golden file in the layout of olop.npz; returns how many plans were compared."""
     checked = 0
     for name in names(z):
         case = golden_case(z, name)
@@ -75,7 +76,11 @@ def test_restatement_equals_reference_goldens(z):
         assert sorted(visits) == [str(k) for k in case["visit_keys"]], name
         assert [visits[str(k)] for k in case["visit_keys"]] == case["visit_counts"].tolist(), name
         checked += 1
-    assert checked >= 15
+    return checked
+
+
+def test_restatement_equals_reference_goldens(z):
+    assert restatement_equals_golden_cases(z) >= 15
 
 
 def test_goldens_cover_the_issue_cases(z):
