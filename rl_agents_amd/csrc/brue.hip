@@ -14,10 +14,9 @@
 //     ceil(cdf * 2^53) (uct_stoch.hip builds them per model), 64 per ballot.
 // A stochastic model's clone is re-seeded per rollout (state.seed(np_random.randint(2**30)), :25): the kernel runs numpy's
 // SeedSequence -> PCG64 seeding (seed_sequence.hpp) on the 30-bit draw and steps THAT generator, one double per model step.
-// Nodes live in a global workspace in creation order (the reference's order of dict insertion): at most
-// 1 + 2 * (budget + H) per tree.  The workspace has one tree per root while the batch's trees fit kBrueKeepBytes (every tree
-// exportable), else one per workgroup (plus one for root 0, the tree an agent exports).  gamma ** d comes from a host table
-// of Python `**`; everything else is + - * / on f64 and integer counts, in the reference's order: results are bit-exact.
+// Nodes live in a global workspace in creation order (the reference's order of dict insertion): at most 1 + 2 * (budget + H)
+// per tree, a tree per root or per workgroup (wave_host.hpp: wave_tree).  gamma ** d comes from a host table of Python `**`;
+// everything else is + - * / on f64 and integer counts, in the reference's order: results are bit-exact.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,6 +27,8 @@
 #include "each_host.hpp"
 #include "pcg64.hpp"
 #include "seed_sequence.hpp"
+#include "wave.hpp"
+#include "wave_host.hpp"
 
 namespace mp {
 
@@ -117,9 +118,7 @@ __global__ __launch_bounds__(64) void brue_kernel(BrueArgs p)
         int base = 0;
         if constexpr (LDS_MODEL) {                                 // (the previous root's reads ended at the barrier closing its iteration)
             base = s_root / p.Sb * p.Sb;
-            const uint4 *src = reinterpret_cast<const uint4 *>(p.rec + (long)base * A);
-            uint4 *dst = reinterpret_cast<uint4 *>(lrec);
-            for (int i = lane; i < p.Sb * A; i += 64) dst[i] = src[i];
+            wave_lds_records(lrec, p.rec, base, A, p.Sb, lane);
         }
         if (lane == 0) {                                           // DecisionNode(parent=None), brue.py:22
             BrueNode r;
@@ -334,74 +333,40 @@ int brue_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t 
                    int32_t *status, int32_t mem, bool each)
 {
     if (!ctx || !model || !root_state || !rng_state || !gpow) return fail(MP_ERR_ARG, "mp_brue_plan: NULL argument");
-    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_brue_plan: unknown mem flags %d", mem);
-    const int rmem = mem_rng(mem);
-    mem = mem_arrays(mem);
-    if (model->mode != MP_MODE_DETERMINISTIC && model->mode != MP_MODE_STOCHASTIC && model->mode != MP_MODE_SPARSE)
-        return fail(MP_ERR_MODE, "mp_brue_plan: model mode %d is not a finite MDP", model->mode);
-    if (model->M != 1 || (!each && model->NB != 1) || (model->mode == MP_MODE_STOCHASTIC && model->Sc != model->S))
-        return fail(MP_ERR_MODE, "mp_brue_plan: one whole model expected (no joint, batch or row-block model)");
+    int rmem;
+    MP_TRY(wave_mem("mp_brue_plan", &mem, &rmem));
+    MP_TRY(wave_mdp_check("mp_brue_plan", model, each));
     const int A = model->A;
     // (a rollout of no step never spends the budget: the reference loops for ever with horizon 0)
     if (n_roots < 1 || horizon < 1 || horizon > kBrueMaxHorizon || A < 1)
         return fail(MP_ERR_ARG, "mp_brue_plan: bad sizes (1 <= horizon <= %d)", kBrueMaxHorizon);
     if (budget < 0) budget = 0;
-    if (mem == MP_MEM_HOST && !pinned_alias(ctx, root_state, (size_t)n_roots * sizeof(int32_t)))
-        for (int i = 0; i < n_roots; ++i)
-            if (root_state[i] < 0 || root_state[i] >= model->S) return fail(MP_ERR_ARG, "mp_brue_plan: root state %d out of range", root_state[i]);
+    MP_TRY(wave_roots(ctx, "mp_brue_plan", root_state, n_roots, model->S, mem));
     const long cap = 1 + 2 * ((long)budget + horizon);
     if (cap * A > (1L << 30)) return fail(MP_ERR_ARG, "mp_brue_plan: %ld nodes of %d actions per tree", cap, A);
-    MP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (model->mode != MP_MODE_DETERMINISTIC) MP_TRY(ensure_thresholds(ctx, model));
+    BrueArgs a;
+    MP_TRY(wave_mdp(ctx, model, &a));
 
     std::vector<double> tab(gpow, gpow + horizon + 1);             // gamma ** d, the host's Python `**`
     double *d_tab = nullptr;
     MP_TRY(upload_tables(ctx, 41, tab, &d_tab));
 
-    BrueArgs a;
     a.Sb = model->Sb > 0 ? model->Sb : model->S;
     // (the global form is the launch mp_brue_plan always made: CUs * 32 wavefronts at most, rew[] and po[] in LDS)
     const int cus = ctx->prop.multiProcessorCount;
     const EachForm form = each ? each_form(EACH_BRUE, a.Sb, A, horizon, n_roots, cus) : each_form_global(EACH_BRUE, horizon, n_roots, cus);
-    a.grid = form.grid;
-    const size_t per_tree = (size_t)cap * (sizeof(BrueNode) + (size_t)A * sizeof(int32_t));
-    a.keep = (size_t)n_roots * per_tree <= kBrueKeepBytes;
-    const size_t slots = a.keep ? (size_t)n_roots : (size_t)a.grid + 1;
     a.n_roots = n_roots; a.A = A; a.H = horizon; a.budget = budget; a.cap = (int)cap; a.done_on_next = model->done_on_next;
-    a.mode = model->mode; a.W = model->mode == MP_MODE_STOCHASTIC ? model->S : model->B; a.gamma = gamma;
-    a.rec = model->rec; a.thr = model->thr; a.nxt = model->NXT; a.R = model->R; a.term = model->term; a.gpow = d_tab;
-    MP_TRY(ws_get(ctx, WS_TREE0, slots * cap * (sizeof(BrueNode) / sizeof(double)), reinterpret_cast<double **>(&a.nodes)));
-    MP_TRY(ws_get(ctx, WS_TREE1, slots * cap * A, &a.ctab));
-    MP_TRY(ws_get(ctx, WS_TREE7, (size_t)n_roots, &a.n_nodes_out));
-    ctx->tree.kind = 6; ctx->tree.armed = false; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap;
-    ctx->tree.K = a.keep ? -1 : a.grid; // which slot holds a root's tree: its own (-1), else root 0 only, in slot `grid`
-
-    int32_t *d_rs = nullptr;
-    MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n_roots, mem, &d_rs));
-    a.root_state = d_rs;
-    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n_roots * 6, rmem, &a.rng));
-    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n_roots, mem, &a.plans));
-    MP_TRY(stage_out_alloc(ctx, WS_IO5, root_value, (size_t)n_roots, mem, &a.root_value));
-    MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
-    MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, mem, &a.env_steps));
-
-    void (*const kfn)(BrueArgs) = form.lds ? brue_kernel<true> : brue_kernel<false>;
-    if (form.lds_bytes() > 64 * 1024)
-        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)form.lds_bytes()));
-    form_record(ctx->last_variant, each ? each_form_name(EACH_BRUE, form.lds, a.keep) : brue_form_name(a.keep));
-    MP_TRY(kernels_begin(ctx));
-    hipLaunchKernelGGL(kfn, dim3((unsigned)a.grid), dim3(64), form.lds_bytes(), st, a);
-    MP_TRY(kernels_end(ctx, 1));
-    MP_HIP(hipGetLastError());
-
-    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n_roots * 6, rmem));
-    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, root_value, a.root_value, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, status, a.status, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n_roots, mem));
-    if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
-    return MP_OK;
+    a.grid = form.grid; a.gamma = gamma; a.term = model->term; a.gpow = d_tab;
+    MP_TRY(wave_tree(ctx, 6, n_roots, A, cap, (size_t)A, kBrueKeepBytes, a.grid + 1, a.grid, &a.nodes, &a.ctab, &a.n_nodes_out, &a.keep));
+    WaveIo io(mem, rmem, n_roots, root_state, &a.root_state, rng_state, &a.rng);
+    io.add(WS_IO3, plans, &a.plans);
+    io.add(WS_IO5, root_value, &a.root_value);
+    io.add(WS_IO7, status, &a.status);
+    io.add(WS_IO8, env_steps, &a.env_steps);
+    MP_TRY(wave_stage(ctx, io));
+    MP_TRY(wave_launch(ctx, form.lds ? brue_kernel<true> : brue_kernel<false>, a.grid, form.lds_bytes(),
+                       each ? each_form_name(EACH_BRUE, form.lds, a.keep) : brue_form_name(a.keep), a));
+    return wave_unstage(ctx, io);
 }
 } // namespace
 } // extern "C++"
@@ -429,23 +394,11 @@ int mp_brue_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int
 int mp_brue_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *key,
                         uint8_t *is_chance, int32_t *depth, int64_t *count, double *stat)
 {
-    if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
-    if (ctx->tree.kind != 6) return fail(MP_ERR_ARG, "mp_brue_tree_export: no tree of mp_brue_plan on this ctx");
-    if (root < 0 || root >= ctx->tree.n_roots) return fail(MP_ERR_ARG, "mp_brue_tree_export: root %d out of range", root);
-    const bool keep = ctx->tree.K < 0;
-    if (!keep && root != 0)
-        return fail(MP_ERR_ARG, "mp_brue_tree_export: the batch's trees did not all fit the workspace; only root 0's was kept");
-    const long slot = keep ? root : ctx->tree.K;
-    const long tcap = ctx->tree.cap;
-    MP_HIP(hipSetDevice(ctx->device));
-    MP_HIP(hipStreamSynchronize(ctx->stream));
-    int32_t n = 0;
-    MP_HIP(hipMemcpy(&n, (const int32_t *)ctx->ws[WS_TREE7].p + root, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (n < 1 || n > tcap) return fail(MP_ERR_ARG, "mp_brue_tree_export: bad node count %d", n);
+    int32_t slot, n;
+    MP_TRY(wave_export_begin(ctx, 6, "mp_brue_tree_export", "mp_brue_plan", root, &slot, &n));
     if (n > cap) return fail(MP_ERR_ARG, "mp_brue_tree_export: capacity %d < %d nodes", cap, n);
     std::vector<BrueNode> na((size_t)n);
-    MP_HIP(hipMemcpy(na.data(), (const BrueNode *)ctx->ws[WS_TREE0].p + slot * tcap, (size_t)n * sizeof(BrueNode),
-                     hipMemcpyDeviceToHost));
+    MP_TRY(wave_pull(ctx, WS_TREE0, slot, n, sizeof(BrueNode), na.data()));
     for (int i = 0; i < n; ++i) {
         if (parent) parent[i] = na[i].parent;
         if (key) key[i] = na[i].key;

@@ -44,6 +44,7 @@
 #include "opd_closing.hpp"
 #include "pcg64.hpp"
 #include "wave.hpp"
+#include "wave_host.hpp"
 
 struct mp_gbopd {
     mp_ctx *ctx = nullptr;
@@ -446,9 +447,8 @@ int mp_gbopd_plan(mp_ctx *ctx, mp_gbopd *pl, const int32_t *root_state, int32_t 
                   double *value_lower, double *value_upper, int64_t *env_steps, int64_t *updates, int32_t *status, int32_t mem)
 {
     if (!ctx || !pl || !root_state || !rng_state) return fail(MP_ERR_ARG, "mp_gbopd_plan: NULL argument");
-    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_gbopd_plan: unknown mem flags %d", mem);
-    const int rmem = mem_rng(mem);
-    mem = mem_arrays(mem);
+    int rmem;
+    MP_TRY(wave_mem("mp_gbopd_plan", &mem, &rmem));
     if (pl->ctx != ctx) return fail(MP_ERR_ARG, "mp_gbopd_plan: planners belong to another context");
     if (pl->model->serial != pl->model_serial)
         return fail(MP_ERR_ARG, "mp_gbopd_plan: the model's tables or action sets changed under a kept graph (bounds, parents and "
@@ -459,11 +459,7 @@ int mp_gbopd_plan(mp_ctx *ctx, mp_gbopd *pl, const int32_t *root_state, int32_t 
     if (!(gamma > -1.0 && gamma < 1.0) || !(value_max == value_max) || !(accuracy >= 0.0))
         return fail(MP_ERR_ARG, "mp_gbopd_plan: need -1 < gamma < 1, accuracy >= 0 and a number for 1 / (1 - gamma)");
     const int n = pl->n, S = pl->S, A = pl->A;
-    if (mem == MP_MEM_HOST && !pinned_alias(ctx, root_state, (size_t)n * sizeof(int32_t)))
-        for (int i = 0; i < n; ++i)
-            if (root_state[i] < 0 || root_state[i] >= S) return fail(MP_ERR_ARG, "mp_gbopd_plan: root state %d out of range", root_state[i]);
-    MP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    MP_TRY(wave_roots(ctx, "mp_gbopd_plan", root_state, n, S, mem));
 
     GbArgs a;
     a.n = n; a.S = S; a.A = A; a.K = budget > 0 ? budget / A : 0; // :120: budget // state.action_space.n
@@ -478,17 +474,15 @@ int mp_gbopd_plan(mp_ctx *ctx, mp_gbopd *pl, const int32_t *root_state, int32_t 
     a.lower = pl->lower; a.upper = pl->upper; a.index = pl->index; a.npar = pl->npar; a.created = pl->created; a.par = pl->par;
     a.queue = pl->queue; a.n_created = pl->n_created; a.failed = pl->failed; a.root_of = pl->root_of; a.expanded = pl->expanded;
     a.visits = pl->visits; a.updates = pl->updates; a.n_obs = pl->n_obs;
-    int32_t *d_rs = nullptr;
-    MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n, mem, &d_rs));
-    a.root_state = d_rs;
-    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n * 6, rmem, &a.rng));
-    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n * sampling_timeout, mem, &a.plans));
-    MP_TRY(stage_out_alloc(ctx, WS_IO4, plan_len, (size_t)n, mem, &a.plan_len));
-    MP_TRY(stage_out_alloc(ctx, WS_IO5, status, (size_t)n, mem, &a.status));
-    MP_TRY(stage_out_alloc(ctx, WS_IO6, env_steps, (size_t)n, mem, &a.env_steps));
-    MP_TRY(stage_out_alloc(ctx, WS_IO7, updates, (size_t)n, mem, &a.n_updates));
-    MP_TRY(stage_out_alloc(ctx, WS_IO8, value_lower, (size_t)n, mem, &a.root_lower));
-    MP_TRY(stage_out_alloc(ctx, WS_IO9, value_upper, (size_t)n, mem, &a.root_upper));
+    WaveIo io(mem, rmem, n, root_state, &a.root_state, rng_state, &a.rng);
+    io.add(WS_IO3, plans, &a.plans, (size_t)sampling_timeout);
+    io.add(WS_IO4, plan_len, &a.plan_len);
+    io.add(WS_IO5, status, &a.status);
+    io.add(WS_IO6, env_steps, &a.env_steps);
+    io.add(WS_IO7, updates, &a.n_updates);
+    io.add(WS_IO8, value_lower, &a.root_lower);
+    io.add(WS_IO9, value_upper, &a.root_upper);
+    MP_TRY(wave_stage(ctx, io));
 
     // both bounds in LDS while they are small (16 KiB: ten planners per CU); MP_GBOPD_LDS_BYTES moves the limit (0: never)
     size_t lds_limit = 16 * 1024;
@@ -496,23 +490,8 @@ int mp_gbopd_plan(mp_ctx *ctx, mp_gbopd *pl, const int32_t *root_state, int32_t 
     if (lds_limit > 64 * 1024) lds_limit = 64 * 1024;
     const size_t lds = (size_t)S * 16;
     const bool use_lds = lds <= lds_limit;
-    form_record(ctx->last_variant, gbopd_form_name(use_lds));
-    MP_TRY(kernels_begin(ctx));
-    if (use_lds) hipLaunchKernelGGL(gbopd_kernel<true>, dim3((unsigned)n), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL(gbopd_kernel<false>, dim3((unsigned)n), dim3(64), 0, st, a);
-    MP_TRY(kernels_end(ctx, 1));
-    MP_HIP(hipGetLastError());
-
-    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n * 6, rmem));
-    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n * sampling_timeout, mem));
-    MP_TRY(stage_out_copy(ctx, plan_len, a.plan_len, (size_t)n, mem));
-    MP_TRY(stage_out_copy(ctx, status, a.status, (size_t)n, mem));
-    MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n, mem));
-    MP_TRY(stage_out_copy(ctx, updates, a.n_updates, (size_t)n, mem));
-    MP_TRY(stage_out_copy(ctx, value_lower, a.root_lower, (size_t)n, mem));
-    MP_TRY(stage_out_copy(ctx, value_upper, a.root_upper, (size_t)n, mem));
-    if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
-    return MP_OK;
+    MP_TRY(wave_launch(ctx, use_lds ? gbopd_kernel<true> : gbopd_kernel<false>, n, use_lds ? lds : 0, gbopd_form_name(use_lds), a));
+    return wave_unstage(ctx, io);
 }
 
 int mp_gbopd_info(mp_gbopd *pl, int32_t *n_planners, int32_t *n_states, int32_t *n_actions, int32_t *queue_cap, int64_t *n_edges)

@@ -9,10 +9,9 @@
 //   * the L bounds of an episode's path are independent (each node appears once on the path and only the backup reads them),
 //     so the lanes cover the L path nodes and run their Newton iterations (utils.py:123-203) at the same time, after the walk.
 // Nodes live in a global workspace, children contiguous in creation order (the reference's order of dict insertion): at most
-// 1 + M * L * |A| nodes per tree.  The workspace has one tree per root while the batch's trees fit kOlopKeepBytes (every tree
-// exportable), else one per workgroup (plus one for root 0, the tree an agent exports).  Everything that is not a basic IEEE
-// operation -- the initial upper bounds (Python **), the thresholds (eval of the config string, np.log) -- comes from host
-// tables.  The Newton step's log is the device's (parity of the bounds is 1e-12, not bit-exact).
+// 1 + M * L * |A| nodes per tree, a tree per root or per workgroup (wave_host.hpp: wave_tree).  Everything that is not a basic
+// IEEE operation -- the initial upper bounds (Python **), the thresholds (eval of the config string, np.log) -- comes from
+// host tables.  The Newton step's log is the device's (parity of the bounds is 1e-12, not bit-exact).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -22,6 +21,8 @@
 #include "common.hpp"
 #include "each_host.hpp"
 #include "pcg64.hpp"
+#include "wave.hpp"
+#include "wave_host.hpp"
 
 namespace mp {
 
@@ -184,9 +185,7 @@ __global__ __launch_bounds__(64) void olop_kernel(OlopArgs p)
         if constexpr (LDS_MODEL) {
             s_root = p.root_state[root];
             base = s_root / p.Sb * p.Sb;
-            const uint4 *src = reinterpret_cast<const uint4 *>(p.rec + (long)base * A);
-            uint4 *dst = reinterpret_cast<uint4 *>(lrec);
-            for (int i = lane; i < p.Sb * A; i += 64) dst[i] = src[i];
+            wave_lds_records(lrec, p.rec, base, A, p.Sb, lane);
         }
         if (lane == 0) {
             OlopNode r;
@@ -347,9 +346,8 @@ int olop_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t 
                    double *root_value, int64_t *env_steps, int32_t *status, int32_t mem, bool each)
 {
     if (!ctx || !model || !root_state || !rng_state || !value_upper_init) return fail(MP_ERR_ARG, "mp_olop_plan: NULL argument");
-    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_olop_plan: unknown mem flags %d", mem);
-    const int rmem = mem_rng(mem);
-    mem = mem_arrays(mem);
+    int rmem;
+    MP_TRY(wave_mem("mp_olop_plan", &mem, &rmem));
     if (model->mode != MP_MODE_DETERMINISTIC)
         return fail(MP_ERR_MODE, "mp_olop_plan: model mode %d is not a deterministic table", model->mode);
     const int A = model->A;
@@ -357,13 +355,9 @@ int olop_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t 
         return fail(MP_ERR_ARG, "mp_olop_plan: bad sizes");
     if (bound_type == 1 && episodes > 0 && !thresholds) return fail(MP_ERR_ARG, "mp_olop_plan: thresholds are NULL");
     if (continuation >= A) return fail(MP_ERR_ARG, "mp_olop_plan: continuation action %d out of range", continuation);
-    if (mem == MP_MEM_HOST && !pinned_alias(ctx, root_state, (size_t)n_roots * sizeof(int32_t)))
-        for (int i = 0; i < n_roots; ++i)
-            if (root_state[i] < 0 || root_state[i] >= model->S) return fail(MP_ERR_ARG, "mp_olop_plan: root state %d out of range", root_state[i]);
+    MP_TRY(wave_roots(ctx, "mp_olop_plan", root_state, n_roots, model->S, mem));
     const long cap = 1 + (long)episodes * horizon * A;
     if (cap > (1L << 30)) return fail(MP_ERR_ARG, "mp_olop_plan: %ld nodes per tree", cap);
-    MP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
 
     // one table: thresholds [M] then value_upper_init [L + 1] (host pointers; the values the reference's Python computes)
     std::vector<double> tab((size_t)episodes + horizon + 1);
@@ -377,47 +371,20 @@ int olop_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t 
     // (the global form is the launch mp_olop_plan always made: CUs * 32 wavefronts at most, path[] in LDS)
     const int cus = ctx->prop.multiProcessorCount;
     const EachForm form = each ? each_form(EACH_OLOP, a.Sb, A, horizon, n_roots, cus) : each_form_global(EACH_OLOP, horizon, n_roots, cus);
-    a.grid = form.grid;
-    const size_t per_tree = (size_t)cap * (sizeof(OlopNode) + sizeof(double));
-    a.keep = (size_t)n_roots * per_tree <= kOlopKeepBytes;
-    const size_t slots = a.keep ? (size_t)n_roots : (size_t)a.grid + 1;
     a.n_roots = n_roots; a.A = A; a.M = episodes; a.L = horizon; a.cap = (int)cap; a.done_on_next = model->done_on_next;
     a.kl = bound_type == 1; a.cont = continuation; a.max_plan_len = max_plan_len; a.gamma = gamma;
-    a.rec = model->rec;
-    a.thr = d_tab; a.vinit = d_tab + episodes;
-    MP_TRY(ws_get(ctx, WS_TREE0, slots * cap * (sizeof(OlopNode) / sizeof(double)), reinterpret_cast<double **>(&a.nodes)));
-    MP_TRY(ws_get(ctx, WS_TREE1, slots * cap, &a.vu));
-    MP_TRY(ws_get(ctx, WS_TREE7, (size_t)n_roots, &a.n_nodes_out));
-    ctx->tree.kind = 5; ctx->tree.armed = false; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap;
-    ctx->tree.K = a.keep ? -1 : a.grid; // which slot holds a root's tree: its own (-1), else root 0 only, in slot `grid`
-
-    int32_t *d_rs = nullptr;
-    MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n_roots, mem, &d_rs));
-    a.root_state = d_rs;
-    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n_roots * 6, rmem, &a.rng));
-    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n_roots * max_plan_len, mem, &a.plans));
-    MP_TRY(stage_out_alloc(ctx, WS_IO4, plan_len, (size_t)n_roots, mem, &a.plan_len));
-    MP_TRY(stage_out_alloc(ctx, WS_IO5, root_value, (size_t)n_roots, mem, &a.root_value));
-    MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
-    MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, mem, &a.env_steps));
-
-    void (*const kfn)(OlopArgs) = form.lds ? olop_kernel<true> : olop_kernel<false>;
-    if (form.lds_bytes() > 64 * 1024)
-        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)form.lds_bytes()));
-    form_record(ctx->last_variant, each ? each_form_name(EACH_OLOP, form.lds, a.keep) : olop_form_name(a.keep));
-    MP_TRY(kernels_begin(ctx));
-    hipLaunchKernelGGL(kfn, dim3((unsigned)a.grid), dim3(64), form.lds_bytes(), st, a);
-    MP_TRY(kernels_end(ctx, 1));
-    MP_HIP(hipGetLastError());
-
-    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n_roots * 6, rmem));
-    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n_roots * max_plan_len, mem));
-    MP_TRY(stage_out_copy(ctx, plan_len, a.plan_len, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, root_value, a.root_value, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, status, a.status, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n_roots, mem));
-    if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
-    return MP_OK;
+    a.grid = form.grid; a.rec = model->rec; a.thr = d_tab; a.vinit = d_tab + episodes;
+    MP_TRY(wave_tree(ctx, 5, n_roots, A, cap, 1, kOlopKeepBytes, a.grid + 1, a.grid, &a.nodes, &a.vu, &a.n_nodes_out, &a.keep));
+    WaveIo io(mem, rmem, n_roots, root_state, &a.root_state, rng_state, &a.rng);
+    io.add(WS_IO3, plans, &a.plans, (size_t)max_plan_len);
+    io.add(WS_IO4, plan_len, &a.plan_len);
+    io.add(WS_IO5, root_value, &a.root_value);
+    io.add(WS_IO7, status, &a.status);
+    io.add(WS_IO8, env_steps, &a.env_steps);
+    MP_TRY(wave_stage(ctx, io));
+    MP_TRY(wave_launch(ctx, form.lds ? olop_kernel<true> : olop_kernel<false>, a.grid, form.lds_bytes(),
+                       each ? each_form_name(EACH_OLOP, form.lds, a.keep) : olop_form_name(a.keep), a));
+    return wave_unstage(ctx, io);
 }
 } // namespace
 } // extern "C++"
@@ -448,26 +415,13 @@ int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
                         int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *value_upper,
                         uint8_t *done, int32_t *state)
 {
-    if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
-    if (ctx->tree.kind != 5) return fail(MP_ERR_ARG, "mp_olop_tree_export: no tree of mp_olop_plan on this ctx");
-    if (root < 0 || root >= ctx->tree.n_roots) return fail(MP_ERR_ARG, "mp_olop_tree_export: root %d out of range", root);
-    const bool keep = ctx->tree.K < 0;
-    if (!keep && root != 0)
-        return fail(MP_ERR_ARG, "mp_olop_tree_export: the batch's trees did not all fit the workspace; only root 0's was kept");
-    const long slot = keep ? root : ctx->tree.K;
-    const long tcap = ctx->tree.cap;
-    MP_HIP(hipSetDevice(ctx->device));
-    MP_HIP(hipStreamSynchronize(ctx->stream));
-    int32_t n = 0;
-    MP_HIP(hipMemcpy(&n, (const int32_t *)ctx->ws[WS_TREE7].p + root, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (n < 1 || n > tcap) return fail(MP_ERR_ARG, "mp_olop_tree_export: bad node count %d", n);
+    int32_t slot, n;
+    MP_TRY(wave_export_begin(ctx, 5, "mp_olop_tree_export", "mp_olop_plan", root, &slot, &n));
     if (n > cap) return fail(MP_ERR_ARG, "mp_olop_tree_export: capacity %d < %d nodes", cap, n);
     std::vector<OlopNode> na((size_t)n);
     std::vector<double> vu((size_t)n);
-    MP_HIP(hipMemcpy(na.data(), (const OlopNode *)ctx->ws[WS_TREE0].p + slot * tcap, (size_t)n * sizeof(OlopNode),
-                     hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(vu.data(), (const double *)ctx->ws[WS_TREE1].p + slot * tcap, (size_t)n * sizeof(double),
-                     hipMemcpyDeviceToHost));
+    MP_TRY(wave_pull(ctx, WS_TREE0, slot, n, sizeof(OlopNode), na.data()));
+    MP_TRY(wave_pull(ctx, WS_TREE1, slot, n, sizeof(double), vu.data()));
     for (int i = 0; i < n; ++i) {
         if (parent) parent[i] = na[i].parent;
         if (action) action[i] = na[i].action;

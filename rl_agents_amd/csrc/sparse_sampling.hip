@@ -36,6 +36,7 @@
 #include "opd_closing.hpp"
 #include "pcg64.hpp"
 #include "seed_sequence.hpp"
+#include "wave_host.hpp"
 
 namespace mp {
 
@@ -475,29 +476,21 @@ int mp_ss_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *roo
                uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *samples, int32_t *status, int32_t mem)
 {
     if (!ctx || !model || !root_state || !rng_state) return fail(MP_ERR_ARG, "mp_ss_plan: NULL argument");
-    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_ss_plan: unknown mem flags %d", mem);
-    const int rmem = mem_rng(mem);
-    mem = mem_arrays(mem);
-    if (model->mode != MP_MODE_DETERMINISTIC && model->mode != MP_MODE_STOCHASTIC && model->mode != MP_MODE_SPARSE)
-        return fail(MP_ERR_MODE, "mp_ss_plan: model mode %d is not a finite MDP", model->mode);
-    if (model->M != 1 || model->NB != 1 || (model->mode == MP_MODE_STOCHASTIC && model->Sc != model->S))
-        return fail(MP_ERR_MODE, "mp_ss_plan: one whole model expected (no joint, batch or row-block model)");
+    int rmem;
+    MP_TRY(wave_mem("mp_ss_plan", &mem, &rmem));
+    MP_TRY(wave_mdp_check("mp_ss_plan", model, false));
     const int A = model->A;
     if (n_roots < 1 || A < 1) return fail(MP_ERR_ARG, "mp_ss_plan: bad sizes");
     // (horizon 0: the root gets no child and the reference's selection raises; C 0: its backup reads a reward no sample set)
     if (horizon < 1 || horizon > kSsMaxHorizon)
         return fail(MP_ERR_ARG, "mp_ss_plan: horizon %d: the frames serve 1 <= horizon <= %d", horizon, kSsMaxHorizon);
     if (C < 1 || C > kSsMaxC) return fail(MP_ERR_ARG, "mp_ss_plan: C %d: the frames serve 1 <= C <= %d samples", C, kSsMaxC);
-    if (mem == MP_MEM_HOST && !pinned_alias(ctx, root_state, (size_t)n_roots * sizeof(int32_t)))
-        for (int i = 0; i < n_roots; ++i)
-            if (root_state[i] < 0 || root_state[i] >= model->S) return fail(MP_ERR_ARG, "mp_ss_plan: root state %d out of range", root_state[i]);
-    MP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    if (model->mode != MP_MODE_DETERMINISTIC) MP_TRY(ensure_thresholds(ctx, model));
+    MP_TRY(wave_roots(ctx, "mp_ss_plan", root_state, n_roots, model->S, mem));
+    SsArgs a;
+    MP_TRY(wave_mdp(ctx, model, &a));
     int W = 1;
     MP_TRY(ss_outdegree(ctx, model, &W));
 
-    SsArgs a;
     a.L = C < W ? C : W;
     const int64_t bound = ss_node_bound(A, horizon, a.L);
     if (bound < 0)
@@ -512,67 +505,34 @@ int mp_ss_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *roo
     }
     const long waves = (long)ctx->prop.multiProcessorCount * 32;
     a.grid = (int)(n_roots < waves ? n_roots : waves);
-    a.keep = (size_t)n_roots * per_tree <= keep_bytes;
-    a.n_roots = n_roots; a.A = A; a.H = horizon; a.C = C; a.mode = model->mode; a.cap = (int)bound; a.gamma = gamma;
-    a.W = model->mode == MP_MODE_STOCHASTIC ? model->S : model->B;
-    a.rec = model->rec; a.thr = model->thr; a.nxt = model->NXT; a.R = model->R; a.avail = model->masked ? model->avail : nullptr;
+    a.n_roots = n_roots; a.A = A; a.H = horizon; a.C = C; a.cap = (int)bound; a.gamma = gamma;
+    a.avail = model->masked ? model->avail : nullptr;
     MP_TRY(ss_jump_table(ctx, &a.jump));
-    const size_t slots = a.keep ? (size_t)n_roots : 1;
-    MP_TRY(ws_get(ctx, WS_TREE0, slots * (size_t)bound * (sizeof(SsNode) / sizeof(double)), reinterpret_cast<double **>(&a.nodes)));
-    MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots * A, &a.rootq));
-    MP_TRY(ws_get(ctx, WS_TREE7, (size_t)n_roots, &a.n_nodes_out));
     const size_t frame_bytes = (size_t)horizon * ss_frame_stride(a.L);
     const bool use_lds = ss_use_lds(frame_bytes);
     a.frames = nullptr;
     if (!use_lds) MP_TRY(ws_get(ctx, WS_TREE2, (size_t)a.grid * frame_bytes, &a.frames));
-    ctx->tree.kind = 7; ctx->tree.armed = false; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)bound;
-    ctx->tree.K = a.keep ? -1 : 0; // which slot holds a root's tree: its own (-1), else root 0 only
-
-    int32_t *d_rs = nullptr;
-    MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n_roots, mem, &d_rs));
-    a.root_state = d_rs;
-    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n_roots * 6, rmem, &a.rng));
-    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n_roots, mem, &a.plans));
-    MP_TRY(stage_out_alloc(ctx, WS_IO5, root_value, (size_t)n_roots, mem, &a.root_value));
-    MP_TRY(stage_out_alloc(ctx, WS_IO7, status, (size_t)n_roots, mem, &a.status));
-    MP_TRY(stage_out_alloc(ctx, WS_IO8, samples, (size_t)n_roots, mem, &a.samples));
-
-    form_record(ctx->last_variant, ss_form_name(use_lds));
-    MP_TRY(kernels_begin(ctx));
-    if (use_lds) hipLaunchKernelGGL(ss_kernel<true>, dim3((unsigned)a.grid), dim3(64), frame_bytes, st, a);
-    else hipLaunchKernelGGL(ss_kernel<false>, dim3((unsigned)a.grid), dim3(64), 0, st, a);
-    MP_TRY(kernels_end(ctx, 1));
-    MP_HIP(hipGetLastError());
-
-    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n_roots * 6, rmem));
-    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, root_value, a.root_value, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, status, a.status, (size_t)n_roots, mem));
-    MP_TRY(stage_out_copy(ctx, samples, a.samples, (size_t)n_roots, mem));
-    if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
-    return MP_OK;
+    MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots * A, &a.rootq)); // (not a per-slot array here)
+    MP_TRY(wave_tree(ctx, 7, n_roots, A, bound, 0, keep_bytes, 1, 0, &a.nodes, (double **)nullptr, &a.n_nodes_out, &a.keep));
+    WaveIo io(mem, rmem, n_roots, root_state, &a.root_state, rng_state, &a.rng);
+    io.add(WS_IO3, plans, &a.plans);
+    io.add(WS_IO5, root_value, &a.root_value);
+    io.add(WS_IO7, status, &a.status);
+    io.add(WS_IO8, samples, &a.samples);
+    MP_TRY(wave_stage(ctx, io));
+    MP_TRY(wave_launch(ctx, use_lds ? ss_kernel<true> : ss_kernel<false>, a.grid, use_lds ? frame_bytes : 0, ss_form_name(use_lds), a));
+    return wave_unstage(ctx, io);
 }
 
 int mp_ss_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *key, uint8_t *is_chance,
                       int32_t *depth, int64_t *count, double *value)
 {
-    if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
-    if (ctx->tree.kind != 7) return fail(MP_ERR_ARG, "mp_ss_tree_export: no tree of mp_ss_plan on this ctx");
-    if (root < 0 || root >= ctx->tree.n_roots) return fail(MP_ERR_ARG, "mp_ss_tree_export: root %d out of range", root);
-    const bool keep = ctx->tree.K < 0;
-    if (!keep && root != 0)
-        return fail(MP_ERR_ARG, "mp_ss_tree_export: the batch's trees did not all fit the workspace; only root 0's was kept");
-    const long slot = keep ? root : 0;
-    const long tcap = ctx->tree.cap;
-    MP_HIP(hipSetDevice(ctx->device));
-    MP_HIP(hipStreamSynchronize(ctx->stream));
-    int32_t n = 0;
-    MP_HIP(hipMemcpy(&n, (const int32_t *)ctx->ws[WS_TREE7].p + root, sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (n < 1 || n > tcap) return fail(MP_ERR_ARG, "mp_ss_tree_export: bad node count %d", n);
-    if (n_nodes) *n_nodes = n;
+    int32_t slot, n;
+    MP_TRY(wave_export_begin(ctx, 7, "mp_ss_tree_export", "mp_ss_plan", root, &slot, &n));
+    if (n_nodes) *n_nodes = n;                                     // (before the refusal: the caller learns the capacity it needs)
     if (n > cap) return fail(MP_ERR_ARG, "mp_ss_tree_export: capacity %d < %d nodes", cap, n);
     std::vector<SsNode> na((size_t)n);
-    MP_HIP(hipMemcpy(na.data(), (const SsNode *)ctx->ws[WS_TREE0].p + slot * tcap, (size_t)n * sizeof(SsNode), hipMemcpyDeviceToHost));
+    MP_TRY(wave_pull(ctx, WS_TREE0, slot, n, sizeof(SsNode), na.data()));
     for (int i = 0; i < n; ++i) {
         if (parent) parent[i] = na[i].parent;
         if (key) key[i] = na[i].key;

@@ -9,6 +9,16 @@ namespace mp {
 __device__ __forceinline__ unsigned long long ballot64(bool pred) { return __builtin_amdgcn_ballot_w64(pred); }
 __device__ __forceinline__ bool any64(bool pred) { return __builtin_amdgcn_ballot_w64(pred) != 0ull; }
 
+// The Sb * |A| 16-byte records (Rec) of the MDP that starts at state `base` of the table `rec` into LDS, a record a lane.  No
+// barrier: the caller's next one separates the copy from its readers.
+template <typename R>
+__device__ __forceinline__ void wave_lds_records(R *lrec, const R *rec, int base, int A, int Sb, int lane)
+{
+    static_assert(sizeof(R) == 16, "one uint4 a record");
+    const uint4 *src = reinterpret_cast<const uint4 *>(rec + (long)base * A);
+    uint4 *dst = reinterpret_cast<uint4 *>(lrec);
+    for (int i = lane; i < Sb * A; i += 64) dst[i] = src[i];
+}
 
 // ---- 32-bit DPP reductions written as ONE instruction per step: `v_op_dpp v, v, v` computes op(dpp(v), v) in place and
 // lanes without a valid DPP source keep their value (bound_ctrl off = the lane is disabled for the instruction).  The
