@@ -689,7 +689,49 @@ int mp_model_set_available_joint(mp_model *model, const uint8_t *available);
 int mp_ropd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t budget, double gamma,
                  double terminal_reward, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len,
                  double *root_lower, double *root_upper, int64_t *env_steps, int32_t *status, int32_t mem);
-/* Tree of root `root` after the last mp_ropd_plan, creation order (A children per expanded node); host arrays of capacity
+/*
+ * One SET of M models per root.  DiscreteRobustPlannerAgent.plan builds its models again before every plan --
+ * preprocess_env(self.true_env, preprocessors) for each entry of config["models"], the M results in a JointEnv
+ * (agents/robust/robust.py:68-71) -- so a batch of such agents on environments whose tables are extracted at every step holds
+ * N sets of M hypothesis tables, all of which change between two steps.
+ *   transition int64 [N,M,S,A] (next states LOCAL to each table, 0 <= t < S), reward double [N,M,S,A],
+ *   terminal uint8 [N,M,S] or NULL; done_on_next as mp_model_load_joint.  N * S * A < 2^31, and the N * M * S * A records
+ *   (with their tables, 28 bytes each) must fit the device's memory: else MP_ERR_ARG.
+ * The result is ONE joint model of M models over the disjoint union of the N state spaces: GLOBAL state n * S + s, the
+ * records model-major over global states ([M][N * S][A], next states global), mp_model_info reports M and S = N * S,
+ * mp_model_batch_info N and S.  mp_ropd_plan takes it with global joint states, mp_ropd_plan_models with (set, local joint
+ * state) pairs; the kernels are those of a plain joint model.  Tree exports report global states.
+ */
+int mp_model_load_joint_batch(mp_ctx *ctx, int32_t N, int32_t M, int32_t S, int32_t A, const int64_t *transition,
+                              const double *reward, const uint8_t *terminal, int32_t done_on_next, mp_model **out);
+/*
+ * Replace sets [first, first + count) of such a model: the per-step delta of a batch of robust agents (robust.py:68-71 once
+ * per agent and step).  Arrays as mp_model_load_joint_batch with N = count (host pointers; terminal iff the model was loaded
+ * with terminal flags).  Availability flags set before are kept.  A next state outside [0, S) returns MP_ERR_ARG and leaves
+ * the model as it was.  Stream-ordered through the model's pinned staging block like mp_model_update_tables; ONE launch packs
+ * the count * M tables.  (mp_model_update_tables / _rows refuse every joint model, this one included: MP_ERR_MODE.)
+ */
+int mp_model_update_joint_tables(mp_model *model, int32_t first, int32_t count, const int64_t *transition, const double *reward,
+                                 const uint8_t *terminal);
+/*
+ * JointEnv.get_available_actions (robust.py:22-25) for every set: available uint8 [N,M,S,A], host pointer; every
+ * (set, model, state) needs at least one action.  The flags live in the records (the union over the models is taken by the
+ * planner per joint state) and survive mp_model_update_joint_tables.
+ */
+int mp_model_set_available_joint_batch(mp_model *model, const uint8_t *available);
+/*
+ * mp_ropd_plan with one set per root (robust.py:68-73: every agent plans on the joint env it has just built): root i plans on
+ * set model_index[i] from the LOCAL joint state root_state[i][0..M).
+ *   model_index int32 [n_roots], root_state int32 [n_roots,M]; everything else as mp_ropd_plan (MP_MEM_HOST, MP_MEM_DEVICE,
+ *   MP_MEM_RNG_DEVICE).  Host arrays out of range: MP_ERR_ARG; device arrays: the root is clamped to state 0 of set 0 and
+ *   counted (mp_ctx_device_faults), as mp_opd_plan_models does.  MP_ERR_MODE for anything but a model of
+ *   mp_model_load_joint_batch.  The kernel is mp_ropd_plan's, and so is the name mp_last_kernel_variant reports.
+ */
+int mp_ropd_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                        int32_t budget, double gamma, double terminal_reward, uint64_t *rng_state, int32_t max_plan_len,
+                        int32_t *plans, int32_t *plan_len, double *root_lower, double *root_upper, int64_t *env_steps,
+                        int32_t *status, int32_t mem);
+/* Tree of root `root` after the last mp_ropd_plan / mp_ropd_plan_models, creation order (A children per expanded node); host arrays of capacity
  * `cap` nodes; state / reward / lower / upper / done are [cap,M]: a leaf's per-model values, an expanded node's
  * backed-up scalars repeated M times; n_children: children per node (contiguous from first_child; < A with restricted
  * action sets). */

@@ -100,8 +100,10 @@ class DiscreteRobustPlanner(OptimisticDeterministicPlanner):
         n = int(out["plan_len"][0])
         return [int(a) for a in out["plans"][0, :n]]
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, model=None):
-        """root_states: [n] (all models start in the same state) or [n, M] joint states."""
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, model=None, model_index=None):
+        """root_states: [n] (all models start in the same state) or [n, M] joint states.  ``model_index`` int [n] with a joint
+        batch model (``Context.load_joint_batch``): root i plans on set ``model_index[i]`` from its LOCAL joint state
+        (mp_ropd_plan_models) -- a batch of agents that each built their own models (robust.py:68-71)."""
         if model is None:
             model, _ = self.joint_model(state)
         rs = np.asarray(root_states, dtype=np.int32)
@@ -114,11 +116,13 @@ class DiscreteRobustPlanner(OptimisticDeterministicPlanner):
             raise ZeroDivisionError("float division by zero")       # gamma ** depth / (1 - gamma), deterministic.py:53
         self.about_to_plan()
         out = self.models.ctx.ropd_plan(model, rs, budget, cfg["gamma"], cfg.get("terminal_reward", 0), rng_states,
-                                        max_plan_len=budget // model.A + 1)
+                                        max_plan_len=budget // model.A + 1, model_index=model_index)
         if (out["status"] == native.ERR_REWARD_RANGE).any():
             raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # deterministic.py:46-47
         out["rng_states"] = rng_states
         self.last, self._root, self._last_actions, self._last_models = out, None, model.A, model.M
+        # (a tree on a joint batch model holds global states n * S_each + s: export_tree reports the set's own)
+        self._last_states_each = model.S_each if model_index is not None else None
         self.claim_device_tree()
         self.env_steps += int(out["env_steps"].sum())
         return out
@@ -158,7 +162,7 @@ class DiscreteRobustPlanner(OptimisticDeterministicPlanner):
         ctx.ropd_plan_device(jm, n, self._d_joint, budget, cfg["gamma"], cfg.get("terminal_reward", 0), d_rng,
                              int(d_plans.shape[1]), plans=d_plans, plan_len=d_len, root_lower=d_value, env_steps=d_env_steps,
                              status=d_status)
-        self._last_actions, self._last_models = jm.A, jm.M
+        self._last_actions, self._last_models, self._last_states_each = jm.A, jm.M, None
         self.claim_device_tree()
         self.last, self._root = None, None
 
@@ -166,6 +170,8 @@ class DiscreteRobustPlanner(OptimisticDeterministicPlanner):
         self.require_device_tree()
         a, m = self._last_actions, self._last_models
         arrays = self.models.ctx.ropd_tree(root, 1 + (int(self.config["budget"]) // a) * a, m)
+        if getattr(self, "_last_states_each", None):
+            arrays["state"] = arrays["state"] % self._last_states_each
         lower, upper = arrays["lower"], arrays["upper"]
         arrays["value_lower_min"], arrays["value_upper_min"] = lower.min(axis=1), upper.min(axis=1)
         tree = build_tree(arrays, "value_upper_min", extra=("value_lower_min", "value_upper_min"), planner=self)

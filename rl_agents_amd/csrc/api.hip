@@ -161,6 +161,35 @@ __global__ void pack_records_range(int s0, int ns, int A, const int32_t *__restr
     if (t16) t16[i] = (uint16_t)((uint32_t)r.next | (term && term[r.next] ? 0x8000u : 0u));
 }
 
+// joint batch models (mp_model_load_joint_batch / mp_model_update_joint_tables): `count` sets of M tables, staged as the caller
+// holds them ([count][M][Sb][A], next states local; term [count][M][Sb]), into the model's model-major arrays over global states
+// ([M][S][A], S = NB * Sb, next states global) and their records -- ONE launch for all count * M tables.  A thread reads staged
+// values only (the terminal flag of its next state included), so no thread depends on what another one writes.
+__global__ void pack_joint_range(int first, int count, int M, int Sb, int A, long S, const int32_t *__restrict__ t_new,
+                                 const double *__restrict__ r_new, const uint8_t *__restrict__ term_new,
+                                 const uint8_t *__restrict__ avail, int32_t *__restrict__ T, double *__restrict__ R,
+                                 uint8_t *__restrict__ term_all, Rec *__restrict__ rec_all)
+{
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long sa = (long)Sb * A;
+    if (j >= (long)count * M * sa) return;
+    const int cm = (int)(j / sa);       // (set, model) pair of the staged block
+    const int c = cm / M, m = cm - c * M;
+    const int sl = (int)((j - (long)cm * sa) / A), a = (int)(j - (long)cm * sa - (long)sl * A);
+    const int base = (first + c) * Sb;  // first global state of the set
+    const long i = ((long)m * S + base + sl) * A + a;
+    const int nl = t_new[j];
+    const uint8_t *tm = term_new ? term_new + (long)cm * Sb : nullptr;
+    Rec r;
+    r.next = base + nl;
+    r.flags = (tm && tm[sl] ? 1u : 0u) | (tm && tm[nl] ? 2u : 0u) | (!avail || avail[i] ? 4u : 0u);
+    r.reward = r_new[j];
+    T[i] = r.next;
+    R[i] = r.reward;
+    rec_all[i] = r;
+    if (a == 0 && tm) term_all[(long)m * S + base + sl] = tm[sl];
+}
+
 // mp_model_update_rows: rows[k] = global state id; its |A| transitions / rewards (+ terminal flag, + reward indices) from the
 // staged arrays into the model's tables
 __global__ void scatter_rows(int n_rows, int A, const int32_t *__restrict__ rows, const int32_t *__restrict__ t_new,
@@ -208,6 +237,23 @@ __global__ void globalize_roots(int n, int Sb, int NB, const int32_t *__restrict
     const bool bad = m < 0 || m >= NB || s < 0 || s >= Sb;
     if (bad && fault) atomicAdd(fault, 1);
     global[i] = bad ? 0 : m * Sb + s;
+}
+
+// the joint form: root i of a joint batch model holds M local states of set model_index[i].  One thread per root; a bad set or
+// ANY bad state clamps the whole root to state 0 of set 0 and counts it once.
+__global__ void globalize_joint_roots(int n, int M, int Sb, int NB, const int32_t *__restrict__ model_index,
+                                      const int32_t *__restrict__ local, int32_t *__restrict__ global, int32_t *__restrict__ fault)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = model_index[i];
+    bool bad = b < 0 || b >= NB;
+    for (int m = 0; m < M; ++m) {
+        const int s = local[(long)i * M + m];
+        bad |= s < 0 || s >= Sb;
+    }
+    if (bad && fault) atomicAdd(fault, 1);
+    for (int m = 0; m < M; ++m) global[(long)i * M + m] = bad ? 0 : b * Sb + local[(long)i * M + m];
 }
 
 // compact transitions for the LDS variant of the UCT kernel (S < 32768)
@@ -302,6 +348,16 @@ __global__ void unpack_rows_kernel(RowCols c, int n_total, int world, int per, c
     static_cast<uint32_t *>(const_cast<void *>(c.ptr[k]))[(long)row * w + (col - c.off[k])] = packed[((long)r * per + j) * wpr + col];
 }
 
+// the ctx's sticky fault word (common.hpp), allocated on the first device-array plan on a batch model
+static int fault_word(mp_ctx *ctx)
+{
+    if (ctx->fault_host) return MP_OK;
+    MP_HIP(hipHostMalloc((void **)&ctx->fault_host, 64, hipHostMallocMapped));
+    *ctx->fault_host = 0;
+    MP_HIP(hipHostGetDevicePointer((void **)&ctx->fault_dev, ctx->fault_host, 0));
+    return MP_OK;
+}
+
 int globalize_roots_arg(mp_ctx *ctx, const mp_model *model, int n_roots, const int32_t *model_index, const int32_t *root_state,
                         int mem, std::vector<int32_t> &host_tmp, const int32_t **out)
 {
@@ -313,11 +369,7 @@ int globalize_roots_arg(mp_ctx *ctx, const mp_model *model, int n_roots, const i
         int32_t *d = nullptr;
         MP_HIP(hipSetDevice(ctx->device));
         MP_TRY(ws_get(ctx, WS_GROOT, (size_t)n_roots, &d));
-        if (!ctx->fault_host) {
-            MP_HIP(hipHostMalloc((void **)&ctx->fault_host, 64, hipHostMallocMapped));
-            *ctx->fault_host = 0;
-            MP_HIP(hipHostGetDevicePointer((void **)&ctx->fault_dev, ctx->fault_host, 0));
-        }
+        MP_TRY(fault_word(ctx));
         hipLaunchKernelGGL(globalize_roots, dim3((unsigned)((n_roots + 255) / 256)), dim3(256), 0, ctx->stream, n_roots, Sb,
                            model->NB > 0 ? model->NB : 1, model_index, root_state, d, ctx->fault_dev);
         MP_HIP(hipGetLastError());
@@ -331,6 +383,40 @@ int globalize_roots_arg(mp_ctx *ctx, const mp_model *model, int n_roots, const i
         if (root_state[i] < 0 || root_state[i] >= Sb)
             return fail(MP_ERR_ARG, "plan on a batch model: root_state[%d] = %d outside [0, %d)", i, root_state[i], Sb);
         host_tmp[i] = model_index[i] * Sb + root_state[i];
+    }
+    *out = host_tmp.data();
+    return MP_OK;
+}
+
+int globalize_joint_roots_arg(mp_ctx *ctx, const mp_model *model, int n_roots, const int32_t *model_index, const int32_t *root_state,
+                              int mem, std::vector<int32_t> &host_tmp, const int32_t **out)
+{
+    if (!ctx || !model || !model_index || !root_state) return fail(MP_ERR_ARG, "plan on a joint batch model: NULL argument");
+    if (model->mode != MP_MODE_DETERMINISTIC || !model->rec_all || !model->joint_batch)
+        return fail(MP_ERR_MODE, "plan on a joint batch model: needs a model of mp_model_load_joint_batch");
+    if (n_roots < 1) return fail(MP_ERR_ARG, "plan on a joint batch model: n_roots = %d", n_roots);
+    const int Sb = model->Sb, M = model->M;
+    if (mem_arrays(mem) == MP_MEM_DEVICE) {
+        int32_t *d = nullptr;
+        MP_HIP(hipSetDevice(ctx->device));
+        MP_TRY(ws_get(ctx, WS_GROOT, (size_t)n_roots * M, &d));
+        MP_TRY(fault_word(ctx));
+        hipLaunchKernelGGL(globalize_joint_roots, dim3((unsigned)((n_roots + 255) / 256)), dim3(256), 0, ctx->stream, n_roots, M, Sb,
+                           model->NB, model_index, root_state, d, ctx->fault_dev);
+        MP_HIP(hipGetLastError());
+        *out = d;
+        return MP_OK;
+    }
+    host_tmp.resize((size_t)n_roots * M);
+    for (int i = 0; i < n_roots; ++i) {
+        if (model_index[i] < 0 || model_index[i] >= model->NB)
+            return fail(MP_ERR_ARG, "plan on a joint batch model: model_index[%d] = %d outside [0, %d)", i, model_index[i], model->NB);
+        for (int m = 0; m < M; ++m) {
+            const int32_t s = root_state[(size_t)i * M + m];
+            if (s < 0 || s >= Sb)
+                return fail(MP_ERR_ARG, "plan on a joint batch model: root_state[%d][%d] = %d outside [0, %d)", i, m, s, Sb);
+            host_tmp[(size_t)i * M + m] = model_index[i] * Sb + s;
+        }
     }
     *out = host_tmp.data();
     return MP_OK;
@@ -1189,6 +1275,130 @@ int mp_model_load_joint(mp_ctx *ctx, int32_t M, int32_t S, int32_t A, const int6
     return MP_OK;
 }
 
+extern "C++" {
+namespace {
+// sets [first, first + count) of a joint batch model from the caller's [count][M][Sb][A] arrays: validated before anything is
+// touched, staged in the model's pinned block, copied to its device scratch block and packed by ONE launch (stream-ordered)
+int joint_batch_write(const char *who, mp_model *m, int32_t first, int32_t count, const int64_t *transition, const double *reward,
+                      const uint8_t *terminal)
+{
+    mp_ctx *ctx = m->ctx;
+    const int Sb = m->Sb, A = m->A, M = m->M;
+    const size_t sa = (size_t)Sb * A, n = (size_t)count * M * sa, ns = (size_t)count * M * Sb;
+    // staging = device scratch layout: T int32 [n] | R double [n] | term uint8 [ns]
+    const size_t off_r = (n * 4 + 15) & ~(size_t)15, off_term = off_r + n * 8, total = off_term + ns;
+    MP_TRY(update_blocks(m, total, total));
+    char *st = static_cast<char *>(m->upd_stage);
+    int32_t *t32 = reinterpret_cast<int32_t *>(st);
+    uint64_t bad = 0;
+    for (size_t j = 0; j < n; ++j) {
+        const uint64_t v = (uint64_t)transition[j];
+        bad |= v >= (uint64_t)Sb ? 1u : 0u;
+        t32[j] = (int32_t)v;
+    }
+    if (bad)
+        for (size_t j = 0; j < n; ++j)
+            if (transition[j] < 0 || transition[j] >= Sb)
+                return fail(MP_ERR_ARG, "%s: transition[%zu] = %lld outside [0, %d)", who, j, (long long)transition[j], Sb);
+    memcpy(st + off_r, reward, n * 8);
+    if (terminal) memcpy(st + off_term, terminal, ns);
+    hipStream_t s = ctx->stream;
+    char *dv = static_cast<char *>(m->upd_dev);
+    MP_HIP(hipMemcpyAsync(dv, st, total, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(pack_joint_range, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, first, count, M, Sb, A, (long)m->S,
+                       reinterpret_cast<const int32_t *>(dv), reinterpret_cast<const double *>(dv + off_r),
+                       terminal ? reinterpret_cast<const uint8_t *>(dv + off_term) : (const uint8_t *)nullptr,
+                       (const uint8_t *)m->avail, m->T, m->R, m->term_all, m->rec_all);
+    MP_HIP(hipGetLastError());
+    MP_HIP(hipEventRecord(m->upd_done, s));
+    m->upd_pending = true;
+    m->serial = mp::next_model_serial();
+    return MP_OK;
+}
+} // namespace
+} // extern "C++"
+
+// agents/robust/robust.py:68-71 for N agents: each one's M preprocessed models, as one joint model over the union of the state spaces
+int mp_model_load_joint_batch(mp_ctx *ctx, int32_t N, int32_t M, int32_t S, int32_t A, const int64_t *transition,
+                              const double *reward, const uint8_t *terminal, int32_t done_on_next, mp_model **out)
+{
+    if (!ctx || !out || !transition || !reward) return fail(MP_ERR_ARG, "mp_model_load_joint_batch: NULL argument");
+    if (N < 1 || M < 1 || S < 1 || A < 1) return fail(MP_ERR_ARG, "mp_model_load_joint_batch: bad shape N=%d M=%d S=%d A=%d", N, M, S, A);
+    if ((int64_t)N * S * A >= ((int64_t)1 << 31))
+        return fail(MP_ERR_ARG, "mp_model_load_joint_batch: N * S * A = %lld does not fit 31 bits", (long long)N * S * A);
+    const size_t nsa = (size_t)N * S * A;
+    // per record: Rec 16 B + transition 4 B + reward 8 B (the staging copy of a whole-model load comes on top)
+    if ((double)nsa * M * 28.0 > (double)ctx->prop.totalGlobalMem)
+        return fail(MP_ERR_ARG, "mp_model_load_joint_batch: %lld x %d records (28 bytes each) exceed the device's %zu bytes of memory",
+                    (long long)nsa, M, (size_t)ctx->prop.totalGlobalMem);
+    MP_HIP(hipSetDevice(ctx->device));
+    mp_model *m = new mp_model();
+    m->ctx = ctx; m->mode = MP_MODE_DETERMINISTIC; m->M = M; m->S = N * S; m->A = A; m->Sc = N * S; m->NB = N; m->Sb = S;
+    m->done_on_next = done_on_next ? 1 : 0; m->joint_batch = true;
+    auto bail = [&](int rc) { mp_model_free(m); return rc; };
+    if (hipMalloc(&m->T, nsa * M * sizeof(int32_t)) != hipSuccess || hipMalloc(&m->R, nsa * M * sizeof(double)) != hipSuccess ||
+        hipMalloc(&m->rec_all, nsa * M * sizeof(Rec)) != hipSuccess ||
+        (terminal && hipMalloc(&m->term_all, (size_t)M * N * S) != hipSuccess))
+        return bail(fail(MP_ERR_ALLOC, "mp_model_load_joint_batch: hipMalloc failed"));
+    m->rec = m->rec_all;   // model 0's records / flags: what the entry points that plan on ONE model of a joint model read
+    m->term = m->term_all;
+    const int rc = joint_batch_write("mp_model_load_joint_batch", m, 0, N, transition, reward, terminal);
+    if (rc != MP_OK) return bail(rc);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail(fail(MP_ERR_HIP, "mp_model_load_joint_batch: pack_joint_range failed"));
+    m->upd_pending = false;
+    *out = m;
+    return MP_OK;
+}
+
+int mp_model_update_joint_tables(mp_model *m, int32_t first, int32_t count, const int64_t *transition, const double *reward,
+                                 const uint8_t *terminal)
+{
+    if (!m || !transition || !reward) return fail(MP_ERR_ARG, "mp_model_update_joint_tables: NULL argument");
+    if (m->mode != MP_MODE_DETERMINISTIC || !m->joint_batch)
+        return fail(MP_ERR_MODE, "mp_model_update_joint_tables: models of mp_model_load_joint_batch only");
+    if (first < 0 || count < 1 || (int64_t)first + count > m->NB)
+        return fail(MP_ERR_ARG, "mp_model_update_joint_tables: sets [%d, %lld) of %d", first, (long long)first + count, m->NB);
+    if ((terminal != nullptr) != (m->term_all != nullptr))
+        return fail(MP_ERR_ARG, "mp_model_update_joint_tables: terminal flags must be given iff the model was loaded with them");
+    MP_HIP(hipSetDevice(m->ctx->device));
+    return joint_batch_write("mp_model_update_joint_tables", m, first, count, transition, reward, terminal);
+}
+
+int mp_model_set_available_joint_batch(mp_model *m, const uint8_t *available)
+{
+    if (!m || !available) return fail(MP_ERR_ARG, "mp_model_set_available_joint_batch: NULL argument");
+    if (m->mode != MP_MODE_DETERMINISTIC || !m->joint_batch)
+        return fail(MP_ERR_MODE, "mp_model_set_available_joint_batch: models of mp_model_load_joint_batch only");
+    mp_ctx *ctx = m->ctx;
+    const int Sb = m->Sb, A = m->A, M = m->M, N = m->NB;
+    const size_t sa = (size_t)Sb * A, nsa = (size_t)N * sa;
+    std::vector<uint8_t> av((size_t)M * nsa); // [N][M][Sb][A] -> the records' order [M][N * Sb][A]
+    for (int b = 0; b < N; ++b)
+        for (int k = 0; k < M; ++k) {
+            const uint8_t *src = available + ((size_t)b * M + k) * sa;
+            uint8_t *dst = av.data() + (size_t)k * nsa + (size_t)b * sa;
+            for (int s = 0; s < Sb; ++s) {
+                bool any = false;
+                for (int a = 0; a < A; ++a) { dst[(size_t)s * A + a] = src[(size_t)s * A + a] ? 1 : 0; any |= src[(size_t)s * A + a] != 0; }
+                if (!any) return fail(MP_ERR_ARG, "mp_model_set_available_joint_batch: set %d model %d state %d has no available action", b, k, s);
+            }
+        }
+    MP_HIP(hipSetDevice(ctx->device));
+    MP_HIP(hipStreamSynchronize(ctx->stream));
+    if (!m->avail && hipMalloc(&m->avail, av.size()) != hipSuccess) return fail(MP_ERR_ALLOC, "mp_model_set_available_joint_batch: hipMalloc failed");
+    MP_HIP(hipMemcpy(m->avail, av.data(), av.size(), hipMemcpyHostToDevice));
+    // (T holds global next states and term_all is indexed by global states: each model's table is an (N * Sb)-state table)
+    for (int k = 0; k < M; ++k)
+        hipLaunchKernelGGL(pack_records, dim3((unsigned)((nsa + 255) / 256)), dim3(256), 0, ctx->stream, m->S, A, m->T + k * nsa,
+                           m->R + k * nsa, m->term_all ? (const uint8_t *)(m->term_all + (size_t)k * m->S) : (const uint8_t *)nullptr,
+                           (const uint8_t *)(m->avail + (size_t)k * nsa), m->rec_all + k * nsa);
+    MP_HIP(hipGetLastError());
+    MP_HIP(hipStreamSynchronize(ctx->stream));
+    m->masked = true;
+    m->serial = mp::next_model_serial();
+    return MP_OK;
+}
+
 int mp_model_set_available(mp_model *m, const uint8_t *available)
 {
     if (!m || !available) return fail(MP_ERR_ARG, "mp_model_set_available: NULL argument");
@@ -1197,6 +1407,7 @@ int mp_model_set_available(mp_model *m, const uint8_t *available)
     const bool finite = (m->mode == MP_MODE_STOCHASTIC && m->Sc == m->S) || m->mode == MP_MODE_SPARSE;
     if (!table && !(finite && m->M == 1 && m->NB == 1))
         return fail(MP_ERR_MODE, "mp_model_set_available: deterministic tables and whole dense / sparse models only");
+    if (m->joint_batch) return fail(MP_ERR_MODE, "mp_model_set_available: a joint batch model takes mp_model_set_available_joint_batch");
     mp_ctx *ctx = m->ctx;
     const int S = m->S, A = m->A;
     for (int s = 0; s < S; ++s) {
@@ -1223,6 +1434,7 @@ int mp_model_set_available_joint(mp_model *m, const uint8_t *available)
 {
     if (!m || !available) return fail(MP_ERR_ARG, "mp_model_set_available_joint: NULL argument");
     if (m->mode != MP_MODE_DETERMINISTIC || !m->rec_all) return fail(MP_ERR_MODE, "mp_model_set_available_joint: joint models only");
+    if (m->joint_batch) return fail(MP_ERR_MODE, "mp_model_set_available_joint: a joint batch model takes mp_model_set_available_joint_batch");
     mp_ctx *ctx = m->ctx;
     const int S = m->S, A = m->A, M = m->M;
     for (long sm = 0; sm < (long)M * S; ++sm) {
@@ -1397,10 +1609,10 @@ int mp_model_free(mp_model *m)
     if (!m->borrowed) {
         if (m->P) hipFree(const_cast<double *>(m->P));
         if (m->R) hipFree(m->R);
-        if (m->term) hipFree(m->term);
+        if (m->term && m->term != m->term_all) hipFree(m->term);
     }
     if (m->T) hipFree(m->T);
-    if (m->rec) hipFree(m->rec);
+    if (m->rec && m->rec != m->rec_all) hipFree(m->rec);
     if (m->t16) hipFree(m->t16);
     if (m->r8) hipFree(m->r8);
     if (m->rdict) hipFree(m->rdict);

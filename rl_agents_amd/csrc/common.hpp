@@ -224,6 +224,9 @@ struct mp_model {
     mp::Rec *rec = nullptr;  // packed model 0, [S*A]
     mp::Rec *rec_all = nullptr;  // joint models (mp_model_load_joint): packed records of every model, [M][S*A]; rec = rec_all
     uint8_t *term_all = nullptr; // joint models: terminal flags per model, [M][S]
+    // joint batch models (mp_model_load_joint_batch): NB sets of M tables of Sb states, S = NB * Sb global states; T, R,
+    // rec_all and avail are [M][S][A], term_all [M][S]; rec and term ALIAS model 0's part of rec_all / term_all
+    bool joint_batch = false;
     uint16_t *t16 = nullptr; // model 0 as {bit15 = terminal[next], next}, [S*A]; only when S < 32768
     uint8_t *r8 = nullptr;   // model 0's rewards as indices into rdict, [S*A] (padded to 16 B); only with t16 and <= 256 distinct rewards
     double *rdict = nullptr; // the distinct reward values (bit patterns), [256]
@@ -309,6 +312,9 @@ namespace mp {
 // host arrays (validated), WS_GROOT for device arrays (one small launch on the ctx stream)
 int globalize_roots_arg(mp_ctx *ctx, const mp_model *model, int n_roots, const int32_t *model_index, const int32_t *root_state,
                         int mem, std::vector<int32_t> &host_tmp, const int32_t **out);
+// the joint form (mp_ropd_plan_models): (set, local joint state [M]) pairs of a joint batch model -> global joint states
+int globalize_joint_roots_arg(mp_ctx *ctx, const mp_model *model, int n_roots, const int32_t *model_index, const int32_t *root_state,
+                              int mem, std::vector<int32_t> &host_tmp, const int32_t **out);
 
 // side streams for the pipelined host-mode plan: `n` streams forked off the ctx stream / joined back into it
 int pipe_fork(mp_ctx *ctx, int n);

@@ -873,6 +873,21 @@ int mp_ropd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     return opd_unstage(ctx, n_roots, max_plan_len, mem, rmem, res, a.rng, a.out);
 }
 
+// one set of M models per root (robust.py:68-73 for a batch of agents): the (set, local joint state) pairs become global joint
+// states of the joint batch model, and the plan is mp_ropd_plan's -- same kernels, same recorded form
+int mp_ropd_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                        int32_t budget, double gamma, double terminal_reward, uint64_t *rng_state, int32_t max_plan_len,
+                        int32_t *plans, int32_t *plan_len, double *root_lower, double *root_upper, int64_t *env_steps,
+                        int32_t *status, int32_t mem)
+{
+    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_ropd_plan_models: unknown mem flags %d", mem);
+    std::vector<int32_t> tmp;
+    const int32_t *global = nullptr;
+    MP_TRY(globalize_joint_roots_arg(ctx, model, n_roots, model_index, root_state, mem, tmp, &global));
+    return mp_ropd_plan(ctx, model, n_roots, global, budget, gamma, terminal_reward, rng_state, max_plan_len, plans, plan_len,
+                        root_lower, root_upper, env_steps, status, mem);
+}
+
 int mp_ropd_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *action,
                         int32_t *state, int32_t *depth, double *reward, double *lower, double *upper, uint8_t *done,
                         int64_t *count, int32_t *first_child, int32_t *n_children)

@@ -101,6 +101,11 @@ SIGNATURES = {
     "mp_ropd_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_f64, c_f64, _vp, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_ropd_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_model_set_available_joint": (C.c_int, [_vp, _vp]),
+    "mp_model_load_joint_batch": (C.c_int, [_vp, c_i32, c_i32, c_i32, c_i32, _vp, _vp, _vp, c_i32, P(_vp)]),
+    "mp_model_update_joint_tables": (C.c_int, [_vp, c_i32, c_i32, _vp, _vp, _vp]),
+    "mp_model_set_available_joint_batch": (C.c_int, [_vp, _vp]),
+    "mp_ropd_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_f64, c_f64, _vp, c_i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      c_i32]),
     "mp_saopd_create": (C.c_int, [_vp, _vp, c_i32, P(_vp)]),
     "mp_saopd_free": (C.c_int, [_vp]),
     "mp_saopd_plan": (C.c_int, [_vp, _vp, _vp, c_i32, c_f64, c_f64, c_f64, c_i32, c_i32, _vp, c_i32, _vp, _vp, _vp, _vp,
@@ -701,6 +706,26 @@ class Context(object):
             model.available = av.astype(bool)
         return model
 
+    def load_joint_batch(self, transitions, rewards, terminals=None, done_rule="source", available=None):
+        """N sets of M models of one (S, A) shape (mp_model_load_joint_batch): what N robust agents that build their models
+        again before every plan hold (agents/robust/robust.py:68-71).  transitions int [N,M,S,A] (next states LOCAL to each
+        table), rewards [N,M,S,A], terminals [N,M,S] or None, available bool [N,M,S,A] or None -> a :class:`JointBatchModel`
+        (``n_models`` = N sets, ``M``, ``S_each``); :meth:`ropd_plan` takes it with ``model_index=``."""
+        t = np.ascontiguousarray(transitions, dtype=np.int64)
+        r = np.ascontiguousarray(rewards, dtype=np.float64)
+        if t.shape != r.shape or t.ndim != 4:
+            raise ValueError("transitions and rewards must both be [N, M, S, A]")
+        n, m, s, a = t.shape
+        term = None if terminals is None else np.ascontiguousarray(np.asarray(terminals).reshape(n, m, s).astype(np.uint8))
+        h = _vp()
+        _check(self._lib.mp_model_load_joint_batch(self._h, n, m, s, a, _ptr(t), _ptr(r), _ptr(term), int(done_rule == "next"),
+                                                   C.byref(h)))
+        model = JointBatchModel(self, h, MODE_DETERMINISTIC, m, n * s, a, 0)
+        model.n_models, model.S_each = n, s
+        if available is not None:
+            model.set_available(available)
+        return model
+
     def load_dense(self, transition, reward, terminal=None):
         """Dense model: transition float [S,A,S] or [M,S,A,S] (numpy -> copied; torch cuda tensor -> borrowed)."""
         on_device = hasattr(transition, "data_ptr")
@@ -1119,9 +1144,10 @@ class Context(object):
                                      _ptr(plan_len), _ptr(root_lower), _ptr(root_upper), _ptr(env_steps),
                                      _ptr(status), MP_MEM_DEVICE))
 
-    def ropd_plan(self, model, root_state, budget, gamma, terminal_reward, rng_state, max_plan_len=64):
+    def ropd_plan(self, model, root_state, budget, gamma, terminal_reward, rng_state, max_plan_len=64, model_index=None):
         """DiscreteRobustPlanner.plan for a batch of roots of a joint model; root_state int [n] (every model starts in
-        the same state) or [n, M]."""
+        the same state) or [n, M].  model_index int [n]: a joint batch model, root i plans on set model_index[i] from its
+        LOCAL joint state (mp_ropd_plan_models)."""
         rs = np.asarray(root_state, dtype=np.int32)
         if rs.ndim == 1:
             rs = np.repeat(rs[:, None], model.M, axis=1)
@@ -1134,6 +1160,13 @@ class Context(object):
         out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32),
                    root_lower=np.zeros(n, np.float64), root_upper=np.zeros(n, np.float64),
                    env_steps=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
+        if model_index is not None:
+            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
+            _check(self._lib.mp_ropd_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(budget), float(gamma),
+                                                 float(terminal_reward), _ptr(rng_state), mpl, _ptr(out["plans"]),
+                                                 _ptr(out["plan_len"]), _ptr(out["root_lower"]), _ptr(out["root_upper"]),
+                                                 _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
+            return out
         _check(self._lib.mp_ropd_plan(self._h, model._h, n, _ptr(rs), int(budget), float(gamma), float(terminal_reward),
                                       _ptr(rng_state), mpl, _ptr(out["plans"]), _ptr(out["plan_len"]),
                                       _ptr(out["root_lower"]), _ptr(out["root_upper"]), _ptr(out["env_steps"]),
@@ -1141,7 +1174,13 @@ class Context(object):
         return out
 
     def ropd_plan_device(self, model, n_roots, root_state, budget, gamma, terminal_reward, rng_state, max_plan_len,
-                         plans=None, plan_len=None, root_lower=None, root_upper=None, env_steps=None, status=None):
+                         plans=None, plan_len=None, root_lower=None, root_upper=None, env_steps=None, status=None, model_index=None):
+        if model_index is not None:
+            _check(self._lib.mp_ropd_plan_models(self._h, model._h, int(n_roots), _ptr(model_index), _ptr(root_state), int(budget),
+                                                 float(gamma), float(terminal_reward), _ptr(rng_state), int(max_plan_len), _ptr(plans),
+                                                 _ptr(plan_len), _ptr(root_lower), _ptr(root_upper), _ptr(env_steps),
+                                                 _ptr(status), MP_MEM_DEVICE))
+            return
         _check(self._lib.mp_ropd_plan(self._h, model._h, int(n_roots), _ptr(root_state), int(budget), float(gamma),
                                       float(terminal_reward), _ptr(rng_state), int(max_plan_len), _ptr(plans),
                                       _ptr(plan_len), _ptr(root_lower), _ptr(root_upper), _ptr(env_steps),
@@ -1404,6 +1443,27 @@ class Model(object):
             self.close()
         except Exception:
             pass
+
+
+class JointBatchModel(Model):
+    """N sets of M deterministic tables (mp_model_load_joint_batch): ``n_models`` sets, ``M`` models a set, ``S_each`` states a
+    table; ``S`` counts the N * S_each global states."""
+
+    def set_available(self, available):
+        """What each model's env lists in get_available_actions(): bool [N, M, S, A] (mp_model_set_available_joint_batch).
+        The flags survive :meth:`update_tables`."""
+        av = np.ascontiguousarray(np.asarray(available).reshape(self.n_models, self.M, self.S_each, self.A).astype(np.uint8))
+        _check(self.ctx._lib.mp_model_set_available_joint_batch(self._h, _ptr(av)))
+        self.available = av.astype(bool)
+
+    def update_tables(self, first, transition, reward, terminal=None):
+        """Replace sets [first, first + count) (mp_model_update_joint_tables): transition int [count,M,S,A] LOCAL next
+        states, reward [count,M,S,A], terminal [count,M,S] iff the model has terminal flags.  Stream-ordered."""
+        t = np.ascontiguousarray(transition, dtype=np.int64).reshape(-1, self.M, self.S_each, self.A)
+        r = np.ascontiguousarray(reward, dtype=np.float64).reshape(t.shape)
+        term = None if terminal is None else np.ascontiguousarray(
+            np.asarray(terminal).reshape(t.shape[0], self.M, self.S_each).astype(np.uint8))
+        _check(self.ctx._lib.mp_model_update_joint_tables(self._h, int(first), int(t.shape[0]), _ptr(t), _ptr(r), _ptr(term)))
 
 
 class StateAwarePlanners(object):

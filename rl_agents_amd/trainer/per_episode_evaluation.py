@@ -13,7 +13,8 @@ Here N environments advance in lock-step and share ONE launch per step:
                                                                                       a batch is each episode's own table)
                                        ONE batched plan, one MDP per root            (mp_vi_solve_batch + argmax /
                                                                                       mp_uct_plan_models / mp_opd_plan_models /
-                                                                                      mp_olop_plan_models / mp_brue_plan_models)
+                                                                                      mp_olop_plan_models / mp_brue_plan_models /
+                                                                                      mp_ropd_plan_models)
                                        env_i.step(action_i)                          (host: the environments are host objects)
 
 Episode i draws from the generator a sequential ``Evaluation`` would give agent i (``np_random(sim_seed + i)``,
@@ -27,7 +28,10 @@ the Boltzmann rows with numpy on the host -- the reference's distribution is num
 device restatement can be checked against -- and ``mp_policy_load`` over the batch model's global states),
 ``DeterministicPlannerAgent``, ``OLOPAgent`` (OLOP / KL-OLOP: the planner's own thresholds and initial bounds, its
 continuation and its exceptions, as ``OLOP.plan_batch``) and ``BRUEAgent`` (which draws over ALL actions, brue.py:27: its
-batch model carries neither the availability table nor the listing order, as ``BRUE.model_for`` loads it); environments: deterministic finite MDPs of one (S, A) shape, with or without restricted /
+batch model carries neither the availability table nor the listing order, as ``BRUE.model_for`` loads it) and
+``DiscreteRobustPlannerAgent`` (which builds its M candidate models again before every plan, robust.py:68-71: every episode owns a
+SET of M tables per step, held as one joint batch model -- ``mp_model_load_joint_batch`` / ``mp_model_update_joint_tables`` --
+and planned on by ``mp_ropd_plan_models``; see :meth:`PerEpisodeEvaluation._sync_joint`); environments: deterministic finite MDPs of one (S, A) shape, with or without restricted /
 re-ordered action sets (``get_available_actions``: the restriction must be the same table for every episode, as it is for
 grids of one shape -- device_model.availability_of).
 """
@@ -81,8 +85,9 @@ class PerEpisodeEvaluation(object):
         from rl_agents_amd.agents.tree_search.brue import BRUE
         from rl_agents_amd.agents.tree_search.olop import OLOP
         # (BRUE first: it subclasses OLOP; both before the fallback, which runs the optimistic deterministic planner)
+        # (the robust planner subclasses the optimistic one and plans on its JointEnv of candidate models: before the fallback too)
         self.kind = "vi" if self.vi else "brue" if isinstance(planner, BRUE) else "olop" if isinstance(planner, OLOP) else \
-            ("uct" if hasattr(planner, "prior_policy") else "opd")
+            "ropd" if getattr(planner, "plans_on_joint_env", False) else ("uct" if hasattr(planner, "prior_policy") else "opd")
         if not self.vi:
             cfg = planner.config
             if cfg.get("step_strategy", "reset") != "reset":
@@ -126,8 +131,127 @@ class PerEpisodeEvaluation(object):
         spec.version = version
         return spec, state, steps
 
+    def _extract_joint(self, i):
+        """(set or None, joint state [M]) of environment i as it is now: its M candidate models, built the way the agent builds
+        them before every plan (``preprocess_env(true_env, preprocessors)`` for each entry of ``config["models"]``,
+        robust.py:68-71).  set -- dict(t [M,S,A], r, term [M,S], masks, rule, max_steps, version) -- is None when every model's
+        MDP vouches through ``tables_version`` that its tables are the ones the batch holds for episode i."""
+        from rl_agents_amd.agents.common.factory import preprocess_env
+        env = self.envs[i]
+        models = [preprocess_env(env, preprocessors) for preprocessors in self.agent.config["models"]]
+        if not models:
+            raise TypeError("the discrete robust planner plans on a JointEnv of at least one model")
+        mdps = [device_model.finite_mdp_of(e) for e in models]
+        for mdp in mdps:
+            if mdp.mode != "deterministic":
+                raise TypeError("every model must be a deterministic finite MDP, got mode '{}'".format(mdp.mode))
+        state = [int(mdp.state) for mdp in mdps]
+        versions = []
+        for mdp in mdps:
+            v = getattr(mdp, "tables_version", None)
+            versions.append(v if isinstance(v, tuple) and v[0] is not None else None)
+        version = None if any(v is None for v in versions) else tuple(versions)
+        # JointEnv.get_available_actions (robust.py:22-25) lists list(set().union(...)) of what each model lists in its own state:
+        # the models' own listing orders are lost in the set, and the device expands the union in ascending order
+        avail = [device_model.availability_of(e, mdp) for e, mdp in zip(models, mdps)]
+        masks = [a[0] for a in avail]
+        rows = []
+        for (mask, order), mdp in zip(avail, mdps):
+            n_actions = np.asarray(mdp.reward).shape[-1]
+            seq = range(n_actions) if order is None else order
+            rows.append([int(a) for a in seq if mask is None or mask[int(mdp.state), int(a)]])
+        listed = list(set().union(*rows))
+        if listed != sorted(listed):
+            raise NotImplementedError("per-episode tables: the discrete robust planner plans on a joint environment that lists its "
+                                      "actions in ascending order, got {}".format(listed))
+        if self.model is not None and version is not None and self._versions[i] == version:
+            return None, state
+        shapes = {np.asarray(m.transition).shape for m in mdps}
+        if len(shapes) != 1:
+            raise ValueError("all models must share the state and action spaces, got tables of shapes {}".format(shapes))
+        rules = {getattr(m, "done_rule", "source") for m in mdps}
+        if len(rules) != 1:
+            raise ValueError("all models of a joint environment must share one done_rule, got {}".format(sorted(rules)))
+        limits = {device_model.env_max_steps(e) for e in models}
+        if len(limits) != 1:
+            raise ValueError("all models of a joint environment must share one max_steps, got {}".format(sorted(limits)))
+        return dict(t=np.stack([np.asarray(m.transition, dtype=np.int64) for m in mdps]),
+                    r=np.stack([np.asarray(m.reward, dtype=np.float64) for m in mdps]),
+                    term=np.stack([np.asarray(m.terminal).reshape(-1).astype(np.uint8) for m in mdps]),
+                    masks=masks, rule=rules.pop(), max_steps=limits.pop(), version=version), state
+
+    def _check_joint(self, sp, first):
+        if sp["t"].shape != first["t"].shape:
+            raise ValueError("every environment of the batch must have the same number of models, states and actions")
+        same_avail = all((a is None) == (b is None) and (a is None or (a.shape == b.shape and
+                                                                       np.asarray(a).tobytes() == np.asarray(b).tobytes()))
+                         for a, b in zip(sp["masks"], first["masks"]))
+        if not (same_avail and sp["rule"] == first["rule"] and sp["max_steps"] == first["max_steps"]):
+            raise NotImplementedError("per-episode evaluation: the episodes' environments must restrict the actions of each model "
+                                      "identically and share done_rule / max_steps")
+
+    def _sync_joint(self, live):
+        """The robust planner's :meth:`_sync_model`: the joint batch model holds one SET of M tables per episode; returns
+        (joint states [N, M], steps).  One upload is one episode's set."""
+        n = self.n
+        m = len(self.agent.config["models"])
+        states, steps = np.zeros((n, max(m, 1)), np.int32), np.zeros(n, np.int32)
+        sets = [None] * n
+        c0 = time.perf_counter()
+        for i in live:
+            sets[i], states[i] = self._extract_joint(i)
+        self.seconds["extract"] += time.perf_counter() - c0
+        if self.model is None:
+            first = self._first_spec = sets[live[0]]
+            self._tables = dict(t=np.zeros((n,) + first["t"].shape, np.int64), r=np.zeros((n,) + first["r"].shape, np.float64),
+                                term=np.zeros((n,) + first["term"].shape, np.uint8))
+            self._versions = [None] * n
+            for i in live:
+                self._check_joint(sets[i], first)
+                self._tables["t"][i], self._tables["r"][i], self._tables["term"][i] = sets[i]["t"], sets[i]["r"], sets[i]["term"]
+                self._versions[i] = sets[i]["version"]
+            available = None
+            if any(a is not None for a in first["masks"]):      # (a model whose env has no get_available_actions lists everything)
+                per_set = np.stack([np.ones(first["t"].shape[1:], dtype=bool) if a is None else np.asarray(a).astype(bool)
+                                    for a in first["masks"]])
+                available = np.broadcast_to(per_set, (n,) + per_set.shape)
+            self.model = self.ctx.load_joint_batch(self._tables["t"], self._tables["r"], self._tables["term"],
+                                                   done_rule=first["rule"], available=available)
+            self.uploads += len(live)
+            return states, steps
+        changed = []
+        tb = self._tables
+        for i in live:
+            sp = sets[i]
+            if sp is None:
+                continue
+            self._check_joint(sp, self._first_spec)
+            self._versions[i] = sp["version"]
+            # (as in _sync_model: the CONTENT decides what is sent)
+            if not (tb["t"][i].tobytes() == sp["t"].tobytes() and tb["r"][i].tobytes() == sp["r"].tobytes()
+                    and tb["term"][i].tobytes() == sp["term"].tobytes()):
+                tb["t"][i], tb["r"][i], tb["term"][i] = sp["t"], sp["r"], sp["term"]
+                changed.append(i)
+        self._send_changed(changed)
+        return states, steps
+
+    def _send_changed(self, changed):
+        """Contiguous runs of changed episodes: one mp_model_update_tables (mp_model_update_joint_tables) each."""
+        tb = self._tables
+        k = 0
+        while k < len(changed):
+            j = k
+            while j + 1 < len(changed) and changed[j + 1] == changed[j] + 1:
+                j += 1
+            lo, hi = changed[k], changed[j] + 1
+            self.model.update_tables(lo, tb["t"][lo:hi], tb["r"][lo:hi], tb["term"][lo:hi])
+            k = j + 1
+        self.uploads += len(changed)
+
     def _sync_model(self, live):
         """Bring the batch model up to date with the live episodes' environments; returns (states, steps)."""
+        if self.kind == "ropd":
+            return self._sync_joint(live)
         n = self.n
         states, steps = np.zeros(n, np.int32), np.zeros(n, np.int32)
         specs = [None] * n
@@ -170,16 +294,7 @@ class PerEpisodeEvaluation(object):
                     and tb_m.tobytes() == sp.terminal.tobytes()):
                 tb_t[...], tb_r[...], tb_m[...] = sp.transition, sp.reward, sp.terminal
                 changed.append(i)
-        # contiguous runs of changed episodes: one mp_model_update_tables each
-        k = 0
-        while k < len(changed):
-            j = k
-            while j + 1 < len(changed) and changed[j + 1] == changed[j] + 1:
-                j += 1
-            lo, hi = changed[k], changed[j] + 1
-            self.model.update_tables(lo, tb["t"][lo:hi], tb["r"][lo:hi], tb["term"][lo:hi])
-            k = j + 1
-        self.uploads += len(changed)
+        self._send_changed(changed)
         if changed and getattr(self, "_policy", None) is not None:      # fused policy records hold the old transitions
             self._policy.close()
             self._policy = None
@@ -292,6 +407,15 @@ class PerEpisodeEvaluation(object):
                 raise ValueError("zero-size array to reduction operation maximum which has no identity")
             out["plans"] = out["plans"].reshape(len(idx), 1)
             out["plan_len"] = np.ones(len(idx), np.int32)
+        elif self.kind == "ropd":
+            budget = int(cfg["budget"])
+            if cfg["gamma"] == 1 and budget >= model.A:
+                raise ZeroDivisionError("float division by zero")           # gamma ** depth / (1 - gamma), deterministic.py:53
+            # (root i: set i, the joint state of its M models; the plans are the env's action ids -- the joint env lists ascending)
+            out = self.ctx.ropd_plan(model, states[idx], budget, cfg["gamma"], cfg.get("terminal_reward", 0), rng, max_plan_len=1,
+                                     model_index=idx)
+            if (out["status"] == native.ERR_REWARD_RANGE).any():
+                raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")     # deterministic.py:46-47
         else:
             budget = int(cfg["budget"])
             if cfg["gamma"] == 1 and budget >= model.A:
