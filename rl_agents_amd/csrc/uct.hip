@@ -261,6 +261,12 @@ void uct_kernel(UctArgs p)
     // tables hold) take the IEEE division itself -- the same correctly rounded quotient the host put in the tables
     auto explore = [&](int a, int cnt1) { return cnt1 <= TE + 1 ? tpdiv[a * (TE + 2) + cnt1] : tp[a] / (double)cnt1; };
     auto inv = [&](int c) { return c <= TE ? rcp[c] : 1.0 / (double)c; };
+    // The same quotients for the register-held tree phase (AT > 0): the table entry at a CLAMPED index, read unconditionally --
+    // no test, branch or wait of its own per child, so the reads of a level go out together.  A count beyond the tables gets
+    // the division in ONE block per level / per backup, which a wave enters only in an episode where `beyond` (below) says
+    // that one of its roots can hold such a count.
+    auto explore_tab = [&](int a, int cnt1) { return tpdiv[a * (TE + 2) + min(cnt1, TE + 1)]; };
+    auto inv_tab = [&](int c) { return rcp[min(c, TE)]; };
     int32_t *path_all = reinterpret_cast<int32_t *>(lds_d + ntab); // [H + 1][waves * 64]  (not in the LDS-resident variant)
     const int ntab2 = (ntab + 1) & ~1;                             // (16-byte alignment of what follows)
     const double *rdict = lds_d + ntab2;                           // LDSR: [n_rdict] distinct rewards
@@ -398,6 +404,16 @@ void uct_kernel(UctArgs p)
         }                                                                                       \
     } while (0)
 
+    // WAVE PRIORITY of the saturated form (one-lane LDS-resident model: sixteen waves per CU, four per SIMD, each an in-order
+    // stream).  Its tree phases are chains of dependent gathers from the trees in HBM (selection: one per level; backup: a read
+    // and two stores per node below the kept levels) with little arithmetic between them; its rollouts are arithmetic on LDS.
+    // With equal priorities the SIMD serves the oldest wave first, and a wave in a tree phase waits behind its partners'
+    // rollout arithmetic before it can issue the few instructions that put its next gather in flight.  Raised priority in the
+    // tree phases starts those gathers as early as possible, and the rollouts of the other waves fill the time they take.
+    // (Plain bench runs alternating with the parent's library, eight each: priority alone 0.7836 ms per step against 0.7877,
+    // ranges overlapping; with the table quotients below 0.7796, ranges apart.  Rollouts at priority 2 instead: slower.
+    // profiles/uct_tree_phase.md.)  The other forms run one or two waves per SIMD and keep the default.
+    constexpr int TREE_PRIO = LDSR && !QD ? 2 : 0;
 #ifdef MP_PROFILE
     long long t_sel = 0, t_expd = 0, t_roll = 0, t_bak = 0, n_sel = 0, n_roll = 0;
     const long long t_all0 = clock64();
@@ -407,6 +423,7 @@ void uct_kernel(UctArgs p)
 #endif
     for (int ep = 0; ep < E; ++ep) { // mcts.py:179-184
         PROF_T(c0);
+        if constexpr (TREE_PRIO > 0) __builtin_amdgcn_s_setprio(TREE_PRIO);
         int32_t s = s0, st = st0;
         double x4[4] = {x0[0], x0[1], x0[2], x0[3]};
         int node = 0, depth = 0;
@@ -417,6 +434,11 @@ void uct_kernel(UctArgs p)
         if (!RC) PATH_PUT(0, tree.root_handle());
         int hnode = tree.root_handle(); // where `node` lives (TreeRef handle)
         int fc = RC ? tf0 : tree[0].first_child;
+        // No node's count exceeds the root's (a backup adds one to every node of a path that starts at the root; re-rooting keeps a
+        // subtree as it is), and this episode adds one: while every root of the wave has counted fewer than TE episodes, every
+        // quotient of the episode is in the tables -- fresh trees of at most TE episodes never leave them.  Wave-uniform, so what
+        // a level and a backup pay for the division is one scalar branch.
+        const bool beyond = RC && any64(tc0 >= TE);
         // ---- selection, mcts.py:143-149
         while (owner && depth < H && fc >= 0 && !terminal) {
             // MCTSNode.selection_strategy (mcts.py:275-286): value + temperature*|A|*prior/(count+1);
@@ -451,8 +473,24 @@ void uct_kernel(UctArgs p)
                         if (MK && c[a].count < 0) sc[a] = -INFINITY; // phantom slot: not a child
                     }
                 } else {
+                    double ex[AR];
 #pragma unroll
-                    for (int a = 0; a < AR; ++a) sc[a] = c[a].value + explore(a, c[a].count + 1);
+                    for (int a = 0; a < AR; ++a) ex[a] = explore_tab(a, c[a].count + 1);
+                    if (beyond) {
+                        // counts beyond the tables: the IEEE division, one child per trip (one division sequence in the code),
+                        // kept only where a lane's child needs it
+#pragma nounroll
+                        for (int b = 0; b < AR; ++b) {
+                            int cb = c[0].count;
+#pragma unroll
+                            for (int a = 1; a < AR; ++a) cb = b == a ? c[a].count : cb;
+                            const double q = tp[b] / (double)(cb + 1);
+#pragma unroll
+                            for (int a = 0; a < AR; ++a) ex[a] = (b == a && cb > TE) ? q : ex[a];
+                        }
+                    }
+#pragma unroll
+                    for (int a = 0; a < AR; ++a) sc[a] = c[a].value + ex[a];
                 }
                 double m = sc[0];
 #pragma unroll
@@ -567,6 +605,7 @@ void uct_kernel(UctArgs p)
             }
             n_nodes += A;
         }
+        if constexpr (TREE_PRIO > 0) __builtin_amdgcn_s_setprio(0);
         PROF_T(c2);
         // ---- rollout, mcts.py:156-157 / 160-177.  Two steps per trip over two generator copies (ga, gb):
         // step "a" consumes the draw in `u`, advances gb = next(ga) speculatively while its lookup is in flight
@@ -1104,49 +1143,84 @@ void uct_kernel(UctArgs p)
             g = stopped_in_a ? ga : gb; // the generator whose draw was consumed last
             st += h - depth; steps_taken += h - depth;
         }
+        if constexpr (TREE_PRIO > 0) __builtin_amdgcn_s_setprio(TREE_PRIO);
         PROF_T(c3);
         // ---- backup, mcts.py:248-265: the same return for every node on the path
-        for (int d = depth; d >= (RC ? 2 : 0); --d) {
-            int n;
-            PATH_GET(n, d);
-            if (RC && d < 2 + KEEP) {
-                double v = kv[0];
-                int cnt = kc[0];
+        auto inv_fast = [&](int c) { if constexpr (RC) return inv_tab(c); else return inv(c); };
+        if (RC && beyond) {
+            // a count of this wave may lie beyond the tables: every level of the path, the root and its child included, through
+            // ONE body with the division in it (the values and the order of operations of the table form below)
+            for (int d = depth; d >= 0; --d) {
+                int n = 0;
+                if (d >= 1) PATH_GET(n, d);
+                const int a1 = n - tree.handle(1, 0); // d == 1: which child of the root
+                double v = tv0;
+                int cnt = tc0;
+                if (d >= 2 + KEEP) {
+                    const UctNode c = tree.at(n);
+                    v = c.value; cnt = c.count;
+                } else {
 #pragma unroll
-                for (int i = 1; i < KEEP; ++i) { v = d == 2 + i ? kv[i] : v; cnt = d == 2 + i ? kc[i] : cnt; }
+                    for (int a = 0; a < AR; ++a) { v = (d == 1 && a1 == a) ? tv[a] : v; cnt = (d == 1 && a1 == a) ? tc[a] : cnt; }
+#pragma unroll
+                    for (int i = 0; i < KEEP; ++i) { v = d == 2 + i ? kv[i] : v; cnt = d == 2 + i ? kc[i] : cnt; }
+                }
                 cnt += 1;
                 v += inv(cnt) * (total - v);
-                tree.at(n).value = v;       // first_child is left alone (the node may just have been expanded)
-                tree.at(n).count = cnt;
-            } else {
-                UctNode c = tree.at(n);
-                c.count += 1;
-                c.value += inv(c.count) * (total - c.value);
-                tree.at(n).value = c.value;
-                tree.at(n).count = c.count;
+                if (d >= 2) {
+                    tree.at(n).value = v;       // first_child is left alone (the node may just have been expanded)
+                    tree.at(n).count = cnt;
+                } else if (d == 1) {
+#pragma unroll
+                    for (int a = 0; a < AR; ++a) { tv[a] = a1 == a ? v : tv[a]; tc[a] = a1 == a ? cnt : tc[a]; }
+                } else {
+                    tv0 = v; tc0 = cnt;
+                }
             }
-        }
-        if (RC) {
-            if (depth >= 1) {
+        } else {
+            for (int d = depth; d >= (RC ? 2 : 0); --d) {
                 int n;
-                PATH_GET(n, 1);
-                n -= tree.handle(1, 0); // level-1 node: which child of the root
-                double v = tv[0];
-                int cnt = tc[0];
+                PATH_GET(n, d);
+                if (RC && d < 2 + KEEP) {
+                    double v = kv[0];
+                    int cnt = kc[0];
 #pragma unroll
-                for (int a = 1; a < AR; ++a) { v = n == a ? tv[a] : v; cnt = n == a ? tc[a] : cnt; }
-                cnt += 1;
-                v += inv(cnt) * (total - v);
-#pragma unroll
-                for (int a = 0; a < AR; ++a) { tv[a] = n == a ? v : tv[a]; tc[a] = n == a ? cnt : tc[a]; }
+                    for (int i = 1; i < KEEP; ++i) { v = d == 2 + i ? kv[i] : v; cnt = d == 2 + i ? kc[i] : cnt; }
+                    cnt += 1;
+                    v += inv_fast(cnt) * (total - v);
+                    tree.at(n).value = v;       // first_child is left alone (the node may just have been expanded)
+                    tree.at(n).count = cnt;
+                } else {
+                    UctNode c = tree.at(n);
+                    c.count += 1;
+                    c.value += inv_fast(c.count) * (total - c.value);
+                    tree.at(n).value = c.value;
+                    tree.at(n).count = c.count;
+                }
             }
-            tc0 += 1;
-            tv0 += inv(tc0) * (total - tv0);
+            if (RC) {
+                if (depth >= 1) {
+                    int n;
+                    PATH_GET(n, 1);
+                    n -= tree.handle(1, 0); // level-1 node: which child of the root
+                    double v = tv[0];
+                    int cnt = tc[0];
+#pragma unroll
+                    for (int a = 1; a < AR; ++a) { v = n == a ? tv[a] : v; cnt = n == a ? tc[a] : cnt; }
+                    cnt += 1;
+                    v += inv_fast(cnt) * (total - v);
+#pragma unroll
+                    for (int a = 0; a < AR; ++a) { tv[a] = n == a ? v : tv[a]; tc[a] = n == a ? cnt : tc[a]; }
+                }
+                tc0 += 1;
+                tv0 += inv_fast(tc0) * (total - tv0);
+            }
         }
 #ifdef MP_PROFILE
         { const long long c4 = clock64(); t_sel += c1 - c0; t_expd += c2 - c1; t_roll += c3 - c2; t_bak += c4 - c3; }
 #endif
     }
+    if constexpr (TREE_PRIO > 0) __builtin_amdgcn_s_setprio(0);
 #ifdef MP_PROFILE
     if (r == 0)
         printf("uct prof wave0: total=%lld select=%lld expand=%lld rollout=%lld backup=%lld | lane0 select steps=%lld rollout steps=%lld\n",
