@@ -425,6 +425,19 @@ int mp_uct_plan_policy(mp_ctx *ctx, mp_model *model, mp_policy *policy, int32_t 
  * mp_uct_reset_tree drops the kept trees (step_by_reset, mcts.py:129-130).
  */
 int mp_uct_step_tree(mp_ctx *ctx, int32_t n_roots, const int32_t *actions, int32_t mem);
+/*
+ * The same step for a batch that changes: episodes of a lock-step evaluation end at different steps, and only the live ones
+ * plan on (abstract.py:172-206 once per live agent).  The next plan has n_new roots; new root j continues the subtree under
+ * child actions[j] of OLD root source_root[j] -- the old roots in any order, one of them for several new roots if wanted;
+ * old roots that are not named are dropped.  Serves every tree mp_uct_step_tree serves (mp_uct_plan / _policy / _models and
+ * the open-loop trees of mp_uct_plan_stochastic / _policy, stored priors included), with its rules: a root that was never
+ * expanded, or an action that is not a child (the slot of an unlisted action), starts a fresh tree; a step that arrives
+ * before the plan of the previous one descends one more level, its sources counting the previous step's roots.
+ * Host arrays: MP_ERR_ARG, with the trees untouched, for n_new < 1, a source outside [0, n_old) or a ctx without such trees
+ * (closed-loop trees among them).  MP_MEM_DEVICE (only enqueues): a source outside the old batch starts a fresh tree.
+ * Until the next plan the tree exports refuse (the buffers hold the old batch); mp_uct_reset_tree drops the selection.
+ */
+int mp_uct_step_tree_select(mp_ctx *ctx, int32_t n_new, const int32_t *source_root, const int32_t *actions, int32_t mem);
 int mp_uct_reset_tree(mp_ctx *ctx);
 /* Node capacity per root of the trees currently on this ctx (array size for mp_uct_tree_export). */
 int mp_uct_tree_capacity(mp_ctx *ctx, int32_t *cap);

@@ -59,6 +59,30 @@ int ws_reserve(mp_ctx *ctx, int slot, size_t bytes, void **out)
     return MP_OK;
 }
 
+int ws_reserve_keep(mp_ctx *ctx, int slot, size_t bytes)
+{
+    DevBuf &b = ctx->ws[slot];
+    if (bytes <= b.cap) return MP_OK;
+    const size_t want = bytes + bytes / 4 + 256;
+    void *p = nullptr;
+    if (hipMalloc(&p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(MP_ERR_ALLOC, "hipMalloc(%zu bytes) failed", want);
+    }
+    if (b.p) { // (enqueued work may still write the old block: wait, copy, free)
+        hipError_t e = hipStreamSynchronize(ctx->stream);
+        if (e == hipSuccess) e = hipMemcpy(p, b.p, b.cap, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return fail(MP_ERR_HIP, "ws_reserve_keep: %s", hipGetErrorString(e));
+        }
+        (void)hipFree(b.p);
+    }
+    b.p = p;
+    b.cap = want;
+    return MP_OK;
+}
+
 int upload_tables(mp_ctx *ctx, int kind, const std::vector<double> &tab, double **dev)
 {
     double *d = nullptr;

@@ -59,6 +59,8 @@ struct TreeMeta {
     int il = 0;          // UCT: 1 = wave-interleaved tree layout (see uct.hip TreeRef)
     long kept_bound = 0; // UCT: upper bound on the nodes a kept (re-rooted) tree can hold, see uct_plan_impl
     bool sp = false;     // stochastic UCT: the last plan used per-state policies (stored priors in the cold halves, phantom slots)
+    int n_src = 0;       // UCT, while armed by mp_uct_step_tree_select: the roots the tree buffers still hold (n_roots is already
+                         // the selection's; sources [n_roots] + room for the new sizes [n_roots] in WS_TREE7); 0 = root i continues root i
 };
 
 enum { WS_TREE0 = 0, WS_TREE1, WS_TREE2, WS_TREE3, WS_TREE4, WS_TREE5, WS_TREE6, WS_TREE7, WS_IO0, WS_IO1, WS_IO2, WS_IO3, WS_IO4,
@@ -279,6 +281,8 @@ namespace mp {
 
 // grow-only device workspace
 int ws_reserve(mp_ctx *ctx, int slot, size_t bytes, void **out);
+// the same, but a slot that has to grow keeps what it holds (ws_reserve drops it): for workspaces a pending call still reads
+int ws_reserve_keep(mp_ctx *ctx, int slot, size_t bytes);
 
 // upload `tab` to WS_TAB0 unless the same table (same kind, same bytes) is already there
 int upload_tables(mp_ctx *ctx, int kind, const std::vector<double> &tab, double **dev);
@@ -301,7 +305,21 @@ inline int mem_arrays(int mem) { return mem & 1; }
 inline int mem_rng(int mem) { return (mem & (MP_MEM_DEVICE | MP_MEM_RNG_DEVICE)) ? MP_MEM_DEVICE : MP_MEM_HOST; }
 inline bool mem_valid(int mem) { return mem >= 0 && mem <= 3; }
 
-// uct_stoch.hip: apply a pending re-rooting of the open-loop stochastic trees (mp_uct_step_tree arms it)
+// a selection (mp_uct_step_tree_select) is armed: the tree buffers hold other roots than tree.n_roots says, until the next plan
+inline bool selection_pending(const mp_ctx *ctx) { return ctx->tree.armed && ctx->tree.n_src > 0; }
+// the re-rooting of a selection wrote the new trees' sizes behind the sources in WS_TREE7: they become the sizes in WS_TREE1
+// (grown beforehand where the selection is larger than the old batch), in stream order behind the kernel that read the old ones
+inline int reroot_sizes_back(mp_ctx *ctx)
+{
+    const int n = ctx->tree.n_roots;
+    int32_t *sizes = nullptr;
+    MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n, &sizes));
+    MP_HIP(hipMemcpyAsync(sizes, (const int32_t *)ctx->ws[WS_TREE7].p + n, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->tree.n_src = 0;
+    return MP_OK;
+}
+
+// uct_stoch.hip: apply a pending re-rooting of the open-loop stochastic trees (mp_uct_step_tree / mp_uct_step_tree_select arm it)
 } // namespace mp
 int uct_stoch_reroot_now(mp_ctx *ctx, long cap_new);
 // uct_stoch.hip: the sampling thresholds ceil(cdf * 2^53) of a dense / sparse model's rows (model->thr), built once per model

@@ -1066,7 +1066,7 @@ int mp_opd_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *ro
     MP_TRY(ws_get(ctx, WS_TREE2, nn, &a.reward));
     a.leaf_global = nullptr;
     if (s.glb && !any_a) MP_TRY(ws_get(ctx, WS_TREE3, (size_t)n_roots * 64 * (s.sib ? s.Tsib : s.T), &a.leaf_global));
-    ctx->tree.kind = 2; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = s.cap; ctx->tree.K = s.K;
+    ctx->tree.kind = 2; ctx->tree.n_src = 0; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = s.cap; ctx->tree.K = s.K;
 
     const OpdResults res = {rng_state, plans, plan_len, root_lower, root_upper, env_steps, status};
     int32_t *d_rs = nullptr;

@@ -2100,19 +2100,28 @@ __global__ void uct_path_count_kernel(UctNode *trees, int root, int cap, int A, 
     out[0] = c < 0 ? -1 : c; // (count < 0: the phantom slot of an action a listed policy does not list)
 }
 
+// `source` (mp_uct_step_tree_select): new root r continues OLD root source[r] of the n_src old ones -- in any order, one source
+// for several new roots, a source outside the old batch = a fresh tree; then n_new is another array than n_old (a new root's
+// size must not overwrite an old root's before every lane has read its own).  source == nullptr: root r continues root r.
 template <int IL>
-__global__ __launch_bounds__(64) void uct_reroot_kernel(int n_roots, int A, int cap_old, int cap_new,
+__global__ __launch_bounds__(64) void uct_reroot_kernel(int n_roots, int n_src, int A, int cap_old, int cap_new,
                                                         const UctNode *__restrict__ old_trees, UctNode *__restrict__ new_trees,
-                                                        const int32_t *n_old, const int32_t *__restrict__ actions,
-                                                        int32_t *n_new) // (n_old and n_new may be the same array)
+                                                        const int32_t *n_old, const int32_t *__restrict__ source,
+                                                        const int32_t *__restrict__ actions,
+                                                        int32_t *n_new) // (n_old and n_new are the same array when source == nullptr)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_roots) return;
-    const TreeRef<IL, 0> o = tree_of<IL, 0>(const_cast<UctNode *>(old_trees), r, cap_old, A); // (generic ids: operator[])
+    const int q = source ? source[r] : r;
+    if (q < 0 || q >= n_src) {
+        n_new[r] = 0;
+        return;
+    }
+    const TreeRef<IL, 0> o = tree_of<IL, 0>(const_cast<UctNode *>(old_trees), q, cap_old, A); // (generic ids: operator[])
     const TreeRef<IL, 0> n = tree_of<IL, 0>(new_trees, r, cap_new, A);
     const int a = actions[r];
     // `if action in self.root.children` (abstract.py:201): an unlisted action has a phantom slot, not a child
-    if (n_old[r] < 1 || o[0].first_child < 0 || a < 0 || a >= A || o[o[0].first_child + a].count < 0) {
+    if (n_old[q] < 1 || o[0].first_child < 0 || a < 0 || a >= A || o[o[0].first_child + a].count < 0) {
         n_new[r] = 0;
         return;
     }
@@ -2235,23 +2244,32 @@ __global__ void policy_froll_kernel(PolBuild b) // entry (s, k) = the record of 
 
 using namespace mp;
 
-// Apply the re-rooting armed by mp_uct_step_tree: every kept tree -> the subtree under its root's child actions[i], written
-// into the other tree workspace with node stride cap_new (>= the current tree sizes); sizes are updated in place.
+// Apply the re-rooting armed by mp_uct_step_tree / mp_uct_step_tree_select: new tree i = the subtree under child actions[i] of
+// the old root it continues (root i, or root source[i] of the tree.n_src old ones), written into the other tree workspace with
+// node stride cap_new (>= the current tree sizes).  The sizes are updated in place, or -- with a selection -- written beside the
+// sources and copied over the old ones when the kernel is done with them.
 static int uct_reroot_now(mp_ctx *ctx, long cap_new)
 {
     const int n_roots = ctx->tree.n_roots, A = ctx->tree.A;
+    const bool sel = ctx->tree.n_src > 0;
+    const int n_src = sel ? ctx->tree.n_src : n_roots;
     const int old_slot = ctx->tree.buf ? WS_TREE2 : WS_TREE0, new_slot = ctx->tree.buf ? WS_TREE0 : WS_TREE2;
     UctNode *nw = nullptr;
     MP_TRY(ws_get(ctx, new_slot, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_new, A), &nw));
+    // (a selection of more roots than the old batch: the sizes' slot grows now, keeping the old sizes the kernel reads)
+    if (sel) MP_TRY(ws_reserve_keep(ctx, WS_TREE1, (size_t)n_roots * sizeof(int32_t)));
     int32_t *sizes = (int32_t *)ctx->ws[WS_TREE1].p;
     const int32_t *acts = (const int32_t *)ctx->ws[WS_TREE3].p;
+    const int32_t *src = sel ? (const int32_t *)ctx->ws[WS_TREE7].p : nullptr;
+    int32_t *sizes_new = sel ? (int32_t *)ctx->ws[WS_TREE7].p + n_roots : sizes;
     const dim3 rgrid((unsigned)((n_roots + 63) / 64));
     const UctNode *od = (const UctNode *)ctx->ws[old_slot].p;
     if (ctx->tree.il == 2)
-        hipLaunchKernelGGL(uct_reroot_kernel<2>, rgrid, dim3(64), 0, ctx->stream, n_roots, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, acts, sizes);
+        hipLaunchKernelGGL(uct_reroot_kernel<2>, rgrid, dim3(64), 0, ctx->stream, n_roots, n_src, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, src, acts, sizes_new);
     else
-        hipLaunchKernelGGL(uct_reroot_kernel<0>, rgrid, dim3(64), 0, ctx->stream, n_roots, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, acts, sizes);
+        hipLaunchKernelGGL(uct_reroot_kernel<0>, rgrid, dim3(64), 0, ctx->stream, n_roots, n_src, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, src, acts, sizes_new);
     MP_HIP(hipGetLastError());
+    if (sel) MP_TRY(reroot_sizes_back(ctx));
     ctx->tree.buf ^= 1;
     ctx->tree.cap = (int)cap_new;
     ctx->tree.armed = false;
@@ -2679,10 +2697,8 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
 
     // trees: fresh ones, or (step_strategy "subtree") the kept ones re-rooted into the other buffer with room
     // for this plan's expansions
-    int32_t *d_nn = nullptr;
-    MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &d_nn)); // per-root tree sizes (updated in place by re-rooting and planning)
+    int32_t *d_nn = nullptr; // per-root tree sizes (updated in place by re-rooting and planning)
     a.n_nodes_in = nullptr;
-    a.n_nodes_out = d_nn;
     long cap_use = cap;
     if (cont) {
         // a kept subtree only holds nodes created by the last `horizon` plans (a node at depth d survives d re-rootings
@@ -2692,16 +2708,20 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
         if (now > ctx->tree.kept_bound) ctx->tree.kept_bound = now;
         const long bound = ctx->tree.kept_bound;
         cap_use = (ctx->tree.cap < bound ? (long)ctx->tree.cap : bound) + (long)episodes * A;
-        MP_TRY(uct_reroot_now(ctx, cap_use));
+        MP_TRY(uct_reroot_now(ctx, cap_use)); // (reads the kept trees' sizes: before WS_TREE1 may grow to a larger selection)
+        MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &d_nn));
         a.tree = (UctNode *)ctx->ws[ctx->tree.buf ? WS_TREE2 : WS_TREE0].p;
         a.n_nodes_in = d_nn;
     } else {
+        MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &d_nn));
         ctx->tree.armed = false;
+        ctx->tree.n_src = 0;
         ctx->tree.buf = 0;
         ctx->tree.kept_bound = 1 + (long)horizon * episodes * A;
         ctx->tree.il = ch.tree_il;
         MP_TRY(ws_get(ctx, WS_TREE0, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_use, A), &a.tree));
     }
+    a.n_nodes_out = d_nn;
     a.cap = (int)cap_use;
     a.tree_il = ctx->tree.il;
     form_record(ctx->last_variant, uct_form_name(form));
@@ -3216,23 +3236,52 @@ int mp_policy_free(mp_policy *policy)
     return MP_OK;
 }
 
-int mp_uct_step_tree(mp_ctx *ctx, int32_t n_roots, const int32_t *actions, int32_t mem)
+// mp_uct_step_tree (source == nullptr: root i continues root i) and mp_uct_step_tree_select
+static int uct_step_tree_impl(mp_ctx *ctx, const char *who, int32_t n_new, const int32_t *source, const int32_t *actions, int32_t mem)
 {
-    if (!ctx || !actions) return fail(MP_ERR_ARG, "mp_uct_step_tree: NULL argument");
+    if (!ctx || !actions) return fail(MP_ERR_ARG, "%s: NULL argument", who);
     const bool stoch = ctx->tree.kind == 4 && ctx->tree.K == 0; // open-loop trees of mp_uct_plan_stochastic
-    if ((ctx->tree.kind != 1 && !stoch) || ctx->tree.n_roots != n_roots)
-        return fail(MP_ERR_ARG, "mp_uct_step_tree: no UCT trees of %d roots on this ctx (closed-loop trees cannot be re-used)", n_roots);
+    if ((ctx->tree.kind != 1 && !stoch) || (!source && ctx->tree.n_roots != n_new))
+        return fail(MP_ERR_ARG, "%s: no UCT trees of %d roots on this ctx (closed-loop trees cannot be re-used)", who, n_new);
+    if (n_new < 1) return fail(MP_ERR_ARG, "%s: %d roots", who, n_new);
+    const int n_old = ctx->tree.n_roots; // (with a selection pending: the roots IT selects, which the new one counts from)
+    if (source && mem == MP_MEM_HOST)
+        for (int i = 0; i < n_new; ++i)
+            if (source[i] < 0 || source[i] >= n_old)
+                return fail(MP_ERR_ARG, "%s: source_root[%d] = %d is not one of the %d roots of the last plan", who, i, source[i], n_old);
     MP_HIP(hipSetDevice(ctx->device));
+    // (room for this call's arrays first, keeping what a pending step left there: once the pending re-rooting below has run the
+    // trees have moved a level, and nothing after it may fail for want of memory)
+    MP_TRY(ws_reserve_keep(ctx, WS_TREE3, (size_t)n_new * sizeof(int32_t)));
+    if (source) MP_TRY(ws_reserve_keep(ctx, WS_TREE7, (size_t)2 * n_new * sizeof(int32_t)));
     // a second step before the next plan (receding_horizon > 1: abstract.py:70-82 steps the tree on every act) descends
     // one more level: apply the pending re-rooting now, then arm the new one
     if (ctx->tree.armed) MP_TRY(stoch ? uct_stoch_reroot_now(ctx, ctx->tree.cap) : uct_reroot_now(ctx, ctx->tree.cap));
+    const hipMemcpyKind kind = mem == MP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     int32_t *d = nullptr;
-    MP_TRY(ws_get(ctx, WS_TREE3, (size_t)n_roots, &d));
-    MP_HIP(hipMemcpyAsync(d, actions, (size_t)n_roots * sizeof(int32_t),
-                          mem == MP_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
+    MP_TRY(ws_get(ctx, WS_TREE3, (size_t)n_new, &d));
+    MP_HIP(hipMemcpyAsync(d, actions, (size_t)n_new * sizeof(int32_t), kind, ctx->stream));
+    if (source) { // [n_new] sources, then room for the [n_new] sizes the re-rooting writes
+        int32_t *ds = nullptr;
+        MP_TRY(ws_get(ctx, WS_TREE7, (size_t)2 * n_new, &ds));
+        MP_HIP(hipMemcpyAsync(ds, source, (size_t)n_new * sizeof(int32_t), kind, ctx->stream));
+    }
     if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->tree.n_src = source ? n_old : 0;
+    ctx->tree.n_roots = n_new;
     ctx->tree.armed = true;
     return MP_OK;
+}
+
+int mp_uct_step_tree(mp_ctx *ctx, int32_t n_roots, const int32_t *actions, int32_t mem)
+{
+    return uct_step_tree_impl(ctx, "mp_uct_step_tree", n_roots, nullptr, actions, mem);
+}
+
+int mp_uct_step_tree_select(mp_ctx *ctx, int32_t n_new, const int32_t *source_root, const int32_t *actions, int32_t mem)
+{
+    if (!source_root) return fail(MP_ERR_ARG, "mp_uct_step_tree_select: NULL argument");
+    return uct_step_tree_impl(ctx, "mp_uct_step_tree_select", n_new, source_root, actions, mem);
 }
 
 int mp_uct_tree_capacity(mp_ctx *ctx, int32_t *cap)
@@ -3246,7 +3295,10 @@ int mp_uct_tree_capacity(mp_ctx *ctx, int32_t *cap)
 int mp_uct_reset_tree(mp_ctx *ctx)
 {
     if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
+    // (a selection that is dropped: the trees are the last plan's; every planner that replaces them clears n_src)
+    if (selection_pending(ctx)) ctx->tree.n_roots = ctx->tree.n_src;
     ctx->tree.armed = false;
+    ctx->tree.n_src = 0;
     return MP_OK;
 }
 
@@ -3255,6 +3307,7 @@ int mp_uct_path_count(mp_ctx *ctx, int32_t root, const int32_t *actions, int32_t
     if (!ctx || !count || (n > 0 && !actions)) return fail(MP_ERR_ARG, "mp_uct_path_count: NULL argument");
     if (ctx->tree.kind != 1) return fail(MP_ERR_ARG, "mp_uct_path_count: no UCT tree on this ctx");
     if (root < 0 || root >= ctx->tree.n_roots || n < 0) return fail(MP_ERR_ARG, "mp_uct_path_count: root %d / length %d out of range", root, n);
+    if (selection_pending(ctx)) return fail(MP_ERR_ARG, "mp_uct_path_count: a selection of the trees is armed: plan (or mp_uct_reset_tree) first");
     MP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     UctNode *trees = (UctNode *)ctx->ws[ctx->tree.buf ? WS_TREE2 : WS_TREE0].p;
@@ -3278,6 +3331,7 @@ int mp_uct_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes,
     if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
     if (ctx->tree.kind != 1) return fail(MP_ERR_ARG, "mp_uct_tree_export: no UCT tree on this ctx");
     if (root < 0 || root >= ctx->tree.n_roots) return fail(MP_ERR_ARG, "mp_uct_tree_export: root %d out of range", root);
+    if (selection_pending(ctx)) return fail(MP_ERR_ARG, "mp_uct_tree_export: a selection of the trees is armed: plan (or mp_uct_reset_tree) first");
     const int tcap = ctx->tree.cap, A = ctx->tree.A;
     std::vector<UctNode> h((size_t)tcap);
     MP_HIP(hipSetDevice(ctx->device));

@@ -617,20 +617,27 @@ __global__ __launch_bounds__(64) void uct_stoch_kernel(StochArgs p)
 // the root's child `action` is re-numbered breadth-first into the other buffer (every expanded node's |A| children stay
 // contiguous).  While a node waits in the queue its `first` holds its OLD id.  A never-expanded root gives size 0.
 // old_cold != nullptr (per-state policies): the action nodes' cold halves hold their stored priors and travel with them.
-__global__ __launch_bounds__(64) void uct_stoch_reroot_kernel(int n_roots, int A, int cap_old, int cap_new,
+// `source` (mp_uct_step_tree_select): new root r continues OLD root source[r] of the n_src old ones, as uct_reroot_kernel.
+__global__ __launch_bounds__(64) void uct_stoch_reroot_kernel(int n_roots, int n_src, int A, int cap_old, int cap_new,
                                                               const SHot *__restrict__ old_hot, SHot *__restrict__ new_hot,
                                                               const SCold *__restrict__ old_cold, SCold *__restrict__ cold,
-                                                              const int32_t *n_old, const int32_t *__restrict__ actions, int32_t *n_new)
+                                                              const int32_t *n_old, const int32_t *__restrict__ source,
+                                                              const int32_t *__restrict__ actions, int32_t *n_new)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_roots) return;
-    const SHot *o = old_hot + (long)r * cap_old;
+    const int q = source ? source[r] : r;
+    if (q < 0 || q >= n_src) {
+        n_new[r] = 0;
+        return;
+    }
+    const SHot *o = old_hot + (long)q * cap_old;
     SHot *n = new_hot + (long)r * cap_new;
-    const SCold *oc = old_cold ? old_cold + (long)r * cap_old : nullptr;
+    const SCold *oc = old_cold ? old_cold + (long)q * cap_old : nullptr;
     SCold *nc = cold + (long)r * cap_new;
     const int a = actions[r];
     // `if action in self.root.children` (abstract.py:201): an unlisted action has a phantom slot, not a child
-    if (n_old[r] < 1 || o[0].first < 0 || a < 0 || a >= A || o[o[0].first + a].count < 0) {
+    if (n_old[q] < 1 || o[0].first < 0 || a < 0 || a >= A || o[o[0].first + a].count < 0) {
         n_new[r] = 0;
         return;
     }
@@ -726,6 +733,8 @@ int ensure_thresholds(mp_ctx *ctx, mp_model *model)
 int uct_stoch_reroot_now(mp_ctx *ctx, long cap_new)
 {
     const int n_roots = ctx->tree.n_roots, A = ctx->tree.A;
+    const bool sel = ctx->tree.n_src > 0; // (mp_uct_step_tree_select: see uct_reroot_now)
+    const int n_src = sel ? ctx->tree.n_src : n_roots;
     const int old_slot = ctx->tree.buf ? WS_TREE5 : WS_TREE0, new_slot = ctx->tree.buf ? WS_TREE0 : WS_TREE5;
     // (per-state policies keep stored priors in the cold halves: those alternate between two buffers like the hot ones)
     const bool sp = ctx->tree.sp;
@@ -734,12 +743,17 @@ int uct_stoch_reroot_now(mp_ctx *ctx, long cap_new)
     SCold *cold = nullptr;
     MP_TRY(ws_get(ctx, new_slot, (size_t)n_roots * cap_new, &nw));
     MP_TRY(ws_get(ctx, new_cold, (size_t)n_roots * cap_new, &cold));
+    // (a selection of more roots than the old batch: the sizes' slot grows now, keeping the old sizes the kernel reads)
+    if (sel) MP_TRY(ws_reserve_keep(ctx, WS_TREE1, (size_t)n_roots * sizeof(int32_t)));
     int32_t *sizes = (int32_t *)ctx->ws[WS_TREE1].p;
     const int32_t *acts = (const int32_t *)ctx->ws[WS_TREE3].p;
-    hipLaunchKernelGGL(uct_stoch_reroot_kernel, dim3((unsigned)((n_roots + 63) / 64)), dim3(64), 0, ctx->stream, n_roots, A,
+    const int32_t *src = sel ? (const int32_t *)ctx->ws[WS_TREE7].p : nullptr;
+    int32_t *sizes_new = sel ? (int32_t *)ctx->ws[WS_TREE7].p + n_roots : sizes;
+    hipLaunchKernelGGL(uct_stoch_reroot_kernel, dim3((unsigned)((n_roots + 63) / 64)), dim3(64), 0, ctx->stream, n_roots, n_src, A,
                        ctx->tree.cap, (int)cap_new, (const SHot *)ctx->ws[old_slot].p, nw,
-                       sp ? (const SCold *)ctx->ws[old_cold].p : (const SCold *)nullptr, cold, sizes, acts, sizes);
+                       sp ? (const SCold *)ctx->ws[old_cold].p : (const SCold *)nullptr, cold, sizes, src, acts, sizes_new);
     MP_HIP(hipGetLastError());
+    if (sel) MP_TRY(reroot_sizes_back(ctx));
     ctx->tree.buf ^= 1;
     ctx->tree.cap = (int)cap_new;
     ctx->tree.armed = false;
@@ -934,14 +948,15 @@ static int uct_stoch_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *po
     a.pol_prior = pol ? pol->prior : nullptr; a.pol_thr = pol ? pol->thr : nullptr; a.pol_mask = pol ? pol->lmask : nullptr;
     a.pol_listed = pol ? pol->listed8 : nullptr;
     a.pol_rslot = pol ? pol->rslot : nullptr; a.pol_stride = pol ? pol->stride : 0; a.temperature = temperature;
+    if (cont) MP_TRY(uct_stoch_reroot_now(ctx, cap_use)); // (reads the kept trees' sizes: before WS_TREE1 may grow to a larger selection)
     MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &a.n_nodes_out)); // per-root tree sizes (updated in place by re-rooting and planning)
     if (cont) {
-        MP_TRY(uct_stoch_reroot_now(ctx, cap_use));
         a.hot = (SHot *)ctx->ws[ctx->tree.buf ? WS_TREE5 : WS_TREE0].p;
         a.cold = (SCold *)ctx->ws[ctx->tree.sp && ctx->tree.buf ? WS_TREE6 : WS_TREE2].p;
         a.n_nodes_in = a.n_nodes_out;
     } else {
         ctx->tree.buf = 0;
+        ctx->tree.n_src = 0;
         ctx->tree.sp = pol != nullptr;
         ctx->tree.kept_bound = 1 + (long)H * E * A;
         MP_TRY(ws_get(ctx, WS_TREE0, (size_t)n_roots * cap_use, &a.hot));
@@ -1095,6 +1110,7 @@ int mp_uct_stoch_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_
     if (!ctx) return fail(MP_ERR_ARG, "ctx is NULL");
     if (ctx->tree.kind != 4) return fail(MP_ERR_ARG, "mp_uct_stoch_tree_export: no tree of mp_uct_plan_stochastic on this ctx");
     if (root < 0 || root >= ctx->tree.n_roots) return fail(MP_ERR_ARG, "mp_uct_stoch_tree_export: root %d out of range", root);
+    if (selection_pending(ctx)) return fail(MP_ERR_ARG, "mp_uct_stoch_tree_export: a selection of the trees is armed: plan (or mp_uct_reset_tree) first");
     MP_HIP(hipSetDevice(ctx->device));
     MP_HIP(hipStreamSynchronize(ctx->stream));
     int32_t n = 0;

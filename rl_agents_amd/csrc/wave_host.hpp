@@ -97,7 +97,7 @@ inline int wave_tree(mp_ctx *ctx, int kind, int n_roots, int A, long cap, size_t
     MP_TRY(ws_get(ctx, WS_TREE0, slots * cap, nodes));
     if (aux) MP_TRY(ws_get(ctx, WS_TREE1, slots * cap * aux_per_node, aux));
     MP_TRY(ws_get(ctx, WS_TREE7, (size_t)n_roots, n_nodes_out));
-    ctx->tree.kind = kind; ctx->tree.armed = false; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap;
+    ctx->tree.kind = kind; ctx->tree.armed = false; ctx->tree.n_src = 0; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap;
     ctx->tree.K = *keep ? -1 : slot0;
     return MP_OK;
 }

@@ -78,6 +78,7 @@ SIGNATURES = {
     "mp_uct_plan_policy": (C.c_int, [_vp, _vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, c_f64, _vp, c_i32, _vp, _vp,
                                      _vp, _vp, _vp, _vp, c_i32]),
     "mp_uct_step_tree": (C.c_int, [_vp, c_i32, _vp, c_i32]),
+    "mp_uct_step_tree_select": (C.c_int, [_vp, c_i32, _vp, _vp, c_i32]),
     "mp_uct_reset_tree": (C.c_int, [_vp]),
     "mp_uct_tree_capacity": (C.c_int, [_vp, P(c_i32)]),
     "mp_uct_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1069,6 +1070,24 @@ class Context(object):
             return
         a = np.ascontiguousarray(actions, dtype=np.int32).reshape(-1)
         _check(self._lib.mp_uct_step_tree(self._h, a.shape[0], _ptr(a), MP_MEM_HOST))
+
+    def uct_step_tree_select(self, source_root, actions):
+        """The same for a batch that shrinks or is re-ordered: the next plan has len(actions) roots, and root j continues the
+        subtree under child actions[j] of the LAST plan's root source_root[j] (mp_uct_step_tree_select; host arrays, or
+        contiguous int32 device tensors: only enqueues then)."""
+        if hasattr(actions, "data_ptr") or hasattr(source_root, "data_ptr"):
+            for t in (source_root, actions):    # (an int64 tensor would be read as pairs of int32 values)
+                if not (hasattr(t, "data_ptr") and str(t.dtype) == "torch.int32" and t.dim() == 1 and t.is_contiguous() and t.is_cuda):
+                    raise ValueError("source_root and actions must both be contiguous one-dimensional int32 device tensors")
+            if actions.shape[0] != source_root.shape[0]:
+                raise ValueError("source_root and actions must have one entry per new root")
+            _check(self._lib.mp_uct_step_tree_select(self._h, int(actions.shape[0]), _ptr(source_root), _ptr(actions), MP_MEM_DEVICE))
+            return
+        s = np.ascontiguousarray(source_root, dtype=np.int32).reshape(-1)
+        a = np.ascontiguousarray(actions, dtype=np.int32).reshape(-1)
+        if s.shape != a.shape:
+            raise ValueError("source_root and actions must have one entry per new root")
+        _check(self._lib.mp_uct_step_tree_select(self._h, a.shape[0], _ptr(s), _ptr(a), MP_MEM_HOST))
 
     def uct_reset_tree(self):
         _check(self._lib.mp_uct_reset_tree(self._h))

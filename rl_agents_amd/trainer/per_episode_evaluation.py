@@ -21,7 +21,10 @@ Episode i draws from the generator a sequential ``Evaluation`` would give agent 
 evaluation.py:375), continued from step to step, so the batch reproduces N sequential (environment, agent) loops action for
 action (tests/test_gpu_per_episode_eval.py) -- and the unmodified reference's, on tests/golden/per_episode.npz.
 
-Supported agents of this package: ``ValueIterationAgent``, ``MCTSAgent`` (open loop, ``step_strategy="reset"``),
+Supported agents of this package: ``ValueIterationAgent``, ``MCTSAgent`` (``step_strategy`` "reset" or "subtree": the kept
+subtrees of the live episodes are carried from plan to plan by ``mp_uct_step_tree_select``, with the counts, values, children and
+stored priors they had, as abstract.py:172-206 keeps them whatever the table has become; ``closed_loop`` with "reset" plans open
+loop and takes the first action -- the closed-loop plan's on a deterministic model),
 ``MCTSWithPriorPolicyAgent`` (round 6: the prior agent -- value iteration in the reference's own vi_prior.json -- is re-solved
 for EVERY episode's table at every step, as mcts_with_prior.py:47-54 does through ``prior_agent.act``: ``mp_vi_solve_batch``,
 the Boltzmann rows with numpy on the host -- the reference's distribution is numpy's ``exp``, whose SIMD implementation no
@@ -67,12 +70,15 @@ class PerEpisodeEvaluation(object):
     def __init__(self, envs, agent, sim_seed=0, max_steps=None):
         """``envs``: N environments exposing a deterministic finite MDP (``.mdp`` or ``to_finite_mdp()``) of one shape;
         ``agent``: an agent of this package built on ``envs[0]`` -- the template: its class and configuration are what every
-        episode's agent would be.  ``max_steps``: episode length cap (default: the env's ``max_steps``, else 100)."""
+        episode's agent would be.  ``sim_seed``: episode i's agent is seeded ``sim_seed + i`` -- or ``sim_seed[i]``, given one seed
+        per episode.  ``max_steps``: episode length cap (default: the env's ``max_steps``, else 100)."""
         self.envs, self.agent = list(envs), agent
         if not self.envs:
             raise ValueError("at least one environment")
         self.n = len(self.envs)
         self.sim_seed = sim_seed
+        if np.ndim(sim_seed) != 0 and len(sim_seed) != self.n:
+            raise ValueError("sim_seed: one seed, or one per episode ({} for {} episodes)".format(len(sim_seed), self.n))
         self.max_steps = int(max_steps or device_model.env_max_steps(self.envs[0]) or 100)
         self.vi = not hasattr(agent, "planner")
         planner = None if self.vi else agent.planner
@@ -86,15 +92,20 @@ class PerEpisodeEvaluation(object):
         from rl_agents_amd.agents.tree_search.olop import OLOP
         # (BRUE first: it subclasses OLOP; both before the fallback, which runs the optimistic deterministic planner)
         # (the robust planner subclasses the optimistic one and plans on its JointEnv of candidate models: before the fallback too)
+        self.subtree = False
         self.kind = "vi" if self.vi else "brue" if isinstance(planner, BRUE) else "olop" if isinstance(planner, OLOP) else \
             "ropd" if getattr(planner, "plans_on_joint_env", False) else ("uct" if hasattr(planner, "prior_policy") else "opd")
         if not self.vi:
             cfg = planner.config
-            if cfg.get("step_strategy", "reset") != "reset":
+            # MCTS keeps its subtrees as the reference does (abstract.py:172-206: count, value, children and stored priors of the
+            # kept nodes, whatever the table has become); closed loop WITH kept subtrees is broken in the reference itself, and the
+            # other planners' kept trees hold bounds computed on the previous table
+            self.subtree = cfg.get("step_strategy", "reset") == "subtree" and self.kind == "uct" and not cfg.get("closed_loop")
+            if cfg.get("step_strategy", "reset") != "reset" and not self.subtree:
                 raise NotImplementedError("per-episode tables: the tree of the previous step was built on the previous table; "
                                           "step_strategy must be 'reset'")
-            if self.kind == "uct" and cfg.get("closed_loop"):
-                raise NotImplementedError("per-episode tables: open-loop MCTS")
+            # (closed_loop with "reset" plans open loop and takes the first action: on a deterministic model that is the closed-loop
+            # plan's first action, MCTS.supports_device_loop)
         # MCTSWithPriorPolicyAgent: the planner's policies are the prior agent's per-state distribution (mcts_with_prior.py:31-32)
         self.with_prior = self.kind == "uct" and getattr(planner, "policy_source", None) is not None
         self.ctx = (device_model.ModelCache().ctx if self.vi else planner.models.ctx)
@@ -353,6 +364,26 @@ class PerEpisodeEvaluation(object):
             tables = restrict_and_renormalise(tables, self._available)
         return tables
 
+    def _step_kept_trees(self, live):
+        """step_strategy "subtree" for a batch whose episodes end at different steps: the live episodes' trees of the previous
+        plan, each stepped by the action its episode executed (abstract.py:172-206), become the roots of this plan, in its order
+        (mp_uct_step_tree_select).  The first step plans fresh trees.  The trees live in the context's workspaces, which every
+        planner of the process shares: the planner claims them after each plan, and a plan of another one between two steps is
+        an error here rather than a tree silently started afresh."""
+        planner = self.agent.planner
+        planner.about_to_plan()
+        if self._kept_live is None:
+            self.ctx.uct_reset_tree()
+            return
+        if not planner.owns_device_tree():
+            raise RuntimeError("per-episode tables, step_strategy 'subtree': another planner of the process has planned on this "
+                               "context since the previous step, and the kept trees are gone")
+        position = {episode: j for j, episode in enumerate(self._kept_live)}
+        source = np.asarray([position[i] for i in live], dtype=np.int32)
+        # (the executed action as the device labels it: the batch model's column order, planner.device_actions -- the plans'
+        # first entries before they were translated for the environment)
+        self.ctx.uct_step_tree_select(source, self._kept_labels[source])
+
     def _plan(self, live, states, steps):
         """First actions (environment action ids) of the live episodes + planner env steps of this plan."""
         from rl_agents_amd.agents.tree_search.mcts import policy_probabilities
@@ -364,21 +395,32 @@ class PerEpisodeEvaluation(object):
         planner = agent.planner
         cfg = planner.config
         rng = np.ascontiguousarray(self.rng[idx])
+        if self.subtree:
+            self._step_kept_trees(live)
+
+        def plan_with(policy):
+            # per-state policies.  With kept subtrees every plan, the first included, takes the kernel that STORES a node's priors
+            # and child set at expansion (mp_uct_plan_stochastic_policy; it takes deterministic tables): mp_uct_plan_policy looks
+            # both up by the state the descent is in, which is only right while table and policy stay what they were
+            roots = idx * model.S_each + states[idx]
+            if self.subtree:
+                return self.ctx.uct_plan_stochastic(model, roots, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"],
+                                                    None, None, rng, closed_loop=False, root_steps=steps[idx], max_plan_len=1,
+                                                    policy=policy)
+            return self.ctx.uct_plan(model, roots, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], None, None, rng,
+                                     root_steps=steps[idx], max_plan_len=1, policy=policy)
         if self.with_prior:
             tables = np.ascontiguousarray(self._prior_tables(live).reshape(self.n * model.S_each, model.A))
             listed = None if self._available is None else np.tile(self._available, (self.n, 1))
             model.available = self._available
             policy = self.ctx.load_policy(model, tables, tables, listed=listed)
             try:
-                out = self.ctx.uct_plan(model, idx * model.S_each + states[idx], cfg["episodes"], cfg["horizon"], cfg["gamma"],
-                                        cfg["temperature"], None, None, rng, root_steps=steps[idx], max_plan_len=1, policy=policy)
+                out = plan_with(policy)
             finally:
                 policy.close()
         elif self.kind == "uct":
             if self._available is not None:
-                out = self.ctx.uct_plan(model, idx * model.S_each + states[idx], cfg["episodes"], cfg["horizon"], cfg["gamma"],
-                                        cfg["temperature"], None, None, rng, root_steps=steps[idx], max_plan_len=1,
-                                        policy=self._uct_policy())
+                out = plan_with(self._uct_policy())
             else:
                 pp, rp = policy_probabilities(planner.prior_policy, model.A), policy_probabilities(planner.rollout_policy, model.A)
                 out = self.ctx.uct_plan(model, states[idx], cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], pp, rp,
@@ -428,6 +470,9 @@ class PerEpisodeEvaluation(object):
         if (out["plan_len"] < 1).any():
             raise Exception("The agent did not plan any action")             # evaluation.py:168-170
         first = out["plans"][:, 0].astype(np.int64)
+        if self.subtree:
+            planner.claim_device_tree()
+            self._kept_live, self._kept_labels = list(live), out["plans"][:, 0].astype(np.int32)
         order = getattr(model, "action_order", None)
         if order is not None:
             first = np.asarray(order, dtype=np.int64)[first]
@@ -441,7 +486,11 @@ class PerEpisodeEvaluation(object):
         n, T = self.n, self.max_steps
         for env in self.envs:
             env.reset()
-        self.rng = native.seed_sequence_states((), self.sim_seed, n)        # np_random(sim_seed + i), evaluation.py:375
+        if np.ndim(self.sim_seed) == 0:
+            self.rng = native.seed_sequence_states((), self.sim_seed, n)    # np_random(sim_seed + i), evaluation.py:375
+        else:                                                               # one seed per episode
+            self.rng = np.concatenate([native.seed_sequence_states((), int(seed), 1) for seed in self.sim_seed])
+        self._kept_live = self._kept_labels = None                          # (subtree: the episodes and first actions of the last plan)
         alive = np.ones(n, dtype=bool)
         returns, disc, lengths = np.zeros(n), np.zeros(n), np.zeros(n, np.int64)
         actions = np.full((n, T), -1, dtype=np.int32)
