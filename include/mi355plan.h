@@ -620,12 +620,13 @@ int mp_brue_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
 int mp_brue_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
                         int32_t budget, int32_t horizon, double gamma, const double *gpow, uint64_t *rng_state, int32_t *plans,
                         double *root_value, int64_t *env_steps, int32_t *status, int32_t mem);
-/* The form mp_olop_plan_models (planner 0) / mp_brue_plan_models (planner 1) choose for a call of this description, on the host
+/* The form mp_olop_plan_models (planner 0) / mp_brue_plan_models (planner 1) / mp_ss_plan_models (planner 2) choose for a call of this description, on the host
  * alone (no device, no ctx; the function the launch code calls).  A root of these calls reads only its own MDP -- the
  * reference's agent only its own env (olop.py:72, brue.py:24) -- so its S_each * |A| 16-byte records can sit in LDS behind the
- * kernel's own arrays (OLOP: path[horizon + 1] int32; BRUE: 16 bytes per step of the horizon; rounded up to 16 bytes).
+ * kernel's own arrays (OLOP: path[horizon + 1] int32; BRUE: 16 bytes per step of the horizon; Sparse Sampling: a frame of 64
+ * bytes per level of the horizon; rounded up to 16 bytes).
  * The LDS form is the default where it was measured faster: a workgroup of at most 160 KiB / 16 bytes (16 wavefronts stay
- * resident on a CU); OLOP at any batch size, BRUE while all its roots' workgroups are resident at once.  MP_EACH_MODEL=lds|global
+ * resident on a CU); OLOP at any batch size, BRUE and Sparse Sampling while all their roots' workgroups are resident at once.  MP_EACH_MODEL=lds|global
  * in the environment forces a form ("lds" for any table that fits the 160 KiB of a CU, and only those).
  *   out[6]: LDS bytes a workgroup of the LDS form takes (the arrays + S_each * |A| * 16), 1 if this call takes the LDS form else
  *           0, the grid = min(n_roots, cus * min(32, floor(160 KiB / those bytes))) of the LDS form, min(n_roots, cus * 32) of the
@@ -672,6 +673,25 @@ int mp_ss_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, 
 int mp_ss_geometry(int32_t n_actions, int32_t horizon, int32_t C, int32_t W, int64_t *out);
 /* The two names the plan above records for mp_last_kernel_variant, one per line (they are not part of mp_kernel_form_names). */
 const char *mp_ss_form_names(void);
+
+/* mp_ss_plan on a batch model of deterministic tables with one MDP per root (see mp_opd_plan_models / mp_brue_plan_models):
+ * model_index int32 [n_roots], root_state LOCAL; several roots may share an MDP.  Equal to SparseSampling.plan
+ * (sparse_sampling.py:21-28; the per-sample safe_deepcopy_env of :80 and the recursion of :38-51 / :71-88) of one agent per
+ * MDP, and to mp_ss_plan on that table alone, bit for bit: plans, root values, samples, generator records and every tree
+ * array.  The availability table is read as mp_ss_plan reads it: mp_model_set_available, one row per GLOBAL state.
+ * Validation, MP_MEM_HOST / MP_MEM_DEVICE and the clamp-and-count of out-of-range device arrays as mp_opd_plan_models;
+ * MP_ERR_MODE for a dense, sparse, joint or row-block model; MP_ERR_ARG under the conditions of mp_ss_plan (horizon, C, node
+ * bound).  This entry accepts batch models (mp_ss_plan itself refuses them).  Decision nodes' keys are GLOBAL states;
+ * mp_ss_tree_export serves the trees afterwards, under the same keep rule.
+ * On a table an outcome list has one entry: a frame is 64 bytes, the frames always sit in LDS and MP_SS_FRAMES is not read.
+ * Forms "ss_each_global" / "ss_each_lds" (the root's S_each * |A| records in LDS behind the frames): mp_each_form_info,
+ * planner 2. */
+int mp_ss_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                      int32_t horizon, int32_t C, double gamma, uint64_t *rng_state, int32_t *plans, double *root_value,
+                      int64_t *samples, int32_t *status, int32_t mem);
+/* The names the entry above records for mp_last_kernel_variant, one per line (part of neither mp_kernel_form_names,
+ * mp_each_form_names nor mp_ss_form_names). */
+const char *mp_ss_each_form_names(void);
 
 /* ---------------------------------------------------------------- discrete robust OPD ------- */
 /*
@@ -938,8 +958,8 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
  *                 one MDP per root (mp_olop_plan_models / mp_brue_plan_models): "olop_each_lds" / "olop_each_global",
  *                 "brue_each_lds" / "brue_each_global", then "_slots"
  *   GBOP-D        "gbopd_wave_lds", "gbopd_wave_global"
- *   Sparse        "ss_wave_lds", "ss_wave_global" (the frames of the recursion in LDS / in a global workspace)
- *   Sampling
+ *   Sparse        "ss_wave_lds", "ss_wave_global" (the frames of the recursion in LDS / in a global workspace); one MDP per root
+ *   Sampling      (mp_ss_plan_models): "ss_each_lds" / "ss_each_global"
  *   OPD           "opd_any" (more than 64 actions); "opd_lds" / "opd_ldsx" (bounds in LDS / the parent map in HBM), then "_gen"
  *                 (the main loop for arbitrary bounds), then "_chain" (the closing pass on the node array);
  *                 "opd_wide_sib" / "opd_wide_cls" (bounds in HBM, sibling / residue-class layout), then "_small" (at most two
@@ -956,7 +976,7 @@ const char *mp_last_kernel_variant(mp_ctx *ctx);
 /* Every name mp_last_kernel_variant can return, one per line, built by the functions that name the launches (host only, no
  * device): a test table that is to cover every form is compared with this list.  (Sparse Sampling's two names are listed by
  * its own mp_ss_form_names, single-model value iteration's by mp_vi_form_names, the one-MDP-per-root forms of OLOP and BRUE by
- * mp_each_form_names.) */
+ * mp_each_form_names, those of Sparse Sampling by mp_ss_each_form_names.) */
 const char *mp_kernel_form_names(void);
 /* Hardware self-test (no reference counterpart): LDS atomics of ONE wavefront instruction that hit the same address apply
  * in LANE ORDER on this device -- the state-aware OPD kernel's grouped backup relies on it (one ds_min_rtn_f64 of the group

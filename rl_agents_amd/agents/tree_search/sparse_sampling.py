@@ -22,7 +22,9 @@ logger = logging.getLogger(__name__)
 
 class SparseSampling(AbstractPlanner):
     """Sparse Sampling planner (sparse_sampling.py:11-28) for one or many roots of one finite MDP."""
-    per_episode_entry_point = None      # PerEpisodeEvaluation: the device plans on ONE model per call
+    # PerEpisodeEvaluation refuses this planner: the device plans on one MDP per root (Context.ss_plan with model_index,
+    # mp_ss_plan_models), but that loop has no kind that calls it yet
+    per_episode_entry_point = None
 
     def __init__(self, env, config=None):
         self.env = env

@@ -863,7 +863,7 @@ const char *mp_each_form_names(void)
 int mp_each_form_info(int32_t planner, int32_t S_each, int32_t A, int32_t horizon, int32_t n_roots, int32_t cus, int64_t *out)
 {
     if (!out) return mp::fail(MP_ERR_ARG, "mp_each_form_info: NULL output");
-    if ((planner != mp::EACH_OLOP && planner != mp::EACH_BRUE) || S_each < 1 || A < 1 || horizon < 0 || n_roots < 1 || cus < 1)
+    if ((planner != mp::EACH_OLOP && planner != mp::EACH_BRUE && planner != mp::EACH_SS) || S_each < 1 || A < 1 || horizon < 0 || n_roots < 1 || cus < 1)
         return mp::fail(MP_ERR_ARG, "mp_each_form_info: bad arguments");
     const mp::EachForm f = mp::each_form(planner, S_each, A, horizon, n_roots, cus);
     out[0] = (int64_t)f.lds_need; out[1] = f.lds ? 1 : 0; out[2] = f.grid; out[3] = (int64_t)f.lds_bytes();

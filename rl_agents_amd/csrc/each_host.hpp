@@ -1,10 +1,10 @@
-// each_host.hpp -- OLOP and BRUE on a batch model with one MDP per root (mp_olop_plan_models / mp_brue_plan_models): the ONE
-// host function that picks the kernel form, its grid and its LDS bytes.  The launch code (olop.hip, brue.hip) and
-// mp_each_form_info (api.hip, no device) call the same function, as opd_shape / mp_uct_choose_form do for their planners.
+// each_host.hpp -- OLOP, BRUE and Sparse Sampling on a batch model with one MDP per root (mp_olop_plan_models /
+// mp_brue_plan_models / mp_ss_plan_models): the ONE host function that picks the kernel form, its grid and its LDS bytes.  The
+// launch code (olop.hip, brue.hip, sparse_sampling.hip) and mp_each_form_info (api.hip, no device) call the same function, as opd_shape / mp_uct_choose_form do for their planners.
 //
 // A root of such a call only ever reads ITS MDP's S_each * |A| records.  The "lds" form copies them into the workgroup's LDS
 // behind the arrays the kernel already keeps there and serves every model read of the root from LDS; the "global" form is the
-// kernel of mp_olop_plan / mp_brue_plan on the batch model's global states.
+// kernel of mp_olop_plan / mp_brue_plan / mp_ss_plan on the batch model's global states.
 //   MP_EACH_MODEL=lds|global   forces a form where it fits ("lds" is ignored for a table that does not fit LDS)
 #pragma once
 #include <stdlib.h>
@@ -14,7 +14,7 @@
 
 namespace mp {
 
-enum { EACH_OLOP = 0, EACH_BRUE = 1 };
+enum { EACH_OLOP = 0, EACH_BRUE = 1, EACH_SS = 2 };
 
 // Where the LDS form is the DEFAULT: only where it was measured to beat the global form by more than the spread between
 // repeated medians (tools/micro_each.py -> profiles/each_model_ab.json; the highway shape, 120 states x
@@ -22,12 +22,17 @@ enum { EACH_OLOP = 0, EACH_BRUE = 1 };
 //   * a workgroup of at most kLdsBytes / 16 bytes, the footprint measured: 16 wavefronts stay resident on a CU.  A larger table
 //     leaves fewer, and its copy costs more than the few hundred records a plan reads of it: not measured, not the default;
 //   * OLOP at every batch size (0.3 - 6.6 % faster); BRUE (0.7 - 3.3 %) only while every root's workgroup is resident at once --
-//     at 65 536 roots, where the LDS form halves the resident wavefronts, the difference was inside the spread.
+//     at 65 536 roots, where the LDS form halves the resident wavefronts, the difference was inside the spread;
+//   * Sparse Sampling (tools/micro_ss_each.py -> profiles/ss_each_ab.json; horizon 3, C 3) as BRUE: 2.2 % faster at 1
+//     and 256 roots and 4.4 % at 4 096 = 256 CUs x 16, each beyond the spread (0.2 % / 3.3 % of the time); at 65 536 roots, where
+//     a workgroup of 9 792 bytes leaves 16 wavefronts resident on a CU against the global form's 32, it was 0.3 % SLOWER.
+//     (Smaller tables take the LDS form by the same rule; only this footprint was measured.)
 // MP_EACH_MODEL=lds takes the LDS form for any table that fits the CU's LDS.
 constexpr size_t kEachLdsDefaultBytes = kLdsBytes / 16;
 
 struct EachForm {
-    size_t arrays;   // bytes of the kernel's own LDS arrays (OLOP: path[L + 1] int32, BRUE: rew[H] f64 + po[H] int2), 16-byte rounded
+    size_t arrays;   // bytes of the kernel's own LDS arrays (OLOP: path[L + 1] int32, BRUE: rew[H] f64 + po[H] int2, Sparse
+                     // Sampling: H frames of 64 bytes), 16-byte rounded
     size_t lds_need; // arrays + S_each * |A| * 16: what a workgroup of the LDS form takes
     bool lds;        // the form of this call
     int grid;        // workgroups launched (one wavefront each): what is resident, at most n_roots
@@ -36,7 +41,8 @@ struct EachForm {
 
 inline size_t each_kernel_arrays(int planner, int horizon)
 {
-    const size_t raw = planner == EACH_OLOP ? (size_t)(horizon + 1) * sizeof(int32_t) : (size_t)horizon * (sizeof(double) + 2 * sizeof(int32_t));
+    const size_t raw = planner == EACH_OLOP ? (size_t)(horizon + 1) * sizeof(int32_t)
+                     : planner == EACH_BRUE ? (size_t)horizon * (sizeof(double) + 2 * sizeof(int32_t)) : (size_t)horizon * 64;
     return (raw + 15) & ~(size_t)15;
 }
 
@@ -47,6 +53,7 @@ inline EachForm each_form(int planner, int S_each, int A, int horizon, int n_roo
     f.lds_need = f.arrays + (size_t)S_each * A * sizeof(Rec);
     const bool fits = f.lds_need <= kLdsBytes;
     const long lds_per_cu = fits ? (long)(kLdsBytes / f.lds_need < 32 ? kLdsBytes / f.lds_need : 32) : 0;
+    // (BRUE, Sparse Sampling: only while every root's workgroup is resident at once)
     f.lds = fits && f.lds_need <= kEachLdsDefaultBytes && (planner == EACH_OLOP || (long)n_roots <= (long)cus * lds_per_cu);
     if (const char *force = getenv("MP_EACH_MODEL")) {
         if (!strcmp(force, "lds")) f.lds = fits;
@@ -57,7 +64,7 @@ inline EachForm each_form(int planner, int S_each, int A, int horizon, int n_roo
     return f;
 }
 
-// the global form whatever the table and the knob: the launch of mp_olop_plan / mp_brue_plan themselves
+// the global form whatever the table and the knob: the launch of mp_olop_plan / mp_brue_plan / mp_ss_plan themselves
 inline EachForm each_form_global(int planner, int horizon, int n_roots, int cus)
 {
     EachForm f;

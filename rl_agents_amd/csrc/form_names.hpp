@@ -104,6 +104,17 @@ inline std::string each_form_names()
     return out;
 }
 
+// Sparse Sampling on a batch model with one MDP per root (mp_ss_plan_models, each_host.hpp): the root's table in LDS or read from
+// global memory (the trees have no `_slots` form: every root's is kept, or root 0's alone).  Listed by mp_ss_each_form_names --
+// mp_each_form_names and mp_ss_form_names are pinned name for name by the tests of the planners they cover.
+inline FormName ss_each_form_name(bool lds)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "ss_each_%s", lds ? "lds" : "global");
+    return n;
+}
+inline std::string ss_each_form_names() { return std::string(ss_each_form_name(true).s) + "\n" + ss_each_form_name(false).s + "\n"; }
+
 // ---- single-model value iteration (vi.hip: mp_vi_solve, mp_vi_solve_v, mp_vi_solve_v_robust, mp_vi_sweeps, mp_vi_backup):
 // the form of the launch that produced the returned values.  Reported by mp_last_kernel_variant after a call and listed by
 // mp_vi_form_names -- NOT by all_form_names below, as for Sparse Sampling.

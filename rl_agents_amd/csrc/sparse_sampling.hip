@@ -24,6 +24,10 @@
 // node's outcome list (state, count; the children's node ids are consecutive).  The tree is a write-only log in global memory
 // in creation order (the reference's order of dict insertion) whose only fix-up is the store of `value` when a node's
 // recursion returns.  Two forms: the frames in LDS (ss_wave_lds) or in a global workspace (ss_wave_global).
+// mp_ss_plan_models -- a batch model of deterministic tables, one MDP per root: a batch of agents that each hold their own
+// environment -- runs the same kernel with the frames always in LDS (64 bytes a level) and the root's records read from the
+// batch model (ss_each_global) or from a copy of the root's own table in LDS behind the frames (ss_each_lds); each_host.hpp
+// picks.
 // `done` is never read (:81); `gamma` enters as one multiplication per chance node: + * / on f64 and integer counts in the
 // reference's order, results are bit-exact.
 #include <math.h>
@@ -33,9 +37,11 @@
 #include <vector>
 
 #include "common.hpp"
+#include "each_host.hpp"
 #include "opd_closing.hpp"
 #include "pcg64.hpp"
 #include "seed_sequence.hpp"
+#include "wave.hpp"
 #include "wave_host.hpp"
 
 namespace mp {
@@ -82,6 +88,7 @@ struct SsArgs {
     int32_t *plans, *status;
     double *root_value;
     int64_t *samples;
+    int Sb;                  // one MDP per root: states per MDP of the batch model (a root's MDP starts at global state (s / Sb) * Sb)
 };
 
 __host__ __device__ inline size_t ss_frame_stride(int L) { return sizeof(SsFrame) + (size_t)L * sizeof(int2); }
@@ -202,19 +209,42 @@ __device__ __forceinline__ int ss_nth_listed(const uint8_t *avail, int s, int A,
     return a;
 }
 
-template <bool LDSF>
+// EACH (mp_ss_plan_models: a batch model of deterministic tables, one MDP per root, the roots' states GLOBAL).  W = 1 on a table:
+// an outcome list has one entry, a frame is 64 bytes and the frames always sit in LDS.  SS_EACH_GLOBAL reads the batch model's
+// records as SS_WHOLE reads a single model's; SS_EACH_LDS copies the root's own Sb * |A| records into LDS behind the frames --
+// once for consecutive roots of a workgroup that share an MDP -- and serves every model read of the root from there, the
+// parallel reads of the one-pass last level included.  SS_WHOLE is the kernel of mp_ss_plan, as it was.
+enum { SS_WHOLE = 0, SS_EACH_GLOBAL = 1, SS_EACH_LDS = 2 };
+constexpr size_t kSsEachFrame = 64;                // sizeof(SsFrame) + one int2 list entry
+
+template <bool LDSF, int EACH>
 __global__ __launch_bounds__(64) void ss_kernel(SsArgs p)
 {
     extern __shared__ __attribute__((aligned(16))) char ss_smem[];
+    constexpr bool each = EACH != SS_WHOLE;
+    static_assert(!each || LDSF, "the frames of the one-MDP-per-root forms sit in LDS");
     const int lane = threadIdx.x, A = p.A, H = p.H, C = p.C;
-    const size_t fstride = ss_frame_stride(p.L);
+    const size_t fstride = each ? kSsEachFrame : ss_frame_stride(p.L);
     char *const fbase = LDSF ? ss_smem : p.frames + (size_t)blockIdx.x * H * fstride;
+    Rec *const lrec = reinterpret_cast<Rec *>(ss_smem + (size_t)H * kSsEachFrame);   // [Sb * A] SS_EACH_LDS: the root's table
     const double gamma = p.gamma;
+    int mdp_base = 0, loaded = -1;                                 // SS_EACH_LDS: first global state of the root's MDP / of the MDP in LDS
+    // record (s, a), s a GLOBAL state.  SS_EACH_LDS: at (s - mdp_base) * |A| + a of the copy; s is the root's state or the `next` of
+    // one of this MDP's records, which the batch model's load-time validation keeps inside the MDP: s - mdp_base is in [0, Sb)
+    auto rec_at = [&](long sa) -> const Rec & { return EACH == SS_EACH_LDS ? lrec[sa - (long)mdp_base * A] : p.rec[sa]; };
     for (int root = blockIdx.x; root < p.n_roots; root += p.grid) {
         const bool log = p.keep || root == 0;
         SsNode *const N = p.nodes + (p.keep ? (long)root * p.cap : 0);
         double *const rootq = p.rootq + (long)root * A;
         const int s_root = p.root_state[root];
+        if constexpr (EACH == SS_EACH_LDS) {                       // (the previous root's reads ended at the barrier closing its iteration)
+            mdp_base = s_root / p.Sb * p.Sb;
+            if (mdp_base != loaded) {
+                wave_lds_records(lrec, p.rec, mdp_base, A, p.Sb, lane);
+                loaded = mdp_base;
+                __syncthreads();
+            }
+        }
         if (log && lane == 0) {                                    // DecisionNode(parent=None), sparse_sampling.py:19
             SsNode r;
             r.value = 0.0; r.parent = -1; r.key = -1; r.count = 0; r.depthc = 0;
@@ -245,7 +275,10 @@ __global__ __launch_bounds__(64) void ss_kernel(SsArgs p)
                     const int m = total - base < 64 ? total - base : 64;
                     const int t = base + lane;
                     int sn = -1;
-                    if (lane < m) sn = ss_sample(p, gen, lane, (long)state * A + ss_nth_listed(p.avail, state, A, t / C));
+                    if (lane < m) {
+                        const long sa = (long)state * A + ss_nth_listed(p.avail, state, A, t / C);
+                        if constexpr (each) sn = rec_at(sa).next; else sn = ss_sample(p, gen, lane, sa);
+                    }
                     ss_skip(p, gen, m);
                     for (int slot = base / C; slot * C < base + m && !bad; ++slot) {
                         a = ss_nth_listed(p.avail, state, A, slot);
@@ -257,7 +290,7 @@ __global__ __launch_bounds__(64) void ss_kernel(SsArgs p)
                         bad = !ss_list_add(list, n_out, p.L, t >= slot * C && t < (slot + 1) * C && lane < m, sn, lane);
                         if (bad || (slot + 1) * C > base + m) continue;   // (the action's samples go on in the next chunk)
                         if (n_nodes + n_out > p.cap) { bad = true; break; }
-                        const double r = p.mode == MP_MODE_DETERMINISTIC ? p.rec[(long)state * A + a].reward : p.R[(long)state * A + a];
+                        const double r = each || p.mode == MP_MODE_DETERMINISTIC ? rec_at((long)state * A + a).reward : p.R[(long)state * A + a];
                         q = r + gamma * 0.0 / (double)C;           // the children hold the int 0 (:45-46, :87-88)
                         if (log) {
                             if (lane == 0) {
@@ -290,8 +323,8 @@ __global__ __launch_bounds__(64) void ss_kernel(SsArgs p)
                 // ---- ChanceNode.estimateQ (:76-84): C samples, 64 at a time
                 const long sa = (long)state * A + a;
                 n_out = 0;
-                if (p.mode == MP_MODE_DETERMINISTIC) {
-                    const Rec rc = p.rec[sa];
+                if (each || p.mode == MP_MODE_DETERMINISTIC) {
+                    const Rec rc = rec_at(sa);
                     reward = rc.reward;
                     if (lane == 0) list[0] = make_int2(rc.next, C);
                     n_out = 1;
@@ -302,7 +335,7 @@ __global__ __launch_bounds__(64) void ss_kernel(SsArgs p)
                 for (int base = 0; base < C && !full; base += 64) {
                     const int m = C - base < 64 ? C - base : 64;
                     int sn = -1;
-                    if (p.mode != MP_MODE_DETERMINISTIC && lane < m) sn = ss_sample(p, gen, lane, sa);
+                    if (!each && p.mode != MP_MODE_DETERMINISTIC && lane < m) sn = ss_sample(p, gen, lane, sa);
                     ss_skip(p, gen, m);
                     full = !ss_list_add(list, n_out, p.L, sn >= 0, sn, lane);
                 }
@@ -472,20 +505,32 @@ const char *mp_ss_form_names(void)
     return names.c_str();
 }
 
-int mp_ss_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t horizon, int32_t C, double gamma,
-               uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *samples, int32_t *status, int32_t mem)
+const char *mp_ss_each_form_names(void)
 {
-    if (!ctx || !model || !root_state || !rng_state) return fail(MP_ERR_ARG, "mp_ss_plan: NULL argument");
+    static const std::string names = ss_each_form_names();
+    return names.c_str();
+}
+
+extern "C++" {
+namespace {
+// mp_ss_plan (each = false: `root_state` holds states of the one model) and mp_ss_plan_models (each = true: a batch model of
+// deterministic tables; it holds the GLOBAL states globalize_roots_arg made of the (model_index, local state) pairs, the frames
+// sit in LDS and the form is each_form's)
+int ss_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t horizon, int32_t C, double gamma,
+                 uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *samples, int32_t *status, int32_t mem, bool each)
+{
+    const char *const who = each ? "mp_ss_plan_models" : "mp_ss_plan";
+    if (!ctx || !model || !root_state || !rng_state) return fail(MP_ERR_ARG, "%s: NULL argument", who);
     int rmem;
-    MP_TRY(wave_mem("mp_ss_plan", &mem, &rmem));
-    MP_TRY(wave_mdp_check("mp_ss_plan", model, false));
+    MP_TRY(wave_mem(who, &mem, &rmem));
+    MP_TRY(wave_mdp_check(who, model, each));
     const int A = model->A;
-    if (n_roots < 1 || A < 1) return fail(MP_ERR_ARG, "mp_ss_plan: bad sizes");
+    if (n_roots < 1 || A < 1) return fail(MP_ERR_ARG, "%s: bad sizes", who);
     // (horizon 0: the root gets no child and the reference's selection raises; C 0: its backup reads a reward no sample set)
     if (horizon < 1 || horizon > kSsMaxHorizon)
-        return fail(MP_ERR_ARG, "mp_ss_plan: horizon %d: the frames serve 1 <= horizon <= %d", horizon, kSsMaxHorizon);
-    if (C < 1 || C > kSsMaxC) return fail(MP_ERR_ARG, "mp_ss_plan: C %d: the frames serve 1 <= C <= %d samples", C, kSsMaxC);
-    MP_TRY(wave_roots(ctx, "mp_ss_plan", root_state, n_roots, model->S, mem));
+        return fail(MP_ERR_ARG, "%s: horizon %d: the frames serve 1 <= horizon <= %d", who, horizon, kSsMaxHorizon);
+    if (C < 1 || C > kSsMaxC) return fail(MP_ERR_ARG, "%s: C %d: the frames serve 1 <= C <= %d samples", who, C, kSsMaxC);
+    MP_TRY(wave_roots(ctx, who, root_state, n_roots, model->S, mem));
     SsArgs a;
     MP_TRY(wave_mdp(ctx, model, &a));
     int W = 1;
@@ -494,22 +539,25 @@ int mp_ss_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *roo
     a.L = C < W ? C : W;
     const int64_t bound = ss_node_bound(A, horizon, a.L);
     if (bound < 0)
-        return fail(MP_ERR_ARG, "mp_ss_plan: a tree of %d actions, horizon %d and %d outcomes a sample set does not fit int32 node indices",
+        return fail(MP_ERR_ARG, "%s: a tree of %d actions, horizon %d and %d outcomes a sample set does not fit int32 node indices", who,
                     A, horizon, a.L);
     const size_t per_tree = (size_t)bound * sizeof(SsNode);
-    if (per_tree > kSsKeepBytes) return fail(MP_ERR_ARG, "mp_ss_plan: a tree of up to %ld nodes does not fit the workspace", (long)bound);
+    if (per_tree > kSsKeepBytes) return fail(MP_ERR_ARG, "%s: a tree of up to %ld nodes does not fit the workspace", who, (long)bound);
     size_t keep_bytes = kSsKeepBytes;
     if (const char *e = getenv("MP_SS_KEEP_BYTES")) { // test knob: a smaller workspace (never a larger one)
         const long long v = atoll(e);
         if (v >= 0 && (size_t)v < keep_bytes) keep_bytes = (size_t)v;
     }
-    const long waves = (long)ctx->prop.multiProcessorCount * 32;
-    a.grid = (int)(n_roots < waves ? n_roots : waves);
+    // (the global form is the launch mp_ss_plan always made: CUs * 32 wavefronts at most)
+    const int cus = ctx->prop.multiProcessorCount;
+    a.Sb = model->Sb > 0 ? model->Sb : model->S;
+    const EachForm form = each ? each_form(EACH_SS, a.Sb, A, horizon, n_roots, cus) : each_form_global(EACH_SS, horizon, n_roots, cus);
+    a.grid = form.grid;
     a.n_roots = n_roots; a.A = A; a.H = horizon; a.C = C; a.cap = (int)bound; a.gamma = gamma;
     a.avail = model->masked ? model->avail : nullptr;
     MP_TRY(ss_jump_table(ctx, &a.jump));
     const size_t frame_bytes = (size_t)horizon * ss_frame_stride(a.L);
-    const bool use_lds = ss_use_lds(frame_bytes);
+    const bool use_lds = each || ss_use_lds(frame_bytes);              // (one MDP per root: W = 1, at most 1 KiB of frames)
     a.frames = nullptr;
     if (!use_lds) MP_TRY(ws_get(ctx, WS_TREE2, (size_t)a.grid * frame_bytes, &a.frames));
     MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots * A, &a.rootq)); // (not a per-slot array here)
@@ -520,8 +568,32 @@ int mp_ss_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *roo
     io.add(WS_IO7, status, &a.status);
     io.add(WS_IO8, samples, &a.samples);
     MP_TRY(wave_stage(ctx, io));
-    MP_TRY(wave_launch(ctx, use_lds ? ss_kernel<true> : ss_kernel<false>, a.grid, use_lds ? frame_bytes : 0, ss_form_name(use_lds), a));
+    if (each)
+        MP_TRY(wave_launch(ctx, form.lds ? ss_kernel<true, SS_EACH_LDS> : ss_kernel<true, SS_EACH_GLOBAL>, a.grid, form.lds_bytes(),
+                           ss_each_form_name(form.lds), a));
+    else
+        MP_TRY(wave_launch(ctx, use_lds ? ss_kernel<true, SS_WHOLE> : ss_kernel<false, SS_WHOLE>, a.grid, use_lds ? frame_bytes : 0,
+                           ss_form_name(use_lds), a));
     return wave_unstage(ctx, io);
+}
+} // namespace
+} // extern "C++"
+
+int mp_ss_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t horizon, int32_t C, double gamma,
+               uint64_t *rng_state, int32_t *plans, double *root_value, int64_t *samples, int32_t *status, int32_t mem)
+{
+    return ss_plan_impl(ctx, model, n_roots, root_state, horizon, C, gamma, rng_state, plans, root_value, samples, status, mem, false);
+}
+
+int mp_ss_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                      int32_t horizon, int32_t C, double gamma, uint64_t *rng_state, int32_t *plans, double *root_value,
+                      int64_t *samples, int32_t *status, int32_t mem)
+{
+    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_ss_plan_models: unknown mem flags %d", mem);
+    std::vector<int32_t> tmp;
+    const int32_t *global = nullptr;
+    MP_TRY(globalize_roots_arg(ctx, model, n_roots, model_index, root_state, mem, tmp, &global));
+    return ss_plan_impl(ctx, model, n_roots, global, horizon, C, gamma, rng_state, plans, root_value, samples, status, mem, true);
 }
 
 int mp_ss_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, int32_t *parent, int32_t *key, uint8_t *is_chance,

@@ -133,6 +133,8 @@ SIGNATURES = {
     "mp_ss_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_ss_geometry": (C.c_int, [c_i32, c_i32, c_i32, c_i32, _vp]),
     "mp_ss_form_names": (C.c_char_p, []),
+    "mp_ss_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_ss_each_form_names": (C.c_char_p, []),
     "mp_uct_choose_form": (C.c_int, [_vp, _vp, P(C.c_char_p)]),
     "mp_last_kernel_ms": (C.c_int, [_vp, P(c_f64), P(c_i32)]),
     "mp_last_kernel_variant": (C.c_char_p, [_vp]),
@@ -318,14 +320,14 @@ def each_form_names():
     return load().mp_each_form_names().decode().split()
 
 
-EACH_PLANNERS = {"olop": 0, "brue": 1}
+EACH_PLANNERS = {"olop": 0, "brue": 1, "ss": 2}
 
 
 def each_form_info(planner, s_each, n_actions, horizon, n_roots, cus=256):
-    """The form ``olop_plan`` / ``brue_plan`` with ``model_index`` take for a call of this description (mp_each_form_info; host
+    """The form ``olop_plan`` / ``brue_plan`` / ``ss_plan`` with ``model_index`` take for a call of this description (mp_each_form_info; host
     only, MP_EACH_MODEL is read): dict(lds_bytes = what a workgroup of the LDS form takes, lds = the call takes it, grid,
     launch_lds_bytes, default_limit = the most bytes that take the LDS form by default, fit_limit = the most that fit a compute
-    unit's LDS and can be forced).  ``planner``: "olop" or "brue"."""
+    unit's LDS and can be forced).  ``planner``: "olop", "brue" or "ss"."""
     out = np.zeros(6, np.int64)
     _check(load().mp_each_form_info(EACH_PLANNERS[planner], int(s_each), int(n_actions), int(horizon), int(n_roots), int(cus),
                                     _ptr(out)))
@@ -337,6 +339,12 @@ def ss_form_names():
     """The names a Sparse Sampling plan records for Context.last_kernel_variant() (mp_ss_form_names; host only).  They are
     not part of kernel_form_names()."""
     return load().mp_ss_form_names().decode().split()
+
+
+def ss_each_form_names():
+    """The names a Sparse Sampling plan on one MDP per root (``ss_plan`` with ``model_index``) records for
+    Context.last_kernel_variant() (mp_ss_each_form_names; host only).  They are part of no other list of names."""
+    return load().mp_ss_each_form_names().decode().split()
 
 
 def ss_geometry(n_actions, horizon, C, W):
@@ -1294,9 +1302,10 @@ class Context(object):
                                              _ptr(t["is_chance"]), _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["stat"])))
         return {k: v[:n.value].copy() for k, v in t.items()}
 
-    def ss_plan(self, model, root_state, horizon, C, gamma, rng_state):
+    def ss_plan(self, model, root_state, horizon, C, gamma, rng_state, model_index=None):
         """SparseSampling.plan for a batch of roots (host arrays): mp_ss_plan.  ``plans`` [n]: the one planned action per
-        root (a column of the model); ``samples`` [n]: model steps taken."""
+        root (a column of the model); ``samples`` [n]: model steps taken.  ``model_index`` int [n]: a batch model with one
+        MDP per root, ``root_state`` local (mp_ss_plan_models)."""
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
         n = rs.shape[0]
         if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
@@ -1304,6 +1313,12 @@ class Context(object):
             raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
         out = dict(plans=np.full(n, -1, np.int32), root_value=np.zeros(n, np.float64), samples=np.zeros(n, np.int64),
                    status=np.zeros(n, np.int32))
+        if model_index is not None:
+            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
+            _check(self._lib.mp_ss_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(horizon), int(C), float(gamma),
+                                               _ptr(rng_state), _ptr(out["plans"]), _ptr(out["root_value"]), _ptr(out["samples"]),
+                                               _ptr(out["status"]), MP_MEM_HOST))
+            return out
         _check(self._lib.mp_ss_plan(self._h, model._h, n, _ptr(rs), int(horizon), int(C), float(gamma), _ptr(rng_state),
                                     _ptr(out["plans"]), _ptr(out["root_value"]), _ptr(out["samples"]), _ptr(out["status"]),
                                     MP_MEM_HOST))

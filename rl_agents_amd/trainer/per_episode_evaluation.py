@@ -86,8 +86,8 @@ class PerEpisodeEvaluation(object):
             raise NotImplementedError("per-episode tables: {} keeps its planner state (graph, bounds, state values) from plan to "
                                       "plan, and a kept state was built on the previous step's table".format(type(planner).__name__))
         if getattr(planner, "per_episode_entry_point", True) is None:
-            raise NotImplementedError("per-episode tables: {} has no entry point that plans a batch on one model per episode, "
-                                      "and this loop would run the optimistic planner in its place".format(type(planner).__name__))
+            raise NotImplementedError("per-episode tables: this loop has no kind that plans {} on one model per episode, "
+                                      "and would run the optimistic planner in its place".format(type(planner).__name__))
         from rl_agents_amd.agents.tree_search.brue import BRUE
         from rl_agents_amd.agents.tree_search.olop import OLOP
         # (BRUE first: it subclasses OLOP; both before the fallback, which runs the optimistic deterministic planner)
