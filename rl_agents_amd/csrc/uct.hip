@@ -26,7 +26,11 @@
 //           in HBM; the A children of a node are contiguous.  cap = 1 + episodes*A (+ the kept tree).
 //           The root and its children (ids 0..A) live in registers for the whole plan, and the path
 //           nodes of depths 2..5 keep the statistics their selection read until the backup: the
-//           saturated kernel is bound by L2/HBM requests, and these remove a third of them.
+//           saturated kernel is bound by L2/HBM requests, and these remove a third of them.  A node below them is written ONCE per
+//           episode: the backup stores value and count in one 12-byte store, and the leaf whole (16 bytes) with the first_child
+//           its expansion assigned -- no store of its own for that.  The forms that gather the model from global memory write
+//           the zero nodes of a wave's expansions lane-contiguously (the group-interleaved layout: one run per group and wave)
+//           instead of |A| strided nodes per lane (uct_kernel, TREE STORES; profiles/uct_tree_stores.md).
 //   path    per-lane stack of visited node ids in LDS ([depth][lane], conflict-free): the backup
 //           walks known addresses, not parent pointers.
 #include <limits.h>
@@ -102,6 +106,8 @@ struct UctArgs {
     int lanes; // roots per wavefront (64 = dense; fewer spreads a small batch over more SIMDs)
     int rep_shift; // CartPole: a root is replicated over 2^rep_shift lanes (see the launch code: wavefronts of few ACTIVE lanes run slow)
     int waves; // wavefronts per workgroup
+    int tree_stores; // 1: a full wave writes its expansions' zero nodes lane-contiguously and the backup stores the leaf whole;
+                     // 0 (MP_UCT_TREE_STORES=lane, an A/B knob): every store per lane, first_child of an expanded node on its own
     int Sb;    // batch models: states per MDP (root r plans on MDP root_state[r] / Sb); = S for any other model
     const Rec *rec;
     const uint16_t *t16; // compact transitions (LDS variants), [S*A]
@@ -309,6 +315,29 @@ void uct_kernel(UctArgs p)
     if (slot >= p.lanes || r >= p.n_roots) return;   // (QD: whole quads leave together)
     static_assert(IL != 2 || AT > 0, "the group-interleaved layout needs |A| at compile time");
     const TreeRef<IL, AT> tree = tree_of<IL, AT>(p.tree, r, p.cap, A);
+    // TREE STORES.  Layout 2 puts group g of a wave's 64 roots in ONE run of 64 x |A| nodes, and every slot of a new group gets the
+    // same constant {0.0, 0, -1}: a lane that writes its own |A| nodes makes |A| stores at an |A| x 16 B stride, each lane of each a
+    // line request of its own (320 for 40 lines of data at |A| = 5).  WEXP: the WAVE writes the run instead, lane j of store i the
+    // element i * 64 + j (TreeRef::handle transposed), masked to the slots whose owner lane expands at that group -- the same bytes
+    // as before in |A| coalesced stores (the expansion below).  Only for a wave whose 64 lanes are 64 consecutive live roots
+    // (wave_exp: wave-uniform); a tail wave, fewer roots per wave, phantom counts (MK), root-major trees and CartPole keep the
+    // per-lane stores.  LEAF1: an expanded node below the root's children gets its first_child with the 16-byte
+    // store of its statistics in the backup that follows (it is the first node the backup writes) instead of a 4-byte store of its
+    // own at the expansion.  p.tree_stores == 0 (MP_UCT_TREE_STORES=lane) runs the per-lane forms of both: for A/B runs.
+    // Which instantiations take part (profiles/uct_tree_stores.md): the wave's stores cost four to six VGPRs, which |A| >= 6 does
+    // not have (the gather form would lose its fourth wave per SIMD), and they are for the forms that gather the model from global
+    // memory, where they measure 3-5 % -- in the LDS-resident forms, whose env steps make no memory request, they measured as
+    // nothing beside the leaf's store, and those keep the per-lane stores.  The leaf's first_child is one more value alive over
+    // the rollout, and the LDS-resident form of |A| >= 7 already spills without it.
+    constexpr bool WEXP = IL == 2 && AT > 0 && AT <= 5 && !MK && !LDSR && !CART;
+    constexpr int WEXP_PASSES = 4;   // wave-wide passes per expansion, one per distinct tree size (fresh trees: 2-4 sizes per wave)
+    constexpr bool LEAF1 = AT > 0 && !(LDSR && !QD && AT >= 7);
+    const bool leaf1 = LEAF1 && p.tree_stores != 0;
+    bool wave_exp = false;
+    if constexpr (WEXP) {
+        const int wave_r0 = (blockIdx.x * p.waves + __builtin_amdgcn_readfirstlane(wave)) * 64;
+        wave_exp = p.tree_stores != 0 && p.lanes == 64 && wave_r0 + 64 <= p.n_roots;
+    }
     const Rec *__restrict__ rec = p.rec;
     Pcg64 g;
     g.load(p.rng + (long)r * 6);
@@ -406,7 +435,7 @@ void uct_kernel(UctArgs p)
 
     // WAVE PRIORITY of the saturated form (one-lane LDS-resident model: sixteen waves per CU, four per SIMD, each an in-order
     // stream).  Its tree phases are chains of dependent gathers from the trees in HBM (selection: one per level; backup: a read
-    // and two stores per node below the kept levels) with little arithmetic between them; its rollouts are arithmetic on LDS.
+    // and one store per node below the kept levels) with little arithmetic between them; its rollouts are arithmetic on LDS.
     // With equal priorities the SIMD serves the oldest wave first, and a wave in a tree phase waits behind its partners'
     // rollout arithmetic before it can issue the few instructions that put its next gather in flight.  Raised priority in the
     // tree phases starts those gathers as early as possible, and the rollouts of the other waves fill the time they take.
@@ -573,6 +602,7 @@ void uct_kernel(UctArgs p)
         }
         PROF_T(c1);
         // ---- expansion, mcts.py:151-154 / 237-246
+        bool wexp_pend = false; // WEXP: the new group of this lane is still to be written
         if (owner && fc < 0 && depth < H && (!terminal || node == 0)) {
             UctNode n;
             n.value = 0.0; n.count = 0; n.first_child = -1;
@@ -580,9 +610,10 @@ void uct_kernel(UctArgs p)
                 if (node == 0) tf0 = n_nodes;
 #pragma unroll
                 for (int a = 0; a < AR; ++a) tf[a] = node == 1 + a ? n_nodes : tf[a];
-            } else {
+            } else if (!leaf1) {
                 tree.at(hnode).first_child = n_nodes;
             }
+            if (LEAF1) fc = n_nodes; // first_child of the leaf, for the backup's store of it (unchanged where nothing expands)
             if (MK) {
                 if (node == 0) {
 #pragma unroll
@@ -595,15 +626,56 @@ void uct_kernel(UctArgs p)
                     }
                 }
             } else if (!(RC && node == 0)) { // the root's children were zero-initialised in registers
-                UctNode *grp = &tree.child(n_nodes, 0);
-                if (AT > 0) {
-#pragma unroll
-                    for (int a = 0; a < AR; ++a) tree.sibling(grp, a) = n;
+                if constexpr (WEXP) {
+                    wexp_pend = true;
                 } else {
-                    for (int a = 0; a < A; ++a) tree.sibling(grp, a) = n;
+                    UctNode *grp = &tree.child(n_nodes, 0);
+                    if (AT > 0) {
+#pragma unroll
+                        for (int a = 0; a < AR; ++a) tree.sibling(grp, a) = n;
+                    } else {
+                        for (int a = 0; a < A; ++a) tree.sibling(grp, a) = n;
+                    }
                 }
             }
             n_nodes += A;
+        }
+        if constexpr (WEXP) {
+            // the new groups, outside the divergent test.  A wave-wide pass per distinct tree size v among the expanding lanes: the
+            // lanes M that expand at v own the slots [l |A|, (l + 1) |A|) of the run of group v, and lane j writes element
+            // e = i * 64 + j in store i if its owner e / |A| is in M -- no other lane's group is touched, and the 64-block is
+            // allocated whole.  Kept trees can hold 64 sizes: after WEXP_PASSES passes the remaining lanes write their own group.
+            UctNode n;
+            n.value = 0.0; n.count = 0; n.first_child = -1;
+            const int grp_id = n_nodes - AT; // (of a lane that expanded: the first id of its new group)
+            if (wave_exp) {
+                unsigned long long rem = ballot64(wexp_pend);
+                for (int pass = 0; pass < WEXP_PASSES && rem != 0ull; ++pass) {
+                    const int v = __builtin_amdgcn_readlane(grp_id, __ffsll((long long)rem) - 1);
+                    const bool mine = wexp_pend && grp_id == v;
+                    const unsigned long long M = ballot64(mine);
+                    const uint32_t m_lo = (uint32_t)M, m_hi = (uint32_t)(M >> 32);
+                    // (the lane's number from the count of lanes below it: `lane` itself need not stay in a register for this)
+                    const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+                    UctNode *run = tree.base - ln * AT + (unsigned)((v - 1 + AT) << 6); // (r & 63 == lane in a full wave)
+#pragma nounroll
+                    for (int i = 0; i < AT; ++i) {
+                        const unsigned e = (unsigned)(i * 64 + ln), q = e / (unsigned)AT;
+                        if ((((q & 32u) ? m_hi : m_lo) >> (q & 31u)) & 1u) run[e] = n;
+                    }
+                    wexp_pend = wexp_pend && !mine;
+                    rem &= ~M;
+                }
+                // A group is read back by its owner lane, not by the lanes that stored it.  Both are lanes of ONE wave, whose vector-
+                // memory operations reach the L1 in issue order, and no other wave reads these bytes during the kernel: what is needed
+                // is that the compiler keeps the order -- a release at wavefront scope (no instruction).
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            }
+            if (wexp_pend) {
+                UctNode *grp = &tree.child(grp_id, 0);
+#pragma unroll
+                for (int a = 0; a < AR; ++a) tree.sibling(grp, a) = n;
+            }
         }
         if constexpr (TREE_PRIO > 0) __builtin_amdgcn_s_setprio(0);
         PROF_T(c2);
@@ -1147,6 +1219,22 @@ void uct_kernel(UctArgs p)
         PROF_T(c3);
         // ---- backup, mcts.py:248-265: the same return for every node on the path
         auto inv_fast = [&](int c) { if constexpr (RC) return inv_tab(c); else return inv(c); };
+        // the new statistics of a path node below the root's children: value and count as ONE 12-byte store, first_child left alone
+        // -- but the LEAF (leaf1: the first node a backup writes) whole, with the first_child the expansion gave it (`fc`; that of
+        // the descent's last read where nothing expanded)
+        typedef uint32_t stat3 __attribute__((ext_vector_type(3), may_alias));
+        auto put_stats = [&](int n, double v, int cnt, bool leaf) {
+            if (LEAF1 && leaf) {
+                UctNode w;
+                w.value = v; w.count = cnt; w.first_child = fc;
+                tree.at(n) = w;
+            } else {
+                stat3 w;
+                w.x = (uint32_t)__double2loint(v); w.y = (uint32_t)__double2hiint(v); w.z = (uint32_t)cnt;
+                *reinterpret_cast<stat3 *>(&tree.at(n)) = w;
+            }
+        };
+        bool leaf = leaf1; // (uniform over the lanes of a trip: every lane's first)
         if (RC && beyond) {
             // a count of this wave may lie beyond the tables: every level of the path, the root and its child included, through
             // ONE body with the division in it (the values and the order of operations of the table form below)
@@ -1168,14 +1256,14 @@ void uct_kernel(UctArgs p)
                 cnt += 1;
                 v += inv(cnt) * (total - v);
                 if (d >= 2) {
-                    tree.at(n).value = v;       // first_child is left alone (the node may just have been expanded)
-                    tree.at(n).count = cnt;
+                    put_stats(n, v, cnt, leaf);
                 } else if (d == 1) {
 #pragma unroll
                     for (int a = 0; a < AR; ++a) { tv[a] = a1 == a ? v : tv[a]; tc[a] = a1 == a ? cnt : tc[a]; }
                 } else {
                     tv0 = v; tc0 = cnt;
                 }
+                leaf = false;
             }
         } else {
             for (int d = depth; d >= (RC ? 2 : 0); --d) {
@@ -1188,15 +1276,19 @@ void uct_kernel(UctArgs p)
                     for (int i = 1; i < KEEP; ++i) { v = d == 2 + i ? kv[i] : v; cnt = d == 2 + i ? kc[i] : cnt; }
                     cnt += 1;
                     v += inv_fast(cnt) * (total - v);
-                    tree.at(n).value = v;       // first_child is left alone (the node may just have been expanded)
-                    tree.at(n).count = cnt;
+                    put_stats(n, v, cnt, leaf);
                 } else {
                     UctNode c = tree.at(n);
                     c.count += 1;
                     c.value += inv_fast(c.count) * (total - c.value);
-                    tree.at(n).value = c.value;
-                    tree.at(n).count = c.count;
+                    if constexpr (RC) {
+                        put_stats(n, c.value, c.count, leaf);
+                    } else {
+                        tree.at(n).value = c.value;
+                        tree.at(n).count = c.count;
+                    }
                 }
+                leaf = false;
             }
             if (RC) {
                 if (depth >= 1) {
@@ -2292,6 +2384,7 @@ struct UctKnobs {
     int row_waves, row_roots, lanes, cart_rep, cart_waves;   // MP_UCT_ROW_WAVES / ROW_ROOTS / LANES / CART_REP / CART_WAVES
     int path;         // MP_UCT_PATH: 1 "spill" (the register / global path stack, a test hook), 0 any other value
     long ldsr_waves;  // MP_UCT_LDSR_WAVES (LONG_MIN: not set)
+    int tree_stores;  // MP_UCT_TREE_STORES: 0 "lane" (the per-lane tree stores of uct_kernel, for A/B runs), 1 any other value or unset
 };
 static int uct_knob(const char *name)
 {
@@ -2311,6 +2404,8 @@ static UctKnobs uct_knobs_read()
     if (k.lone_waves != kUnset && k.lone_waves != 1 && k.lone_waves != 2 && k.lone_waves != 4 && k.lone_waves != 8) k.lone_waves = 0;
     k.row_waves = uct_knob("MP_UCT_ROW_WAVES"); k.row_roots = uct_knob("MP_UCT_ROW_ROOTS"); k.lanes = uct_knob("MP_UCT_LANES");
     k.cart_rep = uct_knob("MP_UCT_CART_REP"); k.cart_waves = uct_knob("MP_UCT_CART_WAVES");
+    const char *tree_stores = getenv("MP_UCT_TREE_STORES");
+    k.tree_stores = !(tree_stores && !strcmp(tree_stores, "lane"));
     return k;
 }
 
@@ -2663,7 +2758,9 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
     call.kept_il = cont ? ctx->tree.il : -1;
     call.cus = ctx->prop.multiProcessorCount;
     UctChoice ch;
-    MP_TRY(uct_choose(call, uct_knobs_read(), &ch));
+    const UctKnobs knobs = uct_knobs_read();
+    MP_TRY(uct_choose(call, knobs, &ch));
+    a.tree_stores = knobs.tree_stores;   // (how uct_kernel issues its tree stores: neither the form nor its name)
     const UctForm form = ch.form;
     a.Sb = model->NB > 1 && model->Sb > 0 ? model->Sb : model->S;
     a.jump = nullptr;
