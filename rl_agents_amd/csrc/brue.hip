@@ -345,7 +345,7 @@ int brue_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t 
     const long cap = 1 + 2 * ((long)budget + horizon);
     if (cap * A > (1L << 30)) return fail(MP_ERR_ARG, "mp_brue_plan: %ld nodes of %d actions per tree", cap, A);
     BrueArgs a;
-    MP_TRY(wave_mdp(ctx, model, &a));
+    MP_TRY(wave_mdp(ctx, "mp_brue_plan", model, &a));
 
     std::vector<double> tab(gpow, gpow + horizon + 1);             // gamma ** d, the host's Python `**`
     double *d_tab = nullptr;

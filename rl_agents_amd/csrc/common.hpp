@@ -323,7 +323,7 @@ inline int reroot_sizes_back(mp_ctx *ctx)
 } // namespace mp
 int uct_stoch_reroot_now(mp_ctx *ctx, long cap_new);
 // uct_stoch.hip: the sampling thresholds ceil(cdf * 2^53) of a dense / sparse model's rows (model->thr), built once per model
-int ensure_thresholds(mp_ctx *ctx, mp_model *model);
+int ensure_thresholds(mp_ctx *ctx, const char *who, mp_model *model);
 namespace mp {
 
 // (model_index, local root state) pairs of a batch model -> global root states for the planners: `host_tmp` backs *out for

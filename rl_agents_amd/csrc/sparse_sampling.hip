@@ -532,7 +532,7 @@ int ss_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     if (C < 1 || C > kSsMaxC) return fail(MP_ERR_ARG, "%s: C %d: the frames serve 1 <= C <= %d samples", who, C, kSsMaxC);
     MP_TRY(wave_roots(ctx, who, root_state, n_roots, model->S, mem));
     SsArgs a;
-    MP_TRY(wave_mdp(ctx, model, &a));
+    MP_TRY(wave_mdp(ctx, who, model, &a));
     int W = 1;
     MP_TRY(ss_outdegree(ctx, model, &W));
 

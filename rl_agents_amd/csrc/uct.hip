@@ -47,6 +47,7 @@
 #include "common.hpp"
 #include "libm_sincos.hpp"
 #include "pcg64.hpp"
+#include "uct_host.hpp"
 #include "wave.hpp"
 
 namespace mp {
@@ -2336,36 +2337,19 @@ __global__ void policy_froll_kernel(PolBuild b) // entry (s, k) = the record of 
 
 using namespace mp;
 
-// Apply the re-rooting armed by mp_uct_step_tree / mp_uct_step_tree_select: new tree i = the subtree under child actions[i] of
-// the old root it continues (root i, or root source[i] of the tree.n_src old ones), written into the other tree workspace with
-// node stride cap_new (>= the current tree sizes).  The sizes are updated in place, or -- with a selection -- written beside the
-// sources and copied over the old ones when the kernel is done with them.
+// Apply the re-rooting armed by mp_uct_step_tree / mp_uct_step_tree_select (reroot_apply) to the trees of the last mp_uct_plan,
+// into the other tree workspace with node stride cap_new.
 static int uct_reroot_now(mp_ctx *ctx, long cap_new)
 {
-    const int n_roots = ctx->tree.n_roots, A = ctx->tree.A;
-    const bool sel = ctx->tree.n_src > 0;
-    const int n_src = sel ? ctx->tree.n_src : n_roots;
+    const int n_roots = ctx->tree.n_roots;
     const int old_slot = ctx->tree.buf ? WS_TREE2 : WS_TREE0, new_slot = ctx->tree.buf ? WS_TREE0 : WS_TREE2;
     UctNode *nw = nullptr;
-    MP_TRY(ws_get(ctx, new_slot, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_new, A), &nw));
-    // (a selection of more roots than the old batch: the sizes' slot grows now, keeping the old sizes the kernel reads)
-    if (sel) MP_TRY(ws_reserve_keep(ctx, WS_TREE1, (size_t)n_roots * sizeof(int32_t)));
-    int32_t *sizes = (int32_t *)ctx->ws[WS_TREE1].p;
-    const int32_t *acts = (const int32_t *)ctx->ws[WS_TREE3].p;
-    const int32_t *src = sel ? (const int32_t *)ctx->ws[WS_TREE7].p : nullptr;
-    int32_t *sizes_new = sel ? (int32_t *)ctx->ws[WS_TREE7].p + n_roots : sizes;
-    const dim3 rgrid((unsigned)((n_roots + 63) / 64));
-    const UctNode *od = (const UctNode *)ctx->ws[old_slot].p;
-    if (ctx->tree.il == 2)
-        hipLaunchKernelGGL(uct_reroot_kernel<2>, rgrid, dim3(64), 0, ctx->stream, n_roots, n_src, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, src, acts, sizes_new);
-    else
-        hipLaunchKernelGGL(uct_reroot_kernel<0>, rgrid, dim3(64), 0, ctx->stream, n_roots, n_src, A, ctx->tree.cap, (int)cap_new, od, nw, sizes, src, acts, sizes_new);
-    MP_HIP(hipGetLastError());
-    if (sel) MP_TRY(reroot_sizes_back(ctx));
-    ctx->tree.buf ^= 1;
-    ctx->tree.cap = (int)cap_new;
-    ctx->tree.armed = false;
-    return MP_OK;
+    MP_TRY(ws_get(ctx, new_slot, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_new, ctx->tree.A), &nw));
+    return reroot_apply(ctx, cap_new, [&](const Reroot &r) {
+        hipLaunchKernelGGL(ctx->tree.il == 2 ? uct_reroot_kernel<2> : uct_reroot_kernel<0>, dim3((unsigned)((r.n_roots + 63) / 64)), dim3(64), 0,
+                           ctx->stream, r.n_roots, r.n_src, r.A, r.cap_old, r.cap_new, (const UctNode *)ctx->ws[old_slot].p, nw, r.sizes, r.src,
+                           r.acts, r.sizes_new);
+    });
 }
 
 // ---- which kernel form a plan takes, and its geometry: a pure host function of the call's shape, the model's and the
@@ -2643,13 +2627,21 @@ static int uct_launch(const UctChoice &ch, bool listed, const UctArgs &a, hipStr
     return fail(MP_ERR_ARG, "mp_uct_plan: no %s kernel for |A| = %d in tree layout %d", uct_form_name(ch.form).c_str(), a.A, a.tree_il);
 }
 
-static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int32_t n_roots, const void *root_state,
-                         const int32_t *root_steps, int32_t episodes, int32_t horizon, double gamma, double temperature,
-                         const double *prior_p, const double *rollout_p, uint64_t *rng_state, int32_t max_plan_len,
-                         int32_t *plans, int32_t *plan_len, double *root_value, int64_t *root_child_count,
-                         double *root_child_value, int64_t *env_steps, int32_t mem)
+// the kernel of a form for this |A|: the unrolled forms for 2..8 actions, the loop form beyond
+static int uct_dispatch(const UctChoice &ch, bool listed, const UctArgs &a, hipStream_t st)
 {
-    if (!ctx || !model || !root_state || !rng_state || (!pol && (!prior_p || !rollout_p)))
+    static int (*const launch[8])(const UctChoice &, bool, const UctArgs &, hipStream_t) = {
+        uct_launch<2>, uct_launch<3>, uct_launch<4>, uct_launch<5>, uct_launch<6>, uct_launch<7>, uct_launch<8>, uct_launch<0>};
+    return launch[a.A >= 2 && a.A <= 8 ? a.A - 2 : 7](ch, listed, a, st);
+}
+
+// ---- the steps of a plan call, in the order uct_plan_impl takes them
+
+static int uct_check(const mp_ctx *ctx, const UctPlan &c)
+{
+    const mp_model *model = c.model;
+    const mp_policy *pol = c.pol;
+    if (!ctx || !model || !c.root_state || !c.rng_state || (!pol && (!c.prior_p || !c.rollout_p)))
         return fail(MP_ERR_ARG, "mp_uct_plan: NULL argument");
     const bool cart = model->mode == MP_MODE_CARTPOLE;
     if (pol && !cart && pol->model == model && pol->model_serial == model->serial && pol->ctx == ctx && !pol->frec && pol->A > 8)
@@ -2662,292 +2654,231 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
     if (model->masked && !(pol && pol->listed))
         return fail(MP_ERR_ARG, "mp_uct_plan: the model restricts its action sets (mp_model_set_available): MCTS reads "
                                 "availability through its policies -- plan with a policy from mp_policy_load_listed");
-    if (n_roots < 1 || episodes < 0 || horizon < 0 || max_plan_len < 0)
-        return fail(MP_ERR_ARG, "mp_uct_plan: bad sizes (n_roots=%d episodes=%d horizon=%d)", n_roots, episodes, horizon);
-    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_uct_plan: unknown mem flags %d", mem);
-    const int A = model->A, H = horizon, E = episodes;
-    MP_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const long cap = 1 + (long)episodes * A;
+    if (c.n_roots < 1 || c.episodes < 0 || c.horizon < 0 || c.max_plan_len < 0)
+        return fail(MP_ERR_ARG, "mp_uct_plan: bad sizes (n_roots=%d episodes=%d horizon=%d)", c.n_roots, c.episodes, c.horizon);
+    if (!mem_valid(c.mem)) return fail(MP_ERR_ARG, "mp_uct_plan: unknown mem flags %d", c.mem);
+    return MP_OK;
+}
 
-    // small per-call tables, computed on the host exactly as Python computes them
-    // (the quotient tables live in LDS: 16 KB of them at most; counts beyond take the division in the kernel)
-    const int te_max = (int)(16384 / (sizeof(double) * (size_t)(A + 1)));
-    const int TE = E < te_max ? E : te_max;
-    const size_t ntab = (size_t)(H + 1) + 2 * (size_t)A + (TE + 1) + (size_t)A * (TE + 2);
-    std::vector<double> tab(ntab);
-    double *gpow = tab.data(), *cdf = gpow + (H + 1), *tpv = cdf + A, *rcp = tpv + A, *tpdiv = rcp + (TE + 1);
-    for (int h = 0; h <= H; ++h) gpow[h] = pow(gamma, (double)h);                 // gamma ** h
-    double acc = 0.0;
-    for (int a = 0; a < A; ++a) { acc += pol ? 1.0 : rollout_p[a]; cdf[a] = acc; } // numpy cumsum
-    for (int a = 0; a < A; ++a) cdf[a] /= acc;                                     // cdf /= cdf[-1]
-    for (int a = 0; a < A; ++a) {
-        // Generator.choice(p=...): idx = searchsorted(cdf, u, 'right') with u = k * 2^-53, k < 2^53 integer;
-        // cdf[a] <= u  <=>  ceil(cdf[a] * 2^53) <= k  (the scaling by 2^53 is exact)
-        const double scaled = ceil(ldexp(cdf[a], 53));
-        const uint64_t t = scaled >= 18446744073709551615.0 ? ~0ULL : (uint64_t)scaled;
-        memcpy(&cdf[a], &t, sizeof(t));
-    }
-    rcp[0] = 0.0;
-    for (int n = 1; n <= TE; ++n) rcp[n] = 1.0 / (double)n;                        // mcts.py:255  K / count, K = 1
-    for (int a = 0; a < A; ++a) {
-        const double tp = temperature * (double)A * (pol ? 0.0 : prior_p[a]);     // mcts.py:286, left to right
-        tpv[a] = tp;
-        tpdiv[(size_t)a * (TE + 2)] = 0.0;
-        for (int n = 1; n <= TE + 1; ++n) tpdiv[(size_t)a * (TE + 2) + n] = tp / (double)n; // ... / (count + 1)
-    }
-    double *d_tab = nullptr;
-    MP_TRY(upload_tables(ctx, 1, tab, &d_tab));
+// div_by_const's conditions (see the rollout): every parameter a numerator is built from within [2^-50, 2^50], the divisor
+// normal with a significand that is not all ones, the other denominator bounded away from zero.  MP_CART_FASTDIV=0: A/B.
+static bool cart_fastdiv(const mp_cartpole_params &cq, double *inv_tm)
+{
+    const double tm = cq.masspole + cq.masscart;
+    auto mid = [](double v) { return std::isfinite(v) && fabs(v) >= 0x1p-50 && fabs(v) <= 0x1p50; };
+    uint64_t bits;
+    memcpy(&bits, &tm, 8);
+    const char *e = getenv("MP_CART_FASTDIV");
+    if (!(mid(tm) && tm > 0 && (bits & ((1ULL << 52) - 1)) != (1ULL << 52) - 1 && mid(cq.masspole) && cq.masspole > 0 && mid(cq.length) &&
+          cq.length > 0 && mid(cq.force_mag) && mid(cq.gravity) && mid(cq.tau) && cq.length * (4.0 / 3.0 - cq.masspole / tm) >= 0x1p-50 &&
+          !(e && atoi(e) == 0)))
+        return false;
+    *inv_tm = 1.0 / tm;
+    return true;
+}
 
-    UctArgs a;
-    a.n_roots = n_roots; a.S = model->S; a.A = A; a.episodes = episodes; a.horizon = horizon; a.cap = (int)cap;
-    a.table_n = TE; a.rep_shift = 0;
-    a.done_on_next = model->done_on_next; a.max_steps = model->max_steps; a.max_plan_len = max_plan_len;
+// the kernel arguments that the model, the policy and the tables decide; `thr`: the A thresholds of the tables
+static void uct_args_model(const UctPlan &c, int TE, const double *d_tab, const double *thr, UctArgs *out)
+{
+    const mp_model *model = c.model;
+    const mp_policy *pol = c.pol;
+    const int A = model->A;
+    UctArgs &a = *out;
+    a.n_roots = c.n_roots; a.S = model->S; a.A = A; a.episodes = c.episodes; a.horizon = c.horizon;
+    a.table_n = TE;
+    a.done_on_next = model->done_on_next; a.max_steps = model->max_steps; a.max_plan_len = c.max_plan_len;
     a.rec = model->rec; a.t16 = model->t16; a.tab = d_tab;
+    a.r8 = model->r8; a.rdict = model->rdict; a.n_rdict = model->n_rdict;
+    a.Sb = model->NB > 1 && model->Sb > 0 ? model->Sb : model->S;
     a.thr_valid = 0;
     for (int i = 0; i < 8; ++i) {
         a.thr_arg[i] = ~0ULL;
         if (i < A) {
             uint64_t t;
-            memcpy(&t, &cdf[i], sizeof(uint64_t));
+            memcpy(&t, &thr[i], sizeof(uint64_t));
             if (t < (1ULL << 53)) {
                 a.thr_arg[i] = t << 11;
                 if (i < A - 1) a.thr_valid = i + 1;     // (thresholds are non-decreasing: the valid ones are a prefix)
             }
         }
     }
-    a.cp = model->cp; a.cp_sincos = model->cp_sincos; a.root_x = nullptr;
-    a.cp_fastdiv = 0; a.cp_inv_tm = 0.0;
-    if (cart) {
-        // div_by_const's conditions (see the rollout): every parameter a numerator is built from within [2^-50, 2^50], the divisor
-        // normal with a significand that is not all ones, the other denominator bounded away from zero.  MP_CART_FASTDIV=0: A/B.
-        const mp_cartpole_params &cq = model->cp;
-        const double tm = cq.masspole + cq.masscart;
-        auto mid = [](double v) { return std::isfinite(v) && fabs(v) >= 0x1p-50 && fabs(v) <= 0x1p50; };
-        uint64_t bits;
-        memcpy(&bits, &tm, 8);
-        const char *e = getenv("MP_CART_FASTDIV");
-        if (mid(tm) && tm > 0 && (bits & ((1ULL << 52) - 1)) != (1ULL << 52) - 1 && mid(cq.masspole) && cq.masspole > 0 && mid(cq.length) &&
-            cq.length > 0 && mid(cq.force_mag) && mid(cq.gravity) && mid(cq.tau) && cq.length * (4.0 / 3.0 - cq.masspole / tm) >= 0x1p-50 &&
-            !(e && atoi(e) == 0)) {
-            a.cp_fastdiv = 1;
-            a.cp_inv_tm = 1.0 / tm;
-        }
-    }
+    a.cp = model->cp; a.cp_sincos = model->cp_sincos;
+    a.cp_inv_tm = 0.0;
+    a.cp_fastdiv = model->mode == MP_MODE_CARTPOLE && cart_fastdiv(model->cp, &a.cp_inv_tm) ? 1 : 0;
     a.pol_prior = pol ? pol->prior : nullptr; a.pol_thr = pol ? pol->thr : nullptr; a.pol_frec = pol ? pol->frec : nullptr;
     a.pol_frec_roll = pol ? (pol->frec_roll ? pol->frec_roll : pol->frec) : nullptr;
     a.pol_stride = pol ? pol->stride : 0;
     // 16-byte records for saturated batches (see mp_policy_load)
-    bool use16 = pol && pol->packed && n_roots > 16384;
+    bool use16 = pol && pol->packed && c.n_roots > 16384;
     if (const char *rf = getenv("MP_UCT_POLICY_RECORD")) use16 = pol && pol->packed && rf[0] == 'p' ? true : (rf[0] == 'f' ? false : use16);
-    const bool listed = pol && pol->listed;
-    if (listed) use16 = false; // the listed-action masks live in the fused records' flags word
+    if (pol && pol->listed) use16 = false; // the listed-action masks live in the fused records' flags word
     a.pol_shift = pol ? (use16 ? 43 : pol->shift) : 21;
     a.pol_sat = use16 ? 1023u : 0xffffffffu;
     a.pol_packed = use16 ? 1 : 0;
     if (use16) a.pol_frec = pol->frec16;
-    a.TA = temperature * (double)A;
-    a.temperature = temperature;
+    a.TA = c.temperature * (double)A;
+    a.temperature = c.temperature;
+}
 
-    // the kernel form and its geometry: nothing below changes them
-    const bool cont = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
+// limbs of A^n and G_n = 1 + A + ... + A^(n-1) (mod 2^128), n = 0..H, resident in WS_JUMP: the generator after n draws is
+// A^n state + inc G_n
+static int uct_jump_table(mp_ctx *ctx, int H, const uint32_t **jump)
+{
+    if (ctx->jump_entries < H + 5) {
+        typedef unsigned __int128 u128;
+        const u128 mult = ((u128)0x2360ED051FC65DA4ULL << 64) | 0x4385DF649FCCF645ULL;
+        const int n_e = H + 5 > 64 ? H + 5 : 64;
+        // (kept in the context: the upload is asynchronous on the planner's stream -- a caller that runs the planners
+        // from a stream with pending waits, e.g. ShardedDevicePlan's double-buffered exchange, must not be synchronised here)
+        ctx->jump_host.emplace_back((size_t)n_e * 8, 0u);
+        std::vector<uint32_t> &tabj = ctx->jump_host.back();
+        u128 an = 1, gn = 0;
+        for (int n = 0; n < n_e; ++n) {
+            for (int i = 0; i < 4; ++i) { tabj[(size_t)n * 8 + i] = (uint32_t)(an >> (32 * i)); tabj[(size_t)n * 8 + 4 + i] = (uint32_t)(gn >> (32 * i)); }
+            gn = gn * mult + 1;
+            an = an * mult;
+        }
+        uint32_t *dj = nullptr;
+        ctx->jump_entries = 0;
+        MP_TRY(ws_get(ctx, WS_JUMP, tabj.size(), &dj));
+        MP_HIP(hipMemcpyAsync(dj, tabj.data(), tabj.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        ctx->jump_entries = n_e;
+    }
+    *jump = static_cast<const uint32_t *>(ctx->ws[WS_JUMP].p);
+    return MP_OK;
+}
+
+// the kernel form and its geometry (uct_choose), the kernel arguments they decide, the jump table of the forms that jump ahead
+static int uct_form(mp_ctx *ctx, const UctPlan &c, bool cont, UctChoice *ch, UctArgs *a)
+{
+    const mp_model *model = c.model;
     UctCall call;
-    call.n_roots = n_roots; call.episodes = E; call.horizon = H; call.A = A; call.S = model->S; call.NB = model->NB; call.Sb = model->Sb;
+    call.n_roots = c.n_roots; call.episodes = c.episodes; call.horizon = c.horizon; call.A = model->A; call.S = model->S;
+    call.NB = model->NB; call.Sb = model->Sb;
     call.t16 = model->t16 != nullptr; call.r8 = model->r8 != nullptr; call.n_rdict = model->n_rdict;
-    call.cart = cart; call.pol = pol != nullptr; call.listed = listed;
+    call.cart = model->mode == MP_MODE_CARTPOLE; call.pol = c.pol != nullptr; call.listed = c.pol && c.pol->listed;
     call.kept_il = cont ? ctx->tree.il : -1;
     call.cus = ctx->prop.multiProcessorCount;
-    UctChoice ch;
     const UctKnobs knobs = uct_knobs_read();
-    MP_TRY(uct_choose(call, knobs, &ch));
-    a.tree_stores = knobs.tree_stores;   // (how uct_kernel issues its tree stores: neither the form nor its name)
-    const UctForm form = ch.form;
-    a.Sb = model->NB > 1 && model->Sb > 0 ? model->Sb : model->S;
-    a.jump = nullptr;
+    MP_TRY(uct_choose(call, knobs, ch));
+    a->tree_stores = knobs.tree_stores;   // (how uct_kernel issues its tree stores: neither the form nor its name)
+    a->lanes = ch->lanes; a->waves = ch->waves; a->rep_shift = ch->rep_shift;
+    a->jump = nullptr;
+    const UctForm form = ch->form;
     if (form == UF_QUAD || form == UF_LONE || form == UF_LONE_MW || form == UF_LONE_EACH || form == UF_ROW_EACH || form == UF_ROW_SHARED ||
-        form == UF_CARTPOLE) {
-        // limbs of A^n and G_n = 1 + A + ... + A^(n-1) (mod 2^128), n = 0..H: the generator after n draws is A^n state + inc G_n
-        if (ctx->jump_entries < H + 5) {
-            typedef unsigned __int128 u128;
-            const u128 mult = ((u128)0x2360ED051FC65DA4ULL << 64) | 0x4385DF649FCCF645ULL;
-            const int n_e = H + 5 > 64 ? H + 5 : 64;
-            // (kept in the context: the upload is asynchronous on the planner's stream -- a caller that runs the planners
-            // from a stream with pending waits, e.g. ShardedDevicePlan's double-buffered exchange, must not be synchronised here)
-            ctx->jump_host.emplace_back((size_t)n_e * 8, 0u);
-            std::vector<uint32_t> &tabj = ctx->jump_host.back();
-            u128 an = 1, gn = 0;
-            for (int n = 0; n < n_e; ++n) {
-                for (int i = 0; i < 4; ++i) { tabj[(size_t)n * 8 + i] = (uint32_t)(an >> (32 * i)); tabj[(size_t)n * 8 + 4 + i] = (uint32_t)(gn >> (32 * i)); }
-                gn = gn * mult + 1;
-                an = an * mult;
-            }
-            uint32_t *dj = nullptr;
-            ctx->jump_entries = 0;
-            MP_TRY(ws_get(ctx, WS_JUMP, tabj.size(), &dj));
-            MP_HIP(hipMemcpyAsync(dj, tabj.data(), tabj.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-            ctx->jump_entries = n_e;
-        }
-        a.jump = static_cast<const uint32_t *>(ctx->ws[WS_JUMP].p);
-    }
-    a.r8 = model->r8; a.rdict = model->rdict; a.n_rdict = model->n_rdict; a.path_spill = nullptr; a.spill_stride = 0;
-    a.lanes = ch.lanes; a.waves = ch.waves; a.rep_shift = ch.rep_shift;
+        form == UF_CARTPOLE)
+        MP_TRY(uct_jump_table(ctx, c.horizon, &a->jump));
+    return MP_OK;
+}
 
-    // trees: fresh ones, or (step_strategy "subtree") the kept ones re-rooted into the other buffer with room
-    // for this plan's expansions
-    int32_t *d_nn = nullptr; // per-root tree sizes (updated in place by re-rooting and planning)
-    a.n_nodes_in = nullptr;
-    long cap_use = cap;
+// trees: fresh ones, or (step_strategy "subtree") the kept ones re-rooted into the other buffer with room for this plan's
+// expansions; the per-root tree sizes (updated in place by re-rooting and planning); the spilled path stacks of the forms
+// that keep their paths in registers
+static int uct_trees(mp_ctx *ctx, const UctPlan &c, bool cont, const UctChoice &ch, UctArgs *a)
+{
+    const int n_roots = c.n_roots, A = a->A, H = c.horizon, E = c.episodes;
+    long cap_use = 1 + (long)E * A;
+    a->n_nodes_in = nullptr;
     if (cont) {
-        // a kept subtree only holds nodes created by the last `horizon` plans (a node at depth d survives d re-rootings
-        // and d <= horizon), so the stride stays O(horizon * episodes * |A|) however long the episode runs
-        // (the largest horizon * episodes of the plans since the last fresh tree, should the caller vary them)
-        const long now = 1 + (long)horizon * episodes * A;
-        if (now > ctx->tree.kept_bound) ctx->tree.kept_bound = now;
-        const long bound = ctx->tree.kept_bound;
-        cap_use = (ctx->tree.cap < bound ? (long)ctx->tree.cap : bound) + (long)episodes * A;
+        cap_use = uct_kept_cap(ctx, H, E, A);
         MP_TRY(uct_reroot_now(ctx, cap_use)); // (reads the kept trees' sizes: before WS_TREE1 may grow to a larger selection)
-        MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &d_nn));
-        a.tree = (UctNode *)ctx->ws[ctx->tree.buf ? WS_TREE2 : WS_TREE0].p;
-        a.n_nodes_in = d_nn;
+        MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &a->n_nodes_out));
+        a->tree = (UctNode *)ctx->ws[ctx->tree.buf ? WS_TREE2 : WS_TREE0].p;
+        a->n_nodes_in = a->n_nodes_out;
     } else {
-        MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &d_nn));
-        ctx->tree.armed = false;
-        ctx->tree.n_src = 0;
-        ctx->tree.buf = 0;
-        ctx->tree.kept_bound = 1 + (long)horizon * episodes * A;
+        MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &a->n_nodes_out));
+        uct_fresh_tree(ctx, H, E, A);
         ctx->tree.il = ch.tree_il;
-        MP_TRY(ws_get(ctx, WS_TREE0, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_use, A), &a.tree));
+        MP_TRY(ws_get(ctx, WS_TREE0, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_use, A), &a->tree));
     }
-    a.n_nodes_out = d_nn;
-    a.cap = (int)cap_use;
-    a.tree_il = ctx->tree.il;
-    form_record(ctx->last_variant, uct_form_name(form));
-    if (form == UF_LDSR || form == UF_QUAD || form == UF_GLOBAL_SPILL) {
-        a.spill_stride = ((long)n_roots + 63) & ~63L;
-        MP_TRY(ws_get(ctx, WS_TREE4, (size_t)(H + 1) * (size_t)a.spill_stride, &a.path_spill));
+    a->cap = (int)cap_use;
+    a->tree_il = ctx->tree.il;
+    a->path_spill = nullptr; a->spill_stride = 0;
+    if (ch.form == UF_LDSR || ch.form == UF_QUAD || ch.form == UF_GLOBAL_SPILL) {
+        a->spill_stride = ((long)n_roots + 63) & ~63L;
+        MP_TRY(ws_get(ctx, WS_TREE4, (size_t)(H + 1) * (size_t)a->spill_stride, &a->path_spill));
     }
     ctx->tree.kind = 1; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap_use;
+    return MP_OK;
+}
 
-    // ---- staging.  Device arrays are used in place; host arrays get device twins (no copy yet: the copies are issued
-    // per chunk, below).  The generator records follow their own flag (MP_MEM_RNG_DEVICE: an mp_rng).
-    int amem = mem_arrays(mem), rmem = mem_rng(mem);
-    const bool host_call = amem == MP_MEM_HOST;       // the call synchronises before it returns
-    bool all_pinned = false;                          // every host array lies in mp_host_alloc memory
+// ---- staging.  Device arrays are used in place; host arrays get device twins (no copy yet: the copies are issued per chunk).
+// The generator records follow their own flag (MP_MEM_RNG_DEVICE: an mp_rng).  -> *all_pinned: every host array lies in
+// mp_host_alloc memory.
+static int uct_stage(mp_ctx *ctx, WaveIo *io, bool *all_pinned)
+{
+    *all_pinned = false;
     // Zero-copy: when EVERY array the caller hands over lives in mp_host_alloc memory (pinned and mapped into the
     // device's address space) the kernel reads the root states from and writes the results to the caller's arrays over
     // the bus, and the whole call is one launch + one synchronisation: no copy is issued at all.
-    if (host_call) {
+    if (io->mem == MP_MEM_HOST) {
+        void *alias[10];
         bool all = true;
-        auto alias = [&](const void *p, size_t bytes, auto **out) {
-            if (!p) return;
-            void *d = pinned_alias(ctx, p, bytes);
-            if (!d) all = false; else *out = static_cast<std::remove_reference_t<decltype(*out)>>(d);
-        };
-        const void *z_rs = nullptr; const int32_t *z_st = nullptr; uint64_t *z_rng = rng_state;
-        int32_t *z_plans = nullptr, *z_len = nullptr; double *z_val = nullptr, *z_cv = nullptr; int64_t *z_cc = nullptr, *z_es = nullptr;
-        alias(root_state, (size_t)n_roots * (cart ? 32 : 4), &z_rs);
-        alias(root_steps, (size_t)n_roots * 4, &z_st);
-        if (rmem == MP_MEM_HOST) alias(rng_state, (size_t)n_roots * 48, &z_rng);
-        alias(plans, (size_t)n_roots * max_plan_len * 4, &z_plans);
-        alias(plan_len, (size_t)n_roots * 4, &z_len);
-        alias(root_value, (size_t)n_roots * 8, &z_val);
-        alias(root_child_count, (size_t)n_roots * A * 8, &z_cc);
-        alias(root_child_value, (size_t)n_roots * A * 8, &z_cv);
-        alias(env_steps, (size_t)n_roots * 8, &z_es);
-        all_pinned = all;
+        for (int i = 0; i < io->n; ++i) {
+            const WaveIo::Item &t = io->item[i];
+            alias[i] = t.host && t.mem == MP_MEM_HOST ? pinned_alias(ctx, t.host, io->bytes(t)) : t.host;
+            if (t.host && !alias[i]) all = false;
+        }
+        *all_pinned = all;
         // Measured (262 144 roots, 13 MB of results): the kernel writing over the bus 1.52 ms; one launch + asynchronous
         // copies into the same pinned arrays 1.48 ms; two saturating chunks back to back on two streams, the first
         // chunk's results travelling under the second chunk's kernel, 1.35-1.37 ms (device-resident: 1.12).  Small batches
         // (4 096 roots: 0.349 ms zero-copy against 0.346 ms device-resident) are dominated by the calls a copy costs.
         long zc_max = 65536;
         if (const char *e = getenv("MP_ZERO_COPY_MAX")) zc_max = atol(e);
-        if (all && !getenv("MP_NO_ZERO_COPY") && n_roots <= zc_max) {
-            root_state = z_rs; root_steps = z_st; rng_state = z_rng; plans = z_plans; plan_len = z_len; root_value = z_val;
-            root_child_count = z_cc; root_child_value = z_cv; env_steps = z_es;
-            amem = MP_MEM_DEVICE; rmem = MP_MEM_DEVICE;     // from here on: device arrays (their aliases)
+        if (all && !getenv("MP_NO_ZERO_COPY") && io->n_roots <= zc_max) {
+            for (int i = 0; i < io->n; ++i) { io->item[i].host = alias[i]; io->item[i].mem = MP_MEM_DEVICE; }
+            io->mem = MP_MEM_DEVICE; io->rmem = MP_MEM_DEVICE;     // from here on: device arrays (their aliases)
         }
     }
-    const bool host = amem == MP_MEM_HOST;
-    int32_t *d_rs = nullptr, *d_st = nullptr;
-    double *d_rx = nullptr;
-    if (!host) {
-        if (cart) d_rx = (double *)const_cast<void *>(root_state); else d_rs = (int32_t *)const_cast<void *>(root_state);
-        d_st = const_cast<int32_t *>(root_steps);
-    } else {
-        if (cart) MP_TRY(ws_get(ctx, WS_IO9, (size_t)n_roots * 4, &d_rx)); else MP_TRY(ws_get(ctx, WS_IO0, (size_t)n_roots, &d_rs));
-        if (root_steps) MP_TRY(ws_get(ctx, WS_IO1, (size_t)n_roots, &d_st));
-    }
-    if (rmem == MP_MEM_DEVICE) a.rng = rng_state; else MP_TRY(ws_get(ctx, WS_IO2, (size_t)n_roots * 6, &a.rng));
-    a.root_x = d_rx; a.root_state = d_rs; a.root_steps = d_st;
     // (device twins from the workspaces, NOT stage_out_alloc: that helper would hand back the device alias of a pinned
-    // array -- the zero-copy form, decided above for the whole call -- and the chunk copies below would copy it onto itself)
-    auto twin = [&](int slot, auto *dst, size_t count, auto **dev) -> int {
-        if (!host) { *dev = dst; return MP_OK; }
-        if (!dst) { *dev = nullptr; return MP_OK; }
-        return ws_get(ctx, slot, count, dev);
-    };
-    MP_TRY(twin(WS_IO3, plans, (size_t)n_roots * max_plan_len, &a.plans));
-    MP_TRY(twin(WS_IO4, plan_len, (size_t)n_roots, &a.plan_len));
-    MP_TRY(twin(WS_IO5, root_value, (size_t)n_roots, &a.root_value));
-    MP_TRY(twin(WS_IO6, root_child_count, (size_t)n_roots * A, &a.root_child_count));
-    MP_TRY(twin(WS_IO7, root_child_value, (size_t)n_roots * A, &a.root_child_value));
-    MP_TRY(twin(WS_IO8, env_steps, (size_t)n_roots, &a.env_steps));
+    // array -- the zero-copy form, decided above for the whole call -- and the chunk copies would copy it onto itself)
+    for (int i = 0; i < io->n; ++i) {
+        WaveIo::Item &t = io->item[i];
+        void *d = t.host;
+        if (t.mem == MP_MEM_HOST && t.host) MP_TRY(ws_reserve(ctx, t.slot, io->bytes(t), &d));
+        t.base = static_cast<char *>(d);
+    }
+    return MP_OK;
+}
 
-    // ---- one chunk of roots [r0, r1): copies in, the kernel, copies out, all on stream `s`.  A chunk is the same launch
-    // on shifted pointers (r0 is a multiple of 1024: whole wavefront blocks of the interleaved tree layouts and whole
-    // workgroups of every variant), so chunked and unchunked calls leave identical trees and results.
-    const long tree_off_per_block = ctx->tree.il == 2 ? (cap_use + A) * 64 : cap_use * 64;
-    auto run_chunk = [&](int r0, int r1, hipStream_t s) -> int {
-        const size_t cnt = (size_t)(r1 - r0);
-        if (host) {
-            if (cart) MP_HIP(hipMemcpyAsync(d_rx + (size_t)r0 * 4, (const double *)root_state + (size_t)r0 * 4, cnt * 32, hipMemcpyHostToDevice, s));
-            else MP_HIP(hipMemcpyAsync(d_rs + r0, (const int32_t *)root_state + r0, cnt * 4, hipMemcpyHostToDevice, s));
-            if (root_steps) MP_HIP(hipMemcpyAsync(d_st + r0, root_steps + r0, cnt * 4, hipMemcpyHostToDevice, s));
-        }
-        if (rmem == MP_MEM_HOST) MP_HIP(hipMemcpyAsync(a.rng + (size_t)r0 * 6, rng_state + (size_t)r0 * 6, cnt * 48, hipMemcpyHostToDevice, s));
-        UctArgs c = a;
-        c.n_roots = r1 - r0;
-        if (c.root_x) c.root_x += (size_t)r0 * 4;
-        if (c.root_state) c.root_state += r0;
-        if (c.root_steps) c.root_steps += r0;
-        c.rng += (size_t)r0 * 6;
-        c.tree += (long)(r0 >> 6) * tree_off_per_block;
-        if (c.path_spill) c.path_spill += r0;
-        if (c.n_nodes_in) c.n_nodes_in += r0;
-        c.n_nodes_out += r0;
-        if (c.plans) c.plans += (size_t)r0 * max_plan_len;
-        if (c.plan_len) c.plan_len += r0;
-        if (c.root_value) c.root_value += r0;
-        if (c.root_child_count) c.root_child_count += (size_t)r0 * A;
-        if (c.root_child_value) c.root_child_value += (size_t)r0 * A;
-        if (c.env_steps) c.env_steps += r0;
-        switch (A) {
-        case 2: MP_TRY(uct_launch<2>(ch, listed, c, s)); break;
-        case 3: MP_TRY(uct_launch<3>(ch, listed, c, s)); break;
-        case 4: MP_TRY(uct_launch<4>(ch, listed, c, s)); break;
-        case 5: MP_TRY(uct_launch<5>(ch, listed, c, s)); break;
-        case 6: MP_TRY(uct_launch<6>(ch, listed, c, s)); break;
-        case 7: MP_TRY(uct_launch<7>(ch, listed, c, s)); break;
-        case 8: MP_TRY(uct_launch<8>(ch, listed, c, s)); break;
-        default: MP_TRY(uct_launch<0>(ch, listed, c, s)); break;
-        }
-        if (rmem == MP_MEM_HOST) MP_HIP(hipMemcpyAsync(rng_state + (size_t)r0 * 6, c.rng, cnt * 48, hipMemcpyDeviceToHost, s));
-        if (host) {
-            if (plans && max_plan_len) MP_HIP(hipMemcpyAsync(plans + (size_t)r0 * max_plan_len, c.plans, cnt * max_plan_len * 4, hipMemcpyDeviceToHost, s));
-            if (plan_len) MP_HIP(hipMemcpyAsync(plan_len + r0, c.plan_len, cnt * 4, hipMemcpyDeviceToHost, s));
-            if (root_value) MP_HIP(hipMemcpyAsync(root_value + r0, c.root_value, cnt * 8, hipMemcpyDeviceToHost, s));
-            if (root_child_count) MP_HIP(hipMemcpyAsync(root_child_count + (size_t)r0 * A, c.root_child_count, cnt * A * 8, hipMemcpyDeviceToHost, s));
-            if (root_child_value) MP_HIP(hipMemcpyAsync(root_child_value + (size_t)r0 * A, c.root_child_value, cnt * A * 8, hipMemcpyDeviceToHost, s));
-            if (env_steps) MP_HIP(hipMemcpyAsync(env_steps + r0, c.env_steps, cnt * 8, hipMemcpyDeviceToHost, s));
-        }
-        return MP_OK;
-    };
+// ---- one chunk of roots [r0, r1): copies in, the kernel, copies out (the generator records first, then the results in their
+// ABI order), all on stream `s`.  A chunk is the same launch on shifted pointers (r0 is a multiple of 1024: whole wavefront
+// blocks of the interleaved tree layouts and whole workgroups of every variant), so chunked and unchunked calls leave
+// identical trees and results.  `a` holds the arguments of the whole batch; the table's pointers in it move to the chunk.
+static int uct_run_chunk(const WaveIo &io, const UctChoice &ch, bool listed, UctArgs &a, int r0, int r1, hipStream_t s)
+{
+    const size_t cnt = (size_t)(r1 - r0);
+    for (int i = 0; i < io.n; ++i) {
+        const WaveIo::Item &t = io.item[i];
+        char *d = t.base ? t.base + (size_t)r0 * t.per_root : nullptr;
+        *t.dev = d;
+        if ((t.dir & WaveIo::IN) && t.mem == MP_MEM_HOST && t.host)
+            MP_HIP(hipMemcpyAsync(d, (const char *)t.host + (size_t)r0 * t.per_root, cnt * t.per_root, hipMemcpyHostToDevice, s));
+    }
+    UctArgs c = a;
+    c.n_roots = r1 - r0;
+    c.tree += (long)(r0 >> 6) * (long)tree_stride_alloc(a.tree_il, a.cap, a.A) * 64;
+    if (c.path_spill) c.path_spill += r0;
+    if (c.n_nodes_in) c.n_nodes_in += r0;
+    c.n_nodes_out += r0;
+    MP_TRY(uct_dispatch(ch, listed, c, s));
+    for (int i = 0; i < io.n; ++i) {
+        const WaveIo::Item &t = io.item[i];
+        if ((t.dir & WaveIo::OUT) && t.mem == MP_MEM_HOST && t.host && t.per_root)
+            MP_HIP(hipMemcpyAsync((char *)t.host + (size_t)r0 * t.per_root, *t.dev, cnt * t.per_root, hipMemcpyDeviceToHost, s));
+    }
+    return MP_OK;
+}
 
-    // ---- host arrays and a big batch: chunks pipelined over side streams (H2D of chunk i+1 and D2H of chunk i-1 run
-    // under the kernel of chunk i, and kernels of different chunks share the chip).  Everything else: one chunk on the
-    // ctx stream, as ever.
-    // pageable arrays, measured at 262 144 roots: 65 536 x 4 streams 4.1 ms, 32 768 x 4 7.3 ms, 8 192 x 8 12.6 ms (the
-    // runtime stages every pageable copy); pinned arrays: two chunks that each fill the chip, see above
+// ---- host arrays and a big batch: chunks pipelined over side streams (H2D of chunk i+1 and D2H of chunk i-1 run
+// under the kernel of chunk i, and kernels of different chunks share the chip).  Everything else: one chunk on the
+// ctx stream, as ever.
+// pageable arrays, measured at 262 144 roots: 65 536 x 4 streams 4.1 ms, 32 768 x 4 7.3 ms, 8 192 x 8 12.6 ms (the
+// runtime stages every pageable copy); pinned arrays: two chunks that each fill the chip, see uct_stage
+template <typename Chunk>
+static int uct_pipeline(mp_ctx *ctx, int n_roots, bool host, bool all_pinned, Chunk run_chunk)
+{
     int chunk = 65536, n_streams = 4;
     if (all_pinned) { chunk = (((n_roots + 1) / 2) + 1023) & ~1023; n_streams = 2; }
     if (const char *e = getenv("MP_PIPE_CHUNK")) chunk = atoi(e) > 0 ? ((atoi(e) + 1023) & ~1023) : 0;
@@ -2966,11 +2897,60 @@ static int uct_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int
         MP_TRY(pipe_join(ctx, n_streams));
         launches = n_chunks;
     } else {
-        MP_TRY(run_chunk(0, n_roots, st));
+        MP_TRY(run_chunk(0, n_roots, ctx->stream));
     }
     MP_TRY(kernels_end(ctx, launches));
     MP_HIP(hipGetLastError());
-    if (host_call) MP_HIP(hipStreamSynchronize(st));
+    return MP_OK;
+}
+
+static int uct_plan_impl(mp_ctx *ctx, const UctPlan &c)
+{
+    MP_TRY(uct_check(ctx, c));
+    mp_model *model = c.model;
+    const bool cart = model->mode == MP_MODE_CARTPOLE;
+    const int n_roots = c.n_roots, A = model->A, H = c.horizon, E = c.episodes;
+    MP_HIP(hipSetDevice(ctx->device));
+
+    // small per-call tables
+    // (the quotient tables live in LDS: 16 KB of them at most; counts beyond take the division in the kernel)
+    const int te_max = (int)(16384 / (sizeof(double) * (size_t)(A + 1)));
+    const int TE = E < te_max ? E : te_max;
+    std::vector<double> tab;
+    const UctTables to = uct_tables(H, A, TE, c.gamma, c.temperature, c.prior_p, c.rollout_p, tab);
+    double *d_tab = nullptr;
+    MP_TRY(upload_tables(ctx, 1, tab, &d_tab));
+
+    UctArgs a;
+    uct_args_model(c, TE, d_tab, tab.data() + to.cdf, &a);
+    // the kernel form and its geometry: nothing below changes them
+    const bool cont = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
+    UctChoice ch;
+    MP_TRY(uct_form(ctx, c, cont, &ch, &a));
+    MP_TRY(uct_trees(ctx, c, cont, ch, &a));
+    form_record(ctx->last_variant, uct_form_name(ch.form));
+
+    // the caller's arrays: root states, steps and generator records in, the records and the results out
+    const bool host_call = mem_arrays(c.mem) == MP_MEM_HOST;       // the call synchronises before it returns
+    WaveIo io(mem_arrays(c.mem), mem_rng(c.mem), n_roots);
+    a.root_x = nullptr; a.root_state = nullptr;
+    if (cart) io.in(WS_IO9, (const double *)c.root_state, &a.root_x, 4);
+    else io.in(WS_IO0, (const int32_t *)c.root_state, &a.root_state);
+    io.in(WS_IO1, c.root_steps, &a.root_steps);
+    io.rng(c.rng_state, &a.rng);
+    io.add(WS_IO3, c.plans, &a.plans, c.max_plan_len);
+    io.add(WS_IO4, c.plan_len, &a.plan_len);
+    io.add(WS_IO5, c.root_value, &a.root_value);
+    io.add(WS_IO6, c.root_child_count, &a.root_child_count, A);
+    io.add(WS_IO7, c.root_child_value, &a.root_child_value, A);
+    io.add(WS_IO8, c.env_steps, &a.env_steps);
+    bool all_pinned = false;
+    MP_TRY(uct_stage(ctx, &io, &all_pinned));
+
+    const bool listed = c.pol && c.pol->listed;
+    MP_TRY(uct_pipeline(ctx, n_roots, io.mem == MP_MEM_HOST, all_pinned,
+                        [&](int r0, int r1, hipStream_t s) { return uct_run_chunk(io, ch, listed, a, r0, r1, s); }));
+    if (host_call) MP_HIP(hipStreamSynchronize(ctx->stream));
     return MP_OK;
 }
 
@@ -2982,9 +2962,9 @@ int mp_uct_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const void *root_
                 int32_t *plan_len, double *root_value, int64_t *root_child_count, double *root_child_value,
                 int64_t *env_steps, int32_t mem)
 {
-    return uct_plan_impl(ctx, model, nullptr, n_roots, root_state, root_steps, episodes, horizon, gamma, temperature,
-                         prior_p, rollout_p, rng_state, max_plan_len, plans, plan_len, root_value, root_child_count,
-                         root_child_value, env_steps, mem);
+    return uct_plan_impl(ctx, {model, nullptr, n_roots, root_state, root_steps, episodes, horizon, gamma, temperature, prior_p,
+                               rollout_p, 0, rng_state, nullptr, max_plan_len, plans, plan_len, root_value, root_child_count,
+                               root_child_value, env_steps, mem});
 }
 
 int mp_uct_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
@@ -2997,8 +2977,9 @@ int mp_uct_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int3
     std::vector<int32_t> tmp;
     const int32_t *global = nullptr;
     MP_TRY(globalize_roots_arg(ctx, model, n_roots, model_index, root_state, mem, tmp, &global));
-    return uct_plan_impl(ctx, model, nullptr, n_roots, global, root_steps, episodes, horizon, gamma, temperature, prior_p, rollout_p,
-                         rng_state, max_plan_len, plans, plan_len, root_value, root_child_count, root_child_value, env_steps, mem);
+    return uct_plan_impl(ctx, {model, nullptr, n_roots, global, root_steps, episodes, horizon, gamma, temperature, prior_p,
+                               rollout_p, 0, rng_state, nullptr, max_plan_len, plans, plan_len, root_value, root_child_count,
+                               root_child_value, env_steps, mem});
 }
 
 int mp_uct_plan_policy(mp_ctx *ctx, mp_model *model, mp_policy *policy, int32_t n_roots, const void *root_state,
@@ -3007,9 +2988,9 @@ int mp_uct_plan_policy(mp_ctx *ctx, mp_model *model, mp_policy *policy, int32_t 
                        int64_t *root_child_count, double *root_child_value, int64_t *env_steps, int32_t mem)
 {
     if (!policy) return fail(MP_ERR_ARG, "mp_uct_plan_policy: policy is NULL");
-    return uct_plan_impl(ctx, model, policy, n_roots, root_state, root_steps, episodes, horizon, gamma, temperature,
-                         nullptr, nullptr, rng_state, max_plan_len, plans, plan_len, root_value, root_child_count,
-                         root_child_value, env_steps, mem);
+    return uct_plan_impl(ctx, {model, policy, n_roots, root_state, root_steps, episodes, horizon, gamma, temperature, nullptr,
+                               nullptr, 0, rng_state, nullptr, max_plan_len, plans, plan_len, root_value, root_child_count,
+                               root_child_value, env_steps, mem});
 }
 
 // mcts_with_prior.py:47-62 as tables: per state, the prior row and the integer sampling thresholds of the rollout row

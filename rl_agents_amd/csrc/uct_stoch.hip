@@ -23,6 +23,7 @@
 
 #include "common.hpp"
 #include "pcg64.hpp"
+#include "uct_host.hpp"
 
 namespace mp {
 
@@ -715,26 +716,25 @@ __global__ void env_step_stoch_kernel(int n, int A, int sparse, int W, const uin
 
 using namespace mp;
 
-// sampling thresholds of a stochastic / sparse model's rows, built once per model on the device (numpy's cumsum / division order)
-int ensure_thresholds(mp_ctx *ctx, mp_model *model)
+// sampling thresholds of a stochastic / sparse model's rows, built once per model on the device (numpy's cumsum / division order);
+// `who`: the entry point that needs them, for the message
+int ensure_thresholds(mp_ctx *ctx, const char *who, mp_model *model)
 {
     if (model->thr) return MP_OK;
     const long rows = (long)model->S * model->A;
     const int W = model->mode == MP_MODE_STOCHASTIC ? model->S : model->B;
     if (hipMalloc(&model->thr, (size_t)rows * W * sizeof(uint64_t)) != hipSuccess)
-        return fail(MP_ERR_ALLOC, "%zu B for the sampling thresholds", (size_t)rows * W * 8);
+        return fail(MP_ERR_ALLOC, "%s: %zu B for the sampling thresholds", who, (size_t)rows * W * 8);
     hipLaunchKernelGGL(build_thresholds, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, ctx->stream, rows, W, model->P, model->thr);
     MP_HIP(hipGetLastError());
     return MP_OK;
 }
 
 // Apply the re-rooting armed by mp_uct_step_tree to the open-loop trees of the last mp_uct_plan_stochastic: every kept tree
-// -> the subtree under its root's child actions[i], into the other hot buffer with node stride cap_new.
+// -> the subtree under its root's child actions[i], into the other hot buffer with node stride cap_new (reroot_apply).
 int uct_stoch_reroot_now(mp_ctx *ctx, long cap_new)
 {
-    const int n_roots = ctx->tree.n_roots, A = ctx->tree.A;
-    const bool sel = ctx->tree.n_src > 0; // (mp_uct_step_tree_select: see uct_reroot_now)
-    const int n_src = sel ? ctx->tree.n_src : n_roots;
+    const int n_roots = ctx->tree.n_roots;
     const int old_slot = ctx->tree.buf ? WS_TREE5 : WS_TREE0, new_slot = ctx->tree.buf ? WS_TREE0 : WS_TREE5;
     // (per-state policies keep stored priors in the cold halves: those alternate between two buffers like the hot ones)
     const bool sp = ctx->tree.sp;
@@ -743,21 +743,11 @@ int uct_stoch_reroot_now(mp_ctx *ctx, long cap_new)
     SCold *cold = nullptr;
     MP_TRY(ws_get(ctx, new_slot, (size_t)n_roots * cap_new, &nw));
     MP_TRY(ws_get(ctx, new_cold, (size_t)n_roots * cap_new, &cold));
-    // (a selection of more roots than the old batch: the sizes' slot grows now, keeping the old sizes the kernel reads)
-    if (sel) MP_TRY(ws_reserve_keep(ctx, WS_TREE1, (size_t)n_roots * sizeof(int32_t)));
-    int32_t *sizes = (int32_t *)ctx->ws[WS_TREE1].p;
-    const int32_t *acts = (const int32_t *)ctx->ws[WS_TREE3].p;
-    const int32_t *src = sel ? (const int32_t *)ctx->ws[WS_TREE7].p : nullptr;
-    int32_t *sizes_new = sel ? (int32_t *)ctx->ws[WS_TREE7].p + n_roots : sizes;
-    hipLaunchKernelGGL(uct_stoch_reroot_kernel, dim3((unsigned)((n_roots + 63) / 64)), dim3(64), 0, ctx->stream, n_roots, n_src, A,
-                       ctx->tree.cap, (int)cap_new, (const SHot *)ctx->ws[old_slot].p, nw,
-                       sp ? (const SCold *)ctx->ws[old_cold].p : (const SCold *)nullptr, cold, sizes, src, acts, sizes_new);
-    MP_HIP(hipGetLastError());
-    if (sel) MP_TRY(reroot_sizes_back(ctx));
-    ctx->tree.buf ^= 1;
-    ctx->tree.cap = (int)cap_new;
-    ctx->tree.armed = false;
-    return MP_OK;
+    return reroot_apply(ctx, cap_new, [&](const Reroot &r) {
+        hipLaunchKernelGGL(uct_stoch_reroot_kernel, dim3((unsigned)((r.n_roots + 63) / 64)), dim3(64), 0, ctx->stream, r.n_roots, r.n_src,
+                           r.A, r.cap_old, r.cap_new, (const SHot *)ctx->ws[old_slot].p, nw,
+                           sp ? (const SCold *)ctx->ws[old_cold].p : (const SCold *)nullptr, cold, r.sizes, r.src, r.acts, r.sizes_new);
+    });
 }
 
 extern "C" {
@@ -772,40 +762,18 @@ int mp_model_set_episode_rules(mp_model *model, int32_t done_on_next, int32_t ma
 
 } // extern "C"
 
-static int uct_stoch_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *pol, int32_t n_roots, const int32_t *root_state,
-                               const int32_t *root_steps, int32_t episodes, int32_t horizon, double gamma, double temperature,
-                               const double *prior_p, const double *rollout_p, int32_t closed_loop, uint64_t *rng_state,
-                               const uint64_t *env_rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len,
-                               double *root_value, int64_t *root_child_count, double *root_child_value, int64_t *env_steps,
-                               int32_t mem)
+// ---- the model as the kernels read it, prepared once per model: fused records (one gather per env step) for sparse rows of at
+// most four successors and for dense rows with at most four non-zero entries, sampling thresholds for the rows that are not
+// fused.  *wbk: the form the records really have (0: none, 2 / 4: uint4 per record, 1: compact).  MP_UCT_STOCH_FUSED=0: never
+// fused, =2: keep the 32-byte records -- test hooks.
+static int stoch_records_ensure(mp_ctx *ctx, mp_model *model, int *wbk)
 {
-    if (!ctx || !model || !root_state || !rng_state || (!pol && (!prior_p || !rollout_p)))
-        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: NULL argument");
-    if (pol && (pol->model != model || pol->model_serial != model->serial || pol->ctx != ctx || !pol->lmask))
-        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic_policy: the policy was not loaded for this (stochastic) model");
-    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: unknown mem flags %d", mem);
-    const int mode = model->mode;
-    if (mode != MP_MODE_DETERMINISTIC && mode != MP_MODE_STOCHASTIC && mode != MP_MODE_SPARSE)
-        return fail(MP_ERR_MODE, "mp_uct_plan_stochastic: model mode %d is not a finite MDP", mode);
-    if (mode != MP_MODE_DETERMINISTIC && !env_rng_state)
-        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: a stochastic model needs the env's generator records");
-    if (mode == MP_MODE_STOCHASTIC && (model->M != 1 || model->Sc != model->S))
-        return fail(MP_ERR_MODE, "mp_uct_plan_stochastic: one full dense model [S,A,S] expected");
-    if (model->masked && !pol)
-        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: the model restricts its action sets: plan with a policy (mp_uct_plan_stochastic_policy)");
-    if (n_roots < 1 || episodes < 0 || horizon < 0 || max_plan_len < 0)
-        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: bad sizes (n_roots=%d episodes=%d horizon=%d)", n_roots, episodes, horizon);
-    const int A = model->A, S = model->S, H = horizon, E = episodes;
-    const int W = mode == MP_MODE_STOCHASTIC ? S : (mode == MP_MODE_SPARSE ? model->B : 0);
-    MP_HIP(hipSetDevice(ctx->device));
+    const int mode = model->mode, A = model->A;
+    const int W = mode == MP_MODE_STOCHASTIC ? model->S : (mode == MP_MODE_SPARSE ? model->B : 0);
     hipStream_t st = ctx->stream;
-    const int amem = mem_arrays(mem), rmem = mem_rng(mem);
-
-    // Fused records (one gather per env step) for sparse rows of at most four successors and for dense rows with at most
-    // four non-zero entries; MP_UCT_STOCH_FUSED=0: never -- test hook.
     const char *fz = getenv("MP_UCT_STOCH_FUSED");
     const bool fuse_ok = !(fz && fz[0] == '0');
-    const long rows = (long)S * A;
+    const long rows = (long)model->S * A;
     if (model->srec_wb == 0 && mode == MP_MODE_SPARSE) model->srec_wb = W <= 2 ? 2 : (W <= 4 ? 4 : -1);
     if (model->srec_wb == 0 && mode == MP_MODE_STOCHASTIC && fuse_ok) {
         int *d_max = nullptr, h_max = 0;
@@ -817,14 +785,8 @@ static int uct_stoch_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *po
         model->srec_wb = h_max <= 2 ? 2 : (h_max <= 4 ? 4 : -1);
     }
     const int wb = fuse_ok && model->srec_wb > 0 ? model->srec_wb : 0;
-    // sampling thresholds of the model's rows (rows that are not fused), built once per model on the device (numpy's cumsum /
-    // division order)
-    if (mode != MP_MODE_DETERMINISTIC && !model->thr && (!wb || mode == MP_MODE_SPARSE)) {
-        if (hipMalloc(&model->thr, (size_t)rows * W * sizeof(uint64_t)) != hipSuccess)
-            return fail(MP_ERR_ALLOC, "mp_uct_plan_stochastic: %zu B for the sampling thresholds", (size_t)rows * W * 8);
-        hipLaunchKernelGGL(build_thresholds, dim3((unsigned)((rows + 127) / 128)), dim3(128), 0, st, rows, W, model->P, model->thr);
-        MP_HIP(hipGetLastError());
-    }
+    // sampling thresholds of the model's rows (rows that are not fused)
+    if (mode != MP_MODE_DETERMINISTIC && (!wb || mode == MP_MODE_SPARSE)) MP_TRY(ensure_thresholds(ctx, "mp_uct_plan_stochastic", model));
     if (wb && !model->srec) {
         if (hipMalloc(&model->srec, (size_t)rows * wb * sizeof(uint4)) != hipSuccess)
             return fail(MP_ERR_ALLOC, "mp_uct_plan_stochastic: %zu B for the fused records", (size_t)rows * wb * sizeof(uint4));
@@ -890,31 +852,68 @@ static int uct_stoch_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *po
             }
         }
     }
-    const int wbk = wb ? model->srec_wb : 0; // the form the records really have (1: compact)
+    *wbk = wb ? model->srec_wb : 0;
+    return MP_OK;
+}
 
-    // per-call tables, computed on the host exactly as Python computes them (see uct_plan_impl)
+// the kernel of a record form (wbk), path-entry width (p16), |A| = at (0: the loop forms, any |A|) and policy kind (sp: per state)
+typedef void (*uct_stoch_kernel_t)(StochArgs);
+static uct_stoch_kernel_t uct_stoch_kernel_of(int wbk, bool p16, int at, bool sp)
+{
+    typedef uct_stoch_kernel_t kernel_t;
+#define MP_ROW(WBV, PTV) {uct_stoch_kernel<WBV, 0, PTV>, uct_stoch_kernel<WBV, 0, PTV>, uct_stoch_kernel<WBV, 2, PTV>, \
+                          uct_stoch_kernel<WBV, 3, PTV>, uct_stoch_kernel<WBV, 4, PTV>, uct_stoch_kernel<WBV, 5, PTV>, \
+                          uct_stoch_kernel<WBV, 6, PTV>, uct_stoch_kernel<WBV, 7, PTV>, uct_stoch_kernel<WBV, 8, PTV>}
+    static const kernel_t table16[4][9] = {MP_ROW(0, uint16_t), MP_ROW(2, uint16_t), MP_ROW(4, uint16_t), MP_ROW(1, uint16_t)};
+    static const kernel_t table32[4][9] = {MP_ROW(0, int32_t), MP_ROW(2, int32_t), MP_ROW(4, int32_t), MP_ROW(1, int32_t)};
+#undef MP_ROW
+#define MP_ROWP(WBV) {uct_stoch_kernel<WBV, 2, int32_t, true>, uct_stoch_kernel<WBV, 3, int32_t, true>, uct_stoch_kernel<WBV, 4, int32_t, true>, \
+                      uct_stoch_kernel<WBV, 5, int32_t, true>, uct_stoch_kernel<WBV, 6, int32_t, true>, uct_stoch_kernel<WBV, 7, int32_t, true>, \
+                      uct_stoch_kernel<WBV, 8, int32_t, true>}
+    static const kernel_t table_sp[4][7] = {MP_ROWP(0), MP_ROWP(2), MP_ROWP(4), MP_ROWP(1)};
+#undef MP_ROWP
+    // per-state policies, |A| in 2..8: the unrolled forms; beyond (round 4): the loop forms -- any number of actions
+    static const kernel_t any_sp[4] = {uct_stoch_kernel<0, 0, int32_t, true>, uct_stoch_kernel<2, 0, int32_t, true>,
+                                       uct_stoch_kernel<4, 0, int32_t, true>, uct_stoch_kernel<1, 0, int32_t, true>};
+    const int wrow = wbk == 2 ? 1 : wbk == 4 ? 2 : wbk == 1 ? 3 : 0;
+    if (sp) return at ? table_sp[wrow][at - 2] : any_sp[wrow];
+    return (p16 ? table16 : table32)[wrow][at];
+}
+
+static int uct_stoch_plan_impl(mp_ctx *ctx, const UctPlan &c)
+{
+    mp_model *model = c.model;
+    const mp_policy *pol = c.pol;
+    const int32_t n_roots = c.n_roots, closed_loop = c.closed_loop, max_plan_len = c.max_plan_len, mem = c.mem;
+    if (!ctx || !model || !c.root_state || !c.rng_state || (!pol && (!c.prior_p || !c.rollout_p)))
+        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: NULL argument");
+    if (pol && (pol->model != model || pol->model_serial != model->serial || pol->ctx != ctx || !pol->lmask))
+        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic_policy: the policy was not loaded for this (stochastic) model");
+    if (!mem_valid(mem)) return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: unknown mem flags %d", mem);
+    const int mode = model->mode;
+    if (mode != MP_MODE_DETERMINISTIC && mode != MP_MODE_STOCHASTIC && mode != MP_MODE_SPARSE)
+        return fail(MP_ERR_MODE, "mp_uct_plan_stochastic: model mode %d is not a finite MDP", mode);
+    if (mode != MP_MODE_DETERMINISTIC && !c.env_rng_state)
+        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: a stochastic model needs the env's generator records");
+    if (mode == MP_MODE_STOCHASTIC && (model->M != 1 || model->Sc != model->S))
+        return fail(MP_ERR_MODE, "mp_uct_plan_stochastic: one full dense model [S,A,S] expected");
+    if (model->masked && !pol)
+        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: the model restricts its action sets: plan with a policy (mp_uct_plan_stochastic_policy)");
+    if (n_roots < 1 || c.episodes < 0 || c.horizon < 0 || max_plan_len < 0)
+        return fail(MP_ERR_ARG, "mp_uct_plan_stochastic: bad sizes (n_roots=%d episodes=%d horizon=%d)", n_roots, c.episodes, c.horizon);
+    const int A = model->A, S = model->S, H = c.horizon, E = c.episodes;
+    const int W = mode == MP_MODE_STOCHASTIC ? S : (mode == MP_MODE_SPARSE ? model->B : 0);
+    MP_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int wbk = 0;
+    MP_TRY(stoch_records_ensure(ctx, model, &wbk));
+
     int TE = E < 512 ? E : 512; // the quotient tables live in LDS: longer plans divide beyond them
     // (any number of actions: the [A][TE + 2] table of the state-independent prior must leave room for the path stack; counts
     // beyond the tables take the IEEE division itself -- the same quotients)
     while (TE > 1 && (size_t)A * (TE + 2) * sizeof(double) > 24 * 1024) TE >>= 1;
-    const size_t ntab = (size_t)(H + 1) + 2 * (size_t)A + (size_t)(TE + 1) + (size_t)A * (TE + 2);
-    std::vector<double> tab(ntab);
-    double *gpow = tab.data(), *cdf = gpow + (H + 1), *tpv = cdf + A, *rcp = tpv + A, *tpdiv = rcp + (TE + 1);
-    for (int h = 0; h <= H; ++h) gpow[h] = pow(gamma, (double)h);
-    double acc = 0.0;
-    for (int a = 0; a < A; ++a) { acc += pol ? 1.0 : rollout_p[a]; cdf[a] = acc; }
-    for (int a = 0; a < A; ++a) {
-        const double scaled = ceil(ldexp(cdf[a] / acc, 53));
-        const uint64_t t = scaled >= 18446744073709551615.0 ? ~0ULL : (uint64_t)scaled;
-        memcpy(&cdf[a], &t, sizeof(t));
-    }
-    for (int a = 0; a < A; ++a) tpv[a] = temperature * (double)A * (pol ? 0.0 : prior_p[a]); // mcts.py:286, left to right
-    rcp[0] = 0.0;
-    for (int n = 1; n <= TE; ++n) rcp[n] = 1.0 / (double)n;                    // mcts.py:257: 1 / count
-    for (int a = 0; a < A; ++a) {
-        tpdiv[(size_t)a * (TE + 2)] = 0.0;
-        for (int n = 1; n <= TE + 1; ++n) tpdiv[(size_t)a * (TE + 2) + n] = tpv[a] / (double)n; // mcts.py:286: / (count + 1)
-    }
+    std::vector<double> tab;
+    const size_t ntab = uct_tables(H, A, TE, c.gamma, c.temperature, c.prior_p, c.rollout_p, tab).n;
     double *d_tab = nullptr;
     MP_TRY(upload_tables(ctx, 7, tab, &d_tab));
 
@@ -922,15 +921,10 @@ static int uct_stoch_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *po
     // observation node -- the descent stops at a new node, which has no children yet (mcts.py:143-149)
     const long cap = 1 + (long)E * ((long)A + (closed_loop ? 1 : 0));
     // step_strategy "subtree" (open loop): the trees kept by mp_uct_step_tree are re-rooted into the other buffer with room
-    // for this plan's expansions; a kept subtree only holds nodes of the last `horizon` plans (see uct_plan_impl)
+    // for this plan's expansions
     const bool cont = ctx->tree.armed && ctx->tree.kind == 4 && ctx->tree.K == 0 && !closed_loop && ctx->tree.n_roots == n_roots &&
                       ctx->tree.A == A && ctx->tree.sp == (pol != nullptr);
-    long cap_use = cap;
-    if (cont) {
-        const long now = 1 + (long)H * E * A;
-        if (now > ctx->tree.kept_bound) ctx->tree.kept_bound = now;
-        cap_use = (ctx->tree.cap < ctx->tree.kept_bound ? (long)ctx->tree.cap : ctx->tree.kept_bound) + (long)E * A;
-    }
+    const long cap_use = cont ? uct_kept_cap(ctx, H, E, A) : cap;
     const bool p16 = cap_use <= 65535 && !pol; // (the per-state-policy kernels are built with 32-bit path entries only)
     // path stack entries: the root + one per level, two per level in closed loop (action node, observation node)
     const size_t lds = (ntab + (wbk == 1 ? 256 : 0)) * sizeof(double) + (size_t)(closed_loop ? 2 * H + 2 : H + 2) * 64 * (p16 ? sizeof(uint16_t) : sizeof(int32_t));
@@ -943,11 +937,11 @@ static int uct_stoch_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *po
     a.table_n = TE;
     a.max_plan_len = max_plan_len;
     a.T = model->T; a.thr = model->thr; a.nxt = model->NXT; a.R = model->R; a.term = model->term; a.tab = d_tab;
-    a.srec = wb ? model->srec : nullptr;
+    a.srec = wbk ? model->srec : nullptr;
     a.rtab = model->srec_rtab;
     a.pol_prior = pol ? pol->prior : nullptr; a.pol_thr = pol ? pol->thr : nullptr; a.pol_mask = pol ? pol->lmask : nullptr;
     a.pol_listed = pol ? pol->listed8 : nullptr;
-    a.pol_rslot = pol ? pol->rslot : nullptr; a.pol_stride = pol ? pol->stride : 0; a.temperature = temperature;
+    a.pol_rslot = pol ? pol->rslot : nullptr; a.pol_stride = pol ? pol->stride : 0; a.temperature = c.temperature;
     if (cont) MP_TRY(uct_stoch_reroot_now(ctx, cap_use)); // (reads the kept trees' sizes: before WS_TREE1 may grow to a larger selection)
     MP_TRY(ws_get(ctx, WS_TREE1, (size_t)n_roots, &a.n_nodes_out)); // per-root tree sizes (updated in place by re-rooting and planning)
     if (cont) {
@@ -955,80 +949,48 @@ static int uct_stoch_plan_impl(mp_ctx *ctx, mp_model *model, const mp_policy *po
         a.cold = (SCold *)ctx->ws[ctx->tree.sp && ctx->tree.buf ? WS_TREE6 : WS_TREE2].p;
         a.n_nodes_in = a.n_nodes_out;
     } else {
-        ctx->tree.buf = 0;
-        ctx->tree.n_src = 0;
+        uct_fresh_tree(ctx, H, E, A); // (only now: a call refused above leaves the trees of the last plan as they are)
         ctx->tree.sp = pol != nullptr;
-        ctx->tree.kept_bound = 1 + (long)H * E * A;
         MP_TRY(ws_get(ctx, WS_TREE0, (size_t)n_roots * cap_use, &a.hot));
         MP_TRY(ws_get(ctx, WS_TREE2, (size_t)n_roots * cap_use, &a.cold));
     }
-    ctx->tree.kind = 4; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap_use; ctx->tree.armed = false;
+    ctx->tree.kind = 4; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap_use;
     ctx->tree.K = closed_loop ? 1 : 0;
 
-    int32_t *d_rs = nullptr, *d_st = nullptr;
-    MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n_roots, amem, &d_rs));
-    if (root_steps) MP_TRY(stage_in(ctx, WS_IO1, root_steps, (size_t)n_roots, amem, &d_st));
-    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n_roots * 6, rmem, &a.rng));
-    uint64_t *d_erng = nullptr;
-    if (env_rng_state) MP_TRY(stage_in(ctx, WS_IO9, env_rng_state, (size_t)n_roots * 6, amem, &d_erng));
-    a.env_rng = d_erng;
-    a.root_state = d_rs; a.root_steps = d_st;
-    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n_roots * max_plan_len, amem, &a.plans));
-    MP_TRY(stage_out_alloc(ctx, WS_IO4, plan_len, (size_t)n_roots, amem, &a.plan_len));
-    MP_TRY(stage_out_alloc(ctx, WS_IO5, root_value, (size_t)n_roots, amem, &a.root_value));
-    MP_TRY(stage_out_alloc(ctx, WS_IO6, root_child_count, (size_t)n_roots * A, amem, &a.root_child_count));
-    MP_TRY(stage_out_alloc(ctx, WS_IO7, root_child_value, (size_t)n_roots * A, amem, &a.root_child_value));
-    MP_TRY(stage_out_alloc(ctx, WS_IO8, env_steps, (size_t)n_roots, amem, &a.env_steps));
+    // the caller's arrays, aliased or copied per array (wave_stage): root states, steps, both generators in; the results out
+    WaveIo io(mem_arrays(mem), mem_rng(mem), n_roots);
+    io.in(WS_IO0, (const int32_t *)c.root_state, &a.root_state);
+    io.in(WS_IO1, c.root_steps, &a.root_steps);
+    io.rng(c.rng_state, &a.rng);
+    io.in(WS_IO9, c.env_rng_state, &a.env_rng, 6);
+    io.add(WS_IO3, c.plans, &a.plans, max_plan_len);
+    io.add(WS_IO4, c.plan_len, &a.plan_len);
+    io.add(WS_IO5, c.root_value, &a.root_value);
+    io.add(WS_IO6, c.root_child_count, &a.root_child_count, A);
+    io.add(WS_IO7, c.root_child_value, &a.root_child_value, A);
+    io.add(WS_IO8, c.env_steps, &a.env_steps);
+    MP_TRY(wave_stage(ctx, io));
 
     // mp_uct_record_visits armed this call: every env step of the plan is counted by the state it lands in
     int32_t *visits_host = ctx->visits_host;
     ctx->visits_host = nullptr;
     if (visits_host) {
-        if (amem != MP_MEM_HOST) return fail(MP_ERR_ARG, "mp_uct_record_visits: the recording call takes host arrays");
+        if (io.mem != MP_MEM_HOST) return fail(MP_ERR_ARG, "mp_uct_record_visits: the recording call takes host arrays");
         MP_TRY(ws_get(ctx, WS_VI4, (size_t)n_roots * S, &a.visits)); // (a value-iteration slot: idle during a plan)
         MP_HIP(hipMemsetAsync(a.visits, 0, (size_t)n_roots * S * sizeof(int32_t), st));
     }
     MP_TRY(kernels_begin(ctx));
-    {
-        typedef void (*kernel_t)(StochArgs);
-#define MP_ROW(WBV, PTV) {uct_stoch_kernel<WBV, 0, PTV>, uct_stoch_kernel<WBV, 0, PTV>, uct_stoch_kernel<WBV, 2, PTV>, \
-                          uct_stoch_kernel<WBV, 3, PTV>, uct_stoch_kernel<WBV, 4, PTV>, uct_stoch_kernel<WBV, 5, PTV>, \
-                          uct_stoch_kernel<WBV, 6, PTV>, uct_stoch_kernel<WBV, 7, PTV>, uct_stoch_kernel<WBV, 8, PTV>}
-        static const kernel_t table16[4][9] = {MP_ROW(0, uint16_t), MP_ROW(2, uint16_t), MP_ROW(4, uint16_t), MP_ROW(1, uint16_t)};
-        static const kernel_t table32[4][9] = {MP_ROW(0, int32_t), MP_ROW(2, int32_t), MP_ROW(4, int32_t), MP_ROW(1, int32_t)};
-#undef MP_ROW
-#define MP_ROWP(WBV) {uct_stoch_kernel<WBV, 2, int32_t, true>, uct_stoch_kernel<WBV, 3, int32_t, true>, uct_stoch_kernel<WBV, 4, int32_t, true>, \
-                      uct_stoch_kernel<WBV, 5, int32_t, true>, uct_stoch_kernel<WBV, 6, int32_t, true>, uct_stoch_kernel<WBV, 7, int32_t, true>, \
-                      uct_stoch_kernel<WBV, 8, int32_t, true>}
-        static const kernel_t table_sp[4][7] = {MP_ROWP(0), MP_ROWP(2), MP_ROWP(4), MP_ROWP(1)};
-#undef MP_ROWP
-        const char *ag = getenv("MP_UCT_STOCH_GENERIC_A"); // "1": the loop form of the selection for any |A| -- test hook
-        const int at = A >= 2 && A <= 8 && !(ag && ag[0] == '1') ? A : 0;
-        const int wrow = wbk == 2 ? 1 : wbk == 4 ? 2 : wbk == 1 ? 3 : 0;
-        form_record(ctx->last_variant, uct_stoch_form_name(wbk, p16, at, pol != nullptr));
-        if (pol) {
-            static const kernel_t any_sp[4] = {uct_stoch_kernel<0, 0, int32_t, true>, uct_stoch_kernel<2, 0, int32_t, true>,
-                                               uct_stoch_kernel<4, 0, int32_t, true>, uct_stoch_kernel<1, 0, int32_t, true>};
-            if (A < 2) return fail(MP_ERR_ARG, "mp_uct_plan_stochastic_policy: |A| = %d", A);
-            // |A| in 2..8: the unrolled forms; beyond (round 4): the loop forms -- any number of actions
-            hipLaunchKernelGGL(at ? table_sp[wrow][A - 2] : any_sp[wrow], dim3((unsigned)((n_roots + 63) / 64)), dim3(64), lds, st, a);
-        } else {
-            hipLaunchKernelGGL((p16 ? table16 : table32)[wrow][at], dim3((unsigned)((n_roots + 63) / 64)), dim3(64), lds, st, a);
-        }
-    }
+    const char *ag = getenv("MP_UCT_STOCH_GENERIC_A"); // "1": the loop form of the selection for any |A| -- test hook
+    const int at = A >= 2 && A <= 8 && !(ag && ag[0] == '1') ? A : 0;
+    form_record(ctx->last_variant, uct_stoch_form_name(wbk, p16, at, pol != nullptr));
+    if (pol && A < 2) return fail(MP_ERR_ARG, "mp_uct_plan_stochastic_policy: |A| = %d", A);
+    hipLaunchKernelGGL(uct_stoch_kernel_of(wbk, p16, at, pol != nullptr), dim3((unsigned)((n_roots + 63) / 64)), dim3(64), lds, st, a);
     MP_TRY(kernels_end(ctx, 1));
     MP_HIP(hipGetLastError());
 
-    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n_roots * 6, rmem));
-    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n_roots * max_plan_len, amem));
-    MP_TRY(stage_out_copy(ctx, plan_len, a.plan_len, (size_t)n_roots, amem));
-    MP_TRY(stage_out_copy(ctx, root_value, a.root_value, (size_t)n_roots, amem));
-    MP_TRY(stage_out_copy(ctx, root_child_count, a.root_child_count, (size_t)n_roots * A, amem));
-    MP_TRY(stage_out_copy(ctx, root_child_value, a.root_child_value, (size_t)n_roots * A, amem));
-    MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n_roots, amem));
+    // (the visit counts are queued before wave_unstage synchronises a host call)
     if (visits_host) MP_HIP(hipMemcpyAsync(visits_host, a.visits, (size_t)n_roots * S * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    if (amem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
-    return MP_OK;
+    return wave_unstage(ctx, io);
 }
 
 extern "C" {
@@ -1046,9 +1008,9 @@ int mp_uct_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const 
                            int32_t max_plan_len, int32_t *plans, int32_t *plan_len, double *root_value,
                            int64_t *root_child_count, double *root_child_value, int64_t *env_steps, int32_t mem)
 {
-    return uct_stoch_plan_impl(ctx, model, nullptr, n_roots, root_state, root_steps, episodes, horizon, gamma, temperature, prior_p,
-                               rollout_p, closed_loop, rng_state, env_rng_state, max_plan_len, plans, plan_len, root_value,
-                               root_child_count, root_child_value, env_steps, mem);
+    return uct_stoch_plan_impl(ctx, {model, nullptr, n_roots, root_state, root_steps, episodes, horizon, gamma, temperature, prior_p,
+                                     rollout_p, closed_loop, rng_state, env_rng_state, max_plan_len, plans, plan_len, root_value,
+                                     root_child_count, root_child_value, env_steps, mem});
 }
 
 int mp_uct_plan_stochastic_policy(mp_ctx *ctx, mp_model *model, mp_policy *policy, int32_t n_roots, const int32_t *root_state,
@@ -1058,9 +1020,9 @@ int mp_uct_plan_stochastic_policy(mp_ctx *ctx, mp_model *model, mp_policy *polic
                                   double *root_child_value, int64_t *env_steps, int32_t mem)
 {
     if (!policy) return fail(MP_ERR_ARG, "mp_uct_plan_stochastic_policy: policy is NULL");
-    return uct_stoch_plan_impl(ctx, model, policy, n_roots, root_state, root_steps, episodes, horizon, gamma, temperature, nullptr,
-                               nullptr, closed_loop, rng_state, env_rng_state, max_plan_len, plans, plan_len, root_value,
-                               root_child_count, root_child_value, env_steps, mem);
+    return uct_stoch_plan_impl(ctx, {model, policy, n_roots, root_state, root_steps, episodes, horizon, gamma, temperature, nullptr,
+                                     nullptr, closed_loop, rng_state, env_rng_state, max_plan_len, plans, plan_len, root_value,
+                                     root_child_count, root_child_value, env_steps, mem});
 }
 
 int mp_env_step_stochastic(mp_ctx *ctx, mp_model *model, int32_t n, int32_t *state, int32_t *steps, uint8_t *alive,
@@ -1077,7 +1039,7 @@ int mp_env_step_stochastic(mp_ctx *ctx, mp_model *model, int32_t n, int32_t *sta
         return fail(MP_ERR_MODE, "mp_env_step_stochastic: one full dense model [S,A,S] expected");
     if (n < 1 || plan_stride < 1 || max_steps < 1) return fail(MP_ERR_ARG, "mp_env_step_stochastic: bad sizes");
     MP_HIP(hipSetDevice(ctx->device));
-    MP_TRY(ensure_thresholds(ctx, model));
+    MP_TRY(ensure_thresholds(ctx, "mp_env_step_stochastic", model));
     MP_HIP(hipMemsetAsync(n_alive, 0, sizeof(int32_t), ctx->stream));
     const int W = model->mode == MP_MODE_STOCHASTIC ? model->S : model->B;
     hipLaunchKernelGGL(env_step_stoch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, model->A,

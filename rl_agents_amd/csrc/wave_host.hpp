@@ -39,27 +39,46 @@ inline int wave_mdp_check(const char *who, const mp_model *model, bool each)
 }
 
 template <typename Args>
-inline int wave_mdp(mp_ctx *ctx, mp_model *model, Args *a)
+inline int wave_mdp(mp_ctx *ctx, const char *who, mp_model *model, Args *a)
 {
-    if (model->mode != MP_MODE_DETERMINISTIC) MP_TRY(ensure_thresholds(ctx, model));
+    if (model->mode != MP_MODE_DETERMINISTIC) MP_TRY(ensure_thresholds(ctx, who, model));
     a->mode = model->mode; a->W = model->mode == MP_MODE_STOCHASTIC ? model->S : model->B;
     a->rec = model->rec; a->thr = model->thr; a->nxt = model->NXT; a->R = model->R;
     return MP_OK;
 }
 
-// ---- the caller's arrays of a plan call and their device side: the root states and the generator records in (WS_IO0, WS_IO2),
-// then the results a planner adds, `per_root` elements a root, each with the workspace slot that backs a host array
+// ---- the caller's arrays of a plan call and their device side, named once: inputs (root states, optional ones such as
+// root_steps), the generator records (in and out, following their own flag rmem: MP_MEM_RNG_DEVICE is an mp_rng) and the results
+// a planner adds, `per_root` elements a root, each with the workspace slot that backs a host array.  The generator records are
+// named before the results.  (mp_uct_plan reads the same table with a staging of its own: uct.hip.)
 struct WaveIo {
-    struct Item { void *host; void **dev; size_t bytes; int slot; };
+    enum { IN = 1, OUT = 2 };
+    struct Item {
+        void *host; void **dev;   // the caller's array (NULL: an optional one left out) and where the args struct keeps its device side
+        size_t per_root;          // bytes a root
+        int slot, dir, mem;       // workspace slot; IN, OUT or both; the memory flag it follows
+        char *base;               // mp_uct_plan: the device side of root 0 (*dev moves from chunk to chunk)
+    };
     Item item[10];
     int n = 0, mem, rmem, n_roots;
+    size_t bytes(const Item &t) const { return n_roots * t.per_root; }
     template <typename T, typename D>
-    void add(int slot, T *host, D **dev, size_t per_root = 1) { item[n++] = {(void *)host, (void **)dev, n_roots * per_root * sizeof(T), slot}; }
-    WaveIo(int mem, int rmem, int n_roots, const int32_t *root_state, const int32_t **d_root_state, uint64_t *rng_state, uint64_t **d_rng)
-        : mem(mem), rmem(rmem), n_roots(n_roots)
+    void put(int slot, T *host, D **dev, size_t per_root, int dir, int flag)
     {
-        add(WS_IO0, root_state, d_root_state);
-        add(WS_IO2, rng_state, d_rng, 6);
+        item[n++] = {(void *)host, (void **)dev, per_root * sizeof(T), slot, dir, flag, nullptr};
+    }
+    template <typename T, typename D>
+    void add(int slot, T *host, D **dev, size_t per_root = 1) { put(slot, host, dev, per_root, OUT, mem); }   // a result
+    template <typename T, typename D>
+    void in(int slot, T *host, D **dev, size_t per_root = 1) { put(slot, host, dev, per_root, IN, mem); }     // an input
+    template <typename D>
+    void rng(uint64_t *rng_state, D **d_rng) { put(WS_IO2, rng_state, d_rng, 6, IN | OUT, rmem); }
+    WaveIo(int mem, int rmem, int n_roots) : mem(mem), rmem(rmem), n_roots(n_roots) {}
+    WaveIo(int mem, int rmem, int n_roots, const int32_t *root_state, const int32_t **d_root_state, uint64_t *rng_state, uint64_t **d_rng)
+        : WaveIo(mem, rmem, n_roots)
+    {
+        in(WS_IO0, root_state, d_root_state);
+        rng(rng_state, d_rng);
     }
 };
 
@@ -67,9 +86,9 @@ inline int wave_stage(mp_ctx *ctx, const WaveIo &io)
 {
     for (int i = 0; i < io.n; ++i) {
         const WaveIo::Item &t = io.item[i];
-        char *d = nullptr;
-        if (i < 2) MP_TRY(stage_in(ctx, t.slot, (const char *)t.host, t.bytes, i ? io.rmem : io.mem, &d));
-        else MP_TRY(stage_out_alloc(ctx, t.slot, (char *)t.host, t.bytes, io.mem, &d));
+        char *d = nullptr; // (an array left out stays null: the kernels skip it)
+        if (t.host && (t.dir & WaveIo::IN)) MP_TRY(stage_in(ctx, t.slot, (const char *)t.host, io.bytes(t), t.mem, &d));
+        else if (t.host) MP_TRY(stage_out_alloc(ctx, t.slot, (char *)t.host, io.bytes(t), t.mem, &d));
         *t.dev = d; // (stored as a void *: the type that may alias the args struct's pointer of any type)
     }
     return MP_OK;
@@ -78,8 +97,10 @@ inline int wave_stage(mp_ctx *ctx, const WaveIo &io)
 // the generator records back first, then the results in the order they were named; host arrays are complete on return
 inline int wave_unstage(mp_ctx *ctx, const WaveIo &io)
 {
-    for (int i = 1; i < io.n; ++i)
-        MP_TRY(stage_out_copy(ctx, (char *)io.item[i].host, (const char *)*io.item[i].dev, io.item[i].bytes, i == 1 ? io.rmem : io.mem));
+    for (int i = 0; i < io.n; ++i) {
+        const WaveIo::Item &t = io.item[i];
+        if (t.dir & WaveIo::OUT) MP_TRY(stage_out_copy(ctx, (char *)t.host, (const char *)*t.dev, io.bytes(t), t.mem));
+    }
     if (io.mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(ctx->stream));
     return MP_OK;
 }
