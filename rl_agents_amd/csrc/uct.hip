@@ -30,7 +30,9 @@
 //           episode: the backup stores value and count in one 12-byte store, and the leaf whole (16 bytes) with the first_child
 //           its expansion assigned -- no store of its own for that.  The forms that gather the model from global memory write
 //           the zero nodes of a wave's expansions lane-contiguously (the group-interleaved layout: one run per group and wave)
-//           instead of |A| strided nodes per lane (uct_kernel, TREE STORES; profiles/uct_tree_stores.md).
+//           instead of |A| strided nodes per lane (uct_kernel, TREE STORES; profiles/uct_tree_stores.md).  The children of a node
+//           that was visited once are all zero nodes: they are not loaded, and a fresh tree does not store them before they are
+//           entered (uct_kernel, VIRGIN GROUPS; uct_virgin.hpp; profiles/uct_virgin_groups.md).
 //   path    per-lane stack of visited node ids in LDS ([depth][lane], conflict-free): the backup
 //           walks known addresses, not parent pointers.
 #include <limits.h>
@@ -48,6 +50,7 @@
 #include "libm_sincos.hpp"
 #include "pcg64.hpp"
 #include "uct_host.hpp"
+#include "uct_virgin.hpp"
 #include "wave.hpp"
 
 namespace mp {
@@ -108,6 +111,7 @@ struct UctArgs {
     int rep_shift; // CartPole: a root is replicated over 2^rep_shift lanes (see the launch code: wavefronts of few ACTIVE lanes run slow)
     int waves; // wavefronts per workgroup
     int tree_stores; // 1: a full wave writes its expansions' zero nodes lane-contiguously and the backup stores the leaf whole;
+                     // 2 (the default): as 1, and virgin groups are not loaded and, in fresh trees, not stored (VIRGIN GROUPS below);
                      // 0 (MP_UCT_TREE_STORES=lane, an A/B knob): every store per lane, first_child of an expanded node on its own
     int Sb;    // batch models: states per MDP (root r plans on MDP root_state[r] / Sb); = S for any other model
     const Rec *rec;
@@ -334,6 +338,17 @@ void uct_kernel(UctArgs p)
     constexpr int WEXP_PASSES = 4;   // wave-wide passes per expansion, one per distinct tree size (fresh trees: 2-4 sizes per wave)
     constexpr bool LEAF1 = AT > 0 && !(LDSR && !QD && AT >= 7);
     const bool leaf1 = LEAF1 && p.tree_stores != 0;
+    // VIRGIN GROUPS (profiles/uct_virgin_groups.md).  A node expands on its first visit only, so a node with children and count 1
+    // has not been entered since: its children are all {0.0, 0, -1}.  VSKIP: the selection that stands in such a node takes the
+    // constant instead of loading the group (kept trees too: a node that expands late there gets count >= 2).  VDEFER, fresh
+    // trees only: the expansion stores no zero group at all -- most groups are never entered again -- and the first entry stores
+    // the |A| - 1 siblings it does not pick; the picked one is the episode's leaf, which the backup stores whole (LEAF1).  Until
+    // then the group's memory holds whatever was there: every reader applies the rule (uct_virgin.hpp; the host marks the trees).
+    // p.tree_stores == 2 (the default) runs both, 1 (MP_UCT_TREE_STORES=group) neither.
+    constexpr bool VSKIP = uct_virgin_form(AT, ENV, SP, MK, IL, QD);
+    constexpr bool VDEFER = VSKIP && LEAF1;
+    const bool vskip = VSKIP && p.tree_stores == 2;
+    const bool vdefer = VDEFER && p.tree_stores == 2 && p.n_nodes_in == nullptr;
     bool wave_exp = false;
     if constexpr (WEXP) {
         const int wave_r0 = (blockIdx.x * p.waves + __builtin_amdgcn_readfirstlane(wave)) * 64;
@@ -469,6 +484,7 @@ void uct_kernel(UctArgs p)
         // quotient of the episode is in the tables -- fresh trees of at most TE episodes never leave them.  Wave-uniform, so what
         // a level and a backup pay for the division is one scalar branch.
         const bool beyond = RC && any64(tc0 >= TE);
+        int node_c = 0; // VSKIP: the count of the node the descent stands in (below the root: the picked child's, as read)
         // ---- selection, mcts.py:143-149
         while (owner && depth < H && fc >= 0 && !terminal) {
             // MCTSNode.selection_strategy (mcts.py:275-286): value + temperature*|A|*prior/(count+1);
@@ -477,9 +493,14 @@ void uct_kernel(UctArgs p)
             int act = 0, nfc = -1;
             if (AT > 0) {
                 UctNode c[AR];
+                bool virgin = false;
                 if (fc == 1) { // the root's children: registers
 #pragma unroll
                     for (int a = 0; a < AR; ++a) { c[a].value = tv[a]; c[a].count = tc[a]; c[a].first_child = tf[a]; }
+                } else if (VSKIP && vskip && node_c == 1) { // a virgin group: nothing to load
+                    virgin = true;
+#pragma unroll
+                    for (int a = 0; a < AR; ++a) { c[a].value = 0.0; c[a].count = 0; c[a].first_child = -1; }
                 } else {
                     UctNode *grp = &tree.child(fc, 0);
 #pragma unroll
@@ -544,6 +565,19 @@ void uct_kernel(UctArgs p)
 #pragma unroll
                 for (int i = 0; i < KEEP; ++i)
                     if (depth + 1 == 2 + i) { kv[i] = sel_v; kc[i] = sel_c; }
+                node_c = sel_c;
+                if (VDEFER && vdefer && virgin) {
+                    // the first entry of a group no expansion stored: the siblings of the pick (the backup stores the pick whole) --
+                    // and the pick too where the backup READS a node's statistics back before it stores them (below the levels
+                    // whose statistics stay in registers: rare)
+                    UctNode z;
+                    z.value = 0.0; z.count = 0; z.first_child = -1;
+                    UctNode *grp = &tree.child(fc, 0);
+                    const bool deep = depth + 1 >= 2 + KEEP;
+#pragma unroll
+                    for (int a = 0; a < AR; ++a)
+                        if (a != act || deep) tree.sibling(grp, a) = z;
+                }
             } else {
                 double m = 0.0;
                 for (int a = 0; a < A; ++a) {
@@ -626,6 +660,8 @@ void uct_kernel(UctArgs p)
                         tree.sibling(grp, a) = n;
                     }
                 }
+            } else if (VDEFER && vdefer) {
+                // (no zero group: the selection that enters it first completes it)
             } else if (!(RC && node == 0)) { // the root's children were zero-initialised in registers
                 if constexpr (WEXP) {
                     wexp_pend = true;
@@ -1339,7 +1375,14 @@ void uct_kernel(UctArgs p)
     {
         int len = 0;
         int fc = tree[0].first_child;
+        int at_c = 0; // VDEFER: the count of the node whose children are read (the root's group is always stored)
         while (fc >= 0) {
+            if (VDEFER && vdefer && at_c == 1) {
+                // a group that was never stored, all {0.0, 0, -1}: the first action, whose node has no children
+                if (p.plans && len < p.max_plan_len) p.plans[(long)r * p.max_plan_len + len] = 0;
+                ++len;
+                break;
+            }
             int mc = tree.child(fc, 0).count;
             for (int a = 1; a < A; ++a) mc = max(mc, tree.child(fc, a).count);
             int best = -1;
@@ -1350,6 +1393,7 @@ void uct_kernel(UctArgs p)
             }
             if (p.plans && len < p.max_plan_len) p.plans[(long)r * p.max_plan_len + len] = best;
             ++len;
+            at_c = tree.child(fc, best).count;
             fc = tree.child(fc, best).first_child;
         }
         if (p.plans)
@@ -2174,25 +2218,29 @@ __global__ __launch_bounds__(SHARED ? 1024 : 256) void uct_row_kernel(UctArgs p)
     }
 }
 
-// AbstractPlanner.step_by_subtree (abstract.py:195-206), one root per lane: the subtree of the root's child
-// `action` is re-numbered breadth-first into the other tree buffer (children stay contiguous).  While a node
-// waits in the BFS queue its first_child field holds its OLD id.  A never-expanded root gives size 0 (fresh tree).
 // one thread: the visit count at the end of an action path (mp_uct_path_count)
+// `virgin`: the children of a count-1 node were never stored (uct_virgin.hpp) -- a path that enters them ends at a node of count 0
+// without children
 template <int IL>
-__global__ void uct_path_count_kernel(UctNode *trees, int root, int cap, int A, const int32_t *actions, int n, int64_t *out)
+__global__ void uct_path_count_kernel(UctNode *trees, int root, int cap, int A, const int32_t *actions, int n, int64_t *out, int virgin)
 {
     const TreeRef<IL, 0> tree = tree_of<IL, 0>(trees, root, cap, A);
     int node = 0;
+    bool unstored = false; // `node` is a child of a count-1 node
     for (int i = 0; i < n; ++i) {
-        const int fc = tree[node].first_child;
+        const int fc = unstored ? -1 : tree[node].first_child;
         const int a = actions[i];
         if (fc < 0 || a < 0 || a >= A) { out[0] = -1; return; }
+        unstored = virgin && tree[node].count == 1;
         node = fc + a;
     }
-    const int c = tree[node].count;
+    const int c = unstored ? 0 : tree[node].count;
     out[0] = c < 0 ? -1 : c; // (count < 0: the phantom slot of an action a listed policy does not list)
 }
 
+// AbstractPlanner.step_by_subtree (abstract.py:195-206), one root per lane: the subtree of the root's child
+// `action` is re-numbered breadth-first into the other tree buffer (children stay contiguous).  While a node
+// waits in the BFS queue its first_child field holds its OLD id.  A never-expanded root gives size 0 (fresh tree).
 // `source` (mp_uct_step_tree_select): new root r continues OLD root source[r] of the n_src old ones -- in any order, one source
 // for several new roots, a source outside the old batch = a fresh tree; then n_new is another array than n_old (a new root's
 // size must not overwrite an old root's before every lane has read its own).  source == nullptr: root r continues root r.
@@ -2201,7 +2249,8 @@ __global__ __launch_bounds__(64) void uct_reroot_kernel(int n_roots, int n_src, 
                                                         const UctNode *__restrict__ old_trees, UctNode *__restrict__ new_trees,
                                                         const int32_t *n_old, const int32_t *__restrict__ source,
                                                         const int32_t *__restrict__ actions,
-                                                        int32_t *n_new) // (n_old and n_new are the same array when source == nullptr)
+                                                        int32_t *n_new, // (n_old and n_new are the same array when source == nullptr)
+                                                        int virgin) // the old trees hold unstored groups (uct_virgin.hpp); the new ones are whole
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_roots) return;
@@ -2223,14 +2272,18 @@ __global__ __launch_bounds__(64) void uct_reroot_kernel(int n_roots, int n_src, 
     first.first_child = o[0].first_child + a;
     n[0] = first;
     while (head < tail) {
-        const UctNode src = o[n[head].first_child];
+        const int oid = n[head].first_child; // (-2: a child of a count-1 node of a tree with unstored groups -- the constant node)
+        UctNode src;
+        src.value = 0.0; src.count = 0; src.first_child = -1;
+        if (oid >= 0) src = o[oid];
         UctNode out;
         out.value = src.value; out.count = src.count; out.first_child = -1;
         if (src.first_child >= 0) {
             out.first_child = tail;
+            const bool unstored = virgin && src.count == 1;
             for (int c = 0; c < A; ++c) {
                 UctNode q;
-                q.value = 0.0; q.count = 0; q.first_child = src.first_child + c;
+                q.value = 0.0; q.count = 0; q.first_child = unstored ? -2 : src.first_child + c;
                 n[tail + c] = q;
             }
             tail += A;
@@ -2345,10 +2398,12 @@ static int uct_reroot_now(mp_ctx *ctx, long cap_new)
     const int old_slot = ctx->tree.buf ? WS_TREE2 : WS_TREE0, new_slot = ctx->tree.buf ? WS_TREE0 : WS_TREE2;
     UctNode *nw = nullptr;
     MP_TRY(ws_get(ctx, new_slot, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_new, ctx->tree.A), &nw));
+    const int virgin = ctx->tree.virgin ? 1 : 0;
+    ctx->tree.virgin = false; // (the re-rooted trees are whole)
     return reroot_apply(ctx, cap_new, [&](const Reroot &r) {
         hipLaunchKernelGGL(ctx->tree.il == 2 ? uct_reroot_kernel<2> : uct_reroot_kernel<0>, dim3((unsigned)((r.n_roots + 63) / 64)), dim3(64), 0,
                            ctx->stream, r.n_roots, r.n_src, r.A, r.cap_old, r.cap_new, (const UctNode *)ctx->ws[old_slot].p, nw, r.sizes, r.src,
-                           r.acts, r.sizes_new);
+                           r.acts, r.sizes_new, virgin);
     });
 }
 
@@ -2368,7 +2423,9 @@ struct UctKnobs {
     int row_waves, row_roots, lanes, cart_rep, cart_waves;   // MP_UCT_ROW_WAVES / ROW_ROOTS / LANES / CART_REP / CART_WAVES
     int path;         // MP_UCT_PATH: 1 "spill" (the register / global path stack, a test hook), 0 any other value
     long ldsr_waves;  // MP_UCT_LDSR_WAVES (LONG_MIN: not set)
-    int tree_stores;  // MP_UCT_TREE_STORES: 0 "lane" (the per-lane tree stores of uct_kernel, for A/B runs), 1 any other value or unset
+    int tree_stores;  // MP_UCT_TREE_STORES: 0 "lane" (the per-lane tree stores of uct_kernel, for A/B runs), 1 "group" (the wave's
+                      // expansions and the leaf's single store, every zero group stored and loaded), 2 any other value or unset
+                      // (virgin groups neither loaded nor, in fresh trees, stored)
 };
 static int uct_knob(const char *name)
 {
@@ -2389,7 +2446,7 @@ static UctKnobs uct_knobs_read()
     k.row_waves = uct_knob("MP_UCT_ROW_WAVES"); k.row_roots = uct_knob("MP_UCT_ROW_ROOTS"); k.lanes = uct_knob("MP_UCT_LANES");
     k.cart_rep = uct_knob("MP_UCT_CART_REP"); k.cart_waves = uct_knob("MP_UCT_CART_WAVES");
     const char *tree_stores = getenv("MP_UCT_TREE_STORES");
-    k.tree_stores = !(tree_stores && !strcmp(tree_stores, "lane"));
+    k.tree_stores = tree_stores && !strcmp(tree_stores, "lane") ? 0 : (tree_stores && !strcmp(tree_stores, "group") ? 1 : 2);
     return k;
 }
 
@@ -2799,6 +2856,10 @@ static int uct_trees(mp_ctx *ctx, const UctPlan &c, bool cont, const UctChoice &
         MP_TRY(ws_get(ctx, WS_TREE4, (size_t)(H + 1) * (size_t)a->spill_stride, &a->path_spill));
     }
     ctx->tree.kind = 1; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap_use;
+    // fresh trees of a form that leaves its virgin groups unstored (uct_kernel's VDEFER, uct_virgin.hpp): the readers apply the rule
+    const int env = ch.form == UF_LDSR ? ENV_TABLE_LDSR : (ch.form == UF_GLOBAL ? ENV_TABLE : (ch.form == UF_GLOBAL_SPILL ? ENV_TABLE_SPILL : -1));
+    ctx->tree.virgin = !cont && a->tree_stores == 2 && env >= 0 &&
+                       uct_virgin_form(A, env, false, false, ctx->tree.il, false);
     return MP_OK;
 }
 
@@ -3394,9 +3455,9 @@ int mp_uct_path_count(mp_ctx *ctx, int32_t root, const int32_t *actions, int32_t
     MP_TRY(ws_get(ctx, WS_IO1, (size_t)(n > 0 ? n : 1), &d_act));
     MP_TRY(ws_get(ctx, WS_IO8, 1, &d_out));
     if (n > 0) MP_HIP(hipMemcpyAsync(d_act, actions, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const int tcap = ctx->tree.cap, A = ctx->tree.A;
-    if (ctx->tree.il == 2) hipLaunchKernelGGL(uct_path_count_kernel<2>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out);
-    else hipLaunchKernelGGL(uct_path_count_kernel<0>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out);
+    const int tcap = ctx->tree.cap, A = ctx->tree.A, virgin = ctx->tree.virgin ? 1 : 0;
+    if (ctx->tree.il == 2) hipLaunchKernelGGL(uct_path_count_kernel<2>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out, virgin);
+    else hipLaunchKernelGGL(uct_path_count_kernel<0>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out, virgin);
     MP_HIP(hipGetLastError());
     MP_HIP(hipMemcpyAsync(count, d_out, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     MP_HIP(hipStreamSynchronize(st));
@@ -3426,9 +3487,8 @@ int mp_uct_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes,
         MP_HIP(hipMemcpy(h.data(), trees + (long)root * tcap, (size_t)tcap * sizeof(UctNode), hipMemcpyDeviceToHost));
     // node slots are appended A at a time; the tree in use is the closure of first_child links.  Slots with
     // count < 0 are the phantoms of actions a listed policy did not list (uct_kernel<.., MK>): they are not nodes.
-    int n = 1;
-    for (int i = 0; i < n && i < tcap; ++i)
-        if (h[i].first_child >= 0 && h[i].first_child + A > n) n = h[i].first_child + A;
+    // Groups a fresh-tree plan never stored (the children of a count-1 node) get the constant node first.
+    const int n = uct_virgin_fill(h.data(), tcap, A, ctx->tree.virgin);
     std::vector<int32_t> id((size_t)n, -1);
     int kept = 0;
     for (int i = 0; i < n; ++i)
