@@ -10,12 +10,27 @@
 // Keeping the generator state per root on the device and stepping it exactly like numpy makes
 // UCT plans bit-identical to the reference at equal seeds (no "tolerance parity" needed).
 // PCG64 = 128-bit LCG (multiplier 0x2360ED051FC65DA44385DF649FCCF645) + XSL-RR 128/64 output.
+//
+// Two per-lane forms: Pcg64 (state and increment as 64-bit halves; every planner) and Pcg64W (the same generator on four 32-bit
+// words, at the end of this file; the one-lane table rollouts of uct_kernel).  Pcg64W is plain C++ outside a HIP compilation: a
+// host compiler that includes this header gets Pcg64W alone (tests/host/pcg64_words_check.cpp).
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define MP_PCG_FN __device__ __forceinline__
+#else
+#define MP_PCG_FN inline
+#endif
+#if defined(__has_builtin)
+#if __has_builtin(__builtin_addc)
+#define MP_PCG_HAS_ADDC 1
+#endif
+#endif
 
 namespace mp {
 
+#if defined(__HIPCC__)
 struct Pcg64 {
     uint64_t s_hi, s_lo, inc_hi, inc_lo;
     uint32_t has_uint32, uinteger;
@@ -35,7 +50,9 @@ struct Pcg64 {
     // d = a * m + c as one v_mad_u64_u32 (32 x 32 + 64 -> 64); the instruction's carry-out lane mask goes to a dead SGPR pair.
     // The multiplier limb sits in an SGPR (one constant-bus operand); written as inline assembly because the compiler
     // otherwise expands the schoolbook product into twice as many instructions (zero-extending moves, multiplies by a
-    // literal 0 used as 64-bit adds: 60 VALU instructions per step against the 27 of this form).
+    // literal 0 used as 64-bit adds: 60 VALU instructions per step; next64 of this form compiles to 35 in isolation -- the 14
+    // of the step proper plus moves that build the 64-bit addend pairs, compares and selects that turn carries into values and
+    // the 128-bit add of the increment; Pcg64W below trims that glue).
     __device__ __forceinline__ static uint64_t mad64(uint32_t a, uint32_t m, uint64_t c)
     {
         uint64_t d, cy;
@@ -260,6 +277,120 @@ struct Pcg64U {
             }
         }
         return (uint32_t)(m >> 32);
+    }
+};
+#endif // __HIPCC__
+
+// The generator of Pcg64 on FOUR 32-BIT WORDS (w0 the lowest), increment included: the form a loop keeps across its trips when it
+// only steps and reads the output (uct_kernel's one-lane table rollout).  Same ten multiply-adds as Pcg64::mul_add; what differs
+// is the glue around them.  Held as uint64_t halves, the step builds the addend pairs {A0.hi, 0} and {A1.hi, c1} with moves, turns
+// two 64-bit compares into carry values and adds the increment as a 128-bit sum of 64-bit adds (35 vector instructions for
+// next64 in isolation).  On words:
+//   * column 2 starts from A1 >> 32 alone.  Its carry-in c1 = (A1 < B) has weight 2^32 in that column, which is bit 0 of word 3,
+//     and column 2's accumulators are taken modulo 2^64 anyway: r3 = lo(Q) + hi(A2) + c1;
+//   * the increment is added by one 32-bit carry chain (add, two add-with-carry, and w3 = r3 + inc3 + carry);
+//   * the output reads the words: no 64-bit shift or xor is formed.
+// 8 vector instructions fewer per trip of two draws in uct_kernel's LDS-resident form of |A| = 5 (113 -> 105; 101 in a stand-alone
+// copy of the trip; profiles/uct_pcg_words.md).  Checked against Python integers and numpy's PCG64 (tests/test_pcg64_words.py), against
+// unsigned __int128 on the host (tests/test_pcg64_words_host.py) and by the rollouts themselves (tests/test_gpu_uct_pcg_words.py).
+struct Pcg64W {
+    uint32_t w0, w1, w2, w3;   // state
+    uint32_t i0, i1, i2, i3;   // increment (odd: Pcg64::load forces the bit)
+
+    // a * m + c; on the device as Pcg64::mad64 (one v_mad_u64_u32, the multiplier limb an SGPR / literal, the carry-out dead)
+    MP_PCG_FN static uint64_t mad64(uint32_t a, uint32_t m, uint64_t c)
+    {
+#if defined(__HIP_DEVICE_COMPILE__)
+        uint64_t d, cy;
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(cy) : "v"(a), "s"(m), "v"(c));
+        return d;
+#else
+        return (uint64_t)a * m + c;
+#endif
+    }
+    // a + b + carry_in -> sum, *carry_out (0 / 1)
+    MP_PCG_FN static uint32_t addc(uint32_t a, uint32_t b, uint32_t cin, uint32_t *cout)
+    {
+#if defined(MP_PCG_HAS_ADDC)
+        unsigned int co;
+        const uint32_t r = __builtin_addc(a, b, cin, &co);
+        *cout = co;
+        return r;
+#else
+        const uint64_t t = (uint64_t)a + b + cin;
+        *cout = (uint32_t)(t >> 32);
+        return (uint32_t)t;
+#endif
+    }
+    // G: any generator with s_lo, s_hi, inc_lo, inc_hi as uint64_t (Pcg64).  A uint64_t is two 32-bit registers: no instruction.
+    template <typename G>
+    MP_PCG_FN static Pcg64W from(const G &g)
+    {
+        Pcg64W w;
+        w.w0 = (uint32_t)g.s_lo; w.w1 = (uint32_t)(g.s_lo >> 32); w.w2 = (uint32_t)g.s_hi; w.w3 = (uint32_t)(g.s_hi >> 32);
+        w.i0 = (uint32_t)g.inc_lo; w.i1 = (uint32_t)(g.inc_lo >> 32); w.i2 = (uint32_t)g.inc_hi; w.i3 = (uint32_t)(g.inc_hi >> 32);
+        return w;
+    }
+    // the state back into g (its increment is the one this was built from; buffered 32-bit draws are g's own business)
+    template <typename G>
+    MP_PCG_FN void state_to(G &g) const
+    {
+        g.s_lo = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        g.s_hi = (uint64_t)w2 | ((uint64_t)w3 << 32);
+    }
+    // state <- state * 0x2360ED051FC65DA44385DF649FCCF645 + inc (mod 2^128)
+    MP_PCG_FN void advance()
+    {
+        const uint32_t m0 = 0x9FCCF645u, m1 = 0x4385DF64u, m2 = 0x1FC65DA4u, m3 = 0x2360ED05u;
+        const uint64_t A0 = mad64(w0, m0, 0);                        // column 0
+        const uint64_t B = mad64(w0, m1, A0 >> 32);                  // column 1: w0 m1 + carry (no overflow)
+        const uint64_t A1 = mad64(w1, m0, B);                        //           + w1 m0 (65 bits: the carry is c1)
+        const uint32_t c1 = A1 < B ? 1u : 0u;                        // (a compare the compiler sees: the hazard note of Pcg64::mul_add)
+        const uint64_t C = mad64(w0, m2, A1 >> 32);                  // column 2 without c1 (it lands in word 3, below)
+        const uint64_t D = mad64(w1, m1, C);
+        const uint64_t A2 = mad64(w2, m0, D);
+        uint64_t Q = mad64(w0, m3, 0);                               // column 3: the low 32 bits only
+        Q = mad64(w1, m2, Q);
+        Q = mad64(w2, m1, Q);
+        Q = mad64(w3, m0, Q);
+        const uint32_t r1 = (uint32_t)A1, r3 = (uint32_t)Q + (uint32_t)(A2 >> 32) + c1;
+        uint32_t r0 = (uint32_t)A0, r2 = (uint32_t)A2;
+#if defined(__HIP_DEVICE_COMPILE__)
+        // (no instruction: the chain below starts once column 2 is done.  Started when A0 is known, its carries wait in SGPR
+        // pairs across the multiply-adds, and uct_kernel's LDS-resident form of |A| = 5 has none to spare: two spilled SGPRs)
+        asm volatile("" : "+v"(r0), "+v"(r2));
+#endif
+        uint32_t k;
+        w0 = addc(r0, i0, 0u, &k);
+        w1 = addc(r1, i1, k, &k);
+        w2 = addc(r2, i2, k, &k);
+        w3 = r3 + i3 + k;
+    }
+    // v_alignbit_b32: the low word of {hi, lo} >> (s mod 32)
+    MP_PCG_FN static uint32_t alignbit(uint32_t hi, uint32_t lo, uint32_t s)
+    {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_alignbit(hi, lo, s);
+#else
+        return (uint32_t)((((uint64_t)hi << 32) | lo) >> (s & 31u));
+#endif
+    }
+    // XSL-RR of the CURRENT state as two words: rotr64(hi ^ lo, w3 >> 26); a rotation by 32 or more (w3's top bit) swaps the halves
+    MP_PCG_FN void output(uint32_t &lo, uint32_t &hi) const
+    {
+        const uint32_t xl = w0 ^ w2, xh = w1 ^ w3;
+        const uint32_t rot = w3 >> 26;
+        const bool sw = (int32_t)w3 < 0;
+        const uint32_t a = sw ? xh : xl, b = sw ? xl : xh;           // rotating {b, a} by rot & 31
+        lo = alignbit(b, a, rot);
+        hi = alignbit(a, b, rot);
+    }
+    MP_PCG_FN uint64_t next64()
+    {
+        advance();
+        uint32_t lo, hi;
+        output(lo, hi);
+        return ((uint64_t)hi << 32) | lo;
     }
 };
 

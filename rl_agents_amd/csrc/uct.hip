@@ -212,6 +212,15 @@ enum { ENV_TABLE = 0, ENV_CARTPOLE = 2, ENV_TABLE_LDSR = 3, ENV_TABLE_SPILL = 4 
 #ifndef MP_UCT_MIN_WAVES
 #define MP_UCT_MIN_WAVES 1
 #endif
+#ifndef MP_PCG_WORDS
+#define MP_PCG_WORDS 1
+#endif
+// The instantiations of uct_kernel whose one-lane table rollout runs on Pcg64W: every table form (CartPole draws in its own
+// loops, the four-lane form jumps instead of stepping).
+constexpr bool uct_pcg_words_form(int AT, int ENV, bool SP, bool MK, int IL, bool QD)
+{
+    return ENV != ENV_CARTPOLE && !QD;
+}
 // SP: the prior and the rollout distribution are rows of per-state tables (mcts_with_prior.py:47-62).  The env is
 // deterministic, so the state a node is reached in is a function of its action sequence and the prior stored in a
 // child at expansion (mcts.py:237-246) is prior[state of the parent][action]: it is looked up with the state the
@@ -226,7 +235,8 @@ enum { ENV_TABLE = 0, ENV_CARTPOLE = 2, ENV_TABLE_LDSR = 3, ENV_TABLE_SPILL = 4 
 // of the state it is in without another gather; len(children) in the exploration term is the mask's population count.
 // QD (with ENV_TABLE_LDSR; round 5): FOUR LANES PER ROOT, for batches too small to fill the chip (SURVEY 8(d)'s own sizes: 4096
 // roots, one root).  A lone wave per SIMD runs at the latency of its dependency chain, and in a rollout step that chain is
-// numpy's PCG64 (27 of the step's 52 vector instructions) + the model lookup.  With state-independent policies the ACTION
+// numpy's PCG64 (next64 compiles to 35 vector instructions in isolation, a step of the one-lane loop to 56) + the model
+// lookup.  With state-independent policies the ACTION
 // SEQUENCE of a rollout does not depend on the states it visits: the four lanes of a root draw the rollout's H actions four
 // at a time -- lane j holds the generator j + 1 steps ahead and jumps by four per round (state <- A^4 state + inc G_4: one
 // 128-bit multiply, as a single step) -- and the root's first lane (its OWNER: tree phases are its alone) walks the model in
@@ -357,6 +367,13 @@ void uct_kernel(UctArgs p)
     const Rec *__restrict__ rec = p.rec;
     Pcg64 g;
     g.load(p.rng + (long)r * 6);
+    // The one-lane table rollout steps its two generator copies as four 32-bit words each (Pcg64W: 8 vector instructions fewer
+    // per trip of two env steps; profiles/uct_pcg_words.md).  `g` itself, the tie draws of the selection and every other rollout
+    // form keep Pcg64.  -DMP_PCG_WORDS=0 builds the loop on Pcg64 as before, for A/B runs.
+    constexpr bool PCGW = MP_PCG_WORDS != 0 && uct_pcg_words_form(AT, ENV, SP, MK, IL, QD);
+    using RollGen = typename std::conditional<PCGW, Pcg64W, Pcg64>::type;
+    auto roll_gen = [](const Pcg64 &x) { if constexpr (PCGW) return Pcg64W::from(x); else return x; };
+    auto roll_gen_commit = [](Pcg64 &x, const RollGen &y) { if constexpr (PCGW) y.state_to(x); else x = y; };
     uint64_t g4_lo = 0, g4_hi = 0;          // QD: inc * G_4, the additive term of a four-step jump of this root's generator
     if (QD || (CART && p.rep_shift >= 2)) g.inc_g4(g4_lo, g4_hi);
     uint64_t g16_lo = 0, g16_hi = 0;        // CartPole, sixteen replicas: inc * G_16
@@ -1119,7 +1136,7 @@ void uct_kernel(UctArgs p)
             // the step after which the rollout stops at the latest: the horizon, or the environment's step limit (the first step
             // is unconditional, as in the reference's loop: hmax <= depth stops after it)
             const int hmax = p.max_steps > 0 ? min(H, depth + p.max_steps - st) : H;
-            Pcg64 ga = g, gb = g;
+            RollGen ga = roll_gen(g), gb = ga;
             uint64_t u = ga.next64() >> USH; // the 53 random bits of Generator.random() (RAWU: all 64, see thr_arg)
             bool stopped_in_a = true;
             double r_a = 0.0, r_b = 0.0, g_a = 0.0, g_b = 0.0;
@@ -1142,7 +1159,7 @@ void uct_kernel(UctArgs p)
             }
             // one rollout step; returns true when the rollout must stop after it
             auto step = [&](double &r_mine, double &g_mine, const double r_prev, const double g_prev, bool add_prev,
-                            const Pcg64 &gcur, Pcg64 &gspec, uint64_t &unext) -> bool {
+                            const RollGen &gcur, RollGen &gspec, uint64_t &unext) -> bool {
                 // searchsorted(cdf, u, 'right') = #{a : cdf[a] <= u} = #{a : thr[a] <= k}
                 int act = 0;
                 if (SP) {
@@ -1172,8 +1189,9 @@ void uct_kernel(UctArgs p)
                     for (int a = 0; a < A; ++a) act += thr[a] <= u ? 1 : 0;
                 }
                 g_mine = gpow[h];
-                // 32-bit record index (S * |A| < 2^31): one multiply-add instead of a 64-bit address chain
-                const unsigned ridx = (unsigned)(s * A + act);
+                // 32-bit record index (S * |A| < 2^31): one multiply-add instead of a 64-bit address chain; a 24-bit one where the
+                // form bounds S * |A| below 2^24 (the LDS-resident model: three bytes per (s, a) in at most 160 KB)
+                const unsigned ridx = PCGW && LDSR ? __umul24((unsigned)s, (unsigned)A) + (unsigned)act : (unsigned)(s * A + act);
                 bool term_h;
                 if (CART) {
                     gspec = gcur;
@@ -1249,7 +1267,7 @@ void uct_kernel(UctArgs p)
                 u = un;
             }
             if (LDSR) total += stopped_in_a ? g_a * r_a : g_b * r_b;
-            g = stopped_in_a ? ga : gb; // the generator whose draw was consumed last
+            roll_gen_commit(g, stopped_in_a ? ga : gb); // the generator whose draw was consumed last
             st += h - depth; steps_taken += h - depth;
         }
         if constexpr (TREE_PRIO > 0) __builtin_amdgcn_s_setprio(TREE_PRIO);
