@@ -568,6 +568,30 @@ int mp_olop_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int
                         const double *thresholds, const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len,
                         int32_t *plans, int32_t *plan_len, double *root_value, int64_t *env_steps, int32_t *status, int32_t mem);
 
+/* OLOP.plan (tree_search/olop.py:64-193, utils.py:89-203) on a STOCHASTIC finite MDP: a whole dense ([S,A,S]) or sparse
+ * ([S,A,B]) model.  Arguments, host tables, mem flags, validation and outputs are those of mp_olop_plan; what differs is what
+ * the reference does on such an env:
+ *   - run (:64-92) re-seeds its clone per episode, state.seed(np_random.randint(2**30)) (:73): the one draw x of the planner's
+ *     generator makes the clone's Generator(PCG64(SeedSequence(x))), and every model step takes ONE double from THAT generator
+ *     (k = next64 >> 11, successor #{j : thr_j <= k} over the row's thresholds ceil(cdf * 2^53)); reward R[s,a]; done by the
+ *     model's done rule on the source or the next state (mp_model_set_episode_rules).  Exactly `horizon` steps, done or not;
+ *   - the state belongs to the episode, not to the node: OLOPNode.expand (:165-180) lists the actions of the clone's CURRENT
+ *     state (mp_model_set_available's row in column order, else every action), a node's children are fixed at its first
+ *     expansion, and a later episode that reaches the node in another state steps the selected child (:84-88) whether or not
+ *     that state lists its action;
+ *   - OLOPNode.update (:132-142): the reward range is checked after the step was counted, done is sticky PER NODE (set by any
+ *     realisation that reports it), a done node adds 0; compute_reward_ucb (:144-163), backup_to_root (:182-193) and get_plan
+ *     with selection_rule (:126-130) as mp_olop_plan.
+ * The planner's generator sees exactly the draws it sees on a table.  MP_ERR_MODE for a deterministic table (mp_olop_plan plans
+ * on those) and for a joint, batch or row-block model.  mp_olop_tree_export serves the trees afterwards, same layout, creation
+ * order and capacity; `state` holds the root's state at node 0 and -1 elsewhere (a node stands for no single state).
+ * mp_last_kernel_variant records one of mp_olop_stoch_form_names: "olop_stoch_dense\nolop_stoch_sparse" (part of no other list). */
+int mp_olop_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes,
+                            int32_t horizon, double gamma, int32_t bound_type, int32_t continuation, const double *thresholds,
+                            const double *value_upper_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans,
+                            int32_t *plan_len, double *root_value, int64_t *env_steps, int32_t *status, int32_t mem);
+const char *mp_olop_stoch_form_names(void);
+
 /* Test hook: what the DEVICE computes for the three functions behind mu_ucb, the only planner outputs that are held to a
  * tolerance (1e-12) and not to bits.  Host arrays of n elements in and out, one input per lane of 64-lane workgroups (the lanes
  * of a wave run different iteration counts, as the path nodes of an episode do); the kernel calls the very __device__ functions

@@ -1,7 +1,10 @@
 """Open-Loop Optimistic Planning, OLOP / KL-OLOP, on the MI355X planning core (reference
 ``rl_agents/agents/tree_search/olop.py``); the episodes run in ``mp_olop_plan`` (rl_agents_amd/csrc/olop.hip).
 
-Same class names, config keys and results as the reference on deterministic finite-MDP tables.  What the host computes:
+Same class names, config keys and results as the reference on deterministic finite-MDP tables (``OLOPAgent``) and, through
+``mp_olop_plan_stochastic``, on ``stochastic`` [S, A, S] and ``sparse`` [S, A, B] models too (``StochasticOLOPAgent``): the
+clone re-seeded per episode, the state carried by the episode, a node's children fixed at its first expansion.  What the host
+computes:
 the budget split (``allocation``, also used by MCTS), the initial upper bounds by depth (Python ``**``) and the bound's
 threshold per episode (``eval`` of the config string) -- every constant that is not a basic IEEE operation.  The
 device computes the KL bound's Newton iteration with its own ``log``: bounds agree with the reference within 1e-12 and
@@ -18,7 +21,7 @@ logger = logging.getLogger(__name__)
 
 
 class OLOP(AbstractPlanner):
-    """OLOP planner (olop.py:11-100) for one or many roots of one deterministic finite MDP."""
+    """OLOP planner (olop.py:11-100) for one or many roots of one finite MDP."""
 
     def __init__(self, env, config=None):
         self.env = env
@@ -85,11 +88,36 @@ class OLOP(AbstractPlanner):
             out[episode] = float(eval(bound["threshold"], {"np": np}, {"time": time}))
         return out
 
+    # OLOP itself plans on deterministic tables and refuses anything else with the base class's TypeError, as it always has;
+    # StochasticOLOP, below, sets this and plans on every finite MDP
+    accepts_stochastic_models = False
+
+    def model_for(self, state):
+        """A deterministic table goes through the base class, and so does everything else unless the planner
+        ``accepts_stochastic_models``.  Then a ``stochastic`` [S, A, S] or ``sparse`` [S, A, B] model is loaded with the env's
+        availability table, its columns in the env's listing order (the expansion asks the clone which actions it lists,
+        olop.py:169), and with the env's done rule (no step limit: done = terminated)."""
+        mdp = None
+        if self.accepts_stochastic_models and not device_model.is_cartpole(state):
+            mdp = device_model.finite_mdp_of(state)
+        if mdp is None or mdp.mode == "deterministic":
+            return super(OLOP, self).model_for(state)
+        available, order = device_model.availability_of(state, mdp)
+        spec = device_model.spec_from_mdp(mdp, available=available, action_order=order)
+        model = self.models.get(spec)
+        if spec.available is not None and getattr(model, "available", None) is None:
+            model.set_available(spec.available)          # (columns = listing order; as SparseSampling.model_for)
+        model.set_episode_rules(getattr(mdp, "done_rule", "source"), 0)
+        return model
+
     def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
         """``root_steps`` is accepted for the common interface: the step limit ends no OLOP episode (done = terminated)."""
         cfg = self.config
         episodes, horizon = int(cfg["episodes"]), int(cfg["horizon"])        # KeyError without "episodes" (olop.py:95)
         model = self.model_for(state)
+        # a dense / sparse model: the episodes sample it with the clone's generator (mp_olop_plan_stochastic)
+        stochastic = model.mode in (native.MODE_STOCHASTIC, native.MODE_SPARSE)
+        olop_plan = self.models.ctx.olop_plan_stochastic if stochastic else self.models.ctx.olop_plan
         self.about_to_plan()
         n = len(root_states)
         if rng_states is None:
@@ -104,8 +132,8 @@ class OLOP(AbstractPlanner):
             thresholds = np.zeros(0, np.float64)
         # "uniform": a random new child; anything else: action 0 of the environment, in the device's labels
         continuation = -1 if cfg["continuation_type"] == "uniform" else int(self.device_actions([0], model)[0])
-        out = self.models.ctx.olop_plan(model, root_states, episodes, horizon, cfg["gamma"], kl, continuation, thresholds,
-                                        self._value_upper_init, rng_states, max_plan_len=max(horizon, 1))
+        out = olop_plan(model, root_states, episodes, horizon, cfg["gamma"], kl, continuation, thresholds,
+                        self._value_upper_init, rng_states, max_plan_len=max(horizon, 1))
         # the reference's observations and generator draws up to the failing step are taken before it raises: the step
         # count is booked, and the records in `rng_states` are advanced, also on an error
         self.env_steps += int(out["env_steps"].sum())
@@ -117,6 +145,7 @@ class OLOP(AbstractPlanner):
         out["rng_states"] = rng_states
         self.relabel(out, model)
         self.last, self._root, self._last_model, self._last_actions = out, None, model, model.A
+        self._last_stochastic = stochastic
         self.claim_device_tree()
         return out
 
@@ -143,6 +172,10 @@ class OLOP(AbstractPlanner):
         """Observations stepped through (abstract.py:163-167).  On a deterministic model a node stands for one state and
         was stepped into ``count`` times, so the counts come from the exported tree (the last plan, as for OPD)."""
         from collections import defaultdict
+        if self.last is not None and getattr(self, "_last_stochastic", False):
+            raise NotImplementedError("on a stochastic model a node of the OLOP tree is an action sequence reached in many "
+                                      "states and stands for no single one: the states stepped through leave no trace on "
+                                      "the device and get_visits is not available")
         visits = defaultdict(int)
         if self.root is not None:
             for node, _ in self.root.breadth_first_search(self.root):
@@ -182,7 +215,8 @@ def build_olop_tree(arrays, planner=None):
         node.mu_ucb = float(arrays["mu"][i])
         node.cumulative_reward = float(arrays["cum"][i])
         node.done = bool(arrays["done"][i])
-        node.state = int(arrays["state"][i])
+        # (a stochastic model's export holds -1 below the root: such a node stands for no single state)
+        node.state = int(arrays["state"][i]) if arrays["state"][i] >= 0 else None
         if par is not None:
             par.children[node.action] = node
         nodes.append(node)
@@ -190,5 +224,20 @@ def build_olop_tree(arrays, planner=None):
 
 
 class OLOPAgent(AbstractTreeSearchAgent):
-    """Drop-in for ``rl_agents.agents.tree_search.olop.OLOPAgent``."""
+    """Drop-in for ``rl_agents.agents.tree_search.olop.OLOPAgent`` on deterministic finite-MDP tables; any other model is
+    refused with ``TypeError``."""
     PLANNER_TYPE = OLOP
+
+
+class StochasticOLOP(OLOP):
+    """OLOP on every finite MDP: what :class:`OLOP` does on a deterministic table, and on a ``stochastic`` / ``sparse`` model
+    the reference's own behaviour there (``mp_olop_plan_stochastic``): the clone re-seeded per episode, the state carried by
+    the episode, a node's children fixed at its first expansion, ``done`` sticky per node."""
+    accepts_stochastic_models = True
+
+
+class StochasticOLOPAgent(AbstractTreeSearchAgent):
+    """``rl_agents.agents.tree_search.olop.OLOPAgent`` with the reference's reach: the reference's OLOP / KL-OLOP configs
+    (``SailingEnv/agents/kl-olop.json``) run on a ``StochasticMDP`` / ``SparseMDP`` env with only the ``__class__`` line
+    changed.  :class:`OLOPAgent` keeps its name and its refusal of such envs, which earlier code may rely on."""
+    PLANNER_TYPE = StochasticOLOP

@@ -69,6 +69,14 @@ inline FormName slots_form_name(const char *planner, bool keep) // OLOP, BRUE: t
 }
 inline FormName olop_form_name(bool keep) { return slots_form_name("olop", keep); }
 inline FormName brue_form_name(bool keep) { return slots_form_name("brue", keep); }
+// OLOP on a stochastic finite MDP (mp_olop_plan_stochastic, olop.hip): named by the model's rows.  Listed by
+// mp_olop_stoch_form_names -- NOT by all_form_names below, as for Sparse Sampling.
+inline FormName olop_stoch_form_name(bool sparse)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "olop_stoch_%s", sparse ? "sparse" : "dense");
+    return n;
+}
 inline FormName gbopd_form_name(bool use_lds)
 {
     FormName n;

@@ -122,7 +122,10 @@ SIGNATURES = {
     "mp_olop_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp, _vp,
                                _vp, _vp, c_i32]),
     "mp_olop_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "mp_brue_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_olop_plan_stochastic": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp,
+                                          _vp, _vp, _vp, c_i32]),
+    "mp_olop_stoch_form_names": (C.c_char_p, []),
+    "mp_brue_plan":(C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_brue_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_olop_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp,
                                       _vp, _vp, _vp, c_i32]),
@@ -333,6 +336,12 @@ def each_form_info(planner, s_each, n_actions, horizon, n_roots, cus=256):
                                     _ptr(out)))
     return dict(lds_bytes=int(out[0]), lds=bool(out[1]), grid=int(out[2]), launch_lds_bytes=int(out[3]), default_limit=int(out[4]),
                 fit_limit=int(out[5]))
+
+
+def olop_stoch_form_names():
+    """The names an OLOP plan on a dense / sparse model (``olop_plan_stochastic``) records for
+    Context.last_kernel_variant() (mp_olop_stoch_form_names; host only).  They are part of no other list of names."""
+    return load().mp_olop_stoch_form_names().decode().split()
 
 
 def ss_form_names():
@@ -1255,6 +1264,29 @@ class Context(object):
                                       int(continuation), _ptr(thr) if thr.size else None, _ptr(vin), _ptr(rng_state), mpl,
                                       _ptr(out["plans"]), _ptr(out["plan_len"]), _ptr(out["root_value"]), _ptr(out["env_steps"]),
                                       _ptr(out["status"]), MP_MEM_HOST))
+        return out
+
+    def olop_plan_stochastic(self, model, root_state, episodes, horizon, gamma, kl, continuation, thresholds, value_upper_init,
+                             rng_state, max_plan_len=None):
+        """OLOP.plan on a ``stochastic`` / ``sparse`` model for a batch of roots (host arrays): mp_olop_plan_stochastic.
+        Arguments and results as :meth:`olop_plan`; the clone is re-seeded per episode from the planner's draw and every model
+        step samples the model's row with the clone's own generator.  :meth:`olop_tree` serves the trees afterwards."""
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        n = rs.shape[0]
+        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
+                and rng_state.size == n * 6):
+            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
+        mpl = max(int(horizon), 1) if max_plan_len is None else int(max_plan_len)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        vin = np.ascontiguousarray(value_upper_init, dtype=np.float64).reshape(-1)
+        if vin.size != int(horizon) + 1 or (kl and thr.size < int(episodes)):
+            raise ValueError("olop_plan_stochastic: thresholds [episodes] and value_upper_init [horizon + 1] expected")
+        out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32), root_value=np.zeros(n, np.float64),
+                   env_steps=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
+        _check(self._lib.mp_olop_plan_stochastic(self._h, model._h, n, _ptr(rs), int(episodes), int(horizon), float(gamma),
+                                                 1 if kl else 0, int(continuation), _ptr(thr) if thr.size else None, _ptr(vin),
+                                                 _ptr(rng_state), mpl, _ptr(out["plans"]), _ptr(out["plan_len"]),
+                                                 _ptr(out["root_value"]), _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
         return out
 
     def olop_tree(self, root, cap):
