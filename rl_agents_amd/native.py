@@ -244,6 +244,117 @@ def _ptr(a):
     raise TypeError("expected numpy array, torch tensor or None, got {}".format(type(a)))
 
 
+def _ptrs(*arrays):
+    return [_ptr(a) for a in arrays]
+
+
+def _check_rng(rng_state, n, shape="n_roots", or_what=""):
+    """The generator records of a host-array call are a C-contiguous uint64 array of ``n`` records, or ValueError."""
+    if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
+            and rng_state.size == n * 6):
+        raise ValueError("rng_state must be a C-contiguous uint64 array of shape [{}, 6]{}".format(shape, or_what))
+
+
+# The result arrays of every planner family, in the order of the C arguments: (name, dtype, trailing shape, fill), a
+# trailing "L" = the plan length, "A" = the model's actions.  The host result dicts, plan_buffers and the pinned scratch
+# arrays of small plans are all made from it.
+_PLANS, _LEN, _STEPS = ("plans", np.int32, ("L",), -1), ("plan_len", np.int32, (), 0), ("env_steps", np.int64, (), 0)
+_ACTION, _VALUE, _STATUS = ("plans", np.int32, (), -1), ("root_value", np.float64, (), 0), ("status", np.int32, (), 0)
+RESULTS = {
+    "uct": (_PLANS, _LEN, _VALUE, ("root_child_count", np.int64, ("A",), 0), ("root_child_value", np.float64, ("A",), 0), _STEPS),
+    "opd": (_PLANS, _LEN, ("root_lower", np.float64, (), 0), ("root_upper", np.float64, (), 0), _STEPS, _STATUS),
+    "olop": (_PLANS, _LEN, _VALUE, _STEPS, _STATUS),
+    "brue": (_ACTION, _VALUE, _STEPS, _STATUS),
+    "ss": (_ACTION, _VALUE, ("samples", np.int64, (), 0), _STATUS),
+    "saopd": (_PLANS, _LEN, _STEPS, ("updates", np.int64, (), 0), _STATUS),
+    "gbopd": (_PLANS, _LEN, ("value_lower", np.float64, (), 0), ("value_upper", np.float64, (), 0), _STEPS,
+              ("updates", np.int64, (), 0), _STATUS),
+}
+# what a small plan's pinned scratch arrays hold in front of the family's results
+SCRATCH_INPUTS = {"uct": (("root_state", np.int32, ()), ("root_steps", np.int32, ()), ("rng", np.uint64, (6,))),
+                  "opd": (("root_state", np.int32, ()), ("rng", np.uint64, (6,)))}
+
+
+def _results(family, n, **dims):
+    """The host result dict of a plan of ``n`` roots."""
+    out = {}
+    for k, dtype, tail, fill in RESULTS[family]:
+        out[k] = np.zeros((n,) + tuple([dims[d] for d in tail]) if tail else n, dtype)
+        if fill:
+            out[k].fill(fill)
+    return out
+
+
+def _result_spec(family, n, **dims):
+    """``{name: (shape, dtype)}`` of the family's results (PinnedArrays' spec); an array whose dimension is None is left out."""
+    return {k: ((n,) + tuple(dims[d] for d in tail), dtype) for k, dtype, tail, _ in RESULTS[family]
+            if None not in [dims[d] for d in tail]}
+
+
+def _result_ptrs(family, out):
+    """The addresses of the result arrays ``out`` holds, in the order of the C arguments (None: not asked for)."""
+    return [_ptr(out[k]) if k in out else None for k, _, _, _ in RESULTS[family]]
+
+
+def _zeros(cap, fields):
+    """``fields`` (name, dtype, trailing shape) -> ``{name: zeros [cap, ...]}``."""
+    return {k: np.zeros((cap,) + tuple(tail), dtype) for k, dtype, tail in fields}
+
+
+def _export_tree(fn, head, cap, fields):
+    """A tree export ``fn(*head, cap, &n, one pointer per field)`` -> the fields' arrays, cut to the n nodes and copied."""
+    t, n = _zeros(cap, fields), c_i32()
+    _check(fn(*(tuple(head) + (int(cap), C.byref(n)) + tuple(_ptr(v) for v in t.values()))))
+    return {k: v[:n.value].copy() for k, v in t.items()}
+
+
+def _flags(x, *shape):
+    """Flags (terminal, available, listed, ...) -> contiguous uint8 of ``shape`` (none: the shape they have); None stays."""
+    if x is None:
+        return None
+    x = np.asarray(x)
+    return np.ascontiguousarray((x.reshape(shape) if shape else x).astype(np.uint8))
+
+
+def _same_shape(a, b, ndims, message):
+    if a.shape != b.shape or a.ndim not in ndims:
+        raise ValueError(message)
+
+
+def _int_tables(transition, reward, ndims, message):
+    """Deterministic tables as the library reads them: int64 next states and float64 rewards of one shape."""
+    t = np.ascontiguousarray(transition, dtype=np.int64)
+    r = np.ascontiguousarray(reward, dtype=np.float64)
+    _same_shape(t, r, ndims, message)
+    return t, r
+
+
+def _priors(prior_p, rollout_p, n_actions=None):
+    """The per-action prior / rollout probabilities as float64; ``n_actions``: the length both must have."""
+    pp = np.ascontiguousarray(prior_p, dtype=np.float64)
+    rp = np.ascontiguousarray(rollout_p, dtype=np.float64)
+    if n_actions is not None and (pp.shape != (n_actions,) or rp.shape != (n_actions,)):
+        raise ValueError("prior_p / rollout_p must have one entry per action")
+    return pp, rp
+
+
+class _Handle(object):
+    """Owner of a library handle ``_h`` made on the context ``ctx``: ``close`` gives it to the class's ``_free`` symbol, once
+    and only while the context lives; a dying owner closes itself and swallows what that raises."""
+    _free = None
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            getattr(self.ctx._lib, self._free)(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def entropy_words(entropy):
     """numpy's split of entropy integers into little-endian uint32 words (bit_generator.pyx _coerce_to_uint32_array):
     an int or a sequence of ints, each non-negative; 0 -> [0]."""
@@ -555,13 +666,10 @@ class Context(object):
         requested ``outputs`` (``uct_plan(..., out=buffers)`` fills exactly those; outputs not listed are not computed
         into host memory at all).  The caller owns them: a later call with the same buffers overwrites the results."""
         n, mpl = int(n_roots), int(max_plan_len)
-        shapes = dict(root_state=((n,), np.int32), plans=((n, mpl), np.int32), plan_len=((n,), np.int32),
-                      root_value=((n,), np.float64), env_steps=((n,), np.int64), root_lower=((n,), np.float64),
-                      root_upper=((n,), np.float64), status=((n,), np.int32))
-        if n_actions is not None:
-            shapes.update(root_child_count=((n, int(n_actions)), np.int64), root_child_value=((n, int(n_actions)), np.float64))
-        names = ["root_state"] + [k for k in outputs]
-        return PinnedArrays(self, {k: shapes[k] for k in names})
+        shapes = dict(root_state=((n,), np.int32))
+        for family in ("uct", "opd"):
+            shapes.update(_result_spec(family, n, L=mpl, A=None if n_actions is None else int(n_actions)))
+        return PinnedArrays(self, {k: shapes[k] for k in ["root_state"] + list(outputs)})
 
     # Host-array plans of FEW roots (a single agent's act(): one root) are made through pinned scratch arrays the context
     # keeps: the kernel reads and writes them in place (zero-copy) and the call is one launch + one synchronisation instead of
@@ -577,6 +685,23 @@ class Context(object):
                 cache.pop(next(iter(cache))).close()
             buf = cache[key] = PinnedArrays(self, spec)
         return buf
+
+    def _small_plan(self, family, n, mpl, n_actions=None):
+        """The scratch arrays of a small ``family`` plan, looked up by the plan's shape alone -> (arrays, their addresses, the
+        result arrays among them, those arrays' addresses in the order of the C arguments).  (Building the spec and asking numpy
+        for ten ctypes addresses cost a single agent's act() ~10 us of its ~120 -- tools/act_profile.py.)"""
+        small = self.__dict__.setdefault("_small_plans", {})
+        hit = small.get((family, n, mpl, n_actions))
+        if hit is None or hit[0]._ptr is None:          # (evicted from the pinned-array cache: freed)
+            spec = {k: ((n,) + tail, dtype) for k, dtype, tail in SCRATCH_INPUTS[family]}
+            spec.update(_result_spec(family, n, L=mpl, A=n_actions))
+            scratch = self._scratch(family, n, spec)
+            if len(small) >= 8:
+                small.clear()
+            out = {k: scratch[k] for k, _, _, _ in RESULTS[family]}
+            hit = small[(family, n, mpl, n_actions)] = (scratch, {k: v.ctypes.data for k, v in scratch.items()}, out,
+                                                         [v.ctypes.data for v in out.values()])
+        return hit
 
     def device_rng(self, states_or_n):
         """Generator records resident on the device (mp_rng): an int n (uninitialised) or a uint64 [n, 6] array."""
@@ -610,20 +735,10 @@ class Context(object):
                                    rng_state, env_rng_state, max_plan_len, closed_loop=False, plans=None, plan_len=None,
                                    root_value=None, env_steps=None, root_steps=None, policy=None):
         """mp_uct_plan_stochastic / _policy on device tensors; only enqueues."""
-        if policy is not None:
-            _check(self._lib.mp_uct_plan_stochastic_policy(self._h, model._h, policy._h, int(n_roots), _ptr(root_state),
-                                                           _ptr(root_steps), int(episodes), int(horizon), float(gamma),
-                                                           float(temperature), int(bool(closed_loop)), _ptr(rng_state),
-                                                           _ptr(env_rng_state), int(max_plan_len), _ptr(plans), _ptr(plan_len),
-                                                           _ptr(root_value), None, None, _ptr(env_steps), MP_MEM_DEVICE))
-            return
-        pp = np.ascontiguousarray(prior_p, dtype=np.float64)
-        rp = np.ascontiguousarray(rollout_p, dtype=np.float64)
-        _check(self._lib.mp_uct_plan_stochastic(self._h, model._h, int(n_roots), _ptr(root_state), _ptr(root_steps), int(episodes),
-                                                int(horizon), float(gamma), float(temperature), _ptr(pp), _ptr(rp),
-                                                int(bool(closed_loop)), _ptr(rng_state), _ptr(env_rng_state), int(max_plan_len),
-                                                _ptr(plans), _ptr(plan_len), _ptr(root_value), None, None, _ptr(env_steps),
-                                                MP_MEM_DEVICE))
+        pp, rp = (None, None) if policy is not None else _priors(prior_p, rollout_p)
+        self._uct_stoch_call(MP_MEM_DEVICE, model, int(n_roots), _ptr(root_state), _ptr(root_steps), episodes, horizon, gamma,
+                             temperature, _ptr(pp), _ptr(rp), closed_loop, _ptr(rng_state), _ptr(env_rng_state),
+                             int(max_plan_len), _ptrs(plans, plan_len, root_value, None, None, env_steps), policy)
 
     def greedy_actions_device(self, q, state, plans):
         """plans[:, 0] = argmax_a q[state, a] (first maximum), device tensors."""
@@ -654,19 +769,16 @@ class Context(object):
     def load_table(self, transition, reward, terminal=None, done_rule="source", max_steps=0, available=None):
         """Deterministic tables: transition int [S,A] or [M,S,A], reward like it, terminal [S].
         available: bool [S,A], the actions state.get_available_actions() lists per state (None = all)."""
-        t = np.ascontiguousarray(transition, dtype=np.int64)
-        r = np.ascontiguousarray(reward, dtype=np.float64)
-        if t.shape != r.shape or t.ndim not in (2, 3):
-            raise ValueError("transition and reward must both be [S, A] (or [M, S, A])")
+        t, r = _int_tables(transition, reward, (2, 3), "transition and reward must both be [S, A] (or [M, S, A])")
         m = 1 if t.ndim == 2 else t.shape[0]
         s, a = t.shape[-2:]
-        term = None if terminal is None else np.ascontiguousarray(np.asarray(terminal).reshape(s).astype(np.uint8))
+        term = _flags(terminal, s)
         h = _vp()
         _check(self._lib.mp_model_load_table(self._h, m, s, a, _ptr(t), _ptr(r), _ptr(term),
                                              int(done_rule == "next"), int(max_steps or 0), C.byref(h)))
         model = Model(self, h, MODE_DETERMINISTIC, m, s, a, 0)
         if available is not None:
-            av = np.ascontiguousarray(np.asarray(available).reshape(s, a).astype(np.uint8))
+            av = _flags(available, s, a)
             _check(self._lib.mp_model_set_available(h, _ptr(av)))
             model.available = av.astype(bool)
         return model
@@ -676,12 +788,9 @@ class Context(object):
         (states LOCAL to each MDP), reward [N,S,A], terminal [N,S] or None -> one :class:`Model` over the N * S GLOBAL
         states ``b * S + s`` (``model.n_models``, ``model.S_each``); every deterministic-table entry point takes it, the
         planners with ``model_index=`` (one MDP per root) or with global root states."""
-        t = np.ascontiguousarray(transition, dtype=np.int64)
-        r = np.ascontiguousarray(reward, dtype=np.float64)
-        if t.shape != r.shape or t.ndim != 3:
-            raise ValueError("transition and reward must both be [N, S, A]")
+        t, r = _int_tables(transition, reward, (3,), "transition and reward must both be [N, S, A]")
         n, s, a = t.shape
-        term = None if terminal is None else np.ascontiguousarray(np.asarray(terminal).reshape(n, s).astype(np.uint8))
+        term = _flags(terminal, n, s)
         h = _vp()
         _check(self._lib.mp_model_load_table_batch(self._h, n, s, a, _ptr(t), _ptr(r), _ptr(term), int(done_rule == "next"),
                                                    int(max_steps or 0), C.byref(h)))
@@ -708,18 +817,15 @@ class Context(object):
         """A joint environment of M models (agents/robust/robust.py:9-26): transitions int [M,S,A], rewards [M,S,A],
         terminals [M,S] (each model's own flags) or None.  available: bool [M,S,A], what each model's env lists in
         get_available_actions() (the joint env lists the union over its models' states, robust.py:22-25); None = all."""
-        t = np.ascontiguousarray(transitions, dtype=np.int64)
-        r = np.ascontiguousarray(rewards, dtype=np.float64)
-        if t.shape != r.shape or t.ndim != 3:
-            raise ValueError("transitions and rewards must both be [M, S, A]")
+        t, r = _int_tables(transitions, rewards, (3,), "transitions and rewards must both be [M, S, A]")
         m, s, a = t.shape
-        term = None if terminals is None else np.ascontiguousarray(np.asarray(terminals).reshape(m, s).astype(np.uint8))
+        term = _flags(terminals, m, s)
         h = _vp()
         _check(self._lib.mp_model_load_joint(self._h, m, s, a, _ptr(t), _ptr(r), _ptr(term), int(done_rule == "next"),
                                              C.byref(h)))
         model = Model(self, h, MODE_DETERMINISTIC, m, s, a, 0)
         if available is not None:
-            av = np.ascontiguousarray(np.asarray(available).reshape(m, s, a).astype(np.uint8))
+            av = _flags(available, m, s, a)
             _check(self._lib.mp_model_set_available_joint(h, _ptr(av)))
             model.available = av.astype(bool)
         return model
@@ -729,12 +835,9 @@ class Context(object):
         again before every plan hold (agents/robust/robust.py:68-71).  transitions int [N,M,S,A] (next states LOCAL to each
         table), rewards [N,M,S,A], terminals [N,M,S] or None, available bool [N,M,S,A] or None -> a :class:`JointBatchModel`
         (``n_models`` = N sets, ``M``, ``S_each``); :meth:`ropd_plan` takes it with ``model_index=``."""
-        t = np.ascontiguousarray(transitions, dtype=np.int64)
-        r = np.ascontiguousarray(rewards, dtype=np.float64)
-        if t.shape != r.shape or t.ndim != 4:
-            raise ValueError("transitions and rewards must both be [N, M, S, A]")
+        t, r = _int_tables(transitions, rewards, (4,), "transitions and rewards must both be [N, M, S, A]")
         n, m, s, a = t.shape
-        term = None if terminals is None else np.ascontiguousarray(np.asarray(terminals).reshape(n, m, s).astype(np.uint8))
+        term = _flags(terminals, n, m, s)
         h = _vp()
         _check(self._lib.mp_model_load_joint_batch(self._h, n, m, s, a, _ptr(t), _ptr(r), _ptr(term), int(done_rule == "next"),
                                                    C.byref(h)))
@@ -744,29 +847,28 @@ class Context(object):
             model.set_available(available)
         return model
 
+    @staticmethod
+    def _dense_arrays(transition, reward, terminal, square):
+        """What load_dense and load_dense_rows hand the library -> (transition, reward, terminal flags, transition's shape,
+        MP_MEM_*, the arrays to keep alive): torch tensors are borrowed as they are, anything else is copied to float64 /
+        uint8 host arrays (``square``: one terminal flag per column)."""
+        if hasattr(transition, "data_ptr"):
+            return transition, reward, terminal, tuple(transition.shape), MP_MEM_DEVICE, (transition, reward, terminal)
+        t = np.ascontiguousarray(transition, dtype=np.float64)
+        term = _flags(terminal, t.shape[-1]) if square else _flags(terminal)
+        return t, np.ascontiguousarray(reward, dtype=np.float64), term, t.shape, MP_MEM_HOST, None
+
     def load_dense(self, transition, reward, terminal=None):
         """Dense model: transition float [S,A,S] or [M,S,A,S] (numpy -> copied; torch cuda tensor -> borrowed)."""
-        on_device = hasattr(transition, "data_ptr")
-        if on_device:
-            t, r, term = transition, reward, terminal
-            if not (t.is_contiguous() and r.is_contiguous()):
-                raise ValueError("device arrays must be contiguous")
-            shape = tuple(t.shape)
-            keep = (t, r, term)
-        else:
-            t = np.ascontiguousarray(transition, dtype=np.float64)
-            r = np.ascontiguousarray(reward, dtype=np.float64)
-            shape = t.shape
-            s_ = shape[-1]
-            term = None if terminal is None else np.ascontiguousarray(np.asarray(terminal).reshape(s_).astype(np.uint8))
-            keep = None
+        t, r, term, shape, mem, keep = self._dense_arrays(transition, reward, terminal, True)
+        if mem == MP_MEM_DEVICE and not (t.is_contiguous() and r.is_contiguous()):
+            raise ValueError("device arrays must be contiguous")
         if len(shape) not in (3, 4) or shape[-1] != shape[-3]:
             raise ValueError("transition must be [S, A, S] (or [M, S, A, S])")
         m = 1 if len(shape) == 3 else shape[0]
         s, a = shape[-3], shape[-2]
         h = _vp()
-        _check(self._lib.mp_model_load_dense(self._h, m, s, a, _ptr(t), _ptr(r), _ptr(term),
-                                             MP_MEM_DEVICE if on_device else MP_MEM_HOST, C.byref(h)))
+        _check(self._lib.mp_model_load_dense(self._h, m, s, a, _ptr(t), _ptr(r), _ptr(term), mem, C.byref(h)))
         mod = Model(self, h, MODE_STOCHASTIC, m, s, a, 0)
         mod._keep = keep
         return mod
@@ -774,22 +876,11 @@ class Context(object):
     def load_dense_rows(self, transition, reward, terminal=None):
         """Row block of a dense model: transition [S_rows,A,S] or [M,S_rows,A,S] (numpy copied / torch borrowed),
         reward [..,S_rows,A], terminal [S_rows] flags of the owned rows."""
-        on_device = hasattr(transition, "data_ptr")
-        if on_device:
-            t, r, term = transition, reward, terminal
-            shape = tuple(t.shape)
-            keep = (t, r, term)
-        else:
-            t = np.ascontiguousarray(transition, dtype=np.float64)
-            r = np.ascontiguousarray(reward, dtype=np.float64)
-            shape = t.shape
-            term = None if terminal is None else np.ascontiguousarray(np.asarray(terminal).astype(np.uint8))
-            keep = None
+        t, r, term, shape, mem, keep = self._dense_arrays(transition, reward, terminal, False)
         m = 1 if len(shape) == 3 else shape[0]
         rows, a, cols = shape[-3], shape[-2], shape[-1]
         h = _vp()
-        _check(self._lib.mp_model_load_dense_rows(self._h, m, rows, a, cols, _ptr(t), _ptr(r), _ptr(term),
-                                                  MP_MEM_DEVICE if on_device else MP_MEM_HOST, C.byref(h)))
+        _check(self._lib.mp_model_load_dense_rows(self._h, m, rows, a, cols, _ptr(t), _ptr(r), _ptr(term), mem, C.byref(h)))
         mod = Model(self, h, MODE_STOCHASTIC, m, rows, a, 0)
         mod.S_cols = cols
         mod._keep = keep
@@ -810,10 +901,9 @@ class Context(object):
         t = np.ascontiguousarray(transition, dtype=np.float64)
         n = np.ascontiguousarray(next_states, dtype=np.int64)
         r = np.ascontiguousarray(reward, dtype=np.float64)
-        if t.shape != n.shape or t.ndim != 3:
-            raise ValueError("next and transition must both be [S, A, B]")
+        _same_shape(t, n, (3,), "next and transition must both be [S, A, B]")
         s, a, b = t.shape
-        term = None if terminal is None else np.ascontiguousarray(np.asarray(terminal).reshape(s).astype(np.uint8))
+        term = _flags(terminal, s)
         h = _vp()
         _check(self._lib.mp_model_load_sparse(self._h, s, a, b, _ptr(t), _ptr(n), _ptr(r), _ptr(term), C.byref(h)))
         return Model(self, h, MODE_SPARSE, 1, s, a, b)
@@ -882,8 +972,7 @@ class Context(object):
         if pr.shape != (rows, model.A) or ro.shape != (rows, model.A):
             raise ValueError("prior / rollout must be [S, A] = [{}, {}]".format(model.S, model.A))
         h = _vp()
-        li = None if listed is None else np.ascontiguousarray(np.asarray(listed).reshape(rows, model.A).astype(np.uint8))
-        sl = None if rollout_slots is None else np.ascontiguousarray(np.asarray(rollout_slots).reshape(rows, model.A).astype(np.uint8))
+        li, sl = _flags(listed, rows, model.A), _flags(rollout_slots, rows, model.A)
         _check(self._lib.mp_policy_load_rows(self._h, model._h, _ptr(pr), _ptr(ro), _ptr(li), _ptr(sl), int(rows), C.byref(h)))
         return Policy(self, h, model)
 
@@ -914,66 +1003,39 @@ class Context(object):
         elif (n <= self.SMALL_PLAN_ROOTS and mem == MP_MEM_HOST and mi is None and model.mode != MODE_CARTPOLE
               and not os.environ.get("MP_NO_PINNED_SCRATCH")):
             mpl = int(horizon if max_plan_len is None else max_plan_len)
-            a_ = int(model.A)
-            # (the arrays and their addresses are looked up by the plan's shape alone: building the spec and asking numpy for ten
-            # ctypes addresses cost a single agent's act() ~10 us of its ~120 -- tools/act_profile.py)
-            small = self.__dict__.setdefault("_small_plans", {})
-            hit = small.get((n, mpl, a_))
-            if hit is None or hit[0]._ptr is None:       # (evicted from the pinned-array cache: freed)
-                scratch = self._scratch("uct", n, dict(
-                    root_state=((n,), np.int32), root_steps=((n,), np.int32), rng=((n, 6), np.uint64), plans=((n, mpl), np.int32),
-                    plan_len=((n,), np.int32), root_value=((n,), np.float64), root_child_count=((n, a_), np.int64),
-                    root_child_value=((n, a_), np.float64), env_steps=((n,), np.int64)))
-                if len(small) >= 8:
-                    small.clear()
-                hit = small[(n, mpl, a_)] = (scratch, {k: scratch[k].ctypes.data for k in (
-                    "root_state", "root_steps", "rng", "plans", "plan_len", "root_value", "root_child_count", "root_child_value",
-                    "env_steps")})
-            scratch, sp = hit
+            scratch, sp, out, o = self._small_plan("uct", n, mpl, int(model.A))
             scratch["root_state"][:] = rs
             scratch["rng"][:] = rng_state.reshape(n, 6)
             scratch["plans"][:] = -1
             if st is not None:
                 scratch["root_steps"][:] = st
-            out = {k: scratch[k] for k in ("plans", "plan_len", "root_value", "root_child_count", "root_child_value", "env_steps")}
-            if policy is None and mi is None:
-                pp = np.ascontiguousarray(prior_p, dtype=np.float64)
-                rp = np.ascontiguousarray(rollout_p, dtype=np.float64)
-                if pp.shape != (model.A,) or rp.shape != (model.A,):
-                    raise ValueError("prior_p / rollout_p must have one entry per action")
-                _check(self._lib.mp_uct_plan(self._h, model._h, n, sp["root_state"], None if st is None else sp["root_steps"],
-                                             int(episodes), int(horizon), float(gamma), float(temperature), pp.ctypes.data,
-                                             rp.ctypes.data, sp["rng"], mpl, sp["plans"], sp["plan_len"], sp["root_value"],
-                                             sp["root_child_count"], sp["root_child_value"], sp["env_steps"], mem))
+            if policy is None:                  # (a single agent's act(): the scratch arrays' addresses are the cached ones)
+                pp, rp = _priors(prior_p, rollout_p, model.A)
+                self._uct_call(mem, model, n, sp["root_state"], None if st is None else sp["root_steps"], episodes, horizon, gamma,
+                               temperature, pp.ctypes.data, rp.ctypes.data, sp["rng"], mpl, o)
                 return self._from_scratch(scratch, out, rng_state)
             rs, rng_ptr = scratch["root_state"], sp["rng"]
             if st is not None:
                 st = scratch["root_steps"]
         else:
             mpl = int(horizon if max_plan_len is None else max_plan_len)
-            out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32),
-                       root_value=np.zeros(n, np.float64), root_child_count=np.zeros((n, model.A), np.int64),
-                       root_child_value=np.zeros((n, model.A), np.float64), env_steps=np.zeros(n, np.int64))
-        o = [_ptr(out[k]) if k in out else None for k in ("plans", "plan_len", "root_value", "root_child_count",
-                                                           "root_child_value", "env_steps")]
-        if policy is not None:
-            _check(self._lib.mp_uct_plan_policy(self._h, model._h, policy._h, n, _ptr(rs), _ptr(st), int(episodes),
-                                                int(horizon), float(gamma), float(temperature), rng_ptr, mpl,
-                                                o[0], o[1], o[2], o[3], o[4], o[5], mem))
-            return self._from_scratch(scratch, out, rng_state)
-        pp = np.ascontiguousarray(prior_p, dtype=np.float64)
-        rp = np.ascontiguousarray(rollout_p, dtype=np.float64)
-        if pp.shape != (model.A,) or rp.shape != (model.A,):
-            raise ValueError("prior_p / rollout_p must have one entry per action")
-        if mi is not None:
-            _check(self._lib.mp_uct_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), _ptr(st), int(episodes), int(horizon),
-                                                float(gamma), float(temperature), _ptr(pp), _ptr(rp), rng_ptr, mpl,
-                                                o[0], o[1], o[2], o[3], o[4], o[5], mem))
-            return out
-        _check(self._lib.mp_uct_plan(self._h, model._h, n, _ptr(rs), _ptr(st), int(episodes), int(horizon),
-                                     float(gamma), float(temperature), _ptr(pp), _ptr(rp), rng_ptr, mpl,
-                                     o[0], o[1], o[2], o[3], o[4], o[5], mem))
+            out = _results("uct", n, L=mpl, A=model.A)
+        o = _result_ptrs("uct", out)
+        pp, rp = (None, None) if policy is not None else _priors(prior_p, rollout_p, model.A)
+        self._uct_call(mem, model, n, _ptr(rs), _ptr(st), episodes, horizon, gamma, temperature, _ptr(pp), _ptr(rp), rng_ptr, mpl,
+                       o, policy, _ptr(mi))
         return self._from_scratch(scratch, out, rng_state)
+
+    def _uct_call(self, mem, model, n, rs, st, episodes, horizon, gamma, temperature, pp, rp, rng, mpl, o, policy=None, mi=None):
+        """The one call of mp_uct_plan and of its _policy / _models entry points: every array is an address (``o``: those of
+        the six results), ``mem`` says where they live."""
+        run = (int(episodes), int(horizon), float(gamma), float(temperature))
+        if policy is not None:
+            _check(self._lib.mp_uct_plan_policy(self._h, model._h, policy._h, n, rs, st, *run, rng, mpl, *o, mem))
+        elif mi is not None:
+            _check(self._lib.mp_uct_plan_models(self._h, model._h, n, mi, rs, st, *run, pp, rp, rng, mpl, *o, mem))
+        else:
+            _check(self._lib.mp_uct_plan(self._h, model._h, n, rs, st, *run, pp, rp, rng, mpl, *o, mem))
 
     @staticmethod
     def _from_scratch(scratch, out, rng_state):
@@ -992,9 +1054,7 @@ class Context(object):
             if rng_state.n < n:
                 raise ValueError("the device generator holds {} records, the batch has {} roots".format(rng_state.n, n))
             return MP_MEM_HOST | MP_MEM_RNG_DEVICE, rng_state.ptr(0)
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6] or a DeviceRng")
+        _check_rng(rng_state, n, or_what=" or a DeviceRng")
         return MP_MEM_HOST, rng_state.ctypes.data
 
     def uct_plan_device(self, model, n_roots, root_state, episodes, horizon, gamma, temperature, prior_p, rollout_p,
@@ -1002,31 +1062,12 @@ class Context(object):
                         root_child_value=None, env_steps=None, root_steps=None, policy=None, model_index=None):
         """Same, on device tensors (torch); only enqueues on the ctx stream.  model_index (int32 device tensor): batch
         model, one MDP per root, root_state LOCAL."""
-        if model_index is not None and policy is None:
-            pp = np.ascontiguousarray(prior_p, dtype=np.float64)
-            rp = np.ascontiguousarray(rollout_p, dtype=np.float64)
-            _check(self._lib.mp_uct_plan_models(self._h, model._h, int(n_roots), _ptr(model_index), _ptr(root_state),
-                                                _ptr(root_steps), int(episodes), int(horizon), float(gamma), float(temperature),
-                                                _ptr(pp), _ptr(rp), _ptr(rng_state), int(max_plan_len), _ptr(plans),
-                                                _ptr(plan_len), _ptr(root_value), _ptr(root_child_count),
-                                                _ptr(root_child_value), _ptr(env_steps), MP_MEM_DEVICE))
-            return
-        if model_index is not None:
+        if model_index is not None and policy is not None:
             raise ValueError("per-state policies on a batch model are indexed by global state: pass global root states")
-        if policy is not None:
-            _check(self._lib.mp_uct_plan_policy(self._h, model._h, policy._h, int(n_roots), _ptr(root_state),
-                                                _ptr(root_steps), int(episodes), int(horizon), float(gamma),
-                                                float(temperature), _ptr(rng_state), int(max_plan_len), _ptr(plans),
-                                                _ptr(plan_len), _ptr(root_value), _ptr(root_child_count),
-                                                _ptr(root_child_value), _ptr(env_steps), MP_MEM_DEVICE))
-            return
-        pp = np.ascontiguousarray(prior_p, dtype=np.float64)
-        rp = np.ascontiguousarray(rollout_p, dtype=np.float64)
-        _check(self._lib.mp_uct_plan(self._h, model._h, int(n_roots), _ptr(root_state), _ptr(root_steps),
-                                     int(episodes), int(horizon), float(gamma), float(temperature), _ptr(pp),
-                                     _ptr(rp), _ptr(rng_state), int(max_plan_len), _ptr(plans), _ptr(plan_len),
-                                     _ptr(root_value), _ptr(root_child_count), _ptr(root_child_value),
-                                     _ptr(env_steps), MP_MEM_DEVICE))
+        pp, rp = (None, None) if policy is not None else _priors(prior_p, rollout_p)
+        self._uct_call(MP_MEM_DEVICE, model, int(n_roots), _ptr(root_state), _ptr(root_steps), episodes, horizon, gamma,
+                       temperature, _ptr(pp), _ptr(rp), _ptr(rng_state), int(max_plan_len),
+                       _ptrs(plans, plan_len, root_value, root_child_count, root_child_value, env_steps), policy, _ptr(model_index))
 
     def uct_plan_stochastic(self, model, root_state, episodes, horizon, gamma, temperature, prior_p, rollout_p, rng_state,
                             env_rng_state=None, closed_loop=False, root_steps=None, max_plan_len=None, policy=None, visits=None):
@@ -1039,45 +1080,40 @@ class Context(object):
         mem, rng_ptr = self._rng_arg(rng_state, n)
         erng = None if env_rng_state is None else np.ascontiguousarray(env_rng_state, dtype=np.uint64).reshape(n, 6)
         mpl = int((2 if closed_loop else 1) * horizon if max_plan_len is None else max_plan_len)
-        out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32),
-                   root_value=np.zeros(n, np.float64), root_child_count=np.zeros((n, model.A), np.int64),
-                   root_child_value=np.zeros((n, model.A), np.float64), env_steps=np.zeros(n, np.int64))
+        out = _results("uct", n, L=mpl, A=model.A)
         if visits is not None:          # int32 [n, S]: how often the plan's env steps land in each state (mp_uct_record_visits)
             if visits.dtype != np.int32 or visits.shape != (n, model.S) or not visits.flags.c_contiguous:
                 raise ValueError("visits must be a C-contiguous int32 [n_roots, S] array")
             _check(self._lib.mp_uct_record_visits(self._h, _ptr(visits)))
-        if policy is not None:          # per-state policies (load_policy on this stochastic model)
-            _check(self._lib.mp_uct_plan_stochastic_policy(self._h, model._h, policy._h, n, _ptr(rs), _ptr(st), int(episodes),
-                                                           int(horizon), float(gamma), float(temperature), int(bool(closed_loop)),
-                                                           rng_ptr, _ptr(erng), mpl, _ptr(out["plans"]), _ptr(out["plan_len"]),
-                                                           _ptr(out["root_value"]), _ptr(out["root_child_count"]),
-                                                           _ptr(out["root_child_value"]), _ptr(out["env_steps"]), mem))
-            return out
-        pp = np.ascontiguousarray(prior_p, dtype=np.float64)
-        rp = np.ascontiguousarray(rollout_p, dtype=np.float64)
-        if pp.shape != (model.A,) or rp.shape != (model.A,):
-            raise ValueError("prior_p / rollout_p must have one entry per action")
-        _check(self._lib.mp_uct_plan_stochastic(self._h, model._h, n, _ptr(rs), _ptr(st), int(episodes), int(horizon),
-                                                float(gamma), float(temperature), _ptr(pp), _ptr(rp), int(bool(closed_loop)),
-                                                rng_ptr, _ptr(erng), mpl, _ptr(out["plans"]), _ptr(out["plan_len"]),
-                                                _ptr(out["root_value"]), _ptr(out["root_child_count"]),
-                                                _ptr(out["root_child_value"]), _ptr(out["env_steps"]), mem))
+        # (policy: per-state policies, load_policy on this stochastic model)
+        pp, rp = (None, None) if policy is not None else _priors(prior_p, rollout_p, model.A)
+        self._uct_stoch_call(mem, model, n, _ptr(rs), _ptr(st), episodes, horizon, gamma, temperature, _ptr(pp), _ptr(rp),
+                             closed_loop, rng_ptr, _ptr(erng), mpl, _result_ptrs("uct", out), policy)
         return out
+
+    def _uct_stoch_call(self, mem, model, n, rs, st, episodes, horizon, gamma, temperature, pp, rp, closed_loop, rng, erng, mpl, o,
+                        policy=None):
+        """The one call of mp_uct_plan_stochastic and of its _policy entry point, on addresses as in :meth:`_uct_call`."""
+        run = (int(episodes), int(horizon), float(gamma), float(temperature))
+        tail = (int(bool(closed_loop)), rng, erng, mpl) + tuple(o) + (mem,)
+        if policy is not None:
+            _check(self._lib.mp_uct_plan_stochastic_policy(self._h, model._h, policy._h, n, rs, st, *(run + tail)))
+        else:
+            _check(self._lib.mp_uct_plan_stochastic(self._h, model._h, n, rs, st, *(run + (pp, rp) + tail)))
+
+    UCT_STOCH_TREE = (("parent", np.int32, ()), ("action", np.int32, ()), ("is_obs", np.uint8, ()), ("count", np.int64, ()),
+                      ("value", np.float64, ()))
 
     def uct_stoch_tree(self, root):
         """Tree of `root` after the last uct_plan_stochastic, creation order: parent, action (= key: action id or observed
         state), is_obs, count, value."""
         c = c_i32()
         _check(self._lib.mp_uct_stoch_tree_capacity(self._h, C.byref(c)))
-        cap = c.value
-        t = dict(parent=np.zeros(cap, np.int32), action=np.zeros(cap, np.int32), is_obs=np.zeros(cap, np.uint8),
-                 count=np.zeros(cap, np.int64), value=np.zeros(cap, np.float64))
-        n = c_i32()
-        _check(self._lib.mp_uct_stoch_tree_export(self._h, int(root), cap, C.byref(n), _ptr(t["parent"]), _ptr(t["action"]),
-                                                  _ptr(t["is_obs"]), _ptr(t["count"]), _ptr(t["value"])))
-        t["prior"] = np.zeros(cap, np.float64)      # stored child priors (per-state policies; zeros otherwise)
-        _check(self._lib.mp_uct_stoch_tree_priors(self._h, cap, _ptr(t["prior"])))
-        return {k: v[:n.value].copy() for k, v in t.items()}
+        t = _export_tree(self._lib.mp_uct_stoch_tree_export, (self._h, int(root)), c.value, self.UCT_STOCH_TREE)
+        prior = np.zeros(c.value, np.float64)       # stored child priors (per-state policies; zeros otherwise)
+        _check(self._lib.mp_uct_stoch_tree_priors(self._h, c.value, _ptr(prior)))
+        t["prior"] = prior[:len(t["parent"])].copy()
+        return t
 
     def uct_step_tree(self, actions):
         """step_strategy 'subtree': keep, for the next uct_plan, the subtree under each root's child actions[i] (a host
@@ -1109,18 +1145,15 @@ class Context(object):
     def uct_reset_tree(self):
         _check(self._lib.mp_uct_reset_tree(self._h))
 
+    UCT_TREE = (("parent", np.int32, ()), ("action", np.int32, ()), ("count", np.int64, ()), ("value", np.float64, ()),
+                ("first_child", np.int32, ()), ("n_children", np.int32, ()))
+
     def uct_tree(self, root, cap=None):
         if cap is None:
             c = c_i32()
             _check(self._lib.mp_uct_tree_capacity(self._h, C.byref(c)))
             cap = c.value
-        t = dict(parent=np.zeros(cap, np.int32), action=np.zeros(cap, np.int32), count=np.zeros(cap, np.int64),
-                 value=np.zeros(cap, np.float64), first_child=np.zeros(cap, np.int32), n_children=np.zeros(cap, np.int32))
-        n = c_i32()
-        _check(self._lib.mp_uct_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]),
-                                            _ptr(t["action"]), _ptr(t["count"]), _ptr(t["value"]),
-                                            _ptr(t["first_child"]), _ptr(t["n_children"])))
-        return {k: v[:n.value].copy() for k, v in t.items()}
+        return _export_tree(self._lib.mp_uct_tree_export, (self._h, int(root)), cap, self.UCT_TREE)
 
     def uct_path_count(self, root, actions):
         """Visit count of the node the action sequence reaches in the last plan's tree of `root` (-1: it leaves the tree)."""
@@ -1133,52 +1166,42 @@ class Context(object):
         """OptimisticDeterministicPlanner.plan for a batch of roots (host arrays).  model_index: batch model, root i plans
         on MDP model_index[i] from its LOCAL state."""
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        return self._opd_plan(False, model, rs, budget, gamma, terminal_reward, rng_state, max_plan_len, model_index)
+
+    def _opd_plan(self, robust, model, rs, budget, gamma, terminal_reward, rng_state, max_plan_len, model_index):
+        """opd_plan and ropd_plan behind their root states ``rs`` ([n] / [n, M]); the few roots of a single-model OPD plan go
+        through the context's pinned scratch arrays."""
         n = rs.shape[0]
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
+        _check_rng(rng_state, n)
         mpl = int(max_plan_len)
-        if n <= self.SMALL_PLAN_ROOTS and model_index is None and not os.environ.get("MP_NO_PINNED_SCRATCH"):
-            scratch = self._scratch("opd", n, dict(
-                root_state=((n,), np.int32), rng=((n, 6), np.uint64), plans=((n, mpl), np.int32), plan_len=((n,), np.int32),
-                root_lower=((n,), np.float64), root_upper=((n,), np.float64), env_steps=((n,), np.int64), status=((n,), np.int32)))
+        mi = None if model_index is None else np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
+        scratch, rng = None, rng_state
+        if not robust and n <= self.SMALL_PLAN_ROOTS and mi is None and not os.environ.get("MP_NO_PINNED_SCRATCH"):
+            scratch, sp, out, o = self._small_plan("opd", n, mpl)
             scratch["root_state"][:] = rs
             scratch["rng"][:] = rng_state.reshape(n, 6)
             scratch["plans"][:] = -1
-            out = {k: scratch[k] for k in ("plans", "plan_len", "root_lower", "root_upper", "env_steps", "status")}
-            _check(self._lib.mp_opd_plan(self._h, model._h, n, _ptr(scratch["root_state"]), int(budget), float(gamma),
-                                         float(terminal_reward), _ptr(scratch["rng"]), mpl, _ptr(out["plans"]),
-                                         _ptr(out["plan_len"]), _ptr(out["root_lower"]), _ptr(out["root_upper"]),
-                                         _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
-            return self._from_scratch(scratch, out, rng_state)
-        out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32),
-                   root_lower=np.zeros(n, np.float64), root_upper=np.zeros(n, np.float64),
-                   env_steps=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
-        if model_index is not None:
-            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
-            _check(self._lib.mp_opd_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(budget), float(gamma),
-                                                float(terminal_reward), _ptr(rng_state), mpl, _ptr(out["plans"]),
-                                                _ptr(out["plan_len"]), _ptr(out["root_lower"]), _ptr(out["root_upper"]),
-                                                _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
-            return out
-        _check(self._lib.mp_opd_plan(self._h, model._h, n, _ptr(rs), int(budget), float(gamma),
-                                     float(terminal_reward), _ptr(rng_state), mpl, _ptr(out["plans"]),
-                                     _ptr(out["plan_len"]), _ptr(out["root_lower"]), _ptr(out["root_upper"]),
-                                     _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
-        return out
+            rs, rng = scratch["root_state"], scratch["rng"]
+        else:
+            out = _results("opd", n, L=mpl)
+            o = _result_ptrs("opd", out)
+        self._opd_call(robust, MP_MEM_HOST, model, n, _ptr(mi), _ptr(rs), budget, gamma, terminal_reward, _ptr(rng), mpl, o)
+        return self._from_scratch(scratch, out, rng_state)
+
+    def _opd_call(self, robust, mem, model, n, mi, rs, budget, gamma, terminal_reward, rng, mpl, o):
+        """The one call of mp_opd_plan / mp_ropd_plan and of their _models entry points (``mi``: one model (set) per root),
+        on addresses."""
+        if mi is None:
+            fn, roots = self._lib.mp_ropd_plan if robust else self._lib.mp_opd_plan, (n, rs)
+        else:
+            fn, roots = self._lib.mp_ropd_plan_models if robust else self._lib.mp_opd_plan_models, (n, mi, rs)
+        _check(fn(self._h, model._h, *roots, int(budget), float(gamma), float(terminal_reward), rng, mpl, *o, mem))
 
     def opd_plan_device(self, model, n_roots, root_state, budget, gamma, terminal_reward, rng_state, max_plan_len,
                         plans=None, plan_len=None, root_lower=None, root_upper=None, env_steps=None, status=None, model_index=None):
-        if model_index is not None:
-            _check(self._lib.mp_opd_plan_models(self._h, model._h, int(n_roots), _ptr(model_index), _ptr(root_state), int(budget),
-                                                float(gamma), float(terminal_reward), _ptr(rng_state), int(max_plan_len), _ptr(plans),
-                                                _ptr(plan_len), _ptr(root_lower), _ptr(root_upper), _ptr(env_steps),
-                                                _ptr(status), MP_MEM_DEVICE))
-            return
-        _check(self._lib.mp_opd_plan(self._h, model._h, int(n_roots), _ptr(root_state), int(budget), float(gamma),
-                                     float(terminal_reward), _ptr(rng_state), int(max_plan_len), _ptr(plans),
-                                     _ptr(plan_len), _ptr(root_lower), _ptr(root_upper), _ptr(env_steps),
-                                     _ptr(status), MP_MEM_DEVICE))
+        self._opd_call(False, MP_MEM_DEVICE, model, int(n_roots), _ptr(model_index), _ptr(root_state), budget, gamma,
+                       terminal_reward, _ptr(rng_state), int(max_plan_len),
+                       _ptrs(plans, plan_len, root_lower, root_upper, env_steps, status))
 
     def ropd_plan(self, model, root_state, budget, gamma, terminal_reward, rng_state, max_plan_len=64, model_index=None):
         """DiscreteRobustPlanner.plan for a batch of roots of a joint model; root_state int [n] (every model starts in
@@ -1188,52 +1211,38 @@ class Context(object):
         if rs.ndim == 1:
             rs = np.repeat(rs[:, None], model.M, axis=1)
         rs = np.ascontiguousarray(rs.reshape(-1, model.M))
-        n = rs.shape[0]
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
-        mpl = int(max_plan_len)
-        out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32),
-                   root_lower=np.zeros(n, np.float64), root_upper=np.zeros(n, np.float64),
-                   env_steps=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
-        if model_index is not None:
-            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
-            _check(self._lib.mp_ropd_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(budget), float(gamma),
-                                                 float(terminal_reward), _ptr(rng_state), mpl, _ptr(out["plans"]),
-                                                 _ptr(out["plan_len"]), _ptr(out["root_lower"]), _ptr(out["root_upper"]),
-                                                 _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
-            return out
-        _check(self._lib.mp_ropd_plan(self._h, model._h, n, _ptr(rs), int(budget), float(gamma), float(terminal_reward),
-                                      _ptr(rng_state), mpl, _ptr(out["plans"]), _ptr(out["plan_len"]),
-                                      _ptr(out["root_lower"]), _ptr(out["root_upper"]), _ptr(out["env_steps"]),
-                                      _ptr(out["status"]), MP_MEM_HOST))
-        return out
+        return self._opd_plan(True, model, rs, budget, gamma, terminal_reward, rng_state, max_plan_len, model_index)
 
     def ropd_plan_device(self, model, n_roots, root_state, budget, gamma, terminal_reward, rng_state, max_plan_len,
                          plans=None, plan_len=None, root_lower=None, root_upper=None, env_steps=None, status=None, model_index=None):
-        if model_index is not None:
-            _check(self._lib.mp_ropd_plan_models(self._h, model._h, int(n_roots), _ptr(model_index), _ptr(root_state), int(budget),
-                                                 float(gamma), float(terminal_reward), _ptr(rng_state), int(max_plan_len), _ptr(plans),
-                                                 _ptr(plan_len), _ptr(root_lower), _ptr(root_upper), _ptr(env_steps),
-                                                 _ptr(status), MP_MEM_DEVICE))
-            return
-        _check(self._lib.mp_ropd_plan(self._h, model._h, int(n_roots), _ptr(root_state), int(budget), float(gamma),
-                                      float(terminal_reward), _ptr(rng_state), int(max_plan_len), _ptr(plans),
-                                      _ptr(plan_len), _ptr(root_lower), _ptr(root_upper), _ptr(env_steps),
-                                      _ptr(status), MP_MEM_DEVICE))
+        self._opd_call(True, MP_MEM_DEVICE, model, int(n_roots), _ptr(model_index), _ptr(root_state), budget, gamma,
+                       terminal_reward, _ptr(rng_state), int(max_plan_len),
+                       _ptrs(plans, plan_len, root_lower, root_upper, env_steps, status))
+
+    @staticmethod
+    def _opd_tree_fields(*per_model):
+        """The node arrays of an OPD tree; robust OPD holds state, reward, bounds and done flag once per model."""
+        return (("parent", np.int32, ()), ("action", np.int32, ()), ("state", np.int32, per_model), ("depth", np.int32, ()),
+                ("reward", np.float64, per_model), ("lower", np.float64, per_model), ("upper", np.float64, per_model),
+                ("done", np.uint8, per_model), ("count", np.int64, ()), ("first_child", np.int32, ()), ("n_children", np.int32, ()))
+
+    def opd_tree(self, root, cap):
+        return _export_tree(self._lib.mp_opd_tree_export, (self._h, int(root)), cap, self._opd_tree_fields())
 
     def ropd_tree(self, root, cap, n_models):
-        m = int(n_models)
-        t = dict(parent=np.zeros(cap, np.int32), action=np.zeros(cap, np.int32), state=np.zeros((cap, m), np.int32),
-                 depth=np.zeros(cap, np.int32), reward=np.zeros((cap, m), np.float64), lower=np.zeros((cap, m), np.float64),
-                 upper=np.zeros((cap, m), np.float64), done=np.zeros((cap, m), np.uint8), count=np.zeros(cap, np.int64),
-                 first_child=np.zeros(cap, np.int32), n_children=np.zeros(cap, np.int32))
-        n = c_i32()
-        _check(self._lib.mp_ropd_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]),
-                                             _ptr(t["action"]), _ptr(t["state"]), _ptr(t["depth"]), _ptr(t["reward"]),
-                                             _ptr(t["lower"]), _ptr(t["upper"]), _ptr(t["done"]), _ptr(t["count"]),
-                                             _ptr(t["first_child"]), _ptr(t["n_children"])))
-        return {k: v[:n.value].copy() for k, v in t.items()}
+        return _export_tree(self._lib.mp_ropd_tree_export, (self._h, int(root)), cap, self._opd_tree_fields(int(n_models)))
+
+    def _each_plan(self, fn, fn_models, family, model, rs, model_index, run, rng_state, mpl=None):
+        """The host call OLOP, BRUE and Sparse Sampling plans share: ``fn(ctx, model, n, roots, *run, rng, [mpl], results,
+        MP_MEM_HOST)``, or ``fn_models`` with ``model_index`` (one MDP per root) in front of the roots -> the result dict."""
+        n = rs.shape[0]
+        out = _results(family, n, **({} if mpl is None else {"L": mpl}))
+        roots = (n, _ptr(rs))
+        if model_index is not None:
+            fn, roots = fn_models, (n, _ptr(np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)), _ptr(rs))
+        _check(fn(self._h, model._h, *roots, *run, _ptr(rng_state), *(() if mpl is None else (mpl,)), *_result_ptrs(family, out),
+                  MP_MEM_HOST))
+        return out
 
     def olop_plan(self, model, root_state, episodes, horizon, gamma, kl, continuation, thresholds, value_upper_init, rng_state,
                   max_plan_len=None, model_index=None):
@@ -1241,147 +1250,79 @@ class Context(object):
         inf); ``continuation``: < 0 = uniform, else the action label taken after an expansion; ``thresholds`` float64
         [episodes], ``value_upper_init`` float64 [horizon + 1] from the host.  ``model_index`` int [n]: a batch model with one
         MDP per root, ``root_state`` local (mp_olop_plan_models)."""
-        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
-        n = rs.shape[0]
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
-        mpl = max(int(horizon), 1) if max_plan_len is None else int(max_plan_len)
-        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
-        vin = np.ascontiguousarray(value_upper_init, dtype=np.float64).reshape(-1)
-        if vin.size != int(horizon) + 1 or (kl and thr.size < int(episodes)):
-            raise ValueError("olop_plan: thresholds [episodes] and value_upper_init [horizon + 1] expected")
-        out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32), root_value=np.zeros(n, np.float64),
-                   env_steps=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
-        if model_index is not None:
-            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
-            _check(self._lib.mp_olop_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(episodes), int(horizon), float(gamma),
-                                                 1 if kl else 0, int(continuation), _ptr(thr) if thr.size else None, _ptr(vin),
-                                                 _ptr(rng_state), mpl, _ptr(out["plans"]), _ptr(out["plan_len"]),
-                                                 _ptr(out["root_value"]), _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
-            return out
-        _check(self._lib.mp_olop_plan(self._h, model._h, n, _ptr(rs), int(episodes), int(horizon), float(gamma), 1 if kl else 0,
-                                      int(continuation), _ptr(thr) if thr.size else None, _ptr(vin), _ptr(rng_state), mpl,
-                                      _ptr(out["plans"]), _ptr(out["plan_len"]), _ptr(out["root_value"]), _ptr(out["env_steps"]),
-                                      _ptr(out["status"]), MP_MEM_HOST))
-        return out
+        return self._olop_plan(self._lib.mp_olop_plan, self._lib.mp_olop_plan_models, "olop_plan", model, root_state, episodes,
+                               horizon, gamma, kl, continuation, thresholds, value_upper_init, rng_state, max_plan_len, model_index)
 
     def olop_plan_stochastic(self, model, root_state, episodes, horizon, gamma, kl, continuation, thresholds, value_upper_init,
                              rng_state, max_plan_len=None):
         """OLOP.plan on a ``stochastic`` / ``sparse`` model for a batch of roots (host arrays): mp_olop_plan_stochastic.
         Arguments and results as :meth:`olop_plan`; the clone is re-seeded per episode from the planner's draw and every model
         step samples the model's row with the clone's own generator.  :meth:`olop_tree` serves the trees afterwards."""
+        return self._olop_plan(self._lib.mp_olop_plan_stochastic, None, "olop_plan_stochastic", model, root_state, episodes,
+                               horizon, gamma, kl, continuation, thresholds, value_upper_init, rng_state, max_plan_len, None)
+
+    def _olop_plan(self, fn, fn_models, name, model, root_state, episodes, horizon, gamma, kl, continuation, thresholds,
+                   value_upper_init, rng_state, max_plan_len, model_index):
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
-        n = rs.shape[0]
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
+        _check_rng(rng_state, rs.shape[0])
         mpl = max(int(horizon), 1) if max_plan_len is None else int(max_plan_len)
         thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
         vin = np.ascontiguousarray(value_upper_init, dtype=np.float64).reshape(-1)
         if vin.size != int(horizon) + 1 or (kl and thr.size < int(episodes)):
-            raise ValueError("olop_plan_stochastic: thresholds [episodes] and value_upper_init [horizon + 1] expected")
-        out = dict(plans=np.full((n, mpl), -1, np.int32), plan_len=np.zeros(n, np.int32), root_value=np.zeros(n, np.float64),
-                   env_steps=np.zeros(n, np.int64), status=np.zeros(n, np.int32))
-        _check(self._lib.mp_olop_plan_stochastic(self._h, model._h, n, _ptr(rs), int(episodes), int(horizon), float(gamma),
-                                                 1 if kl else 0, int(continuation), _ptr(thr) if thr.size else None, _ptr(vin),
-                                                 _ptr(rng_state), mpl, _ptr(out["plans"]), _ptr(out["plan_len"]),
-                                                 _ptr(out["root_value"]), _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
-        return out
+            raise ValueError("{}: thresholds [episodes] and value_upper_init [horizon + 1] expected".format(name))
+        run = (int(episodes), int(horizon), float(gamma), 1 if kl else 0, int(continuation), _ptr(thr) if thr.size else None,
+               _ptr(vin))
+        return self._each_plan(fn, fn_models, "olop", model, rs, model_index, run, rng_state, mpl)
+
+    OLOP_TREE = (("parent", np.int32, ()), ("action", np.int32, ()), ("depth", np.int32, ()), ("count", np.int64, ()),
+                 ("cum", np.float64, ()), ("mu", np.float64, ()), ("vu", np.float64, ()), ("done", np.uint8, ()),
+                 ("state", np.int32, ()))
 
     def olop_tree(self, root, cap):
         """Creation-order arrays of root ``root``'s tree after the last olop_plan (mp_olop_tree_export)."""
-        t = dict(parent=np.zeros(cap, np.int32), action=np.zeros(cap, np.int32), depth=np.zeros(cap, np.int32),
-                 count=np.zeros(cap, np.int64), cum=np.zeros(cap, np.float64), mu=np.zeros(cap, np.float64),
-                 vu=np.zeros(cap, np.float64), done=np.zeros(cap, np.uint8), state=np.zeros(cap, np.int32))
-        n = c_i32()
-        _check(self._lib.mp_olop_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]), _ptr(t["action"]),
-                                             _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["cum"]), _ptr(t["mu"]), _ptr(t["vu"]),
-                                             _ptr(t["done"]), _ptr(t["state"])))
-        return {k: v[:n.value].copy() for k, v in t.items()}
+        return _export_tree(self._lib.mp_olop_tree_export, (self._h, int(root)), cap, self.OLOP_TREE)
 
     def brue_plan(self, model, root_state, budget, horizon, gamma, gpow, rng_state, model_index=None):
         """BRUE.plan for a batch of roots (host arrays): mp_brue_plan.  ``gpow`` float64 [horizon + 1]: gamma ** d from the
         host.  ``plans`` [n]: the one planned action per root (-1 where no rollout was made).  ``model_index`` int [n]: a batch
         model with one MDP per root, ``root_state`` local (mp_brue_plan_models)."""
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
-        n = rs.shape[0]
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
+        _check_rng(rng_state, rs.shape[0])
         gp = np.ascontiguousarray(gpow, dtype=np.float64).reshape(-1)
         if gp.size != int(horizon) + 1:
             raise ValueError("brue_plan: gpow [horizon + 1] expected")
-        out = dict(plans=np.full(n, -1, np.int32), root_value=np.zeros(n, np.float64), env_steps=np.zeros(n, np.int64),
-                   status=np.zeros(n, np.int32))
-        if model_index is not None:
-            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
-            _check(self._lib.mp_brue_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(budget), int(horizon), float(gamma),
-                                                 _ptr(gp), _ptr(rng_state), _ptr(out["plans"]), _ptr(out["root_value"]),
-                                                 _ptr(out["env_steps"]), _ptr(out["status"]), MP_MEM_HOST))
-            return out
-        _check(self._lib.mp_brue_plan(self._h, model._h, n, _ptr(rs), int(budget), int(horizon), float(gamma), _ptr(gp),
-                                      _ptr(rng_state), _ptr(out["plans"]), _ptr(out["root_value"]), _ptr(out["env_steps"]),
-                                      _ptr(out["status"]), MP_MEM_HOST))
-        return out
+        return self._each_plan(self._lib.mp_brue_plan, self._lib.mp_brue_plan_models, "brue", model, rs, model_index,
+                               (int(budget), int(horizon), float(gamma), _ptr(gp)), rng_state)
+
+    BRUE_TREE = (("parent", np.int32, ()), ("key", np.int32, ()), ("is_chance", np.uint8, ()), ("depth", np.int32, ()),
+                 ("count", np.int64, ()), ("stat", np.float64, ()))
 
     def brue_tree(self, root, cap):
         """Creation-order arrays of root ``root``'s tree after the last brue_plan (mp_brue_tree_export)."""
-        t = dict(parent=np.zeros(cap, np.int32), key=np.zeros(cap, np.int32), is_chance=np.zeros(cap, np.uint8),
-                 depth=np.zeros(cap, np.int32), count=np.zeros(cap, np.int64), stat=np.zeros(cap, np.float64))
-        n = c_i32()
-        _check(self._lib.mp_brue_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]), _ptr(t["key"]),
-                                             _ptr(t["is_chance"]), _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["stat"])))
-        return {k: v[:n.value].copy() for k, v in t.items()}
+        return _export_tree(self._lib.mp_brue_tree_export, (self._h, int(root)), cap, self.BRUE_TREE)
 
     def ss_plan(self, model, root_state, horizon, C, gamma, rng_state, model_index=None):
         """SparseSampling.plan for a batch of roots (host arrays): mp_ss_plan.  ``plans`` [n]: the one planned action per
         root (a column of the model); ``samples`` [n]: model steps taken.  ``model_index`` int [n]: a batch model with one
         MDP per root, ``root_state`` local (mp_ss_plan_models)."""
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
-        n = rs.shape[0]
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_roots, 6]")
-        out = dict(plans=np.full(n, -1, np.int32), root_value=np.zeros(n, np.float64), samples=np.zeros(n, np.int64),
-                   status=np.zeros(n, np.int32))
-        if model_index is not None:
-            mi = np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)
-            _check(self._lib.mp_ss_plan_models(self._h, model._h, n, _ptr(mi), _ptr(rs), int(horizon), int(C), float(gamma),
-                                               _ptr(rng_state), _ptr(out["plans"]), _ptr(out["root_value"]), _ptr(out["samples"]),
-                                               _ptr(out["status"]), MP_MEM_HOST))
-            return out
-        _check(self._lib.mp_ss_plan(self._h, model._h, n, _ptr(rs), int(horizon), int(C), float(gamma), _ptr(rng_state),
-                                    _ptr(out["plans"]), _ptr(out["root_value"]), _ptr(out["samples"]), _ptr(out["status"]),
-                                    MP_MEM_HOST))
-        return out
+        _check_rng(rng_state, rs.shape[0])
+        return self._each_plan(self._lib.mp_ss_plan, self._lib.mp_ss_plan_models, "ss", model, rs, model_index,
+                               (int(horizon), int(C), float(gamma)), rng_state)
+
+    SS_TREE = (("parent", np.int32, ()), ("key", np.int32, ()), ("is_chance", np.uint8, ()), ("depth", np.int32, ()),
+               ("count", np.int64, ()), ("value", np.float64, ()))
 
     def ss_tree(self, root, cap=None):
         """Creation-order arrays of root ``root``'s tree after the last ss_plan (mp_ss_tree_export).  ``cap`` None: the
         tree's own node count is asked first."""
-        n = c_i32()
         if cap is None:
+            n = c_i32()
             rc = self._lib.mp_ss_tree_export(self._h, int(root), 0, C.byref(n), None, None, None, None, None, None)
             if n.value < 1:                                     # (no tree to size: the refusal itself)
                 _check(rc)
             cap = n.value
-        t = dict(parent=np.zeros(cap, np.int32), key=np.zeros(cap, np.int32), is_chance=np.zeros(cap, np.uint8),
-                 depth=np.zeros(cap, np.int32), count=np.zeros(cap, np.int64), value=np.zeros(cap, np.float64))
-        _check(self._lib.mp_ss_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]), _ptr(t["key"]),
-                                           _ptr(t["is_chance"]), _ptr(t["depth"]), _ptr(t["count"]), _ptr(t["value"])))
-        return {k: v[:n.value].copy() for k, v in t.items()}
-
-    def opd_tree(self, root, cap):
-        t = dict(parent=np.zeros(cap, np.int32), action=np.zeros(cap, np.int32), state=np.zeros(cap, np.int32),
-                 depth=np.zeros(cap, np.int32), reward=np.zeros(cap, np.float64), lower=np.zeros(cap, np.float64),
-                 upper=np.zeros(cap, np.float64), done=np.zeros(cap, np.uint8), count=np.zeros(cap, np.int64),
-                 first_child=np.zeros(cap, np.int32), n_children=np.zeros(cap, np.int32))
-        n = c_i32()
-        _check(self._lib.mp_opd_tree_export(self._h, int(root), int(cap), C.byref(n), _ptr(t["parent"]),
-                                            _ptr(t["action"]), _ptr(t["state"]), _ptr(t["depth"]), _ptr(t["reward"]),
-                                            _ptr(t["lower"]), _ptr(t["upper"]), _ptr(t["done"]), _ptr(t["count"]),
-                                            _ptr(t["first_child"]), _ptr(t["n_children"])))
-        return {k: v[:n.value].copy() for k, v in t.items()}
+        return _export_tree(self._lib.mp_ss_tree_export, (self._h, int(root)), cap, self.SS_TREE)
 
 
 class PinnedArrays(dict):
@@ -1415,9 +1356,10 @@ class PinnedArrays(dict):
             pass
 
 
-class DeviceRng(object):
+class DeviceRng(_Handle):
     """numpy-PCG64 generator records of a batch of roots, resident on the device (mp_rng): the planners advance them in
     place and nothing crosses PCIe until ``get`` is asked for."""
+    _free = "mp_rng_free"
 
     def __init__(self, ctx, n):
         self.ctx, self.n = ctx, int(n)
@@ -1447,20 +1389,11 @@ class DeviceRng(object):
             raise NativeError(MP_ERR_ARG, load().mp_last_error().decode("utf-8", "replace"))
         return p
 
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx._lib.mp_rng_free(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class Model(object):
+class Model(_Handle):
     """Device-resident transition model (mp_model)."""
+    _free = "mp_model_free"
 
     def __init__(self, ctx, handle, mode, m, s, a, b):
         self.ctx, self._h, self.mode, self.M, self.S, self.A, self.B = ctx, handle, mode, m, s, a, b
@@ -1469,7 +1402,7 @@ class Model(object):
 
     def set_available(self, available):
         """Restrict the action sets (mp_model_set_available): bool [S, A] over this model's (global) states."""
-        av = np.ascontiguousarray(np.asarray(available).reshape(self.S, self.A).astype(np.uint8))
+        av = _flags(available, self.S, self.A)
         _check(self.ctx._lib.mp_model_set_available(self._h, _ptr(av)))
         self.available = av.astype(bool)
 
@@ -1480,7 +1413,7 @@ class Model(object):
         become invalid."""
         t = np.ascontiguousarray(transition, dtype=np.int64).reshape(-1, self.S_each, self.A)
         r = np.ascontiguousarray(reward, dtype=np.float64).reshape(t.shape)
-        term = None if terminal is None else np.ascontiguousarray(np.asarray(terminal).reshape(t.shape[0], self.S_each).astype(np.uint8))
+        term = _flags(terminal, t.shape[0], self.S_each)
         _check(self.ctx._lib.mp_model_update_tables(self._h, int(first), int(t.shape[0]), _ptr(t), _ptr(r), _ptr(term)))
 
     def update_rows(self, rows, transition, reward, terminal=None):
@@ -1489,7 +1422,7 @@ class Model(object):
         rw = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
         t = np.ascontiguousarray(transition, dtype=np.int64).reshape(rw.shape[0], self.A)
         r = np.ascontiguousarray(reward, dtype=np.float64).reshape(t.shape)
-        term = None if terminal is None else np.ascontiguousarray(np.asarray(terminal).reshape(rw.shape[0]).astype(np.uint8))
+        term = _flags(terminal, rw.shape[0])
         if len(np.unique(rw)) != len(rw):
             raise ValueError("update_rows: row ids must be distinct")
         _check(self.ctx._lib.mp_model_update_rows(self._h, int(rw.shape[0]), _ptr(rw), _ptr(t), _ptr(r), _ptr(term)))
@@ -1499,16 +1432,6 @@ class Model(object):
         at load time)."""
         _check(self.ctx._lib.mp_model_set_episode_rules(self._h, int(done_rule == "next"), int(max_steps or 0)))
 
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx._lib.mp_model_free(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class JointBatchModel(Model):
@@ -1518,7 +1441,7 @@ class JointBatchModel(Model):
     def set_available(self, available):
         """What each model's env lists in get_available_actions(): bool [N, M, S, A] (mp_model_set_available_joint_batch).
         The flags survive :meth:`update_tables`."""
-        av = np.ascontiguousarray(np.asarray(available).reshape(self.n_models, self.M, self.S_each, self.A).astype(np.uint8))
+        av = _flags(available, self.n_models, self.M, self.S_each, self.A)
         _check(self.ctx._lib.mp_model_set_available_joint_batch(self._h, _ptr(av)))
         self.available = av.astype(bool)
 
@@ -1527,14 +1450,14 @@ class JointBatchModel(Model):
         states, reward [count,M,S,A], terminal [count,M,S] iff the model has terminal flags.  Stream-ordered."""
         t = np.ascontiguousarray(transition, dtype=np.int64).reshape(-1, self.M, self.S_each, self.A)
         r = np.ascontiguousarray(reward, dtype=np.float64).reshape(t.shape)
-        term = None if terminal is None else np.ascontiguousarray(
-            np.asarray(terminal).reshape(t.shape[0], self.M, self.S_each).astype(np.uint8))
+        term = _flags(terminal, t.shape[0], self.M, self.S_each)
         _check(self.ctx._lib.mp_model_update_joint_tables(self._h, int(first), int(t.shape[0]), _ptr(t), _ptr(r), _ptr(term)))
 
 
-class StateAwarePlanners(object):
+class StateAwarePlanners(_Handle):
     """A batch of device-resident StateAwarePlanner objects (mp_saopd): state values, state-node lists and the node
     arena persist across plan() calls, as in the reference (tree_search/state_aware.py:76-83)."""
+    _free = "mp_saopd_free"
 
     def __init__(self, ctx, model, n_planners):
         self.ctx, self.model, self.n = ctx, model, int(n_planners)
@@ -1546,19 +1469,19 @@ class StateAwarePlanners(object):
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
         if rs.shape[0] != self.n:
             raise ValueError("one root state per planner ({}), got {}".format(self.n, rs.shape[0]))
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == self.n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_planners, 6]")
+        _check_rng(rng_state, self.n, "n_planners")
         mpl = int(budget + 1 if max_plan_len is None else max_plan_len)
-        out = dict(plans=np.full((self.n, mpl), -1, np.int32), plan_len=np.zeros(self.n, np.int32),
-                   env_steps=np.zeros(self.n, np.int64), updates=np.zeros(self.n, np.int64),
-                   status=np.zeros(self.n, np.int32))
-        _check(self.ctx._lib.mp_saopd_plan(self.ctx._h, self._h, _ptr(rs), int(budget), float(gamma),
-                                           float(terminal_reward), float(accuracy), int(bool(backup_aggregated_nodes)),
-                                           int(bool(prune_suboptimal_leaves)), _ptr(rng_state), mpl, _ptr(out["plans"]),
-                                           _ptr(out["plan_len"]), _ptr(out["env_steps"]), _ptr(out["updates"]),
-                                           _ptr(out["status"]), MP_MEM_HOST))
+        out = _results("saopd", self.n, L=mpl)
+        self._call(MP_MEM_HOST, _ptr(rs), budget, gamma, terminal_reward, accuracy, backup_aggregated_nodes,
+                   prune_suboptimal_leaves, _ptr(rng_state), mpl, _result_ptrs("saopd", out))
         return out
+
+    def _call(self, mem, rs, budget, gamma, terminal_reward, accuracy, backup_aggregated_nodes, prune_suboptimal_leaves, rng, mpl,
+              o):
+        """The one call of mp_saopd_plan, on addresses (``o``: those of the five results)."""
+        _check(self.ctx._lib.mp_saopd_plan(self.ctx._h, self._h, rs, int(budget), float(gamma), float(terminal_reward),
+                                           float(accuracy), int(bool(backup_aggregated_nodes)),
+                                           int(bool(prune_suboptimal_leaves)), rng, int(mpl), *o, mem))
 
     def plan_device(self, root_state, budget, gamma, terminal_reward, rng_state, max_plan_len, accuracy=0.0,
                     backup_aggregated_nodes=True, prune_suboptimal_leaves=True, plans=None, plan_len=None, env_steps=None,
@@ -1567,29 +1490,25 @@ class StateAwarePlanners(object):
         [n], rng_state uint64-as-int64 [n, 6], plans int32 [n, max_plan_len], plan_len / status int32 [n], env_steps /
         updates int64 [n]); one launch on the context's stream, nothing read back.  A planner whose backup queue fills up
         reports MP_ERR_ALLOC in ``status`` and stays failed for every later call (mi355plan.h)."""
-        _check(self.ctx._lib.mp_saopd_plan(self.ctx._h, self._h, _ptr(root_state), int(budget), float(gamma),
-                                           float(terminal_reward), float(accuracy), int(bool(backup_aggregated_nodes)),
-                                           int(bool(prune_suboptimal_leaves)), _ptr(rng_state), int(max_plan_len), _ptr(plans),
-                                           _ptr(plan_len), _ptr(env_steps), _ptr(updates), _ptr(status), MP_MEM_DEVICE))
+        self._call(MP_MEM_DEVICE, _ptr(root_state), budget, gamma, terminal_reward, accuracy, backup_aggregated_nodes,
+                   prune_suboptimal_leaves, _ptr(rng_state), max_plan_len, _ptrs(plans, plan_len, env_steps, updates, status))
 
     def info(self):
         n, nn, root, s = c_i32(), c_i32(), c_i32(), c_i32()
         _check(self.ctx._lib.mp_saopd_info(self._h, C.byref(n), C.byref(nn), C.byref(root), C.byref(s)))
         return dict(n_planners=n.value, n_nodes=nn.value, root=root.value, n_states=s.value)
 
+    ARENA = (("parent", np.int32, ()), ("action", np.int32, ()), ("state", np.int32, ()), ("depth", np.int32, ()),
+             ("reward", np.float64, ()), ("lower", np.float64, ()), ("done", np.uint8, ()), ("count", np.int64, ()),
+             ("first_child", np.int32, ()), ("alive", np.uint8, ()))
+
     def export(self, planner=0, current_tree_only=True):
         """Arena of one planner; current_tree_only: the nodes of the last plan's tree, ids re-based at its root."""
         inf = self.info()
         cap = inf["n_nodes"]
-        t = dict(parent=np.zeros(cap, np.int32), action=np.zeros(cap, np.int32), state=np.zeros(cap, np.int32),
-                 depth=np.zeros(cap, np.int32), reward=np.zeros(cap, np.float64), lower=np.zeros(cap, np.float64),
-                 done=np.zeros(cap, np.uint8), count=np.zeros(cap, np.int64), first_child=np.zeros(cap, np.int32),
-                 alive=np.zeros(cap, np.uint8))
+        t = _zeros(cap, self.ARENA)
         sv = np.zeros(inf["n_states"], np.float64)
-        _check(self.ctx._lib.mp_saopd_export(self._h, int(planner), cap, _ptr(t["parent"]), _ptr(t["action"]),
-                                             _ptr(t["state"]), _ptr(t["depth"]), _ptr(t["reward"]), _ptr(t["lower"]),
-                                             _ptr(t["done"]), _ptr(t["count"]), _ptr(t["first_child"]), _ptr(t["alive"]),
-                                             _ptr(sv)))
+        _check(self.ctx._lib.mp_saopd_export(self._h, int(planner), cap, *(_ptrs(*t.values()) + [_ptr(sv)])))
         # Rows of actions the environment does not list (restricted action sets, deterministic.py:32-35) are PHANTOMS in
         # the arena -- lower = -inf, never alive -- that only keep the ids of an expansion's |A| slots contiguous: they
         # are not nodes of the tree.  Drop them and renumber; a node's children are then contiguous from first_child,
@@ -1617,22 +1536,13 @@ class StateAwarePlanners(object):
             out[k] = np.where(out[k] >= lo, new_id[np.maximum(out[k], 0)] - base, -1).astype(np.int32)
         return out, sv
 
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx._lib.mp_saopd_free(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class GraphBasedPlanners(object):
+class GraphBasedPlanners(_Handle):
     """A batch of device-resident GraphBasedPlanner objects (mp_gbopd): the graph of observed states with both bounds, the
     parents in insertion order and the lifetime visit / update counters persist across plan() calls, as in the reference
     (tree_search/graph_based.py:87-94).  ``queue_cap``: entries of a planner's backup queue (None: the library's default)."""
+    _free = "mp_gbopd_free"
 
     def __init__(self, ctx, model, n_planners, queue_cap=None):
         self.ctx, self.model, self.n = ctx, model, int(n_planners)
@@ -1644,29 +1554,24 @@ class GraphBasedPlanners(object):
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
         if rs.shape[0] != self.n:
             raise ValueError("one root state per planner ({}), got {}".format(self.n, rs.shape[0]))
-        if not (isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.flags.c_contiguous
-                and rng_state.size == self.n * 6):
-            raise ValueError("rng_state must be a C-contiguous uint64 array of shape [n_planners, 6]")
+        _check_rng(rng_state, self.n, "n_planners")
         t = int(sampling_timeout)
-        out = dict(plans=np.full((self.n, t), -1, np.int32), plan_len=np.zeros(self.n, np.int32),
-                   value_lower=np.zeros(self.n, np.float64), value_upper=np.zeros(self.n, np.float64),
-                   env_steps=np.zeros(self.n, np.int64), updates=np.zeros(self.n, np.int64),
-                   status=np.zeros(self.n, np.int32))
-        _check(self.ctx._lib.mp_gbopd_plan(self.ctx._h, self._h, _ptr(rs), int(budget), float(gamma), float(value_max),
-                                           float(accuracy), t, _ptr(rng_state), _ptr(out["plans"]), _ptr(out["plan_len"]),
-                                           _ptr(out["value_lower"]), _ptr(out["value_upper"]), _ptr(out["env_steps"]),
-                                           _ptr(out["updates"]), _ptr(out["status"]), MP_MEM_HOST))
+        out = _results("gbopd", self.n, L=t)
+        self._call(MP_MEM_HOST, _ptr(rs), budget, gamma, value_max, accuracy, t, _ptr(rng_state), _result_ptrs("gbopd", out))
         return out
+
+    def _call(self, mem, rs, budget, gamma, value_max, accuracy, sampling_timeout, rng, o):
+        """The one call of mp_gbopd_plan, on addresses (``o``: those of the seven results)."""
+        _check(self.ctx._lib.mp_gbopd_plan(self.ctx._h, self._h, rs, int(budget), float(gamma), float(value_max),
+                                           float(accuracy), int(sampling_timeout), rng, *o, mem))
 
     def plan_device(self, root_state, budget, gamma, value_max, accuracy, sampling_timeout, rng_state, plans=None,
                     plan_len=None, value_lower=None, value_upper=None, env_steps=None, updates=None, status=None):
         """Asynchronous form: every array is a device buffer (torch tensors on the context's device: root_state int32 [n],
         rng_state uint64-as-int64 [n, 6], plans int32 [n, sampling_timeout], plan_len / status int32 [n], value_lower /
         value_upper float64 [n], env_steps / updates int64 [n]); one launch on the context's stream, nothing read back."""
-        _check(self.ctx._lib.mp_gbopd_plan(self.ctx._h, self._h, _ptr(root_state), int(budget), float(gamma), float(value_max),
-                                           float(accuracy), int(sampling_timeout), _ptr(rng_state), _ptr(plans), _ptr(plan_len),
-                                           _ptr(value_lower), _ptr(value_upper), _ptr(env_steps), _ptr(updates), _ptr(status),
-                                           MP_MEM_DEVICE))
+        self._call(MP_MEM_DEVICE, _ptr(root_state), budget, gamma, value_max, accuracy, sampling_timeout, _ptr(rng_state),
+                   _ptrs(plans, plan_len, value_lower, value_upper, env_steps, updates, status))
 
     def info(self):
         n, s, a, q, e = c_i32(), c_i32(), c_i32(), c_i32(), c_i64()
@@ -1701,34 +1606,15 @@ class GraphBasedPlanners(object):
                     parent_ptr=pptr[:n + 1].copy(), parent_idx=pidx[:pptr[n]].copy(), visits=visits, updates=updates,
                     n_observations=np.asarray(nobs.value), root=np.asarray(root.value))
 
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx._lib.mp_gbopd_free(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class Policy(object):
+class Policy(_Handle):
     """Device-resident per-state prior / rollout policy tables (mp_policy)."""
+    _free = "mp_policy_free"
 
     def __init__(self, ctx, handle, model=None):
         self.ctx, self._h, self.model = ctx, handle, model      # keeps the model it is tied to alive
 
-    def close(self):
-        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
-            self.ctx._lib.mp_policy_free(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def check_device_sweeps(sweeps_out):
