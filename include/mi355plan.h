@@ -967,6 +967,20 @@ int mp_olop_allocation(int32_t budget, double gamma, int32_t *episodes, int32_t 
  *   *name:    the form, as mp_last_kernel_variant names it.
  * A call the plan refuses for its shape gets the plan's MP_ERR_ARG. */
 int mp_uct_choose_form(const int64_t *call, int64_t *out, const char **name);
+/* The same for a call of mp_saopd_plan (host only); the MP_SAOPD_* knobs are read as the plan reads them, the planners' mapping is
+ * the one mp_saopd_create would give them now (|A| and MP_SAOPD_MODEL).
+ *   call[10]:  n_planners, the model's S and |A|, budget, what the planners hold per planner: node rows in use (mp_saopd_info; 0:
+ *              fresh), rows and queue entries allocated (0: none yet, or not known: the form depends on neither unless
+ *              MP_SAOPD_QUEUE is smaller than the queue they have), costs to sort by (0 / 1: an earlier plan of these planners, or
+ *              of another batch on the model), device arrays (0 / 1), compute units.
+ *   out[20]:   wave mapping (0 / 1), K, node rows after the plan, rows and queue entries allocated for it, chunk-pool ints, the
+ *              kernel arguments tab_plain, tab_lds, lds_rows, lds_qcap, scap (first launch / global-memory queue), par_backup,
+ *              csr_old, prune_rows, sticky, whether the dispatch order is sorted, the dynamic LDS bytes of the first launch and of
+ *              the fallback, the byte limit of a growing queue.
+ *   *name:     the first launch, as mp_last_kernel_variant names it, "_ordered" included, never "_retry".
+ *   *fallback: the form a call whose backup queue fills up runs again on (recorded with "_retry").
+ * A call the plan refuses for its sizes gets the plan's MP_ERR_ARG. */
+int mp_saopd_choose_form(const int64_t *call, int64_t *out, const char **name, const char **fallback);
 /* Timing of the last kernel batch enqueued by a plan / solve call, from HIP events recorded on
  * the ctx stream around the kernel launches only (no copies).  Synchronises the stream. */
 int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);

@@ -252,6 +252,15 @@ inline FormName saopd_form_name(const SaopdForm &f)
              f.retry ? "_retry" : "");
     return n;
 }
+// (the same name in static storage: mp_saopd_choose_form hands out pointers)
+inline const char *saopd_form_name_static(const SaopdForm &f)
+{
+    static const struct Names {
+        FormName n[16];
+        Names() { for (int i = 0; i < 16; ++i) n[i] = saopd_form_name({(i & 12) != 0, (i & 12) == 8, (i & 12) == 12, (i & 2) != 0, (i & 1) != 0}); }
+    } names;
+    return names.n[(!f.wave ? 0 : f.lds ? 12 : f.dict ? 8 : 4) | (f.ordered ? 2 : 0) | (f.retry ? 1 : 0)].s;
+}
 
 // ---- UCT on stochastic models (uct_stoch.hip).  wbk: the form the step records really have (0 rows + thresholds, 2 / 4 fused
 // records of that many successors, 1 the compact 16-byte records); p16: 16-bit path entries; at: the unrolled |A| in 2..8 or

@@ -40,6 +40,7 @@
 //           neighbour's parent, 64 / |A| neighbours of several pending descriptors per pass; applied in queue and list
 //           order with register patching / re-evaluation when a state value moves (first plan of fresh planners)
 //   meta    bits 24..29 = the action that led to the node (its sibling group = the children of its parent)
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -51,6 +52,7 @@
 #include "common.hpp"
 #include "pcg64.hpp"
 #include "wave.hpp"
+#include "wave_host.hpp"
 
 namespace mp {
 
@@ -1592,7 +1594,6 @@ __global__ __launch_bounds__(256) void saopd_learn_kernel(int n, int S, const in
     if ((unsigned)rs < (unsigned)S) model_cost[rs] = cost[r]; // (never a store beyond the [S] table, whatever the status says)
 }
 
-// grow a node array from old_cap to new_cap rows per planner, keeping the used_rows rows in use
 // undo the list appends of a rolled-back plan: after the tails are restored, every tail is the end of its list again
 // host mode, no room left to grow the queue: the planners that still report MP_ERR_ALLOC stay failed
 __global__ __launch_bounds__(64) void saopd_mark_failed_kernel(int n, const int32_t *status, int32_t *overflow)
@@ -1636,18 +1637,18 @@ static void sa_release(mp_saopd *pl, void *p)
     (void)hipFree(p);
 }
 
-template <typename T>
-static int grow_rows(mp_saopd *pl, T **buf, size_t used_rows, size_t old_cap, size_t new_cap, size_t n, bool planner_major, hipStream_t st)
+// grow a node array of `elem`-byte rows from old_cap to new_cap rows per planner, keeping the used_rows rows in use
+static int grow_rows(mp_saopd *pl, void **buf, size_t elem, size_t used_rows, size_t old_cap, size_t new_cap, size_t n, bool planner_major,
+                     hipStream_t st)
 {
-    T *nw = nullptr;
-    MP_HIP(sa_alloc(pl, &nw, new_cap * n * sizeof(T)));
+    char *nw = nullptr;
+    MP_HIP(sa_alloc(pl, &nw, new_cap * n * elem));
     if (*buf) {
         if (planner_major) { // [planner][row]: every planner's prefix moves to its new pitch
             if (used_rows)
-                MP_HIP(hipMemcpy2DAsync(nw, new_cap * sizeof(T), *buf, old_cap * sizeof(T), used_rows * sizeof(T), n,
-                                        hipMemcpyDeviceToDevice, st));
+                MP_HIP(hipMemcpy2DAsync(nw, new_cap * elem, *buf, old_cap * elem, used_rows * elem, n, hipMemcpyDeviceToDevice, st));
         } else {             // [row][planner]: one contiguous prefix
-            MP_HIP(hipMemcpyAsync(nw, *buf, used_rows * n * sizeof(T), hipMemcpyDeviceToDevice, st));
+            MP_HIP(hipMemcpyAsync(nw, *buf, used_rows * n * elem, hipMemcpyDeviceToDevice, st));
         }
         MP_HIP(hipStreamSynchronize(st));
         sa_release(pl, *buf);
@@ -1656,9 +1657,290 @@ static int grow_rows(mp_saopd *pl, T **buf, size_t used_rows, size_t old_cap, si
     return MP_OK;
 }
 
+// ---- the MP_SAOPD_* knobs (kSaUnset / LONG_MIN: not set), read once per call -- tests change them between calls
+constexpr int kSaUnset = INT_MIN;
+struct SaKnobs {
+    int lane;                         // MP_SAOPD_MODEL: 1 a value that begins with 'l' (one planner per lane), 0 any other value
+    int lds, dict, order, par_backup; // MP_SAOPD_LDS / DICT / ORDER / PAR_BACKUP: 1 a value that begins with '1', 0 any other value
+    int csr;                          // MP_SAOPD_CSR: 0 a value that begins with '0', 1 any other value
+    int lane_scratch, prune_rows;     // MP_SAOPD_LANE_SCRATCH / PRUNE_ROWS: their atoi
+    long queue, queue_limit_mb;       // MP_SAOPD_QUEUE (entries per planner) / QUEUE_LIMIT_MB: their atol
+};
+static SaKnobs sa_knobs_read()
+{
+    auto begins = [](const char *name, char c) { const char *e = getenv(name); return e ? (int)(e[0] == c) : kSaUnset; };
+    auto number = [](const char *name) { const char *e = getenv(name); return e ? atoi(e) : kSaUnset; };
+    auto number_long = [](const char *name) { const char *e = getenv(name); return e ? atol(e) : LONG_MIN; };
+    SaKnobs k;
+    k.lane = begins("MP_SAOPD_MODEL", 'l');
+    k.lds = begins("MP_SAOPD_LDS", '1'); k.dict = begins("MP_SAOPD_DICT", '1'); k.order = begins("MP_SAOPD_ORDER", '1');
+    k.par_backup = begins("MP_SAOPD_PAR_BACKUP", '1');
+    const int csr_off = begins("MP_SAOPD_CSR", '0');
+    k.csr = csr_off == kSaUnset ? kSaUnset : !csr_off;
+    k.lane_scratch = number("MP_SAOPD_LANE_SCRATCH"); k.prune_rows = number("MP_SAOPD_PRUNE_ROWS");
+    k.queue = number_long("MP_SAOPD_QUEUE"); k.queue_limit_mb = number_long("MP_SAOPD_QUEUE_LIMIT_MB");
+    return k;
+}
+
+// one planner per wavefront unless asked otherwise (MP_SAOPD_MODEL=lane: one per lane, the first implementation), or |A| > 64
+static bool sa_wave_mapping(int A, const SaKnobs &k) { return k.lane != 1 && A <= 64; }
+
+// scratch entries per lane in the prune pass of a queue of qcap entries
+static int sa_lane_scratch(int qcap, const SaKnobs &k)
+{
+    int v = qcap >> 6;
+    if (k.lane_scratch != kSaUnset && k.lane_scratch >= 0 && k.lane_scratch < v) v = k.lane_scratch; // test knob: a tiny slice forces the serial prune pass
+    return v;
+}
+
+// ---- which kernel form a plan takes, and every size it derives from the call: a pure host function of the call's shape, what
+// the planners hold and the knobs.  No HIP call, no mp_saopd: mp_saopd_choose_form runs it without a device.  DESIGN.md §4.10
+// tabulates the forms.
+struct SaCall {
+    int n, S, A, budget;
+    int n_nodes;         // the rows kept per planner (0: fresh planners)
+    int cap, qcap;       // the rows and the queue entries allocated per planner (0: none yet)
+    bool wave;           // the planners' mapping (sa_wave_mapping when they were created)
+    bool have_cost;      // there are costs to sort by: an earlier plan of these planners, or of another batch on the model
+    bool device_arrays;  // the asynchronous mode
+    int cus;             // compute units (<= 0: taken as 256)
+};
+struct SaChoice {
+    SaopdForm form, fallback;  // the first launch; the form a queue overflow runs again on (the same one unless the arena is in LDS)
+    size_t lds, lds_fallback;  // their dynamic LDS bytes
+    int K, need, cap, qcap;    // iterations; rows after the plan, rows and queue entries to have allocated before it
+    long pool_ints;
+    int tab_plain, tab_lds, lds_rows, lds_qcap;
+    int scap, scap_global;     // scratch entries per lane of the first launch / of the forms with the queue in global memory
+    int par_backup, csr_old, prune_rows, sticky;
+    bool ordered;              // saopd_order_kernel runs
+    size_t max_queue_bytes;    // per batch: a full queue grows up to here
+};
+
+static int sa_choose(const SaCall &c, const SaKnobs &k, SaChoice *out)
+{
+    SaChoice &ch = *out;
+    const int A = c.A, n = c.n;
+    const bool wave = c.wave, fresh = c.n_nodes == 0, async = c.device_arrays;
+    const long cus = c.cus > 0 ? c.cus : 256;
+    const int K = ch.K = c.budget / A; // deterministic.py:118
+    if (K + 2 > (int)SA_DEPTH) return fail(MP_ERR_ARG, "mp_saopd_plan: budget too large");
+    // backup queue: the reference's list holds duplicates and reaches ~10x the node count of a plan (4 600 entries at
+    // 325 nodes on the 10x10 grid); 32 entries per node of this plan, at least 4096, a power of two.  MP_SAOPD_QUEUE
+    // sets the entries per planner; a full queue is reported per planner (MP_ERR_ALLOC), never dropped silently.
+    // The queue is empty between plans, so it can be replaced when a larger budget comes along.
+    {
+        long want = 32L * (1 + K * A);
+        int q = 4096;
+        if (k.queue != LONG_MIN) { want = k.queue; q = 2; }
+        while (q < want && q < (1 << 28)) q <<= 1;
+        ch.qcap = q > c.qcap ? q : c.qcap;
+        if (1 + K * A > ch.qcap) // the prune pass lists its candidate leaves in the idle queue
+            return fail(MP_ERR_ARG, "mp_saopd_plan: queue of %d entries is smaller than the %d nodes of a plan", ch.qcap, 1 + K * A);
+    }
+    const int need = ch.need = c.n_nodes + 1 + K * A;
+    ch.cap = need > c.cap ? need + (need - c.cap < 4096 ? need / 2 : 0) : c.cap; // some slack for the following plans
+    {   // chunk pool: at most one partly filled chunk per non-empty state, contents rebuilt by every plan (nothing to keep)
+        const long states = c.S < ch.cap ? c.S : ch.cap;
+        ch.pool_ints = 16L * (states + ch.cap / 15 + 2);
+    }
+    ch.scap_global = sa_lane_scratch(ch.qcap, k);
+    // The grouped parallel backup pays where the backups are: the first plan of fresh planners runs ~4 200 of them, the
+    // following plans ~200 -- there the upkeep of the chunked lists (rebuild at the start, two more accesses per append)
+    // costs more than it saves (16 384 planners: 7.8 / 9.0 ms against 6.9 / 7.9).  MP_SAOPD_PAR_BACKUP=0|1 forces it.
+    ch.par_backup = fresh ? 1 : 0;
+    if (k.par_backup != kSaUnset) ch.par_backup = k.par_backup;
+    ch.csr_old = 1;
+    if (k.csr != kSaUnset) ch.csr_old = k.csr ? 2 : 0;
+    ch.prune_rows = 256;
+    if (k.prune_rows != kSaUnset) // test knob: 0 = every changed state through the streamed form
+        ch.prune_rows = k.prune_rows < 0 ? 0 : (k.prune_rows > 256 ? 256 : k.prune_rows);
+
+    // tables (+ 512 B the wave kernel uses as a counter).  The wave kernels keep at most 2 560 depth entries (60 KB) in LDS and
+    // read deeper nodes' entries from the global copy, so the budget is not bounded by LDS (round 4); the lane kernel holds them all
+    ch.tab_plain = wave ? std::min(K + 3, 2560) : K + 3;
+    const size_t lds = (size_t)3 * ch.tab_plain * sizeof(double) + 128 * sizeof(int32_t);
+    if (lds > 64 * 1024)
+        return fail(MP_ERR_ARG, "mp_saopd_plan: budget %d needs %zu B of LDS tables (> 64 KiB) in the one-planner-per-lane kernel", c.budget, lds);
+    // LDS-resident variant of the wave kernel: the arena after this plan, the dictionaries and a (smaller) queue in LDS.
+    // A queue overflow there rolls the plan back like any other and the retry runs on the global-memory form.
+    ch.lds_rows = need;
+    ch.lds_qcap = 4096;
+    while (ch.lds_qcap < 2 * (1 + K * A) && ch.lds_qcap < (1 << 20)) ch.lds_qcap <<= 1; // the prune pass lists a plan's leaves in it
+    if (k.queue != LONG_MIN && ch.qcap < ch.lds_qcap) ch.lds_qcap = ch.qcap; // (test knob: a deliberately small queue)
+    const size_t lds_res = ((lds + 15) & ~(size_t)15) + 16 + (size_t)need * (16 + 8 + 12) + (size_t)c.S * (8 + 12) + (size_t)ch.lds_qcap * 4;
+    // Measured (GridWorld 10x10, budget 500, first plan / following plans): 1 planner 4.8 / 2.4 ms against 6.1 / 3.1 ms
+    // from global memory, 64 planners 11.6 / 5.6 ms against 14.4 / 7.0 ms -- but 4 096 planners 32 / 40 ms against
+    // 22 / 16 ms: the chain is bound by the wave's own instruction latency (~300 ns per dependent step even from LDS), so
+    // what a big batch needs is resident waves, which 39 KB of LDS per planner takes away.  Hence: latency mode only,
+    // at most one planner per CU.
+    bool use_lds = wave && lds_res <= kLdsBytes - 1024 && n <= cus;
+    if (k.lds != kSaUnset) use_lds = wave && lds_res <= kLdsBytes - 1024 && k.lds;
+    // dictionaries in LDS (LDSD): while they leave five planners per SIMD
+    // (5 KB per planner = 32 per CU = eight waves per SIMD; the depth tables take what the dictionaries leave, at least 16 entries)
+    const long dict_room = 5 * 1024 - 32 - (long)c.S * (8 + 16 + 16);
+    ch.tab_lds = (int)std::min<long>(K + 3, dict_room / 24);
+    const size_t lds_dict = (size_t)ch.tab_lds * 24 + 32 + (size_t)c.S * (8 + 16 + 16);
+    bool use_dict = wave && ch.tab_lds >= 16;
+    if (k.dict != kSaUnset) use_dict = use_dict && k.dict;
+    // with the dictionaries in LDS and the grouped backup the global-memory arena is as fast for ONE planner as the all-in-LDS
+    // latency mode (first plan, light / heavy root: 1.4 / 3.3 ms against 1.4 / 4.6 ms): MP_SAOPD_LDS=1 still forces that one
+    if (use_dict && k.lds == kSaUnset) use_lds = false;
+    // mem = MP_MEM_DEVICE: ASYNCHRONOUS -- one launch, nothing read back.  A planner whose backup queue fills up cannot be
+    // rolled back and retried then: it reports MP_ERR_ALLOC and stays failed (every later call reports it again), the
+    // other planners of the batch are unaffected.  With host arrays the call synchronises anyway, reads the overflow
+    // word and retries with a larger queue.
+    ch.sticky = async ? 1 : 0;
+    if (async) use_lds = false; // (its small queue relies on the retry)
+    ch.scap = use_lds && ch.lds_qcap >> 6 < ch.scap_global ? ch.lds_qcap >> 6 : ch.scap_global;
+    ch.max_queue_bytes = (size_t)8 << 30; // per batch; MP_SAOPD_QUEUE_LIMIT_MB overrides
+    if (k.queue_limit_mb != LONG_MIN) ch.max_queue_bytes = (size_t)k.queue_limit_mb << 20;
+    // Dispatch order (wave kernel, batches beyond one residency round = 32 planners per CU): by the cost of the planner's
+    // previous plan, or -- fresh planners -- by what first plans from the same root state cost on this model so far.
+    // Only the ORDER in which workgroups start depends on it; MP_SAOPD_ORDER=0 keeps the index order.
+    bool ordered = wave && n > 32 * cus;
+    if (k.order != kSaUnset) ordered = wave && k.order;
+    ch.ordered = ordered && c.have_cost;
+    ch.fallback = {wave, use_dict, false, ch.ordered, false};
+    ch.lds_fallback = use_dict ? lds_dict : lds;
+    ch.form = ch.fallback;
+    ch.lds = ch.lds_fallback;
+    if (use_lds) { ch.form.dict = false; ch.form.lds = true; ch.lds = lds_res; }
+    return MP_OK;
+}
+
 } // namespace mp
 
 using namespace mp;
+
+// ---- the steps of mp_saopd_plan
+// the queue (empty between plans: replaced), the node rows (kept: moved) and the chunk pool (rebuilt by every plan: replaced)
+static int sa_reserve(mp_saopd *pl, const SaChoice &ch, hipStream_t st)
+{
+    const size_t n = (size_t)pl->n;
+    if (ch.qcap > pl->qcap) {
+        if (pl->queue) { MP_HIP(hipStreamSynchronize(st)); sa_release(pl, pl->queue); pl->queue = nullptr; pl->qcap = 0; }
+        if (sa_alloc(pl, &pl->queue, n * ch.qcap * 4) != hipSuccess)
+            return fail(MP_ERR_ALLOC, "mp_saopd_plan: %zu B for the backup queues", n * ch.qcap * 4);
+        pl->qcap = ch.qcap;
+    }
+    if (ch.cap > pl->cap) {
+        const struct { void **buf; size_t elem; } rows[] = {
+            {(void **)&pl->node, sizeof(SaNode)}, {(void **)&pl->state, 4}, {(void **)&pl->parent, 4}, {(void **)&pl->first_child, 4},
+            {(void **)&pl->reward, 8}, {(void **)&pl->done, 1}, {(void **)&pl->oldlive, sizeof(int2)}};
+        for (const auto &r : rows) MP_TRY(grow_rows(pl, r.buf, r.elem, (size_t)pl->n_nodes, (size_t)pl->cap, (size_t)ch.cap, n, pl->wave != 0, st));
+        pl->cap = ch.cap;
+    }
+    if (ch.pool_ints > pl->pool_ints) {
+        if (pl->lpool) { MP_HIP(hipStreamSynchronize(st)); sa_release(pl, pl->lpool); pl->lpool = nullptr; pl->pool_ints = 0; }
+        if (sa_alloc(pl, &pl->lpool, n * ch.pool_ints * 4) != hipSuccess)
+            return fail(MP_ERR_ALLOC, "mp_saopd_plan: %zu B for the state-list chunks", n * ch.pool_ints * 4);
+        pl->pool_ints = ch.pool_ints;
+    }
+    return MP_OK;
+}
+
+// tables with the reference's own operations: gpow[K+3] | trg[K+3] | acc[K+3]
+static int sa_tables(mp_ctx *ctx, int K, double gamma, double terminal_reward, double accuracy, const double **d_tab)
+{
+    std::vector<double> tab((size_t)3 * (K + 3));
+    double *gpow = tab.data(), *trg = gpow + (K + 3), *acc = trg + (K + 3);
+    for (int d = 0; d < K + 3; ++d) {
+        gpow[d] = pow(gamma, (double)d);                                          // gamma ** depth
+        trg[d] = terminal_reward * gpow[d] / (1 - gamma);                          // deterministic.py:60
+        acc[d] = d >= 1 ? accuracy * (1 - gamma) * pow(gamma, (double)(d - 1)) : 0.0; // state_aware.py:62
+    }
+    double *d = nullptr;
+    MP_TRY(upload_tables(ctx, 3, tab, &d));
+    *d_tab = d;
+    return MP_OK;
+}
+
+// what the kernels read of the planners and of the choice; the call's own values and arrays are the caller's to fill in
+static void sa_args_of(const mp_saopd *pl, const SaChoice &ch, SaArgs *out)
+{
+    SaArgs &a = *out;
+    a.n = pl->n; a.S = pl->S; a.A = pl->A; a.K = ch.K; a.root = pl->n_nodes; a.n_prev = pl->n_nodes;
+    a.prev_root = pl->root < 0 ? 0 : pl->root; a.qcap = pl->qcap;
+    a.done_on_next = pl->model->done_on_next; a.fresh = pl->n_nodes == 0;
+    a.rec = pl->model->rec;
+    a.node = pl->node; a.state = pl->state; a.parent = pl->parent; a.first_child = pl->first_child;
+    a.reward = pl->reward; a.done = pl->done; a.oldlive = pl->oldlive; a.lstate = pl->lstate;
+    a.lpool = pl->lpool; a.pool_ints = pl->pool_ints; a.sv = pl->sv; a.head = pl->head; a.tail = pl->tail; a.queue = pl->queue;
+    a.stamp = pl->stamp; a.iter_base = pl->iters; a.cap = pl->cap;
+    a.scap = ch.scap; a.par_backup = ch.par_backup; a.csr_old = ch.csr_old; a.prune_rows = ch.prune_rows;
+    a.tab_plain = ch.tab_plain; a.tab_lds = ch.tab_lds; a.lds_rows = ch.lds_rows; a.lds_qcap = ch.lds_qcap;
+    a.sticky = ch.sticky; a.overflow = pl->overflow;
+    a.order = nullptr; a.cost = pl->wave ? pl->cost : nullptr;
+}
+
+// What a plan changes outside its own node rows: the per-state dictionaries, the list links of older tail nodes and the
+// generator states.  They are copied first, so that a plan that fills its backup queue (values decaying to floating-point
+// underflow make the reference run tens of thousands of backups) can be rolled back and run again with a larger queue.
+// Costs one 4-byte read-back (a stream synchronisation) per call.  Fresh planners hold no dictionaries yet.  `restore`: the
+// copies go back, and a kernel (-> *launches + 1) mends the list links.
+static int sa_snapshot(mp_saopd *pl, uint64_t *rng, bool fresh, hipStream_t st, bool restore = false, int *launches = nullptr)
+{
+    const size_t sn = (size_t)pl->S * pl->n;
+    const struct { void *live, *copy; size_t bytes; } kept[5] = {
+        {pl->sv, pl->snap_sv, sn * 8}, {pl->head, pl->snap_head, sn * 4}, {pl->tail, pl->snap_tail, sn * 4},
+        {pl->stamp, pl->snap_stamp, sn * 4}, {rng, pl->snap_rng, (size_t)pl->n * 48}};
+    auto copy = [&](int i) {
+        return hipMemcpyAsync(restore ? kept[i].live : kept[i].copy, restore ? kept[i].copy : kept[i].live, kept[i].bytes, hipMemcpyDeviceToDevice, st);
+    };
+    for (int i = fresh ? 4 : 0; i < 4; ++i) MP_HIP(copy(i));
+    if (restore && !fresh) { // undo the list appends of the rolled-back plan: with the tails restored, every tail is the end of its list again
+        hipLaunchKernelGGL(saopd_fix_tails_kernel, dim3((unsigned)((sn + 63) / 64)), dim3(64), 0, st, pl->n, pl->S, pl->node_si(),
+                           pl->node_sr(), pl->state_si(), pl->state_sr(), pl->tail, pl->node);
+        ++*launches;
+    }
+    MP_HIP(copy(4));
+    return MP_OK;
+}
+static int sa_restore(mp_saopd *pl, uint64_t *rng, bool fresh, hipStream_t st, int *launches) { return sa_snapshot(pl, rng, fresh, st, true, launches); }
+
+// the planning kernel of a form: one workgroup per planner, or one lane
+static int sa_launch(const SaopdForm &f, size_t lds, const SaArgs &a, hipStream_t st)
+{
+    const dim3 grid((unsigned)(f.wave ? a.n : (a.n + 63) / 64)), wg(64);
+    if (f.lds) {
+        if (lds > 64 * 1024)
+            MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(saopd_wave_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(saopd_wave_kernel<true>, grid, wg, lds, st, a);
+    } else if (f.dict) hipLaunchKernelGGL((saopd_wave_kernel<false, true>), grid, wg, lds, st, a);
+    else if (f.wave) hipLaunchKernelGGL(saopd_wave_kernel<false>, grid, wg, lds, st, a);
+    else hipLaunchKernelGGL(saopd_kernel, grid, wg, lds, st, a);
+    return MP_OK;
+}
+
+// a full queue in global memory, host arrays: one four times as large, unless that passes the batch's limit (-> *grown = false)
+static int sa_queue_grow(mp_saopd *pl, const SaKnobs &knobs, size_t max_queue_bytes, SaArgs *a, bool *grown)
+{
+    const size_t bigger = (size_t)pl->n * pl->qcap * 4 * 4;
+    *grown = bigger <= max_queue_bytes;
+    if (!*grown) return MP_OK;
+    const int qcap = pl->qcap * 4;
+    sa_release(pl, pl->queue);
+    pl->queue = nullptr; pl->qcap = 0;
+    if (sa_alloc(pl, &pl->queue, bigger) != hipSuccess) return fail(MP_ERR_ALLOC, "mp_saopd_plan: %zu B for the backup queues", bigger);
+    pl->qcap = qcap;
+    a->queue = pl->queue; a->qcap = pl->qcap;
+    a->scap = sa_lane_scratch(pl->qcap, knobs);
+    return MP_OK;
+}
+
+// the wave kernel's costs are there to sort the next plan by; what the first plan of a fresh planner cost is remembered by
+// root state with the model (-> *launches + 1)
+static void sa_learn(mp_saopd *pl, const SaArgs &a, bool fresh, hipStream_t st, int *launches)
+{
+    if (!pl->wave) return;
+    pl->cost_valid = true;
+    if (fresh && pl->model->sa_cost) {
+        hipLaunchKernelGGL(saopd_learn_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, st, a.n, pl->model->S, a.root_state, pl->cost,
+                           a.status, pl->model->sa_cost);
+        ++*launches;
+    }
+}
 
 extern "C" {
 
@@ -1672,10 +1954,7 @@ int mp_saopd_create(mp_ctx *ctx, mp_model *model, int32_t n_planners, mp_saopd *
     mp_saopd *pl = new (std::nothrow) mp_saopd;
     if (!pl) return fail(MP_ERR_ALLOC, "mp_saopd_create: out of memory");
     pl->ctx = ctx; pl->model = model; pl->model_serial = model->serial; pl->n = n_planners; pl->S = model->S; pl->A = model->A;
-    // one planner per wavefront unless asked otherwise (MP_SAOPD_MODEL=lane: one per lane, the first implementation)
-    const char *force = getenv("MP_SAOPD_MODEL");
-    pl->wave = !(force && force[0] == 'l');
-    if (pl->wave && model->A > 64) pl->wave = 0;
+    pl->wave = sa_wave_mapping(model->A, sa_knobs_read());
     const size_t sn = (size_t)pl->S * pl->n;
     if (sa_alloc(pl, &pl->sv, sn * 8) != hipSuccess || sa_alloc(pl, &pl->head, sn * 4) != hipSuccess ||
         sa_alloc(pl, &pl->tail, sn * 4) != hipSuccess || sa_alloc(pl, &pl->stamp, sn * 4) != hipSuccess ||
@@ -1722,176 +2001,43 @@ int mp_saopd_plan(mp_ctx *ctx, mp_saopd *pl, const int32_t *root_state, int32_t 
         return fail(MP_ERR_ARG, "mp_saopd_plan: gamma changed (%g -> %g) on a planner that holds state values", pl->gamma, gamma);
     MP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const int A = pl->A, n = pl->n;
-    const int K = budget / A; // deterministic.py:118
-    if (K + 2 > (int)SA_DEPTH) return fail(MP_ERR_ARG, "mp_saopd_plan: budget too large");
-    // backup queue: the reference's list holds duplicates and reaches ~10x the node count of a plan (4 600 entries at
-    // 325 nodes on the 10x10 grid); 32 entries per node of this plan, at least 4096, a power of two.  MP_SAOPD_QUEUE
-    // sets the entries per planner; a full queue is reported per planner (MP_ERR_ALLOC), never dropped silently.
-    // The queue is empty between plans, so it can be replaced when a larger budget comes along.
-    {
-        long want = 32L * (1 + K * A);
-        int q = 4096;
-        if (const char *e = getenv("MP_SAOPD_QUEUE")) { want = atol(e); q = 2; }
-        while (q < want && q < (1 << 28)) q <<= 1;
-        if (q > pl->qcap) {
-            if (pl->queue) { MP_HIP(hipStreamSynchronize(ctx->stream)); sa_release(pl, pl->queue); pl->queue = nullptr; }
-            if (sa_alloc(pl, &pl->queue, (size_t)pl->n * q * 4) != hipSuccess)
-                return fail(MP_ERR_ALLOC, "mp_saopd_plan: %zu B for the backup queues", (size_t)pl->n * q * 4);
-            pl->qcap = q;
-        }
-        if (1 + K * A > pl->qcap) // the prune pass lists its candidate leaves in the idle queue
-            return fail(MP_ERR_ARG, "mp_saopd_plan: queue of %d entries is smaller than the %d nodes of a plan", pl->qcap, 1 + K * A);
-    }
-    const int need = pl->n_nodes + 1 + K * A;
-    if (need > pl->cap) {
-        const int new_cap = need + (need - pl->cap < 4096 ? need / 2 : 0); // some slack for the following plans
-        const size_t o = (size_t)pl->n_nodes, oc = (size_t)pl->cap;
-        const bool pm = pl->wave != 0;
-        MP_TRY(grow_rows(pl, &pl->node, o, oc, new_cap, n, pm, st));
-        MP_TRY(grow_rows(pl, &pl->state, o, oc, new_cap, n, pm, st));
-        MP_TRY(grow_rows(pl, &pl->parent, o, oc, new_cap, n, pm, st));
-        MP_TRY(grow_rows(pl, &pl->first_child, o, oc, new_cap, n, pm, st));
-        MP_TRY(grow_rows(pl, &pl->reward, o, oc, new_cap, n, pm, st));
-        MP_TRY(grow_rows(pl, &pl->done, o, oc, new_cap, n, pm, st));
-        MP_TRY(grow_rows(pl, &pl->oldlive, o, oc, new_cap, n, pm, st));
-        pl->cap = new_cap;
-    }
-    {   // chunk pool: at most one partly filled chunk per non-empty state, contents rebuilt by every plan (nothing to keep)
-        const long states = pl->S < pl->cap ? pl->S : pl->cap;
-        const long want = 16L * (states + pl->cap / 15 + 2);
-        if (want > pl->pool_ints) {
-            if (pl->lpool) { MP_HIP(hipStreamSynchronize(st)); sa_release(pl, pl->lpool); pl->lpool = nullptr; }
-            if (sa_alloc(pl, &pl->lpool, (size_t)n * want * 4) != hipSuccess)
-                return fail(MP_ERR_ALLOC, "mp_saopd_plan: %zu B for the state-list chunks", (size_t)n * want * 4);
-            pl->pool_ints = want;
-        }
-    }
-    // tables with the reference's own operations
-    std::vector<double> tab((size_t)3 * (K + 3));
-    double *gpow = tab.data(), *trg = gpow + (K + 3), *acc = trg + (K + 3);
-    for (int d = 0; d < K + 3; ++d) {
-        gpow[d] = pow(gamma, (double)d);                                          // gamma ** depth
-        trg[d] = terminal_reward * gpow[d] / (1 - gamma);                          // deterministic.py:60
-        acc[d] = d >= 1 ? accuracy * (1 - gamma) * pow(gamma, (double)(d - 1)) : 0.0; // state_aware.py:62
-    }
-    double *d_tab = nullptr;
-    MP_TRY(upload_tables(ctx, 3, tab, &d_tab));
+    const int n = pl->n;
+    const bool async = mem == MP_MEM_DEVICE;
+    const SaKnobs knobs = sa_knobs_read();
+    const SaCall call = {n, pl->S, pl->A, budget, pl->n_nodes, pl->cap, pl->qcap, pl->wave != 0,
+                         fresh ? pl->model->sa_cost != nullptr : pl->cost_valid, async, ctx->prop.multiProcessorCount};
+    SaChoice ch;
+    MP_TRY(sa_choose(call, knobs, &ch));
+    MP_TRY(sa_reserve(pl, ch, st));
 
     SaArgs a;
-    a.n = n; a.S = pl->S; a.A = A; a.K = K; a.root = pl->n_nodes; a.n_prev = pl->n_nodes;
-    a.prev_root = pl->root < 0 ? 0 : pl->root; a.qcap = pl->qcap;
-    a.done_on_next = pl->model->done_on_next; a.max_plan_len = max_plan_len;
-    a.backup_aggregated = backup_aggregated_nodes ? 1 : 0; a.prune = prune_suboptimal_leaves ? 1 : 0; a.fresh = fresh;
+    sa_args_of(pl, ch, &a);
+    a.max_plan_len = max_plan_len;
+    a.backup_aggregated = backup_aggregated_nodes ? 1 : 0; a.prune = prune_suboptimal_leaves ? 1 : 0;
     a.gamma = gamma; a.vmax = 1 / (1 - gamma);
-    a.rec = pl->model->rec; a.tab = d_tab;
-    a.node = pl->node; a.state = pl->state; a.parent = pl->parent; a.first_child = pl->first_child;
-    a.reward = pl->reward; a.done = pl->done; a.oldlive = pl->oldlive; a.lstate = pl->lstate;
-    a.lpool = pl->lpool; a.pool_ints = pl->pool_ints; a.sv = pl->sv; a.head = pl->head; a.tail = pl->tail; a.queue = pl->queue;
-    a.stamp = pl->stamp; a.iter_base = pl->iters; a.cap = pl->cap;
-    auto lane_scratch = [&]() {
-        int v = pl->qcap >> 6;
-        if (const char *e = getenv("MP_SAOPD_LANE_SCRATCH")) { // test knob: a tiny slice forces the serial prune pass
-            const int w = atoi(e);
-            if (w >= 0 && w < v) v = w;
-        }
-        return v;
-    };
-    a.scap = lane_scratch();
-    // The grouped parallel backup pays where the backups are: the first plan of fresh planners runs ~4 200 of them, the
-    // following plans ~200 -- there the upkeep of the chunked lists (rebuild at the start, two more accesses per append)
-    // costs more than it saves (16 384 planners: 7.8 / 9.0 ms against 6.9 / 7.9).  MP_SAOPD_PAR_BACKUP=0|1 forces it.
-    a.par_backup = fresh ? 1 : 0;
-    if (const char *e = getenv("MP_SAOPD_PAR_BACKUP")) a.par_backup = e[0] == '1';
-    a.csr_old = 1;
-    if (const char *e = getenv("MP_SAOPD_CSR")) a.csr_old = e[0] == '0' ? 0 : 2;
-    a.prune_rows = 256;
-    if (const char *e = getenv("MP_SAOPD_PRUNE_ROWS")) { // test knob: 0 = every changed state through the streamed form
-        const int v = atoi(e);
-        a.prune_rows = v < 0 ? 0 : (v > 256 ? 256 : v);
-    }
-    int32_t *d_rs = nullptr;
-    MP_TRY(stage_in(ctx, WS_IO0, root_state, (size_t)n, mem, &d_rs));
-    a.root_state = d_rs;
-    MP_TRY(stage_in(ctx, WS_IO2, (const uint64_t *)rng_state, (size_t)n * 6, rmem, &a.rng));
-    MP_TRY(stage_out_alloc(ctx, WS_IO3, plans, (size_t)n * max_plan_len, mem, &a.plans));
-    MP_TRY(stage_out_alloc(ctx, WS_IO4, plan_len, (size_t)n, mem, &a.plan_len));
-    MP_TRY(stage_out_alloc(ctx, WS_IO5, status, (size_t)n, mem, &a.status));
-    MP_TRY(stage_out_alloc(ctx, WS_IO6, env_steps, (size_t)n, mem, &a.env_steps));
-    MP_TRY(stage_out_alloc(ctx, WS_IO7, updates, (size_t)n, mem, &a.updates));
-
-    // tables (+ 512 B the wave kernel uses as a counter).  The wave kernels keep at most 2 560 depth entries (60 KB) in LDS and
-    // read deeper nodes' entries from the global copy, so the budget is not bounded by LDS (round 4); the lane kernel holds them all
-    a.tab_plain = pl->wave ? std::min(K + 3, 2560) : K + 3;
-    const size_t lds = (size_t)3 * a.tab_plain * sizeof(double) + 128 * sizeof(int32_t);
-    if (lds > 64 * 1024)
-        return fail(MP_ERR_ARG, "mp_saopd_plan: budget %d needs %zu B of LDS tables (> 64 KiB) in the one-planner-per-lane kernel", budget, lds);
-    // LDS-resident variant of the wave kernel: the arena after this plan, the dictionaries and a (smaller) queue in LDS.
-    // A queue overflow there rolls the plan back like any other and the retry runs on the global-memory form.
-    a.lds_rows = need;
-    a.lds_qcap = 4096;
-    while (a.lds_qcap < 2 * (1 + K * A) && a.lds_qcap < (1 << 20)) a.lds_qcap <<= 1; // the prune pass lists a plan's leaves in it
-    if (getenv("MP_SAOPD_QUEUE") && pl->qcap < a.lds_qcap) a.lds_qcap = pl->qcap; // (test knob: a deliberately small queue)
-    const size_t lds_res = ((lds + 15) & ~(size_t)15) + 16 + (size_t)need * (16 + 8 + 12) + (size_t)pl->S * (8 + 12) + (size_t)a.lds_qcap * 4;
-    // Measured (GridWorld 10x10, budget 500, first plan / following plans): 1 planner 4.8 / 2.4 ms against 6.1 / 3.1 ms
-    // from global memory, 64 planners 11.6 / 5.6 ms against 14.4 / 7.0 ms -- but 4 096 planners 32 / 40 ms against
-    // 22 / 16 ms: the chain is bound by the wave's own instruction latency (~300 ns per dependent step even from LDS), so
-    // what a big batch needs is resident waves, which 39 KB of LDS per planner takes away.  Hence: latency mode only,
-    // at most one planner per CU.
-    bool use_lds = pl->wave && lds_res <= kLdsBytes - 1024 && n <= ctx->prop.multiProcessorCount;
-    if (const char *e = getenv("MP_SAOPD_LDS")) use_lds = pl->wave && lds_res <= kLdsBytes - 1024 && e[0] == '1';
-    // mem = MP_MEM_DEVICE: ASYNCHRONOUS -- one launch, nothing read back.  A planner whose backup queue fills up cannot be
-    // rolled back and retried then: it reports MP_ERR_ALLOC and stays failed (every later call reports it again), the
-    // other planners of the batch are unaffected.  With host arrays the call synchronises anyway, reads the overflow
-    // word and retries with a larger queue.
-    // dictionaries in LDS (LDSD): while they leave five planners per SIMD
-    // (5 KB per planner = 32 per CU = eight waves per SIMD; the depth tables take what the dictionaries leave, at least 16 entries)
-    const long dict_room = 5 * 1024 - 32 - (long)pl->S * (8 + 16 + 16);
-    a.tab_lds = (int)std::min<long>(K + 3, dict_room / 24);
-    const size_t lds_dict = (size_t)a.tab_lds * 24 + 32 + (size_t)pl->S * (8 + 16 + 16);
-    bool use_dict = pl->wave && a.tab_lds >= 16;
-    if (const char *e = getenv("MP_SAOPD_DICT")) use_dict = use_dict && e[0] == '1';
-    // with the dictionaries in LDS and the grouped backup the global-memory arena is as fast for ONE planner as the all-in-LDS
-    // latency mode (first plan, light / heavy root: 1.4 / 3.3 ms against 1.4 / 4.6 ms): MP_SAOPD_LDS=1 still forces that one
-    if (use_dict && !getenv("MP_SAOPD_LDS")) use_lds = false;
-    const bool async = mem == MP_MEM_DEVICE;
-    a.sticky = async ? 1 : 0;
-    if (async) use_lds = false; // (its small queue relies on the retry)
-    const int scap_global = a.scap;
-    if (use_lds) a.scap = a.lds_qcap >> 6 < a.scap ? a.lds_qcap >> 6 : a.scap;
-    // what a plan changes outside its own node rows: the per-state dictionaries, the list links of older tail nodes
-    // and the generator states.  They are copied first, so that a plan that fills its backup queue (values decaying
-    // to floating-point underflow make the reference run tens of thousands of backups) can be rolled back and run
-    // again with a larger queue.  Costs one 4-byte read-back (a stream synchronisation) per call.
-    const size_t sn = (size_t)pl->S * n;
-    a.overflow = pl->overflow;
+    MP_TRY(sa_tables(ctx, ch.K, gamma, terminal_reward, accuracy, &a.tab));
+    WaveIo io(mem, rmem, n, root_state, &a.root_state, rng_state, &a.rng);
+    io.add(WS_IO3, plans, &a.plans, (size_t)max_plan_len);
+    io.add(WS_IO4, plan_len, &a.plan_len);
+    io.add(WS_IO5, status, &a.status);
+    io.add(WS_IO6, env_steps, &a.env_steps);
+    io.add(WS_IO7, updates, &a.updates);
+    MP_TRY(wave_stage(ctx, io));
     // (an asynchronous call never rolls back -- a full queue is sticky there -- so it takes no snapshot: ADVICE r2)
-    if (!fresh && !async) {
-        MP_HIP(hipMemcpyAsync(pl->snap_sv, pl->sv, sn * 8, hipMemcpyDeviceToDevice, st));
-        MP_HIP(hipMemcpyAsync(pl->snap_head, pl->head, sn * 4, hipMemcpyDeviceToDevice, st));
-        MP_HIP(hipMemcpyAsync(pl->snap_tail, pl->tail, sn * 4, hipMemcpyDeviceToDevice, st));
-        MP_HIP(hipMemcpyAsync(pl->snap_stamp, pl->stamp, sn * 4, hipMemcpyDeviceToDevice, st));
-    }
-    if (!async) MP_HIP(hipMemcpyAsync(pl->snap_rng, a.rng, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
-    size_t max_queue_bytes = (size_t)8 << 30; // per batch; MP_SAOPD_QUEUE_LIMIT_MB overrides
-    if (const char *e = getenv("MP_SAOPD_QUEUE_LIMIT_MB")) max_queue_bytes = (size_t)atol(e) << 20;
-    int launches = 0;
-    // Dispatch order (wave kernel, batches beyond one residency round = 32 planners per CU): by the cost of the planner's
-    // previous plan, or -- fresh planners -- by what first plans from the same root state cost on this model so far.
-    // Only the ORDER in which workgroups start depends on it; MP_SAOPD_ORDER=0 keeps the index order.
-    a.order = nullptr; a.cost = pl->wave ? pl->cost : nullptr;
-    bool ordered = pl->wave && n > 32 * ctx->prop.multiProcessorCount;
-    if (const char *e = getenv("MP_SAOPD_ORDER")) ordered = pl->wave && e[0] == '1';
-    const bool have_cost = fresh ? pl->model->sa_cost != nullptr : pl->cost_valid;
+    if (!async) MP_TRY(sa_snapshot(pl, a.rng, fresh, st));
     if (pl->wave && fresh && !pl->model->sa_cost && hipMalloc(&pl->model->sa_cost, 4 * (size_t)pl->S) == hipSuccess)
         MP_HIP(hipMemsetAsync(pl->model->sa_cost, 0, 4 * (size_t)pl->S, st));
+
+    int launches = 0;
     MP_TRY(kernels_begin(ctx));
-    if (ordered && have_cost) { // (inside the timed region: the sort is part of what a plan costs)
-        hipLaunchKernelGGL(saopd_order_kernel, dim3(1), dim3(1024), 0, st, n, pl->model->S, pl->cost, fresh ? pl->model->sa_cost : nullptr, d_rs, pl->order);
+    if (ch.ordered) { // (inside the timed region: the sort is part of what a plan costs)
+        hipLaunchKernelGGL(saopd_order_kernel, dim3(1), dim3(1024), 0, st, n, pl->model->S, pl->cost, fresh ? pl->model->sa_cost : nullptr,
+                           a.root_state, pl->order);
         a.order = pl->order;
         ++launches;
     }
-    bool retried = false;
+    SaopdForm form = ch.form;
+    size_t lds = ch.lds;
     for (;;) {
         MP_HIP(hipMemsetAsync(pl->overflow, 0, 4, st));
         if (fresh) {
@@ -1900,77 +2046,58 @@ int mp_saopd_plan(mp_ctx *ctx, mp_saopd *pl, const int32_t *root_state, int32_t 
                                pl->head, pl->tail, pl->stamp);
             ++launches;
         }
-        if (pl->wave && use_lds) {
-            if (lds_res > 64 * 1024)
-                MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(saopd_wave_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_res));
-            hipLaunchKernelGGL(saopd_wave_kernel<true>, dim3((unsigned)n), dim3(64), lds_res, st, a);
-        } else if (pl->wave && use_dict) hipLaunchKernelGGL((saopd_wave_kernel<false, true>), dim3((unsigned)n), dim3(64), lds_dict, st, a);
-        else if (pl->wave) hipLaunchKernelGGL(saopd_wave_kernel<false>, dim3((unsigned)n), dim3(64), lds, st, a);
-        else hipLaunchKernelGGL(saopd_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), lds, st, a);
+        MP_TRY(sa_launch(form, lds, a, st));
         ++launches;
-        form_record(ctx->last_variant, saopd_form_name({pl->wave != 0, pl->wave && !use_lds && use_dict, pl->wave && use_lds, a.order != nullptr, retried}));
+        form_record(ctx->last_variant, saopd_form_name(form));
         if (async) break;
         int32_t ovf = 0;
         MP_HIP(hipMemcpyAsync(&ovf, pl->overflow, 4, hipMemcpyDeviceToHost, st));
         MP_HIP(hipStreamSynchronize(st));
         MP_HIP(hipGetLastError());
-        const size_t bigger = (size_t)n * pl->qcap * 4 * 4;
         if (!ovf) break;
-        if (use_lds) {
-            // the small LDS queue filled up: roll back and run the plan on the global-memory form (full-size queue)
-            use_lds = false;
-            a.scap = scap_global;
-        } else {
-            if (bigger > max_queue_bytes) { // out of room: the full planners keep MP_ERR_ALLOC, now and in later calls
+        if (form.lds) { // the small LDS queue filled up: roll back and run the plan on the global-memory form (full-size queue)
+            form = ch.fallback; lds = ch.lds_fallback;
+            a.scap = ch.scap_global;
+        } else {        // roll back and run again with a queue four times as large
+            bool grown = false;
+            MP_TRY(sa_queue_grow(pl, knobs, ch.max_queue_bytes, &a, &grown));
+            if (!grown) { // out of room: the full planners keep MP_ERR_ALLOC, now and in later calls
                 if (a.status) {
                     hipLaunchKernelGGL(saopd_mark_failed_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, n, a.status, pl->overflow);
                     ++launches;
                 }
                 break;
             }
-            // roll back and run again with a queue four times as large
-            sa_release(pl, pl->queue);
-            pl->queue = nullptr;
-            if (sa_alloc(pl, &pl->queue, bigger) != hipSuccess) return fail(MP_ERR_ALLOC, "mp_saopd_plan: %zu B for the backup queues", bigger);
-            pl->qcap *= 4;
-            a.queue = pl->queue; a.qcap = pl->qcap;
-            a.scap = lane_scratch();
         }
-        if (!fresh) {
-            MP_HIP(hipMemcpyAsync(pl->sv, pl->snap_sv, sn * 8, hipMemcpyDeviceToDevice, st));
-            MP_HIP(hipMemcpyAsync(pl->head, pl->snap_head, sn * 4, hipMemcpyDeviceToDevice, st));
-            MP_HIP(hipMemcpyAsync(pl->tail, pl->snap_tail, sn * 4, hipMemcpyDeviceToDevice, st));
-            MP_HIP(hipMemcpyAsync(pl->stamp, pl->snap_stamp, sn * 4, hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(saopd_fix_tails_kernel, dim3((unsigned)((sn + 63) / 64)), dim3(64), 0, st, n, pl->S, pl->node_si(),
-                               pl->node_sr(), pl->state_si(), pl->state_sr(), pl->tail, pl->node);
-            ++launches;
-        }
-        MP_HIP(hipMemcpyAsync(a.rng, pl->snap_rng, (size_t)n * 48, hipMemcpyDeviceToDevice, st));
-        retried = true;
+        MP_TRY(sa_restore(pl, a.rng, fresh, st, &launches));
+        form.retry = true;
     }
-    if (pl->wave) {
-        pl->cost_valid = true;
-        if (fresh && pl->model->sa_cost) { // remember the first plans' costs by root state
-            hipLaunchKernelGGL(saopd_learn_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, pl->model->S, d_rs, pl->cost, a.status,
-                               pl->model->sa_cost);
-            ++launches;
-        }
-    }
+    sa_learn(pl, a, fresh, st, &launches);
     MP_TRY(kernels_end(ctx, launches));
     MP_HIP(hipGetLastError());
     pl->gamma = gamma;
-    pl->iters += K;
+    pl->iters += ch.K;
     pl->root = pl->n_nodes;
-    pl->n_nodes = need;
+    pl->n_nodes = ch.need;
+    return wave_unstage(ctx, io);
+}
 
-    MP_TRY(stage_out_copy(ctx, rng_state, a.rng, (size_t)n * 6, rmem));
-    MP_TRY(stage_out_copy(ctx, plans, a.plans, (size_t)n * max_plan_len, mem));
-    MP_TRY(stage_out_copy(ctx, plan_len, a.plan_len, (size_t)n, mem));
-    MP_TRY(stage_out_copy(ctx, status, a.status, (size_t)n, mem));
-    MP_TRY(stage_out_copy(ctx, env_steps, a.env_steps, (size_t)n, mem));
-    MP_TRY(stage_out_copy(ctx, updates, a.updates, (size_t)n, mem));
-    if (mem == MP_MEM_HOST) MP_HIP(hipStreamSynchronize(st));
+int mp_saopd_choose_form(const int64_t *call, int64_t *out, const char **name, const char **fallback)
+{
+    if (!call || !out || !name || !fallback) return fail(MP_ERR_ARG, "mp_saopd_choose_form: NULL argument");
+    if (call[0] < 1 || call[1] < 1 || call[2] < 1 || call[3] < 0 || call[4] < 0 || call[5] < 0 || call[6] < 0)
+        return fail(MP_ERR_ARG, "mp_saopd_choose_form: bad sizes");
+    const SaKnobs knobs = sa_knobs_read();
+    const SaCall c = {(int)call[0], (int)call[1], (int)call[2], (int)call[3], (int)call[4], (int)call[5], (int)call[6],
+                      sa_wave_mapping((int)call[2], knobs), call[7] != 0, call[8] != 0, (int)call[9]};
+    SaChoice ch;
+    MP_TRY(sa_choose(c, knobs, &ch));
+    const int64_t fields[] = {c.wave, ch.K, ch.need, ch.cap, ch.qcap, ch.pool_ints, ch.tab_plain, ch.tab_lds, ch.lds_rows, ch.lds_qcap,
+                              ch.scap, ch.scap_global, ch.par_backup, ch.csr_old, ch.prune_rows, ch.sticky, ch.ordered,
+                              (int64_t)ch.lds, (int64_t)ch.lds_fallback, (int64_t)ch.max_queue_bytes};
+    memcpy(out, fields, sizeof(fields));
+    *name = saopd_form_name_static(ch.form);
+    *fallback = saopd_form_name_static(ch.fallback);
     return MP_OK;
 }
 

@@ -139,6 +139,7 @@ SIGNATURES = {
     "mp_ss_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_ss_each_form_names": (C.c_char_p, []),
     "mp_uct_choose_form": (C.c_int, [_vp, _vp, P(C.c_char_p)]),
+    "mp_saopd_choose_form": (C.c_int, [_vp, _vp, P(C.c_char_p), P(C.c_char_p)]),
     "mp_last_kernel_ms": (C.c_int, [_vp, P(c_f64), P(c_i32)]),
     "mp_last_kernel_variant": (C.c_char_p, [_vp]),
     "mp_kernel_form_names": (C.c_char_p, []),
@@ -421,6 +422,25 @@ def uct_choose_form(call):
     name = C.c_char_p()
     _check(load().mp_uct_choose_form(_ptr(c), _ptr(out), C.byref(name)))
     return name.value.decode(), out
+
+
+SAOPD_CALL_FIELDS = ("n", "S", "A", "budget", "n_nodes", "cap", "qcap", "have_cost", "device_arrays", "cus")
+SAOPD_FORM_FIELDS = ("wave", "K", "need", "cap", "qcap", "pool_ints", "tab_plain", "tab_lds", "lds_rows", "lds_qcap", "scap",
+                     "scap_global", "par_backup", "csr_old", "prune_rows", "sticky", "ordered", "lds", "lds_fallback",
+                     "max_queue_bytes")
+
+
+def saopd_choose_form(call):
+    """The kernel form StateAwarePlanners.plan chooses for a call (mp_saopd_choose_form; host only): ``call`` holds the
+    SAOPD_CALL_FIELDS in order, the MP_SAOPD_* knobs come from the environment -> (name of the first launch, name of the
+    form a full backup queue falls back to, int64 array of the SAOPD_FORM_FIELDS).  Sizes the plan refuses raise its
+    NativeError."""
+    c = np.ascontiguousarray(call, dtype=np.int64)
+    assert c.shape == (len(SAOPD_CALL_FIELDS),), c.shape
+    out = np.zeros(len(SAOPD_FORM_FIELDS), dtype=np.int64)
+    name, fallback = C.c_char_p(), C.c_char_p()
+    _check(load().mp_saopd_choose_form(_ptr(c), _ptr(out), C.byref(name), C.byref(fallback)))
+    return name.value.decode(), fallback.value.decode(), out
 
 
 def kernel_form_names():

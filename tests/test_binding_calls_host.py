@@ -691,7 +691,8 @@ def _cases():
     c["olop_allocation"] = lambda h: native.olop_allocation(100, 0.9)
     c["olop_allocation failed"] = lambda h: _failing(h, "mp_olop_allocation", -4, lambda: native.olop_allocation(1, 0.9))
     c["uct_choose_form"] = lambda h: native.uct_choose_form(list(range(len(native.UCT_CALL_FIELDS))))
-    c["form names"] = lambda h: [f() for f in (native.kernel_form_names, native.each_form_names, native.olop_stoch_form_names,
+    c["saopd_choose_form"] = lambda h: native.saopd_choose_form(list(range(len(native.SAOPD_CALL_FIELDS))))
+    c["form names"] =lambda h: [f() for f in (native.kernel_form_names, native.each_form_names, native.olop_stoch_form_names,
                                                native.ss_form_names, native.ss_each_form_names, native.vi_form_names)]
     c["each_form_info"] = lambda h: native.each_form_info("ss", S, A, HORIZON, 2)
     c["ss_geometry"] = lambda h: native.ss_geometry(A, HORIZON, 2, 1)
