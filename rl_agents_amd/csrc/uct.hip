@@ -49,6 +49,7 @@
 #include "common.hpp"
 #include "libm_sincos.hpp"
 #include "pcg64.hpp"
+#include "uct_balance.hpp"
 #include "uct_host.hpp"
 #include "uct_virgin.hpp"
 #include "wave.hpp"
@@ -113,7 +114,12 @@ struct UctArgs {
     int tree_stores; // 1: a full wave writes its expansions' zero nodes lane-contiguously and the backup stores the leaf whole;
                      // 2 (the default): as 1, and virgin groups are not loaded and, in fresh trees, not stored (VIRGIN GROUPS below);
                      // 0 (MP_UCT_TREE_STORES=lane, an A/B knob): every store per lane, first_child of an expanded node on its own
+    int balance; // host side only: 1 launches the BAL instantiation of the one-lane LDS-resident form (WAVE BALANCE in uct_kernel) with
+                 // 64 more bytes of LDS; 0: MP_UCT_BALANCE=0, any other form, or a model that leaves no room for them
     int Sb;    // batch models: states per MDP (root r plans on MDP root_state[r] / Sb); = S for any other model
+#ifdef MP_WAVE_STAMPS
+    unsigned long long *wave_stamps; // diagnostic build: [waves of the launch][kWaveStampWords], or nullptr (WAVE STAMPS in uct_kernel)
+#endif
     const Rec *rec;
     const uint16_t *t16; // compact transitions (LDS variants), [S*A]
     const uint8_t *r8;   // LDS-resident variant: index of reward[s, a] in rdict, [S*A]
@@ -203,6 +209,22 @@ __device__ __forceinline__ bool cartpole_step(const mp_cartpole_params &c, doubl
     return x < -c.x_threshold || x > c.x_threshold || theta < -c.theta_threshold || theta > c.theta_threshold;
 }
 
+// a progress word of the wave balance (uct_balance.hpp), read and written as a relaxed atomic of the workgroup: a plain LDS read or
+// write that the compiler neither keeps in a register nor moves out of the episode loop -- other waves write the words
+__device__ __forceinline__ uint32_t bal_load(const uint32_t *w) { return __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void bal_store(uint32_t *w, uint32_t v) { __hip_atomic_store(w, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+// the SIMD of its CU that the wave runs on (HW_ID bits 5:4); a wave stays where it was placed
+__device__ __forceinline__ uint32_t simd_id()
+{
+    uint32_t v;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 4, 2)" : "=s"(v));
+    return v;
+}
+#ifdef MP_WAVE_STAMPS
+constexpr int kWaveStampWords = 8;   // 64-bit words per wave: entry, staged, last episode done, exit, HW_ID | XCC_ID << 32 (three unused)
+#endif
+
 enum { ENV_TABLE = 0, ENV_CARTPOLE = 2, ENV_TABLE_LDSR = 3, ENV_TABLE_SPILL = 4 };
 // ENV_TABLE_SPILL: ENV_TABLE with the path stack in registers + a global spill array instead of LDS -- for horizons whose
 // [H + 1][64] stack would not fit (the reference has no horizon limit: tree_search/mcts.py:116-118)
@@ -243,7 +265,9 @@ constexpr bool uct_pcg_words_form(int AT, int ENV, bool SP, bool MK, int IL, boo
 // LDS through each round's four actions while the next round's draws are computed beside it: per step one LDS lookup on the
 // state chain and no generator arithmetic.  The walk consumes n draws; the generator then jumps by exactly n (limbs of A^n,
 // G_n from a table), so the stream stays the reference's.  Same trees, plans and generator states as every other variant.
-template <int AT, int ENV, bool SP = false, bool MK = false, int IL = 0, bool QD = false>
+// BAL (the one-lane LDS-resident form): WAVE BALANCE below -- a template argument, not a kernel argument, because the form has no
+// scalar register left for a flag that lives over the whole plan (a run-time flag spilled in five of its seven instantiations).
+template <int AT, int ENV, bool SP = false, bool MK = false, int IL = 0, bool QD = false, bool BAL = false>
 // Per-state-policy kernels with |A| <= 5 are held to the registers of 4 waves per SIMD (they would take 134-140 VGPRs = 3
 // waves; TA 52 %, VALU 45 %, L1 28 % busy: latency-bound -- 2.14 -> 1.91 ms at 262 144 roots with the fourth wave).
 __global__ __launch_bounds__(ENV == ENV_TABLE_LDSR ? 1024 : (ENV == ENV_CARTPOLE ? 256 : 64),
@@ -265,7 +289,12 @@ void uct_kernel(UctArgs p)
     // <=> thr << 11 <= out) instead of shifting every draw down to its 53 random bits
     constexpr bool RAWU = AT > 0 && !SP;
     constexpr int USH = RAWU ? 0 : 11;
-    extern __shared__ __attribute__((aligned(16))) double lds_d[];
+    static_assert(!BAL || (LDSR && !QD), "the wave balance: the one-lane LDS-resident form");
+    extern __shared__ __attribute__((aligned(16))) double lds_raw[];
+    // BAL: the sixteen progress words come FIRST, at an address known at compile time, and everything else moves up by their 64
+    // bytes (the launch adds them to the form's LDS size): behind the model their address would be one more value to keep
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_bal[];   // (the same bytes as lds_raw: every dynamic array starts there)
+    double *lds_d = lds_raw + (BAL ? kUctBalBytes / sizeof(double) : 0);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int A = AT > 0 ? AT : p.A, H = p.horizon, E = p.episodes;
     const int nthreads = p.waves * 64;
@@ -305,6 +334,25 @@ void uct_kernel(UctArgs p)
     if (CART && p.rep_shift >= 2)
         for (int i = tid; i < (H + 5) * 8; i += nthreads) cjump[i] = p.jump[i];
     const double *sctab = CART ? sctab_lds : nullptr;
+#ifdef MP_WAVE_STAMPS
+    // WAVE STAMPS (diagnostic build, -DMP_WAVE_STAMPS; tools/uct_wave_finish.py): lane 0 of every wave stores the 100 MHz
+    // constant clock at entry, after the staging barrier, after its last episode and at exit, and where it runs (HW_ID, XCC_ID),
+    // each with a plain vector store at once -- nothing is held in a register.  No stamp executes in the plain build.
+    const long stamp_wave = (long)blockIdx.x * p.waves + wave;
+    auto wave_stamp = [&](int k) {
+        if (p.wave_stamps && lane == 0) p.wave_stamps[stamp_wave * kWaveStampWords + k] = __builtin_amdgcn_s_memrealtime();
+    };
+    if (p.wave_stamps && lane == 0) {
+        unsigned hw, xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        p.wave_stamps[stamp_wave * kWaveStampWords + 4] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
+    }
+    wave_stamp(0);
+#define WAVE_STAMP(k) wave_stamp(k)
+#else
+#define WAVE_STAMP(k)
+#endif
     for (int i = tid; i < ntab; i += nthreads) lds_d[i] = p.tab[i];
     if (LDSR) {
         for (int i = tid; i < p.n_rdict; i += nthreads) lds_d[ntab2 + i] = p.rdict[i];
@@ -322,12 +370,31 @@ void uct_kernel(UctArgs p)
         for (int i = tid; i < n8; i += nthreads) dst[i] = src[i];
         for (int i = (n8 << 3) + tid; i < n; i += nthreads) t16[i] = p.t16[i];
     }
+    // WAVE BALANCE (profiles/uct_wave_balance.md; the rule: uct_balance.hpp).  The saturated form runs four waves per SIMD for the
+    // whole kernel, in one round, and with equal priorities the SIMD serves the oldest first: the oldest runs its rollouts near the
+    // speed of its dependency chain, the youngest gets what is left, and the last wave of every SIMD ends the kernel alone, at
+    // half a SIMD's issue rate with every gather exposed.  So each wave keeps a PROGRESS WORD at the start of the LDS -- its
+    // episode and the SIMD it runs on, kUctBalGone once it is done or if it has no root -- reads its workgroup's sixteen before each
+    // rollout, and runs the rollout at priority 1 if it has a mate on its SIMD and none of them is in an earlier episode, at 0
+    // otherwise: the waves that are ahead yield.  Nobody waits for anybody and no result depends on a word.  The word's slot is
+    // the wave's number in the launch modulo 16 (a workgroup's waves -- a power of two <= 16 of them -- take distinct slots), which
+    // the wave reads off its root index: no register is kept for it.  Here each wave initialises the slots congruent to its own
+    // modulo the waves per workgroup (every slot exactly once), before the barrier that publishes the model.
+    if constexpr (BAL) {
+        const int g0 = blockIdx.x * p.waves + wave;
+        const uint32_t mine = (long)g0 * p.lanes < p.n_roots ? uct_bal_word(0, simd_id()) : kUctBalGone;
+        if (lane < kUctBalWords && ((lane ^ g0) & (p.waves - 1)) == 0) bal_store(&lds_bal[lane], lane == (g0 & (kUctBalWords - 1)) ? mine : kUctBalGone);
+    }
     __syncthreads();
+    WAVE_STAMP(1);
     int32_t *path = path_all + wave * 64; // slot d of this lane: path[d * nthreads + lane]
     const int slot = QD ? lane >> 2 : (CART ? lane >> p.rep_shift : lane);   // which root of the wave (QD: four lanes per root, the first one owns it)
     const bool owner = QD ? (lane & 3) == 0 : true;
     const int r = (blockIdx.x * p.waves + wave) * p.lanes + slot;
-    if (slot >= p.lanes || r >= p.n_roots) return;   // (QD: whole quads leave together)
+#ifdef MP_WAVE_STAMPS
+    if (slot >= p.lanes || r >= p.n_roots) { WAVE_STAMP(2); WAVE_STAMP(3); }   // (lane 0 leaves only with its whole wave)
+#endif
+    if (slot >= p.lanes || r >= p.n_roots) return;   // (QD: whole quads leave together; BAL: a wave without roots wrote kUctBalGone above)
     static_assert(IL != 2 || AT > 0, "the group-interleaved layout needs |A| at compile time");
     const TreeRef<IL, AT> tree = tree_of<IL, AT>(p.tree, r, p.cap, A);
     // TREE STORES.  Layout 2 puts group g of a wave's 64 roots in ONE run of 64 x |A| nodes, and every slot of a new group gets the
@@ -731,7 +798,31 @@ void uct_kernel(UctArgs p)
                 for (int a = 0; a < AR; ++a) tree.sibling(grp, a) = n;
             }
         }
-        if constexpr (TREE_PRIO > 0) __builtin_amdgcn_s_setprio(0);
+        if constexpr (BAL) {
+            // WAVE BALANCE: publish this wave's episode, read the workgroup's words, pick the rollout's priority.  Lane 0 holds the
+            // wave's lowest root, so it is live in every wave that plans, and a wave's live lanes are its first ones: lane j reads word
+            // j mod 16.  A tail wave of fewer than sixteen lanes sees the words of its first waves only and may then take priority 1
+            // with a mate behind it: one wave of a launch at most, and the words decide nothing but a priority.
+            // The wave's own word is its episode counter and remembers its SIMD: the next episode is the word + 4, and neither `ep`
+            // nor the SIMD's number is asked for again.
+            // (64 roots per wave in this form: r >> 6 is the wave's number in the launch)
+            const uint32_t me = __builtin_amdgcn_readfirstlane((uint32_t)r >> 6) & (kUctBalWords - 1);
+            const uint32_t mine = __builtin_amdgcn_readfirstlane(bal_load(&lds_bal[me])) + 4u;
+            // (the lane's number, asked for here each time: as plain C++ it is loop-invariant, and the compiler keeps it and the mask
+            // of lane 0 in registers over the whole plan -- two scalar registers that the |A| = 5 kernel does not have)
+            uint32_t ln;
+            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+            const uint32_t j = ln & (kUctBalWords - 1);
+            if (ln == 0u) bal_store(&lds_bal[me], mine);
+            const uint32_t w = bal_load(&lds_bal[j]);
+            const bool other = j != me;
+            const uint32_t mates = (uint32_t)ballot64(other & uct_bal_mate(mine, w));
+            const uint32_t behind = (uint32_t)ballot64(other & uct_bal_behind(mine, w));
+            if ((mates != 0u) & (behind == 0u)) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
+        } else if constexpr (TREE_PRIO > 0) {
+            __builtin_amdgcn_s_setprio(0);
+        }
         PROF_T(c2);
         // ---- rollout, mcts.py:156-157 / 160-177.  Two steps per trip over two generator copies (ga, gb):
         // step "a" consumes the draw in `u`, advances gb = next(ga) speculatively while its lookup is in flight
@@ -1367,6 +1458,11 @@ void uct_kernel(UctArgs p)
         { const long long c4 = clock64(); t_sel += c1 - c0; t_expd += c2 - c1; t_roll += c3 - c2; t_bak += c4 - c3; }
 #endif
     }
+    if constexpr (BAL) {
+        // done planning: nobody's mate any more (what follows -- the root's write-back and the plan's read-out -- is short)
+        if ((((uint32_t)r) & 63u) == 0u) bal_store(&lds_bal[((uint32_t)r >> 6) & (kUctBalWords - 1)], kUctBalGone);
+    }
+    WAVE_STAMP(2);
     if constexpr (TREE_PRIO > 0) __builtin_amdgcn_s_setprio(0);
 #ifdef MP_PROFILE
     if (r == 0)
@@ -1426,6 +1522,8 @@ void uct_kernel(UctArgs p)
         if (p.root_child_count) p.root_child_count[(long)r * A + a] = rfc >= 0 ? max(tree.child(rfc, a).count, 0) : 0;
         if (p.root_child_value) p.root_child_value[(long)r * A + a] = rfc >= 0 ? tree.child(rfc, a).value : 0.0;
     }
+    WAVE_STAMP(3);
+#undef WAVE_STAMP
 }
 
 // ---- ONE ROOT PER WORKGROUP (round 5): the plan of a single agent's act(), and of every batch small enough to give each root
@@ -2444,6 +2542,8 @@ struct UctKnobs {
     int tree_stores;  // MP_UCT_TREE_STORES: 0 "lane" (the per-lane tree stores of uct_kernel, for A/B runs), 1 "group" (the wave's
                       // expansions and the leaf's single store, every zero group stored and loaded), 2 any other value or unset
                       // (virgin groups neither loaded nor, in fresh trees, stored)
+    int balance;      // MP_UCT_BALANCE: 0 runs the LDS-resident form without its wave balance (every rollout at priority 0, for A/B
+                      // runs and tests), any other value or unset with it
 };
 static int uct_knob(const char *name)
 {
@@ -2465,6 +2565,7 @@ static UctKnobs uct_knobs_read()
     k.cart_rep = uct_knob("MP_UCT_CART_REP"); k.cart_waves = uct_knob("MP_UCT_CART_WAVES");
     const char *tree_stores = getenv("MP_UCT_TREE_STORES");
     k.tree_stores = tree_stores && !strcmp(tree_stores, "lane") ? 0 : (tree_stores && !strcmp(tree_stores, "group") ? 1 : 2);
+    k.balance = uct_knob("MP_UCT_BALANCE") != 0;
     return k;
 }
 
@@ -2660,9 +2761,10 @@ static int uct_choose(const UctCall &c, const UctKnobs &k, UctChoice *out)
 template <typename Kernel>
 static int uct_go(Kernel kernel, const UctChoice &ch, const UctArgs &a, hipStream_t st)
 {
-    if (ch.lds > 64 * 1024)
-        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ch.lds));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n_roots + ch.roots_per_wg - 1) / ch.roots_per_wg)), dim3((unsigned)ch.threads), ch.lds,
+    const size_t lds = ch.lds + (a.balance ? (size_t)kUctBalBytes : 0);   // (the progress words of the wave balance, in front of the tables)
+    if (lds > 64 * 1024)
+        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n_roots + ch.roots_per_wg - 1) / ch.roots_per_wg)), dim3((unsigned)ch.threads), lds,
                        st, a);
     return MP_OK;
 }
@@ -2674,7 +2776,10 @@ static int uct_launch(const UctChoice &ch, bool listed, const UctArgs &a, hipStr
     const bool il2 = a.tree_il == 2;
     if constexpr (AT > 0) {
         switch (ch.form) {
-        case UF_LDSR: return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2>, ch, a, st);
+        case UF_LDSR:
+            if constexpr (uct_balance_form(AT))
+                if (a.balance) return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, true>, ch, a, st);
+            return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2>, ch, a, st);
         case UF_QUAD: return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, true>, ch, a, st);
         case UF_LONE: return uct_go(uct_lone_kernel<AT>, ch, a, st);
         case UF_LONE_MW: return uct_go(uct_lone_kernel<AT, false, true>, ch, a, st);
@@ -2837,6 +2942,9 @@ static int uct_form(mp_ctx *ctx, const UctPlan &c, bool cont, UctChoice *ch, Uct
     const UctKnobs knobs = uct_knobs_read();
     MP_TRY(uct_choose(call, knobs, ch));
     a->tree_stores = knobs.tree_stores;   // (how uct_kernel issues its tree stores: neither the form nor its name)
+    // the wave balance of the one-lane LDS-resident form: where the model leaves its 64 bytes, else the form runs unbalanced
+    a->balance = knobs.balance && ch->form == UF_LDSR && ch->lanes == 64 && ch->lds + kUctBalBytes <= kLdsBytes &&
+                 model->A >= 2 && model->A <= 8 && uct_balance_form(model->A) ? 1 : 0;
     a->lanes = ch->lanes; a->waves = ch->waves; a->rep_shift = ch->rep_shift;
     a->jump = nullptr;
     const UctForm form = ch->form;
@@ -2941,7 +3049,31 @@ static int uct_run_chunk(const WaveIo &io, const UctChoice &ch, bool listed, Uct
     if (c.path_spill) c.path_spill += r0;
     if (c.n_nodes_in) c.n_nodes_in += r0;
     c.n_nodes_out += r0;
+#ifdef MP_WAVE_STAMPS
+    // diagnostic build: MP_UCT_WAVE_STAMPS=<file> gets the stamps of the launch (overwritten per launch), read by tools/uct_wave_finish.py
+    const char *stamp_file = getenv("MP_UCT_WAVE_STAMPS");
+    const size_t stamp_words = (size_t)((c.n_roots + ch.roots_per_wg - 1) / ch.roots_per_wg) * (size_t)(ch.threads / 64) * kWaveStampWords;
+    c.wave_stamps = nullptr;
+    if (stamp_file) {
+        MP_HIP(hipMalloc(&c.wave_stamps, stamp_words * 8));
+        MP_HIP(hipMemsetAsync(c.wave_stamps, 0, stamp_words * 8, s));
+    }
+#endif
     MP_TRY(uct_dispatch(ch, listed, c, s));
+#ifdef MP_WAVE_STAMPS
+    if (stamp_file) {
+        std::vector<unsigned long long> h(stamp_words);
+        MP_HIP(hipStreamSynchronize(s));
+        MP_HIP(hipMemcpy(h.data(), c.wave_stamps, stamp_words * 8, hipMemcpyDeviceToHost));
+        MP_HIP(hipFree(c.wave_stamps));
+        if (FILE *f = fopen(stamp_file, "wb")) {
+            const unsigned long long head[2] = {(unsigned long long)(ch.threads / 64), (unsigned long long)kWaveStampWords};
+            fwrite(head, 8, 2, f);
+            fwrite(h.data(), 8, h.size(), f);
+            fclose(f);
+        }
+    }
+#endif
     for (int i = 0; i < io.n; ++i) {
         const WaveIo::Item &t = io.item[i];
         if ((t.dir & WaveIo::OUT) && t.mem == MP_MEM_HOST && t.host && t.per_root)
