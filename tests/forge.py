@@ -7,6 +7,10 @@ the step has an inverse; and for any wanted output ``o`` and any ``hi``, ``lo = 
 is ``o``.  Stepping that state back gives the record to hand to a planner.  Python integers only; tests/test_forge_host.py checks
 every function here against numpy itself.
 
+A generator that a planner seeds ON THE DEVICE from a draw of the record (a model clone) is reached the other way round: the
+record fixes the seed, ``clone_k53`` asks numpy for the clone's draw, and ``row_on`` builds the model row that this draw meets
+exactly on a cdf entry (tests/forged_clone_cases.py).
+
 A record is the project's six words: state hi, state lo, inc hi, inc lo, has_uint32, uinteger."""
 
 M64 = (1 << 64) - 1
@@ -169,6 +173,78 @@ class Stream(object):
             cdf /= cdf[-1]
             i = int(np.searchsorted(cdf, self.random(), side="right"))
         return i if np.ndim(a) == 0 else a[i]
+
+
+class LoggingStream(Stream):
+    """A Stream that logs every draw a planner restatement makes: ``log`` holds (kind, words, outputs, arg, rejections) -- where in
+    the stream the draw begins: ``words`` 32-bit draws were made before it (a 64-bit output counts as two; a half the record
+    entered with is draw 0) and ``outputs`` 64-bit outputs; ``arg`` is the ``k`` of a bounded draw ("below") or the ``p`` of a
+    weighted choice ("choice"); ``rejections``: the words the bounded draw threw away."""
+
+    def __init__(self, rec, next64=None):
+        Stream.__init__(self, rec, next64)
+        self.log, self._entry = [], self.has_uint32
+
+    def words(self):
+        return 2 * self.outputs + self._entry - self.has_uint32
+
+    def below(self, k):
+        at, before = (self.words(), self.outputs), self.rejections
+        value = Stream.below(self, k)
+        if k > 1:
+            self.log.append(("below",) + at + (int(k), self.rejections - before))
+        return value
+
+    def choice(self, a, p=None):
+        if p is None:
+            return Stream.choice(self, a)
+        import numpy as np
+        self.log.append(("choice", self.words(), self.outputs, np.array(p, dtype=np.float64), 0))
+        return Stream.choice(self, a, p)
+
+
+# ---- the generator of a clone that a planner seeds on the device, and model rows forged to its draws ----------------------------
+TWO53 = 1 << 53
+
+
+def clone_k53(x, n=0):
+    """The 53-bit integer of the n-th ``random()`` (from 0) of ``Generator(PCG64(SeedSequence(x)))``: what a clone seeded with the
+    planner's draw ``x`` draws at its (n + 1)-th model step.  numpy's own, exact: random() is k53 * 2^-53."""
+    import numpy as np
+    u = float(np.random.Generator(np.random.PCG64(np.random.SeedSequence(int(x)))).random(n + 1)[n])
+    k53 = int(u * float(TWO53))
+    assert k53 * 2.0 ** -53 == u
+    return k53
+
+
+def row_on(k53, W, b, zeros=()):
+    """A float64 row of ``W`` probabilities n_j * 2^-53 with integer n_j >= 0, sum n_j = 2^53 and n_0 + .. + n_b = ``k53``: every
+    partial sum is exact, cdf[-1] == 1.0 and cdf[b] == k53 * 2^-53.  ``zeros``: indices that get n_j = 0 (not ``b``; a zero at
+    b + 1 makes cdf[b + 1] == cdf[b]).  A draw of k53 * 2^-53 sits ON cdf[b]: searchsorted 'right' passes it (and the zeros
+    behind it), 'left' stops at b.  The twin row_on(k53 + 1, ...) has the same draw one step below cdf[b]: both stop at b."""
+    import numpy as np
+    zeros = set(int(z) for z in zeros)
+    assert 0 <= b <= W - 2 and b not in zeros and all(0 <= z < W for z in zeros)
+    head = [j for j in range(b + 1) if j not in zeros]
+    tail = [j for j in range(b + 1, W) if j not in zeros]
+    assert tail and len(head) <= k53 and len(tail) <= TWO53 - k53, (k53, W, b)
+    n = [0] * W
+    for idx, total in ((head, k53), (tail, TWO53 - k53)):
+        for j in idx:
+            n[j] = total // len(idx)
+        n[idx[-1]] += total - (total // len(idx)) * len(idx)       # (head: the remainder goes to b itself)
+    assert sum(n) == TWO53 and sum(n[:b + 1]) == k53 and n[b] >= 1
+    row = np.array([float(x) for x in n], dtype=np.float64) * 2.0 ** -53
+    assert [int(x * float(TWO53)) for x in row] == n
+    return row
+
+
+def passed(row, b):
+    """The index numpy answers for a draw ON cdf[b] of ``row``: b + 1, and past every zero entry that follows."""
+    j = b + 1
+    while row[j] == 0.0:
+        j += 1
+    return j
 
 
 def threshold53(c):

@@ -6,7 +6,12 @@ on and just below a cdf threshold -- and is then pinned to: numpy's ``Generator`
 the C oracle's ``pcg64_replay`` / ``pchoice_replay``, the host restatements of the device's generator step (the scalar form of
 tests/test_host_logic.py and the 32-bit column form restated below, jump-ahead constants included), and the planner
 restatements tests/{olop,brue,gbopd}_restatement.py through the generators they take.  tests/test_gpu_forged_draws.py hands
-the same records to the kernels."""
+the same records to the kernels.
+
+The last section does the same for the cases of tests/forged_clone_cases.py -- model rows forged to the draws of a clone that a
+planner seeds on the device, and later draws of a plan reached with ``skip`` -- which tests/test_gpu_forged_clone_draws.py
+hands to BRUE, stochastic OLOP and Sparse Sampling: every twin pair tells searchsorted 'right' from 'left' on numpy itself, and
+every restatement is pinned on the draw it meets the forged value with."""
 import numpy as np
 import pytest
 
@@ -15,7 +20,10 @@ from rl_agents_amd import native
 from tests import brue_restatement as brr
 from tests import forge
 from tests import gbopd_restatement as gbr
+from tests import forged_clone_cases as fc
 from tests import olop_restatement as olr
+from tests import olop_stoch_restatement as osr
+from tests import sparse_sampling_restatement as ssr
 from tests.helpers import CDF_ROWS as ROWS
 from tests.helpers import generator_from, scalar_output, scalar_step, stochastic_model, zero_table
 
@@ -373,3 +381,229 @@ def test_oracle_stochastic_uct_meets_the_forged_tie_after_the_first_rollout(kind
     for _ in range(horizon - 1):
         pred.random()
     assert after_episodes(2) == pred.record()
+
+
+# ---- models forged to a clone's draw (tests/forged_clone_cases.py) ---------------------------------------------------------------
+TWIN_SETS = [("stochastic", fc.DENSE_W, "word", 0), ("stochastic", fc.DENSE_W, "word", 1), ("stochastic", fc.DENSE_W, "zeros", 0)] + \
+            [("sparse", B, first, 0) for B in (1, 3, 4, 5) for first in ("word", "zeros")] + [("sparse", 4, "word", 1)]
+N_ACTIONS = 3
+
+
+def clone_of(x):
+    return np.random.Generator(np.random.PCG64(np.random.SeedSequence(int(x))))
+
+
+def test_clone_k53_is_numpys_own_draw():
+    for x in (0, 1, 2 ** 30 - 1, 123456789, 0x9E3779B9 >> 2):
+        u = clone_of(x).random(3)
+        raw = np.random.PCG64(np.random.SeedSequence(x)).random_raw(3)
+        for n in range(3):
+            k = forge.clone_k53(x, n)
+            assert k * 2.0 ** -53 == u[n] and k == int(raw[n]) >> 11
+
+
+def assert_twin_on_numpy(x, n, row, b, twin, want):
+    """The forged row on numpy itself: exact cumsum, choice() of the clone's n-th draw, and 'left' against 'right'."""
+    W = len(row)
+    ints = [int(v * 2.0 ** 53) for v in row]
+    assert all(v >= 0 for v in ints) and sum(ints) == forge.TWO53
+    cdf = row.cumsum()
+    assert cdf[-1] == 1.0 and [int(c * 2.0 ** 53) for c in cdf] == list(np.cumsum(np.array(ints, dtype=object)))
+    k53 = forge.clone_k53(x, n)
+    assert sum(ints[:b + 1]) == k53 + twin
+    gen = clone_of(x)
+    gen.random(n)
+    assert int(gen.choice(W, p=row)) == want == (b if twin else forge.passed(row, b))
+    u = k53 * 2.0 ** -53
+    right, left = int(np.searchsorted(cdf, u, "right")), int(np.searchsorted(cdf, u, "left"))
+    assert right == want and left == b
+    assert (left != right) == (twin == 0)          # the pair tells `<` from `<=`: only the twin ON the threshold moves
+    # the form the kernels search in: integer thresholds ceil(cdf * 2^53) <= k
+    assert sum(forge.threshold53(c) <= k53 for c in cdf) == want
+    assert sum(forge.threshold53(c) < k53 for c in cdf) == b
+
+
+@pytest.mark.parametrize("kind,W,first,step", TWIN_SETS)
+def test_clone_twins_on_numpy(kind, W, first, step):
+    batch = fc.clone_twins(kind, W, N_ACTIONS, first=first, step=step)
+    seen = set()
+    for c in batch["cases"]:
+        if c["b"] is None:
+            continue
+        assert np.array_equal(batch["cfg"]["transition"][c["state"], c["action"]], c["row"])
+        assert_twin_on_numpy(c["x"], step, c["row"], c["b"], c["twin"], c["want"])
+        seen.add((c["x"], c["b"], c["twin"]))
+    bs = fc.DENSE_BS if kind == "stochastic" else fc.SPARSE_BS[W]
+    assert seen == {(w >> 2, b, t) for w in fc.SEED_WORDS for b in bs for t in (0, 1)}
+    assert {w >> 2 for w in fc.SEED_WORDS} >= {0, 1, 2 ** 30 - 1}
+    if len(bs) > 1:
+        assert any((c["row"] == 0).any() for c in batch["cases"])         # rows with equal adjacent thresholds
+
+
+def next_state(cfg, s, a, idx):
+    return int(idx) if cfg["mode"] == "stochastic" else int(cfg["next"][s, a, idx])
+
+
+@pytest.mark.parametrize("kind,W,first,step", [t for t in TWIN_SETS if t[2] == "word"])
+def test_brue_restatement_meets_the_forged_rows(kind, W, first, step):
+    """The rollout's seed is the record's first word, its first action the second, and the clone's draw number ``step`` meets
+    the forged row: the tree's first (second) outcome node is the state numpy's choice gives."""
+    batch = fc.clone_twins(kind, W, N_ACTIONS, first=first, step=step)
+    cfg = batch["cfg"]
+    for c in batch["cases"]:
+        i = c["root"]
+        st = forge.LoggingStream(batch["records"][i])
+        res = brr.brue_plan(cfg["mode"], cfg["transition"], cfg["reward"], np.zeros(len(cfg["reward"]), bool), i, 12, 3, 0.9, st,
+                            nxt=cfg["next"])
+        assert st.log[0][:4] == ("below", 0, 0, 1 << 30) and st.log[1][:4] == ("below", 1, 1, N_ACTIONS)
+        assert st.log[0][4] == st.log[1][4] == 0
+        assert forge.Stream(batch["records"][i]).below(1 << 30) == c["x"]
+        if c["b"] is None:
+            continue
+        # creation order: chance node 1, outcome 2 (step 0); chance node 3, outcome 4 (step 1)
+        node = 2 + 2 * step
+        assert res["key"][node - 1] == c["action"] and res["key"][node] == next_state(cfg, c["state"], c["action"], c["want"])
+        assert res["key"][node] != next_state(cfg, c["state"], c["action"], c["b"]) or c["twin"] == 1
+        if step == 1:
+            assert res["key"][2] == c["state"]
+
+
+@pytest.mark.parametrize("kind,W,first,step", [t for t in TWIN_SETS if t[3] == 0])
+def test_olop_stoch_restatement_meets_the_forged_rows(kind, W, first, step):
+    """One episode of two steps: the seed is the record's first word, the uniform continuation the second ("zeros": none), and the
+    second step's reward is that of the state the forged row gives -- the tree holds no states, the rewards tell."""
+    batch = fc.clone_twins(kind, W, N_ACTIONS, first=first, step=0)
+    cfg = batch["cfg"]
+    thr = olr.thresholds("4*np.log(time)", "global", 1)
+    for c in batch["cases"]:
+        i = c["root"]
+        st = forge.LoggingStream(batch["records"][i])
+        res = osr.olop_stoch_plan(cfg["mode"], cfg["transition"], cfg["reward"], None, i, 1, 2, 0.8, True, thr,
+                                  "uniform" if first == "word" else "zeros", st, next_states=cfg["next"])
+        assert res["error"] is None and st.log[0][:4] == ("below", 0, 0, 1 << 30)
+        if first == "word":
+            assert st.log[1][:4] == ("below", 1, 1, N_ACTIONS) and st.log[1][4] == 0
+        else:
+            assert len(st.log) == 1
+        path = [n for n in range(len(res["count"])) if res["count"][n] == 1]
+        assert len(path) == 2 and res["action"][path[0]] == c["action"] and res["depth"][path[1]] == 2
+        if c["b"] is None:
+            continue
+        a2 = int(res["action"][path[1]])
+        assert res["cum"][path[1]] == cfg["reward"][next_state(cfg, i, c["action"], c["want"]), a2]
+        if c["twin"] == 0:
+            assert res["cum"][path[1]] != cfg["reward"][next_state(cfg, i, c["action"], c["b"]), a2]
+
+
+@pytest.mark.parametrize("k", fc.TIE_KS)
+def test_olop_stoch_restatement_meets_the_forged_rejections(k):
+    """On a one-hot model the restatement draws what olop_restatement draws on the table: seed word, then the tie (lead = 1)."""
+    n_actions = 8 if k < 8 else k
+    cfg, (t, r, term), avail = fc.one_hot_tie_model(12, n_actions, k)
+    thr = olr.thresholds("4*np.log(time)", "global", 4)
+    for case in [c for c in CASES if c != "reject3"]:
+        rec, expect = forge.tie_case_record(case, k, lead=1)
+        st = forge.LoggingStream(rec)
+        a = osr.olop_stoch_plan("stochastic", cfg["transition"], cfg["reward"], None, 0, 4, 3, 0.8, True, thr, "uniform", st,
+                                available=avail)
+        b = olr.olop_plan(t, r, term, 0, 4, 3, 0.8, True, thr, "uniform", forge.Stream(rec), available=avail)
+        assert st.log[1][:2] == ("below", 1) and st.log[1][3:] == (k, expect), case
+        for key in ("plan", "parent", "action", "count", "cum", "mu", "vu"):
+            assert np.array_equal(a[key], b[key]), (case, key)
+
+
+# ---- Sparse Sampling: the clone of one sample, and the root's tie -----------------------------------------------------------------
+SS_SETS = [("stochastic", 150, 1), ("sparse", 2, 1), ("sparse", 3, 1), ("stochastic", 2, 1), ("stochastic", 3, 1), ("sparse", 3, 2)]
+
+
+def ss_counts(cfg, s0, horizon, rec, action):
+    """Outcome counts {state: count} of the root's chance node of ``action``, and the stream after the plan."""
+    st = forge.LoggingStream(rec)
+    res = ssr.ss_plan(cfg["mode"], cfg["transition"], cfg["reward"], s0, horizon, fc.SS_C, 0.9, st, nxt=cfg["next"])
+    chance = [n for n in range(len(res["parent"])) if res["parent"][n] == 0 and res["key"][n] == action]
+    assert len(chance) == 1
+    kids = [n for n in range(len(res["parent"])) if res["parent"][n] == chance[0]]
+    return {int(res["key"][n]): int(res["count"][n]) for n in kids}, st
+
+
+@pytest.mark.parametrize("kind,W,horizon", SS_SETS)
+def test_sparse_sampling_twins_on_numpy_and_the_sample_that_meets_them(kind, W, horizon):
+    """Every case: the target sample's word is the forged one, its clone's draw sits on / below cdf[b] of the row, and in the
+    restatement exactly that ONE sample changes sides when the row is swapped for its twin."""
+    batches = fc.ss_batches(kind, W, horizon)
+    assert sum(len(b["cases"]) for b in batches) == len(fc.ss_cases(W, horizon))
+    swapped = 0
+    for batch in batches:
+        cfg = batch["cfg"]
+        for c in batch["cases"]:
+            rec = batch["records"][c["root"]]
+            words = ssr.half_words(rec, c["t"] + 1)
+            assert words[c["t"]] >> 2 == c["x"] and words[c["t"]] in fc.SS_WORDS and bool(rec[4]) == c["buffered"]
+            assert np.array_equal(cfg["transition"][c["root"], c["action"]], c["row"])
+            assert_twin_on_numpy(c["x"], 0, c["row"], c["b"], c["twin"], c["want"])
+            if c["twin"] or (kind == "stochastic" and W < 150) or (c["b"] not in (0, W - 2) and c["t"] not in (0, 64)):
+                continue                  # (the swap below: every on-twin of the small rows once, the wide rows' edges)
+            got, st = ss_counts(cfg, c["root"], horizon, rec, c["action"])
+            assert [e[:4] for e in st.log[:c["t"] + 1]] == [("below", j, (j + 1 - int(c["buffered"])) // 2, 1 << 30) for j in range(c["t"] + 1)]
+            other = dict(cfg, transition=cfg["transition"].copy())
+            other["transition"][c["root"], c["action"]] = forge.row_on(forge.clone_k53(c["x"]) + 1, W, c["b"],
+                                                                        [j for j in range(W) if c["row"][j] == 0])
+            base, _ = ss_counts(other, c["root"], horizon, rec, c["action"])
+            hit, miss = next_state(cfg, c["root"], c["action"], c["want"]), next_state(cfg, c["root"], c["action"], c["b"])
+            moved = dict(base)
+            moved[miss] = moved.get(miss, 0) - 1
+            moved[hit] = moved.get(hit, 0) + 1
+            assert {s: n for s, n in moved.items() if n} == got, (c["t"], c["b"])
+            swapped += 1
+    assert swapped >= 8 or (kind == "stochastic" and W < 150)
+
+
+@pytest.mark.parametrize("k", fc.TIE_KS)
+def test_sparse_sampling_restatement_meets_the_forged_root_tie(k):
+    """Horizon 1 on a zero-reward table: the samples consume k * C words whatever they are, then the root ties among its k
+    listed actions -- the LAST draw of the plan, where the record's forged words sit."""
+    from tests.helpers import zero_table
+    n_actions = 8 if k < 8 else k
+    t, r, _, avail = zero_table(12, n_actions, k)
+    n_words = k * fc.SS_TIE_C
+    recs, names, expect = fc.ss_tie_batch(k, 2 * len(fc.SS_TIE_CASES), n_words)
+    assert set(names) == set(forge.TIE_CASES) - {"reject3"}
+    for rec, name, e in zip(recs, names, expect):
+        st = forge.LoggingStream(rec)
+        res = ssr.ss_plan("deterministic", t, r, 0, 1, fc.SS_TIE_C, 0.9, st, available=avail if k < n_actions else None)
+        assert res["samples"] == n_words and len(st.log) == n_words + 1
+        assert st.log[-1][0] == "below" and st.log[-1][1] == n_words and st.log[-1][3] == k, name
+        if e is not None:
+            assert st.log[-1][4] == e, (name, k)
+        if name == "buffered_plain" and n_words % 2 == 0:
+            assert st.log[-1][2] == st.outputs                       # the tie's word came from the buffered half: no new output
+    if k & (k - 1):
+        assert max(e for e in expect if e is not None) == 2
+
+
+# ---- BRUE's estimate() choice on an exact boundary --------------------------------------------------------------------------------
+def test_brue_estimate_choice_is_the_sixth_output_over_counts_one_one():
+    cfg = fc.estimate_chain()
+    recs, ks = fc.estimate_records()
+    values = []
+    for rec, k53 in zip(recs, ks):
+        st = forge.LoggingStream(rec)
+        res = brr.brue_plan("stochastic", cfg["transition"], cfg["reward"], np.zeros(6, bool), 0, fc.EST["budget"], fc.EST["horizon"],
+                            fc.EST["gamma"], st)
+        choices = [e for e in st.log if e[0] == "choice"]
+        assert len(choices) == 6 and st.outputs == 7 and res["env_steps"] == 6
+        target = choices[4]
+        assert target[2] == fc.EST["skip"] and target[3].tolist() == [0.5, 0.5]      # counts (1, 1) / 2
+        assert sorted(fc.estimate_sides(rec)) == [2, 3]
+        replay = forge.Stream(rec)
+        replay.below(1 << 30)
+        for _ in range(3):
+            replay.random()
+        replay.below(1 << 30)
+        replay.random()
+        assert replay.random() == k53 * 2.0 ** -53
+        assert int(np.searchsorted([0.5, 1.0], k53 * 2.0 ** -53, "right")) == (1 if k53 == 1 << 52 else 0)
+        assert int(np.searchsorted([0.5, 1.0], k53 * 2.0 ** -53, "left")) == 0
+        values.append(float(res["stat"][1]))
+    for on, below in zip(values[0::2], values[1::2]):
+        assert on != below              # the root's chance value holds R(3) = 0.75 or R(2) = 0.25 of the chosen outcome

@@ -33,6 +33,11 @@ middle); a masked table where k < |A|.
                                                                                                           the episode's seed word)
   BRUE (the rollout's integers(|A|))                                                3, 6, 7, 70, 150      first action draw (same)
   GBOP-D                                                                            3, 6, 7, 70, 150      the sampling rule's first tie
+  in tests/test_gpu_forged_clone_draws.py:
+  stochastic OLOP olop_stoch_dense (one-hot rows, uniform continuation)             3, 6, 7, 70, 150      first continuation draw (after
+                                                                                                          the episode's seed word)
+  Sparse Sampling ss_wave_lds; one model per root ss_each_lds / ss_each_global      3, 6, 7, 70, 150      the root's tie, the plan's LAST
+                                                                                    / 3, 6, 7             draw (after k * C sample words)
 
 The form is asserted by name in every test: mp_uct_plan_stochastic runs uct_stoch_r0 (dense rows), r4 (sparse rows of 3 and 4),
 r1 / r2 (sparse rows of 2: compact records / kept at 32 bytes) with 16-bit path entries; these small batches run olop_global,
@@ -51,10 +56,19 @@ shipped 32 coarse bits, packed 16-byte ones with 10; listed and ordered policies
 root's exact row, coarsened in the kernel -- AND as the second, decided by the thresholds stored in the record the walk
 fetched; there also t + 1 and both ends of the range that shares the threshold's coarse bits.
 
-OUT OF REACH (no caller-passed record reaches them): BRUE's per-rollout env clone, re-seeded on the device from the drawn
-seed (seed_sequence.hpp) -- its model-row draws on stochastic models; OLOP's and UCT's env seed draws are powers of two (2^30)
-and cannot reject; BRUE's estimate() draw (choice(p=counts)) and its final root tie, and every later tie of a plan, follow
-draws whose count depends on the plan and are met only with unforged words."""
+REACHED BY FORGING THE MODEL (tests/test_gpu_forged_clone_draws.py; no caller-passed record holds these draws, but the record
+fixes the seed x of the clone a planner seeds on the device (seed_sequence.hpp), numpy gives the clone's draws, and the model
+row they meet is built so that the draw sits on, or one step below, a cdf entry): the model-row draws of BRUE's per-rollout
+clone (ballot search, dense rows of 150 and sparse rows of 1, 3, 4, 5; first and second step), of olop_stoch_kernel's per-episode
+clone (the same search, continuation "zeros" and "uniform") and of one chosen sample of Sparse Sampling's root (binary search
+on the sample's own lane, the jump to its half-word with and without a half buffered on entry; both frame forms).  Reached
+with ``skip``, where the number of outputs before the draw does not depend on their values: Sparse Sampling's root tie (table
+above) and BRUE's estimate() draw, choice(p=counts / counts.sum()), at u == cdf[0] over counts (1, 1) on a one-action chain.
+
+OUT OF REACH: OLOP's, BRUE's, Sparse Sampling's and UCT's env seed draws are powers of two (2^30) and cannot reject; BRUE's final
+root tie, and every later tie of a plan whose draw count depends on the drawn values (a rollout that may end early, a tree
+whose shape the draws decide), are met only with unforged words; BRUE's estimate() choice over more than 64 outcomes (the
+chunk logic of the kernel's weighted choice) meets an exact cdf entry in no plan a test can construct."""
 import numpy as np
 import pytest
 
