@@ -33,6 +33,7 @@ extern "C" {
 #define MP_OK 0
 #define MP_ERR_HIP (-1)          /* a HIP runtime call failed (message has the hipError string)  */
 #define MP_ERR_REWARD_RANGE (-2) /* OPD: reward outside [0,1] (deterministic.py:46-47 ValueError) */
+#define MP_ERR_GAPE_NO_CHALLENGER (-9) /* MDP-GapE status: the root lists one action (mdp_gape.py:247, max() of an empty list: ValueError) */
 #define MP_ERR_ALLOC (-3)
 #define MP_ERR_ARG (-4)          /* invalid argument / unsupported configuration                  */
 #define MP_ERR_MODE (-5)         /* model kind not valid for this call ("Unknown mode")           */
@@ -601,10 +602,54 @@ const char *mp_olop_stoch_form_names(void);
  *     clamp (utils.py:195), 2 = the in-loop lower clamp (:193), 4 = the finite difference that replaces the derivative after a
  *     ZeroDivisionError (:188), 8 / 16 = the final lower / upper clamp (:198-201);
  *   what 1: out[i] = bernoulli_kullback_leibler(p = x[i], q = y[i]) (utils.py:89-107);
- *   what 2: out[i] = log(x[i]), the device's.
- * count, iterations and decisions are read and written with what 0 only; y with what 0 and 1. */
+ *   what 2: out[i] = log(x[i]), the device's;
+ *   what 3: kl_upper_bound(..., lower=True) (utils.py:136-147, MDP-GapE's mu_lcb): inputs and outputs as what 0.
+ * count, iterations and decisions are read and written with what 0 and 3 only; y with what 0, 1 and 3. */
 int mp_selftest_olop_bound(mp_ctx *ctx, int32_t what, int32_t n, const double *x, const double *y, const int32_t *count,
                            double *out, int32_t *iterations, int32_t *decisions);
+
+/* ---------------------------------------------------------------- MDP-GapE ------------------ */
+/*
+ * MDPGapE.plan (tree_search/mdp_gape.py:94-110) for n_roots independent roots of a deterministic table model, with
+ * max_next_states_count 1: episodes of MDPGapE.run (:60-92) until challenger.value_upper - best.value_lower < accuracy or
+ * episodes + 2 of them have run.  An episode: one generator draw (randint(2**30), :67); the root expanded if childless; exactly
+ * `horizon` steps -- at the root the arm best_arm_identification_selection picks (:228-249), at an inner node with children
+ * random_argmax over the chance children's value_upper (exact ties, a draw only for two or more), at a childless node
+ * randint(n_actions_env) over ALL environment actions or action 0, an unlisted action giving way to the first listed one
+ * (:155-160); ChanceNode.update, OLOPNode.update (olop.py:132-142: reward range, done sticky per node); then mu_ucb and mu_lcb
+ * (kl_upper_bound, lower=False / True) of the path's decision nodes and backup_to_root (:214-226, :288-305; with one next state a
+ * chance node's values are mu + gamma * value of its decision child).  get_plan: the best arm's action.
+ *   continuation: 1 = "uniform", 0 = action 0 of the environment.
+ *   action_column int32 [n_actions_env]: the model column of each environment action, -1 for none (NULL: the identity, and
+ *     n_actions_env must equal |A|): the model's columns are in the environment's listing order.
+ *   thr_by_count double [episodes + 2]: the bound's threshold for a node of count c at [c - 1] (eval of the config string);
+ *   value_init double [horizon + 1]: (1 - gamma ** (horizon - depth)) / (1 - gamma).  Host pointers, evaluated in Python.
+ *   rng_state [n_roots][6], advanced; plans int32 [n_roots, max_plan_len] (one action, -1 padded), plan_len, episodes_run,
+ *   env_steps (= episodes_run * horizon without an error), status (MP_OK / MP_ERR_REWARD_RANGE / MP_ERR_GAPE_NO_CHALLENGER, or
+ *   MP_ERR_ARG where a bound below the root came out NaN and random_argmax's tie set is empty: np_random.choice raises),
+ *   child_lower / child_upper double and child_count int64 [n_roots, |A|]: the root's chance children by column (count -1
+ *   where the root lists no such action), best_challenger int32 [n_roots, 2]: the actions of the two arms of the last episode.
+ * MP_ERR_MODE for a dense, sparse, joint, batch or row-block model; MP_ERR_ARG, with the reason, for a gamma, accuracy,
+ * threshold or initial value that is not finite (the reference plans on the NaN bounds they make) and when the node bound
+ * 1 + (episodes + 2) * horizon * |A| does not fit a 32-bit index or 1 GiB.  mp_last_kernel_variant records one of
+ * mp_gape_form_names: "gape_global\ngape_global_slots" (part of no other list).
+ */
+int mp_gape_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
+                 double gamma, double accuracy, int32_t continuation, int32_t n_actions_env, const int32_t *action_column,
+                 const double *thr_by_count, const double *value_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans,
+                 int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps, int32_t *status, double *child_lower,
+                 double *child_upper, int64_t *child_count, int32_t *best_challenger, int32_t mem);
+const char *mp_gape_form_names(void);
+/* Tree of root `root` after the last mp_gape_plan, decision and chance nodes in the reference's creation order: per node its
+ * kind (0 decision, 1 chance), parent (-1 at the root), action (a chance node's action column; a decision node's observed
+ * state), depth (a chance node has its parent's), count, and cumulative_reward, mu_ucb, mu_lcb, done (0 for chance nodes, which
+ * hold none), value_upper, value_lower, state.  Host arrays of capacity `cap` (at most 2 * (1 + (episodes + 2) * horizon * |A|)
+ * nodes; *n_nodes is set also when `cap` is too small).  When a batch's trees do not all fit the workspace only root 0's is
+ * kept (MP_ERR_ARG for the others).  The tree of a root whose status is not MP_OK is what the plan had built when it stopped,
+ * not the reference's state at its raise (the failing step's counts and decision child are not booked). */
+int mp_gape_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, uint8_t *kind, int32_t *parent, int32_t *action,
+                        int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *mu_lcb,
+                        double *value_upper, double *value_lower, uint8_t *done, int32_t *state);
 
 /* ---------------------------------------------------------------- BRUE ---------------------- */
 /*

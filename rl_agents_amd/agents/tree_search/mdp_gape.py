@@ -1,0 +1,281 @@
+"""MDP-GapE, best-arm identification MCTS, on the MI355X planning core (reference
+``rl_agents/agents/tree_search/mdp_gape.py``); the episodes run in ``mp_gape_plan`` (rl_agents_amd/csrc/gape.hip).
+
+Same class names, config keys and results as the reference on deterministic finite-MDP tables with
+``max_next_states_count: 1`` (``HighwayEnv/agents/MDPGapEAgent/baseline.json``).  The host computes the budget split, the
+initial values by depth (Python ``**``) and the bound's threshold by count (``eval`` of the config string) -- every constant
+that is not a basic IEEE operation.  The device computes both KL bounds' Newton iterations with its own ``log``: bounds and
+values agree with the reference within 1e-12 / (1 - gamma), and every discrete output -- the plan, the episodes run, the
+tree's shape and counts, the generator record -- is identical wherever the reference's comparisons do not hang on the last
+bits of a bound.
+
+Refused: ``stochastic`` / ``sparse`` models (TypeError) and ``max_next_states_count != 1`` (NotImplementedError) -- the
+transition bounds of the reference (``max_expectation_under_constraint``) go through numpy's vectorised ``exp`` / ``log`` and
+BLAS, which no restatement can be held to; ``step_strategy: "subtree"`` (NotImplementedError at ``reset``); a bound type other
+than ``"kullback-leibler"`` (ValueError: the reference only logs an error and plans on infinite bounds).
+"""
+import logging
+
+import numpy as np
+
+from rl_agents_amd import device_model, native
+from rl_agents_amd.agents.tree_search.abstract import Node
+from rl_agents_amd.agents.tree_search.olop import OLOP, OLOPAgent
+
+logger = logging.getLogger(__name__)
+
+
+class MDPGapE(OLOP):
+    """MDP-GapE planner (mdp_gape.py:11-131) for one or many roots of one deterministic finite MDP."""
+
+    # PerEpisodeEvaluation has no kind that plans MDP-GapE on one model per episode; it must refuse this subclass of OLOP,
+    # not run OLOP in its place
+    per_episode_entry_point = None
+
+    def __init__(self, env, config=None):
+        super(MDPGapE, self).__init__(env, config)
+        self.next_observation = None
+        self.budget_used = 0
+
+    @classmethod
+    def default_config(cls):
+        cfg = super(MDPGapE, cls).default_config()
+        cfg.update({
+            "accuracy": 1.0,
+            "confidence": 0.9,
+            "continuation_type": "uniform",
+            "horizon_from_accuracy": False,
+            "max_next_states_count": 1,
+            "upper_bound": {
+                "type": "kullback-leibler",
+                "time": "global",
+                "threshold": "3*np.log(1 + np.log(count))"
+                             "+ horizon*np.log(actions)"
+                             "+ np.log(1/(1-confidence))",
+                "transition_threshold": "0.1*np.log(time)"
+            },
+        })
+        return cfg
+
+    def reset(self):
+        """mdp_gape.py:42-45.  The reference builds its root here, so what that raises is raised here: a non-mapping
+        ``upper_bound`` (TypeError), ``gamma == 1`` (ZeroDivisionError in the root's initial value)."""
+        super(OLOP, self).reset()
+        if self.config["step_strategy"] == "subtree":
+            raise NotImplementedError("step_strategy 'subtree' is not available for MDP-GapE: the kept subtree's bounds "
+                                      "stay on the device of the previous plan only until the next one overwrites them")
+        if "horizon" not in self.config:
+            self.allocate_budget()
+        self.config["upper_bound"]["type"]              # mdp_gape.py:142 reads it
+        self._value_init = self.value_init(self.config["gamma"], self.config["horizon"])
+
+    def allocate_budget(self):
+        """mdp_gape.py:47-58."""
+        if self.config["horizon_from_accuracy"]:
+            self.config["horizon"] = int(np.ceil(np.log(self.config["accuracy"] * (1 - self.config["gamma"]) / 2)
+                                                 / np.log(self.config["gamma"])))
+            self.config["episodes"] = self.config["budget"] // self.config["horizon"]
+            assert self.config["episodes"] > 1
+            logger.debug("Planning at depth H={}".format(self.config["horizon"]))
+        else:
+            super(MDPGapE, self).allocate_budget()
+
+    @staticmethod
+    def value_init(gamma, horizon):
+        """A new node's value_upper by depth 0..horizon (mdp_gape.py:147, :258), in Python arithmetic."""
+        out = np.empty(int(horizon) + 1, np.float64)
+        for depth in range(int(horizon) + 1):
+            out[depth] = (1 - gamma ** (horizon - depth)) / (1 - gamma)
+        return out
+
+    def thresholds(self):
+        """The bound's threshold by the count of a node, 1 .. episodes + 2 (mdp_gape.py:200-208): the config string evaluated
+        with the reference's variable names.  What the ``eval`` raises is raised as it is."""
+        bound = self.config["upper_bound"]
+        names = dict(horizon=self.config["horizon"], actions=self.env.action_space.n, confidence=self.config["confidence"],
+                     time=self.config["episodes"])
+        counts = int(self.config["episodes"]) + 2
+        out = np.zeros(counts, np.float64)
+        for count in range(1, counts + 1):
+            out[count - 1] = float(eval(bound["threshold"], {"np": np}, dict(names, count=count)))
+        return out
+
+    def supports_device_loop(self):
+        return False
+
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
+        """``root_steps`` is accepted for the common interface: the step limit ends no episode (done = terminated)."""
+        cfg = self.config
+        episodes, horizon = int(cfg["episodes"]), int(cfg["horizon"])
+        if cfg["max_next_states_count"] != 1:
+            raise NotImplementedError("max_next_states_count != 1: the unassigned placeholder children of a chance node put "
+                                      "mass on unseen states through max_expectation_under_constraint, numpy's exp / log of "
+                                      "arrays and BLAS products, which the device cannot be held to")
+        if cfg["upper_bound"]["type"] != "kullback-leibler":
+            raise ValueError("MDP-GapE needs the 'kullback-leibler' bound: with '{}' the reference only logs an error and "
+                             "plans on infinite bounds".format(cfg["upper_bound"]["type"]))
+        model = self.model_for(state)
+        self.about_to_plan()
+        n = len(root_states)
+        if rng_states is None:
+            rng_states = self.batch_rng_states(n)
+        try:
+            thresholds = self.thresholds()
+        except Exception:
+            # the reference evaluates the string at the first node update: one draw and one model step of every plan have
+            # been made by then (mdp_gape.py:67, :82-87)
+            for i in range(n):
+                gen = np.random.Generator(np.random.PCG64(0))
+                native.generator_set_state(gen, rng_states[i])
+                gen.integers(2 ** 30)
+                rng_states[i] = native.rng_state_from_generator(gen)
+            self.env_steps += n
+            raise
+        if not (np.isfinite(thresholds).all() and np.isfinite(self._value_init).all() and np.isfinite(cfg["gamma"])
+                and np.isfinite(cfg["accuracy"])):
+            raise ValueError("MDP-GapE: the bound's thresholds (count {}), the initial values, gamma and accuracy must be finite: "
+                             "the reference plans on the NaN bounds they make".format(
+                                 1 + int(np.flatnonzero(~np.isfinite(thresholds))[0]) if not np.isfinite(thresholds).all() else "-"))
+        order = self.action_order(model)
+        n_env = int(state.action_space.n)
+        column = None
+        if order is not None or n_env != model.A:
+            column = np.full(n_env, -1, np.int32)
+            listed = np.arange(model.A) if order is None else np.asarray(order)
+            column[listed[listed < n_env]] = np.flatnonzero(listed < n_env)
+        out = self.models.ctx.gape_plan(model, root_states, episodes, horizon, cfg["gamma"], cfg["accuracy"],
+                                        cfg["continuation_type"] == "uniform", n_env, column, thresholds, self._value_init,
+                                        rng_states)
+        # the reference's steps and draws up to the failing step are taken before it raises
+        self.env_steps += int(out["env_steps"].sum())
+        failed = np.flatnonzero(out["status"] != native.MP_OK)
+        if failed.size:
+            if out["status"][failed[0]] == native.ERR_GAPE_NO_CHALLENGER:
+                raise ValueError("max() arg is an empty sequence")                              # mdp_gape.py:247
+            if out["status"][failed[0]] == native.ERR_ARG:
+                # a bound below the root came out NaN (a mean one ulp below 1): np.amax is NaN, nothing equals it, and
+                # np_random.choice of the empty tie set raises (abstract.py:310-311)
+                raise ValueError("'a' cannot be empty unless no samples are taken")
+            raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # olop.py:133-134
+        out["rng_states"] = rng_states
+        self.relabel(out, model)
+        if order is not None:
+            arms = out["best_challenger"]
+            out["best_challenger"] = np.where(arms >= 0, order[np.maximum(arms, 0)], -1).astype(arms.dtype)
+            for k, fill in (("child_lower", 0), ("child_upper", 0), ("child_count", -1)):
+                back = np.full((n, max(n_env, int(order.max()) + 1)), fill, out[k].dtype)
+                back[:, order] = out[k]
+                out[k] = back
+        self.budget_used = int(out["episodes_run"][0]) * horizon
+        self.last, self._root, self._last_model = out, None, model
+        self.claim_device_tree()
+        return out
+
+    def plan(self, state, observation):
+        """MDPGapE.plan (mdp_gape.py:94-110), with the planner's generator written back also when the plan raises."""
+        s0, steps0 = device_model.env_root_state(state)
+        rng = native.rng_state_from_generator(self.np_random).reshape(1, 6)
+        try:
+            out = self.plan_batch(state, [s0], [steps0], rng_states=rng)
+        finally:
+            native.generator_set_state(self.np_random, rng[0])
+        return [int(out["plans"][0, 0])]
+
+    def step_tree(self, actions):
+        """mdp_gape.py:112-127 with the one strategy there is: the tree is rebuilt."""
+        self.step_by_reset()
+
+    def export_tree(self, root=0):
+        self.require_device_tree()
+        arrays = self.models.ctx.gape_tree(root)
+        order = self.action_order(self._last_model)
+        if order is not None:
+            act = arrays["action"]
+            arrays["action"] = np.where(arrays["kind"] == 1, order[np.clip(act, 0, len(order) - 1)], act).astype(act.dtype)
+        return build_gape_tree(arrays, self)
+
+    def get_visits(self):
+        """Observations stepped through (abstract.py:163-167): every model step leads to a decision node and counts once
+        there, so the counts come from the exported tree's decision nodes by their observation (the last plan)."""
+        from collections import defaultdict
+        visits = defaultdict(int)
+        if self.root is not None:
+            for node, _ in self.root.breadth_first_search(self.root):
+                if isinstance(node, DecisionNode) and node.parent is not None and node.count > 0:
+                    visits[str(node.observation)] += node.count
+        return visits
+
+
+class DecisionNode(Node):
+    """A state node of an exported MDP-GapE tree (mdp_gape.py:134-249): ``count``, ``cumulative_reward``, ``mu_ucb``,
+    ``mu_lcb``, ``value_upper``, ``value_lower``, ``done``, ``children`` by action in creation order, ``observation`` (the
+    state; None at the root)."""
+
+    def get_value(self):
+        return self.value_upper
+
+    def selection_rule(self):
+        """mdp_gape.py:172-181 without the tie draw: the first child of the largest value_lower (a viewer must not consume
+        the planner's stream); at the root the planner's own best arm."""
+        if not self.children:
+            return None
+        if self.parent is None and self.planner is not None and self.planner.last is not None:
+            return int(self.planner.last["plans"][0, 0])
+        return max(self.children, key=lambda a: self.children[a].value_lower)
+
+
+class ChanceNode(Node):
+    """An action node of an exported MDP-GapE tree (mdp_gape.py:252-313): ``count``, ``value_upper``, ``value_lower``,
+    ``children`` by ``str(observation)``.  It has its parent's depth."""
+
+    def get_value(self):
+        return self.value_upper
+
+    def selection_rule(self):
+        raise AttributeError("Selection is done in DecisionNodes, not ChanceNodes")
+
+
+def build_gape_tree(arrays, planner=None):
+    """Creation-order arrays of mp_gape_tree_export -> linked :class:`DecisionNode` / :class:`ChanceNode` objects."""
+    nodes = []
+    for i in range(len(arrays["parent"])):
+        par = nodes[arrays["parent"][i]] if arrays["parent"][i] >= 0 else None
+        key, args = int(arrays["action"][i]), (int(arrays["count"][i]), float(arrays["vu"][i]), int(arrays["depth"][i]), planner)
+        if arrays["kind"][i]:
+            node = ChanceNode(par, key, *args)
+            par.children[key] = node
+        else:
+            node = DecisionNode(par, None if par is None else str(key), *args)
+            node.cumulative_reward = float(arrays["cum"][i])
+            node.mu_ucb, node.mu_lcb = float(arrays["mu_ucb"][i]), float(arrays["mu_lcb"][i])
+            node.done = bool(arrays["done"][i])
+            node.observation = None if par is None else key
+            if par is not None:
+                par.children[str(key)] = node
+        node.value_upper, node.value_lower = float(arrays["vu"][i]), float(arrays["vl"][i])
+        node.state = int(arrays["state"][i])
+        nodes.append(node)
+    return nodes[0]
+
+
+class MDPGapEAgent(OLOPAgent):
+    """Drop-in for ``rl_agents.agents.tree_search.mdp_gape.MDPGapEAgent`` on deterministic finite-MDP tables."""
+    PLANNER_TYPE = MDPGapE
+
+    def step(self, actions):
+        """The receding horizon with chance nodes (mdp_gape.py:322-341)."""
+        replanning_required = self.remaining_horizon == 0
+        if replanning_required:
+            self.remaining_horizon = self.config["receding_horizon"] - 1
+            self.planner.step_by_reset()
+        else:
+            self.remaining_horizon -= 1
+            # "reset" is the one strategy there is, so every step replans: step_tree rebuilds the tree, the reference then finds
+            # the root childless and asks for a new plan (:334-339)
+            self.planner.step_tree(actions)
+            replanning_required = True
+            self.planner.step_by_reset()
+        return replanning_required
+
+    def record(self, state, action, reward, next_state, done, info):
+        self.planner.next_observation = next_state

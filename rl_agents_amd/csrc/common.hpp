@@ -51,7 +51,7 @@ struct DevBuf {
 
 // what the last tree-search call left on the device (for the *_tree_export entry points)
 struct TreeMeta {
-    int kind = 0; // 0 none, 1 uct, 2 opd, 3 robust opd, 4 stochastic uct (mp_uct_plan_stochastic), 5 olop, 6 brue, 7 sparse sampling
+    int kind = 0; // 0 none, 1 uct, 2 opd, 3 robust opd, 4 stochastic uct (mp_uct_plan_stochastic), 5 olop, 6 brue, 7 sparse sampling, 8 mdp-gape
     int n_roots = 0, A = 0, cap = 0, K = 0, M = 1;
     double gamma = 0.0; // robust opd: the export recomputes leaf upper-bound vectors
     int buf = 0;        // UCT: which of the two tree workspaces (WS_TREE0 / WS_TREE2) holds the current trees
@@ -66,7 +66,9 @@ struct TreeMeta {
 
 enum { WS_TREE0 = 0, WS_TREE1, WS_TREE2, WS_TREE3, WS_TREE4, WS_TREE5, WS_TREE6, WS_TREE7, WS_IO0, WS_IO1, WS_IO2, WS_IO3, WS_IO4,
        WS_IO5, WS_IO6, WS_IO7, WS_IO8, WS_IO9, WS_TAB0, WS_TAB1, WS_TAB2, WS_TAB3, WS_VI0, WS_VI1, WS_VI2, WS_VI3,
-       WS_VI4, WS_VI5, WS_GROOT, WS_JUMP, WS_POL0, WS_POL1, WS_POL2, WS_POL3, WS_POL4, WS_COUNT };
+       WS_VI4, WS_VI5, WS_GROOT, WS_JUMP, WS_POL0, WS_POL1, WS_POL2, WS_POL3, WS_POL4,
+       WS_IO10, // (an eleventh caller array: mp_gape_plan's best_challenger)
+       WS_COUNT };
 
 // everything a captured chain of deterministic VI sweeps bakes into its kernel arguments
 struct ViGraphKey {

@@ -1,0 +1,451 @@
+// gape.hip -- MDP-GapE, best-arm identification at the root of a tree of decision and chance nodes (tree_search/mdp_gape.py,
+// olop.py:132-142, utils.py:89-203), on deterministic tables with one next state per chance node (max_next_states_count 1).
+//
+// Mapping: ONE ROOT PER WAVEFRONT (one 64-lane workgroup), the workgroups striding over the roots, as olop.hip.  A plan is at most
+// `episodes + 2` episodes (mdp_gape.py:94-110) of exactly `horizon` model steps:
+//   * the walk is the serial chain, one model step per depth, every lane holding the same (wave-uniform) state and generator;
+//   * the lanes cover a node's chance children, 64 at a time when |A| > 64: their creation at an expansion (one 16-byte model
+//     gather each, listing order by a ballot prefix count), the root's best-arm identification (:228-249: gaps, first minimum,
+//     challenger, the wider of the two), the tie set of random_argmax over value_upper below the root (:189-192, exact equality,
+//     a draw only for two or more ties) and the backup's two np.amax (:219-220);
+//   * the 2 * horizon Newton solves of an episode's path -- mu_ucb and mu_lcb of every decision node stepped into -- are
+//     independent (a node is on the path once and only the backup reads them): they go on the lanes after the walk, 64 at a time.
+// With one next state, p_hat = [1.0] and max_expectation_under_constraint returns it (utils.py:325-326), so a chance node's
+// values are mu + gamma * value of its decision child (:296-304), both sides.
+// A chance node and its single decision child share ONE record (GapeNode): the chance node's two values sit in a second array,
+// [cap][2], which is what the lanes read; the record keeps the order in which the two were created (cseq, dseq) for the export.
+// Records live in the wave_tree workspace, children contiguous in creation order: at most 1 + (episodes + 2) * horizon * |A|.
+// Everything that is not a basic IEEE operation -- the initial values (Python **), the thresholds by count (eval of the config
+// string) -- comes from host tables.  The Newton step's log is the device's (bounds to 1e-12, not bit-exact).
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "each_host.hpp"
+#include "kl_bound.hpp"
+#include "pcg64.hpp"
+#include "wave.hpp"
+#include "wave_host.hpp"
+
+namespace mp {
+
+constexpr size_t kGapeKeepBytes = (size_t)1 << 30; // trees of every root kept while they fit (the rule of OLOP and BRUE)
+
+struct GapeNode {
+    double cum, mu_ucb, mu_lcb;     // the decision child: cumulative_reward, mu_ucb, mu_lcb (olop.py:109-116, mdp_gape.py:139-143)
+    double vu, vl;                  // the decision child's value_upper / value_lower
+    int32_t count_c, count_d;       // visits of the chance node and of its decision child (equal once stepped through)
+    int32_t state, parent, first_child, n_children; // the child's state; the record of the parent decision node; the child's children
+    int32_t action, depth, done;    // the chance node's action (a column); the CHILD's depth (the chance node's is depth - 1)
+    int32_t cseq, dseq, pad;        // creation numbers of the chance node and of the decision child (-1: not created yet)
+};
+static_assert(sizeof(GapeNode) == 88, "GapeNode layout");
+
+struct GapeArgs {
+    int n_roots, A, M, H, cap, done_on_next, uniform, n_env, keep, grid, max_plan_len;
+    double gamma, accuracy;
+    const Rec *rec;
+    const int32_t *root_state;
+    const double *thr;   // [M + 2] threshold by count - 1
+    const double *vinit; // [H + 1] (1 - gamma ** (H - d)) / (1 - gamma)
+    const double *col;   // [n_env] the column of environment action a, -1 without one (small integers, kept in the double table)
+    uint64_t *rng;
+    GapeNode *nodes;     // [slots][cap]
+    double *val;         // [slots][cap][2] the chance nodes' value_upper, value_lower
+    int32_t *n_nodes_out;
+    int32_t *plans, *plan_len, *episodes_run, *status, *arms; // arms [n_roots][2]: the best arm's action and the challenger's
+    int64_t *env_steps, *child_count; // child_count [n_roots][A] by column, -1 where the root lists no such action
+    double *child_lower, *child_upper; // [n_roots][A]
+};
+
+// the first maximum of f(i) over [0, k), NaN never winning (`v > best` is false for it); f gives -inf where i is left out.
+// The index is ALWAYS in [0, k): where nothing exceeds -inf -- every value left out, -inf or NaN -- it is `fallback`, which the
+// caller chooses among the indices it has not left out.
+template <typename F>
+__device__ __forceinline__ int gape_first_max(int k, int lane, int fallback, F f, double *value = nullptr)
+{
+    double bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = lane; i < k; i += 64) {
+        const double v = f(i);
+        if (v > bv) { bv = v; bi = i; }
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+    }
+    if (value) *value = bv;
+    return bi < k ? bi : fallback;
+}
+
+// best_arm_identification_selection (mdp_gape.py:228-249) over k >= 2 children, C = [k][2] (value_upper, value_lower).
+// gap_i = max over j != i of (U_j - L_i), from -inf with Python's max(a, b), which a NaN term never replaces: rounding is
+// monotone, so that is (max over the non-NaN U_j, j != i) - L_i, -inf where that difference is NaN; and the maximum without i
+// is the largest U, or the second largest where i is the first to hold the largest.  min() by gap keeps the first minimum (no
+// gap is NaN); max() by value_upper over the rest keeps its first element when that is NaN, and a later NaN never wins.
+// Every index handed back is in [0, k), whatever the values are.
+__device__ void gape_bai(const double *C, int k, int lane, int *selected, int *best, int *challenger)
+{
+    double top1, top2;
+    const int i1 = gape_first_max(k, lane, 0, [&](int i) { return C[2 * i]; }, &top1);
+    gape_first_max(k, lane, 0, [&](int i) { return i == i1 ? -INFINITY : C[2 * i]; }, &top2);
+    const int b = gape_first_max(k, lane, 0, [&](int i) {
+        const double gap = (i == i1 ? top2 : top1) - C[2 * i + 1];
+        return isnan(gap) ? (double)INFINITY : -gap; // min by gap
+    });
+    const int rest0 = b == 0 ? 1 : 0; // the first of the rest (k >= 2)
+    int c = rest0;
+    if (!isnan(C[2 * rest0])) c = gape_first_max(k, lane, rest0, [&](int i) { return i == b ? -INFINITY : C[2 * i]; });
+    const double wb = C[2 * b] - C[2 * b + 1], wc = C[2 * c] - C[2 * c + 1];
+    *best = b; *challenger = c; *selected = wc > wb ? c : b; // max([best, challenger], key=width): the first unless exceeded
+}
+
+// np.amax of column `which` of the children's values: NaN if any is NaN
+__device__ __forceinline__ double gape_amax(const double *C, int k, int which, int lane)
+{
+    double m = -INFINITY;
+    bool nan_seen = false;
+    for (int i = lane; i < k; i += 64) {
+        const double v = C[2 * i + which];
+        if (isnan(v)) nan_seen = true;
+        else if (v > m) m = v;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        const double o = __shfl_xor(m, off);
+        m = o > m ? o : m;
+    }
+    return __ballot(nan_seen) ? (double)NAN : m;
+}
+
+// random_argmax over the children's value_upper (abstract.py:296-311): the positions equal to the maximum, one of them drawn by
+// Generator.choice -- which draws nothing from a set of one.  -1 for an empty set (a NaN among the values: nothing equals the
+// NaN np.amax returns, and Generator.choice raises ValueError), else a position in [0, k)
+__device__ int gape_random_argmax(const double *C, int k, int lane, Pcg64 &gen)
+{
+    const double m = gape_amax(C, k, 0, lane);
+    int ties = 0;
+    for (int i0 = 0; i0 < k; i0 += 64) {
+        const int i = i0 + lane;
+        ties += __popcll(__ballot(i < k && C[2 * i] == m));
+    }
+    if (ties == 0) return -1;
+    int r = ties > 1 ? (int)gen.below((uint32_t)ties) : 0;
+    for (int i0 = 0; i0 < k; i0 += 64) {
+        const int i = i0 + lane;
+        unsigned long long bal = __ballot(i < k && C[2 * i] == m);
+        const int c = __popcll(bal);
+        if (r >= c) { r -= c; continue; }
+        for (; r > 0; --r) bal &= bal - 1;
+        return i0 + __ffsll((long long)bal) - 1;
+    }
+    return 0; // (not reached: r < ties)
+}
+
+__global__ __launch_bounds__(64) void gape_kernel(GapeArgs p)
+{
+    extern __shared__ int32_t path[]; // [H + 1] records of the episode's walk
+    const int lane = threadIdx.x, A = p.A, H = p.H;
+    const uint32_t done_bit = p.done_on_next ? 2u : 1u;
+    for (int root = blockIdx.x; root < p.n_roots; root += p.grid) {
+        const long slot = p.keep ? root : (root == 0 ? p.grid : blockIdx.x);
+        GapeNode *N = p.nodes + slot * p.cap;
+        double *V = p.val + slot * p.cap * 2;
+        if (lane == 0) {
+            GapeNode r;
+            r.cum = 0.0; r.mu_ucb = 1.0; r.mu_lcb = 0.0; r.vu = p.vinit[0]; r.vl = 0.0; r.count_c = 0; r.count_d = 0;
+            r.state = p.root_state[root]; r.parent = -1; r.first_child = -1; r.n_children = 0; r.action = -1; r.depth = 0; r.done = 0;
+            r.cseq = -1; r.dseq = 0; r.pad = 0;
+            N[0] = r;
+            V[0] = 0.0; V[1] = 0.0;
+        }
+        __syncthreads();
+        Pcg64 gen;
+        gen.load(p.rng + (long)root * 6);
+        int n_nodes = 1, n_created = 1, status = MP_OK, episodes_run = 0, best = -1, challenger = -1;
+        long steps = 0;
+
+        // DecisionNode.expand (mdp_gape.py:162-170): a chance child per listed action, in listing order; *rank = the position
+        // of column `col` among them, -1 when it is not listed
+        auto expand = [&](int node, int state, int depth, int col, int *rank) {
+            const Rec *row = p.rec + (long)state * A;
+            const int fc = n_nodes;
+            int pos0 = 0;
+            *rank = -1;
+            for (int a0 = 0; a0 < A; a0 += 64) {
+                const int a = a0 + lane;
+                Rec rc;
+                bool av = false;
+                if (a < A) { rc = row[a]; av = (rc.flags & 4u) != 0; }
+                const unsigned long long bal = __ballot(av);
+                const int pos = pos0 + __popcll(bal & ((1ull << lane) - 1ull));
+                if (av) {
+                    GapeNode c;
+                    c.cum = 0.0; c.mu_ucb = 1.0; c.mu_lcb = 0.0; c.vu = p.vinit[depth + 1]; c.vl = 0.0; c.count_c = 0; c.count_d = 0;
+                    c.state = rc.next; c.parent = node; c.first_child = -1; c.n_children = 0; c.action = a; c.depth = depth + 1;
+                    c.done = 0; c.cseq = n_created + pos; c.dseq = -1; c.pad = 0;
+                    N[fc + pos] = c;
+                    V[2 * (fc + pos)] = p.vinit[depth]; // a chance node has its parent's depth (mdp_gape.py:256-258)
+                    V[2 * (fc + pos) + 1] = 0.0;
+                }
+                if (col >= a0 && col < a0 + 64 && ((bal >> (col - a0)) & 1ull))
+                    *rank = pos0 + __popcll(bal & ((1ull << (col - a0)) - 1ull));
+                pos0 += __popcll(bal);
+            }
+            if (lane == 0) { N[node].first_child = fc; N[node].n_children = pos0; }
+            n_nodes += pos0;
+            n_created += pos0;
+            __syncthreads();
+            return pos0;
+        };
+
+        for (int e = 0; e < p.M + 2 && status == MP_OK; ++e) {
+            gen.below(1u << 30); // state.seed(self.np_random.randint(2**30)), mdp_gape.py:67
+            if (N[0].n_children == 0) {
+                int unused;
+                expand(0, N[0].state, 0, -1, &unused);
+            }
+            int node = 0;
+            if (lane == 0) path[0] = 0;
+            for (int h = 0; h < H; ++h) {
+                const GapeNode nd = N[node];
+                int fc = nd.first_child, k = nd.n_children, j;
+                if (node == 0) { // sampling_rule at the root: the arm best-arm identification selects (mdp_gape.py:185-187)
+                    // one listed action: max() of an empty list (:247).  (None at all cannot be: mp_model_set_available
+                    // asks for one in every state; the reference would fail in min() there.)
+                    if (k < 2) { status = MP_ERR_GAPE_NO_CHALLENGER; break; }
+                    gape_bai(V + 2 * (long)fc, k, lane, &j, &best, &challenger);
+                } else if (k > 0) {
+                    j = gape_random_argmax(V + 2 * (long)fc, k, lane, gen);
+                    if (j < 0) { status = MP_ERR_ARG; break; } // a NaN bound below the root: np_random.choice([]) raises
+                } else {
+                    // a childless node: randint(action_space.n) over ALL actions or action 0 (:194-196), then get_child expands
+                    // and gives an unlisted action up for the first listed one (:155-160)
+                    const int a_env = p.uniform ? (int)gen.below((uint32_t)p.n_env) : 0;
+                    const int col = a_env < p.n_env ? (int)p.col[a_env] : -1;
+                    int rank;
+                    fc = n_nodes;
+                    k = expand(node, nd.state, nd.depth, col, &rank);
+                    j = rank >= 0 ? rank : 0;
+                }
+                const int child = fc + j;
+                const GapeNode c0 = N[child];
+                const Rec rc = p.rec[(long)nd.state * A + c0.action];
+                ++steps;
+                const double r = rc.reward;
+                // olop.py:133-134, after the step was counted.  (The reference has also counted the chance node and made its
+                // decision child by then; the tree of a failed plan is not kept in that state: nothing reads it.)
+                if (!(0.0 <= r && r <= 1.0)) { status = MP_ERR_REWARD_RANGE; break; }
+                if (lane == 0) { // ChanceNode.update (:264-265), get_child (:272-286), OLOPNode.update (olop.py:132-142)
+                    GapeNode c = c0;
+                    c.count_c += 1;
+                    if (c.dseq < 0) c.dseq = n_created;
+                    if (rc.flags & done_bit) c.done = 1;
+                    c.cum += c.done ? 0.0 : r;
+                    c.count_d += 1;
+                    N[child] = c;
+                    path[h + 1] = child;
+                }
+                if (c0.dseq < 0) ++n_created;
+                node = child;
+                __syncthreads();
+            }
+            if (status != MP_OK) break;
+            // compute_reward_ucb (mdp_gape.py:200-210) of the path's decision nodes: H upper bounds, then H lower bounds
+            for (int t0 = 0; t0 < 2 * H; t0 += 64) {
+                const int t = t0 + lane;
+                if (t < 2 * H) {
+                    const bool lower = t >= H;
+                    GapeNode *c = N + path[1 + (lower ? t - H : t)];
+                    const double thr = p.thr[c->count_d - 1];
+                    if (lower) c->mu_lcb = kl_upper_bound<false, true>(c->cum, c->count_d, thr);
+                    else c->mu_ucb = kl_upper_bound<false, false>(c->cum, c->count_d, thr);
+                }
+            }
+            __syncthreads();
+            // backup_to_root (:214-226, :288-305), from the depth-H decision node up
+            for (int h = H; h >= 0; --h) {
+                const int id = path[h];
+                const GapeNode nd = N[id];
+                double vu = 0.0, vl = 0.0; // the depth-H node has no children
+                if (nd.n_children > 0) {
+                    vu = gape_amax(V + 2 * (long)nd.first_child, nd.n_children, 0, lane);
+                    vl = gape_amax(V + 2 * (long)nd.first_child, nd.n_children, 1, lane);
+                }
+                if (lane == 0) {
+                    N[id].vu = vu; N[id].vl = vl;
+                    if (h > 0) {
+                        V[2 * (long)id] = nd.mu_ucb + p.gamma * vu;
+                        V[2 * (long)id + 1] = nd.mu_lcb + p.gamma * vl;
+                    }
+                }
+                __syncthreads();
+            }
+            // the stopping rule (:100-102) on the root's best arm and challenger
+            const int fc0 = N[0].first_child;
+            int sel;
+            gape_bai(V + 2 * (long)fc0, N[0].n_children, lane, &sel, &best, &challenger);
+            episodes_run = e + 1;
+            if (V[2 * (long)(fc0 + challenger)] - V[2 * (long)(fc0 + best) + 1] < p.accuracy) break;
+        }
+        // get_plan (:129-131): the best arm's action; the root's arms for the caller
+        const int fc0 = N[0].first_child, k0 = N[0].n_children;
+        for (int a = lane; a < A; a += 64) {
+            if (p.child_count) p.child_count[(long)root * A + a] = -1;
+            if (p.child_lower) p.child_lower[(long)root * A + a] = 0.0;
+            if (p.child_upper) p.child_upper[(long)root * A + a] = 0.0;
+        }
+        __syncthreads();
+        for (int i = lane; i < k0; i += 64) {
+            const GapeNode c = N[fc0 + i];
+            if (p.child_count) p.child_count[(long)root * A + c.action] = c.count_c;
+            if (p.child_lower) p.child_lower[(long)root * A + c.action] = V[2 * (long)(fc0 + i) + 1];
+            if (p.child_upper) p.child_upper[(long)root * A + c.action] = V[2 * (long)(fc0 + i)];
+        }
+        if (lane == 0) {
+            const bool ok = status == MP_OK && best >= 0;
+            gen.store(p.rng + (long)root * 6);
+            if (p.plans)
+                for (int i = 0; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = ok && i == 0 ? N[fc0 + best].action : -1;
+            if (p.plan_len) p.plan_len[root] = ok ? 1 : 0;
+            if (p.episodes_run) p.episodes_run[root] = episodes_run;
+            if (p.status) p.status[root] = status;
+            if (p.env_steps) p.env_steps[root] = steps;
+            if (p.arms) {
+                p.arms[2 * (long)root] = ok ? N[fc0 + best].action : -1;
+                p.arms[2 * (long)root + 1] = ok ? N[fc0 + challenger].action : -1;
+            }
+            p.n_nodes_out[root] = n_nodes;
+        }
+        __syncthreads();
+    }
+}
+
+inline FormName gape_form_name(bool keep) { return slots_form_name("gape", keep); }
+
+} // namespace mp
+
+using namespace mp;
+
+extern "C" {
+
+int mp_gape_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
+                 double gamma, double accuracy, int32_t continuation, int32_t n_actions_env, const int32_t *action_column,
+                 const double *thr_by_count, const double *value_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans,
+                 int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps, int32_t *status, double *child_lower,
+                 double *child_upper, int64_t *child_count, int32_t *best_challenger, int32_t mem)
+{
+    const char *const who = "mp_gape_plan";
+    if (!ctx || !model || !root_state || !rng_state || !thr_by_count || !value_init) return fail(MP_ERR_ARG, "%s: NULL argument", who);
+    int rmem;
+    MP_TRY(wave_mem(who, &mem, &rmem));
+    if (model->mode != MP_MODE_DETERMINISTIC)
+        return fail(MP_ERR_MODE, "%s: model mode %d is not a deterministic table (a dense or sparse model needs the reference's "
+                                 "transition bounds, which are not built)", who, model->mode);
+    MP_TRY(wave_mdp_check(who, model, false));
+    const int A = model->A;
+    if (n_roots < 1 || episodes < 0 || horizon < 1 || horizon > 16384 || max_plan_len < 0 || A < 1 || n_actions_env < 1)
+        return fail(MP_ERR_ARG, "%s: bad sizes", who);
+    // a NaN among them would make NaN bounds of every node, which the reference plans on and no plan is worth
+    if (!isfinite(gamma) || !isfinite(accuracy)) return fail(MP_ERR_ARG, "%s: gamma and accuracy must be finite", who);
+    for (int c = 0; c < episodes + 2; ++c)
+        if (!isfinite(thr_by_count[c])) return fail(MP_ERR_ARG, "%s: the threshold of count %d is not finite", who, c + 1);
+    for (int d = 0; d <= horizon; ++d)
+        if (!isfinite(value_init[d])) return fail(MP_ERR_ARG, "%s: the initial value of depth %d is not finite", who, d);
+    if (continuation != 0 && continuation != 1) return fail(MP_ERR_ARG, "%s: continuation %d is neither 0 (action 0) nor 1 (uniform)", who, continuation);
+    if (!action_column && n_actions_env != A)
+        return fail(MP_ERR_ARG, "%s: %d environment actions need their columns among the model's %d", who, n_actions_env, A);
+    for (int a = 0; action_column && a < n_actions_env; ++a)
+        if (action_column[a] < -1 || action_column[a] >= A) return fail(MP_ERR_ARG, "%s: column %d out of range", who, action_column[a]);
+    MP_TRY(wave_roots(ctx, who, root_state, n_roots, model->S, mem));
+    // a record per chance node: every step of every episode may expand one decision node
+    const long long cap = 1 + ((long long)episodes + 2) * horizon * A;
+    if (cap > 0x7fffffffLL) return fail(MP_ERR_ARG, "%s: %lld nodes per tree do not fit a 32-bit index", who, cap);
+    if ((size_t)cap * (sizeof(GapeNode) + 2 * sizeof(double)) > kGapeKeepBytes)
+        return fail(MP_ERR_ARG, "%s: %lld nodes per tree take more than 1 GiB", who, cap);
+
+    // one table: thresholds by count [M + 2], the initial values [H + 1], the columns of the environment's actions [n_env]
+    std::vector<double> tab((size_t)episodes + 2 + horizon + 1 + n_actions_env);
+    for (int c = 0; c < episodes + 2; ++c) tab[c] = thr_by_count[c];
+    for (int d = 0; d <= horizon; ++d) tab[(size_t)episodes + 2 + d] = value_init[d];
+    for (int a = 0; a < n_actions_env; ++a) tab[(size_t)episodes + 2 + horizon + 1 + a] = action_column ? action_column[a] : a;
+    double *d_tab = nullptr;
+    MP_TRY(upload_tables(ctx, 42, tab, &d_tab));
+
+    GapeArgs a;
+    const EachForm form = each_form_global(EACH_OLOP, horizon, n_roots, ctx->prop.multiProcessorCount); // path[H + 1] in LDS
+    a.n_roots = n_roots; a.A = A; a.M = episodes; a.H = horizon; a.cap = (int)cap; a.done_on_next = model->done_on_next;
+    a.uniform = continuation; a.n_env = n_actions_env; a.max_plan_len = max_plan_len; a.gamma = gamma; a.accuracy = accuracy;
+    a.grid = form.grid; a.rec = model->rec; a.thr = d_tab; a.vinit = d_tab + episodes + 2; a.col = a.vinit + horizon + 1;
+    MP_TRY(wave_tree(ctx, 8, n_roots, A, (long)cap, 2, kGapeKeepBytes, a.grid + 1, a.grid, &a.nodes, &a.val, &a.n_nodes_out, &a.keep));
+    WaveIo io(mem, rmem, n_roots, root_state, &a.root_state, rng_state, &a.rng);
+    io.add(WS_IO3, plans, &a.plans, (size_t)max_plan_len);
+    io.add(WS_IO4, plan_len, &a.plan_len);
+    io.add(WS_IO5, episodes_run, &a.episodes_run);
+    io.add(WS_IO8, env_steps, &a.env_steps);
+    io.add(WS_IO7, status, &a.status);
+    io.add(WS_IO6, child_lower, &a.child_lower, (size_t)A);
+    io.add(WS_IO9, child_upper, &a.child_upper, (size_t)A);
+    io.add(WS_IO1, child_count, &a.child_count, (size_t)A);
+    io.add(WS_IO10, best_challenger, &a.arms, (size_t)2);
+    MP_TRY(wave_stage(ctx, io));
+    MP_TRY(wave_launch(ctx, gape_kernel, a.grid, form.lds_bytes(), gape_form_name(a.keep), a));
+    return wave_unstage(ctx, io);
+}
+
+const char *mp_gape_form_names(void)
+{
+    static const std::string names = std::string(gape_form_name(true).s) + "\n" + gape_form_name(false).s;
+    return names.c_str();
+}
+
+int mp_gape_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, uint8_t *kind, int32_t *parent, int32_t *action,
+                        int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *mu_lcb,
+                        double *value_upper, double *value_lower, uint8_t *done, int32_t *state)
+{
+    int32_t slot, n;
+    MP_TRY(wave_export_begin(ctx, 8, "mp_gape_tree_export", "mp_gape_plan", root, &slot, &n));
+    std::vector<GapeNode> na((size_t)n);
+    std::vector<double> val((size_t)n * 2);
+    MP_TRY(wave_pull(ctx, WS_TREE0, slot, n, sizeof(GapeNode), na.data()));
+    MP_TRY(wave_pull(ctx, WS_TREE1, slot, n, 2 * sizeof(double), val.data()));
+    // the records hold a chance node and its decision child: both, in the order they were created
+    std::vector<std::pair<int32_t, int32_t>> order; // (creation number, record * 2 + is_chance)
+    order.emplace_back(0, 0);
+    for (int i = 1; i < n; ++i) {
+        if (na[i].cseq < 1 || na[i].parent < 0 || na[i].parent >= n) return fail(MP_ERR_ARG, "mp_gape_tree_export: bad record %d", i);
+        order.emplace_back(na[i].cseq, i * 2 + 1);
+        if (na[i].dseq >= 0) order.emplace_back(na[i].dseq, i * 2);
+    }
+    std::sort(order.begin(), order.end());
+    const int m = (int)order.size();
+    if (n_nodes) *n_nodes = m;
+    if (m > cap) return fail(MP_ERR_ARG, "mp_gape_tree_export: capacity %d < %d nodes", cap, m);
+    std::vector<int32_t> pos((size_t)n * 2, -1);
+    for (int q = 0; q < m; ++q) pos[order[q].second] = q;
+    for (int q = 0; q < m; ++q) {
+        const int i = order[q].second >> 1;
+        const bool chance = order[q].second & 1;
+        const GapeNode &r = na[i];
+        if (kind) kind[q] = chance ? 1 : 0;
+        if (parent) parent[q] = chance ? pos[r.parent * 2] : (i == 0 ? -1 : pos[i * 2 + 1]);
+        if (action) action[q] = chance ? r.action : (i == 0 ? -1 : r.state);
+        if (depth) depth[q] = chance ? r.depth - 1 : r.depth;
+        if (count) count[q] = chance ? r.count_c : r.count_d;
+        if (cumulative_reward) cumulative_reward[q] = chance ? 0.0 : r.cum;
+        if (mu_ucb) mu_ucb[q] = chance ? 0.0 : r.mu_ucb;
+        if (mu_lcb) mu_lcb[q] = chance ? 0.0 : r.mu_lcb;
+        if (value_upper) value_upper[q] = chance ? val[2 * (size_t)i] : r.vu;
+        if (value_lower) value_lower[q] = chance ? val[2 * (size_t)i + 1] : r.vl;
+        if (done) done[q] = chance ? 0 : (uint8_t)r.done;
+        if (state) state[q] = chance ? na[r.parent].state : r.state;
+    }
+    return MP_OK;
+}
+
+} // extern "C"

@@ -22,6 +22,7 @@
 
 #include "common.hpp"
 #include "each_host.hpp"
+#include "kl_bound.hpp"
 #include "pcg64.hpp"
 #include "seed_sequence.hpp"
 #include "wave.hpp"
@@ -55,64 +56,7 @@ struct OlopArgs {
     int Sb;              // LDS_MODEL: states per MDP of the batch model (a root's MDP starts at global state (s / Sb) * Sb)
 };
 
-// utils.py:89-109 bernoulli_kullback_leibler
-__device__ __forceinline__ double bernoulli_kl(double p, double q)
-{
-    double kl1 = 0.0, kl2 = INFINITY;
-    if (p > 0 && q > 0) kl1 = p * log(p / q);
-    if (q < 1) kl2 = p < 1 ? (1 - p) * log((1 - p) / (1 - q)) : 0.0;
-    return kl1 + kl2;
-}
-
-// utils.py:123-146 kl_upper_bound with newton_iteration (:149-203): eps 1e-2, weight 0.9, 100 iterations, the in-loop clamps,
-// the final clamp.  `py` follows whether the iterate is still a Python float: only then does the derivative raise
-// ZeroDivisionError (and the finite difference of :183 replace it); numpy scalars give inf / nan instead.
-// TRACE (mp_selftest_olop_bound only; the planner's instantiation is <false> and holds none of it): the number of iterations
-// and the decisions taken, KL_* below, so that a test can hold them against the reference's, point by point.
-enum { KL_CLAMP_UPPER = 1, KL_CLAMP_LOWER = 2, KL_FINITE_DIFFERENCE = 4, KL_FINAL_LOWER = 8, KL_FINAL_UPPER = 16 };
-
-template <bool TRACE>
-__device__ double kl_upper_bound(double total, int count, double threshold, int *iterations = nullptr, int *decisions = nullptr)
-{
-    int mask = 0, its = 0;
-    if constexpr (TRACE) { *iterations = 0; *decisions = 0; }
-    if (count == 0) return 1.0;
-    const double mu = total / (double)count, max_div = threshold / (double)count;
-    const double a = mu, b = 1.0, eps = 1e-2, w = 0.9, wc = 1.0 - 0.9;
-    const double x0 = (a + b) / 2;
-    if (a == b) return a;
-    double x = INFINITY, xn = x0;
-    bool pyn = true;
-    for (int it = 0; fabs(x - xn) > eps && it < 100; ++it) {
-        x = xn;
-        const bool px = pyn;
-        const double fx = bernoulli_kl(mu, x) - max_div;
-        double dfx;
-        if (px && (1 - x == 0 || x == 0)) {
-            dfx = (fx - (bernoulli_kl(mu, x - eps) - max_div)) / eps;
-            if constexpr (TRACE) mask |= KL_FINITE_DIFFERENCE;
-        } else dfx = (1 - mu) / (1 - x) - mu / x;
-        if (dfx != 0) { xn = x - fx / dfx; pyn = false; }
-        if (xn < a) {
-            xn = w * a + wc * x; pyn = px;
-            if constexpr (TRACE) mask |= KL_CLAMP_LOWER;
-        } else if (xn > b) {
-            xn = w * b + wc * x; pyn = px;
-            if constexpr (TRACE) mask |= KL_CLAMP_UPPER;
-        }
-        if constexpr (TRACE) ++its;
-    }
-    if (xn < a) {
-        xn = a;
-        if constexpr (TRACE) mask |= KL_FINAL_LOWER;
-    }
-    if (xn > b) {
-        xn = b;
-        if constexpr (TRACE) mask |= KL_FINAL_UPPER;
-    }
-    if constexpr (TRACE) { *iterations = its; *decisions = mask; }
-    return xn;
-}
+// bernoulli_kl and kl_upper_bound (utils.py:89-203) are in kl_bound.hpp, which gape.hip includes too
 
 __device__ __forceinline__ unsigned long long olop_ballot(bool p) { return __ballot(p); }
 
@@ -501,7 +445,7 @@ __global__ __launch_bounds__(64) void olop_stoch_kernel(OlopStochArgs p)
     }
 }
 
-// mp_selftest_olop_bound: what the device computes for the three functions above, one input per lane of 64-lane workgroups --
+// mp_selftest_olop_bound: what the device computes for the functions of kl_bound.hpp, one input per lane of 64-lane workgroups --
 // the lanes of a wave run different iteration counts, as the path nodes of an episode do in olop_kernel.
 __global__ __launch_bounds__(64) void olop_bound_selftest_kernel(int n, int what, const double *__restrict__ x,
                                                                  const double *__restrict__ y, const int32_t *__restrict__ count,
@@ -513,6 +457,11 @@ __global__ __launch_bounds__(64) void olop_bound_selftest_kernel(int n, int what
     if (what == 0) {
         int its, mask;
         out[i] = kl_upper_bound<true>(x[i], count[i], y[i], &its, &mask);
+        iterations[i] = its;
+        decisions[i] = mask;
+    } else if (what == 3) { // the lower bound (MDP-GapE's mu_lcb), same outputs
+        int its, mask;
+        out[i] = kl_upper_bound<true, true>(x[i], count[i], y[i], &its, &mask);
         iterations[i] = its;
         decisions[i] = mask;
     } else if (what == 1) out[i] = bernoulli_kl(x[i], y[i]);
@@ -683,7 +632,8 @@ int mp_olop_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
 int mp_selftest_olop_bound(mp_ctx *ctx, int32_t what, int32_t n, const double *x, const double *y, const int32_t *count,
                            double *out, int32_t *iterations, int32_t *decisions)
 {
-    if (!ctx || n < 1 || what < 0 || what > 2 || !x || !out || (what < 2 && !y) || (what == 0 && (!count || !iterations || !decisions)))
+    const bool traced = what == 0 || what == 3; // the two bounds: counts in, iterations and decisions out
+    if (!ctx || n < 1 || what < 0 || what > 3 || !x || !out || (what != 2 && !y) || (traced && (!count || !iterations || !decisions)))
         return fail(MP_ERR_ARG, "mp_selftest_olop_bound: bad argument");
     MP_HIP(hipSetDevice(ctx->device));
     const size_t N = (size_t)n;
@@ -692,16 +642,16 @@ int mp_selftest_olop_bound(mp_ctx *ctx, int32_t what, int32_t n, const double *x
     int32_t *di = reinterpret_cast<int32_t *>(d + 3 * N);
     hipStream_t st = ctx->stream;
     hipError_t e = hipMemcpyAsync(d, x, N * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && what < 2) e = hipMemcpyAsync(d + N, y, N * sizeof(double), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && what == 0) e = hipMemcpyAsync(di, count, N * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && what != 2) e = hipMemcpyAsync(d + N, y, N * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && traced) e = hipMemcpyAsync(di, count, N * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(mp::olop_bound_selftest_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, st, n, what, d, d + N, di,
                            d + 2 * N, di + N, di + 2 * N);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + 2 * N, N * sizeof(double), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && what == 0) e = hipMemcpyAsync(iterations, di + N, N * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess && what == 0) e = hipMemcpyAsync(decisions, di + 2 * N, N * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && traced) e = hipMemcpyAsync(iterations, di + N, N * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && traced) e = hipMemcpyAsync(decisions, di + 2 * N, N * sizeof(int32_t), hipMemcpyDeviceToHost, st);
     const hipError_t e2 = hipStreamSynchronize(st);
     (void)hipFree(d);
     MP_HIP(e);

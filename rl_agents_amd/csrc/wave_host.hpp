@@ -59,7 +59,7 @@ struct WaveIo {
         int slot, dir, mem;       // workspace slot; IN, OUT or both; the memory flag it follows
         char *base;               // mp_uct_plan: the device side of root 0 (*dev moves from chunk to chunk)
     };
-    Item item[10];
+    Item item[12];
     int n = 0, mem, rmem, n_roots;
     size_t bytes(const Item &t) const { return n_roots * t.per_root; }
     template <typename T, typename D>

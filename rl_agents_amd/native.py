@@ -17,6 +17,7 @@ MP_OK, MP_ERR_HIP, MP_ERR_REWARD_RANGE, MP_ERR_ALLOC, MP_ERR_ARG, MP_ERR_MODE = 
 MODE_DETERMINISTIC, MODE_STOCHASTIC, MODE_SPARSE, MODE_CARTPOLE = 0, 1, 2, 3
 ERR_REWARD_RANGE, ERR_ARG, ERR_MODE = -2, -4, -5
 MP_ERR_GBOPD_DIVERGED, MP_ERR_GBOPD_NO_ACTION = -7, -8
+ERR_GAPE_NO_CHALLENGER = -9  # mp_gape_plan status: the root lists one action (mdp_gape.py:247 ValueError)
 ERR_OLOP_KEY = -6          # mp_olop_plan status: the "zeros" continuation's action is not a child (olop.py:89 KeyError)
 
 _LIB = None
@@ -125,6 +126,10 @@ SIGNATURES = {
     "mp_olop_plan_stochastic": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp,
                                           _vp, _vp, _vp, c_i32]),
     "mp_olop_stoch_form_names": (C.c_char_p, []),
+    "mp_gape_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp, c_i32, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_gape_form_names": (C.c_char_p, []),
+    "mp_gape_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_brue_plan":(C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_brue_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_olop_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp,
@@ -266,6 +271,8 @@ RESULTS = {
     "opd": (_PLANS, _LEN, ("root_lower", np.float64, (), 0), ("root_upper", np.float64, (), 0), _STEPS, _STATUS),
     "olop": (_PLANS, _LEN, _VALUE, _STEPS, _STATUS),
     "brue": (_ACTION, _VALUE, _STEPS, _STATUS),
+    "gape": (_PLANS, _LEN, ("episodes_run", np.int32, (), 0), _STEPS, _STATUS, ("child_lower", np.float64, ("A",), 0),
+             ("child_upper", np.float64, ("A",), 0), ("child_count", np.int64, ("A",), 0), ("best_challenger", np.int32, ("P",), -1)),
     "ss": (_ACTION, _VALUE, ("samples", np.int64, (), 0), _STATUS),
     "saopd": (_PLANS, _LEN, _STEPS, ("updates", np.int64, (), 0), _STATUS),
     "gbopd": (_PLANS, _LEN, ("value_lower", np.float64, (), 0), ("value_upper", np.float64, (), 0), _STEPS,
@@ -469,6 +476,12 @@ def each_form_info(planner, s_each, n_actions, horizon, n_roots, cus=256):
                 fit_limit=int(out[5]))
 
 
+def gape_form_names():
+    """The names an MDP-GapE plan (``gape_plan``) records for Context.last_kernel_variant() (mp_gape_form_names; host only).
+    They are part of no other list of names."""
+    return load().mp_gape_form_names().decode().split()
+
+
 def olop_stoch_form_names():
     """The names an OLOP plan on a dense / sparse model (``olop_plan_stochastic``) records for
     Context.last_kernel_variant() (mp_olop_stoch_form_names; host only).  They are part of no other list of names."""
@@ -647,9 +660,9 @@ class Context(object):
     def selftest_olop_bound(self, what, x, y=None, count=None):
         """What the DEVICE's OLOP code computes, one input per lane (mp_selftest_olop_bound).  ``what``: "kl_upper_bound"
         (x = cumulative rewards, count, y = thresholds) -> (bounds, Newton iterations, decision masks: 1 / 2 the in-loop upper /
-        lower clamp, 4 the finite difference, 8 / 16 the final lower / upper clamp); "bernoulli_kl" (p = x, q = y) -> values;
-        "log" -> values."""
-        code = {"kl_upper_bound": 0, "bernoulli_kl": 1, "log": 2}[what]
+        lower clamp, 4 the finite difference, 8 / 16 the final lower / upper clamp); "kl_lower_bound": the same for the lower
+        bound (MDP-GapE's mu_lcb); "bernoulli_kl" (p = x, q = y) -> values; "log" -> values."""
+        code = {"kl_upper_bound": 0, "bernoulli_kl": 1, "log": 2, "kl_lower_bound": 3}[what]
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         n = x.size
         out = np.zeros(n, np.float64)
@@ -1252,11 +1265,12 @@ class Context(object):
     def ropd_tree(self, root, cap, n_models):
         return _export_tree(self._lib.mp_ropd_tree_export, (self._h, int(root)), cap, self._opd_tree_fields(int(n_models)))
 
-    def _each_plan(self, fn, fn_models, family, model, rs, model_index, run, rng_state, mpl=None):
+    def _each_plan(self, fn, fn_models, family, model, rs, model_index, run, rng_state, mpl=None, **dims):
         """The host call OLOP, BRUE and Sparse Sampling plans share: ``fn(ctx, model, n, roots, *run, rng, [mpl], results,
-        MP_MEM_HOST)``, or ``fn_models`` with ``model_index`` (one MDP per root) in front of the roots -> the result dict."""
+        MP_MEM_HOST)``, or ``fn_models`` with ``model_index`` (one MDP per root) in front of the roots -> the result dict.
+        ``dims``: the family's other trailing dimensions."""
         n = rs.shape[0]
-        out = _results(family, n, **({} if mpl is None else {"L": mpl}))
+        out = _results(family, n, **({} if mpl is None else {"L": mpl}), **dims)
         roots = (n, _ptr(rs))
         if model_index is not None:
             fn, roots = fn_models, (n, _ptr(np.ascontiguousarray(model_index, dtype=np.int32).reshape(n)), _ptr(rs))
@@ -1301,6 +1315,40 @@ class Context(object):
     def olop_tree(self, root, cap):
         """Creation-order arrays of root ``root``'s tree after the last olop_plan (mp_olop_tree_export)."""
         return _export_tree(self._lib.mp_olop_tree_export, (self._h, int(root)), cap, self.OLOP_TREE)
+
+    def gape_plan(self, model, root_state, episodes, horizon, gamma, accuracy, uniform, n_actions_env, action_column, thr_by_count,
+                  value_init, rng_state):
+        """MDPGapE.plan for a batch of roots (host arrays): mp_gape_plan.  ``uniform``: the "uniform" continuation (else action
+        0 of the environment); ``action_column`` int [n_actions_env] or None: the model column of each environment action;
+        ``thr_by_count`` float64 [episodes + 2] and ``value_init`` float64 [horizon + 1] from the host.  ``plans`` [n, 1]: the
+        best arm's action (a column of the model), as ``best_challenger`` [n, 2]; ``child_*`` [n, A] by column."""
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        _check_rng(rng_state, rs.shape[0])
+        thr = np.ascontiguousarray(thr_by_count, dtype=np.float64).reshape(-1)
+        vin = np.ascontiguousarray(value_init, dtype=np.float64).reshape(-1)
+        if vin.size != int(horizon) + 1 or thr.size != int(episodes) + 2:
+            raise ValueError("gape_plan: thr_by_count [episodes + 2] and value_init [horizon + 1] expected")
+        col = None if action_column is None else np.ascontiguousarray(action_column, dtype=np.int32).reshape(-1)
+        if col is not None and col.size != int(n_actions_env):
+            raise ValueError("gape_plan: action_column [n_actions_env] expected")
+        run = (int(episodes), int(horizon), float(gamma), float(accuracy), 1 if uniform else 0, int(n_actions_env), _ptr(col),
+               _ptr(thr), _ptr(vin))
+        return self._each_plan(self._lib.mp_gape_plan, None, "gape", model, rs, None, run, rng_state, 1, A=model.A, P=2)
+
+    GAPE_TREE = (("kind", np.uint8, ()), ("parent", np.int32, ()), ("action", np.int32, ()), ("depth", np.int32, ()),
+                 ("count", np.int64, ()), ("cum", np.float64, ()), ("mu_ucb", np.float64, ()), ("mu_lcb", np.float64, ()),
+                 ("vu", np.float64, ()), ("vl", np.float64, ()), ("done", np.uint8, ()), ("state", np.int32, ()))
+
+    def gape_tree(self, root, cap=None):
+        """Creation-order arrays of root ``root``'s tree after the last gape_plan, decision (``kind`` 0) and chance (1) nodes
+        (mp_gape_tree_export).  ``cap`` None: the tree's own node count is asked first."""
+        if cap is None:
+            n = c_i32()
+            rc = self._lib.mp_gape_tree_export(self._h, int(root), 0, C.byref(n), *([None] * len(self.GAPE_TREE)))
+            if n.value < 1:                                     # (no tree to size: the refusal itself)
+                _check(rc)
+            cap = n.value
+        return _export_tree(self._lib.mp_gape_tree_export, (self._h, int(root)), cap, self.GAPE_TREE)
 
     def brue_plan(self, model, root_state, budget, horizon, gamma, gpow, rng_state, model_index=None):
         """BRUE.plan for a batch of roots (host arrays): mp_brue_plan.  ``gpow`` float64 [horizon + 1]: gamma ** d from the
