@@ -58,7 +58,8 @@ struct TreeMeta {
     bool armed = false; // UCT: mp_uct_step_tree was called; the next plan re-roots and continues
     int il = 0;          // UCT: 1 = wave-interleaved tree layout (see uct.hip TreeRef)
     long kept_bound = 0; // UCT: upper bound on the nodes a kept (re-rooted) tree can hold, see uct_plan_impl
-    bool virgin = false; // UCT: the children of a count-1 node were never stored and read as {0.0, 0, -1} (uct_virgin.hpp)
+    int virgin = 0;      // UCT: which nodes were never stored and read as {0.0, 0, -1} (uct_virgin.hpp, UctTreeMode): 0 none, 1 the
+                         // children of a count-1 node, 2 the children whose bit in the parent's first_child word is clear
     bool sp = false;     // stochastic UCT: the last plan used per-state policies (stored priors in the cold halves, phantom slots)
     int n_src = 0;       // UCT, while armed by mp_uct_step_tree_select: the roots the tree buffers still hold (n_roots is already
                          // the selection's; sources [n_roots] + room for the new sizes [n_roots] in WS_TREE7); 0 = root i continues root i

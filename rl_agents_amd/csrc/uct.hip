@@ -32,7 +32,9 @@
 //           the zero nodes of a wave's expansions lane-contiguously (the group-interleaved layout: one run per group and wave)
 //           instead of |A| strided nodes per lane (uct_kernel, TREE STORES; profiles/uct_tree_stores.md).  The children of a node
 //           that was visited once are all zero nodes: they are not loaded, and a fresh tree does not store them before they are
-//           entered (uct_kernel, VIRGIN GROUPS; uct_virgin.hpp; profiles/uct_virgin_groups.md).
+//           entered (uct_kernel, VIRGIN GROUPS; uct_virgin.hpp; profiles/uct_virgin_groups.md).  A fresh tree stores only the
+//           children an episode picked and marks them in the upper bits of the parent's first_child: the others are neither
+//           stored nor loaded (uct_kernel, VISITED MASK; profiles/uct_visited_mask.md).
 //   path    per-lane stack of visited node ids in LDS ([depth][lane], conflict-free): the backup
 //           walks known addresses, not parent pointers.
 #include <limits.h>
@@ -112,7 +114,9 @@ struct UctArgs {
     int rep_shift; // CartPole: a root is replicated over 2^rep_shift lanes (see the launch code: wavefronts of few ACTIVE lanes run slow)
     int waves; // wavefronts per workgroup
     int tree_stores; // 1: a full wave writes its expansions' zero nodes lane-contiguously and the backup stores the leaf whole;
-                     // 2 (the default): as 1, and virgin groups are not loaded and, in fresh trees, not stored (VIRGIN GROUPS below);
+                     // 2 (MP_UCT_TREE_STORES=virgin): as 1, and virgin groups are not loaded and, in fresh trees, not stored (VIRGIN
+                     // GROUPS below); 3 (the default; the host passes it for fresh trees of a form of uct_mask_form only, else 2): as
+                     // 2, and only the children an episode picked are stored or loaded (VISITED MASK below);
                      // 0 (MP_UCT_TREE_STORES=lane, an A/B knob): every store per lane, first_child of an expanded node on its own
     int balance; // host side only: 1 launches the BAL instantiation of the one-lane LDS-resident form (WAVE BALANCE in uct_kernel) with
                  // 64 more bytes of LDS; 0: MP_UCT_BALANCE=0, any other form, or a model that leaves no room for them
@@ -237,6 +241,11 @@ enum { ENV_TABLE = 0, ENV_CARTPOLE = 2, ENV_TABLE_LDSR = 3, ENV_TABLE_SPILL = 4 
 #ifndef MP_PCG_WORDS
 #define MP_PCG_WORDS 1
 #endif
+// -DMP_UCT_MASK_LOADS=0 builds the visited-mask form (VM) with the whole group loaded wherever any child of it was stored, instead
+// of one predicated load per stored child: the dropped sibling stores alone, for A/B runs (profiles/uct_visited_mask.md).
+#ifndef MP_UCT_MASK_LOADS
+#define MP_UCT_MASK_LOADS 1
+#endif
 // The instantiations of uct_kernel whose one-lane table rollout runs on Pcg64W: every table form (CartPole draws in its own
 // loops, the four-lane form jumps instead of stepping).
 constexpr bool uct_pcg_words_form(int AT, int ENV, bool SP, bool MK, int IL, bool QD)
@@ -267,7 +276,8 @@ constexpr bool uct_pcg_words_form(int AT, int ENV, bool SP, bool MK, int IL, boo
 // G_n from a table), so the stream stays the reference's.  Same trees, plans and generator states as every other variant.
 // BAL (the one-lane LDS-resident form): WAVE BALANCE below -- a template argument, not a kernel argument, because the form has no
 // scalar register left for a flag that lives over the whole plan (a run-time flag spilled in five of its seven instantiations).
-template <int AT, int ENV, bool SP = false, bool MK = false, int IL = 0, bool QD = false, bool BAL = false>
+// VM (the forms of uct_mask_form, fresh trees): VISITED MASK below -- a template argument for the same reason.
+template <int AT, int ENV, bool SP = false, bool MK = false, int IL = 0, bool QD = false, bool BAL = false, bool VM = false>
 // Per-state-policy kernels with |A| <= 5 are held to the registers of 4 waves per SIMD (they would take 134-140 VGPRs = 3
 // waves; TA 52 %, VALU 45 %, L1 28 % busy: latency-bound -- 2.14 -> 1.91 ms at 262 144 roots with the fourth wave).
 __global__ __launch_bounds__(ENV == ENV_TABLE_LDSR ? 1024 : (ENV == ENV_CARTPOLE ? 256 : 64),
@@ -421,10 +431,25 @@ void uct_kernel(UctArgs p)
     // trees only: the expansion stores no zero group at all -- most groups are never entered again -- and the first entry stores
     // the |A| - 1 siblings it does not pick; the picked one is the episode's leaf, which the backup stores whole (LEAF1).  Until
     // then the group's memory holds whatever was there: every reader applies the rule (uct_virgin.hpp; the host marks the trees).
-    // p.tree_stores == 2 (the default) runs both, 1 (MP_UCT_TREE_STORES=group) neither.
-    constexpr bool VSKIP = uct_virgin_form(AT, ENV, SP, MK, IL, QD);
+    // p.tree_stores == 2 (MP_UCT_TREE_STORES=virgin; kept trees) runs both, 1 (MP_UCT_TREE_STORES=group) neither.
+    // VISITED MASK (profiles/uct_visited_mask.md; uct_virgin.hpp has the rule), fresh trees only, p.tree_stores == 3 (the default).
+    // A child that no episode picked is the constant node too, whatever its parent's count, so the siblings of a pick need never
+    // be stored: the first_child word of an expanded node carries, above bit 24, which of its children have been.  A descent
+    // loads the children whose bit is set, each under its own predicate, and takes the constant for the others (the whole group
+    // loaded wherever any bit is set: MP_UCT_MASK_LOADS, an A/B build).  A pick whose bit is clear is
+    // the episode's leaf, which the backup stores whole (LEAF1); the descent sets its bit in the parent's word -- a register for the root's
+    // children (tf[]), one 4-byte store for a parent below them.  The root's own children live in registers and are all stored at
+    // the read-out: its word gets the full mask there.  As with VDEFER, a pick below the levels whose statistics stay in registers
+    // is stored at its entry, because the backup reads it back.  The mask rides in words that are registers already (fc, tf[]):
+    // nothing more is alive over the rollout.
+    // VM is a template argument like BAL: as a run-time flag beside the two above it spilled scalar registers in every
+    // LDS-resident instantiation, two vector registers in the headline's, and cost the gather form of |A| = 5 its fourth wave.
+    // The host launches the VM instantiation for fresh trees with p.tree_stores == 3 and no other.
+    static_assert(!VM || (uct_mask_form(AT, ENV, SP, MK, IL, QD) && LEAF1 && !CART), "the visited mask: the forms of uct_mask_form");
+    constexpr bool VMASK = VM;
+    constexpr bool VSKIP = !VM && uct_virgin_form(AT, ENV, SP, MK, IL, QD);
     constexpr bool VDEFER = VSKIP && LEAF1;
-    const bool vskip = VSKIP && p.tree_stores == 2;
+    const bool vskip = VSKIP && p.tree_stores >= 2;
     const bool vdefer = VDEFER && p.tree_stores == 2 && p.n_nodes_in == nullptr;
     bool wave_exp = false;
     if constexpr (WEXP) {
@@ -578,9 +603,27 @@ void uct_kernel(UctArgs p)
             if (AT > 0) {
                 UctNode c[AR];
                 bool virgin = false;
+                const int fcw = fc; // VMASK: the word as the node holds it, the visited mask above the id (the root's own: plain)
+                if (VMASK) fc &= kUctChildBits;
                 if (fc == 1) { // the root's children: registers
 #pragma unroll
                     for (int a = 0; a < AR; ++a) { c[a].value = tv[a]; c[a].count = tc[a]; c[a].first_child = tf[a]; }
+                } else if (VMASK) { // the children that were stored; the others are the constant node
+                    UctNode *grp = &tree.child(fc, 0);
+#pragma unroll
+                    for (int a = 0; a < AR; ++a) {
+                        const bool stored = ((fcw >> (kUctMaskShift + a)) & 1) != 0;
+                        c[a].value = 0.0; c[a].count = 0; c[a].first_child = -1;
+#if MP_UCT_MASK_LOADS
+                        if (stored) c[a] = tree.sibling(grp, a);
+#else
+                        if ((fcw >> kUctMaskShift) != 0) {
+                            const UctNode ld = tree.sibling(grp, a);
+                            asm volatile("" ::"v"(ld.count)); // (keeps the load where it is: the compiler sinks it below `stored`)
+                            if (stored) c[a] = ld;
+                        }
+#endif
+                    }
                 } else if (VSKIP && vskip && node_c == 1) { // a virgin group: nothing to load
                     virgin = true;
 #pragma unroll
@@ -661,6 +704,23 @@ void uct_kernel(UctArgs p)
 #pragma unroll
                     for (int a = 0; a < AR; ++a)
                         if (a != act || deep) tree.sibling(grp, a) = z;
+                }
+                if (VMASK && depth >= 1 && !((fcw >> (kUctMaskShift + act)) & 1)) {
+                    // the first pick of a child below the root's: its bit into the parent's word -- tf[] for a child of the
+                    // root (node = 1 + its action), else the word in memory (hnode is still the parent's handle).  No sibling is
+                    // stored; the pick itself only where the backup reads it back (see VDEFER above)
+                    const int w = fcw | (1 << (kUctMaskShift + act));
+                    if (depth == 1) {
+#pragma unroll
+                        for (int a = 0; a < AR; ++a) tf[a] = node == 1 + a ? w : tf[a];
+                    } else {
+                        tree.at(hnode).first_child = w;
+                    }
+                    if (depth + 1 >= 2 + KEEP) {
+                        UctNode z;
+                        z.value = 0.0; z.count = 0; z.first_child = -1;
+                        tree.child(fc, act) = z;
+                    }
                 }
             } else {
                 double m = 0.0;
@@ -744,8 +804,8 @@ void uct_kernel(UctArgs p)
                         tree.sibling(grp, a) = n;
                     }
                 }
-            } else if (VDEFER && vdefer) {
-                // (no zero group: the selection that enters it first completes it)
+            } else if ((VDEFER && vdefer) || VMASK) {
+                // (no zero group: the selection that enters it first completes it -- VMASK: nobody does, the new word's mask is 0)
             } else if (!(RC && node == 0)) { // the root's children were zero-initialised in registers
                 if constexpr (WEXP) {
                     wexp_pend = true;
@@ -1474,6 +1534,7 @@ void uct_kernel(UctArgs p)
     if (RC) {
         UctNode w;
         w.value = tv0; w.count = tc0; w.first_child = tf0;
+        if (VMASK && tf0 >= 0) w.first_child = tf0 | (((1 << AR) - 1) << kUctMaskShift); // (all its children are stored below)
         tree[0] = w;
         if (tf0 == 1) {
 #pragma unroll
@@ -1497,18 +1558,28 @@ void uct_kernel(UctArgs p)
                 ++len;
                 break;
             }
-            int mc = tree.child(fc, 0).count;
-            for (int a = 1; a < A; ++a) mc = max(mc, tree.child(fc, a).count);
+            // VMASK: a child whose bit in the word is clear was never stored, the constant node
+            unsigned stored = ~0u;
+            if (VMASK) { stored = (unsigned)fc >> kUctMaskShift; fc &= kUctChildBits; }
+            auto child = [&](int a) {
+                UctNode c;
+                c.value = 0.0; c.count = 0; c.first_child = -1;
+                if (!VMASK || ((stored >> a) & 1u)) c = tree.child(fc, a);
+                return c;
+            };
+            int mc = child(0).count;
+            for (int a = 1; a < A; ++a) mc = max(mc, child(a).count);
             int best = -1;
             double bv = 0.0;
             for (int a = 0; a < A; ++a) {
-                const UctNode c = tree.child(fc, a);
+                const UctNode c = child(a);
                 if (c.count == mc && (best < 0 || c.value > bv)) { best = a; bv = c.value; }
             }
             if (p.plans && len < p.max_plan_len) p.plans[(long)r * p.max_plan_len + len] = best;
             ++len;
-            at_c = tree.child(fc, best).count;
-            fc = tree.child(fc, best).first_child;
+            const UctNode b = child(best);
+            at_c = b.count;
+            fc = b.first_child;
         }
         if (p.plans)
             for (int i = len; i < p.max_plan_len; ++i) p.plans[(long)r * p.max_plan_len + i] = -1;
@@ -1517,7 +1588,8 @@ void uct_kernel(UctArgs p)
     if (p.n_nodes_out) p.n_nodes_out[r] = n_nodes;
     if (p.root_value) p.root_value[r] = tree[0].value;
     if (p.env_steps) p.env_steps[r] = (int64_t)steps_taken;
-    const int rfc = tree[0].first_child;
+    int rfc = tree[0].first_child;
+    if (VMASK) rfc = uct_word_child(rfc); // (the root's children are all stored)
     for (int a = 0; a < A; ++a) {
         if (p.root_child_count) p.root_child_count[(long)r * A + a] = rfc >= 0 ? max(tree.child(rfc, a).count, 0) : 0;
         if (p.root_child_value) p.root_child_value[(long)r * A + a] = rfc >= 0 ? tree.child(rfc, a).value : 0.0;
@@ -2335,19 +2407,20 @@ __global__ __launch_bounds__(SHARED ? 1024 : 256) void uct_row_kernel(UctArgs p)
 }
 
 // one thread: the visit count at the end of an action path (mp_uct_path_count)
-// `virgin`: the children of a count-1 node were never stored (uct_virgin.hpp) -- a path that enters them ends at a node of count 0
-// without children
+// `virgin` (UctTreeMode, uct_virgin.hpp): the children of a count-1 node, or the children whose bit in the parent's word is clear,
+// were never stored -- a path that enters one ends at a node of count 0 without children
 template <int IL>
 __global__ void uct_path_count_kernel(UctNode *trees, int root, int cap, int A, const int32_t *actions, int n, int64_t *out, int virgin)
 {
     const TreeRef<IL, 0> tree = tree_of<IL, 0>(trees, root, cap, A);
     int node = 0;
-    bool unstored = false; // `node` is a child of a count-1 node
+    bool unstored = false; // `node` was never stored
     for (int i = 0; i < n; ++i) {
-        const int fc = unstored ? -1 : tree[node].first_child;
+        const int w = unstored ? -1 : tree[node].first_child;
+        const int fc = virgin == kUctTreeMasked ? uct_word_child(w) : w;
         const int a = actions[i];
         if (fc < 0 || a < 0 || a >= A) { out[0] = -1; return; }
-        unstored = virgin && tree[node].count == 1;
+        unstored = virgin == kUctTreeMasked ? !uct_word_stored(w, a) : (virgin == kUctTreeCount1 && tree[node].count == 1);
         node = fc + a;
     }
     const int c = unstored ? 0 : tree[node].count;
@@ -2366,7 +2439,7 @@ __global__ __launch_bounds__(64) void uct_reroot_kernel(int n_roots, int n_src, 
                                                         const int32_t *n_old, const int32_t *__restrict__ source,
                                                         const int32_t *__restrict__ actions,
                                                         int32_t *n_new, // (n_old and n_new are the same array when source == nullptr)
-                                                        int virgin) // the old trees hold unstored groups (uct_virgin.hpp); the new ones are whole
+                                                        int virgin) // which nodes of the old trees were never stored (UctTreeMode, uct_virgin.hpp); the new ones are whole
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_roots) return;
@@ -2379,16 +2452,18 @@ __global__ __launch_bounds__(64) void uct_reroot_kernel(int n_roots, int n_src, 
     const TreeRef<IL, 0> n = tree_of<IL, 0>(new_trees, r, cap_new, A);
     const int a = actions[r];
     // `if action in self.root.children` (abstract.py:201): an unlisted action has a phantom slot, not a child
-    if (n_old[q] < 1 || o[0].first_child < 0 || a < 0 || a >= A || o[o[0].first_child + a].count < 0) {
+    // (a masked tree's root holds the full mask: its children are all stored)
+    const int rfc = n_old[q] < 1 ? -1 : (virgin == kUctTreeMasked ? uct_word_child(o[0].first_child) : o[0].first_child);
+    if (rfc < 0 || a < 0 || a >= A || o[rfc + a].count < 0) {
         n_new[r] = 0;
         return;
     }
     int head = 0, tail = 1;
     UctNode first;
-    first.first_child = o[0].first_child + a;
+    first.first_child = rfc + a;
     n[0] = first;
     while (head < tail) {
-        const int oid = n[head].first_child; // (-2: a child of a count-1 node of a tree with unstored groups -- the constant node)
+        const int oid = n[head].first_child; // (-2: a node of the old tree that was never stored -- the constant node)
         UctNode src;
         src.value = 0.0; src.count = 0; src.first_child = -1;
         if (oid >= 0) src = o[oid];
@@ -2396,10 +2471,12 @@ __global__ __launch_bounds__(64) void uct_reroot_kernel(int n_roots, int n_src, 
         out.value = src.value; out.count = src.count; out.first_child = -1;
         if (src.first_child >= 0) {
             out.first_child = tail;
-            const bool unstored = virgin && src.count == 1;
+            const int sfc = virgin == kUctTreeMasked ? uct_word_child(src.first_child) : src.first_child;
             for (int c = 0; c < A; ++c) {
+                const bool unstored = virgin == kUctTreeMasked ? !uct_word_stored(src.first_child, c)
+                                                               : (virgin == kUctTreeCount1 && src.count == 1);
                 UctNode q;
-                q.value = 0.0; q.count = 0; q.first_child = unstored ? -2 : src.first_child + c;
+                q.value = 0.0; q.count = 0; q.first_child = unstored ? -2 : sfc + c;
                 n[tail + c] = q;
             }
             tail += A;
@@ -2514,8 +2591,8 @@ static int uct_reroot_now(mp_ctx *ctx, long cap_new)
     const int old_slot = ctx->tree.buf ? WS_TREE2 : WS_TREE0, new_slot = ctx->tree.buf ? WS_TREE0 : WS_TREE2;
     UctNode *nw = nullptr;
     MP_TRY(ws_get(ctx, new_slot, (size_t)((n_roots + 63) & ~63) * tree_stride_alloc(ctx->tree.il, cap_new, ctx->tree.A), &nw));
-    const int virgin = ctx->tree.virgin ? 1 : 0;
-    ctx->tree.virgin = false; // (the re-rooted trees are whole)
+    const int virgin = ctx->tree.virgin;
+    ctx->tree.virgin = kUctTreeWhole; // (the re-rooted trees are whole, their words plain)
     return reroot_apply(ctx, cap_new, [&](const Reroot &r) {
         hipLaunchKernelGGL(ctx->tree.il == 2 ? uct_reroot_kernel<2> : uct_reroot_kernel<0>, dim3((unsigned)((r.n_roots + 63) / 64)), dim3(64), 0,
                            ctx->stream, r.n_roots, r.n_src, r.A, r.cap_old, r.cap_new, (const UctNode *)ctx->ws[old_slot].p, nw, r.sizes, r.src,
@@ -2540,8 +2617,10 @@ struct UctKnobs {
     int path;         // MP_UCT_PATH: 1 "spill" (the register / global path stack, a test hook), 0 any other value
     long ldsr_waves;  // MP_UCT_LDSR_WAVES (LONG_MIN: not set)
     int tree_stores;  // MP_UCT_TREE_STORES: 0 "lane" (the per-lane tree stores of uct_kernel, for A/B runs), 1 "group" (the wave's
-                      // expansions and the leaf's single store, every zero group stored and loaded), 2 any other value or unset
-                      // (virgin groups neither loaded nor, in fresh trees, stored)
+                      // expansions and the leaf's single store, every zero group stored and loaded), 2 "virgin" (virgin groups
+                      // neither loaded nor, in fresh trees, stored before their first entry: the count-1 rule of uct_virgin.hpp),
+                      // 3 any other value or unset (fresh trees store and load only the children an episode picked: the visited
+                      // mask of uct_virgin.hpp; a form or a tree that cannot keep it runs as 2)
     int balance;      // MP_UCT_BALANCE: 0 runs the LDS-resident form without its wave balance (every rollout at priority 0, for A/B
                       // runs and tests), any other value or unset with it
 };
@@ -2564,7 +2643,7 @@ static UctKnobs uct_knobs_read()
     k.row_waves = uct_knob("MP_UCT_ROW_WAVES"); k.row_roots = uct_knob("MP_UCT_ROW_ROOTS"); k.lanes = uct_knob("MP_UCT_LANES");
     k.cart_rep = uct_knob("MP_UCT_CART_REP"); k.cart_waves = uct_knob("MP_UCT_CART_WAVES");
     const char *tree_stores = getenv("MP_UCT_TREE_STORES");
-    k.tree_stores = tree_stores && !strcmp(tree_stores, "lane") ? 0 : (tree_stores && !strcmp(tree_stores, "group") ? 1 : 2);
+    k.tree_stores = !tree_stores ? 3 : (!strcmp(tree_stores, "lane") ? 0 : (!strcmp(tree_stores, "group") ? 1 : (!strcmp(tree_stores, "virgin") ? 2 : 3)));
     k.balance = uct_knob("MP_UCT_BALANCE") != 0;
     return k;
 }
@@ -2774,9 +2853,16 @@ template <int AT>
 static int uct_launch(const UctChoice &ch, bool listed, const UctArgs &a, hipStream_t st)
 {
     const bool il2 = a.tree_il == 2;
+    [[maybe_unused]] const bool vm = a.tree_stores == 3;   // (uct_trees: fresh trees of a form that keeps the visited mask, and no other plan)
     if constexpr (AT > 0) {
         switch (ch.form) {
         case UF_LDSR:
+            if constexpr (uct_mask_form(AT, ENV_TABLE_LDSR, false, false, 2, false))
+                if (vm) {
+                    if constexpr (uct_balance_form(AT))
+                        if (a.balance) return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, true, true>, ch, a, st);
+                    return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, false, true>, ch, a, st);
+                }
             if constexpr (uct_balance_form(AT))
                 if (a.balance) return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, true>, ch, a, st);
             return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2>, ch, a, st);
@@ -2791,9 +2877,13 @@ static int uct_launch(const UctChoice &ch, bool listed, const UctArgs &a, hipStr
                 return il2 ? uct_go(uct_kernel<AT, ENV_TABLE, true, true, 2>, ch, a, st) : uct_go(uct_kernel<AT, ENV_TABLE, true, true, 0>, ch, a, st);
             return il2 ? uct_go(uct_kernel<AT, ENV_TABLE, true, false, 2>, ch, a, st) : uct_go(uct_kernel<AT, ENV_TABLE, true, false, 0>, ch, a, st);
         case UF_GLOBAL:
+            if constexpr (uct_mask_form(AT, ENV_TABLE, false, false, 2, false))
+                if (il2 && vm) return uct_go(uct_kernel<AT, ENV_TABLE, false, false, 2, false, false, true>, ch, a, st);
             if (il2) return uct_go(uct_kernel<AT, ENV_TABLE, false, false, 2>, ch, a, st);
             break;
         case UF_GLOBAL_SPILL:
+            if constexpr (uct_mask_form(AT, ENV_TABLE_SPILL, false, false, 2, false))
+                if (il2 && vm) return uct_go(uct_kernel<AT, ENV_TABLE_SPILL, false, false, 2, false, false, true>, ch, a, st);
             if (il2) return uct_go(uct_kernel<AT, ENV_TABLE_SPILL, false, false, 2>, ch, a, st);
             break;
         default: break;
@@ -2982,10 +3072,15 @@ static int uct_trees(mp_ctx *ctx, const UctPlan &c, bool cont, const UctChoice &
         MP_TRY(ws_get(ctx, WS_TREE4, (size_t)(H + 1) * (size_t)a->spill_stride, &a->path_spill));
     }
     ctx->tree.kind = 1; ctx->tree.n_roots = n_roots; ctx->tree.A = A; ctx->tree.cap = (int)cap_use;
-    // fresh trees of a form that leaves its virgin groups unstored (uct_kernel's VDEFER, uct_virgin.hpp): the readers apply the rule
+    // fresh trees of a form that leaves zero nodes unstored (uct_kernel's VDEFER and VMASK, uct_virgin.hpp): the readers apply the
+    // rule.  The visited mask needs a form that keeps it, fresh trees and first_child words below 2^24: any other plan runs the
+    // count-1 form (tree_stores 2), as it did before there was a mask.
     const int env = ch.form == UF_LDSR ? ENV_TABLE_LDSR : (ch.form == UF_GLOBAL ? ENV_TABLE : (ch.form == UF_GLOBAL_SPILL ? ENV_TABLE_SPILL : -1));
-    ctx->tree.virgin = !cont && a->tree_stores == 2 && env >= 0 &&
-                       uct_virgin_form(A, env, false, false, ctx->tree.il, false);
+    if (a->tree_stores == 3 && !(!cont && env >= 0 && uct_mask_form(A, env, false, false, ctx->tree.il, false) && cap_use <= kUctChildBits))
+        a->tree_stores = 2;
+    ctx->tree.virgin = kUctTreeWhole;
+    if (!cont && env >= 0 && a->tree_stores == 3) ctx->tree.virgin = kUctTreeMasked;
+    else if (!cont && env >= 0 && a->tree_stores == 2 && uct_virgin_form(A, env, false, false, ctx->tree.il, false)) ctx->tree.virgin = kUctTreeCount1;
     return MP_OK;
 }
 
@@ -3605,7 +3700,7 @@ int mp_uct_path_count(mp_ctx *ctx, int32_t root, const int32_t *actions, int32_t
     MP_TRY(ws_get(ctx, WS_IO1, (size_t)(n > 0 ? n : 1), &d_act));
     MP_TRY(ws_get(ctx, WS_IO8, 1, &d_out));
     if (n > 0) MP_HIP(hipMemcpyAsync(d_act, actions, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    const int tcap = ctx->tree.cap, A = ctx->tree.A, virgin = ctx->tree.virgin ? 1 : 0;
+    const int tcap = ctx->tree.cap, A = ctx->tree.A, virgin = ctx->tree.virgin;
     if (ctx->tree.il == 2) hipLaunchKernelGGL(uct_path_count_kernel<2>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out, virgin);
     else hipLaunchKernelGGL(uct_path_count_kernel<0>, dim3(1), dim3(1), 0, st, trees, root, tcap, A, d_act, n, d_out, virgin);
     MP_HIP(hipGetLastError());
