@@ -122,7 +122,10 @@ def gape_plan(transition, reward, terminal, s0, episodes, horizon, gamma, accura
     """One MDPGapE.plan from state ``s0``.  ``rng``: a numpy Generator (advanced in place).  ``thr_by_count``: the bound's
     threshold by count, ``thr_by_count[count - 1]``.  ``continuation``: "uniform" draws over ALL action ids at a childless
     node, anything else takes action 0; an action that is not listed there gives way to the first listed one.
-    ``observe(kind, values)``: called with every set of numbers the planner compares (for the margin checks).
+    ``observe(kind, values)``: called with every set of numbers the planner compares (for the margin checks), and with what
+    the sweep's contents are read from: "ties" [size of the tie set, rank drawn in it, position drawn among the children] and
+    "continuation" [action drawn, 1 if listed else 0, its column in the listing order]; "arms" [the positions among the root's
+    children of the best arm, the challenger, the selected one, the first largest and the first second-largest value_upper].
     Returns dict(plan, best, challenger, episodes_run, env_steps, error, kind, parent, action, depth, count, cum, mu_ucb,
     mu_lcb, vu, vl, done, state)."""
     observe = observe or (lambda kind, values: None)
@@ -156,6 +159,9 @@ def gape_plan(transition, reward, terminal, s0, episodes, horizon, gamma, accura
         observe("gaps", gaps)
         observe("challenger", [T["vu"][c] for i, c in enumerate(kids) if i != best])
         observe("widths", [T["vu"][kids[i]] - T["vl"][kids[i]] for i in (best, chal)])
+        ups = [T["vu"][c] for c in kids]
+        top1 = max(range(len(kids)), key=lambda i: ups[i])
+        observe("arms", [best, chal, sel, top1, max([i for i in range(len(kids)) if i != top1], key=lambda i: ups[i])])
         return kids[sel], kids[best], kids[chal]
 
     new_node(DECISION, -1, -1, 0, s0)
@@ -179,11 +185,14 @@ def gape_plan(transition, reward, terminal, s0, episodes, horizon, gamma, accura
                 ups = np.array([T["vu"][c] for c in kids])
                 observe("argmax", ups.tolist())
                 ties = np.flatnonzero(ups == np.amax(ups))
-                chance = kids[int(rng.choice(ties))]
+                pick = int(rng.choice(ties))
+                observe("ties", [len(ties), int(np.searchsorted(ties, pick)), pick])
+                chance = kids[pick]
             else:
                 act = int(rng.integers(n_actions)) if continuation == "uniform" else 0
                 expand(node)
                 match = [c for c in children[node] if T["action"][c] == act]
+                observe("continuation", [act, 1 if match else 0, order.index(act) if act in order else -1])
                 chance = match[0] if match else children[node][0]
             act = T["action"][chance]
             r = float(reward[s, act])

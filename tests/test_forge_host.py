@@ -301,6 +301,52 @@ def test_gbopd_restatement_meets_the_forged_rejections(k, n_actions, case):
     assert after(out[0][2]) == out[1][2].record() and out[1][2].rejections >= expect
 
 
+@pytest.mark.parametrize("k,masked", [(k, False) for k in (3, 6, 7, 70, 150)] + [(70, True), (150, True)])
+def test_gape_restatement_meets_the_forged_continuation_draws(k, masked):
+    """MDP-GapE draws its episode's seed (one word) and then, at the childless node below the root, integers(k) over the k
+    environment actions: lead = 1.  Every record of the batch the GPU test plans: numpy's Generator against the prediction."""
+    from tests import gape_cases as gc
+    case, names = gc.forged_continuation_case(k, masked)
+    unlisted = 0
+    for i, (s0, rec) in enumerate(zip(case["roots"], case["rng"])):
+        res, rng_after, seen = gc.restate_plan(case, s0, rec)
+        words, arg, rejections = gc.first_tie(case, s0, rec)
+        assert (words, arg) == (1, k), i
+        if names[i] != "seeded":
+            assert rejections == forge.tie_case_record(names[i], k, salt=i // 6, lead=1)[1], (i, names[i])
+        pred = forge.Stream(rec)
+        pred.below(1 << 30)
+        action, listed, column = [v for kind, v in seen if kind == "continuation"][0]
+        below_root = res["state"][1 + int(case["available"][s0].sum())]     # the first decision node made after the root's arms
+        assert action == column == pred.below(k) and listed == bool(case["available"][below_root, int(action)]), i
+        unlisted += not listed
+        assert res["error"] is None and gc.margin(seen) > gc.MARGIN, i
+    assert {n for n in names} == set(forge.TIE_CASES) - {"reject3"} and (unlisted >= 8) == masked
+
+
+@pytest.mark.parametrize("m", (3, 6, 7, 70, 150))
+def test_gape_restatement_meets_the_forged_tie_draws(m):
+    """With continuation "zeros" the first draw that is no seed draw is random_argmax among the m unvisited children of the node
+    below the root that is visited twice: three seed words come before it (skip = 1 output, lead = 1 word), whatever they are."""
+    from tests import gape_cases as gc
+    case, names, words = gc.forged_tie_case(m)
+    assert words == 3
+    met = set()
+    for i, (s0, rec) in enumerate(zip(case["roots"], case["rng"])):
+        res, rng_after, seen = gc.restate_plan(case, s0, rec)
+        assert gc.first_tie(case, s0, rec)[:2] == (3, m), i
+        size, rank, position = [v for kind, v in seen if kind == "ties" and v[0] > 1][0]
+        pred = forge.Stream(rec)
+        for _ in range(3):
+            pred.below(1 << 30)
+        assert size == m and rank == pred.below(m) and position == rank + 1, i      # (the visited child is the first one)
+        if names[i] != "seeded":
+            assert pred.rejections == forge.tie_case_record(names[i], m, salt=i // 6, lead=1)[1], (i, names[i])
+        met.add(pred.rejections)
+        assert res["error"] is None and gc.margin(seen) > gc.MARGIN, i
+    assert met >= {0, 1, 2}
+
+
 # ---- where the GPU tests put the forged draw -------------------------------------------------------------------------------------
 @pytest.mark.parametrize("k", (3, 6, 7, 70, 150))
 @pytest.mark.parametrize("case", CASES)

@@ -1,6 +1,7 @@
 """MDP-GapE on the host: the test-side restatement against the reference's own outputs (tests/golden/gape.npz, bit for bit, and
-again with a jittered ``log``), the threshold table, the refusals of MDPGapEAgent, the reference's configs, the header -- no GPU
-needed."""
+again with a jittered ``log``), the threshold table, the refusals of MDPGapEAgent, the reference's configs, the header; what the
+sweep of tests/test_gpu_gape_sweep.py contains (tests/gape_cases.py), its share of plans too close to call and the margins of
+the roots the batch tests of tests/test_gpu_gape.py compare -- no GPU needed."""
 import json
 import os
 import re
@@ -11,6 +12,7 @@ import pytest
 from rl_agents_amd import native
 from rl_agents_amd.agents.common.factory import agent_factory
 from rl_agents_amd.envs import FiniteMDPEnv, generators
+from tests import gape_cases as gc
 from tests import gape_restatement as gr
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -253,3 +255,110 @@ def test_header_signatures_and_library_have_the_entry_points():
     for other in (native.kernel_form_names(), native.each_form_names(), native.ss_form_names(), native.olop_stoch_form_names()):
         assert not set(form_names) & set(other)
     assert native.ERR_GAPE_NO_CHALLENGER == -9
+
+
+# ---- the sweep of tests/test_gpu_gape_sweep.py: what it holds, on the restatement alone -----------------------------------------
+@pytest.fixture(scope="module")
+def sweep():
+    """[(case, [(result, generator record after, observations) per root])] of every case."""
+    cases = [gc.sweep_case(i) for i in range(gc.N_CASES)]
+    return [(case, gc.restate_case(case)) for case in cases]
+
+
+def seen_of(plan, kind):
+    return [v for k, v in plan[2] if k == kind]
+
+
+def test_sweep_skips_at_most_the_cap(sweep):
+    """A cap, not a measurement: 7 of 202 plans (3.5 %) have a margin <= 1e-9 -- values that are equal on paper and reached by
+    different arithmetic on the three-valued reward grids, 2e-16 .. 1e-15 apart."""
+    plans = [p for _, restated in sweep for p in restated]
+    close = sum(1 for p in plans if p[0]["error"] is None and gc.margin(p[2]) <= gc.MARGIN)
+    print("sweep: {} plans, {} with margin <= {}".format(len(plans), close, gc.MARGIN))
+    assert len(plans) == gc.N_CASES * gc.ROOTS == 202
+    assert close <= gc.SKIP_CAP * len(plans), close
+
+
+def test_sweep_cases_are_drawn_as_the_docstring_says():
+    for i in range(gc.N_RANDOM):
+        case = gc.sweep_case(i)
+        n_states, n_actions = case["mdp/reward"].shape
+        wide, reward = i % 6 == 5, case["mdp/reward"]
+        assert 2 <= n_states < 40 and (65 <= n_actions < 151 if wide else 2 <= n_actions < 10), i
+        assert reward.min() >= 1e-3 and reward.max() <= 1 - 1e-3, i
+        assert case["available"].all() or i % 3 == 1, i
+        assert np.array_equal(case["order"], np.arange(n_actions)) or i % 6 == 1, i
+        assert int(case["horizon"]) in (gc.WIDE_HORIZONS if wide else gc.HORIZONS), i
+        assert 1 <= int(case["episodes"]) < (6 if int(case["horizon"]) >= 32 else 25), i
+        assert len(case["roots"]) == gc.ROOTS and len({r.tobytes() for r in case["rng"]}) == gc.ROOTS, i
+        again = gc.sweep_case(i)
+        assert all(np.array_equal(case[k], again[k]) for k in case), i
+    rounded = sum(1 for i in range(gc.N_RANDOM) if set(np.unique(gc.sweep_case(i)["mdp/reward"])) <= {0.25, 0.5, 0.75})
+    assert gc.N_RANDOM // 6 <= rounded <= gc.N_RANDOM // 2, rounded
+
+
+def test_sweep_contains_the_cases_it_is_for(sweep):
+    def some(pred):
+        return any(pred(case, plan) for case, restated in sweep for plan in restated)
+
+    def width(case):
+        return case["mdp/reward"].shape[1]
+
+    def masked(case):
+        return not case["available"].all()
+
+    def uniform(case):
+        return str(case["continuation"]) == "uniform"
+    # a mask over more than 64 actions, uniform continuation: an unlisted action drawn (rank 0), and a listed one whose column
+    # lies in the second and in the third chunk with unlisted actions before it
+    assert some(lambda c, p: masked(c) and width(c) > 64 and uniform(c) and any(v[1] == 0 for v in seen_of(p, "continuation")))
+    for first in (64, 128):
+        assert some(lambda c, p: masked(c) and width(c) > 64 and uniform(c)
+                    and any(v[1] == 1 and v[2] >= first for v in seen_of(p, "continuation"))), first
+    assert some(lambda c, p: width(c) > 128)
+    # a tie set of more than 64 members, the drawn one past its 64th and past its 128th (the rank carried over one and two chunks)
+    for rank in (63, 127):
+        assert some(lambda c, p: any(v[0] > 64 and v[1] > rank for v in seen_of(p, "ties"))), rank
+    for horizon in (32, 33, 70):
+        assert some(lambda c, p: int(c["horizon"]) == horizon and p[0]["error"] is None), horizon
+    for continuation in ("uniform", "zeros"):
+        assert some(lambda c, p: masked(c) and str(c["continuation"]) == continuation and p[0]["error"] is None), continuation
+    for on_next in (False, True):
+        assert some(lambda c, p: bool(c["done_on_next"]) == on_next and p[0]["done"].any()), on_next
+    assert some(lambda c, p: p[0]["error"] is None and p[0]["episodes_run"] < int(c["episodes"]) + 2)
+    assert some(lambda c, p: p[0]["error"] is None and p[0]["episodes_run"] == int(c["episodes"]) + 2)
+    assert some(lambda c, p: p[0]["error"] == "one_action" and p[0]["env_steps"] == 0)
+    assert some(lambda c, p: not np.array_equal(c["order"], np.arange(width(c))) and p[0]["error"] is None)
+    assert {str(c["threshold"]) for c, _ in sweep} == {gr.DEFAULT_THRESHOLD, gc.LOG_TIME}
+    assert not any(p[0]["error"] == "range" for _, restated in sweep for p in restated)
+
+
+def test_restatement_reports_its_draws(z):
+    """The observations the contents above are read from, on a golden case whose numbers the golden file holds."""
+    case = golden_case(z, "masked_uniform")
+    res, _, seen = gc.restate_plan(dict(case), int(case["s0"]), case["rng_before"], case_thresholds(case))
+    assert np.array_equal(res["plan"], case["plan"])
+    cont = [v for k, v in seen if k == "continuation"]
+    ties = [v for k, v in seen if k == "ties"]
+    assert sum(1 for v in cont if v[1] == 0) == int(case["unlisted"]) > 0
+    assert sum(1 for v in ties if v[0] > 1) == int(case["tie_draws"]) > 0
+    assert all(0 <= v[1] < v[0] for v in ties) and all(v[2] == v[0] for v in cont)          # (identity order: column = action)
+    assert gc.margin(seen) == pytest.approx(float(case["margin"])) or gc.margin(seen) < float(case["margin"])
+    assert gc.margin(seen) > gc.MARGIN
+
+
+def test_margins_of_the_batch_tests_of_the_device():
+    """The roots that test_300_roots_against_the_restatement and test_more_trees_than_the_workspace_keeps (tests/test_gpu_gape.py)
+    compare with the restatement: no comparison of theirs is closer than 1e-9."""
+    from tests.test_gpu_gape import SMALL_CFG, small_case, small_env
+    env = small_env()
+    for seed, n, sample in ((11, 300, range(300)), (13, 40000, (0, 1, 255, 256, 8192, 8193, 20001, 39999))):
+        agent = agent_factory(env, dict(SMALL_CFG, __class__=GAPE_AGENT))
+        agent.seed(seed)
+        rng = agent.planner.batch_rng_states(n)
+        thr = None
+        for i in sample:
+            case = small_case(i % 12, rng[i])
+            thr = case_thresholds(case) if thr is None else thr
+            res, _, seen = gc.restate_plan(case, i % 12, rng[i], thr)
+            assert res["error"] is None and gc.margin(seen) > gc.MARGIN, (seed, i, gc.margin(seen))

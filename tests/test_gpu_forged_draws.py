@@ -33,6 +33,11 @@ middle); a masked table where k < |A|.
                                                                                                           the episode's seed word)
   BRUE (the rollout's integers(|A|))                                                3, 6, 7, 70, 150      first action draw (same)
   GBOP-D                                                                            3, 6, 7, 70, 150      the sampling rule's first tie
+  MDP-GapE (uniform continuation over k = |A| environment actions; at 70 and 150
+      also under a mask that leaves the forged values unlisted: rank 0)             3, 6, 7, 70, 150      first continuation draw (same)
+  MDP-GapE (continuation "zeros": random_argmax among the m unvisited children
+      of the first node below the root that is visited twice)                       m = 3, 6, 7, 70, 150  the plan's first tie draw (after
+                                                                                                          three seed words: skip 1, lead 1)
   in tests/test_gpu_forged_clone_draws.py:
   stochastic OLOP olop_stoch_dense (one-hot rows, uniform continuation)             3, 6, 7, 70, 150      first continuation draw (after
                                                                                                           the episode's seed word)
@@ -714,3 +719,38 @@ def test_gbopd_tie_draws(ctx, monkeypatch, k):
         assert gr.same_listing(planners.export(i), graph.listing()) == [], i
     planners.close()
     model.close()
+
+
+# ---- MDP-GapE: against the restatement (tests/gape_cases.py builds the cases; tests/test_forge_host.py ties them to numpy) -------
+def check_gape(case, names):
+    from tests import gape_cases as gc
+    from tests.test_gpu_gape import assert_tree
+    from tests.test_gpu_gape_sweep import agent_of, assert_plan, device_tree
+    env, agent = agent_of(case)
+    planner, gamma = agent.planner, float(case["gamma"])
+    rng = case["rng"].copy()
+    out = planner.plan_batch(env, case["roots"], rng_states=rng)
+    assert_form(planner.models.ctx, "gape_global")
+    for i, (res, rng_after, seen) in enumerate(gc.restate_case(case)):
+        assert res["error"] is None and gc.margin(seen) > gc.MARGIN, i
+        assert_plan(out, i, res, rng_after, rng, gamma, i)           # plans, both arms, episodes run, env steps, record, root arms
+        if names[i] in ("reject1", "reject2"):
+            assert_tree(device_tree(planner.models.ctx, i, case["order"]), res, gamma, i)
+
+
+@pytest.mark.parametrize("k,masked", [(k, False) for k in (3, 6, 7, 70, 150)] + [(70, True), (150, True)])
+def test_gape_continuation_draws(monkeypatch, k, masked):
+    """The episode's seed draw takes one word; integers(k) at the childless node below the root the forged ones (lead = 1)."""
+    from tests import gape_cases as gc
+    set_knobs(monkeypatch, "")
+    check_gape(*gc.forged_continuation_case(k, masked))
+
+
+@pytest.mark.parametrize("m", [3, 6, 7, 70, 150])
+def test_gape_tie_draws(monkeypatch, m):
+    """The first random_argmax among two or more: the m unvisited children of a node below the root, after three seed words."""
+    from tests import gape_cases as gc
+    set_knobs(monkeypatch, "")
+    case, names, words = gc.forged_tie_case(m)
+    assert words == 3
+    check_gape(case, names)
