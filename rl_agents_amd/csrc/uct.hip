@@ -34,7 +34,9 @@
 //           that was visited once are all zero nodes: they are not loaded, and a fresh tree does not store them before they are
 //           entered (uct_kernel, VIRGIN GROUPS; uct_virgin.hpp; profiles/uct_virgin_groups.md).  A fresh tree stores only the
 //           children an episode picked and marks them in the upper bits of the parent's first_child: the others are neither
-//           stored nor loaded (uct_kernel, VISITED MASK; profiles/uct_visited_mask.md).
+//           stored nor loaded (uct_kernel, VISITED MASK; profiles/uct_visited_mask.md).  The plan's read-out takes the root and
+//           its children from the registers that hold them and costs one round trip per level below (uct_kernel, READ-OUT FROM
+//           REGISTERS; profiles/uct_step_fixed_costs.md).
 //   path    per-lane stack of visited node ids in LDS ([depth][lane], conflict-free): the backup
 //           walks known addresses, not parent pointers.
 #include <limits.h>
@@ -245,6 +247,11 @@ enum { ENV_TABLE = 0, ENV_CARTPOLE = 2, ENV_TABLE_LDSR = 3, ENV_TABLE_SPILL = 4 
 // of one predicated load per stored child: the dropped sibling stores alone, for A/B runs (profiles/uct_visited_mask.md).
 #ifndef MP_UCT_MASK_LOADS
 #define MP_UCT_MASK_LOADS 1
+#endif
+// -DMP_UCT_READOUT_REGS=0 builds uct_kernel's plan read-out with every value loaded back from the tree, for A/B runs
+// (profiles/uct_step_fixed_costs.md).
+#ifndef MP_UCT_READOUT_REGS
+#define MP_UCT_READOUT_REGS 1
 #endif
 // The instantiations of uct_kernel whose one-lane table rollout runs on Pcg64W: every table form (CartPole draws in its own
 // loops, the four-lane form jumps instead of stepping).
@@ -1531,10 +1538,20 @@ void uct_kernel(UctArgs p)
 #endif
     if (!owner) return;                      // (QD: the helper lanes held no tree)
     if (CART && (lane & ((1 << p.rep_shift) - 1)) != 0) return;   // (replicas of a CartPole root: the first lane reports)
+    // READ-OUT FROM REGISTERS (profiles/uct_step_fixed_costs.md).  The last wave of every SIMD runs what follows alone, every
+    // round trip to memory exposed at the end of the launch.  With the root and its children in registers (RC, tf0 == 1) the root's
+    // word, level 0 of the plan's walk and the root's statistics are taken from them -- no load of what the lines above have just
+    // stored -- and every level below loads each stored child once, picks by selects and stores its action last: one round trip
+    // per level (read-out 20.5 -> 10.2 us per wave, headline step 0.548 -> 0.536 ms).  A re-rooted tree whose root's children
+    // are not at id 1 and the generic |A| keep the loads; so does the four-lane form of |A| >= 7, which spills already and would
+    // spill four VGPRs more (|A| = 7: 8 bytes of scratch, |A| = 8: 4).  -DMP_UCT_READOUT_REGS=0: everything loaded back, for A/B runs.
+    constexpr bool RREG = RC && MP_UCT_READOUT_REGS != 0 && !(QD && AT >= 7);
+    int root_word = -1; // RREG: first_child of the root as stored (VMASK: with the full mask)
     if (RC) {
         UctNode w;
         w.value = tv0; w.count = tc0; w.first_child = tf0;
         if (VMASK && tf0 >= 0) w.first_child = tf0 | (((1 << AR) - 1) << kUctMaskShift); // (all its children are stored below)
+        root_word = w.first_child;
         tree[0] = w;
         if (tf0 == 1) {
 #pragma unroll
@@ -1545,54 +1562,107 @@ void uct_kernel(UctArgs p)
         }
     }
     g.store(p.rng + (long)r * 6);
+    const bool root_regs = RREG && tf0 == 1; // the root's children are tv[] / tc[] / tf[]
     // ---- AbstractPlanner.get_plan (abstract.py:143-156) with MCTSNode.selection_rule
     // (mcts.py:212-218): most visited child, ties -> first maximal value among them
     {
         int len = 0;
-        int fc = tree[0].first_child;
+        int fc = RREG ? root_word : tree[0].first_child;
         int at_c = 0; // VDEFER: the count of the node whose children are read (the root's group is always stored)
+        int32_t *const plan = p.plans ? p.plans + (long)r * p.max_plan_len : nullptr;
+        if (root_regs) {
+            // level 0: the root's children, registers
+            int mc = tc[0];
+#pragma unroll
+            for (int a = 1; a < AR; ++a) mc = max(mc, tc[a]);
+            int best = -1, bfc = -1, bc = 0;
+            double bv = 0.0;
+#pragma unroll
+            for (int a = 0; a < AR; ++a) {
+                const bool take = tc[a] == mc && (best < 0 || tv[a] > bv);
+                best = take ? a : best; bv = take ? tv[a] : bv; bfc = take ? tf[a] : bfc; bc = take ? tc[a] : bc;
+            }
+            if (plan && len < p.max_plan_len) plan[len] = best;
+            ++len;
+            at_c = bc;
+            fc = bfc;
+        }
         while (fc >= 0) {
             if (VDEFER && vdefer && at_c == 1) {
                 // a group that was never stored, all {0.0, 0, -1}: the first action, whose node has no children
-                if (p.plans && len < p.max_plan_len) p.plans[(long)r * p.max_plan_len + len] = 0;
+                if (plan && len < p.max_plan_len) plan[len] = 0;
                 ++len;
                 break;
             }
             // VMASK: a child whose bit in the word is clear was never stored, the constant node
             unsigned stored = ~0u;
             if (VMASK) { stored = (unsigned)fc >> kUctMaskShift; fc &= kUctChildBits; }
-            auto child = [&](int a) {
-                UctNode c;
-                c.value = 0.0; c.count = 0; c.first_child = -1;
-                if (!VMASK || ((stored >> a) & 1u)) c = tree.child(fc, a);
-                return c;
-            };
-            int mc = child(0).count;
-            for (int a = 1; a < A; ++a) mc = max(mc, child(a).count);
-            int best = -1;
-            double bv = 0.0;
-            for (int a = 0; a < A; ++a) {
-                const UctNode c = child(a);
-                if (c.count == mc && (best < 0 || c.value > bv)) { best = a; bv = c.value; }
+            if constexpr (RREG) {
+                // one level: every stored child loaded once, the pick and what the walk needs of it by selects, then the store
+                UctNode *grp = &tree.child(fc, 0);
+                UctNode c[AR];
+#pragma unroll
+                for (int a = 0; a < AR; ++a) {
+                    c[a].value = 0.0; c[a].count = 0; c[a].first_child = -1;
+                    if (!VMASK || ((stored >> a) & 1u)) c[a] = tree.sibling(grp, a);
+                }
+                int mc = c[0].count;
+#pragma unroll
+                for (int a = 1; a < AR; ++a) mc = max(mc, c[a].count);
+                int best = -1, bfc = -1, bc = 0;
+                double bv = 0.0;
+#pragma unroll
+                for (int a = 0; a < AR; ++a) {
+                    const bool take = c[a].count == mc && (best < 0 || c[a].value > bv);
+                    best = take ? a : best; bv = take ? c[a].value : bv; bfc = take ? c[a].first_child : bfc; bc = take ? c[a].count : bc;
+                }
+                if (plan && len < p.max_plan_len) plan[len] = best;
+                ++len;
+                at_c = bc;
+                fc = bfc;
+            } else {
+                auto child = [&](int a) {
+                    UctNode c;
+                    c.value = 0.0; c.count = 0; c.first_child = -1;
+                    if (!VMASK || ((stored >> a) & 1u)) c = tree.child(fc, a);
+                    return c;
+                };
+                int mc = child(0).count;
+                for (int a = 1; a < A; ++a) mc = max(mc, child(a).count);
+                int best = -1;
+                double bv = 0.0;
+                for (int a = 0; a < A; ++a) {
+                    const UctNode c = child(a);
+                    if (c.count == mc && (best < 0 || c.value > bv)) { best = a; bv = c.value; }
+                }
+                if (plan && len < p.max_plan_len) plan[len] = best;
+                ++len;
+                const UctNode b = child(best);
+                at_c = b.count;
+                fc = b.first_child;
             }
-            if (p.plans && len < p.max_plan_len) p.plans[(long)r * p.max_plan_len + len] = best;
-            ++len;
-            const UctNode b = child(best);
-            at_c = b.count;
-            fc = b.first_child;
         }
-        if (p.plans)
-            for (int i = len; i < p.max_plan_len; ++i) p.plans[(long)r * p.max_plan_len + i] = -1;
+        if (plan)
+            for (int i = len; i < p.max_plan_len; ++i) plan[i] = -1;
         if (p.plan_len) p.plan_len[r] = len;
     }
     if (p.n_nodes_out) p.n_nodes_out[r] = n_nodes;
-    if (p.root_value) p.root_value[r] = tree[0].value;
+    if (p.root_value) p.root_value[r] = RREG ? tv0 : tree[0].value;
     if (p.env_steps) p.env_steps[r] = (int64_t)steps_taken;
-    int rfc = tree[0].first_child;
-    if (VMASK) rfc = uct_word_child(rfc); // (the root's children are all stored)
-    for (int a = 0; a < A; ++a) {
-        if (p.root_child_count) p.root_child_count[(long)r * A + a] = rfc >= 0 ? max(tree.child(rfc, a).count, 0) : 0;
-        if (p.root_child_value) p.root_child_value[(long)r * A + a] = rfc >= 0 ? tree.child(rfc, a).value : 0.0;
+    if (root_regs || (RREG && tf0 < 0)) {
+        // the root's children from registers; a root that never expanded has none
+#pragma unroll
+        for (int a = 0; a < AR; ++a) {
+            if (p.root_child_count) p.root_child_count[(long)r * A + a] = tf0 < 0 ? 0 : max(tc[a], 0);
+            if (p.root_child_value) p.root_child_value[(long)r * A + a] = tf0 < 0 ? 0.0 : tv[a];
+        }
+    } else {
+        int rfc = RREG ? tf0 : tree[0].first_child;
+        if (VMASK) rfc = uct_word_child(rfc); // (the root's children are all stored)
+        for (int a = 0; a < A; ++a) {
+            if (p.root_child_count) p.root_child_count[(long)r * A + a] = rfc >= 0 ? max(tree.child(rfc, a).count, 0) : 0;
+            if (p.root_child_value) p.root_child_value[(long)r * A + a] = rfc >= 0 ? tree.child(rfc, a).value : 0.0;
+        }
     }
     WAVE_STAMP(3);
 #undef WAVE_STAMP

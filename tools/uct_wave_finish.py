@@ -48,8 +48,9 @@ def analyse(waves_per_wg, st, out=sys.stdout):
         len(st), waves_per_wg, int(planned.sum()), T / 100.0))
     show("mean wave lifetime / kernel: {:.3f}   launch ramp (entry stamps, last - first): {:.1f} us".format(
         float(((exit_ - entry) / T).mean()), (entry.max() - t0) / 100.0))
-    show("staging (entry -> barrier): mean {:.2f} us, max {:.2f} us; read-out (last episode -> exit): mean {:.2f} us".format(
-        float((staged - entry).mean()) / 100.0, float((staged - entry).max()) / 100.0, float((exit_ - done)[planned].mean()) / 100.0))
+    show("staging (entry -> barrier): mean {:.2f} us, max {:.2f} us; read-out (last episode -> exit): mean {:.2f} us, max {:.2f} us".format(
+        float((staged - entry).mean()) / 100.0, float((staged - entry).max()) / 100.0, float((exit_ - done)[planned].mean()) / 100.0,
+        float((exit_ - done)[planned].max()) / 100.0))
     cu_key = ((xcc * 8 + se) * 2 + sh) * 16 + cu
     wgs_per_cu = len(set(zip(cu_key.tolist(), wg.tolist()))) / float(len(set(cu_key.tolist())))
     show("CUs used {}, workgroups per CU {:.2f}".format(len(set(cu_key.tolist())), wgs_per_cu))
@@ -71,6 +72,12 @@ def analyse(waves_per_wg, st, out=sys.stdout):
             within.append(f.max() - f.min())
         first_in_simd.append(f.min())
         last_in_simd.append(f.max())
+    # the tail: from the moment the first SIMD has no episode left to run (the last of its waves stamped `done`) to the last exit
+    simd_done = [max(done[i] for i in idx) for idx in groups.values()]
+    last_wave = [max(idx, key=lambda i: exit_[i]) for idx in groups.values()]
+    show("first SIMD out of episodes at {:.3f} of the kernel: {:.3f} of it ({:.1f} us) lies behind; read-out of the last wave of a "
+         "SIMD: mean {:.2f} us".format((min(simd_done) - t0) / T, (t1 - min(simd_done)) / T, (t1 - min(simd_done)) / 100.0,
+                                       float(np.mean([exit_[i] - done[i] for i in last_wave])) / 100.0))
     show("\nfinish time (share of the kernel) by age rank within the SIMD, SIMDs that hold {} waves; rank 0 entered first".format(top))
     show("  XCD   " + "  ".join("rank {}".format(k) for k in range(top)) + "    SIMDs")
     for x in sorted(set(xcc.tolist())) + [-1]:
