@@ -336,6 +336,14 @@ int64_t mp_vi_graph_captures(mp_ctx *ctx);
  *     2 in pieces of 8192; [12] column segments of the matrix-core form, [13] columns per segment.
  * The other half of `out` is zero. */
 int mp_vi_geometry(int32_t mode, int32_t S, int32_t A, int32_t M, int32_t Sc, int32_t cus, int64_t *out);
+/* The kernel form mp_vi_solve_batch chooses for N MDPs of Sb states and A actions on a device of `cus` compute units (host only;
+ * the solve launches from the same function).  The MP_VI_BATCH_* knobs are read from the environment as the solve reads them.
+ *   out int64 [7]: [0] form (0 register, 1 cluster, 2 streaming workgroup, 3 LDS workgroup, 4 global-memory workgroup),
+ *                  [1] the compile-time |A| (0: the loop form), [2] states a thread keeps in registers (0: none), [3] threads per
+ *                  workgroup, [4] workgroups per MDP, [5] workgroups of the launch, [6] dynamic LDS bytes.
+ *   *name:         the form, as mp_last_kernel_variant names it (static storage).
+ * MP_ERR_ARG for a NULL argument or a size below 1; iterations may be 0. */
+int mp_vi_batch_geometry(int32_t N, int32_t Sb, int32_t A, int32_t iterations, int32_t cus, int64_t *out, const char **name);
 
 /* ---------------------------------------------------------------- UCT ----------------------- */
 /*

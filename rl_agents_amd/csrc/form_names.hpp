@@ -3,6 +3,7 @@
 // same functions over their selector ranges.  Host only.  A name fits mp_ctx::last_variant (kFormNameBytes with the NUL).
 #pragma once
 #include <stdio.h>
+#include <string.h>
 
 #include <string>
 
@@ -40,6 +41,8 @@ inline const char *uct_form_name_static(int form)
 // the register forms of the batched VI: states per thread, threads per workgroup
 constexpr int kViBatchRegForms = 7;
 constexpr int kViBatchReg[kViBatchRegForms][2] = {{1, 64}, {2, 64}, {2, 128}, {2, 256}, {4, 256}, {4, 512}, {4, 1024}};
+// (entry i is instantiated for the compile-time |A| `at`: four states of 1024 threads hold the rows of at most four actions)
+constexpr bool vi_batch_reg_exists(int at, int i) { return at > 0 && (kViBatchReg[i][1] < 1024 || at <= 4); }
 inline FormName vi_batch_reg_name(int own, int block)
 {
     FormName n;
@@ -59,6 +62,23 @@ inline FormName vi_batch_wg_name(int kind)
     FormName n;
     snprintf(n.s, sizeof(n.s), "vi_batch_wg_%s", name[kind]);
     return n;
+}
+// (one of the 13 names above in static storage: mp_vi_batch_geometry hands out a pointer)
+inline const char *vi_batch_form_name_static(const FormName &n)
+{
+    static const struct Names {
+        FormName n[kViBatchRegForms + 3 + VB_WG_COUNT];
+        Names()
+        {
+            int i = 0;
+            for (const auto &f : kViBatchReg) n[i++] = vi_batch_reg_name(f[0], f[1]);
+            for (int k = 2; k <= 8; k *= 2) n[i++] = vi_batch_cluster_name(k);
+            for (int k = 0; k < VB_WG_COUNT; ++k) n[i++] = vi_batch_wg_name(k);
+        }
+    } names;
+    for (const FormName &s : names.n)
+        if (!strcmp(s.s, n.s)) return s.s;
+    return "";
 }
 
 inline FormName slots_form_name(const char *planner, bool keep) // OLOP, BRUE: the trees kept for export, or slots shared by waves

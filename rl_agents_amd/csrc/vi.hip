@@ -1423,6 +1423,24 @@ struct ViBatchArgs {
     unsigned *gave_up;    // cluster form: [N], raised by any workgroup of the MDP's cluster that left by the give-up exit
 };
 
+// The rows a thread of the two register-resident forms below (vi_det_batch_reg, vi_det_batch_cluster) keeps of state s for the
+// whole solve, next states relative to the MDP's first, and Q_0 = 0.  own: s lies below `end`, the thread has such a state (one
+// that has none reads row 0 of the MDP, and nothing it computes counts).
+template <int AT>
+__device__ __forceinline__ void vi_batch_row_load(const ViBatchArgs &p, long base, int s, int end, int32_t (&t)[AT], double (&r)[AT],
+                                                  double (&qp)[AT], bool &term_s, bool &own)
+{
+    own = s < end;
+    const long sa0 = (base + (own ? s : 0)) * AT;
+    term_s = (p.term && own) ? p.term[base + s] != 0 : false;
+#pragma unroll
+    for (int a = 0; a < AT; ++a) {
+        t[a] = p.T[sa0 + a] - (int32_t)base;
+        r[a] = p.R[sa0 + a];
+        qp[a] = 0.0;                                  // Q_0 = 0 (value_iteration.py:43)
+    }
+}
+
 // REGISTER form (Sb <= OWN * BLOCK): a thread keeps the rows of its OWN states -- transitions, rewards and the last Q row,
 // which is what the allclose test compares with -- in registers for the whole solve; V is double-buffered in LDS; one
 // barrier per sweep (it also carries the "did anything move" vote).
@@ -1439,15 +1457,7 @@ __global__ __launch_bounds__(BLOCK) void vi_det_batch_reg(ViBatchArgs p)
 #pragma unroll
     for (int i = 0; i < OWN; ++i) {
         const int s = tid + i * BLOCK;
-        own[i] = s < S;
-        const long sa0 = (base + (own[i] ? s : 0)) * AT;
-        term_s[i] = (p.term && own[i]) ? p.term[base + s] != 0 : false;
-#pragma unroll
-        for (int a = 0; a < AT; ++a) {
-            t[i][a] = p.T[sa0 + a] - (int32_t)base;
-            r[i][a] = p.R[sa0 + a];
-            qp[i][a] = 0.0;                                  // Q_0 = 0 (value_iteration.py:43)
-        }
+        vi_batch_row_load<AT>(p, base, s, S, t[i], r[i], qp[i], term_s[i], own[i]);
         if (own[i]) V0[s] = 0.0;
     }
     __syncthreads();
@@ -1531,18 +1541,7 @@ __global__ __launch_bounds__(1024) void vi_det_batch_cluster(ViBatchArgs p, int 
     double r[OWN][AT], qp[OWN][AT];
     bool term_s[OWN], own[OWN];
 #pragma unroll
-    for (int i = 0; i < OWN; ++i) {
-        const int s = s_lo + tid + i * NT;
-        own[i] = s < s_hi;
-        const long sa0 = (base + (own[i] ? s : 0)) * AT;
-        term_s[i] = (p.term && own[i]) ? p.term[base + s] != 0 : false;
-#pragma unroll
-        for (int a = 0; a < AT; ++a) {
-            t[i][a] = p.T[sa0 + a] - (int32_t)base;
-            r[i][a] = p.R[sa0 + a];
-            qp[i][a] = 0.0;                                  // Q_0 = 0 (value_iteration.py:43)
-        }
-    }
+    for (int i = 0; i < OWN; ++i) vi_batch_row_load<AT>(p, base, s_lo + tid + i * NT, s_hi, t[i], r[i], qp[i], term_s[i], own[i]);
     for (int i = tid; i < S; i += NT) V0[i] = 0.0;
     __syncthreads();
     int sweeps = p.iterations;
@@ -1849,106 +1848,212 @@ __global__ __launch_bounds__(1024) void vi_det_batch_wgr(ViBatchArgs p, const ui
     }
 }
 
-template <int AT>
-static int vi_batch_launch(mp_ctx *ctx, ViBatchArgs &q, hipStream_t st, FormName *variant)
+// Which of the 13 forms a batched solve takes, shared with mp_vi_batch_geometry: no HIP call, no mp_ctx.
+// The knobs, read from the environment once per call (tests change them between the calls of one process).
+struct ViBatchKnobs {
+    bool no_reg, no_wgr, no_vlds;              // MP_VI_BATCH_NO_REG, MP_VI_BATCH_NO_WGR, MP_VI_BATCH_NO_VLDS
+    int cluster;                               // MP_VI_BATCH_CLUSTER: 0 unset; 2, 4, 8 forced; 1 (any other value) one workgroup per MDP
+    // test hooks of the cluster form.  MP_VI_BATCH_CLUSTER_NEVER_MEETS=1: every cluster waits for one arrival too many and gives
+    // up after a short spin; MP_VI_BATCH_CLUSTER_GIVE_UP=part,sweep[,mdp]: that one workgroup of the cluster gives up after its
+    // arrival at that sweep (short spins for every workgroup, so that its partners' later waits end soon)
+    bool never_meets;
+    int give_part, give_sweep, give_mdp;       // (-1: none / every MDP)
+};
+static ViBatchKnobs vi_batch_knobs()
 {
-    const int S = q.Sb;
-    const unsigned grid = (unsigned)q.N;
-    if constexpr (AT > 0) {
-        const size_t lds = (size_t)2 * S * sizeof(double);
-#define MP_VB(own, block)                                                                                              \
-    if (S <= (own) * (block)) {                                                                                        \
-        hipLaunchKernelGGL((vi_det_batch_reg<AT, own, block>), dim3(grid), dim3(block), lds, st, q);                   \
-        *variant = vi_batch_reg_name(own, block);                                                                   \
-        return MP_OK;                                                                                                  \
+    ViBatchKnobs k = {};
+    k.no_reg = getenv("MP_VI_BATCH_NO_REG") != nullptr;
+    k.no_wgr = getenv("MP_VI_BATCH_NO_WGR") != nullptr;
+    k.no_vlds = getenv("MP_VI_BATCH_NO_VLDS") != nullptr;
+    if (const char *e = getenv("MP_VI_BATCH_CLUSTER")) {
+        const int v = atoi(e);
+        k.cluster = v == 2 || v == 4 || v == 8 ? v : 1;
     }
-        if (!getenv("MP_VI_BATCH_NO_REG")) {
-            MP_VB(1, 64) MP_VB(2, 64) MP_VB(2, 128) MP_VB(2, 256) MP_VB(4, 256) MP_VB(4, 512)
-            if constexpr (AT <= 4) { MP_VB(4, 1024) }
+    k.never_meets = getenv("MP_VI_BATCH_CLUSTER_NEVER_MEETS") != nullptr;
+    k.give_part = k.give_sweep = k.give_mdp = -1;
+    if (const char *e = getenv("MP_VI_BATCH_CLUSTER_GIVE_UP"))
+        if (sscanf(e, "%d,%d,%d", &k.give_part, &k.give_sweep, &k.give_mdp) < 2) k.give_part = -1;
+    return k;
+}
+
+// V_k and V_{k+1} of one MDP in dynamic LDS, and `extra` bytes behind them.  A kernel's static LDS (__syncthreads_or's scratch, 256
+// bytes) comes on top of the dynamic size: hence the margin (without it the cluster form at S = 10 224 .. 10 239 failed in
+// hipFuncSetAttribute instead of taking another form).
+static size_t vi_batch_lds(int Sb, size_t extra) { return (size_t)2 * Sb * sizeof(double) + extra; }
+static bool vi_batch_lds_fits(int Sb, size_t extra) { return vi_batch_lds(Sb, extra) <= kLdsBytes - 512; }
+
+enum ViBatchKind { VBF_REG, VBF_CLUSTER, VBF_WG_STREAM, VBF_WG_LDS, VBF_WG_GLOBAL };
+struct ViBatchGeom {
+    int form;                    // ViBatchKind
+    int at;                      // the compile-time |A|, 0 = the loop form (VBF_WG_LDS and VBF_WG_GLOBAL only)
+    int own, block, k;           // states a thread keeps in registers (0: none), threads per workgroup, workgroups per MDP
+    unsigned grid;
+    size_t lds;                  // dynamic LDS bytes
+    FormName name;
+};
+// The first rung that holds is taken.
+static ViBatchGeom vi_batch_geometry(int cus, int N, int Sb, int A, int iterations, const ViBatchKnobs &knobs)
+{
+    ViBatchGeom g = {};
+    g.at = vi_det_unrolled(A);
+    g.block = 1024; g.k = 1; g.grid = (unsigned)N; g.lds = vi_batch_lds(Sb, 0);
+    if (!knobs.no_reg)
+        for (int i = 0; i < kViBatchRegForms; ++i)
+            if (vi_batch_reg_exists(g.at, i) && Sb <= kViBatchReg[i][0] * kViBatchReg[i][1]) {
+                g.form = VBF_REG; g.own = kViBatchReg[i][0]; g.block = kViBatchReg[i][1];
+                g.name = vi_batch_reg_name(g.own, g.block);
+                return g;
+            }
+    if (g.at > 0 && g.at <= 6 && iterations > 0) {
+        // the batch leaves CUs idle with one workgroup per MDP -> K = 2, 4 or 8 workgroups per MDP, at most one per CU (each takes a
+        // CU's LDS: co-resident by construction on an otherwise idle device), each thread owning <= 3 states
+        int K = knobs.cluster;
+        if (K == 0)
+            for (K = 1; K < 8 && (long)N * (K * 2) <= cus;) K *= 2;
+        const int own = ((Sb + K - 1) / K + 1023) / 1024;
+        if (K > 1 && own <= 3 && vi_batch_lds_fits(Sb, 16)) {           // (16 bytes: the verdict, double-buffered)
+            g.form = VBF_CLUSTER; g.own = own; g.k = K; g.grid = (unsigned)((N + 7) / 8) * 8 * K; g.lds = vi_batch_lds(Sb, 16);
+            g.name = vi_batch_cluster_name(K);
+            return g;
         }
-#undef MP_VB
     }
-    if constexpr (AT > 0 && AT <= 6) {
-        // CLUSTER form: the batch leaves CUs idle with one workgroup per MDP -> K = 2, 4 or 8 workgroups per MDP, at most one per CU
-        // (each takes a CU's LDS: co-resident by construction on an otherwise idle device), each thread owning <= 3 states
-        const long cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-        int K = 1;
-        while (K < 8 && (long)q.N * (K * 2) <= cus) K *= 2;
-        if (const char *e = getenv("MP_VI_BATCH_CLUSTER")) K = atoi(e);    // 0 / 1: off; 2, 4, 8: forced
-        const int own = K > 1 ? ((S + K - 1) / K + 1023) / 1024 : 99;
-        // (the kernel's static LDS -- __syncthreads_or's scratch, 256 bytes -- comes on top of the dynamic size: the same margin as
-        // the other LDS forms; without it S = 10 224 .. 10 239 failed in hipFuncSetAttribute instead of taking another form)
-        const size_t lds = (size_t)2 * S * sizeof(double) + 16;
-        if (K > 1 && K <= 8 && own <= 3 && lds <= kLdsBytes - 512 && q.iterations > 0) {
-            double *Vx = nullptr;
-            unsigned *words = nullptr;
-            MP_TRY(ws_get(ctx, WS_VI1, (size_t)q.N * 3 * S, &Vx));          // (the cluster uses [N][2][S]; the fallback [N][3][S])
-            // one word per (MDP, sweep), then one give-up word per MDP: all cleared by every call
-            MP_TRY(ws_get(ctx, WS_VI3, (size_t)q.N * q.iterations + q.N, &words));
-            MP_HIP(hipMemsetAsync(words, 0, ((size_t)q.N * q.iterations + q.N) * sizeof(unsigned), st));
-            q.gave_up = words + (size_t)q.N * q.iterations;
-            const unsigned cgrid = (unsigned)((q.N + 7) / 8) * 8 * K;
-            // test hooks: MP_VI_BATCH_CLUSTER_NEVER_MEETS=1: every cluster waits for one arrival too many and gives up after a
-            // short spin; MP_VI_BATCH_CLUSTER_GIVE_UP=part,sweep[,mdp]: that one workgroup of the cluster gives up after its
-            // arrival at that sweep (short spins for every workgroup, so that its partners' later waits end soon)
-            const bool hook = getenv("MP_VI_BATCH_CLUSTER_NEVER_MEETS") != nullptr;
-            int give_part = -1, give_sweep = -1, give_mdp = -1;
-            if (const char *e = getenv("MP_VI_BATCH_CLUSTER_GIVE_UP"))
-                if (sscanf(e, "%d,%d,%d", &give_part, &give_sweep, &give_mdp) < 2) give_part = -1;
-            const unsigned need = (unsigned)K + (hook ? 1u : 0u), spin = hook || give_part >= 0 ? 2000u : kSpinLimit;
+    if (Sb <= kViBatchOwn * 1024 && vi_batch_lds_fits(Sb, 0) && !knobs.no_vlds) {
+        const bool stream = g.at > 0 && !knobs.no_wgr;
+        g.form = stream ? VBF_WG_STREAM : VBF_WG_LDS;
+        g.name = vi_batch_wg_name(stream ? VB_WG_STREAM : VB_WG_LDS);
+        return g;
+    }
+    g.form = VBF_WG_GLOBAL; g.lds = 0;
+    g.name = vi_batch_wg_name(VB_WG_GLOBAL);
+    return g;
+}
+
+// Dynamic LDS beyond 64 KiB has to be asked for, once per kernel; at or below it nothing is called.
+template <class Kernel>
+static int vi_batch_allow_lds(Kernel *kernel, size_t lds)
+{
+    if (lds > 64 * 1024) MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    return MP_OK;
+}
+
+// f(the compile-time |A| of g.at as a std::integral_constant).  Every launcher below names the |A| its kernel is instantiated for.
+template <class F>
+static int vi_batch_with_at(int at, F &&f)
+{
+    switch (at) {
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 5: return f(std::integral_constant<int, 5>());
+    case 6: return f(std::integral_constant<int, 6>());
+    case 8: return f(std::integral_constant<int, 8>());
+    default: return f(std::integral_constant<int, 0>());
+    }
+}
+static int vi_batch_no_kernel(const ViBatchGeom &g) { return fail(MP_ERR_ARG, "mp_vi_solve_batch: no kernel %s for |A| = %d", g.name.s, g.at); }
+
+// the register forms, instantiated from kViBatchReg: entry I launches if it is the one chosen (*rc: how that went)
+template <int AT, int I>
+static bool vi_batch_launch_reg_if(const ViBatchArgs &q, const ViBatchGeom &g, hipStream_t st, int *rc)
+{
+    constexpr int OWN = kViBatchReg[I][0], BLOCK = kViBatchReg[I][1];
+    if constexpr (vi_batch_reg_exists(AT, I)) {
+        if (g.own != OWN || g.block != BLOCK) return false;
+        *rc = vi_batch_allow_lds(vi_det_batch_reg<AT, OWN, BLOCK>, g.lds);
+        if (*rc == MP_OK) hipLaunchKernelGGL((vi_det_batch_reg<AT, OWN, BLOCK>), dim3(g.grid), dim3(BLOCK), g.lds, st, q);
+        return true;
+    }
+    return false;
+}
+template <int AT, int... I>
+static bool vi_batch_launch_reg_any(const ViBatchArgs &q, const ViBatchGeom &g, hipStream_t st, int *rc, std::integer_sequence<int, I...>)
+{
+    return (vi_batch_launch_reg_if<AT, I>(q, g, st, rc) || ...);
+}
+static int vi_batch_launch_reg(const ViBatchArgs &q, const ViBatchGeom &g, hipStream_t st)
+{
+    return vi_batch_with_at(g.at, [&](auto at) -> int {
+        int rc = MP_OK;
+        const bool found = vi_batch_launch_reg_any<decltype(at)::value>(q, g, st, &rc, std::make_integer_sequence<int, kViBatchRegForms>());
+        return found ? rc : vi_batch_no_kernel(g);
+    });
+}
+
+static int vi_batch_launch_cluster(mp_ctx *ctx, ViBatchArgs &q, const ViBatchGeom &g, const ViBatchKnobs &knobs, hipStream_t st)
+{
+    const int S = q.Sb, K = g.k;
+    double *Vx = nullptr;
+    unsigned *words = nullptr;
+    MP_TRY(ws_get(ctx, WS_VI1, (size_t)q.N * 3 * S, &Vx));          // (the cluster uses [N][2][S]; the fallback [N][3][S])
+    // one word per (MDP, sweep), then one give-up word per MDP: all cleared by every call
+    MP_TRY(ws_get(ctx, WS_VI3, (size_t)q.N * q.iterations + q.N, &words));
+    MP_HIP(hipMemsetAsync(words, 0, ((size_t)q.N * q.iterations + q.N) * sizeof(unsigned), st));
+    q.gave_up = words + (size_t)q.N * q.iterations;
+    const bool hooked = knobs.never_meets || knobs.give_part >= 0;
+    const unsigned need = (unsigned)K + (knobs.never_meets ? 1u : 0u), spin = hooked ? 2000u : kSpinLimit;
+    return vi_batch_with_at(g.at, [&](auto at) -> int {
+        constexpr int AT = decltype(at)::value;
+        if constexpr (AT > 0 && AT <= 6) {
 #define MP_VC(o)                                                                                                            \
-    {                                                                                                                       \
-        MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vi_det_batch_cluster<AT, o>),                             \
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                                 \
-        hipLaunchKernelGGL((vi_det_batch_cluster<AT, o>), dim3(cgrid), dim3(1024), lds, st, q, K, Vx, words, need, spin,   \
-                           give_part, give_sweep, give_mdp);                                                                \
+    if (g.own == o) {                                                                                                       \
+        MP_TRY(vi_batch_allow_lds(vi_det_batch_cluster<AT, o>, g.lds));                                                     \
+        hipLaunchKernelGGL((vi_det_batch_cluster<AT, o>), dim3(g.grid), dim3(1024), g.lds, st, q, K, Vx, words, need, spin, \
+                           knobs.give_part, knobs.give_sweep, knobs.give_mdp);                                              \
     }
-            if (own == 1) MP_VC(1) else if (own == 2) MP_VC(2) else MP_VC(3)
+            MP_VC(1) MP_VC(2) MP_VC(3)
 #undef MP_VC
             // clusters with a raised give-up word (a busy device): solved again, Q and sweep count, by the global-memory workgroup
             // form (which returns at once for every other MDP)
             ViBatchArgs f = q;
             f.only_failed = 1; f.Vglobal = Vx;
-            hipLaunchKernelGGL((vi_det_batch_wg<AT, false>), dim3(grid), dim3(1024), 0, st, f);
-            *variant = vi_batch_cluster_name(K);
+            hipLaunchKernelGGL((vi_det_batch_wg<AT, false>), dim3((unsigned)q.N), dim3(1024), 0, st, f);
             return MP_OK;
         }
-    }
-    if constexpr (AT > 0) {
-        if (S <= kViBatchOwn * 1024 && (size_t)2 * S * sizeof(double) <= kLdsBytes - 512 && !getenv("MP_VI_BATCH_NO_VLDS") &&
-            !getenv("MP_VI_BATCH_NO_WGR")) {
-            // lane-major copies of the tables (a few microseconds; rebuilt on every call: the tables of a batch change
-            // between two steps of its episodes)
-            const size_t npairs = (size_t)q.N * S * AT;
-            uint16_t *Tt = nullptr;
-            double *Rt = nullptr;
-            MP_TRY(ws_get(ctx, WS_VI2, npairs, &Rt));
-            MP_TRY(ws_get(ctx, WS_VI4, npairs, &Tt));
-            MP_TRY(ws_get(ctx, WS_VI1, (size_t)q.N * 3 * S, &q.Vglobal));
-            hipLaunchKernelGGL(vi_batch_transpose, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, q.N, S, AT, q.T, q.R, q.term, Tt, Rt);
-            const size_t lds = (size_t)2 * S * sizeof(double);
-            MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vi_det_batch_wgr<AT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds));
-            hipLaunchKernelGGL((vi_det_batch_wgr<AT>), dim3(grid), dim3(1024), lds, st, q, (const uint16_t *)Tt, (const double *)Rt);
-            *variant = vi_batch_wg_name(VB_WG_STREAM);
-            return MP_OK;
-        }
-    }
-    if (S <= kViBatchOwn * 1024 && (size_t)2 * S * sizeof(double) <= kLdsBytes - 512 && !getenv("MP_VI_BATCH_NO_VLDS")) {
-        const size_t lds = (size_t)2 * S * sizeof(double);
-        if (lds > 64 * 1024)
-            MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(vi_det_batch_wg<AT, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds));
-        hipLaunchKernelGGL((vi_det_batch_wg<AT, true>), dim3(grid), dim3(1024), lds, st, q);
-        *variant = vi_batch_wg_name(VB_WG_LDS);
-        return MP_OK;
-    }
-    MP_TRY(ws_get(ctx, WS_VI1, (size_t)q.N * 3 * S, &q.Vglobal));
-    hipLaunchKernelGGL((vi_det_batch_wg<AT, false>), dim3(grid), dim3(1024), 0, st, q);
-    *variant = vi_batch_wg_name(VB_WG_GLOBAL);
-    return MP_OK;
+        return vi_batch_no_kernel(g);
+    });
 }
 
+static int vi_batch_launch_stream(mp_ctx *ctx, ViBatchArgs &q, const ViBatchGeom &g, hipStream_t st)
+{
+    // lane-major copies of the tables (a few microseconds; rebuilt on every call: the tables of a batch change between two steps
+    // of its episodes)
+    const size_t npairs = (size_t)q.N * q.Sb * g.at;
+    uint16_t *Tt = nullptr;
+    double *Rt = nullptr;
+    MP_TRY(ws_get(ctx, WS_VI2, npairs, &Rt));
+    MP_TRY(ws_get(ctx, WS_VI4, npairs, &Tt));
+    MP_TRY(ws_get(ctx, WS_VI1, (size_t)q.N * 3 * q.Sb, &q.Vglobal));
+    hipLaunchKernelGGL(vi_batch_transpose, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, st, q.N, q.Sb, g.at, q.T, q.R, q.term, Tt, Rt);
+    return vi_batch_with_at(g.at, [&](auto at) -> int {
+        constexpr int AT = decltype(at)::value;
+        if constexpr (AT > 0) {
+            MP_TRY(vi_batch_allow_lds(vi_det_batch_wgr<AT>, g.lds));
+            hipLaunchKernelGGL((vi_det_batch_wgr<AT>), dim3(g.grid), dim3(1024), g.lds, st, q, (const uint16_t *)Tt, (const double *)Rt);
+            return MP_OK;
+        }
+        return vi_batch_no_kernel(g);
+    });
+}
+
+static int vi_batch_launch_lds(const ViBatchArgs &q, const ViBatchGeom &g, hipStream_t st)
+{
+    return vi_batch_with_at(g.at, [&](auto at) -> int {
+        constexpr int AT = decltype(at)::value;
+        MP_TRY(vi_batch_allow_lds(vi_det_batch_wg<AT, true>, g.lds));
+        hipLaunchKernelGGL((vi_det_batch_wg<AT, true>), dim3(g.grid), dim3(1024), g.lds, st, q);
+        return MP_OK;
+    });
+}
+
+static int vi_batch_launch_global(mp_ctx *ctx, ViBatchArgs &q, const ViBatchGeom &g, hipStream_t st)
+{
+    MP_TRY(ws_get(ctx, WS_VI1, (size_t)q.N * 3 * q.Sb, &q.Vglobal));
+    return vi_batch_with_at(g.at, [&](auto at) -> int {
+        constexpr int AT = decltype(at)::value;
+        hipLaunchKernelGGL((vi_det_batch_wg<AT, false>), dim3(g.grid), dim3(1024), 0, st, q);
+        return MP_OK;
+    });
+}
 static int vi_solve_batch(mp_ctx *ctx, mp_model *m, double gamma, int iterations, double rtol, double atol, double *Q_out,
                           int32_t *sweeps_out, int mem)
 {
@@ -1969,19 +2074,19 @@ static int vi_solve_batch(mp_ctx *ctx, mp_model *m, double gamma, int iterations
     memset(&q, 0, sizeof(q));
     q.N = N; q.Sb = Sb; q.A = A; q.iterations = iterations; q.T = m->T; q.R = m->R; q.term = m->term;
     q.gamma = gamma; q.rtol = rtol; q.atol = atol; q.Q_out = dQ; q.sweeps_out = dSw;
-    FormName variant = {""};
+    const ViBatchKnobs knobs = vi_batch_knobs();
+    const int cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+    const ViBatchGeom g = vi_batch_geometry(cus, N, Sb, A, iterations, knobs);
     MP_TRY(kernels_begin(ctx));
-    switch (A) {
-    case 2: MP_TRY(vi_batch_launch<2>(ctx, q, st, &variant)); break;
-    case 3: MP_TRY(vi_batch_launch<3>(ctx, q, st, &variant)); break;
-    case 4: MP_TRY(vi_batch_launch<4>(ctx, q, st, &variant)); break;
-    case 5: MP_TRY(vi_batch_launch<5>(ctx, q, st, &variant)); break;
-    case 6: MP_TRY(vi_batch_launch<6>(ctx, q, st, &variant)); break;
-    case 8: MP_TRY(vi_batch_launch<8>(ctx, q, st, &variant)); break;
-    default: MP_TRY(vi_batch_launch<0>(ctx, q, st, &variant)); break;
+    switch (g.form) {
+    case VBF_REG: MP_TRY(vi_batch_launch_reg(q, g, st)); break;
+    case VBF_CLUSTER: MP_TRY(vi_batch_launch_cluster(ctx, q, g, knobs, st)); break;
+    case VBF_WG_STREAM: MP_TRY(vi_batch_launch_stream(ctx, q, g, st)); break;
+    case VBF_WG_LDS: MP_TRY(vi_batch_launch_lds(q, g, st)); break;
+    default: MP_TRY(vi_batch_launch_global(ctx, q, g, st)); break;
     }
     MP_TRY(kernels_end(ctx, 1));
-    form_record(ctx->last_variant, variant);
+    form_record(ctx->last_variant, g.name);
     MP_HIP(hipGetLastError());
     MP_TRY(stage_out_copy(ctx, Q_out, dQ, nq, mem));
     MP_TRY(stage_out_copy(ctx, sweeps_out, dSw, (size_t)N, mem));
@@ -2097,6 +2202,17 @@ int mp_vi_geometry(int32_t mode, int32_t S, int32_t A, int32_t M, int32_t Sc, in
     const mp::ViExactGeom g = mp::vi_exact_geometry(Sc, (int)lv.size() / 2, (int)nd.size() / 2, (int)ho.size() - 1, (int)pc.size() - 1, nb);
     out[6] = nb; out[7] = g.nbt; out[8] = g.nw; out[9] = (int64_t)g.fixed; out[10] = g.vm_default; out[11] = g.vm;
     out[12] = mp::vi_dense_segments(Sc); out[13] = out[12] > 1 ? mp::kDenseSegCols : Sc;
+    return MP_OK;
+}
+
+int mp_vi_batch_geometry(int32_t N, int32_t Sb, int32_t A, int32_t iterations, int32_t cus, int64_t *out, const char **name)
+{
+    if (!out || !name) return mp::fail(MP_ERR_ARG, "mp_vi_batch_geometry: NULL argument");
+    if (N < 1 || Sb < 1 || A < 1 || cus < 1 || iterations < 0)
+        return mp::fail(MP_ERR_ARG, "mp_vi_batch_geometry: sizes must be positive (iterations may be 0)");
+    const mp::ViBatchGeom g = mp::vi_batch_geometry(cus, N, Sb, A, iterations, mp::vi_batch_knobs());
+    out[0] = g.form; out[1] = g.at; out[2] = g.own; out[3] = g.block; out[4] = g.k; out[5] = g.grid; out[6] = (int64_t)g.lds;
+    *name = mp::vi_batch_form_name_static(g.name);
     return MP_OK;
 }
 

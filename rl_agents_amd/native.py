@@ -69,6 +69,7 @@ SIGNATURES = {
     "mp_vi_form_names": (C.c_char_p, []),
     "mp_vi_graph_captures": (c_i64, [_vp]),
     "mp_vi_geometry": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, _vp]),
+    "mp_vi_batch_geometry": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, _vp, P(C.c_char_p)]),
     "mp_vi_dense_mode": (C.c_int, [_vp, c_i32]),
     "mp_uct_record_visits": (C.c_int, [_vp, _vp]),
     "mp_vi_exact_plan": (C.c_int, [c_i32, c_i32, _vp, c_i32, _vp, c_i32, _vp, _vp]),
@@ -533,6 +534,21 @@ def vi_geometry(mode, S=1, A=1, M=1, Sc=None, cus=256):
                     persist_wgs=int(out[4]), persist=bool(out[5]))
     return dict(nb=int(out[6]), nbt=int(out[7]), waves=int(out[8]), fixed_lds=int(out[9]), v_default=VI_V_PLACEMENT[out[10]],
                 v=VI_V_PLACEMENT[out[11]], nseg=int(out[12]), seg_cols=int(out[13]))
+
+
+VI_BATCH_FORMS = ("reg", "cluster", "wg_stream", "wg_lds", "wg_global")
+
+
+def vi_batch_geometry(N, Sb, A, iterations=1, cus=256):
+    """The kernel form ``vi_solve_batch`` chooses for N MDPs of Sb states and A actions on a device of ``cus`` compute units
+    (mp_vi_batch_geometry; host only, the function the solve launches from); the MP_VI_BATCH_* knobs are read from the
+    environment -> dict(form = one of VI_BATCH_FORMS, name = what Context.last_kernel_variant() reports, at = the compile-time
+    |A| or 0, own = states a thread keeps in registers, block, k = workgroups per MDP, grid, lds = dynamic LDS bytes)."""
+    out = np.zeros(7, np.int64)
+    name = C.c_char_p()
+    _check(load().mp_vi_batch_geometry(int(N), int(Sb), int(A), int(iterations), int(cus), _ptr(out), C.byref(name)))
+    return dict(form=VI_BATCH_FORMS[out[0]], name=name.value.decode(), at=int(out[1]), own=int(out[2]), block=int(out[3]),
+                k=int(out[4]), grid=int(out[5]), lds=int(out[6]))
 
 
 def vi_exact_plan(n):

@@ -331,6 +331,13 @@ def assert_form(ctx, name):
     assert got == name, "kernel form {!r} ran where the test means {!r}".format(got, name)
 
 
+def assert_vi_batch_form(ctx, N, S, A, iters):
+    """The last vi_solve_batch on ``ctx`` -- N MDPs of S states and A actions -- launched the form the host query names for it
+    (native.vi_batch_geometry: the function the solve launches from, with the knobs as the test has set them)."""
+    from rl_agents_amd import native
+    assert_form(ctx, native.vi_batch_geometry(N, S, A, iters, cus=ctx.device_info()["n_cu"])["name"])
+
+
 def opd_closing_fits(n_actions, budget):
     """closing_compact_fits (csrc/opd_closing.hpp) at the sizes opd_shape derives from |A| and the budget."""
     k = budget // n_actions

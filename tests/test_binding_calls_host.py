@@ -699,6 +699,8 @@ def _cases():
     c["vi_geometry deterministic"] = lambda h: native.vi_geometry("deterministic", S, A, M)
     c["vi_geometry stochastic"] = lambda h: _hooked(h, "mp_vi_geometry", lambda out: out.__setitem__(slice(10, 12), [1, 2]),
                                                     lambda: native.vi_geometry("stochastic", S, A, Sc=16))
+    c["vi_batch_geometry"] = lambda h: _hooked(h, "mp_vi_batch_geometry", lambda out, name: out.__setitem__(0, 1),
+                                               lambda: native.vi_batch_geometry(5, S, A, 200))
     c["vi_exact_plan"] = lambda h: native.vi_exact_plan(20)
     c["rng_state_from_generator"] = lambda h: native.rng_state_from_generator(np.random.Generator(np.random.PCG64(5)))
     c["rng_state_from_generator other"] = lambda h: native.rng_state_from_generator(np.random.Generator(np.random.MT19937(5)))

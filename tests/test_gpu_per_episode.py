@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from rl_agents_amd import native
+from tests.helpers import assert_vi_batch_form
 
 pytestmark = pytest.mark.gpu
 
@@ -135,6 +136,7 @@ def test_vi_batch_register_forms(ctx, n_states, n_actions, own, block):
     model = ctx.load_table_batch(tr, rw, tm)
     q, sweeps = ctx.vi_solve_batch(model, 0.9, 40)
     assert_form(ctx, "vi_batch_reg<{},{}>".format(own, block))
+    assert_vi_batch_form(ctx, n, n_states, n_actions, 40)
     q_ref, sw_ref = oracle.vi_solve_each(tr, rw, tm, gamma=0.9, iterations=40)
     np.testing.assert_array_equal(sweeps, sw_ref)
     assert np.array_equal(q, q_ref)
@@ -156,6 +158,7 @@ def test_vi_batch_workgroup_forms(ctx, monkeypatch, knob, variant):
     model = ctx.load_table_batch(tr, rw, tm)
     q, sweeps = ctx.vi_solve_batch(model, 0.95, 200)
     assert ctx.last_kernel_variant() == variant
+    assert_vi_batch_form(ctx, *rw.shape, 200)
     q_ref, sw_ref = oracle.vi_solve_each(tr, rw, tm, gamma=0.95, iterations=200)
     np.testing.assert_array_equal(sweeps, sw_ref)
     assert np.array_equal(q, q_ref)
@@ -166,6 +169,7 @@ def test_vi_batch_workgroup_forms(ctx, monkeypatch, knob, variant):
     for iters in (0, 1, 2, 200):
         q, sweeps = ctx.vi_solve_batch(model, 0.95, iters)
         assert ctx.last_kernel_variant() == variant
+        assert_vi_batch_form(ctx, *rw.shape, iters)
         q_ref, sw_ref = oracle.vi_solve_each(tr, rw, tm, gamma=0.95, iterations=iters)
         np.testing.assert_array_equal(sweeps, sw_ref)
         assert np.array_equal(q, q_ref), iters
@@ -186,6 +190,7 @@ def test_vi_batch_cluster_form(ctx, monkeypatch, n, k):
     for iters in (1, 3, 200):
         q, sweeps = ctx.vi_solve_batch(model, 0.95, iters)
         assert ctx.last_kernel_variant() == "vi_batch_cluster{}".format(k or (8 if n <= 32 else 4))
+        assert_vi_batch_form(ctx, *rw.shape, iters)
         q_ref, sw_ref = oracle.vi_solve_each(tr, rw, tm, gamma=0.95, iterations=iters)
         np.testing.assert_array_equal(sweeps, sw_ref)
         assert np.array_equal(q, q_ref), iters
@@ -194,15 +199,17 @@ def test_vi_batch_cluster_form(ctx, monkeypatch, n, k):
 
 def test_vi_batch_cluster_small_mdps_and_fallback(ctx, monkeypatch):
     """The cluster form forced on small MDPs (K = 2, 4, 8: slices of a few states, an empty slice at K = 8 x S = 30 is not), and
-    clusters that never meet (test hook: one arrival too many is awaited): every MDP is solved again by the follow-up launch."""
+    clusters that never meet (test hook: one arrival too many is awaited): every MDP is solved again by the follow-up launch.
+    A forced size that is no cluster size (3) means one workgroup per MDP."""
     from oracle import oracle
     monkeypatch.setenv("MP_VI_BATCH_NO_REG", "1")
-    for shape, n, k in (((3, 4, 10), 21, 2), ((3, 4, 10), 21, 4), ((2, 3, 5), 7, 8), ((5, 5, 20), 11, 4)):
+    for shape, n, k in (((3, 4, 10), 21, 2), ((3, 4, 10), 21, 4), ((2, 3, 5), 7, 8), ((5, 5, 20), 11, 4), ((2, 3, 5), 7, 3)):
         monkeypatch.setenv("MP_VI_BATCH_CLUSTER", str(k))
         tr, rw, tm = _tables(n, shape, seed0=90 + k)
         model = ctx.load_table_batch(tr, rw, tm)
         q, sweeps = ctx.vi_solve_batch(model, 0.95, 200)
-        assert ctx.last_kernel_variant() == "vi_batch_cluster{}".format(k)
+        assert ctx.last_kernel_variant() == ("vi_batch_wg_stream" if k == 3 else "vi_batch_cluster{}".format(k))
+        assert_vi_batch_form(ctx, *rw.shape, 200)
         q_ref, sw_ref = oracle.vi_solve_each(tr, rw, tm, gamma=0.95, iterations=200)
         np.testing.assert_array_equal(sweeps, sw_ref)
         assert np.array_equal(q, q_ref), (shape, k)

@@ -11,17 +11,16 @@ buffer holds that call's Q).
     the partners finish with real values, and only the MDP's give-up word sends it to the follow-up launch;
   * a NULL sweeps_out through the C ABI while clusters fail;
   * one workgroup of the persistent grid giving up (MP_VI_PERSIST_GIVE_UP)."""
+import os
+
 import numpy as np
 import pytest
 
 from rl_agents_amd import native
-from tests.helpers import assert_form
+from tests.helpers import assert_form, assert_vi_batch_form
 
 pytestmark = pytest.mark.gpu
 
-LDS_BYTES = 160 * 1024
-# the cluster form keeps [2][S] doubles + 16 bytes of LDS per workgroup, within 512 bytes of the CU's LDS (the kernel's static LDS)
-S_LDS_MAX = (LDS_BYTES - 512 - 16) // 16
 K_LAG = 2                                   # vi.hip kLag: the persistent kernel reads a sweep's verdict kLag sweeps late
 
 
@@ -36,27 +35,48 @@ def _cdiv(a, b):
     return -(-a // b)
 
 
-def _cluster_own(S, K):
-    """States per thread of the cluster form at K workgroups per MDP (as vi_batch_launch computes it)."""
-    return _cdiv(_cdiv(S, K), 1024)
+def _geometry(S, K, A=5):
+    """What the solve chooses for MDPs of S states under the knobs the cluster tests below set (native.vi_batch_geometry: the
+    function the solve launches from; the forced K makes the batch size and the device's size irrelevant).  Also called while
+    the module is collected, so the knobs are set here and put back."""
+    knobs = dict(MP_VI_BATCH_NO_REG="1", MP_VI_BATCH_CLUSTER=str(K))
+    old = {k: os.environ.get(k) for k in knobs}
+    os.environ.update(knobs)
+    try:
+        return native.vi_batch_geometry(3, S, A, 200)
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
 
 
-def _takes_cluster(S, K):
-    return _cluster_own(S, K) <= 3 and S <= S_LDS_MAX
+def _takes_cluster(S, K, own=3):
+    """S takes the cluster form at K workgroups per MDP, a thread keeping at most ``own`` states."""
+    g = _geometry(S, K)
+    return g["form"] == "cluster" and g["k"] == K and g["own"] <= own
+
+
+def _last_cluster(K, own=3):
+    """The largest S with _takes_cluster (it holds up to some S and never after), 0 if there is none."""
+    lo, hi = 0, 1 << 16
+    assert not _takes_cluster(hi, K, own)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if _takes_cluster(mid, K, own) else (lo, mid)
+    return lo
 
 
 def _reachable():
     """(K, OWN) pairs the dispatcher can reach: OWN 1..3 at K = 2 and 4, 1..2 at K = 8 (LDS)."""
-    return [(K, own) for K in (2, 4, 8) for own in (1, 2, 3) if K * 1024 * (own - 1) + 1 <= S_LDS_MAX]
+    return [(K, own) for K in (2, 4, 8) for own in (1, 2, 3) if _last_cluster(K, own) > _last_cluster(K, own - 1)]
 
 
 def _edges(K, own):
-    """S at the edges of the slices of (K, OWN): the first S of OWN, K*1024*OWN (every slice full) where the LDS allows, a
-    ragged last slice (S = 1 mod K), and at OWN = 1 a shape whose last parts own no state."""
-    hi = min(K * 1024 * own, S_LDS_MAX)
-    out = [K * 1024 * (own - 1) + 1]
-    if K * 1024 * own <= S_LDS_MAX:
-        out.append(K * 1024 * own)
+    """S at the edges of the slices of (K, OWN): the first S of OWN, the last one where every slice is full (the LDS may end the
+    form before that), a ragged last slice (S = 1 mod K), and at OWN = 1 a shape whose last parts own no state."""
+    lo, hi = _last_cluster(K, own - 1) + 1, _last_cluster(K, own)
+    out = [lo]
+    if hi == K * _geometry(hi, K)["block"] * own:
+        out.append(hi)
     out.append(hi - (hi - 1) % K)
     if own == 1:
         out.append(K + 1 if K > 2 else 1)
@@ -90,6 +110,7 @@ def _check_device(ctx, model, gamma, iters, ref, variant):
     ctx.vi_solve_batch_device(model, gamma, iters, dq, dsw)
     ctx.synchronize()
     assert ctx.last_kernel_variant() == variant
+    assert_vi_batch_form(ctx, n, S, A, iters)
     np.testing.assert_array_equal(dsw.cpu().numpy(), ref[1])
     q = dq.cpu().numpy().reshape(n, S, A)
     assert np.array_equal(q, ref[0]), "device Q differs in MDPs {}".format(
@@ -99,6 +120,7 @@ def _check_device(ctx, model, gamma, iters, ref, variant):
 def _check_host(ctx, model, gamma, iters, ref, variant):
     q, sw = ctx.vi_solve_batch(model, gamma, iters)
     assert ctx.last_kernel_variant() == variant
+    assert_vi_batch_form(ctx, *ref[0].shape, iters)
     np.testing.assert_array_equal(sw, ref[1])
     assert np.array_equal(q, ref[0]), "host Q differs in MDPs {}".format(
         sorted({int(b) for b in np.argwhere(~(q == ref[0]))[:, 0]}))
@@ -116,7 +138,7 @@ def test_cluster_every_instantiation_at_slice_edges(ctx, monkeypatch, A, K, own)
     monkeypatch.setenv("MP_VI_BATCH_CLUSTER", str(K))
     variant = "vi_batch_cluster{}".format(K)
     for i, S in enumerate(_edges(K, own)):
-        assert _cluster_own(S, K) == own and _takes_cluster(S, K), (S, K, own)
+        assert _takes_cluster(S, K, own) and not _takes_cluster(S, K, own - 1), (S, K, own)
         n = (3, 5, 9)[(A + own + i) % 3]
         tr, rw, tm = _tables(n, S, A, seed=1000 * A + 100 * K + 10 * own + i, terminal=i % 2 == 0)
         model = ctx.load_table_batch(tr, rw, tm)
@@ -130,7 +152,7 @@ def test_cluster_every_instantiation_at_slice_edges(ctx, monkeypatch, A, K, own)
         model.close()
 
 
-@pytest.mark.parametrize("K,S", [(2, 2 * 1024 * 3 + 1), (4, S_LDS_MAX + 1), (8, S_LDS_MAX + 1), (4, 10239), (8, 10239)])
+@pytest.mark.parametrize("K,S", [(K, _last_cluster(K) + 1) for K in (2, 4, 8)] + [(4, 10239), (8, 10239)])
 @pytest.mark.parametrize("A", [2, 6])
 def test_cluster_first_shape_past_the_limit(ctx, monkeypatch, A, K, S):
     """The first S past the cluster form (OWN = 4 at K = 2; the LDS at K = 4, 8), and S = 10 239 (16 S + 16 bytes fit the LDS
@@ -144,6 +166,7 @@ def test_cluster_first_shape_past_the_limit(ctx, monkeypatch, A, K, S):
     ref = oracle.vi_solve_each(tr, rw, tm, gamma=0.9, iterations=200)
     q, sw = ctx.vi_solve_batch(model, 0.9, 200)
     assert not ctx.last_kernel_variant().startswith("vi_batch_cluster"), ctx.last_kernel_variant()
+    assert_vi_batch_form(ctx, 3, S, A, 200)
     np.testing.assert_array_equal(sw, ref[1])
     assert np.array_equal(q, ref[0])
     model.close()
@@ -246,6 +269,7 @@ def test_cluster_null_sweeps_out_through_the_c_abi(ctx, monkeypatch):
                                                  native.MP_MEM_DEVICE))
         ctx.synchronize()
         assert ctx.last_kernel_variant() == "vi_batch_cluster{}".format(K)
+        assert_vi_batch_form(ctx, n, S, A, 200)
         assert np.array_equal(dq.cpu().numpy().reshape(n, S, A), ref[0]), hook
         q = np.full((n, S, A), np.nan)
         native._check(ctx._lib.mp_vi_solve_batch(ctx._h, model._h, 0.9, 200, 1e-5, 1e-8, native._ptr(q), None,
