@@ -100,6 +100,14 @@ class DiscreteRobustPlanner(OptimisticDeterministicPlanner):
         n = int(out["plan_len"][0])
         return [int(a) for a in out["plans"][0, :n]]
 
+    per_episode_kind = "ropd"
+
+    def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None):
+        """root_states: [n] (all models start in the same state) or [n, M] joint states of the joint model ``model``."""
+        budget, gamma, terminal_reward = self.opd_args(model)
+        return self.models.ctx.ropd_plan(model, root_states, budget, gamma, terminal_reward, rng_states, model_index=model_index,
+                                         max_plan_len=budget // model.A + 1 if max_plan_len is None else max_plan_len)
+
     def plan_batch(self, state, root_states, root_steps=None, rng_states=None, model=None, model_index=None):
         """root_states: [n] (all models start in the same state) or [n, M] joint states.  ``model_index`` int [n] with a joint
         batch model (``Context.load_joint_batch``): root i plans on set ``model_index[i]`` from its LOCAL joint state
@@ -107,18 +115,12 @@ class DiscreteRobustPlanner(OptimisticDeterministicPlanner):
         if model is None:
             model, _ = self.joint_model(state)
         rs = np.asarray(root_states, dtype=np.int32)
-        n = rs.shape[0]
         if rng_states is None:
-            rng_states = self.batch_rng_states(n)
-        cfg = self.config
-        budget = int(cfg["budget"])
-        if cfg["gamma"] == 1 and budget >= model.A:
-            raise ZeroDivisionError("float division by zero")       # gamma ** depth / (1 - gamma), deterministic.py:53
+            rng_states = self.batch_rng_states(rs.shape[0])
+        budget = self.opd_args(model)[0]        # (a configuration error comes before another planner's tree is exported)
         self.about_to_plan()
-        out = self.models.ctx.ropd_plan(model, rs, budget, cfg["gamma"], cfg.get("terminal_reward", 0), rng_states,
-                                        max_plan_len=budget // model.A + 1, model_index=model_index)
-        if (out["status"] == native.ERR_REWARD_RANGE).any():
-            raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # deterministic.py:46-47
+        out = self.plan_on(model, rs, root_steps, rng_states, model_index=model_index, max_plan_len=budget // model.A + 1)
+        self.raise_for_result(out)
         out["rng_states"] = rng_states
         self.last, self._root, self._last_actions, self._last_models = out, None, model.A, model.M
         # (a tree on a joint batch model holds global states n * S_each + s: export_tree reports the set's own)
@@ -142,7 +144,6 @@ class DiscreteRobustPlanner(OptimisticDeterministicPlanner):
         rebuilds its JointEnv from the true env before every plan, robust.py:67-70).  ``model`` (the true env's, which the loop
         steps) is not used; ``state`` is the JointEnv."""
         import torch
-        cfg = self.config
         # the joint model of this loop's JointEnv, resolved ONCE: joint_model() stacks and hashes every candidate model's
         # tables on the host, O(M S A) work that would make every step of an asynchronous loop host-bound (ADVICE r4);
         # the evaluation loop announces itself with begin_device_loop()
@@ -150,18 +151,15 @@ class DiscreteRobustPlanner(OptimisticDeterministicPlanner):
         if held is None or held[0] is not state:
             held = self._device_joint = (state, self.joint_model(state)[0])
         jm = held[1]
-        budget = int(cfg["budget"])
-        if cfg["gamma"] == 1 and budget >= jm.A:
-            raise ZeroDivisionError("float division by zero")
+        budget, gamma, terminal_reward = self.opd_args(jm)
         ctx = self.models.ctx
         if getattr(self, "_d_joint", None) is None or self._d_joint.shape != (n, jm.M) or self._d_joint.device != d_state.device:
             self._d_joint = torch.empty((n, jm.M), dtype=torch.int32, device=d_state.device)
         with torch.cuda.stream(torch.cuda.ExternalStream(ctx.stream_ptr(), device=d_state.device)):
             self._d_joint.copy_(d_state[:, None].expand(n, jm.M))          # (on the planner's stream, after the env step)
         self.about_to_plan()
-        ctx.ropd_plan_device(jm, n, self._d_joint, budget, cfg["gamma"], cfg.get("terminal_reward", 0), d_rng,
-                             int(d_plans.shape[1]), plans=d_plans, plan_len=d_len, root_lower=d_value, env_steps=d_env_steps,
-                             status=d_status)
+        ctx.ropd_plan_device(jm, n, self._d_joint, budget, gamma, terminal_reward, d_rng, int(d_plans.shape[1]), plans=d_plans,
+                             plan_len=d_len, root_lower=d_value, env_steps=d_env_steps, status=d_status)
         self._last_actions, self._last_models, self._last_states_each = jm.A, jm.M, None
         self.claim_device_tree()
         self.last, self._root = None, None

@@ -302,6 +302,26 @@ class AbstractPlanner(Configurable):
     def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
         raise NotImplementedError()
 
+    # The planner's ONE device call and the exceptions of its result.  plan_batch, plan_batch_device (through the argument
+    # helpers plan_on uses) and PerEpisodeEvaluation all go through them; the bookkeeping around them -- self.last, the tree
+    # claim, env_steps, relabel -- is the caller's, and so is what it does between the call and the raise.
+    def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None):
+        """The call arguments from the config (a configuration error is raised here, before any launch) and the one
+        ``ctx.*_plan`` call -> the binding's dict.  ``model_index``: a batch model, one MDP per root."""
+        raise NotImplementedError()
+
+    def raise_for_result(self, out):
+        """The reference's exceptions for what :meth:`plan_on` returned: by default those of the status codes, which a planner
+        that has any maps in a static ``raise_for_status(status)`` (planners without codes define none)."""
+        self.raise_for_status(out["status"])
+
+    # what PerEpisodeEvaluation does with this planner: "opd", "ropd", "olop", "brue" (one plan_on per lock-step), "uct" (the
+    # loop's own policy handling); None: the loop refuses the planner
+    per_episode_kind = None
+    # the reference's generator has made the draws of the episodes run before a failing step: planners whose records stay
+    # advanced when a plan raises (OLOP, BRUE)
+    draws_survive_errors = False
+
     def export_tree(self, root=0):
         raise NotImplementedError()
 
@@ -316,7 +336,13 @@ class AbstractPlanner(Configurable):
         return False
 
     def raise_for_device_status(self, d_status, live):
-        pass
+        """What a sequential agent would have raised for the statuses of the live slots.  A planner without status codes (no
+        ``raise_for_status``: MCTS) wrote none, and nothing is read back for it."""
+        mapping = getattr(self, "raise_for_status", None)
+        if mapping is not None:
+            bad = d_status[live]
+            if bad.numel():
+                mapping(bad.cpu().numpy())
 
     def model_for(self, state):
         if device_model.is_cartpole(state):
@@ -372,11 +398,17 @@ class AbstractPlanner(Configurable):
         return arrays
 
     def plan(self, state, observation):
-        """Plan from the current state of the environment object ``state`` (never stepped, never copied)."""
+        """Plan from the current state of the environment object ``state`` (never stepped, never copied).  The planner's
+        generator is written back after the plan -- for a planner whose ``draws_survive_errors``, also when the plan raises."""
         s0, steps0 = device_model.env_root_state(state)
         rng = native.rng_state_from_generator(self.np_random).reshape(1, 6)
-        out = self.plan_batch(state, [s0], [steps0], rng_states=rng)
-        native.generator_set_state(self.np_random, rng[0])
+        planned = False
+        try:
+            out = self.plan_batch(state, [s0], [steps0], rng_states=rng)
+            planned = True
+        finally:
+            if planned or self.draws_survive_errors:
+                native.generator_set_state(self.np_random, rng[0])
         n = int(out["plan_len"][0])
         return [int(a) for a in out["plans"][0, :n]]
 

@@ -10,7 +10,7 @@ import logging
 
 import numpy as np
 
-from rl_agents_amd import device_model, native
+from rl_agents_amd import device_model
 from rl_agents_amd.agents.tree_search.abstract import AbstractTreeSearchAgent, Node
 from rl_agents_amd.agents.tree_search.olop import OLOP
 
@@ -45,38 +45,37 @@ class BRUE(OLOP):
             model.set_episode_rules(getattr(mdp, "done_rule", "source"), 0)
         return model
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
-        """``root_steps`` is accepted for the common interface: the step limit ends no BRUE rollout (done = terminated)."""
+    per_episode_kind = "brue"
+
+    def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None):
+        """``root_steps`` and ``max_plan_len`` are accepted for the common interface: the step limit ends no BRUE rollout (done
+        = terminated) and a plan is ONE action -- ``plans`` [n, 1], -1 where no rollout was made."""
         cfg = self.config
-        budget, horizon = int(cfg["budget"]), int(cfg["horizon"])
-        model = self.model_for(state)
-        self.about_to_plan()
-        n = len(root_states)
-        if rng_states is None:
-            rng_states = self.batch_rng_states(n)
-        out = self.models.ctx.brue_plan(model, root_states, budget, horizon, cfg["gamma"],
-                                        self.gamma_powers(cfg["gamma"], horizon), rng_states)
-        self.env_steps += int(out["env_steps"].sum())
-        out["rng_states"] = rng_states
-        self._cap = 1 + 2 * (max(budget, 0) + horizon)
-        self.last, self._root, self._last_model = out, None, model
-        self.claim_device_tree()
+        horizon = int(cfg["horizon"])
+        out = self.models.ctx.brue_plan(model, root_states, int(cfg["budget"]), horizon, cfg["gamma"],
+                                        self.gamma_powers(cfg["gamma"], horizon), rng_states, model_index=model_index)
+        n = len(out["plans"])
+        out["plans"], out["plan_len"] = out["plans"].reshape(n, 1), np.ones(n, np.int32)
+        return out
+
+    def raise_for_result(self, out):
         if (out["plans"] < 0).any():
             # no rollout was made (budget <= 0): the reference's np.amax([]) of the root's selection raises (brue.py:75)
             raise ValueError("zero-size array to reduction operation maximum which has no identity")
-        out["plans"] = out["plans"].reshape(n, 1)
-        out["plan_len"] = np.ones(n, np.int32)
-        return out
 
-    def plan(self, state, observation):
-        """BRUE.plan (brue.py:66-71), with the planner's generator written back also when the plan raises."""
-        s0, steps0 = device_model.env_root_state(state)
-        rng = native.rng_state_from_generator(self.np_random).reshape(1, 6)
-        try:
-            out = self.plan_batch(state, [s0], [steps0], rng_states=rng)
-        finally:
-            native.generator_set_state(self.np_random, rng[0])
-        return [int(out["plans"][0, 0])]
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
+        model = self.model_for(state)
+        self.about_to_plan()
+        if rng_states is None:
+            rng_states = self.batch_rng_states(len(root_states))
+        out = self.plan_on(model, root_states, root_steps, rng_states)
+        self.env_steps += int(out["env_steps"].sum())
+        out["rng_states"] = rng_states
+        self._cap = 1 + 2 * (max(int(self.config["budget"]), 0) + int(self.config["horizon"]))
+        self.last, self._root, self._last_model = out, None, model
+        self.claim_device_tree()
+        self.raise_for_result(out)          # (after the draws, the steps and the tree of the failing plan are booked)
+        return out
 
     def export_tree(self, root=0):
         self.require_device_tree()

@@ -3,6 +3,8 @@
 (rl_agents_amd/csrc/opd.hip)."""
 import logging
 
+import numpy as np
+
 from rl_agents_amd import native
 from rl_agents_amd.agents.tree_search.abstract import AbstractPlanner, AbstractTreeSearchAgent, build_tree
 
@@ -16,20 +18,40 @@ class OptimisticDeterministicPlanner(AbstractPlanner):
         super(OptimisticDeterministicPlanner, self).__init__(config)
         self.env = env
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
-        self.about_to_plan()
-        model = self.model_for(state)
-        n = len(root_states)
-        if rng_states is None:
-            rng_states = self.batch_rng_states(n)
+    per_episode_kind = "opd"
+
+    def opd_args(self, model):
+        """(budget, gamma, terminal reward) of every opd / ropd call, host or device -- or the reference's error for a
+        configuration it cannot plan with, before anything is launched."""
         cfg = self.config
         budget = int(cfg["budget"])
         if cfg["gamma"] == 1 and budget >= model.A:
             raise ZeroDivisionError("float division by zero")       # gamma ** depth / (1 - gamma), deterministic.py:53
-        out = self.models.ctx.opd_plan(model, root_states, budget, cfg["gamma"], cfg.get("terminal_reward", 0),
-                                       rng_states, max_plan_len=budget // model.A + 1)
-        if (out["status"] == native.ERR_REWARD_RANGE).any():
+        return budget, cfg["gamma"], cfg.get("terminal_reward", 0)
+
+    def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None):
+        """``root_steps`` is accepted for the common interface: the tables' own step limit ends the expansions."""
+        budget, gamma, terminal_reward = self.opd_args(model)
+        return self.models.ctx.opd_plan(model, root_states, budget, gamma, terminal_reward, rng_states, model_index=model_index,
+                                        max_plan_len=budget // model.A + 1 if max_plan_len is None else max_plan_len)
+
+    def raise_for_result(self, out):
+        """The statuses of plan_on's opd / ropd call in this class's mapping: a subclass that maps the codes of its own calls
+        (the state-aware planner's ``raise_for_status``) does not re-read an OPD plan's through it."""
+        OptimisticDeterministicPlanner.raise_for_status(out["status"])
+
+    @staticmethod
+    def raise_for_status(status):
+        if (np.asarray(status) == native.ERR_REWARD_RANGE).any():
             raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # deterministic.py:46-47
+
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
+        self.about_to_plan()
+        model = self.model_for(state)
+        if rng_states is None:
+            rng_states = self.batch_rng_states(len(root_states))
+        out = self.plan_on(model, root_states, root_steps, rng_states)
+        self.raise_for_result(out)
         out["rng_states"] = rng_states
         self.relabel(out, model)
         self.last, self._root, self._last_actions, self._last_model = out, None, model.A, model
@@ -45,22 +67,14 @@ class OptimisticDeterministicPlanner(AbstractPlanner):
         return 1
 
     def plan_batch_device(self, state, model, n, d_state, d_steps, d_rng, d_plans, d_len, d_env_steps, d_status, d_value=None):
-        """One asynchronous batched plan (mp_opd_plan, MP_MEM_DEVICE): only enqueues; reward-range errors land in d_status.
-        ``d_value``: optional float64 [n] buffer for the roots' lower bounds."""
-        cfg = self.config
-        budget = int(cfg["budget"])
-        if cfg["gamma"] == 1 and budget >= model.A:
-            raise ZeroDivisionError("float division by zero")
+        """One asynchronous batched plan (mp_opd_plan, MP_MEM_DEVICE): only enqueues; reward-range errors land in d_status
+        (:meth:`raise_for_device_status`).  ``d_value``: optional float64 [n] buffer for the roots' lower bounds."""
+        budget, gamma, terminal_reward = self.opd_args(model)
         self.about_to_plan()
-        self.models.ctx.opd_plan_device(model, n, d_state, budget, cfg["gamma"], cfg.get("terminal_reward", 0), d_rng,
-                                        int(d_plans.shape[1]), plans=d_plans, plan_len=d_len, root_lower=d_value,
-                                        env_steps=d_env_steps, status=d_status)
+        self.models.ctx.opd_plan_device(model, n, d_state, budget, gamma, terminal_reward, d_rng, int(d_plans.shape[1]),
+                                        plans=d_plans, plan_len=d_len, root_lower=d_value, env_steps=d_env_steps, status=d_status)
         self.claim_device_tree()
         self.last, self._root = None, None
-
-    def raise_for_device_status(self, d_status, live):
-        if bool(((d_status == native.ERR_REWARD_RANGE) & live).any().item()):
-            raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # deterministic.py:46-47
 
     def export_tree(self, root=0):
         self.require_device_tree()

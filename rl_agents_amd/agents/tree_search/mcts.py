@@ -100,6 +100,7 @@ def policy_tables(policy_config, available, col_ids=None, env_rank=None):
 class MCTS(AbstractPlanner):
     """UCT planner (mcts.py:100-200) for one or many roots of one finite MDP (or closed-form CartPole)."""
     supports_cartpole = True
+    per_episode_kind = "uct"
 
     def __init__(self, env, prior_policy, rollout_policy, config=None):
         super(MCTS, self).__init__(config)
@@ -351,21 +352,7 @@ class MCTS(AbstractPlanner):
             if gen is None:
                 raise TypeError("a stochastic environment must expose its numpy generator as `np_random`")
             env_rng_states = np.tile(native.rng_state_from_generator(gen), (n, 1))
-        available = getattr(model, "available", None)
-        policy, pp, rp = None, None, None
-        if self.policy_source is not None or available is not None:
-            # per-state policies: a prior agent's distribution (mcts_with_prior.py:47-62) / policies over the actions the
-            # environment lists (mcts.py:59-97), as [S, A] tables the kernel reads by the state the clone is in
-            if self.policy_source is not None:
-                prior, rollout = self.policy_source(state, model)
-                listed, slots = available, None
-            else:
-                prior, rollout, listed, slots = self.restricted_policy_tables(model, available)
-            policy = self.device_policy(model, prior, rollout, listed, slots)
-            logged = ("tables", prior, rollout, listed, slots)
-        else:
-            pp, rp = policy_probabilities(self.prior_policy, model.A), policy_probabilities(self.rollout_policy, model.A)
-            logged = ("flat", pp, rp)
+        policy, pp, rp, logged = self._policy_choice(state, model)
         self._log_plan(model, root_states, root_steps, rng_states, env_rng_states, logged, getattr(self, "_continued", False))
         out = self.models.ctx.uct_plan_stochastic(
             model, root_states, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], pp, rp, rng_states,
@@ -397,61 +384,25 @@ class MCTS(AbstractPlanner):
         if rng_states is None:
             rng_states = self.batch_rng_states(n)
         if model.mode in (native_modes.MODE_STOCHASTIC, native_modes.MODE_SPARSE) or self.loop_form(model):
-            # (open-loop trees are re-used like the deterministic ones: mp_uct_step_tree armed the re-rooting)
-            armed, self._armed = self._armed and n == 1 and not self.config["closed_loop"], False
-            self._continued = False
-            if keep_actions is not None and self.owns_device_tree() and not self.config["closed_loop"] and self._tree_roots == n:
-                # (batched callers: the executed actions, as device labels)
-                labels = np.asarray(self.device_actions(keep_actions, model), dtype=np.int32)
-                self.models.ctx.uct_step_tree(labels)
-                if not getattr(self, "_visit_gap", None):
-                    self._visit_events().append(("step", labels.copy()))
-                self._continued = True
-            elif not (armed and self.owns_device_tree()):
-                self.models.ctx.uct_reset_tree()
-            else:
-                self._continued = True      # the plan goes on in the tree step_by_subtree kept (logged for get_visits)
+            self._continued = self._continue_trees(model, n, keep_actions, stochastic=True)
             return self.plan_batch_stochastic(state, model, root_states, root_steps, rng_states, env_rng_states)
         self._stochastic = False
         cfg = self.config
-        ctx = self.models.ctx
-        armed, self._armed = self._armed and n == 1, False
-        continued = False
-        if keep_actions is not None and self.owns_device_tree():
-            labels = np.asarray(self.device_actions(keep_actions, model), dtype=np.int32)
-            ctx.uct_step_tree(labels)                                     # batched callers hand the executed actions over here
-            if not getattr(self, "_visit_gap", None):
-                self._visit_events().append(("step", labels.copy()))
-            continued = True
-        elif not (armed and self.owns_device_tree()):
-            ctx.uct_reset_tree()
-        else:
-            continued = True
-        available = getattr(model, "available", None)
-        if self.policy_source is not None or available is not None:
-            if self.policy_source is not None:
-                prior, rollout = self.policy_source(state, model)      # (restricted to the available actions there;
-                listed = available                                     #  columns in the model's listing order)
-                slots = None
-            else:
-                prior, rollout, listed, slots = self.restricted_policy_tables(model, available)
-            self._log_plan(model, root_states, root_steps, rng_states, None, ("tables", prior, rollout, listed, slots), continued)
-            out = ctx.uct_plan(model, root_states, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"],
-                               None, None, rng_states, root_steps=root_steps, max_plan_len=max(cfg["horizon"], 1),
-                               policy=self.device_policy(model, prior, rollout, listed, slots))
+        continued = self._continue_trees(model, n, keep_actions, stochastic=False)
+        policy, prior_p, rollout_p, logged = self._policy_choice(state, model)
+        self._log_plan(model, root_states, root_steps, rng_states, None, logged, continued)
+        out = self.models.ctx.uct_plan(model, root_states, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"],
+                                       prior_p, rollout_p, rng_states, root_steps=root_steps, max_plan_len=max(cfg["horizon"], 1),
+                                       policy=policy)
+        self._last_tables = None
+        if policy is not None:
             order = self.action_order(model)
-            prior_ids = prior
+            prior_ids = prior = logged[1]
             if order is not None:                       # export works in the environment's action ids
                 prior_ids = np.empty_like(prior)
                 prior_ids[:, order] = prior
             self._last_tables = (np.asarray(device_model.finite_mdp_of(state).transition), prior_ids,
                                  np.asarray(root_states, dtype=np.int64))
-        else:
-            prior_p, rollout_p = policy_probabilities(self.prior_policy, model.A), policy_probabilities(self.rollout_policy, model.A)
-            self._log_plan(model, root_states, root_steps, rng_states, None, ("flat", prior_p, rollout_p), continued)
-            out = ctx.uct_plan(model, root_states, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"],
-                               prior_p, rollout_p, rng_states, root_steps=root_steps, max_plan_len=max(cfg["horizon"], 1))
-            self._last_tables = None
         out["rng_states"] = rng_states
         self.relabel(out, model)
         self._last_model = model
@@ -485,70 +436,71 @@ class MCTS(AbstractPlanner):
         if not record:
             self._visit_gap = ("the plans of a device-resident evaluation loop are not logged (set the planner's config "
                                "'record_visits' to log them, or call reset_visits() afterwards)")
-        if model.mode != native_modes.MODE_DETERMINISTIC or self.loop_form(model):
-            # stochastic / sparse models: the episodes' env generator records are a device buffer too (d_env_rng: every
-            # plan's clones start from the env generator as it is at that step; mp_env_step_stochastic advances it)
-            if d_env_rng is None and model.mode != native_modes.MODE_DETERMINISTIC:
-                raise ValueError("a stochastic model needs the episodes' env generator records (d_env_rng)")
-            armed = keep_actions is not None and self.owns_device_tree() and self._tree_roots == n and not cfg["closed_loop"]
-            if armed:
-                ctx.uct_step_tree(keep_actions)
-                if record:
-                    self._visit_events().append(("step", self._device_clone(keep_actions)))
-            else:
-                ctx.uct_reset_tree()
-            available = getattr(model, "available", None)
-            policy, pp, rp = None, None, None
-            if self.policy_source is not None or available is not None:
-                if self.policy_source is not None:
-                    prior, rollout = self.policy_source(state, model)
-                    listed, slots = available, None
-                else:
-                    prior, rollout, listed, slots = self.restricted_policy_tables(model, available)
-                policy = self.device_policy(model, prior, rollout, listed, slots)
-                logged = ("tables", prior, rollout, listed, slots)
-            else:
-                pp, rp = policy_probabilities(self.prior_policy, model.A), policy_probabilities(self.rollout_policy, model.A)
-                logged = ("flat", pp, rp)
-            if record:
-                self._log_plan(model, d_state[:n], None if d_steps is None else d_steps[:n], d_rng[:n],
-                               None if d_env_rng is None else d_env_rng[:n], logged, armed)
-            ctx.uct_plan_stochastic_device(model, n, d_state, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], pp,
-                                           rp, d_rng, d_env_rng, int(d_plans.shape[1]), closed_loop=cfg["closed_loop"],
-                                           plans=d_plans, plan_len=d_len, root_value=d_value, env_steps=d_env_steps,
-                                           root_steps=d_steps, policy=policy)
-            self.claim_device_tree()
-            self.last, self._root, self._tree_roots, self._stochastic = None, None, n, True
-            return
-        armed = keep_actions is not None and self.owns_device_tree() and self._tree_roots == n
+        # stochastic / sparse models (and the loop forms of deterministic ones): the kernel of the stochastic path; the episodes'
+        # env generator records are a device buffer too (d_env_rng: every plan's clones start from the env generator as it is
+        # at that step; mp_env_step_stochastic advances it)
+        stochastic = model.mode != native_modes.MODE_DETERMINISTIC or self.loop_form(model)
+        if stochastic and d_env_rng is None and model.mode != native_modes.MODE_DETERMINISTIC:
+            raise ValueError("a stochastic model needs the episodes' env generator records (d_env_rng)")
+        # the kept trees are stepped only where they are this planner's and as many as the roots (the stochastic path: open loop
+        # only); the step event is logged under record_visits alone, as a device clone
+        armed = keep_actions is not None and self.owns_device_tree() and self._tree_roots == n \
+            and not (stochastic and cfg["closed_loop"])
         if armed:
             ctx.uct_step_tree(keep_actions)
             if record:
                 self._visit_events().append(("step", self._device_clone(keep_actions)))
         else:
             ctx.uct_reset_tree()
-        available = getattr(model, "available", None)
-        policy, pp, rp = None, None, None
-        if self.policy_source is not None or available is not None:
-            if self.policy_source is not None:
-                prior, rollout = self.policy_source(state, model)
-                listed = available
-                slots = None
-            else:
-                prior, rollout, listed, slots = self.restricted_policy_tables(model, available)
-            policy = self.device_policy(model, prior, rollout, listed, slots)
-            logged = ("tables", prior, rollout, listed, slots)
-        else:
-            pp = policy_probabilities(self.prior_policy, model.A)
-            rp = policy_probabilities(self.rollout_policy, model.A)
-            logged = ("flat", pp, rp)
+        policy, pp, rp, logged = self._policy_choice(state, model)
         if record:
-            self._log_plan(model, d_state[:n], None if d_steps is None else d_steps[:n], d_rng[:n], None, logged, armed)
-        ctx.uct_plan_device(model, n, d_state, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], pp, rp, d_rng,
-                            int(d_plans.shape[1]), plans=d_plans, plan_len=d_len, root_value=d_value, env_steps=d_env_steps,
-                            root_steps=d_steps, policy=policy)
+            self._log_plan(model, d_state[:n], None if d_steps is None else d_steps[:n], d_rng[:n],
+                           d_env_rng[:n] if stochastic and d_env_rng is not None else None, logged, armed)
+        if stochastic:
+            ctx.uct_plan_stochastic_device(model, n, d_state, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], pp,
+                                           rp, d_rng, d_env_rng, int(d_plans.shape[1]), closed_loop=cfg["closed_loop"],
+                                           plans=d_plans, plan_len=d_len, root_value=d_value, env_steps=d_env_steps,
+                                           root_steps=d_steps, policy=policy)
+            self._stochastic = True
+        else:
+            ctx.uct_plan_device(model, n, d_state, cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], pp, rp, d_rng,
+                                int(d_plans.shape[1]), plans=d_plans, plan_len=d_len, root_value=d_value, env_steps=d_env_steps,
+                                root_steps=d_steps, policy=policy)
         self.claim_device_tree()
         self.last, self._root, self._tree_roots = None, None, n
+
+    def _policy_choice(self, state, model):
+        """(device policy or None, prior_p, rollout_p, logged) of a plan on ``model``: flat policy vectors over the actions, or
+        -- with a ``policy_source`` (a prior agent's distribution, mcts_with_prior.py:47-62) or an environment that restricts
+        its actions (mcts.py:59-97) -- per-state [S, A] tables the kernel reads by the state the descent is in.  ``logged`` is
+        what a replay needs (:meth:`_log_plan`): ("flat", prior_p, rollout_p) or ("tables", prior, rollout, listed, slots)."""
+        available = getattr(model, "available", None)
+        if self.policy_source is None and available is None:
+            pp, rp = policy_probabilities(self.prior_policy, model.A), policy_probabilities(self.rollout_policy, model.A)
+            return None, pp, rp, ("flat", pp, rp)
+        if self.policy_source is not None:
+            prior, rollout = self.policy_source(state, model)      # (restricted to the available actions there; columns in
+            listed, slots = available, None                        #  the model's listing order)
+        else:
+            prior, rollout, listed, slots = self.restricted_policy_tables(model, available)
+        return self.device_policy(model, prior, rollout, listed, slots), None, None, ("tables", prior, rollout, listed, slots)
+
+    def _continue_trees(self, model, n, keep_actions, stochastic):
+        """A host plan of ``n`` roots: the trees the last plan left are stepped by ``keep_actions`` (batched callers: the
+        executed actions, environment ids), continued where :meth:`step_by_subtree` armed them, or reset -> whether the plan
+        goes on in kept trees (logged for get_visits).  The stochastic path keeps open-loop trees only, and steps them only
+        where they are as many as the roots; the deterministic path compares neither."""
+        ctx, open_loop = self.models.ctx, not (stochastic and self.config["closed_loop"])
+        armed, self._armed = self._armed and n == 1 and open_loop, False
+        if keep_actions is not None and self.owns_device_tree() and open_loop and (not stochastic or self._tree_roots == n):
+            labels = np.asarray(self.device_actions(keep_actions, model), dtype=np.int32)
+            ctx.uct_step_tree(labels)
+            if not getattr(self, "_visit_gap", None):
+                self._visit_events().append(("step", labels.copy()))
+        elif not (armed and self.owns_device_tree()):
+            ctx.uct_reset_tree()
+            return False
+        return True
 
     def restricted_policy_tables(self, model, available):
         """(prior, rollout, listed, rollout slots) of this planner's policy configs on a model whose environment restricts

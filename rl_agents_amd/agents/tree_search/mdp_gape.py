@@ -30,7 +30,7 @@ class MDPGapE(OLOP):
 
     # PerEpisodeEvaluation has no kind that plans MDP-GapE on one model per episode; it must refuse this subclass of OLOP,
     # not run OLOP in its place
-    per_episode_entry_point = None
+    per_episode_kind = None
 
     def __init__(self, env, config=None):
         super(MDPGapE, self).__init__(env, config)

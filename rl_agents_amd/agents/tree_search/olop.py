@@ -110,18 +110,13 @@ class OLOP(AbstractPlanner):
         model.set_episode_rules(getattr(mdp, "done_rule", "source"), 0)
         return model
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
+    per_episode_kind = "olop"
+    draws_survive_errors = True
+
+    def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None):
         """``root_steps`` is accepted for the common interface: the step limit ends no OLOP episode (done = terminated)."""
         cfg = self.config
         episodes, horizon = int(cfg["episodes"]), int(cfg["horizon"])        # KeyError without "episodes" (olop.py:95)
-        model = self.model_for(state)
-        # a dense / sparse model: the episodes sample it with the clone's generator (mp_olop_plan_stochastic)
-        stochastic = model.mode in (native.MODE_STOCHASTIC, native.MODE_SPARSE)
-        olop_plan = self.models.ctx.olop_plan_stochastic if stochastic else self.models.ctx.olop_plan
-        self.about_to_plan()
-        n = len(root_states)
-        if rng_states is None:
-            rng_states = self.batch_rng_states(n)
         kl = cfg["upper_bound"]["type"] == "kullback-leibler"
         if kl:
             if cfg["upper_bound"]["time"] not in ("global", "local"):
@@ -132,34 +127,40 @@ class OLOP(AbstractPlanner):
             thresholds = np.zeros(0, np.float64)
         # "uniform": a random new child; anything else: action 0 of the environment, in the device's labels
         continuation = -1 if cfg["continuation_type"] == "uniform" else int(self.device_actions([0], model)[0])
-        out = olop_plan(model, root_states, episodes, horizon, cfg["gamma"], kl, continuation, thresholds,
-                        self._value_upper_init, rng_states, max_plan_len=max(horizon, 1))
+        args = (model, root_states, episodes, horizon, cfg["gamma"], kl, continuation, thresholds, self._value_upper_init, rng_states)
+        if model.mode in (native.MODE_STOCHASTIC, native.MODE_SPARSE):
+            # a dense / sparse model: the episodes sample it with the clone's generator (one model for every root)
+            return self.models.ctx.olop_plan_stochastic(*args, max_plan_len=max_plan_len)
+        return self.models.ctx.olop_plan(*args, max_plan_len=max_plan_len, model_index=model_index)
+
+    @staticmethod
+    def raise_for_status(status):
+        status = np.asarray(status)
+        failed = np.flatnonzero(status != native.MP_OK)
+        if failed.size:
+            if status[failed[0]] == native.ERR_OLOP_KEY:
+                raise KeyError(0)                                                           # olop.py:89
+            raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # olop.py:133-134
+
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
+        if "episodes" not in self.config:    # (olop.py:95; raised here, before anything is uploaded)
+            raise KeyError("episodes")
+        horizon = int(self.config["horizon"])
+        model = self.model_for(state)
+        self.about_to_plan()
+        if rng_states is None:
+            rng_states = self.batch_rng_states(len(root_states))
+        out = self.plan_on(model, root_states, root_steps, rng_states, max_plan_len=max(horizon, 1))
         # the reference's observations and generator draws up to the failing step are taken before it raises: the step
         # count is booked, and the records in `rng_states` are advanced, also on an error
         self.env_steps += int(out["env_steps"].sum())
-        failed = np.flatnonzero(out["status"] != native.MP_OK)
-        if failed.size:
-            if out["status"][failed[0]] == native.ERR_OLOP_KEY:
-                raise KeyError(0)                                                           # olop.py:89
-            raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # olop.py:133-134
+        self.raise_for_result(out)
         out["rng_states"] = rng_states
         self.relabel(out, model)
         self.last, self._root, self._last_model, self._last_actions = out, None, model, model.A
-        self._last_stochastic = stochastic
+        self._last_stochastic = model.mode in (native.MODE_STOCHASTIC, native.MODE_SPARSE)
         self.claim_device_tree()
         return out
-
-    def plan(self, state, observation):
-        """AbstractPlanner.plan, with the planner's generator written back also when the plan raises (the reference's
-        generator has made the draws of the episodes run before the error)."""
-        s0, steps0 = device_model.env_root_state(state)
-        rng = native.rng_state_from_generator(self.np_random).reshape(1, 6)
-        try:
-            out = self.plan_batch(state, [s0], [steps0], rng_states=rng)
-        finally:
-            native.generator_set_state(self.np_random, rng[0])
-        n = int(out["plan_len"][0])
-        return [int(a) for a in out["plans"][0, :n]]
 
     def export_tree(self, root=0):
         self.require_device_tree()

@@ -24,7 +24,7 @@ class SparseSampling(AbstractPlanner):
     """Sparse Sampling planner (sparse_sampling.py:11-28) for one or many roots of one finite MDP."""
     # PerEpisodeEvaluation refuses this planner: the device plans on one MDP per root (Context.ss_plan with model_index,
     # mp_ss_plan_models), but that loop has no kind that calls it yet
-    per_episode_entry_point = None
+    per_episode_kind = None
 
     def __init__(self, env, config=None):
         self.env = env

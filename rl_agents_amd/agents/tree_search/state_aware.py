@@ -90,11 +90,6 @@ class StateAwarePlanner(OptimisticDeterministicPlanner):
                              env_steps=d_env_steps, updates=self._d_updates, status=d_status)
         self.last, self._root = None, None
 
-    def raise_for_device_status(self, d_status, live):
-        bad = d_status[live]
-        if bad.numel():
-            self.raise_for_status(bad.cpu().numpy())
-
     @staticmethod
     def raise_for_status(status):
         """The reference's exceptions for the per-planner status codes."""

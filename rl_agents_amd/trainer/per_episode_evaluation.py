@@ -85,16 +85,12 @@ class PerEpisodeEvaluation(object):
         if not getattr(planner, "supports_per_episode_tables", True):
             raise NotImplementedError("per-episode tables: {} keeps its planner state (graph, bounds, state values) from plan to "
                                       "plan, and a kept state was built on the previous step's table".format(type(planner).__name__))
-        if getattr(planner, "per_episode_entry_point", True) is None:
+        # every planner class says what this loop does with it (AbstractPlanner.per_episode_kind)
+        self.subtree = False
+        self.kind = "vi" if self.vi else planner.per_episode_kind
+        if self.kind is None:
             raise NotImplementedError("per-episode tables: this loop has no kind that plans {} on one model per episode, "
                                       "and would run the optimistic planner in its place".format(type(planner).__name__))
-        from rl_agents_amd.agents.tree_search.brue import BRUE
-        from rl_agents_amd.agents.tree_search.olop import OLOP
-        # (BRUE first: it subclasses OLOP; both before the fallback, which runs the optimistic deterministic planner)
-        # (the robust planner subclasses the optimistic one and plans on its JointEnv of candidate models: before the fallback too)
-        self.subtree = False
-        self.kind = "vi" if self.vi else "brue" if isinstance(planner, BRUE) else "olop" if isinstance(planner, OLOP) else \
-            "ropd" if getattr(planner, "plans_on_joint_env", False) else ("uct" if hasattr(planner, "prior_policy") else "opd")
         if not self.vi:
             cfg = planner.config
             # MCTS keeps its subtrees as the reference does (abstract.py:172-206: count, value, children and stored priors of the
@@ -425,47 +421,13 @@ class PerEpisodeEvaluation(object):
                 pp, rp = policy_probabilities(planner.prior_policy, model.A), policy_probabilities(planner.rollout_policy, model.A)
                 out = self.ctx.uct_plan(model, states[idx], cfg["episodes"], cfg["horizon"], cfg["gamma"], cfg["temperature"], pp, rp,
                                         rng, root_steps=steps[idx], max_plan_len=1, model_index=idx)
-        elif self.kind == "olop":
-            episodes, horizon = int(cfg["episodes"]), int(cfg["horizon"])    # KeyError without "episodes" (olop.py:95)
-            kl = cfg["upper_bound"]["type"] == "kullback-leibler"
-            thresholds = planner.thresholds() if kl else np.zeros(0, np.float64)
-            # "uniform": a random new child; anything else: action 0 of the environment, in the device's labels
-            continuation = -1 if cfg["continuation_type"] == "uniform" else int(planner.device_actions([0], model)[0])
-            out = self.ctx.olop_plan(model, states[idx], episodes, horizon, cfg["gamma"], kl, continuation, thresholds,
-                                     planner._value_upper_init, rng, max_plan_len=1, model_index=idx)
-            self.rng[idx] = rng                         # (the draws made before a failing step are made: OLOP.plan_batch)
-            failed = np.flatnonzero(out["status"] != native.MP_OK)
-            if failed.size:
-                if out["status"][failed[0]] == native.ERR_OLOP_KEY:
-                    raise KeyError(0)                                                           # olop.py:89
-                raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # olop.py:133-134
-        elif self.kind == "brue":
-            horizon = int(cfg["horizon"])
-            out = self.ctx.brue_plan(model, states[idx], int(cfg["budget"]), horizon, cfg["gamma"],
-                                     planner.gamma_powers(cfg["gamma"], horizon), rng, model_index=idx)
-            self.rng[idx] = rng
-            if (out["plans"] < 0).any():
-                # no rollout was made (budget <= 0): the reference's np.amax([]) of the root's selection raises (brue.py:75)
-                raise ValueError("zero-size array to reduction operation maximum which has no identity")
-            out["plans"] = out["plans"].reshape(len(idx), 1)
-            out["plan_len"] = np.ones(len(idx), np.int32)
-        elif self.kind == "ropd":
-            budget = int(cfg["budget"])
-            if cfg["gamma"] == 1 and budget >= model.A:
-                raise ZeroDivisionError("float division by zero")           # gamma ** depth / (1 - gamma), deterministic.py:53
-            # (root i: set i, the joint state of its M models; the plans are the env's action ids -- the joint env lists ascending)
-            out = self.ctx.ropd_plan(model, states[idx], budget, cfg["gamma"], cfg.get("terminal_reward", 0), rng, max_plan_len=1,
-                                     model_index=idx)
-            if (out["status"] == native.ERR_REWARD_RANGE).any():
-                raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")     # deterministic.py:46-47
         else:
-            budget = int(cfg["budget"])
-            if cfg["gamma"] == 1 and budget >= model.A:
-                raise ZeroDivisionError("float division by zero")           # gamma ** depth / (1 - gamma), deterministic.py:53
-            out = self.ctx.opd_plan(model, states[idx], budget, cfg["gamma"], cfg.get("terminal_reward", 0), rng, max_plan_len=1,
-                                    model_index=idx)
-            if (out["status"] == native.ERR_REWARD_RANGE).any():
-                raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")     # deterministic.py:46-47
+            # the planner's own call: root i plans on MDP i (the robust planner: on set i, from the joint state of its M models;
+            # its plans are the env's action ids -- the joint env lists ascending) and its exceptions are the planner's
+            out = planner.plan_on(model, states[idx], steps[idx], rng, model_index=idx, max_plan_len=1)
+            if planner.draws_survive_errors:            # (the draws made before a failing step are made: OLOP.plan_batch)
+                self.rng[idx] = rng
+            planner.raise_for_result(out)
         self.rng[idx] = rng
         if (out["plan_len"] < 1).any():
             raise Exception("The agent did not plan any action")             # evaluation.py:168-170
