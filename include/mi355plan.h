@@ -34,6 +34,7 @@ extern "C" {
 #define MP_ERR_HIP (-1)          /* a HIP runtime call failed (message has the hipError string)  */
 #define MP_ERR_REWARD_RANGE (-2) /* OPD: reward outside [0,1] (deterministic.py:46-47 ValueError) */
 #define MP_ERR_GAPE_NO_CHALLENGER (-9) /* MDP-GapE status: the root lists one action (mdp_gape.py:247, max() of an empty list: ValueError) */
+#define MP_ERR_GAPE_PLACEHOLDERS (-10) /* MDP-GapE status: more next states observed than max_next_states_count (mdp_gape.py:284 ValueError) */
 #define MP_ERR_ALLOC (-3)
 #define MP_ERR_ARG (-4)          /* invalid argument / unsupported configuration                  */
 #define MP_ERR_MODE (-5)         /* model kind not valid for this call ("Unknown mode")           */
@@ -658,6 +659,50 @@ const char *mp_gape_form_names(void);
 int mp_gape_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, uint8_t *kind, int32_t *parent, int32_t *action,
                         int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *mu_lcb,
                         double *value_upper, double *value_lower, uint8_t *done, int32_t *state);
+
+/*
+ * MDPGapE.plan with a KL confidence region over every chance node's next-state distribution: max_next_states_count =
+ * max_next_states in 1..32, on a deterministic table, a dense or a sparse model.  Everything mp_gape_plan does, and:
+ *   - the clone is re-seeded per episode from the planner's draw (mdp_gape.py:67): Generator(PCG64(SeedSequence(x))), and a step
+ *     of a dense / sparse model draws one double of it (a deterministic table draws nothing).  A decision node stands for one
+ *     observed state and lists that state's actions (:162-170);
+ *   - a chance node gets max_next_states placeholder decision children at its first get_child (:267-270: mu_ucb 1, mu_lcb 0,
+ *     value_upper the initial value of depth + 1, value_lower 0); a state not seen before takes the lowest placeholder left
+ *     (:277-282), and status MP_ERR_GAPE_PLACEHOLDERS where none is left (:284-285 ValueError), after the step was counted;
+ *   - a chance node's backup (:288-305): over its children in the reference's dict order -- the placeholders left, then the
+ *     observed states by first observation -- u_next = mu_ucb + gamma * value_upper, l_next = mu_lcb + gamma * value_lower,
+ *     p_hat = count / the node's count, threshold = transition_thr_by_count[count - 1] / count; value_upper = p_plus @ u_next
+ *     and value_lower = p_minus @ l_next for p_plus = max_expectation_under_constraint(u_next, p_hat, threshold) and
+ *     p_minus = (-l_next, p_hat, threshold) (utils.py:292-342 with newton_iteration :150-203), every branch with numpy's
+ *     semantics.  The two solves run side by side in the halves of the wavefront.
+ *   transition_thr_by_count double [episodes + 2]: transition_threshold() (:307-313) for a chance node of count c at [c - 1].
+ * Results as mp_gape_plan.  MP_ERR_MODE for a CartPole, joint, batch or row-block model; MP_ERR_ARG for max_next_states outside
+ * 1..32, for a gamma, accuracy, threshold of either table or initial value that is not finite, and when the node bound
+ * 1 + (episodes + 2) * horizon * max_next_states + (1 + (episodes + 2) * horizon) * |A| does not fit a 32-bit index or 1 GiB.
+ * At max_next_states 1 on a deterministic table every result equals mp_gape_plan's bit for bit.  mp_last_kernel_variant records
+ * one of mp_gape_stoch_form_names: "gape_stoch_{table,dense,sparse}[_slots]" (part of no other list).
+ */
+int mp_gape_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes,
+                            int32_t horizon, int32_t max_next_states, double gamma, double accuracy, int32_t continuation,
+                            int32_t n_actions_env, const int32_t *action_column, const double *thr_by_count,
+                            const double *transition_thr_by_count, const double *value_init, uint64_t *rng_state,
+                            int32_t max_plan_len, int32_t *plans, int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps,
+                            int32_t *status, double *child_lower, double *child_upper, int64_t *child_count,
+                            int32_t *best_challenger, int32_t mem);
+const char *mp_gape_stoch_form_names(void);
+/* Tree of root `root` after the last mp_gape_plan_stochastic, BREADTH FIRST over decision and chance nodes, a node's children in
+ * the reference's dict order (a chance node's: the placeholders left in number order, then the observed states by first
+ * observation, mdp_gape.py:281).  The fields of mp_gape_tree_export; `parent` is a position of this listing; the action of a
+ * decision node is its observed state, or -1 - i for placeholder_i (state -1).  At most the node bound of the plan call; *n_nodes
+ * is set also when `cap` is too small.  The tree of a root whose status is not MP_OK is what the plan had built when it stopped. */
+int mp_gape_stoch_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, uint8_t *kind, int32_t *parent,
+                              int32_t *action, int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb,
+                              double *mu_lcb, double *value_upper, double *value_lower, uint8_t *done, int32_t *state);
+/* What the DEVICE computes for max_expectation_under_constraint (utils.py:292-342; csrc/kl_transition.hpp) on n problems of
+ * width K in 1..32, two problems per wavefront as in the planner: f, q double [n][K], c double [n] -> p_star double [n][K], the
+ * Newton iterations and the decisions taken (the KT_* bits of kl_transition.hpp) int32 [n].  Host arrays. */
+int mp_selftest_gape_transition(mp_ctx *ctx, int32_t n, int32_t K, const double *f, const double *q, const double *c,
+                                double *p_star, int32_t *iterations, int32_t *decisions);
 
 /* ---------------------------------------------------------------- BRUE ---------------------- */
 /*

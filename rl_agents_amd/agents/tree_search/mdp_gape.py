@@ -1,18 +1,26 @@
 """MDP-GapE, best-arm identification MCTS, on the MI355X planning core (reference
-``rl_agents/agents/tree_search/mdp_gape.py``); the episodes run in ``mp_gape_plan`` (rl_agents_amd/csrc/gape.hip).
+``rl_agents/agents/tree_search/mdp_gape.py``); the episodes run in ``mp_gape_plan`` (rl_agents_amd/csrc/gape.hip) and
+``mp_gape_plan_stochastic`` (rl_agents_amd/csrc/gape_stoch.hip).
 
-Same class names, config keys and results as the reference on deterministic finite-MDP tables with
-``max_next_states_count: 1`` (``HighwayEnv/agents/MDPGapEAgent/baseline.json``).  The host computes the budget split, the
-initial values by depth (Python ``**``) and the bound's threshold by count (``eval`` of the config string) -- every constant
-that is not a basic IEEE operation.  The device computes both KL bounds' Newton iterations with its own ``log``: bounds and
-values agree with the reference within 1e-12 / (1 - gamma), and every discrete output -- the plan, the episodes run, the
-tree's shape and counts, the generator record -- is identical wherever the reference's comparisons do not hang on the last
-bits of a bound (DESIGN.md).
+Same class names, config keys and results as the reference.  The host computes the budget split, the initial values by depth
+(Python ``**``) and both thresholds by count (``eval`` of the config strings) -- every constant that is not a basic IEEE
+operation.  The device computes the KL bounds' Newton iterations and the transition bound with its own ``log`` / ``exp``:
+bounds and values agree with the reference within 1e-12 / (1 - gamma), and every discrete output -- the plan, the episodes run,
+the tree's shape and counts, the generator record -- is identical wherever the reference's comparisons do not hang on the last
+bits of a bound (DESIGN.md 4.12, 4.13).
 
-Refused: ``stochastic`` / ``sparse`` models (TypeError) and ``max_next_states_count != 1`` (NotImplementedError) -- the
-transition bounds of the reference (``max_expectation_under_constraint``) go through numpy's vectorised ``exp`` / ``log`` and
-BLAS, which no restatement can be held to; ``step_strategy: "subtree"`` (NotImplementedError at ``reset``); a bound type other
-than ``"kullback-leibler"`` (ValueError: the reference only logs an error and plans on infinite bounds).
+``MDPGapE`` / ``MDPGapEAgent``: deterministic finite-MDP tables with ``max_next_states_count: 1``
+(``HighwayEnv/agents/MDPGapEAgent/baseline.json``).  They refuse ``stochastic`` / ``sparse`` models (TypeError) and
+``max_next_states_count != 1`` (NotImplementedError), as they always have.
+
+``StochasticMDPGapE`` / ``StochasticMDPGapEAgent``: ``max_next_states_count`` 1..32 on deterministic tables and on
+``stochastic`` / ``sparse`` models -- the reference's other three MDP-GapE configs.  A chance node's placeholder children, their
+dict order and ``max_expectation_under_constraint`` with its Newton iteration run on the device.  The two classes are defined in
+``rl_agents_amd/gape_stochastic.py`` and served from this module by name.
+
+Refused by both: ``step_strategy: "subtree"`` (NotImplementedError at ``reset``); a bound type other than
+``"kullback-leibler"`` (ValueError: the reference only logs an error and plans on infinite bounds); one model per episode
+(``PerEpisodeEvaluation``).  By the stochastic planner also ``max_next_states_count`` above 32 (NotImplementedError).
 """
 import logging
 
@@ -279,3 +287,19 @@ class MDPGapEAgent(OLOPAgent):
 
     def record(self, state, action, reward, next_state, done, info):
         self.planner.next_observation = next_state
+
+
+# StochasticMDPGapE, StochasticMDPGapEAgent, build_gape_stoch_tree and PLACEHOLDERS_MESSAGE live in rl_agents_amd/gape_stochastic.py
+# (which imports this module) and are served from here by name, so that an agent config names them beside MDPGapEAgent.
+_STOCHASTIC_NAMES = ("StochasticMDPGapE", "StochasticMDPGapEAgent", "build_gape_stoch_tree", "PLACEHOLDERS_MESSAGE")
+
+
+def __getattr__(name):
+    if name in _STOCHASTIC_NAMES:
+        from rl_agents_amd import gape_stochastic
+        return getattr(gape_stochastic, name)
+    raise AttributeError("module {!r} has no attribute {!r}".format(__name__, name))
+
+
+def __dir__():
+    return sorted(set(globals()) | set(_STOCHASTIC_NAMES))

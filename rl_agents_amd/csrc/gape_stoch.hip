@@ -1,0 +1,514 @@
+// gape_stoch.hip -- MDP-GapE with a KL confidence region over every chance node's next-state distribution
+// (tree_search/mdp_gape.py:60-110, :252-313; utils.py:292-342), for max_next_states_count K in 1..32 on deterministic tables
+// and on dense [S,A,S] / sparse [S,A,B] models.  gape.hip keeps the corner K = 1 on deterministic tables (mp_gape_plan).
+//
+// Mapping as gape.hip: ONE ROOT PER WAVEFRONT (a 64-lane workgroup), the workgroups striding over the roots.  What differs:
+//   * the clone is re-seeded per episode (state.seed(np_random.randint(2**30)), :67): Generator(PCG64(SeedSequence(x))) made on
+//     the device (seed_sequence.hpp), and a step of a dense / sparse model draws one double of it and finds the next state by the
+//     ballot row search over ceil(cdf * 2^53), as olop_stoch_kernel.  A deterministic table reads no draw, so none is made;
+//   * a decision node belongs to ONE observation: its state is the record's, and expand lists that state's actions;
+//   * a chance node gets K placeholder decision children at its first get_child (:267-270), K contiguous records.  The j-th
+//     state observed takes placeholder j, the lowest left (:277-285), so with m states observed the reference's dict --
+//     placeholders left in number order, then the observed states by first observation -- is the records m .. K-1, 0 .. m-1:
+//     lane i reads record (i + m) mod K, two contiguous runs.  The lookup of an observation is one ballot over m lanes;
+//   * a chance node's backup (:288-305) is the pair of transition bounds of kl_transition.hpp, the upper solve in lanes 0..31
+//     and the lower solve in lanes 32..63 of the same instructions, then p @ next by the same half-wave sums.
+// Decision and chance nodes are records of ONE array (GsNode) with their two values in a second one, [cap][2], which is what
+// the lanes read of a node's children.  A step makes at most K decision and |A| chance records, the root |A| more:
+// cap = 1 + (episodes + 2) * horizon * K  +  (1 + (episodes + 2) * horizon) * |A|.
+// The KL bounds of the path's decision nodes stay deferred to after the walk, 64 at a time; thresholds by count (both tables)
+// and the initial values come from the host.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "each_host.hpp"
+#include "gape_select.hpp"
+#include "kl_bound.hpp"
+#include "kl_transition.hpp"
+#include "pcg64.hpp"
+#include "seed_sequence.hpp"
+#include "wave.hpp"
+#include "wave_host.hpp"
+
+namespace mp {
+
+constexpr size_t kGapeStochKeepBytes = (size_t)1 << 30; // trees of every root kept while they fit (the rule of mp_gape_plan)
+constexpr int kGapeStochTreeKind = 9;
+
+struct GsNode {
+    double cum, mu_ucb, mu_lcb;  // a decision node's cumulative_reward, mu_ucb, mu_lcb (olop.py:109-116, mdp_gape.py:139-143)
+    int32_t count;               // visits
+    int32_t key;                 // decision: the observed state, -1 - i while it is placeholder_i; chance: the action (a column)
+    int32_t parent, first_child, n_children;
+    int32_t depth, done, kind;   // kind 0 decision, 1 chance (a chance node has its parent's depth)
+    int32_t n_assigned, pad;     // chance: the children that stand for an observed state
+};
+static_assert(sizeof(GsNode) == 64, "GsNode layout");
+
+struct GapeStochArgs {
+    int n_roots, A, M, H, K, cap, done_on_next, uniform, n_env, keep, grid, max_plan_len, mode, W;
+    double gamma, accuracy;
+    const Rec *rec;          // deterministic tables
+    const uint64_t *thr;     // dense [S*A][S] / sparse [S*A][B]: ceil(cdf * 2^53)
+    const int32_t *nxt;      // sparse: successors [S*A][B]
+    const double *R;         // reward [S*A] (dense / sparse)
+    const uint8_t *term;     // terminal [S] or nullptr (dense / sparse)
+    const uint8_t *avail;    // [S*A] actions the env lists, or nullptr: all (dense / sparse)
+    const int32_t *root_state;
+    const double *bthr;      // [M + 2] the reward bound's threshold by count - 1
+    const double *tthr;      // [M + 2] transition_threshold() by count - 1 (the kernel divides by the count, :299)
+    const double *vinit;     // [H + 1] (1 - gamma ** (H - d)) / (1 - gamma)
+    const double *col;       // [n_env] the column of environment action a, -1 without one
+    uint64_t *rng;
+    GsNode *nodes;           // [slots][cap]
+    double *val;             // [slots][cap][2] value_upper, value_lower of every node
+    int32_t *n_nodes_out;
+    int32_t *plans, *plan_len, *episodes_run, *status, *arms;
+    int64_t *env_steps, *child_count;
+    double *child_lower, *child_upper;
+};
+
+__global__ __launch_bounds__(64) void gape_stoch_kernel(GapeStochArgs p)
+{
+    extern __shared__ int32_t path[]; // [2 * H + 1] records of the episode's walk: decision, chance, decision, ...
+    const int lane = threadIdx.x, A = p.A, H = p.H, K = p.K, W = p.W;
+    const bool table = p.mode == MP_MODE_DETERMINISTIC;
+    const uint32_t done_bit = p.done_on_next ? 2u : 1u;
+    for (int root = blockIdx.x; root < p.n_roots; root += p.grid) {
+        const long slot = p.keep ? root : (root == 0 ? p.grid : blockIdx.x);
+        GsNode *N = p.nodes + slot * p.cap;
+        double *V = p.val + slot * p.cap * 2;
+        if (lane == 0) {
+            GsNode r;
+            r.cum = 0.0; r.mu_ucb = 1.0; r.mu_lcb = 0.0; r.count = 0; r.key = p.root_state[root]; r.parent = -1; r.first_child = -1;
+            r.n_children = 0; r.depth = 0; r.done = 0; r.kind = 0; r.n_assigned = 0; r.pad = 0;
+            N[0] = r;
+            V[0] = p.vinit[0]; V[1] = 0.0;
+        }
+        __syncthreads();
+        Pcg64 gen;
+        gen.load(p.rng + (long)root * 6);
+        int n_nodes = 1, status = MP_OK, episodes_run = 0, best = -1, challenger = -1;
+        long steps = 0;
+
+        // DecisionNode.expand (mdp_gape.py:162-170): a chance child per action the node's state lists, in listing order; *rank =
+        // the position of column `col` among them, -1 when it is not listed.  -1 when the records would not fit (not reached).
+        auto expand = [&](int node, int state, int depth, int col, int *rank) {
+            const int fc = n_nodes;
+            int pos0 = 0;
+            *rank = -1;
+            if (n_nodes + A > p.cap) return -1;
+            for (int a0 = 0; a0 < A; a0 += 64) {
+                const int a = a0 + lane;
+                bool av = false;
+                if (a < A) av = table ? (p.rec[(long)state * A + a].flags & 4u) != 0 : (!p.avail || p.avail[(long)state * A + a] != 0);
+                const unsigned long long bal = __ballot(av);
+                const int pos = pos0 + __popcll(bal & ((1ull << lane) - 1ull));
+                if (av) {
+                    GsNode c;
+                    c.cum = 0.0; c.mu_ucb = 0.0; c.mu_lcb = 0.0; c.count = 0; c.key = a; c.parent = node; c.first_child = -1;
+                    c.n_children = 0; c.depth = depth; c.done = 0; c.kind = 1; c.n_assigned = 0; c.pad = 0;
+                    N[fc + pos] = c;
+                    V[2 * (long)(fc + pos)] = p.vinit[depth]; // a chance node has its parent's depth (mdp_gape.py:256-258)
+                    V[2 * (long)(fc + pos) + 1] = 0.0;
+                }
+                if (col >= a0 && col < a0 + 64 && ((bal >> (col - a0)) & 1ull))
+                    *rank = pos0 + __popcll(bal & ((1ull << (col - a0)) - 1ull));
+                pos0 += __popcll(bal);
+            }
+            if (lane == 0) { N[node].first_child = fc; N[node].n_children = pos0; }
+            n_nodes += pos0;
+            __syncthreads();
+            return pos0;
+        };
+
+        for (int e = 0; e < p.M + 2 && status == MP_OK; ++e) {
+            const uint32_t x = gen.below(1u << 30); // state.seed(self.np_random.randint(2**30)), mdp_gape.py:67
+            Pcg64U eg;                              // Generator(PCG64(SeedSequence(x))) of the clone
+            eg.s_hi = eg.s_lo = eg.inc_hi = eg.inc_lo = 0; eg.has_uint32 = eg.uinteger = 0;
+            if (!table) {
+                uint64_t rec6[6];
+                seed_sequence_record(&x, 1, rec6);
+                eg.s_hi = Pcg64U::uni(rec6[0]); eg.s_lo = Pcg64U::uni(rec6[1]);
+                eg.inc_hi = Pcg64U::uni(rec6[2]); eg.inc_lo = Pcg64U::uni(rec6[3]);
+            }
+            if (N[0].n_children == 0) {
+                int unused;
+                if (expand(0, N[0].key, 0, -1, &unused) < 0) { status = MP_ERR_ARG; break; }
+            }
+            int node = 0;
+            if (lane == 0) path[0] = 0;
+            for (int h = 0; h < H; ++h) {
+                const GsNode nd = N[node];
+                const int s = nd.key;
+                int fc = nd.first_child, k = nd.n_children, j;
+                if (node == 0) { // sampling_rule at the root: the arm best-arm identification selects (mdp_gape.py:185-187)
+                    if (k < 2) { status = MP_ERR_GAPE_NO_CHALLENGER; break; } // max() of an empty list (:247)
+                    gape_bai(V + 2 * (long)fc, k, lane, &j, &best, &challenger);
+                } else if (k > 0) {
+                    j = gape_random_argmax(V + 2 * (long)fc, k, lane, gen);
+                    if (j < 0) { status = MP_ERR_ARG; break; } // a NaN bound below the root: np_random.choice([]) raises
+                } else {
+                    // a childless node: randint(action_space.n) over ALL actions or action 0 (:194-196), then get_child expands
+                    // and gives an unlisted action up for the first listed one (:155-160)
+                    const int a_env = p.uniform ? (int)gen.below((uint32_t)p.n_env) : 0;
+                    const int col = a_env < p.n_env ? (int)p.col[a_env] : -1;
+                    int rank;
+                    fc = n_nodes;
+                    k = expand(node, s, nd.depth, col, &rank);
+                    if (k < 0) { status = MP_ERR_ARG; break; }
+                    j = rank >= 0 ? rank : 0;
+                }
+                const int ch = fc + j;
+                const GsNode c0 = N[ch];
+                // the model step
+                const long sa = (long)s * A + c0.key;
+                int sn;
+                double r;
+                bool step_done;
+                if (table) {
+                    const Rec rc = p.rec[sa];
+                    sn = rc.next; r = rc.reward; step_done = (rc.flags & done_bit) != 0;
+                } else {
+                    const uint64_t u = eg.next64() >> 11;          // Generator.random() of the clone's generator
+                    const uint64_t *trow = p.thr + sa * W;
+                    int lo = 0;                                    // searchsorted(cdf, u, 'right') = #{j : thr_j <= u}
+                    for (int j0 = 0; j0 < W; j0 += 64) {
+                        const int jj = j0 + lane;
+                        const unsigned long long bal = __ballot(jj < W && trow[jj] <= u);
+                        lo += __popcll(bal);
+                        if (bal != ~0ull) break;
+                    }
+                    if (lo >= W) lo = W - 1;                       // (u < 1 = cdf[-1]: not reached)
+                    sn = p.mode == MP_MODE_SPARSE ? p.nxt[sa * W + lo] : lo;
+                    r = p.R[sa];
+                    step_done = p.term ? (p.done_on_next ? p.term[sn] != 0 : p.term[s] != 0) : false;
+                }
+                ++steps;
+                // ChanceNode.get_child (:272-286): the placeholders at the first call, then the observation among the assigned
+                // children or the lowest placeholder left
+                int dfc = c0.first_child, m = c0.n_assigned;
+                if (c0.n_children == 0) {
+                    if (n_nodes + K > p.cap) { status = MP_ERR_ARG; break; } // (not reached: the bound of mp_gape_plan_stochastic)
+                    dfc = n_nodes;
+                    if (lane < K) {
+                        GsNode d;
+                        d.cum = 0.0; d.mu_ucb = 1.0; d.mu_lcb = 0.0; d.count = 0; d.key = -1 - lane; d.parent = ch; d.first_child = -1;
+                        d.n_children = 0; d.depth = nd.depth + 1; d.done = 0; d.kind = 0; d.n_assigned = 0; d.pad = 0;
+                        N[dfc + lane] = d;
+                        V[2 * (long)(dfc + lane)] = p.vinit[nd.depth + 1];
+                        V[2 * (long)(dfc + lane) + 1] = 0.0;
+                    }
+                    n_nodes += K;
+                    __syncthreads();
+                }
+                const unsigned long long hit = __ballot(lane < m && N[dfc + lane].key == sn);
+                int dec;
+                bool assigned = false;
+                if (hit) dec = dfc + __ffsll((long long)hit) - 1;
+                else if (m < K) { dec = dfc + m; assigned = true; }
+                else { status = MP_ERR_GAPE_PLACEHOLDERS; break; } // :284-285, after the step was counted
+                if (lane == 0) { // ChanceNode.update (:264-265) and what get_child did
+                    GsNode c = c0;
+                    c.count += 1; c.first_child = dfc; c.n_children = K; c.n_assigned = m + (assigned ? 1 : 0);
+                    N[ch] = c;
+                    if (assigned) N[dec].key = sn;
+                    path[2 * h + 1] = ch; path[2 * h + 2] = dec;
+                }
+                if (!(0.0 <= r && r <= 1.0)) { status = MP_ERR_REWARD_RANGE; break; } // olop.py:133-134
+                if (lane == 0) { // OLOPNode.update (olop.py:132-142)
+                    GsNode d = N[dec];
+                    if (step_done) d.done = 1;
+                    d.cum += d.done ? 0.0 : r;
+                    d.count += 1;
+                    N[dec] = d;
+                }
+                node = dec;
+                __syncthreads();
+            }
+            if (status != MP_OK) break;
+            // compute_reward_ucb (mdp_gape.py:200-210) of the path's decision nodes: H upper bounds, then H lower bounds
+            for (int t0 = 0; t0 < 2 * H; t0 += 64) {
+                const int t = t0 + lane;
+                if (t < 2 * H) {
+                    const bool lower = t >= H;
+                    GsNode *c = N + path[2 * (lower ? t - H : t) + 2];
+                    const double thr = p.bthr[c->count - 1];
+                    if (lower) c->mu_lcb = kl_upper_bound<false, true>(c->cum, c->count, thr);
+                    else c->mu_ucb = kl_upper_bound<false, false>(c->cum, c->count, thr);
+                }
+            }
+            __syncthreads();
+            // backup_to_root (:214-226, :288-305), from the depth-H decision node up: decision, chance, decision, ...
+            for (int h = H; h >= 0; --h) {
+                const int id = path[2 * h];
+                const GsNode nd = N[id];
+                double vu = 0.0, vl = 0.0; // the depth-H node has no children
+                if (nd.n_children > 0) {
+                    vu = gape_amax(V + 2 * (long)nd.first_child, nd.n_children, 0, lane);
+                    vl = gape_amax(V + 2 * (long)nd.first_child, nd.n_children, 1, lane);
+                }
+                if (lane == 0) { V[2 * (long)id] = vu; V[2 * (long)id + 1] = vl; }
+                __syncthreads();
+                if (h == 0) break;
+                // the chance node above: lanes 0..31 solve for value_upper (f = u_next), lanes 32..63 for value_lower (f = -l_next)
+                const int ch = path[2 * h - 1];
+                const GsNode cn = N[ch];
+                const int li = lane & 31;
+                const double c = p.tthr[cn.count - 1] / (double)cn.count;
+                const bool lower = lane >= 32;
+                double f = 0.0, q = 0.0, next = 0.0;
+                if (li < K) {
+                    const long i = cn.first_child + (li + cn.n_assigned) % K; // the reference's dict order
+                    const GsNode d = N[i];
+                    next = lower ? d.mu_lcb + p.gamma * V[2 * i + 1] : d.mu_ucb + p.gamma * V[2 * i];
+                    f = lower ? -next : next;
+                    q = (double)d.count / (double)cn.count;
+                }
+                const double ps = kl_transition_p<false>(f, q, c, K, lane);
+                const double v = kt_half_sum(li < K ? ps * next : 0.0);
+                if (li == 0) V[2 * (long)ch + (lower ? 1 : 0)] = v;
+                __syncthreads();
+            }
+            // the stopping rule (:100-102) on the root's best arm and challenger
+            const int fc0 = N[0].first_child;
+            int sel;
+            gape_bai(V + 2 * (long)fc0, N[0].n_children, lane, &sel, &best, &challenger);
+            episodes_run = e + 1;
+            if (V[2 * (long)(fc0 + challenger)] - V[2 * (long)(fc0 + best) + 1] < p.accuracy) break;
+        }
+        __syncthreads();
+        // get_plan (:129-131): the best arm's action; the root's arms for the caller
+        const int fc0 = N[0].first_child, k0 = N[0].n_children;
+        for (int a = lane; a < A; a += 64) {
+            if (p.child_count) p.child_count[(long)root * A + a] = -1;
+            if (p.child_lower) p.child_lower[(long)root * A + a] = 0.0;
+            if (p.child_upper) p.child_upper[(long)root * A + a] = 0.0;
+        }
+        __syncthreads();
+        for (int i = lane; i < k0; i += 64) {
+            const GsNode c = N[fc0 + i];
+            if (p.child_count) p.child_count[(long)root * A + c.key] = c.count;
+            if (p.child_lower) p.child_lower[(long)root * A + c.key] = V[2 * (long)(fc0 + i) + 1];
+            if (p.child_upper) p.child_upper[(long)root * A + c.key] = V[2 * (long)(fc0 + i)];
+        }
+        if (lane == 0) {
+            const bool ok = status == MP_OK && best >= 0;
+            gen.store(p.rng + (long)root * 6);
+            if (p.plans)
+                for (int i = 0; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = ok && i == 0 ? N[fc0 + best].key : -1;
+            if (p.plan_len) p.plan_len[root] = ok ? 1 : 0;
+            if (p.episodes_run) p.episodes_run[root] = episodes_run;
+            if (p.status) p.status[root] = status;
+            if (p.env_steps) p.env_steps[root] = steps;
+            if (p.arms) {
+                p.arms[2 * (long)root] = ok ? N[fc0 + best].key : -1;
+                p.arms[2 * (long)root + 1] = ok ? N[fc0 + challenger].key : -1;
+            }
+            p.n_nodes_out[root] = n_nodes;
+        }
+        __syncthreads();
+    }
+}
+
+// mp_selftest_gape_transition: problem i in half (i & 1) of workgroup i / 2
+__global__ __launch_bounds__(64) void gape_transition_selftest_kernel(int n, int K, const double *__restrict__ f,
+                                                                      const double *__restrict__ q, const double *__restrict__ c,
+                                                                      double *__restrict__ p_star, int32_t *__restrict__ iterations,
+                                                                      int32_t *__restrict__ decisions)
+{
+    const int lane = threadIdx.x, li = lane & 31;
+    const long i = (long)blockIdx.x * 2 + (lane >> 5);
+    const bool live = i < n && li < K;
+    const double fv = live ? f[i * K + li] : 0.0, qv = live ? q[i * K + li] : 0.0, cv = i < n ? c[i] : 0.0;
+    int its, mask;
+    const double ps = kl_transition_p<true>(fv, qv, cv, K, lane, &its, &mask);
+    if (live) p_star[i * K + li] = ps;
+    if (i < n && li == 0) { iterations[i] = its; decisions[i] = mask; }
+}
+
+inline FormName gape_stoch_form_name(int mode, bool keep)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "gape_stoch_%s%s", mode == MP_MODE_DETERMINISTIC ? "table" : mode == MP_MODE_SPARSE ? "sparse" : "dense",
+             keep ? "" : "_slots");
+    return n;
+}
+
+} // namespace mp
+
+using namespace mp;
+
+extern "C" {
+
+int mp_gape_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes,
+                            int32_t horizon, int32_t max_next_states, double gamma, double accuracy, int32_t continuation,
+                            int32_t n_actions_env, const int32_t *action_column, const double *thr_by_count,
+                            const double *transition_thr_by_count, const double *value_init, uint64_t *rng_state,
+                            int32_t max_plan_len, int32_t *plans, int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps,
+                            int32_t *status, double *child_lower, double *child_upper, int64_t *child_count,
+                            int32_t *best_challenger, int32_t mem)
+{
+    const char *const who = "mp_gape_plan_stochastic";
+    if (!ctx || !model || !root_state || !rng_state || !thr_by_count || !transition_thr_by_count || !value_init)
+        return fail(MP_ERR_ARG, "%s: NULL argument", who);
+    int rmem;
+    MP_TRY(wave_mem(who, &mem, &rmem));
+    MP_TRY(wave_mdp_check(who, model, false)); // (a CartPole model is no finite MDP: MP_ERR_MODE)
+    const int A = model->A, K = max_next_states;
+    if (n_roots < 1 || episodes < 0 || horizon < 1 || horizon > 8192 || max_plan_len < 0 || A < 1 || n_actions_env < 1)
+        return fail(MP_ERR_ARG, "%s: bad sizes", who);
+    if (K < 1 || K > 32) return fail(MP_ERR_ARG, "%s: max_next_states_count %d is not in 1..32 (a chance node's children fill half a wavefront)", who, K);
+    // a NaN among them would make NaN bounds of every node, which the reference plans on and no plan is worth
+    if (!isfinite(gamma) || !isfinite(accuracy)) return fail(MP_ERR_ARG, "%s: gamma and accuracy must be finite", who);
+    for (int c = 0; c < episodes + 2; ++c) {
+        if (!isfinite(thr_by_count[c])) return fail(MP_ERR_ARG, "%s: the threshold of count %d is not finite", who, c + 1);
+        if (!isfinite(transition_thr_by_count[c])) return fail(MP_ERR_ARG, "%s: the transition threshold of count %d is not finite", who, c + 1);
+    }
+    for (int d = 0; d <= horizon; ++d)
+        if (!isfinite(value_init[d])) return fail(MP_ERR_ARG, "%s: the initial value of depth %d is not finite", who, d);
+    if (continuation != 0 && continuation != 1) return fail(MP_ERR_ARG, "%s: continuation %d is neither 0 (action 0) nor 1 (uniform)", who, continuation);
+    if (!action_column && n_actions_env != A)
+        return fail(MP_ERR_ARG, "%s: %d environment actions need their columns among the model's %d", who, n_actions_env, A);
+    for (int a = 0; action_column && a < n_actions_env; ++a)
+        if (action_column[a] < -1 || action_column[a] >= A) return fail(MP_ERR_ARG, "%s: column %d out of range", who, action_column[a]);
+    MP_TRY(wave_roots(ctx, who, root_state, n_roots, model->S, mem));
+    // every step of every episode may give a chance node its K placeholders and expand one decision node; the root expands once
+    const long long per = ((long long)episodes + 2) * horizon;
+    const long long cap = 1 + per * K + (1 + per) * A;
+    if (cap > 0x7fffffffLL) return fail(MP_ERR_ARG, "%s: %lld nodes per tree do not fit a 32-bit index", who, cap);
+    if ((size_t)cap * (sizeof(GsNode) + 2 * sizeof(double)) > kGapeStochKeepBytes)
+        return fail(MP_ERR_ARG, "%s: %lld nodes per tree take more than 1 GiB", who, cap);
+    GapeStochArgs a;
+    MP_TRY(wave_mdp(ctx, who, model, &a));
+
+    // one table: both thresholds by count [M + 2] each, the initial values [H + 1], the columns of the environment's actions
+    const size_t M2 = (size_t)episodes + 2;
+    std::vector<double> tab(2 * M2 + horizon + 1 + n_actions_env);
+    for (size_t c = 0; c < M2; ++c) { tab[c] = thr_by_count[c]; tab[M2 + c] = transition_thr_by_count[c]; }
+    for (int d = 0; d <= horizon; ++d) tab[2 * M2 + d] = value_init[d];
+    for (int e = 0; e < n_actions_env; ++e) tab[2 * M2 + horizon + 1 + e] = action_column ? action_column[e] : e;
+    double *d_tab = nullptr;
+    MP_TRY(upload_tables(ctx, 43, tab, &d_tab));
+
+    // the launch of mp_gape_plan with a path of 2 * horizon + 1 records in LDS
+    const EachForm form = each_form_global(EACH_OLOP, 2 * horizon, n_roots, ctx->prop.multiProcessorCount);
+    a.n_roots = n_roots; a.A = A; a.M = episodes; a.H = horizon; a.K = K; a.cap = (int)cap; a.done_on_next = model->done_on_next;
+    a.uniform = continuation; a.n_env = n_actions_env; a.max_plan_len = max_plan_len; a.gamma = gamma; a.accuracy = accuracy;
+    a.grid = form.grid; a.term = model->term; a.avail = model->masked ? model->avail : nullptr;
+    a.bthr = d_tab; a.tthr = d_tab + M2; a.vinit = d_tab + 2 * M2; a.col = a.vinit + horizon + 1;
+    MP_TRY(wave_tree(ctx, kGapeStochTreeKind, n_roots, A, (long)cap, 2, kGapeStochKeepBytes, a.grid + 1, a.grid, &a.nodes, &a.val,
+                     &a.n_nodes_out, &a.keep));
+    WaveIo io(mem, rmem, n_roots, root_state, &a.root_state, rng_state, &a.rng);
+    io.add(WS_IO3, plans, &a.plans, (size_t)max_plan_len);
+    io.add(WS_IO4, plan_len, &a.plan_len);
+    io.add(WS_IO5, episodes_run, &a.episodes_run);
+    io.add(WS_IO8, env_steps, &a.env_steps);
+    io.add(WS_IO7, status, &a.status);
+    io.add(WS_IO6, child_lower, &a.child_lower, (size_t)A);
+    io.add(WS_IO9, child_upper, &a.child_upper, (size_t)A);
+    io.add(WS_IO1, child_count, &a.child_count, (size_t)A);
+    io.add(WS_IO10, best_challenger, &a.arms, (size_t)2);
+    MP_TRY(wave_stage(ctx, io));
+    MP_TRY(wave_launch(ctx, gape_stoch_kernel, a.grid, form.lds_bytes(), gape_stoch_form_name(model->mode, a.keep), a));
+    return wave_unstage(ctx, io);
+}
+
+const char *mp_gape_stoch_form_names(void)
+{
+    static const std::string names = [] {
+        std::string out;
+        for (int mode : {MP_MODE_DETERMINISTIC, MP_MODE_STOCHASTIC, MP_MODE_SPARSE})
+            for (int keep = 1; keep >= 0; --keep) { out += gape_stoch_form_name(mode, keep != 0).s; out += '\n'; }
+        out.pop_back();
+        return out;
+    }();
+    return names.c_str();
+}
+
+int mp_gape_stoch_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, uint8_t *kind, int32_t *parent,
+                              int32_t *action, int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb,
+                              double *mu_lcb, double *value_upper, double *value_lower, uint8_t *done, int32_t *state)
+{
+    const char *const who = "mp_gape_stoch_tree_export";
+    int32_t slot, n;
+    MP_TRY(wave_export_begin(ctx, kGapeStochTreeKind, who, "mp_gape_plan_stochastic", root, &slot, &n));
+    if (n_nodes) *n_nodes = n;
+    if (n > cap) return fail(MP_ERR_ARG, "%s: capacity %d < %d nodes", who, cap, n);
+    std::vector<GsNode> na((size_t)n);
+    std::vector<double> val((size_t)n * 2);
+    MP_TRY(wave_pull(ctx, WS_TREE0, slot, n, sizeof(GsNode), na.data()));
+    MP_TRY(wave_pull(ctx, WS_TREE1, slot, n, 2 * sizeof(double), val.data()));
+    // breadth first, a chance node's children in the reference's dict order: the placeholders left, then the observed states
+    std::vector<int32_t> order(1, 0), par(1, -1);
+    order.reserve((size_t)n); par.reserve((size_t)n);
+    for (size_t q = 0; q < order.size(); ++q) {
+        const GsNode &r = na[order[q]];
+        if (r.n_children <= 0) continue;
+        if (r.first_child < 1 || (long long)r.first_child + r.n_children > n || r.n_assigned < 0 || r.n_assigned > r.n_children ||
+            order.size() + (size_t)r.n_children > (size_t)n)
+            return fail(MP_ERR_ARG, "%s: bad record %d", who, order[q]);
+        const int rot = r.kind ? r.n_assigned : 0;
+        for (int i = 0; i < r.n_children; ++i) {
+            order.push_back(r.first_child + (i + rot) % r.n_children);
+            par.push_back((int32_t)q);
+        }
+    }
+    if ((int)order.size() != n) return fail(MP_ERR_ARG, "%s: %d of %d records are reachable", who, (int)order.size(), n);
+    for (int q = 0; q < n; ++q) {
+        const int i = order[q];
+        const GsNode &r = na[i];
+        const bool chance = r.kind != 0;
+        if (kind) kind[q] = chance ? 1 : 0;
+        if (parent) parent[q] = par[q];
+        if (action) action[q] = i == 0 ? -1 : r.key;
+        if (depth) depth[q] = r.depth;
+        if (count) count[q] = r.count;
+        if (cumulative_reward) cumulative_reward[q] = chance ? 0.0 : r.cum;
+        if (mu_ucb) mu_ucb[q] = chance ? 0.0 : r.mu_ucb;
+        if (mu_lcb) mu_lcb[q] = chance ? 0.0 : r.mu_lcb;
+        if (value_upper) value_upper[q] = val[2 * (size_t)i];
+        if (value_lower) value_lower[q] = val[2 * (size_t)i + 1];
+        if (done) done[q] = chance ? 0 : (uint8_t)r.done;
+        if (state) state[q] = chance ? na[r.parent].key : (r.key >= 0 ? r.key : -1);
+    }
+    return MP_OK;
+}
+
+int mp_selftest_gape_transition(mp_ctx *ctx, int32_t n, int32_t K, const double *f, const double *q, const double *c,
+                                double *p_star, int32_t *iterations, int32_t *decisions)
+{
+    const char *const who = "mp_selftest_gape_transition";
+    if (!ctx || !f || !q || !c || !p_star || !iterations || !decisions) return fail(MP_ERR_ARG, "%s: NULL argument", who);
+    if (n < 1 || K < 1 || K > 32) return fail(MP_ERR_ARG, "%s: n >= 1 problems of width 1..32 expected", who);
+    MP_HIP(hipSetDevice(ctx->device));
+    const size_t nk = (size_t)n * K, N = (size_t)n;
+    double *d = nullptr; // f, q, p_star [n][K] doubles, c [n], then iterations, decisions [n] int32
+    MP_HIP(hipMalloc(&d, (3 * nk + N) * sizeof(double) + 2 * N * sizeof(int32_t)));
+    int32_t *di = reinterpret_cast<int32_t *>(d + 3 * nk + N);
+    hipStream_t st = ctx->stream;
+    hipError_t e = hipMemcpyAsync(d, f, nk * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + nk, q, nk * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + 3 * nk, c, N * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(gape_transition_selftest_kernel, dim3((unsigned)((N + 1) / 2)), dim3(64), 0, st, n, K, d, d + nk,
+                           d + 3 * nk, d + 2 * nk, di, di + N);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(p_star, d + 2 * nk, nk * sizeof(double), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(iterations, di, N * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(decisions, di + N, N * sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(d);
+    MP_HIP(e);
+    MP_HIP(e2);
+    return MP_OK;
+}
+
+} // extern "C"

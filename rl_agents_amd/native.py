@@ -18,6 +18,7 @@ MODE_DETERMINISTIC, MODE_STOCHASTIC, MODE_SPARSE, MODE_CARTPOLE = 0, 1, 2, 3
 ERR_REWARD_RANGE, ERR_ARG, ERR_MODE = -2, -4, -5
 MP_ERR_GBOPD_DIVERGED, MP_ERR_GBOPD_NO_ACTION = -7, -8
 ERR_GAPE_NO_CHALLENGER = -9  # mp_gape_plan status: the root lists one action (mdp_gape.py:247 ValueError)
+ERR_GAPE_PLACEHOLDERS = -10  # mp_gape_plan_stochastic status: no placeholder left for a new next state (mdp_gape.py:284 ValueError)
 ERR_OLOP_KEY = -6          # mp_olop_plan status: the "zeros" continuation's action is not a child (olop.py:89 KeyError)
 
 _LIB = None
@@ -131,6 +132,11 @@ SIGNATURES = {
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_gape_form_names": (C.c_char_p, []),
     "mp_gape_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_gape_plan_stochastic": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp,
+                                          _vp, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_gape_stoch_form_names": (C.c_char_p, []),
+    "mp_gape_stoch_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_selftest_gape_transition": (C.c_int, [_vp, c_i32, c_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_brue_plan":(C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_brue_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_olop_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, c_i32, c_i32, _vp, _vp, _vp, c_i32, _vp, _vp,
@@ -481,6 +487,12 @@ def gape_form_names():
     """The names an MDP-GapE plan (``gape_plan``) records for Context.last_kernel_variant() (mp_gape_form_names; host only).
     They are part of no other list of names."""
     return load().mp_gape_form_names().decode().split()
+
+
+def gape_stoch_form_names():
+    """The names an MDP-GapE plan with transition bounds (``gape_plan_stochastic``) records for Context.last_kernel_variant()
+    (mp_gape_stoch_form_names; host only).  They are part of no other list of names."""
+    return load().mp_gape_stoch_form_names().decode().split()
 
 
 def olop_stoch_form_names():
@@ -1365,6 +1377,55 @@ class Context(object):
                 _check(rc)
             cap = n.value
         return _export_tree(self._lib.mp_gape_tree_export, (self._h, int(root)), cap, self.GAPE_TREE)
+
+    def gape_plan_stochastic(self, model, root_state, episodes, horizon, max_next_states, gamma, accuracy, uniform, n_actions_env,
+                             action_column, thr_by_count, transition_thr_by_count, value_init, rng_state):
+        """MDPGapE.plan with ``max_next_states_count`` = ``max_next_states`` in 1..32 on a deterministic table, a dense or a
+        sparse model, for a batch of roots (host arrays): mp_gape_plan_stochastic.  Arguments and results as :meth:`gape_plan`,
+        and ``transition_thr_by_count`` float64 [episodes + 2]: ``transition_threshold()`` by a chance node's count.
+        ``status`` ERR_GAPE_PLACEHOLDERS where more next states were observed than placeholders.  :meth:`gape_stoch_tree`
+        serves the trees afterwards."""
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        _check_rng(rng_state, rs.shape[0])
+        thr = np.ascontiguousarray(thr_by_count, dtype=np.float64).reshape(-1)
+        tthr = np.ascontiguousarray(transition_thr_by_count, dtype=np.float64).reshape(-1)
+        vin = np.ascontiguousarray(value_init, dtype=np.float64).reshape(-1)
+        if vin.size != int(horizon) + 1 or thr.size != int(episodes) + 2 or tthr.size != int(episodes) + 2:
+            raise ValueError("gape_plan_stochastic: thr_by_count and transition_thr_by_count [episodes + 2] and value_init "
+                             "[horizon + 1] expected")
+        col = None if action_column is None else np.ascontiguousarray(action_column, dtype=np.int32).reshape(-1)
+        if col is not None and col.size != int(n_actions_env):
+            raise ValueError("gape_plan_stochastic: action_column [n_actions_env] expected")
+        run = (int(episodes), int(horizon), int(max_next_states), float(gamma), float(accuracy), 1 if uniform else 0,
+               int(n_actions_env), _ptr(col), _ptr(thr), _ptr(tthr), _ptr(vin))
+        return self._each_plan(self._lib.mp_gape_plan_stochastic, None, "gape", model, rs, None, run, rng_state, 1, A=model.A, P=2)
+
+    def gape_stoch_tree(self, root, cap=None):
+        """BREADTH-FIRST arrays of root ``root``'s tree after the last gape_plan_stochastic, children in the reference's dict
+        order, with the fields of :meth:`gape_tree` (mp_gape_stoch_tree_export): the ``action`` of a decision node is its
+        observed state, or ``-1 - i`` for ``placeholder_i``.  ``cap`` None: the tree's own node count is asked first."""
+        if cap is None:
+            n = c_i32()
+            rc = self._lib.mp_gape_stoch_tree_export(self._h, int(root), 0, C.byref(n), *([None] * len(self.GAPE_TREE)))
+            if n.value < 1:                                     # (no tree to size: the refusal itself)
+                _check(rc)
+            cap = n.value
+        return _export_tree(self._lib.mp_gape_stoch_tree_export, (self._h, int(root)), cap, self.GAPE_TREE)
+
+    def selftest_gape_transition(self, f, q, c):
+        """What the DEVICE computes for ``max_expectation_under_constraint`` (mp_selftest_gape_transition): ``f``, ``q`` float64
+        [n, K], ``c`` float64 [n] -> (p_star [n, K], Newton iterations int32 [n], decisions int32 [n]: the KT_* bits of
+        csrc/kl_transition.hpp)."""
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        c = np.ascontiguousarray(c, dtype=np.float64).reshape(-1)
+        if f.ndim != 2 or q.shape != f.shape or c.size != f.shape[0]:
+            raise ValueError("selftest_gape_transition: f, q [n, K] and c [n] expected")
+        p_star = np.zeros(f.shape, np.float64)
+        its, mask = np.zeros(c.size, np.int32), np.zeros(c.size, np.int32)
+        _check(self._lib.mp_selftest_gape_transition(self._h, f.shape[0], f.shape[1], _ptr(f), _ptr(q), _ptr(c), _ptr(p_star),
+                                                     _ptr(its), _ptr(mask)))
+        return p_star, its, mask
 
     def brue_plan(self, model, root_state, budget, horizon, gamma, gpow, rng_state, model_index=None):
         """BRUE.plan for a batch of roots (host arrays): mp_brue_plan.  ``gpow`` float64 [horizon + 1]: gamma ** d from the
