@@ -660,6 +660,33 @@ int mp_gape_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes
                         int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *mu_lcb,
                         double *value_upper, double *value_lower, uint8_t *done, int32_t *state);
 
+/* mp_gape_plan on a batch model of deterministic tables (mp_model_load_table_batch) with one MDP per root (see
+ * mp_olop_plan_models / mp_ss_plan_models): model_index int32 [n_roots], root_state LOCAL; several roots may share an MDP.
+ * Equal to MDPGapE.plan (tree_search/mdp_gape.py:94-110; the episodes of :60-92, the sampling rule of :185-196, the expansion
+ * of :155-170, the bounds of :200-210, the backup of :214-226 and :288-305, best-arm identification of :228-249) of one agent
+ * per MDP, and to mp_gape_plan on that table alone, bit for bit: every result, the generator records and every tree array.
+ * The availability table is read as mp_gape_plan reads it: mp_model_set_available, one row per GLOBAL state, so every MDP
+ * may list other actions; the done rule is the model's.  The remaining arguments and the results are mp_gape_plan's.
+ * MP_ERR_MODE for a single table, a joint batch, a dense, a sparse or a row-block model; MP_ERR_ARG for a model_index outside
+ * [0, N) or a local state outside [0, S_each) in host arrays (device arrays: the clamp-and-count of mp_opd_plan_models), and
+ * under the conditions of mp_gape_plan.  This entry accepts batch models (mp_gape_plan itself refuses them).  Nodes hold
+ * GLOBAL states: mp_gape_tree_export serves the trees afterwards, its `state` column (and a decision node's `action`) global.
+ * mp_last_kernel_variant records one of mp_gape_each_form_names: "gape_each_lds" (the root's S_each * |A| records in LDS behind
+ * path[horizon + 1]) / "gape_each_global", each also with "_slots" (part of no other list). */
+int mp_gape_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                        int32_t episodes, int32_t horizon, double gamma, double accuracy, int32_t continuation,
+                        int32_t n_actions_env, const int32_t *action_column, const double *thr_by_count, const double *value_init,
+                        uint64_t *rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len, int32_t *episodes_run,
+                        int64_t *env_steps, int32_t *status, double *child_lower, double *child_upper, int64_t *child_count,
+                        int32_t *best_challenger, int32_t mem);
+const char *mp_gape_each_form_names(void);
+/* The form mp_gape_plan_models chooses for a call of this description, on the host alone (no device, no ctx; the function the
+ * launch code calls), with the six outputs of mp_each_form_info: the kernel's own LDS array is path[horizon + 1] int32, as
+ * OLOP's.  The LDS form is the default where it was measured faster beyond the spread of repeated medians (each_host.hpp): a
+ * workgroup of at most 160 KiB / 16 bytes, from 256 roots on, while all the roots' workgroups are resident at once; else the global
+ * form.  MP_EACH_MODEL=lds takes the LDS form for any table that fits the 160 KiB of a CU, MP_EACH_MODEL=global the global one. */
+int mp_gape_each_form_info(int32_t S_each, int32_t A, int32_t horizon, int32_t n_roots, int32_t cus, int64_t *out);
+
 /*
  * MDPGapE.plan with a KL confidence region over every chance node's next-state distribution: max_next_states_count =
  * max_next_states in 1..32, on a deterministic table, a dense or a sparse model.  Everything mp_gape_plan does, and:
@@ -1096,6 +1123,8 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
  *   GBOP-D        "gbopd_wave_lds", "gbopd_wave_global"
  *   Sparse        "ss_wave_lds", "ss_wave_global" (the frames of the recursion in LDS / in a global workspace); one MDP per root
  *   Sampling      (mp_ss_plan_models): "ss_each_lds" / "ss_each_global"
+ *   MDP-GapE      "gape_global", then "_slots"; one MDP per root (mp_gape_plan_models): "gape_each_lds" / "gape_each_global", then
+ *                 "_slots" (listed by mp_gape_form_names / mp_gape_each_form_names, not by mp_kernel_form_names)
  *   OPD           "opd_any" (more than 64 actions); "opd_lds" / "opd_ldsx" (bounds in LDS / the parent map in HBM), then "_gen"
  *                 (the main loop for arbitrary bounds), then "_chain" (the closing pass on the node array);
  *                 "opd_wide_sib" / "opd_wide_cls" (bounds in HBM, sibling / residue-class layout), then "_small" (at most two

@@ -318,6 +318,9 @@ class AbstractPlanner(Configurable):
     # what PerEpisodeEvaluation does with this planner: "opd", "ropd", "olop", "brue" (one plan_on per lock-step), "uct" (the
     # loop's own policy handling); None: the loop refuses the planner
     per_episode_kind = None
+    # a kind the loop runs only when asked for by name, PerEpisodeEvaluation(..., kind=...): "gape", "ss" (planners whose
+    # refusal by default earlier code relies on)
+    per_episode_kind_on_request = None
     # the reference's generator has made the draws of the episodes run before a failing step: planners whose records stay
     # advanced when a plan raises (OLOP, BRUE)
     draws_survive_errors = False

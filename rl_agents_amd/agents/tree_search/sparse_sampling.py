@@ -8,6 +8,10 @@ part.  The samples step a clone directly (sparse_sampling.py:81), not through ``
 count stays 0 and so does ``env_steps`` here; the model steps taken are counted in ``samples``.  Everything a plan computes
 -- the draws, the clones' seeding, the outcome lists, the backups, the root's tie-break -- is the device's, bit for bit
 (DESIGN.md).
+
+One model per episode: ``SparseSampling.plan_on(..., model_index=...)`` plans every root on its own deterministic table of a batch
+model (``mp_ss_plan_models``).  ``PerEpisodeEvaluation`` refuses the agent unasked, as it always has (``per_episode_kind = None``),
+and runs it on request: ``PerEpisodeEvaluation(envs, agent, kind="ss")`` (``per_episode_kind_on_request``).
 """
 import logging
 from collections import defaultdict
@@ -22,9 +26,10 @@ logger = logging.getLogger(__name__)
 
 class SparseSampling(AbstractPlanner):
     """Sparse Sampling planner (sparse_sampling.py:11-28) for one or many roots of one finite MDP."""
-    # PerEpisodeEvaluation refuses this planner: the device plans on one MDP per root (Context.ss_plan with model_index,
-    # mp_ss_plan_models), but that loop has no kind that calls it yet
+    # PerEpisodeEvaluation refuses this planner by default (earlier code relies on the refusal); asked for by name,
+    # PerEpisodeEvaluation(..., kind="ss"), it plans on one MDP per root (Context.ss_plan with model_index, mp_ss_plan_models)
     per_episode_kind = None
+    per_episode_kind_on_request = "ss"
 
     def __init__(self, env, config=None):
         self.env = env
@@ -53,12 +58,10 @@ class SparseSampling(AbstractPlanner):
             model.set_available(spec.available)          # (columns = listing order)
         return model
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, env_rng_states=None):
-        """``root_steps`` and ``env_rng_states`` are accepted for the common interface: ``done`` is never read
-        (sparse_sampling.py:81), and a clone is seeded anew before its one step (:79), whatever generator it copied."""
+    def plan_sizes(self):
+        """(horizon, C) of the config, with what the reference raises for them at plan time."""
         cfg = self.config
         horizon = cfg["horizon"]                                     # KeyError: neither has a default
-        n = len(root_states)
         if horizon == 0:
             # the root gets no child (:45-46): np.amax([]) of the root's selection raises (:55, abstract.py:301)
             raise ValueError("zero-size array to reduction operation maximum which has no identity")
@@ -66,22 +69,42 @@ class SparseSampling(AbstractPlanner):
         if n_samples < 1:
             # (the reference's UnboundLocalError: its backup reads the reward of a sample that was never taken, :87)
             raise ValueError("Sparse Sampling needs C >= 1 samples per chance node, got {}".format(n_samples))
+        return int(horizon), int(n_samples)
+
+    def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None):
+        """The one ``ctx.ss_plan`` call -> the binding's dict with ``plans`` [n, 1], ``plan_len`` and ``env_steps`` added.
+        ``root_steps`` is accepted for the common interface: ``done`` is never read (sparse_sampling.py:81).  ``model_index``:
+        a batch model, one MDP per root (mp_ss_plan_models).  ``max_plan_len``: a plan is one action whatever is asked for."""
+        horizon, n_samples = self.plan_sizes()
+        n = len(root_states)
+        out = self.models.ctx.ss_plan(model, root_states, horizon, n_samples, self.config["gamma"], rng_states,
+                                      model_index=model_index)
+        self.samples += int(out["samples"].sum())
+        out["env_steps"] = np.zeros(n, np.int64)                     # len(planner.observations): planner.step is not used
+        out["plans"] = out["plans"].reshape(n, 1)
+        out["plan_len"] = np.ones(n, np.int32)
+        return out
+
+    def raise_for_result(self, out):
+        if (out["status"] != 0).any():
+            raise RuntimeError("Sparse Sampling: the device refused a root (status {})".format(
+                int(out["status"][out["status"] != 0][0])))
+
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, env_rng_states=None):
+        """``root_steps`` and ``env_rng_states`` are accepted for the common interface: ``done`` is never read
+        (sparse_sampling.py:81), and a clone is seeded anew before its one step (:79), whatever generator it copied."""
+        self.plan_sizes()
+        n = len(root_states)
         model = self.model_for(state)
         self.about_to_plan()
         if rng_states is None:
             rng_states = self.batch_rng_states(n)
-        out = self.models.ctx.ss_plan(model, root_states, int(horizon), int(n_samples), cfg["gamma"], rng_states)
-        self.samples += int(out["samples"].sum())
-        out["env_steps"] = np.zeros(n, np.int64)                     # len(planner.observations): planner.step is not used
+        out = self.plan_on(model, root_states, root_steps, rng_states)
         out["rng_states"] = rng_states
         self.relabel(out, model)
         self.last, self._root, self._last_model = out, None, model
         self.claim_device_tree()
-        if (out["status"] != 0).any():
-            raise RuntimeError("Sparse Sampling: the device refused a root (status {})".format(
-                int(out["status"][out["status"] != 0][0])))
-        out["plans"] = out["plans"].reshape(n, 1)
-        out["plan_len"] = np.ones(n, np.int32)
+        self.raise_for_result(out)
         return out
 
     def plan(self, state, observation):

@@ -1102,6 +1102,7 @@ int mp_model_load_table_batch(mp_ctx *ctx, int32_t N, int32_t S, int32_t A, cons
     MP_TRY(load_table_common(ctx, 1, N * S, A, t32, reward, terminal, done_on_next, max_steps, out));
     (*out)->NB = N;
     (*out)->Sb = S;
+    (*out)->table_batch = true;
     return MP_OK;
 }
 

@@ -210,6 +210,7 @@ struct mp_model {
     // batch models (mp_model_load_table_batch): NB independent MDPs of Sb states each, S = NB * Sb GLOBAL states
     // (b * Sb + s); every table below is the disjoint union.  NB = 1, Sb = S for any other model.
     int NB = 1, Sb = 0;
+    bool table_batch = false; // loaded by mp_model_load_table_batch (a batch of one MDP is otherwise a single table)
     // table updates (mp_model_update_tables / _rows): a pinned staging block + a device scratch block owned by the model,
     // and the event that says the last update's copies out of the staging block are done
     void *upd_stage = nullptr;

@@ -49,6 +49,7 @@ static_assert(sizeof(GapeNode) == 88, "GapeNode layout");
 
 struct GapeArgs {
     int n_roots, A, M, H, cap, done_on_next, uniform, n_env, keep, grid, max_plan_len;
+    int Sb;              // states of one MDP of a batch model (mp_gape_plan_models), else |S|
     double gamma, accuracy;
     const Rec *rec;
     const int32_t *root_state;
@@ -64,15 +65,41 @@ struct GapeArgs {
     double *child_lower, *child_upper; // [n_roots][A]
 };
 
+// EACH (mp_gape_plan_models: a batch model of deterministic tables, one MDP per root, the roots' states GLOBAL -- nodes keep
+// global states, and the availability flag and the done bits are those of the global state's records).  GAPE_WHOLE is the kernel
+// of mp_gape_plan; GAPE_EACH_GLOBAL is the same code on the batch model's records; GAPE_EACH_LDS copies the root's own Sb * |A|
+// records into LDS behind path[] -- before its first episode, and again only when a workgroup's next root sits on another MDP --
+// and serves both kinds of model read, the expansion's row and the step's record, from there: a record's `next` lies inside
+// the root's MDP (mp_model_load_table_batch checks it), so its index is (state - base) * |A| + a.  Everything the LDS form adds
+// sits under `if constexpr` (profiles/gape_each_kernel_resources.txt).
+enum { GAPE_WHOLE = 0, GAPE_EACH_GLOBAL = 1, GAPE_EACH_LDS = 2 };
+
+template <int EACH>
 __global__ __launch_bounds__(64) void gape_kernel(GapeArgs p)
 {
     extern __shared__ int32_t path[]; // [H + 1] records of the episode's walk
     const int lane = threadIdx.x, A = p.A, H = p.H;
+    constexpr bool lds_model = EACH == GAPE_EACH_LDS;
+    Rec *lrec = nullptr;              // [Sb * A] GAPE_EACH_LDS: the root's table, 16-byte aligned behind path[]
+    if constexpr (lds_model) lrec = static_cast<Rec *>(__builtin_assume_aligned(path + ((H + 1 + 3) & ~3), 16));
+    int base = 0, loaded = -1;        // GAPE_EACH_LDS: first global state of the root's MDP / index of the MDP in LDS
+    // the records of state `s` (GLOBAL), one per action
+    auto row_of = [&](int s) -> const Rec * { return lds_model ? lrec + (long)(s - base) * A : p.rec + (long)s * A; };
     const uint32_t done_bit = p.done_on_next ? 2u : 1u;
     for (int root = blockIdx.x; root < p.n_roots; root += p.grid) {
         const long slot = p.keep ? root : (root == 0 ? p.grid : blockIdx.x);
         GapeNode *N = p.nodes + slot * p.cap;
         double *V = p.val + slot * p.cap * 2;
+        // GAPE_EACH_LDS: the root's table into LDS (the previous root's reads ended at the barrier that closes its iteration; this
+        // root's begin after the one below)
+        if constexpr (lds_model) {
+            const int mi = p.root_state[root] / p.Sb;
+            if (mi != loaded) {
+                base = mi * p.Sb;
+                wave_lds_records(lrec, p.rec, base, A, p.Sb, lane);
+                loaded = mi;
+            }
+        }
         if (lane == 0) {
             GapeNode r;
             r.cum = 0.0; r.mu_ucb = 1.0; r.mu_lcb = 0.0; r.vu = p.vinit[0]; r.vl = 0.0; r.count_c = 0; r.count_d = 0;
@@ -90,7 +117,7 @@ __global__ __launch_bounds__(64) void gape_kernel(GapeArgs p)
         // DecisionNode.expand (mdp_gape.py:162-170): a chance child per listed action, in listing order; *rank = the position
         // of column `col` among them, -1 when it is not listed
         auto expand = [&](int node, int state, int depth, int col, int *rank) {
-            const Rec *row = p.rec + (long)state * A;
+            const Rec *row = row_of(state);
             const int fc = n_nodes;
             int pos0 = 0;
             *rank = -1;
@@ -152,7 +179,7 @@ __global__ __launch_bounds__(64) void gape_kernel(GapeArgs p)
                 }
                 const int child = fc + j;
                 const GapeNode c0 = N[child];
-                const Rec rc = p.rec[(long)nd.state * A + c0.action];
+                const Rec rc = row_of(nd.state)[c0.action];
                 ++steps;
                 const double r = rc.reward;
                 // olop.py:133-134, after the step was counted.  (The reference has also counted the chance node and made its
@@ -244,6 +271,15 @@ __global__ __launch_bounds__(64) void gape_kernel(GapeArgs p)
 }
 
 inline FormName gape_form_name(bool keep) { return slots_form_name("gape", keep); }
+// mp_gape_plan_models: the root's table in LDS or read from global memory, with the `_slots` suffix of slots_form_name.  Listed by
+// mp_gape_each_form_names, part of no other list of names.
+inline FormName gape_each_form_name(bool lds, bool keep)
+{
+    if (!lds) return slots_form_name("gape_each", keep);
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "gape_each_lds%s", keep ? "" : "_slots");
+    return n;
+}
 
 } // namespace mp
 
@@ -251,20 +287,30 @@ using namespace mp;
 
 extern "C" {
 
-int mp_gape_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
-                 double gamma, double accuracy, int32_t continuation, int32_t n_actions_env, const int32_t *action_column,
-                 const double *thr_by_count, const double *value_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans,
-                 int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps, int32_t *status, double *child_lower,
-                 double *child_upper, int64_t *child_count, int32_t *best_challenger, int32_t mem)
+extern "C++" {
+namespace {
+// mp_gape_plan (model_index NULL: `root_state` holds states of the one table) and mp_gape_plan_models (a batch model of
+// deterministic tables, `root_state` LOCAL to the MDP model_index names: globalize_roots_arg makes the GLOBAL states the kernel
+// plans from, and the form is each_form's)
+int gape_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                   int32_t episodes, int32_t horizon, double gamma, double accuracy, int32_t continuation, int32_t n_actions_env,
+                   const int32_t *action_column, const double *thr_by_count, const double *value_init, uint64_t *rng_state,
+                   int32_t max_plan_len, int32_t *plans, int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps,
+                   int32_t *status, double *child_lower, double *child_upper, int64_t *child_count, int32_t *best_challenger,
+                   int32_t mem, bool each)
 {
-    const char *const who = "mp_gape_plan";
-    if (!ctx || !model || !root_state || !rng_state || !thr_by_count || !value_init) return fail(MP_ERR_ARG, "%s: NULL argument", who);
+    const char *const who = each ? "mp_gape_plan_models" : "mp_gape_plan";
+    if (!ctx || !model || !root_state || !rng_state || !thr_by_count || !value_init || (each && !model_index))
+        return fail(MP_ERR_ARG, "%s: NULL argument", who);
+    const int32_t mem_flags = mem;
     int rmem;
     MP_TRY(wave_mem(who, &mem, &rmem));
     if (model->mode != MP_MODE_DETERMINISTIC)
         return fail(MP_ERR_MODE, "%s: model mode %d is not a deterministic table (a dense or sparse model needs the reference's "
                                  "transition bounds, which are not built)", who, model->mode);
-    MP_TRY(wave_mdp_check(who, model, false));
+    MP_TRY(wave_mdp_check(who, model, each));
+    if (each && !model->table_batch)
+        return fail(MP_ERR_MODE, "%s: a batch model of deterministic tables (mp_model_load_table_batch) expected", who);
     const int A = model->A;
     if (n_roots < 1 || episodes < 0 || horizon < 1 || horizon > 16384 || max_plan_len < 0 || A < 1 || n_actions_env < 1)
         return fail(MP_ERR_ARG, "%s: bad sizes", who);
@@ -279,6 +325,8 @@ int mp_gape_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
         return fail(MP_ERR_ARG, "%s: %d environment actions need their columns among the model's %d", who, n_actions_env, A);
     for (int a = 0; action_column && a < n_actions_env; ++a)
         if (action_column[a] < -1 || action_column[a] >= A) return fail(MP_ERR_ARG, "%s: column %d out of range", who, action_column[a]);
+    std::vector<int32_t> global_tmp;
+    if (each) MP_TRY(globalize_roots_arg(ctx, model, n_roots, model_index, root_state, mem_flags, global_tmp, &root_state));
     MP_TRY(wave_roots(ctx, who, root_state, n_roots, model->S, mem));
     // a record per chance node: every step of every episode may expand one decision node
     const long long cap = 1 + ((long long)episodes + 2) * horizon * A;
@@ -295,7 +343,10 @@ int mp_gape_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     MP_TRY(upload_tables(ctx, 42, tab, &d_tab));
 
     GapeArgs a;
-    const EachForm form = each_form_global(EACH_OLOP, horizon, n_roots, ctx->prop.multiProcessorCount); // path[H + 1] in LDS
+    a.Sb = model->Sb > 0 ? model->Sb : model->S;
+    // (the global form is the launch mp_gape_plan always made: CUs * 32 wavefronts at most, path[H + 1] in LDS)
+    const int cus = ctx->prop.multiProcessorCount;
+    const EachForm form = each ? each_form(EACH_GAPE, a.Sb, A, horizon, n_roots, cus) : each_form_global(EACH_GAPE, horizon, n_roots, cus);
     a.n_roots = n_roots; a.A = A; a.M = episodes; a.H = horizon; a.cap = (int)cap; a.done_on_next = model->done_on_next;
     a.uniform = continuation; a.n_env = n_actions_env; a.max_plan_len = max_plan_len; a.gamma = gamma; a.accuracy = accuracy;
     a.grid = form.grid; a.rec = model->rec; a.thr = d_tab; a.vinit = d_tab + episodes + 2; a.col = a.vinit + horizon + 1;
@@ -311,8 +362,37 @@ int mp_gape_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *r
     io.add(WS_IO1, child_count, &a.child_count, (size_t)A);
     io.add(WS_IO10, best_challenger, &a.arms, (size_t)2);
     MP_TRY(wave_stage(ctx, io));
-    MP_TRY(wave_launch(ctx, gape_kernel, a.grid, form.lds_bytes(), gape_form_name(a.keep), a));
+    if (each)
+        MP_TRY(wave_launch(ctx, form.lds ? gape_kernel<GAPE_EACH_LDS> : gape_kernel<GAPE_EACH_GLOBAL>, a.grid, form.lds_bytes(),
+                           gape_each_form_name(form.lds, a.keep), a));
+    else
+        MP_TRY(wave_launch(ctx, gape_kernel<GAPE_WHOLE>, a.grid, form.lds_bytes(), gape_form_name(a.keep), a));
     return wave_unstage(ctx, io);
+}
+} // namespace
+} // extern "C++"
+
+int mp_gape_plan(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes, int32_t horizon,
+                 double gamma, double accuracy, int32_t continuation, int32_t n_actions_env, const int32_t *action_column,
+                 const double *thr_by_count, const double *value_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans,
+                 int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps, int32_t *status, double *child_lower,
+                 double *child_upper, int64_t *child_count, int32_t *best_challenger, int32_t mem)
+{
+    return gape_plan_impl(ctx, model, n_roots, nullptr, root_state, episodes, horizon, gamma, accuracy, continuation, n_actions_env,
+                          action_column, thr_by_count, value_init, rng_state, max_plan_len, plans, plan_len, episodes_run, env_steps,
+                          status, child_lower, child_upper, child_count, best_challenger, mem, false);
+}
+
+int mp_gape_plan_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                        int32_t episodes, int32_t horizon, double gamma, double accuracy, int32_t continuation,
+                        int32_t n_actions_env, const int32_t *action_column, const double *thr_by_count, const double *value_init,
+                        uint64_t *rng_state, int32_t max_plan_len, int32_t *plans, int32_t *plan_len, int32_t *episodes_run,
+                        int64_t *env_steps, int32_t *status, double *child_lower, double *child_upper, int64_t *child_count,
+                        int32_t *best_challenger, int32_t mem)
+{
+    return gape_plan_impl(ctx, model, n_roots, model_index, root_state, episodes, horizon, gamma, accuracy, continuation,
+                          n_actions_env, action_column, thr_by_count, value_init, rng_state, max_plan_len, plans, plan_len,
+                          episodes_run, env_steps, status, child_lower, child_upper, child_count, best_challenger, mem, true);
 }
 
 const char *mp_gape_form_names(void)
@@ -321,11 +401,33 @@ const char *mp_gape_form_names(void)
     return names.c_str();
 }
 
+const char *mp_gape_each_form_names(void)
+{
+    static const std::string names = [] {
+        std::string out;
+        for (int lds = 1; lds >= 0; --lds)
+            for (int keep = 1; keep >= 0; --keep) { out += gape_each_form_name(lds != 0, keep != 0).s; out += '\n'; }
+        return out;
+    }();
+    return names.c_str();
+}
+
+int mp_gape_each_form_info(int32_t S_each, int32_t A, int32_t horizon, int32_t n_roots, int32_t cus, int64_t *out)
+{
+    if (!out) return fail(MP_ERR_ARG, "mp_gape_each_form_info: NULL output");
+    if (S_each < 1 || A < 1 || horizon < 1 || n_roots < 1 || cus < 1) return fail(MP_ERR_ARG, "mp_gape_each_form_info: bad arguments");
+    const EachForm f = each_form(EACH_GAPE, S_each, A, horizon, n_roots, cus);
+    out[0] = (int64_t)f.lds_need; out[1] = f.lds ? 1 : 0; out[2] = f.grid; out[3] = (int64_t)f.lds_bytes();
+    out[4] = (int64_t)kEachLdsDefaultBytes; out[5] = (int64_t)kLdsBytes;
+    return MP_OK;
+}
+
 int mp_gape_tree_export(mp_ctx *ctx, int32_t root, int32_t cap, int32_t *n_nodes, uint8_t *kind, int32_t *parent, int32_t *action,
                         int32_t *depth, int64_t *count, double *cumulative_reward, double *mu_ucb, double *mu_lcb,
                         double *value_upper, double *value_lower, uint8_t *done, int32_t *state)
 {
     int32_t slot, n;
+    // (tree kind 8 is what mp_gape_plan and mp_gape_plan_models both leave; after the latter `state` holds GLOBAL states)
     MP_TRY(wave_export_begin(ctx, 8, "mp_gape_tree_export", "mp_gape_plan", root, &slot, &n));
     std::vector<GapeNode> na((size_t)n);
     std::vector<double> val((size_t)n * 2);

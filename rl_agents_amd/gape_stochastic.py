@@ -29,6 +29,7 @@ class StochasticMDPGapE(MDPGapE):
     Refused: ``max_next_states_count`` above 32 (NotImplementedError) or below 1 (ValueError), ``step_strategy: "subtree"``,
     a bound type other than ``"kullback-leibler"``, one model per episode (``per_episode_kind`` None), CartPole models."""
 
+    per_episode_kind_on_request = None        # mp_gape_plan_stochastic takes no batch model: refused also when asked for
     accepts_stochastic_models = True          # OLOP.model_for: availability in listing order, the env's done rule
     MAX_NEXT_STATES = 32                      # a chance node's children fill half a wavefront
 

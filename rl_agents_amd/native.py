@@ -131,6 +131,10 @@ SIGNATURES = {
     "mp_gape_plan": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp, c_i32, _vp, _vp,
                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_gape_form_names": (C.c_char_p, []),
+    "mp_gape_plan_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp, c_i32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_gape_each_form_names": (C.c_char_p, []),
+    "mp_gape_each_form_info": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, _vp]),
     "mp_gape_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_gape_plan_stochastic": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp,
                                           _vp, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
@@ -487,6 +491,21 @@ def gape_form_names():
     """The names an MDP-GapE plan (``gape_plan``) records for Context.last_kernel_variant() (mp_gape_form_names; host only).
     They are part of no other list of names."""
     return load().mp_gape_form_names().decode().split()
+
+
+def gape_each_form_names():
+    """The names an MDP-GapE plan on one MDP per root (``gape_plan`` with ``model_index``) records for
+    Context.last_kernel_variant() (mp_gape_each_form_names; host only).  They are part of no other list of names."""
+    return load().mp_gape_each_form_names().decode().split()
+
+
+def gape_each_form_info(s_each, n_actions, horizon, n_roots, cus=256):
+    """The form ``gape_plan`` with ``model_index`` takes for a call of this description (mp_gape_each_form_info; host only,
+    MP_EACH_MODEL is read): the dict of :func:`each_form_info`."""
+    out = np.zeros(6, np.int64)
+    _check(load().mp_gape_each_form_info(int(s_each), int(n_actions), int(horizon), int(n_roots), int(cus), _ptr(out)))
+    return dict(lds_bytes=int(out[0]), lds=bool(out[1]), grid=int(out[2]), launch_lds_bytes=int(out[3]), default_limit=int(out[4]),
+                fit_limit=int(out[5]))
 
 
 def gape_stoch_form_names():
@@ -1345,11 +1364,12 @@ class Context(object):
         return _export_tree(self._lib.mp_olop_tree_export, (self._h, int(root)), cap, self.OLOP_TREE)
 
     def gape_plan(self, model, root_state, episodes, horizon, gamma, accuracy, uniform, n_actions_env, action_column, thr_by_count,
-                  value_init, rng_state):
+                  value_init, rng_state, model_index=None):
         """MDPGapE.plan for a batch of roots (host arrays): mp_gape_plan.  ``uniform``: the "uniform" continuation (else action
         0 of the environment); ``action_column`` int [n_actions_env] or None: the model column of each environment action;
         ``thr_by_count`` float64 [episodes + 2] and ``value_init`` float64 [horizon + 1] from the host.  ``plans`` [n, 1]: the
-        best arm's action (a column of the model), as ``best_challenger`` [n, 2]; ``child_*`` [n, A] by column."""
+        best arm's action (a column of the model), as ``best_challenger`` [n, 2]; ``child_*`` [n, A] by column.
+        ``model_index`` int [n]: a batch model with one MDP per root, ``root_state`` local (mp_gape_plan_models)."""
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
         _check_rng(rng_state, rs.shape[0])
         thr = np.ascontiguousarray(thr_by_count, dtype=np.float64).reshape(-1)
@@ -1361,7 +1381,8 @@ class Context(object):
             raise ValueError("gape_plan: action_column [n_actions_env] expected")
         run = (int(episodes), int(horizon), float(gamma), float(accuracy), 1 if uniform else 0, int(n_actions_env), _ptr(col),
                _ptr(thr), _ptr(vin))
-        return self._each_plan(self._lib.mp_gape_plan, None, "gape", model, rs, None, run, rng_state, 1, A=model.A, P=2)
+        return self._each_plan(self._lib.mp_gape_plan, self._lib.mp_gape_plan_models, "gape", model, rs, model_index, run, rng_state,
+                               1, A=model.A, P=2)
 
     GAPE_TREE = (("kind", np.uint8, ()), ("parent", np.int32, ()), ("action", np.int32, ()), ("depth", np.int32, ()),
                  ("count", np.int64, ()), ("cum", np.float64, ()), ("mu_ucb", np.float64, ()), ("mu_lcb", np.float64, ()),

@@ -14,7 +14,8 @@ Here N environments advance in lock-step and share ONE launch per step:
                                        ONE batched plan, one MDP per root            (mp_vi_solve_batch + argmax /
                                                                                       mp_uct_plan_models / mp_opd_plan_models /
                                                                                       mp_olop_plan_models / mp_brue_plan_models /
-                                                                                      mp_ropd_plan_models)
+                                                                                      mp_ropd_plan_models; on request
+                                                                                      mp_gape_plan_models / mp_ss_plan_models)
                                        env_i.step(action_i)                          (host: the environments are host objects)
 
 Episode i draws from the generator a sequential ``Evaluation`` would give agent i (``np_random(sim_seed + i)``,
@@ -34,7 +35,11 @@ continuation and its exceptions, as ``OLOP.plan_batch``) and ``BRUEAgent`` (whic
 batch model carries neither the availability table nor the listing order, as ``BRUE.model_for`` loads it) and
 ``DiscreteRobustPlannerAgent`` (which builds its M candidate models again before every plan, robust.py:68-71: every episode owns a
 SET of M tables per step, held as one joint batch model -- ``mp_model_load_joint_batch`` / ``mp_model_update_joint_tables`` --
-and planned on by ``mp_ropd_plan_models``; see :meth:`PerEpisodeEvaluation._sync_joint`); environments: deterministic finite MDPs of one (S, A) shape, with or without restricted /
+and planned on by ``mp_ropd_plan_models``; see :meth:`PerEpisodeEvaluation._sync_joint`); on request, by name --
+``PerEpisodeEvaluation(..., kind="gape")`` / ``kind="ss"`` -- ``MDPGapEAgent`` (``mp_gape_plan_models``) and ``SparseSamplingAgent``
+(``mp_ss_plan_models``): the loop has always refused the two and still does unasked, since earlier code may rely on the refusal;
+their batch model carries the availability table in listing order, as OLOP's, and the one call per lock-step is the planner's own
+``plan_on`` with its exceptions; environments: deterministic finite MDPs of one (S, A) shape, with or without restricted /
 re-ordered action sets (``get_available_actions``: the restriction must be the same table for every episode, as it is for
 grids of one shape -- device_model.availability_of).
 """
@@ -67,11 +72,14 @@ def restrict_and_renormalise(tables, available):
 
 
 class PerEpisodeEvaluation(object):
-    def __init__(self, envs, agent, sim_seed=0, max_steps=None):
+    def __init__(self, envs, agent, sim_seed=0, max_steps=None, kind=None):
         """``envs``: N environments exposing a deterministic finite MDP (``.mdp`` or ``to_finite_mdp()``) of one shape;
         ``agent``: an agent of this package built on ``envs[0]`` -- the template: its class and configuration are what every
         episode's agent would be.  ``sim_seed``: episode i's agent is seeded ``sim_seed + i`` -- or ``sim_seed[i]``, given one seed
-        per episode.  ``max_steps``: episode length cap (default: the env's ``max_steps``, else 100)."""
+        per episode.  ``max_steps``: episode length cap (default: the env's ``max_steps``, else 100).  ``kind``: what the loop does
+        with the planner, by name -- the planner class's ``per_episode_kind`` (the default, None: that kind, or the refusal of
+        a planner that declares none) or its ``per_episode_kind_on_request`` ("gape" for ``MDPGapEAgent``, "ss" for
+        ``SparseSamplingAgent``: planners this loop has always refused and still refuses unasked)."""
         self.envs, self.agent = list(envs), agent
         if not self.envs:
             raise ValueError("at least one environment")
@@ -88,6 +96,13 @@ class PerEpisodeEvaluation(object):
         # every planner class says what this loop does with it (AbstractPlanner.per_episode_kind)
         self.subtree = False
         self.kind = "vi" if self.vi else planner.per_episode_kind
+        if kind is not None:
+            offered = ["vi"] if self.vi else [k for k in (planner.per_episode_kind, getattr(planner, "per_episode_kind_on_request", None))
+                                              if k is not None]
+            if kind not in offered:
+                raise ValueError("per-episode tables: kind {!r} is not one {} offers ({})".format(
+                    kind, "value iteration" if self.vi else type(planner).__name__, ", ".join(repr(k) for k in offered) or "none"))
+            self.kind = kind
         if self.kind is None:
             raise NotImplementedError("per-episode tables: this loop has no kind that plans {} on one model per episode, "
                                       "and would run the optimistic planner in its place".format(type(planner).__name__))
@@ -280,7 +295,7 @@ class PerEpisodeEvaluation(object):
                                                    done_rule=first_spec.done_rule, max_steps=first_spec.max_steps)
             self.model.action_order = first_spec.action_order
             self._available = None if first_spec.available is None else first_spec.available.astype(bool)
-            if self._available is not None and self.kind in ("opd", "olop"):
+            if self._available is not None and self.kind in ("opd", "olop", "gape", "ss"):
                 # (MCTS reads availability through its policies, mcts.py:59-97: see _uct_policy)
                 self.model.set_available(np.tile(self._available, (n, 1)))
             self.uploads += len(live)

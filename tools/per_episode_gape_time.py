@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Plan time per lock-step of PerEpisodeEvaluation with MDPGapEAgent on request (kind="gape"), from ONE run on one machine.
+
+    python tools/per_episode_gape_time.py [--episodes 4096] [--steps 6] [--out profiles/per_episode_gape.json]
+
+ChangingHighwayEnv: a (3, 4, 10) grid re-drawn after every step, restricted action sets listed IDLE first; the reference's
+HighwayEnv/agents/MDPGapEAgent/baseline.json (budget 100 -> 14 episodes of horizon 6, gamma 0.8, accuracy 0.1,
+"1*np.log(time)").  `plan_ms` is the loop's own call per lock-step -- thresholds, the one mp_gape_plan_models launch, results and
+the synchronisation; the first lock-step (model built, workspaces allocated) is reported apart from the mean of the others.  The
+entry "device_lock_step" of the output file is replaced; its other entries (the reference's CPU time) are kept.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+CONFIG = dict(budget=100, gamma=0.8, accuracy=0.1, upper_bound={"type": "kullback-leibler", "threshold": "1*np.log(time)"})
+
+
+def timed_run(n, steps):
+    from rl_agents_amd.agents.tree_search.mdp_gape import MDPGapEAgent
+    from rl_agents_amd.envs import ChangingHighwayEnv
+    from rl_agents_amd.trainer.per_episode_evaluation import PerEpisodeEvaluation
+    envs = [ChangingHighwayEnv(3, 4, 10, table_seed=20 * i, state=((i % 3) * 4 + (i % 4)) * 10, collision_rate=0.03 + 0.02 * (i % 4))
+            for i in range(n)]
+    agent = MDPGapEAgent(envs[0], dict(CONFIG))
+    ev = PerEpisodeEvaluation(envs, agent, sim_seed=1, max_steps=steps, kind="gape")
+    plan_s, forms, live = [], [], []
+    real = ev._plan
+
+    def plan(idx, states, step_counts):
+        ev.ctx.synchronize()
+        t0 = time.perf_counter()
+        out = real(idx, states, step_counts)
+        ev.ctx.synchronize()
+        plan_s.append(time.perf_counter() - t0)
+        forms.append(ev.ctx.last_kernel_variant())
+        live.append(len(idx))
+        return out
+    ev._plan = plan
+    t0 = time.perf_counter()
+    out = ev.run()
+    wall = time.perf_counter() - t0
+    ev.close()
+    lock_steps = len(plan_s)
+    pc = agent.planner.config
+    return dict(what="one run on one machine: PerEpisodeEvaluation(kind='gape') on ChangingHighwayEnv, MDPGapEAgent baseline config",
+                episodes=n, steps=steps, planner_episodes=int(pc["episodes"]), horizon=int(pc["horizon"]), lock_steps=lock_steps,
+                live_per_lock_step=live, kernel_forms=forms, plan_ms_per_lock_step=[1e3 * s for s in plan_s],
+                plan_ms_first=1e3 * plan_s[0],
+                plan_ms_mean_after_first=1e3 * float(np.mean(plan_s[1:])) if lock_steps > 1 else None,
+                wall_ms_per_lock_step=1e3 * wall / max(lock_steps, 1),
+                split_ms_per_lock_step={k: 1e3 * v / max(lock_steps, 1) for k, v in out["seconds"].items()},
+                episode_steps=int(out["lengths"].sum()), planner_env_steps=int(out["planner_env_steps"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--episodes", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=6)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    entry = timed_run(args.episodes, args.steps)
+    print(json.dumps(entry))
+    if args.out:
+        doc = {}
+        if os.path.exists(args.out):
+            with open(args.out) as f:
+                doc = json.load(f)
+        doc["device_lock_step"] = entry
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
