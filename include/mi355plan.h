@@ -35,6 +35,9 @@ extern "C" {
 #define MP_ERR_REWARD_RANGE (-2) /* OPD: reward outside [0,1] (deterministic.py:46-47 ValueError) */
 #define MP_ERR_GAPE_NO_CHALLENGER (-9) /* MDP-GapE status: the root lists one action (mdp_gape.py:247, max() of an empty list: ValueError) */
 #define MP_ERR_GAPE_PLACEHOLDERS (-10) /* MDP-GapE status: more next states observed than max_next_states_count (mdp_gape.py:284 ValueError) */
+#define MP_ERR_GBOP_PLACEHOLDERS (-11) /* GBOP status: more next states observed than max_next_states_count (graph_based_stochastic.py:217 ValueError) */
+#define MP_ERR_GBOP_REWARD_THRESHOLD (-12) /* GBOP status: a reward threshold other than 0 reached the mis-called kl_upper_bound (:79-82 TypeError) */
+#define MP_ERR_GBOP_CHOICE_P (-13) /* GBOP status: p_minus fails the checks of Generator.choice in get_plan (:156 ValueError) */
 #define MP_ERR_ALLOC (-3)
 #define MP_ERR_ARG (-4)          /* invalid argument / unsupported configuration                  */
 #define MP_ERR_MODE (-5)         /* model kind not valid for this call ("Unknown mode")           */
@@ -1011,6 +1014,72 @@ int mp_gbopd_info(mp_gbopd *planners, int32_t *n_planners, int32_t *n_states, in
 int mp_gbopd_export(mp_gbopd *planners, int32_t planner, int32_t cap, int32_t *n_nodes, int32_t *state, double *lower,
                     double *upper, uint8_t *expanded, int32_t *child, double *reward, int32_t *parent_ptr, int32_t *parent_idx,
                     int64_t *visits, int64_t *updates, int64_t *n_observations, int32_t *root);
+
+/* ---------------------------------------------------------------- GBOP ---------------------- */
+/*
+ * StochasticGraphBasedPlanner / GraphDecisionNode / GraphChanceNode (tree_search/graph_based_stochastic.py:15-343): GBOP,
+ * optimistic planning on the graph of observed states of a STOCHASTIC MDP, with known rewards and a KL confidence region over
+ * every (state, action)'s next-state distribution.  It serves the configs whose reward threshold evaluates to 0 -- every
+ * config the reference ships ("0*np.log(time)"): compute_reward_ucb then takes mu_ucb = mu_lcb = cumulative_reward / count
+ * (:76-77).  Any other value reaches the mis-called kl_upper_bound (:79-82) and is reported as the reference's TypeError.
+ * An mp_gbop handle holds, for n_planners independent planners of one finite MDP (mp_gbop_create replaces the planner's
+ * constructor and what reset(), :339-343, leaves alone) -- a deterministic table, a dense or a sparse model, with or without an
+ * availability table and listing order; CartPole, joint, batch and row-block models answer MP_ERR_MODE -- what a reference
+ * planner OBJECT holds across plan() calls and agent.reset(): planner.nodes with both bounds, count and parents of every
+ * state, and per (state, listed action) the chance node with its count, stored bounds, p_plus / p_minus and its
+ * max_next_states (1..32, else MP_ERR_ARG) transition children: placeholder or observed state, count, cumulative reward,
+ * mu_ucb, mu_lcb.  queue_cap as mp_gbopd_create (MP_GBOP_QUEUE in the environment).
+ * mp_gbop_free replaces the planner object's end of life.
+ * mp_gbop_plan = StochasticGraphBasedPlanner.plan (:332-337) for every planner: root = get_node(root_state), `episodes` calls
+ * of run() (:234-268) of `horizon` >= 1 steps each -- the clone re-seeded with one draw of the planner's generator (:239), the
+ * sampling rule (:42-51), the step (its `done` discarded, :251), get_child with the lowest placeholder left (:207-219), the
+ * counts, and partial_value_iteration over the reversed update queue (:89-101) -- then get_plan (graph_based.py:126-135):
+ * the root's selection_rule (:53-60) and the chosen chance node's np_random.choice(keys, p=p_minus) (:152-156).
+ *   max_next_states must be the handle's (MP_ERR_ARG).  value_max = 1 / (1 - gamma) as the host computes it; accuracy and
+ *   sampling_timeout as in the config (a plan holds min(sampling_timeout, 2) entries).  -1 < gamma < 1, accuracy >= 0.
+ *   reward_thr_by_count / transition_thr_by_count double [n_counts]: the config's threshold strings evaluated by count 1 ..
+ *   n_counts (:69-75, :200-205; the kernel divides the transition threshold by the count, :179).  Counts are LIFETIME counts
+ *   of the handle: n_counts must reach mp_gbop_info's max_count plus episodes * horizon (else MP_ERR_ARG); the host extends
+ *   its tables by the new counts only.
+ *   rng_state uint64 [n,6]: the seed draw of every episode, the tie draws of random_argmax, the double of choice.
+ *   action int32 [n] (the model's slot = listing order, -1 without a plan), key int32 [n] (the drawn child: a state, or
+ *   -1 - i for "placeholder_i"), plan_len int32 [n] (0, 1 or 2), value_lower / value_upper double [n] (the root's bounds),
+ *   env_steps / pops int64 [n] (model steps / queue pops of this call), status int32 [n]: MP_OK,
+ *   MP_ERR_GBOP_PLACEHOLDERS (the ValueError of :217-218, after the step was counted), MP_ERR_GBOP_REWARD_THRESHOLD (the
+ *   TypeError of :79-82: by then the seed draw, the tie draw, one step and the counts of the first episode are made),
+ *   MP_ERR_GBOP_CHOICE_P (numpy's "probabilities do not sum to 1" and its kin), MP_ERR_GBOPD_NO_ACTION (a node no action is
+ *   listed for: np.amax([]) in random_argmax, ValueError), MP_ERR_GBOPD_DIVERGED (more than 2^22 pops in one plan),
+ *   MP_ERR_ALLOC (queue full) or MP_ERR_ARG (root out of range in a device array).  A planner that reported any of them
+ *   stays failed and reports it again.  Changed tables or action sets under a kept graph: as mp_gbopd_plan.
+ *   mem as elsewhere (MP_MEM_HOST / MP_MEM_DEVICE / MP_MEM_RNG_DEVICE).  mp_last_kernel_variant reports one of
+ *   mp_gbop_form_names: "gbop_{table,dense,sparse}_{lds,global}" (part of no other list); MP_GBOP_LDS_BYTES moves the limit
+ *   below which the graph nodes' bounds live in LDS (default 16 KiB, 0: never).
+ * mp_gbop_info replaces reading the planner object's sizes; max_count: no count of any planner exceeds it.
+ * mp_gbop_export replaces reading planner.nodes: one planner's graph in creation order, arrays of capacity cap >= n_nodes:
+ *   state, lower, upper, expanded, count [cap]; per action slot [cap, n_actions]: listed, chance_count, chance_assigned (the
+ *   children that stand for a state), chance_backed (that number at the last backup, -1: never backed up), chance_value
+ *   [.., 2] (upper, lower); per child SLOT [cap, n_actions, max_next_states] (slot j is placeholder_j until the j-th state
+ *   observed takes it; the reference's dict order is slots m .. K-1, 0 .. m-1 for m assigned): child_state (-1 - j for a
+ *   placeholder), child_count, child_cumulative_reward, child_mu_ucb, child_mu_lcb; p_plus / p_minus in the dict order of the
+ *   backup that wrote them; parent_ptr / parent_idx, visits [n_states], n_observations, root as mp_gbopd_export.
+ */
+typedef struct mp_gbop mp_gbop;
+int mp_gbop_create(mp_ctx *ctx, mp_model *model, int32_t n_planners, int32_t max_next_states, int32_t queue_cap, mp_gbop **out);
+int mp_gbop_free(mp_gbop *planners);
+int mp_gbop_plan(mp_ctx *ctx, mp_gbop *planners, const int32_t *root_state, int32_t episodes, int32_t horizon,
+                 int32_t max_next_states, double gamma, double value_max, double accuracy, int32_t sampling_timeout,
+                 int32_t n_counts, const double *reward_thr_by_count, const double *transition_thr_by_count, uint64_t *rng_state,
+                 int32_t *action, int32_t *key, int32_t *plan_len, double *value_lower, double *value_upper, int64_t *env_steps,
+                 int64_t *pops, int32_t *status, int32_t mem);
+int mp_gbop_info(mp_gbop *planners, int32_t *n_planners, int32_t *n_states, int32_t *n_actions, int32_t *max_next_states,
+                 int32_t *queue_cap, int64_t *n_edges, int64_t *max_count);
+int mp_gbop_export(mp_gbop *planners, int32_t planner, int32_t cap, int32_t *n_nodes, int32_t *state, double *lower, double *upper,
+                   uint8_t *expanded, int64_t *count, uint8_t *listed, int32_t *chance_count, int32_t *chance_assigned,
+                   int32_t *chance_backed, double *chance_value, int32_t *child_state, int32_t *child_count,
+                   double *child_cumulative_reward, double *child_mu_ucb, double *child_mu_lcb, double *p_plus, double *p_minus,
+                   int32_t *parent_ptr, int32_t *parent_idx, int64_t *visits, int64_t *n_observations, int32_t *root);
+/* The names mp_gbop_plan records for mp_last_kernel_variant, newline separated (host only; part of no other list). */
+const char *mp_gbop_form_names(void);
 
 /* ---------------------------------------------------------------- batched evaluation -------- */
 /*

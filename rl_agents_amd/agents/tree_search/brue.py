@@ -63,7 +63,9 @@ class BRUE(OLOP):
             # no rollout was made (budget <= 0): the reference's np.amax([]) of the root's selection raises (brue.py:75)
             raise ValueError("zero-size array to reduction operation maximum which has no identity")
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, env_rng_states=None):
+        """``env_rng_states`` (what BatchedEvaluation hands every planner on a stochastic env) is accepted and ignored: every
+        episode's clone is re-seeded with a draw of the planner's generator, so the environment's own is never read."""
         model = self.model_for(state)
         self.about_to_plan()
         if rng_states is None:

@@ -142,7 +142,9 @@ class OLOP(AbstractPlanner):
                 raise KeyError(0)                                                           # olop.py:89
             raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # olop.py:133-134
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, env_rng_states=None):
+        """``env_rng_states`` (what BatchedEvaluation hands every planner on a stochastic env) is accepted and ignored: every
+        episode's clone is re-seeded with a draw of the planner's generator, so the environment's own is never read."""
         if "episodes" not in self.config:    # (olop.py:95; raised here, before anything is uploaded)
             raise KeyError("episodes")
         horizon = int(self.config["horizon"])

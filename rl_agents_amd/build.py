@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmi355plan.so")
-SOURCES = ["api.hip", "vi.hip", "uct.hip", "uct_stoch.hip", "opd.hip", "ropd.hip", "saopd.hip", "olop.hip", "brue.hip", "gbopd.hip", "sparse_sampling.hip", "gape.hip", "gape_stoch.hip"]
+SOURCES = ["api.hip", "vi.hip", "uct.hip", "uct_stoch.hip", "opd.hip", "ropd.hip", "saopd.hip", "olop.hip", "brue.hip", "gbopd.hip", "sparse_sampling.hip", "gape.hip", "gape_stoch.hip", "gbop.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp"))   # every header: a stale library is a wrong library
 # -ffp-contract=off: the reference evaluates a*b+c with two roundings (Python floats); a fused
 # multiply-add would change the last bit of bounds and Q values and break bit-exact parity.

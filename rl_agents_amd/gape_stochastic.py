@@ -47,8 +47,10 @@ class StochasticMDPGapE(MDPGapE):
             out[count - 1] = float(eval(bound["transition_threshold"], {"np": np}, dict(names, count=count)))
         return out
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None):
-        """``root_steps`` is accepted for the common interface: the step limit ends no episode (done = terminated)."""
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, env_rng_states=None):
+        """``root_steps`` is accepted for the common interface: the step limit ends no episode (done = terminated).
+        ``env_rng_states`` (what BatchedEvaluation hands every planner on a stochastic env) is accepted and ignored: every
+        episode's clone is re-seeded with a draw of the planner's generator, so the environment's own is never read."""
         cfg = self.config
         episodes, horizon, count = int(cfg["episodes"]), int(cfg["horizon"]), cfg["max_next_states_count"]
         if count != int(count) or int(count) < 1:

@@ -19,6 +19,9 @@ ERR_REWARD_RANGE, ERR_ARG, ERR_MODE = -2, -4, -5
 MP_ERR_GBOPD_DIVERGED, MP_ERR_GBOPD_NO_ACTION = -7, -8
 ERR_GAPE_NO_CHALLENGER = -9  # mp_gape_plan status: the root lists one action (mdp_gape.py:247 ValueError)
 ERR_GAPE_PLACEHOLDERS = -10  # mp_gape_plan_stochastic status: no placeholder left for a new next state (mdp_gape.py:284 ValueError)
+ERR_GBOP_PLACEHOLDERS = -11   # mp_gbop_plan status: no placeholder left for a new next state (graph_based_stochastic.py:217 ValueError)
+ERR_GBOP_REWARD_THRESHOLD = -12   # mp_gbop_plan status: a nonzero reward threshold reached the mis-called kl_upper_bound (:79-82 TypeError)
+ERR_GBOP_CHOICE_P = -13       # mp_gbop_plan status: p_minus fails Generator.choice's checks in get_plan (:156 ValueError)
 ERR_OLOP_KEY = -6          # mp_olop_plan status: the "zeros" continuation's action is not a child (olop.py:89 KeyError)
 
 _LIB = None
@@ -139,6 +142,13 @@ SIGNATURES = {
     "mp_gape_plan_stochastic": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp,
                                           _vp, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_gape_stoch_form_names": (C.c_char_p, []),
+    "mp_gbop_create": (C.c_int, [_vp, _vp, c_i32, c_i32, c_i32, P(_vp)]),
+    "mp_gbop_free": (C.c_int, [_vp]),
+    "mp_gbop_plan": (C.c_int, [_vp, _vp, _vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_gbop_info": (C.c_int, [_vp, P(c_i32), P(c_i32), P(c_i32), P(c_i32), P(c_i32), P(c_i64), P(c_i64)]),
+    "mp_gbop_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32)] + [_vp] * 20 + [P(c_i64), P(c_i32)]),
+    "mp_gbop_form_names": (C.c_char_p, []),
     "mp_gape_stoch_tree_export": (C.c_int, [_vp, c_i32, c_i32, P(c_i32), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_selftest_gape_transition": (C.c_int, [_vp, c_i32, c_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_brue_plan":(C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_f64, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
@@ -288,6 +298,8 @@ RESULTS = {
     "saopd": (_PLANS, _LEN, _STEPS, ("updates", np.int64, (), 0), _STATUS),
     "gbopd": (_PLANS, _LEN, ("value_lower", np.float64, (), 0), ("value_upper", np.float64, (), 0), _STEPS,
               ("updates", np.int64, (), 0), _STATUS),
+    "gbop": (_ACTION, ("key", np.int32, (), 0), _LEN, ("value_lower", np.float64, (), 0), ("value_upper", np.float64, (), 0),
+             _STEPS, ("pops", np.int64, (), 0), _STATUS),
 }
 # what a small plan's pinned scratch arrays hold in front of the family's results
 SCRATCH_INPUTS = {"uct": (("root_state", np.int32, ()), ("root_steps", np.int32, ()), ("rng", np.uint64, (6,))),
@@ -512,6 +524,12 @@ def gape_stoch_form_names():
     """The names an MDP-GapE plan with transition bounds (``gape_plan_stochastic``) records for Context.last_kernel_variant()
     (mp_gape_stoch_form_names; host only).  They are part of no other list of names."""
     return load().mp_gape_stoch_form_names().decode().split()
+
+
+def gbop_form_names():
+    """The names a GBOP plan (``StochasticGraphBasedPlanners.plan``) records for Context.last_kernel_variant()
+    (mp_gbop_form_names; host only).  They are part of no other list of names."""
+    return load().mp_gbop_form_names().decode().split()
 
 
 def olop_stoch_form_names():
@@ -1770,6 +1788,108 @@ class GraphBasedPlanners(_Handle):
                     n_children=n_children, child_action=take(slots, -1).astype(np.int32),
                     child_node=take(child, -1).astype(np.int32), child_reward=take(reward, 0.0),
                     parent_ptr=pptr[:n + 1].copy(), parent_idx=pidx[:pptr[n]].copy(), visits=visits, updates=updates,
+                    n_observations=np.asarray(nobs.value), root=np.asarray(root.value))
+
+
+class StochasticGraphBasedPlanners(_Handle):
+    """A batch of device-resident StochasticGraphBasedPlanner objects (mp_gbop): the graph of observed states with both
+    bounds, counts and parents in insertion order, and per (state, listed action) the chance record with its
+    ``max_next_states`` transition children persist across plan() calls, as in the reference
+    (tree_search/graph_based_stochastic.py:339-343).  ``queue_cap``: entries of a planner's backup queue (None: the library's
+    default)."""
+    _free = "mp_gbop_free"
+    # mp_gbop_export's arrays after n_nodes: (name, dtype, trailing shape in terms of A and K); then visits [S]
+    EXPORT = (("state", np.int32, ""), ("lower", np.float64, ""), ("upper", np.float64, ""), ("expanded", np.uint8, ""),
+              ("count", np.int64, ""), ("listed", np.uint8, "A"), ("chance_count", np.int32, "A"), ("chance_assigned", np.int32, "A"),
+              ("chance_backed", np.int32, "A"), ("chance_value", np.float64, "A2"), ("child_state", np.int32, "AK"),
+              ("child_count", np.int32, "AK"), ("child_cum", np.float64, "AK"), ("child_mu_ucb", np.float64, "AK"),
+              ("child_mu_lcb", np.float64, "AK"), ("p_plus", np.float64, "AK"), ("p_minus", np.float64, "AK"))
+
+    def __init__(self, ctx, model, n_planners, max_next_states, queue_cap=None):
+        self.ctx, self.model, self.n, self.K = ctx, model, int(n_planners), int(max_next_states)
+        self._h = _vp()
+        _check(ctx._lib.mp_gbop_create(ctx._h, model._h, self.n, self.K, int(queue_cap or 0), C.byref(self._h)))
+
+    def plan(self, root_state, episodes, horizon, gamma, value_max, accuracy, sampling_timeout, reward_thr_by_count,
+             transition_thr_by_count, rng_state):
+        """StochasticGraphBasedPlanner.plan for every planner (host arrays).  ``value_max``: the host's ``1 / (1 - gamma)``;
+        the two threshold tables by LIFETIME count, ``[count - 1]``, at least ``info()["max_count"] + episodes * horizon``
+        entries each."""
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        if rs.shape[0] != self.n:
+            raise ValueError("one root state per planner ({}), got {}".format(self.n, rs.shape[0]))
+        _check_rng(rng_state, self.n, "n_planners")
+        out = _results("gbop", self.n)
+        self._call(MP_MEM_HOST, _ptr(rs), episodes, horizon, gamma, value_max, accuracy, sampling_timeout, reward_thr_by_count,
+                   transition_thr_by_count, _ptr(rng_state), _result_ptrs("gbop", out))
+        return out
+
+    def _call(self, mem, rs, episodes, horizon, gamma, value_max, accuracy, sampling_timeout, rthr, tthr, rng, o):
+        """The one call of mp_gbop_plan, on addresses (``o``: those of the eight results)."""
+        rthr = np.ascontiguousarray(rthr, dtype=np.float64).reshape(-1)
+        tthr = np.ascontiguousarray(tthr, dtype=np.float64).reshape(-1)
+        if rthr.size != tthr.size:
+            raise ValueError("the reward and the transition threshold table must hold the same counts")
+        _check(self.ctx._lib.mp_gbop_plan(self.ctx._h, self._h, rs, int(episodes), int(horizon), self.K, float(gamma),
+                                          float(value_max), float(accuracy), int(sampling_timeout), int(rthr.size), _ptr(rthr),
+                                          _ptr(tthr), rng, *o, mem))
+
+    def plan_device(self, root_state, episodes, horizon, gamma, value_max, accuracy, sampling_timeout, reward_thr_by_count,
+                    transition_thr_by_count, rng_state, action=None, key=None, plan_len=None, value_lower=None, value_upper=None,
+                    env_steps=None, pops=None, status=None, rng_device_only=False):
+        """Asynchronous form: every array is a device buffer (torch tensors on the context's device) but the two threshold
+        tables, which stay host arrays; one launch on the context's stream, nothing read back.  ``rng_device_only``: the
+        root states and results are host arrays and only ``rng_state`` lives on the device (MP_MEM_RNG_DEVICE)."""
+        self._call(MP_MEM_RNG_DEVICE if rng_device_only else MP_MEM_DEVICE, _ptr(root_state), episodes, horizon, gamma, value_max,
+                   accuracy, sampling_timeout, reward_thr_by_count, transition_thr_by_count, _ptr(rng_state),
+                   _ptrs(action, key, plan_len, value_lower, value_upper, env_steps, pops, status))
+
+    def info(self):
+        n, s, a, k, q, e, c = c_i32(), c_i32(), c_i32(), c_i32(), c_i32(), c_i64(), c_i64()
+        _check(self.ctx._lib.mp_gbop_info(self._h, C.byref(n), C.byref(s), C.byref(a), C.byref(k), C.byref(q), C.byref(e),
+                                          C.byref(c)))
+        return dict(n_planners=n.value, n_states=s.value, n_actions=a.value, max_next_states=k.value, queue_cap=q.value,
+                    n_edges=e.value, max_count=c.value)
+
+    def export(self, planner=0):
+        """One planner's graph in creation order, in the fields of the goldens' listing (tests/gbop_restatement.py): state,
+        lower, upper, expanded, count, n_children; per listing position [n, A]: action (the model's slot), c_count, c_upper,
+        c_lower, c_backed; per child in the reference's DICT order [n, A, K]: k_state (-1 - i for ``placeholder_i``), k_count,
+        k_cum, k_mu_ucb, k_mu_lcb; p_plus / p_minus as their backup wrote them; parent_ptr / parent_idx, visits [S],
+        n_observations, root."""
+        inf = self.info()
+        S, A, K = inf["n_states"], inf["n_actions"], inf["max_next_states"]
+        tails = {"": (), "A": (A,), "A2": (A, 2), "AK": (A, K)}
+        t = {k: np.zeros((S,) + tails[tail], dtype) for k, dtype, tail in self.EXPORT}
+        pptr, pidx = np.zeros(S + 1, np.int32), np.zeros(max(inf["n_edges"], 1), np.int32)
+        visits = np.zeros(S, np.int64)
+        nn, nobs, root = c_i32(), c_i64(), c_i32()
+        _check(self.ctx._lib.mp_gbop_export(self._h, int(planner), S, C.byref(nn), *([_ptr(v) for v in t.values()] +
+                                            [_ptr(pptr), _ptr(pidx), _ptr(visits), C.byref(nobs), C.byref(root)])))
+        n = nn.value
+        t = {k: v[:n] for k, v in t.items()}
+        listed = t["listed"] != 0
+        rank = np.argsort(~listed, axis=1, kind="stable")                  # the listed slots first, in slot order
+        n_children = listed.sum(axis=1).astype(np.int32)
+        keep = np.arange(A)[None, :] < n_children[:, None]
+
+        def take(x, fill):
+            idx = rank.reshape(rank.shape + (1,) * (x.ndim - 2))
+            mask = keep.reshape(keep.shape + (1,) * (x.ndim - 2))
+            return np.where(mask, np.take_along_axis(x, np.broadcast_to(idx, x.shape), axis=1), fill)
+
+        # the reference's dict order of a chance node's children: the slots m .. K - 1, then 0 .. m - 1
+        rot = (np.arange(K)[None, None, :] + t["chance_assigned"][:, :, None]) % K
+        children = lambda x, fill: take(np.take_along_axis(x, rot, axis=2), fill)  # noqa: E731
+        slots = np.broadcast_to(np.arange(A, dtype=np.int32), (n, A))
+        return dict(state=t["state"].copy(), lower=t["lower"].copy(), upper=t["upper"].copy(), expanded=t["expanded"].copy(),
+                    count=t["count"].copy(), n_children=n_children, action=take(slots, -1).astype(np.int32),
+                    c_count=take(t["chance_count"], 0).astype(np.int64), c_upper=take(t["chance_value"][:, :, 0], 0.0),
+                    c_lower=take(t["chance_value"][:, :, 1], 0.0), c_backed=take(t["chance_backed"], -1).astype(np.int32),
+                    k_state=children(t["child_state"], 0).astype(np.int32), k_count=children(t["child_count"], 0).astype(np.int64),
+                    k_cum=children(t["child_cum"], 0.0), k_mu_ucb=children(t["child_mu_ucb"], 0.0),
+                    k_mu_lcb=children(t["child_mu_lcb"], 0.0), p_plus=take(t["p_plus"], 0.0), p_minus=take(t["p_minus"], 0.0),
+                    parent_ptr=pptr[:n + 1].copy(), parent_idx=pidx[:pptr[n]].copy(), visits=visits,
                     n_observations=np.asarray(nobs.value), root=np.asarray(root.value))
 
 
