@@ -262,6 +262,10 @@ class StochasticGraphBasedPlanner(GraphBasedPlanner):
             raise TypeError(REWARD_THRESHOLD_MESSAGE)
         if (status == native.ERR_GBOP_CHOICE_P).any():
             raise ValueError("probabilities do not sum to 1")                       # Generator.choice in get_plan (:156)
+        if (status == native.MP_ERR_ALLOC).any():                                   # (mp_gbop_create reads its own knob)
+            raise RuntimeError("graph-based planner: backup queue overflow on the device; raise the queue capacity "
+                               "(StochasticGraphBasedPlanner.queue_capacity, or MP_GBOP_QUEUE in the environment) and start "
+                               "again: the planner's graph is half updated and stays failed")
         GraphBasedPlanner.raise_for_status(status)
 
     def raise_for_result(self, out):

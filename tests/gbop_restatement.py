@@ -69,7 +69,16 @@ class Graph(object):
         self.k_mu_lcb = np.zeros((S, A, K))                   # mu_lcb: the same number once a reward was recorded
         self.p_plus = np.zeros((S, A, K))                     # in the dict order of the backup that wrote them
         self.p_minus = np.zeros((S, A, K))
-        self.pops = self.queue_peak = 0                       # diagnostics
+        self.pops = self.queue_peak = 0                       # diagnostics: they change no result
+        self.reset_diagnostics()
+
+    def reset_diagnostics(self):
+        """Per call of partial_value_iteration ``pvi_pushed`` (the initial queue plus every ``extend``) and ``pvi_peak`` (its
+        longest length) are those of the LAST call; ``max_pushed`` / ``queue_peak`` their maxima and ``longest_update_queue`` the
+        longest ``update_queue`` of a run since the graph was made or this was called; ``deepest_requeue`` the highest index
+        at which a run found its state in ``update_queue`` already (-1: no run came back to a state)."""
+        self.queue_peak = self.pvi_pushed = self.pvi_peak = self.max_pushed = self.longest_update_queue = 0
+        self.deepest_requeue = -1
 
     def dict_order(self, s, a):
         m = int(self.c_assigned[s, a])
@@ -126,8 +135,9 @@ class Graph(object):
     # partial_value_iteration (:89-101)
     def partial_value_iteration(self, queue, accuracy, tthr, observe):
         head = 0
+        self.pvi_pushed, self.pvi_peak = len(queue), 0
         while head < len(queue):
-            self.queue_peak = max(self.queue_peak, len(queue) - head)
+            self.pvi_peak = max(self.pvi_peak, len(queue) - head)
             node = queue[head]
             head += 1
             self.pops += 1
@@ -139,6 +149,8 @@ class Graph(object):
             observe("delta", delta, accuracy)
             if delta > accuracy:
                 queue.extend(self.parents[node])
+                self.pvi_pushed += len(self.parents[node])
+        self.queue_peak, self.max_pushed = max(self.queue_peak, self.pvi_peak), max(self.max_pushed, self.pvi_pushed)
 
     def step(self, s, a, clone):
         if self.mode == "deterministic":
@@ -182,7 +194,10 @@ class Graph(object):
             self.k_mu[s, a, j] = self.k_mu_lcb[s, a, j] = self.k_cum[s, a, j] / self.k_count[s, a, j]
             if s not in update_queue:
                 update_queue.append(s)
+            else:
+                self.deepest_requeue = max(self.deepest_requeue, update_queue.index(s))
             s = s_next
+        self.longest_update_queue = max(self.longest_update_queue, len(update_queue))
         self.partial_value_iteration(list(reversed(update_queue)), accuracy, tthr, observe)
 
     def key_of(self, s, a, slot):
