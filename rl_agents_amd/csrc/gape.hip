@@ -17,6 +17,9 @@
 // Records live in the wave_tree workspace, children contiguous in creation order: at most 1 + (episodes + 2) * horizon * |A|.
 // Everything that is not a basic IEEE operation -- the initial values (Python **), the thresholds by count (eval of the config
 // string) -- comes from host tables.  The Newton step's log is the device's (bounds to 1e-12, not bit-exact).
+// What this file has in common with gape_stoch.hip -- the result arrays, the argument checks, the capacity refusals and the tables
+// of the host side; the stopping rule and the read-out of a root on the device -- is in gape_shared.hpp, the selection among a
+// node's children in gape_select.hpp.  The episode loop, the listing of an expansion and the deferred bounds included, is here.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -27,15 +30,11 @@
 
 #include "common.hpp"
 #include "each_host.hpp"
-#include "gape_select.hpp"
+#include "gape_shared.hpp"
 #include "kl_bound.hpp"
-#include "pcg64.hpp"
 #include "wave.hpp"
-#include "wave_host.hpp"
 
 namespace mp {
-
-constexpr size_t kGapeKeepBytes = (size_t)1 << 30; // trees of every root kept while they fit (the rule of OLOP and BRUE)
 
 struct GapeNode {
     double cum, mu_ucb, mu_lcb;     // the decision child: cumulative_reward, mu_ucb, mu_lcb (olop.py:109-116, mdp_gape.py:139-143)
@@ -60,9 +59,7 @@ struct GapeArgs {
     GapeNode *nodes;     // [slots][cap]
     double *val;         // [slots][cap][2] the chance nodes' value_upper, value_lower
     int32_t *n_nodes_out;
-    int32_t *plans, *plan_len, *episodes_run, *status, *arms; // arms [n_roots][2]: the best arm's action and the challenger's
-    int64_t *env_steps, *child_count; // child_count [n_roots][A] by column, -1 where the root lists no such action
-    double *child_lower, *child_upper; // [n_roots][A]
+    GapeResults out;
 };
 
 // EACH (mp_gape_plan_models: a batch model of deterministic tables, one MDP per root, the roots' states GLOBAL -- nodes keep
@@ -230,42 +227,13 @@ __global__ __launch_bounds__(64) void gape_kernel(GapeArgs p)
                 }
                 __syncthreads();
             }
-            // the stopping rule (:100-102) on the root's best arm and challenger
-            const int fc0 = N[0].first_child;
-            int sel;
-            gape_bai(V + 2 * (long)fc0, N[0].n_children, lane, &sel, &best, &challenger);
             episodes_run = e + 1;
-            if (V[2 * (long)(fc0 + challenger)] - V[2 * (long)(fc0 + best) + 1] < p.accuracy) break;
+            if (gape_stop(V, N[0].first_child, N[0].n_children, lane, p.accuracy, &best, &challenger)) break;
         }
-        // get_plan (:129-131): the best arm's action; the root's arms for the caller
-        const int fc0 = N[0].first_child, k0 = N[0].n_children;
-        for (int a = lane; a < A; a += 64) {
-            if (p.child_count) p.child_count[(long)root * A + a] = -1;
-            if (p.child_lower) p.child_lower[(long)root * A + a] = 0.0;
-            if (p.child_upper) p.child_upper[(long)root * A + a] = 0.0;
-        }
-        __syncthreads();
-        for (int i = lane; i < k0; i += 64) {
-            const GapeNode c = N[fc0 + i];
-            if (p.child_count) p.child_count[(long)root * A + c.action] = c.count_c;
-            if (p.child_lower) p.child_lower[(long)root * A + c.action] = V[2 * (long)(fc0 + i) + 1];
-            if (p.child_upper) p.child_upper[(long)root * A + c.action] = V[2 * (long)(fc0 + i)];
-        }
-        if (lane == 0) {
-            const bool ok = status == MP_OK && best >= 0;
-            gen.store(p.rng + (long)root * 6);
-            if (p.plans)
-                for (int i = 0; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = ok && i == 0 ? N[fc0 + best].action : -1;
-            if (p.plan_len) p.plan_len[root] = ok ? 1 : 0;
-            if (p.episodes_run) p.episodes_run[root] = episodes_run;
-            if (p.status) p.status[root] = status;
-            if (p.env_steps) p.env_steps[root] = steps;
-            if (p.arms) {
-                p.arms[2 * (long)root] = ok ? N[fc0 + best].action : -1;
-                p.arms[2 * (long)root + 1] = ok ? N[fc0 + challenger].action : -1;
-            }
-            p.n_nodes_out[root] = n_nodes;
-        }
+        const int fc0 = N[0].first_child;
+        gape_read_out(p.out, p.rng, root, A, p.max_plan_len, lane, V, fc0, N[0].n_children, gen, status, best, challenger, episodes_run,
+                      steps, [&](int i) { return N[fc0 + i].action; }, [&](int i) { return N[fc0 + i].count_c; });
+        if (lane == 0) p.n_nodes_out[root] = n_nodes;
         __syncthreads();
     }
 }
@@ -312,35 +280,17 @@ int gape_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t 
     if (each && !model->table_batch)
         return fail(MP_ERR_MODE, "%s: a batch model of deterministic tables (mp_model_load_table_batch) expected", who);
     const int A = model->A;
-    if (n_roots < 1 || episodes < 0 || horizon < 1 || horizon > 16384 || max_plan_len < 0 || A < 1 || n_actions_env < 1)
-        return fail(MP_ERR_ARG, "%s: bad sizes", who);
-    // a NaN among them would make NaN bounds of every node, which the reference plans on and no plan is worth
-    if (!isfinite(gamma) || !isfinite(accuracy)) return fail(MP_ERR_ARG, "%s: gamma and accuracy must be finite", who);
-    for (int c = 0; c < episodes + 2; ++c)
-        if (!isfinite(thr_by_count[c])) return fail(MP_ERR_ARG, "%s: the threshold of count %d is not finite", who, c + 1);
-    for (int d = 0; d <= horizon; ++d)
-        if (!isfinite(value_init[d])) return fail(MP_ERR_ARG, "%s: the initial value of depth %d is not finite", who, d);
-    if (continuation != 0 && continuation != 1) return fail(MP_ERR_ARG, "%s: continuation %d is neither 0 (action 0) nor 1 (uniform)", who, continuation);
-    if (!action_column && n_actions_env != A)
-        return fail(MP_ERR_ARG, "%s: %d environment actions need their columns among the model's %d", who, n_actions_env, A);
-    for (int a = 0; action_column && a < n_actions_env; ++a)
-        if (action_column[a] < -1 || action_column[a] >= A) return fail(MP_ERR_ARG, "%s: column %d out of range", who, action_column[a]);
+    const GapeTables host_tab{thr_by_count, nullptr, value_init, nullptr};
+    MP_TRY(gape_check_args(who, n_roots, episodes, horizon, 16384, max_plan_len, A, n_actions_env, gamma, accuracy, host_tab,
+                           continuation, action_column));
     std::vector<int32_t> global_tmp;
     if (each) MP_TRY(globalize_roots_arg(ctx, model, n_roots, model_index, root_state, mem_flags, global_tmp, &root_state));
     MP_TRY(wave_roots(ctx, who, root_state, n_roots, model->S, mem));
     // a record per chance node: every step of every episode may expand one decision node
     const long long cap = 1 + ((long long)episodes + 2) * horizon * A;
-    if (cap > 0x7fffffffLL) return fail(MP_ERR_ARG, "%s: %lld nodes per tree do not fit a 32-bit index", who, cap);
-    if ((size_t)cap * (sizeof(GapeNode) + 2 * sizeof(double)) > kGapeKeepBytes)
-        return fail(MP_ERR_ARG, "%s: %lld nodes per tree take more than 1 GiB", who, cap);
-
-    // one table: thresholds by count [M + 2], the initial values [H + 1], the columns of the environment's actions [n_env]
-    std::vector<double> tab((size_t)episodes + 2 + horizon + 1 + n_actions_env);
-    for (int c = 0; c < episodes + 2; ++c) tab[c] = thr_by_count[c];
-    for (int d = 0; d <= horizon; ++d) tab[(size_t)episodes + 2 + d] = value_init[d];
-    for (int a = 0; a < n_actions_env; ++a) tab[(size_t)episodes + 2 + horizon + 1 + a] = action_column ? action_column[a] : a;
-    double *d_tab = nullptr;
-    MP_TRY(upload_tables(ctx, 42, tab, &d_tab));
+    MP_TRY(gape_check_capacity(who, cap, sizeof(GapeNode)));
+    GapeTables tab;
+    MP_TRY(gape_upload_tables(ctx, 42, episodes, horizon, n_actions_env, action_column, host_tab, &tab));
 
     GapeArgs a;
     a.Sb = model->Sb > 0 ? model->Sb : model->S;
@@ -349,18 +299,11 @@ int gape_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t 
     const EachForm form = each ? each_form(EACH_GAPE, a.Sb, A, horizon, n_roots, cus) : each_form_global(EACH_GAPE, horizon, n_roots, cus);
     a.n_roots = n_roots; a.A = A; a.M = episodes; a.H = horizon; a.cap = (int)cap; a.done_on_next = model->done_on_next;
     a.uniform = continuation; a.n_env = n_actions_env; a.max_plan_len = max_plan_len; a.gamma = gamma; a.accuracy = accuracy;
-    a.grid = form.grid; a.rec = model->rec; a.thr = d_tab; a.vinit = d_tab + episodes + 2; a.col = a.vinit + horizon + 1;
+    a.grid = form.grid; a.rec = model->rec; a.thr = tab.thr; a.vinit = tab.vinit; a.col = tab.col;
     MP_TRY(wave_tree(ctx, 8, n_roots, A, (long)cap, 2, kGapeKeepBytes, a.grid + 1, a.grid, &a.nodes, &a.val, &a.n_nodes_out, &a.keep));
     WaveIo io(mem, rmem, n_roots, root_state, &a.root_state, rng_state, &a.rng);
-    io.add(WS_IO3, plans, &a.plans, (size_t)max_plan_len);
-    io.add(WS_IO4, plan_len, &a.plan_len);
-    io.add(WS_IO5, episodes_run, &a.episodes_run);
-    io.add(WS_IO8, env_steps, &a.env_steps);
-    io.add(WS_IO7, status, &a.status);
-    io.add(WS_IO6, child_lower, &a.child_lower, (size_t)A);
-    io.add(WS_IO9, child_upper, &a.child_upper, (size_t)A);
-    io.add(WS_IO1, child_count, &a.child_count, (size_t)A);
-    io.add(WS_IO10, best_challenger, &a.arms, (size_t)2);
+    gape_results_io(io, {plans, plan_len, episodes_run, status, best_challenger, env_steps, child_count, child_lower, child_upper},
+                    &a.out, max_plan_len, A);
     MP_TRY(wave_stage(ctx, io));
     if (each)
         MP_TRY(wave_launch(ctx, form.lds ? gape_kernel<GAPE_EACH_LDS> : gape_kernel<GAPE_EACH_GLOBAL>, a.grid, form.lds_bytes(),

@@ -1,6 +1,7 @@
 // gape_select.hpp -- what the two MDP-GapE kernels (gape.hip, gape_stoch.hip) do alike over a decision node's chance children,
 // whose values lie as C = [k][2] (value_upper, value_lower), 64 lanes at a time: the first maximum, best-arm identification at
-// the root (mdp_gape.py:228-249), np.amax of a column (:219-220) and random_argmax over value_upper (:189-192).
+// the root (mdp_gape.py:228-249), np.amax of a column (:219-220) and random_argmax over value_upper (:189-192).  Everything else
+// the two share, host side included, is in gape_shared.hpp, which includes this header.
 #pragma once
 #include <math.h>
 

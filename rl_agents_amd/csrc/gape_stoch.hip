@@ -18,6 +18,9 @@
 // cap = 1 + (episodes + 2) * horizon * K  +  (1 + (episodes + 2) * horizon) * |A|.
 // The KL bounds of the path's decision nodes stay deferred to after the walk, 64 at a time; thresholds by count (both tables)
 // and the initial values come from the host.
+// What this file has in common with gape.hip -- the result arrays, the argument checks, the capacity refusals and the tables of the
+// host side; the stopping rule and the read-out of a root on the device -- is in gape_shared.hpp, the selection among a node's
+// children in gape_select.hpp.  The episode loop, the listing of an expansion and the deferred bounds included, is here.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -28,17 +31,14 @@
 
 #include "common.hpp"
 #include "each_host.hpp"
-#include "gape_select.hpp"
+#include "gape_shared.hpp"
 #include "kl_bound.hpp"
 #include "kl_transition.hpp"
-#include "pcg64.hpp"
 #include "seed_sequence.hpp"
 #include "wave.hpp"
-#include "wave_host.hpp"
 
 namespace mp {
 
-constexpr size_t kGapeStochKeepBytes = (size_t)1 << 30; // trees of every root kept while they fit (the rule of mp_gape_plan)
 constexpr int kGapeStochTreeKind = 9;
 
 struct GsNode {
@@ -69,9 +69,7 @@ struct GapeStochArgs {
     GsNode *nodes;           // [slots][cap]
     double *val;             // [slots][cap][2] value_upper, value_lower of every node
     int32_t *n_nodes_out;
-    int32_t *plans, *plan_len, *episodes_run, *status, *arms;
-    int64_t *env_steps, *child_count;
-    double *child_lower, *child_upper;
+    GapeResults out;
 };
 
 __global__ __launch_bounds__(64) void gape_stoch_kernel(GapeStochArgs p)
@@ -101,9 +99,9 @@ __global__ __launch_bounds__(64) void gape_stoch_kernel(GapeStochArgs p)
         // the position of column `col` among them, -1 when it is not listed.  -1 when the records would not fit (not reached).
         auto expand = [&](int node, int state, int depth, int col, int *rank) {
             const int fc = n_nodes;
-            int pos0 = 0;
             *rank = -1;
             if (n_nodes + A > p.cap) return -1;
+            int pos0 = 0;
             for (int a0 = 0; a0 < A; a0 += 64) {
                 const int a = a0 + lane;
                 bool av = false;
@@ -276,43 +274,14 @@ __global__ __launch_bounds__(64) void gape_stoch_kernel(GapeStochArgs p)
                 if (li == 0) V[2 * (long)ch + (lower ? 1 : 0)] = v;
                 __syncthreads();
             }
-            // the stopping rule (:100-102) on the root's best arm and challenger
-            const int fc0 = N[0].first_child;
-            int sel;
-            gape_bai(V + 2 * (long)fc0, N[0].n_children, lane, &sel, &best, &challenger);
             episodes_run = e + 1;
-            if (V[2 * (long)(fc0 + challenger)] - V[2 * (long)(fc0 + best) + 1] < p.accuracy) break;
+            if (gape_stop(V, N[0].first_child, N[0].n_children, lane, p.accuracy, &best, &challenger)) break;
         }
         __syncthreads();
-        // get_plan (:129-131): the best arm's action; the root's arms for the caller
-        const int fc0 = N[0].first_child, k0 = N[0].n_children;
-        for (int a = lane; a < A; a += 64) {
-            if (p.child_count) p.child_count[(long)root * A + a] = -1;
-            if (p.child_lower) p.child_lower[(long)root * A + a] = 0.0;
-            if (p.child_upper) p.child_upper[(long)root * A + a] = 0.0;
-        }
-        __syncthreads();
-        for (int i = lane; i < k0; i += 64) {
-            const GsNode c = N[fc0 + i];
-            if (p.child_count) p.child_count[(long)root * A + c.key] = c.count;
-            if (p.child_lower) p.child_lower[(long)root * A + c.key] = V[2 * (long)(fc0 + i) + 1];
-            if (p.child_upper) p.child_upper[(long)root * A + c.key] = V[2 * (long)(fc0 + i)];
-        }
-        if (lane == 0) {
-            const bool ok = status == MP_OK && best >= 0;
-            gen.store(p.rng + (long)root * 6);
-            if (p.plans)
-                for (int i = 0; i < p.max_plan_len; ++i) p.plans[(long)root * p.max_plan_len + i] = ok && i == 0 ? N[fc0 + best].key : -1;
-            if (p.plan_len) p.plan_len[root] = ok ? 1 : 0;
-            if (p.episodes_run) p.episodes_run[root] = episodes_run;
-            if (p.status) p.status[root] = status;
-            if (p.env_steps) p.env_steps[root] = steps;
-            if (p.arms) {
-                p.arms[2 * (long)root] = ok ? N[fc0 + best].key : -1;
-                p.arms[2 * (long)root + 1] = ok ? N[fc0 + challenger].key : -1;
-            }
-            p.n_nodes_out[root] = n_nodes;
-        }
+        const int fc0 = N[0].first_child;
+        gape_read_out(p.out, p.rng, root, A, p.max_plan_len, lane, V, fc0, N[0].n_children, gen, status, best, challenger, episodes_run,
+                      steps, [&](int i) { return N[fc0 + i].key; }, [&](int i) { return N[fc0 + i].count; });
+        if (lane == 0) p.n_nodes_out[root] = n_nodes;
         __syncthreads();
     }
 }
@@ -362,59 +331,31 @@ int mp_gape_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const
     MP_TRY(wave_mem(who, &mem, &rmem));
     MP_TRY(wave_mdp_check(who, model, false)); // (a CartPole model is no finite MDP: MP_ERR_MODE)
     const int A = model->A, K = max_next_states;
-    if (n_roots < 1 || episodes < 0 || horizon < 1 || horizon > 8192 || max_plan_len < 0 || A < 1 || n_actions_env < 1)
-        return fail(MP_ERR_ARG, "%s: bad sizes", who);
     if (K < 1 || K > 32) return fail(MP_ERR_ARG, "%s: max_next_states_count %d is not in 1..32 (a chance node's children fill half a wavefront)", who, K);
-    // a NaN among them would make NaN bounds of every node, which the reference plans on and no plan is worth
-    if (!isfinite(gamma) || !isfinite(accuracy)) return fail(MP_ERR_ARG, "%s: gamma and accuracy must be finite", who);
-    for (int c = 0; c < episodes + 2; ++c) {
-        if (!isfinite(thr_by_count[c])) return fail(MP_ERR_ARG, "%s: the threshold of count %d is not finite", who, c + 1);
-        if (!isfinite(transition_thr_by_count[c])) return fail(MP_ERR_ARG, "%s: the transition threshold of count %d is not finite", who, c + 1);
-    }
-    for (int d = 0; d <= horizon; ++d)
-        if (!isfinite(value_init[d])) return fail(MP_ERR_ARG, "%s: the initial value of depth %d is not finite", who, d);
-    if (continuation != 0 && continuation != 1) return fail(MP_ERR_ARG, "%s: continuation %d is neither 0 (action 0) nor 1 (uniform)", who, continuation);
-    if (!action_column && n_actions_env != A)
-        return fail(MP_ERR_ARG, "%s: %d environment actions need their columns among the model's %d", who, n_actions_env, A);
-    for (int a = 0; action_column && a < n_actions_env; ++a)
-        if (action_column[a] < -1 || action_column[a] >= A) return fail(MP_ERR_ARG, "%s: column %d out of range", who, action_column[a]);
+    const GapeTables host_tab{thr_by_count, transition_thr_by_count, value_init, nullptr};
+    MP_TRY(gape_check_args(who, n_roots, episodes, horizon, 8192, max_plan_len, A, n_actions_env, gamma, accuracy, host_tab,
+                           continuation, action_column));
     MP_TRY(wave_roots(ctx, who, root_state, n_roots, model->S, mem));
     // every step of every episode may give a chance node its K placeholders and expand one decision node; the root expands once
     const long long per = ((long long)episodes + 2) * horizon;
     const long long cap = 1 + per * K + (1 + per) * A;
-    if (cap > 0x7fffffffLL) return fail(MP_ERR_ARG, "%s: %lld nodes per tree do not fit a 32-bit index", who, cap);
-    if ((size_t)cap * (sizeof(GsNode) + 2 * sizeof(double)) > kGapeStochKeepBytes)
-        return fail(MP_ERR_ARG, "%s: %lld nodes per tree take more than 1 GiB", who, cap);
+    MP_TRY(gape_check_capacity(who, cap, sizeof(GsNode)));
     GapeStochArgs a;
     MP_TRY(wave_mdp(ctx, who, model, &a));
-
-    // one table: both thresholds by count [M + 2] each, the initial values [H + 1], the columns of the environment's actions
-    const size_t M2 = (size_t)episodes + 2;
-    std::vector<double> tab(2 * M2 + horizon + 1 + n_actions_env);
-    for (size_t c = 0; c < M2; ++c) { tab[c] = thr_by_count[c]; tab[M2 + c] = transition_thr_by_count[c]; }
-    for (int d = 0; d <= horizon; ++d) tab[2 * M2 + d] = value_init[d];
-    for (int e = 0; e < n_actions_env; ++e) tab[2 * M2 + horizon + 1 + e] = action_column ? action_column[e] : e;
-    double *d_tab = nullptr;
-    MP_TRY(upload_tables(ctx, 43, tab, &d_tab));
+    GapeTables tab;
+    MP_TRY(gape_upload_tables(ctx, 43, episodes, horizon, n_actions_env, action_column, host_tab, &tab));
 
     // the launch of mp_gape_plan with a path of 2 * horizon + 1 records in LDS
     const EachForm form = each_form_global(EACH_OLOP, 2 * horizon, n_roots, ctx->prop.multiProcessorCount);
     a.n_roots = n_roots; a.A = A; a.M = episodes; a.H = horizon; a.K = K; a.cap = (int)cap; a.done_on_next = model->done_on_next;
     a.uniform = continuation; a.n_env = n_actions_env; a.max_plan_len = max_plan_len; a.gamma = gamma; a.accuracy = accuracy;
     a.grid = form.grid; a.term = model->term; a.avail = model->masked ? model->avail : nullptr;
-    a.bthr = d_tab; a.tthr = d_tab + M2; a.vinit = d_tab + 2 * M2; a.col = a.vinit + horizon + 1;
-    MP_TRY(wave_tree(ctx, kGapeStochTreeKind, n_roots, A, (long)cap, 2, kGapeStochKeepBytes, a.grid + 1, a.grid, &a.nodes, &a.val,
+    a.bthr = tab.thr; a.tthr = tab.tthr; a.vinit = tab.vinit; a.col = tab.col;
+    MP_TRY(wave_tree(ctx, kGapeStochTreeKind, n_roots, A, (long)cap, 2, kGapeKeepBytes, a.grid + 1, a.grid, &a.nodes, &a.val,
                      &a.n_nodes_out, &a.keep));
     WaveIo io(mem, rmem, n_roots, root_state, &a.root_state, rng_state, &a.rng);
-    io.add(WS_IO3, plans, &a.plans, (size_t)max_plan_len);
-    io.add(WS_IO4, plan_len, &a.plan_len);
-    io.add(WS_IO5, episodes_run, &a.episodes_run);
-    io.add(WS_IO8, env_steps, &a.env_steps);
-    io.add(WS_IO7, status, &a.status);
-    io.add(WS_IO6, child_lower, &a.child_lower, (size_t)A);
-    io.add(WS_IO9, child_upper, &a.child_upper, (size_t)A);
-    io.add(WS_IO1, child_count, &a.child_count, (size_t)A);
-    io.add(WS_IO10, best_challenger, &a.arms, (size_t)2);
+    gape_results_io(io, {plans, plan_len, episodes_run, status, best_challenger, env_steps, child_count, child_lower, child_upper},
+                    &a.out, max_plan_len, A);
     MP_TRY(wave_stage(ctx, io));
     MP_TRY(wave_launch(ctx, gape_stoch_kernel, a.grid, form.lds_bytes(), gape_stoch_form_name(model->mode, a.keep), a));
     return wave_unstage(ctx, io);

@@ -1,8 +1,9 @@
 """MDP-GapE with the reference's reach: ``max_next_states_count`` 1..32 on deterministic tables and on ``stochastic`` /
 ``sparse`` models (``mp_gape_plan_stochastic``, rl_agents_amd/csrc/gape_stoch.hip).
 
-``StochasticMDPGapE(MDPGapE)`` adds the transition thresholds by count, the plan call with K placeholders per chance node and
-the export of the tree in the reference's dict order; ``StochasticMDPGapEAgent(MDPGapEAgent)`` is the agent that plans with it.
+``StochasticMDPGapE(MDPGapE)`` plans through ``MDPGapE.plan_batch`` and overrides what differs: its refusals, the transition
+thresholds by count and the plan call with K placeholders per chance node (``plan_on``), one more status (``raise_for_result``)
+and the export that reads the tree in the reference's dict order; ``StochasticMDPGapEAgent(MDPGapEAgent)`` plans with it.
 Both are served by name from ``rl_agents_amd.agents.tree_search.mdp_gape``, which is where an agent config names them::
 
     "<class 'rl_agents_amd.agents.tree_search.mdp_gape.StochasticMDPGapEAgent'>"
@@ -14,7 +15,7 @@ from ``MDPGapE`` and is refused there as ``MDPGapE`` is.
 import numpy as np
 
 from rl_agents_amd import native
-from rl_agents_amd.agents.tree_search.mdp_gape import ChanceNode, DecisionNode, MDPGapE, MDPGapEAgent
+from rl_agents_amd.agents.tree_search.mdp_gape import MDPGapE, MDPGapEAgent, build_gape_stoch_tree  # noqa: F401
 
 PLACEHOLDERS_MESSAGE = ("No more placeholder nodes available, we observed more next states than the 'max_next_states_count' "
                         "config")                                                              # mdp_gape.py:284-285
@@ -47,12 +48,9 @@ class StochasticMDPGapE(MDPGapE):
             out[count - 1] = float(eval(bound["transition_threshold"], {"np": np}, dict(names, count=count)))
         return out
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, env_rng_states=None):
-        """``root_steps`` is accepted for the common interface: the step limit ends no episode (done = terminated).
-        ``env_rng_states`` (what BatchedEvaluation hands every planner on a stochastic env) is accepted and ignored: every
-        episode's clone is re-seeded with a draw of the planner's generator, so the environment's own is never read."""
+    def refuse_unbuilt_configs(self):
         cfg = self.config
-        episodes, horizon, count = int(cfg["episodes"]), int(cfg["horizon"]), cfg["max_next_states_count"]
+        horizon, count = (int(cfg["episodes"]), int(cfg["horizon"]))[1], cfg["max_next_states_count"]
         if count != int(count) or int(count) < 1:
             raise ValueError("max_next_states_count {}: a chance node needs a placeholder for its first next state".format(count))
         if count > self.MAX_NEXT_STATES:
@@ -61,24 +59,22 @@ class StochasticMDPGapE(MDPGapE):
         if cfg["upper_bound"]["type"] != "kullback-leibler":
             raise ValueError("MDP-GapE needs the 'kullback-leibler' bound: with '{}' the reference only logs an error and "
                              "plans on infinite bounds".format(cfg["upper_bound"]["type"]))
-        model = self.model_for(state)
-        self.about_to_plan()
-        n = len(root_states)
-        if rng_states is None:
-            rng_states = self.batch_rng_states(n)
-        try:
-            thresholds = self.thresholds()
-        except Exception:
-            # the reference evaluates the string at the first node update: one draw of the planner's generator and one model
-            # step of every plan have been made by then (mdp_gape.py:67, :82-87; the clone's draws are its own generator's)
-            for i in range(n):
-                gen = np.random.Generator(np.random.PCG64(0))
-                native.generator_set_state(gen, rng_states[i])
-                gen.integers(2 ** 30)
-                rng_states[i] = native.rng_state_from_generator(gen)
-            self.env_steps += n
-            raise
-        transition = self.transition_thresholds()        # (raised as it is, before the plan: the generator is not advanced)
+        return horizon
+
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, env_rng_states=None):
+        """``env_rng_states`` (what BatchedEvaluation hands every planner on a stochastic env) is accepted and ignored: every
+        episode's clone is re-seeded with a draw of the planner's generator, so the environment's own is never read."""
+        return super(StochasticMDPGapE, self).plan_batch(state, root_states, root_steps, rng_states)
+
+    def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None, n_env=None):
+        """Both tables by count, the initial values and the column map, and the one ``ctx.gape_plan_stochastic`` call.  The
+        transition thresholds are evaluated before the plan: what they raise is raised with the generator not advanced."""
+        if model_index is not None:
+            raise NotImplementedError("one model per episode: mp_gape_plan_stochastic takes no batch model")
+        cfg = self.config
+        episodes, horizon = int(cfg["episodes"]), self.refuse_unbuilt_configs()
+        thresholds = self.thresholds_or_first_step(len(root_states), rng_states)
+        transition = self.transition_thresholds()
         tables = dict(threshold=thresholds, transition_threshold=transition, initial_value=self._value_init)
         for name, table in tables.items():
             if not np.isfinite(table).all():
@@ -86,77 +82,23 @@ class StochasticMDPGapE(MDPGapE):
                                  "makes".format(name, int(np.flatnonzero(~np.isfinite(table))[0])))
         if not (np.isfinite(cfg["gamma"]) and np.isfinite(cfg["accuracy"])):
             raise ValueError("MDP-GapE: gamma and accuracy must be finite")
-        order = self.action_order(model)
-        n_env = int(state.action_space.n)
-        column = None
-        if order is not None or n_env != model.A:
-            column = np.full(n_env, -1, np.int32)
-            listed = np.arange(model.A) if order is None else np.asarray(order)
-            column[listed[listed < n_env]] = np.flatnonzero(listed < n_env)
-        out = self.models.ctx.gape_plan_stochastic(model, root_states, episodes, horizon, int(count), cfg["gamma"],
-                                                   cfg["accuracy"], cfg["continuation_type"] == "uniform", n_env, column,
-                                                   thresholds, transition, self._value_init, rng_states)
-        # the reference's steps and draws up to the failing step are taken before it raises
-        self.env_steps += int(out["env_steps"].sum())
+        n_env, column = self.action_columns(model, n_env)
+        return self.models.ctx.gape_plan_stochastic(model, root_states, episodes, horizon, int(cfg["max_next_states_count"]),
+                                                    cfg["gamma"], cfg["accuracy"], cfg["continuation_type"] == "uniform", n_env,
+                                                    column, thresholds, transition, self._value_init, rng_states)
+
+    def raise_for_result(self, out):
         failed = np.flatnonzero(out["status"] != native.MP_OK)
         if failed.size:
-            status = out["status"][failed[0]]
-            if status == native.ERR_GAPE_PLACEHOLDERS:
+            if out["status"][failed[0]] == native.ERR_GAPE_PLACEHOLDERS:
                 raise ValueError(PLACEHOLDERS_MESSAGE)
-            if status == native.ERR_GAPE_NO_CHALLENGER:
-                raise ValueError("max() arg is an empty sequence")                              # mdp_gape.py:247
-            if status == native.ERR_ARG:
-                raise ValueError("'a' cannot be empty unless no samples are taken")             # abstract.py:310-311 on a NaN bound
-            raise ValueError("This planner assumes that all rewards are normalized in [0, 1]")  # olop.py:133-134
-        out["rng_states"] = rng_states
-        self.relabel(out, model)
-        if order is not None:
-            arms = out["best_challenger"]
-            out["best_challenger"] = np.where(arms >= 0, order[np.maximum(arms, 0)], -1).astype(arms.dtype)
-            for k, fill in (("child_lower", 0), ("child_upper", 0), ("child_count", -1)):
-                back = np.full((n, max(n_env, int(order.max()) + 1)), fill, out[k].dtype)
-                back[:, order] = out[k]
-                out[k] = back
-        self.budget_used = int(out["episodes_run"][0]) * horizon
-        self.last, self._root, self._last_model = out, None, model
-        self.claim_device_tree()
-        return out
+            super(StochasticMDPGapE, self).raise_for_result(out)
 
-    def export_tree(self, root=0):
-        """:class:`DecisionNode` / :class:`ChanceNode` objects of the last plan's tree, a chance node's children keyed and
-        ordered as the reference's dict: ``"placeholder_i"`` for the placeholders left, then ``str(state)`` by first observation."""
-        self.require_device_tree()
-        arrays = self.models.ctx.gape_stoch_tree(root)
-        order = self.action_order(self._last_model)
-        if order is not None:
-            act = arrays["action"]
-            arrays["action"] = np.where(arrays["kind"] == 1, order[np.clip(act, 0, len(order) - 1)], act).astype(act.dtype)
-        return build_gape_stoch_tree(arrays, self)
+    def device_tree(self, root):
+        """Breadth first, a chance node's children ordered as the reference's dict: the placeholders left, then the observed
+        states by first observation."""
+        return self.models.ctx.gape_stoch_tree(root)
 
-
-def build_gape_stoch_tree(arrays, planner=None):
-    """Breadth-first arrays of mp_gape_stoch_tree_export (a parent before its children, children in dict order) -> linked
-    :class:`DecisionNode` / :class:`ChanceNode` objects."""
-    nodes = []
-    for i in range(len(arrays["parent"])):
-        par = nodes[arrays["parent"][i]] if arrays["parent"][i] >= 0 else None
-        key, args = int(arrays["action"][i]), (int(arrays["count"][i]), float(arrays["vu"][i]), int(arrays["depth"][i]), planner)
-        if arrays["kind"][i]:
-            node = ChanceNode(par, key, *args)
-            par.children[key] = node
-        else:
-            label = None if par is None else ("placeholder_{}".format(-1 - key) if key < 0 else str(key))
-            node = DecisionNode(par, label, *args)
-            node.cumulative_reward = float(arrays["cum"][i])
-            node.mu_ucb, node.mu_lcb = float(arrays["mu_ucb"][i]), float(arrays["mu_lcb"][i])
-            node.done = bool(arrays["done"][i])
-            node.observation = None if par is None or key < 0 else key
-            if par is not None:
-                par.children[label] = node
-        node.value_upper, node.value_lower = float(arrays["vu"][i]), float(arrays["vl"][i])
-        node.state = int(arrays["state"][i])
-        nodes.append(node)
-    return nodes[0]
 
 class StochasticMDPGapEAgent(MDPGapEAgent):
     """``rl_agents.agents.tree_search.mdp_gape.MDPGapEAgent`` with the reference's reach: its MDP-GapE configs with

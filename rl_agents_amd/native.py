@@ -1388,19 +1388,32 @@ class Context(object):
         ``thr_by_count`` float64 [episodes + 2] and ``value_init`` float64 [horizon + 1] from the host.  ``plans`` [n, 1]: the
         best arm's action (a column of the model), as ``best_challenger`` [n, 2]; ``child_*`` [n, A] by column.
         ``model_index`` int [n]: a batch model with one MDP per root, ``root_state`` local (mp_gape_plan_models)."""
+        return self._gape_plan(self._lib.mp_gape_plan, self._lib.mp_gape_plan_models, "gape_plan", model, root_state, episodes,
+                               horizon, gamma, accuracy, uniform, n_actions_env, action_column, thr_by_count, value_init, rng_state,
+                               model_index=model_index)
+
+    def _gape_plan(self, fn, fn_models, name, model, root_state, episodes, horizon, gamma, accuracy, uniform, n_actions_env,
+                   action_column, thr_by_count, value_init, rng_state, transition_thr_by_count=None, max_next_states=None,
+                   model_index=None):
+        """gape_plan and, with ``transition_thr_by_count`` and ``max_next_states``, gape_plan_stochastic."""
         rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
         _check_rng(rng_state, rs.shape[0])
+        stochastic = max_next_states is not None
         thr = np.ascontiguousarray(thr_by_count, dtype=np.float64).reshape(-1)
+        tthr = np.ascontiguousarray(transition_thr_by_count, dtype=np.float64).reshape(-1) if stochastic else None
         vin = np.ascontiguousarray(value_init, dtype=np.float64).reshape(-1)
-        if vin.size != int(horizon) + 1 or thr.size != int(episodes) + 2:
-            raise ValueError("gape_plan: thr_by_count [episodes + 2] and value_init [horizon + 1] expected")
+        if vin.size != int(horizon) + 1 or any(t.size != int(episodes) + 2 for t in ((thr, tthr) if stochastic else (thr,))):
+            raise ValueError("{}: thr_by_count {}[episodes + 2] and value_init [horizon + 1] expected".format(
+                name, "and transition_thr_by_count " if stochastic else ""))
         col = None if action_column is None else np.ascontiguousarray(action_column, dtype=np.int32).reshape(-1)
         if col is not None and col.size != int(n_actions_env):
-            raise ValueError("gape_plan: action_column [n_actions_env] expected")
-        run = (int(episodes), int(horizon), float(gamma), float(accuracy), 1 if uniform else 0, int(n_actions_env), _ptr(col),
-               _ptr(thr), _ptr(vin))
-        return self._each_plan(self._lib.mp_gape_plan, self._lib.mp_gape_plan_models, "gape", model, rs, model_index, run, rng_state,
-                               1, A=model.A, P=2)
+            raise ValueError("{}: action_column [n_actions_env] expected".format(name))
+        shared = (float(gamma), float(accuracy), 1 if uniform else 0, int(n_actions_env), _ptr(col), _ptr(thr))
+        if stochastic:
+            run = (int(episodes), int(horizon), int(max_next_states)) + shared + (_ptr(tthr), _ptr(vin))
+        else:
+            run = (int(episodes), int(horizon)) + shared + (_ptr(vin),)
+        return self._each_plan(fn, fn_models, "gape", model, rs, model_index, run, rng_state, 1, A=model.A, P=2)
 
     GAPE_TREE = (("kind", np.uint8, ()), ("parent", np.int32, ()), ("action", np.int32, ()), ("depth", np.int32, ()),
                  ("count", np.int64, ()), ("cum", np.float64, ()), ("mu_ucb", np.float64, ()), ("mu_lcb", np.float64, ()),
@@ -1409,13 +1422,16 @@ class Context(object):
     def gape_tree(self, root, cap=None):
         """Creation-order arrays of root ``root``'s tree after the last gape_plan, decision (``kind`` 0) and chance (1) nodes
         (mp_gape_tree_export).  ``cap`` None: the tree's own node count is asked first."""
+        return self._gape_tree(self._lib.mp_gape_tree_export, root, cap)
+
+    def _gape_tree(self, fn, root, cap):
         if cap is None:
             n = c_i32()
-            rc = self._lib.mp_gape_tree_export(self._h, int(root), 0, C.byref(n), *([None] * len(self.GAPE_TREE)))
+            rc = fn(self._h, int(root), 0, C.byref(n), *([None] * len(self.GAPE_TREE)))
             if n.value < 1:                                     # (no tree to size: the refusal itself)
                 _check(rc)
             cap = n.value
-        return _export_tree(self._lib.mp_gape_tree_export, (self._h, int(root)), cap, self.GAPE_TREE)
+        return _export_tree(fn, (self._h, int(root)), cap, self.GAPE_TREE)
 
     def gape_plan_stochastic(self, model, root_state, episodes, horizon, max_next_states, gamma, accuracy, uniform, n_actions_env,
                              action_column, thr_by_count, transition_thr_by_count, value_init, rng_state):
@@ -1424,32 +1440,15 @@ class Context(object):
         and ``transition_thr_by_count`` float64 [episodes + 2]: ``transition_threshold()`` by a chance node's count.
         ``status`` ERR_GAPE_PLACEHOLDERS where more next states were observed than placeholders.  :meth:`gape_stoch_tree`
         serves the trees afterwards."""
-        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
-        _check_rng(rng_state, rs.shape[0])
-        thr = np.ascontiguousarray(thr_by_count, dtype=np.float64).reshape(-1)
-        tthr = np.ascontiguousarray(transition_thr_by_count, dtype=np.float64).reshape(-1)
-        vin = np.ascontiguousarray(value_init, dtype=np.float64).reshape(-1)
-        if vin.size != int(horizon) + 1 or thr.size != int(episodes) + 2 or tthr.size != int(episodes) + 2:
-            raise ValueError("gape_plan_stochastic: thr_by_count and transition_thr_by_count [episodes + 2] and value_init "
-                             "[horizon + 1] expected")
-        col = None if action_column is None else np.ascontiguousarray(action_column, dtype=np.int32).reshape(-1)
-        if col is not None and col.size != int(n_actions_env):
-            raise ValueError("gape_plan_stochastic: action_column [n_actions_env] expected")
-        run = (int(episodes), int(horizon), int(max_next_states), float(gamma), float(accuracy), 1 if uniform else 0,
-               int(n_actions_env), _ptr(col), _ptr(thr), _ptr(tthr), _ptr(vin))
-        return self._each_plan(self._lib.mp_gape_plan_stochastic, None, "gape", model, rs, None, run, rng_state, 1, A=model.A, P=2)
+        return self._gape_plan(self._lib.mp_gape_plan_stochastic, None, "gape_plan_stochastic", model, root_state, episodes, horizon,
+                               gamma, accuracy, uniform, n_actions_env, action_column, thr_by_count, value_init, rng_state,
+                               transition_thr_by_count=transition_thr_by_count, max_next_states=max_next_states)
 
     def gape_stoch_tree(self, root, cap=None):
         """BREADTH-FIRST arrays of root ``root``'s tree after the last gape_plan_stochastic, children in the reference's dict
         order, with the fields of :meth:`gape_tree` (mp_gape_stoch_tree_export): the ``action`` of a decision node is its
         observed state, or ``-1 - i`` for ``placeholder_i``.  ``cap`` None: the tree's own node count is asked first."""
-        if cap is None:
-            n = c_i32()
-            rc = self._lib.mp_gape_stoch_tree_export(self._h, int(root), 0, C.byref(n), *([None] * len(self.GAPE_TREE)))
-            if n.value < 1:                                     # (no tree to size: the refusal itself)
-                _check(rc)
-            cap = n.value
-        return _export_tree(self._lib.mp_gape_stoch_tree_export, (self._h, int(root)), cap, self.GAPE_TREE)
+        return self._gape_tree(self._lib.mp_gape_stoch_tree_export, root, cap)
 
     def selftest_gape_transition(self, f, q, c):
         """What the DEVICE computes for ``max_expectation_under_constraint`` (mp_selftest_gape_transition): ``f``, ``q`` float64

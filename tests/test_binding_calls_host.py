@@ -241,6 +241,7 @@ PRIOR = [0.2, 0.3, 0.5]
 THR = [0.5, 1.0, 1.5, 2.0, 2.5]
 VIN = [4.0, 3.0, 2.0, 1.0, 0.0]
 GPOW = [1.0, 0.5, 0.25, 0.125, 0.0625]
+GAPE_THR = [0.5, 1.0, 1.5, 2.0, 2.5, 3.0, 3.5]                # (5 episodes + 2)
 
 # ---- the plan methods: name -> call(h, n, **changes) ---------------------------------------------------------------
 
@@ -282,6 +283,18 @@ def _brue(h, n, model=None, **kw):
     return h.ctx.brue_plan(model or h.model(), kw.pop("root_state", _roots(n)), 6, HORIZON, 0.9, kw.pop("gpow", GPOW), **kw)
 
 
+def _gape(h, n, model=None, method="gape_plan", stochastic=False, **kw):
+    kw.setdefault("rng_state", h.rng(n))
+    tables = (kw.pop("thr_by_count", GAPE_THR),) + ((kw.pop("transition_thr_by_count", GAPE_THR[::-1]),) if stochastic else ())
+    return getattr(h.ctx, method)(model or h.model(), kw.pop("root_state", _roots(n)), 5, HORIZON, *((2,) if stochastic else ()),
+                                  0.9, 0.5, kw.pop("uniform", True), kw.pop("n_actions_env", A), kw.pop("action_column", None),
+                                  *tables, kw.pop("value_init", VIN), **kw)
+
+
+def _gape_stoch(h, n, **kw):
+    return _gape(h, n, model=h.model(native.MODE_SPARSE, b=2), method="gape_plan_stochastic", stochastic=True, **kw)
+
+
 def _ss(h, n, model=None, **kw):
     kw.setdefault("rng_state", h.rng(n))
     return h.ctx.ss_plan(model or h.model(), kw.pop("root_state", _roots(n)), HORIZON, 2, 0.9, **kw)
@@ -298,8 +311,8 @@ def _gbopd(h, n, **kw):
 
 
 PLANS = dict(uct=_uct, uct_stoch=_uct_stoch, opd=_opd, ropd=_ropd, olop=_olop, olop_stoch=_olop_stoch, brue=_brue, ss=_ss,
-             saopd=_saopd, gbopd=_gbopd)
-WITH_MODELS = ("uct", "opd", "olop", "brue", "ss")
+             gape=_gape, gape_stoch=_gape_stoch, saopd=_saopd, gbopd=_gbopd)
+WITH_MODELS = ("uct", "opd", "olop", "brue", "ss", "gape")
 
 
 def _twice(h, plan, n, **kw):
@@ -516,6 +529,19 @@ def _cases():
     c["olop_plan model_index no kl"] = lambda h: _olop(h, 2, model=h.batch_model(), model_index=[3, 1], kl=False, thresholds=[])
     c["brue_plan gpow array"] = lambda h: _brue(h, 2, gpow=h.arr(GPOW, np.float64))
     c["brue_plan short gpow"] = lambda h: _brue(h, 2, gpow=GPOW[:2])
+    for name in ("gape", "gape_stoch"):
+        plan = PLANS[name]
+        c[name + "_plan action_column"] = lambda h, plan=plan: plan(h, 2, n_actions_env=4, action_column=[2, -1, 0, 1], uniform=False)
+        c[name + "_plan arrays in"] = lambda h, plan=plan: plan(h, 2, action_column=h.arr([2, 0, 1], np.int32),
+                                                                thr_by_count=h.arr(GAPE_THR, np.float64),
+                                                                value_init=h.arr(VIN, np.float64))
+        c[name + "_plan short thr_by_count"] = lambda h, plan=plan: plan(h, 2, thr_by_count=GAPE_THR[:5])
+        c[name + "_plan short value_init"] = lambda h, plan=plan: plan(h, 2, value_init=VIN[:2])
+        c[name + "_plan short action_column"] = lambda h, plan=plan: plan(h, 2, n_actions_env=4, action_column=[2, 0, 1])
+    c["gape_plan model_index action_column"] = lambda h: _gape(h, 2, model=h.batch_model(), model_index=[3, 1],
+                                                               action_column=[2, 0, 1])
+    c["gape_stoch_plan short transition_thr_by_count"] = lambda h: _gape_stoch(h, 2, transition_thr_by_count=GAPE_THR[:6])
+    c["gape_stoch_plan transition array"] = lambda h: _gape_stoch(h, 2, transition_thr_by_count=h.arr(GAPE_THR, np.float64))
     c["opd_plan max_plan_len"] = lambda h: _opd(h, 2, max_plan_len=3)
     c["saopd_plan options"] = lambda h: _saopd(h, 2, accuracy=0.5, backup_aggregated_nodes=False, max_plan_len=3)
     c["saopd_plan wrong roots"] = lambda h: _saopd(h, 2, root_state=[1, 2, 3])
@@ -545,6 +571,12 @@ def _cases():
     c["ss_tree cap"] = lambda h: h.ctx.ss_tree(1, cap=9)
     c["ss_tree no tree"] = lambda h: _hooked(h, "mp_ss_tree_export", lambda n, *a: setattr(n, "value", 0),
                                              lambda: _failing(h, "mp_ss_tree_export", native.MP_ERR_ARG, lambda: h.ctx.ss_tree(1)))
+    for name in ("gape", "gape_stoch"):
+        c[name + "_tree"] = lambda h, name=name: getattr(h.ctx, name + "_tree")(1)
+        c[name + "_tree cap"] = lambda h, name=name: getattr(h.ctx, name + "_tree")(1, cap=9)
+        c[name + "_tree no tree"] = lambda h, name=name: _hooked(
+            h, "mp_{}_tree_export".format(name), lambda n, *a: setattr(n, "value", 0),
+            lambda: _failing(h, "mp_{}_tree_export".format(name), native.MP_ERR_ARG, lambda: getattr(h.ctx, name + "_tree")(1)))
     c["saopd info"] = lambda h: h.saopd(2).info()
     c["saopd export"] = lambda h: h.saopd(2).export(1)
     c["saopd export whole arena"] = lambda h: h.saopd(2).export(0, current_tree_only=False)

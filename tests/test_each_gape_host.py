@@ -188,6 +188,30 @@ def test_planners_have_their_own_plan_call():
     assert calls[0]["thr"] == UCT["episodes"] + 2 and calls[0]["vin"] == UCT["horizon"] + 1
     with pytest.raises(ValueError, match="empty sequence"):
         planner.raise_for_result(out)
+    # the stochastic planner's plan call is its own, and it is the other kernel's
+    from rl_agents_amd.gape_stochastic import PLACEHOLDERS_MESSAGE, StochasticMDPGapE
+    assert "plan_on" in vars(StochasticMDPGapE) and StochasticMDPGapE.plan_on is not MDPGapE.plan_on
+    assert "raise_for_result" in vars(StochasticMDPGapE) and "plan_batch" in vars(StochasticMDPGapE)
+
+    class GapeStochCtx(object):
+        def gape_plan_stochastic(self, model, roots, episodes, horizon, count, gamma, accuracy, uniform, n_env, column, thr, tthr,
+                                 vin, rng):
+            calls.append(dict(count=count, n_env=n_env, column=column, thr=len(thr), tthr=len(tthr), vin=len(vin)))
+            return dict(status=np.asarray([0, native.ERR_GAPE_PLACEHOLDERS, native.ERR_GAPE_NO_CHALLENGER]))
+
+    planner = StochasticMDPGapE(plain_env(), dict(UCT, max_next_states_count=2))
+    planner.models = types.SimpleNamespace(ctx=GapeStochCtx())          # (no gape_plan: the inherited call would fail here)
+    out = planner.plan_on(model, [0, 1, 2], [0, 0, 0], np.zeros((3, 6), np.uint64))
+    assert calls[1] == dict(count=2, n_env=3, column=calls[1]["column"], thr=UCT["episodes"] + 2, tthr=UCT["episodes"] + 2,
+                            vin=UCT["horizon"] + 1) and calls[1]["column"].tolist() == [1, 2, 0]
+    with pytest.raises(ValueError) as raised:
+        planner.raise_for_result(out)
+    assert str(raised.value) == PLACEHOLDERS_MESSAGE
+    with pytest.raises(ValueError, match="empty sequence"):
+        planner.raise_for_result(dict(status=out["status"][::-1]))
+    with pytest.raises(NotImplementedError, match="one model per episode"):
+        planner.plan_on(model, [0], [0], np.zeros((1, 6), np.uint64), model_index=[0])
+    assert len(calls) == 2
 
 
 # ---- the fixture of the unmodified reference against the restatement -------------------------------------------------------------

@@ -30,9 +30,10 @@ from rl_agents_amd.agents.robust.robust import DiscreteRobustPlannerAgent  # noq
 from rl_agents_amd.agents.tree_search.brue import BRUEAgent  # noqa: E402
 from rl_agents_amd.agents.tree_search.deterministic import DeterministicPlannerAgent  # noqa: E402
 from rl_agents_amd.agents.tree_search.mcts import MCTSAgent  # noqa: E402
+from rl_agents_amd.agents.tree_search.mdp_gape import MDPGapEAgent, StochasticMDPGapEAgent  # noqa: E402
 from rl_agents_amd.agents.tree_search.olop import OLOPAgent  # noqa: E402
 from rl_agents_amd.agents.tree_search.state_aware import StateAwarePlannerAgent  # noqa: E402
-from rl_agents_amd.envs.finite_mdp import FiniteMDPEnv, MaskedFiniteMDPEnv  # noqa: E402
+from rl_agents_amd.envs.finite_mdp import FiniteMDPEnv, MaskedFiniteMDPEnv, OrderedMaskedFiniteMDPEnv  # noqa: E402
 from rl_agents_amd.trainer.per_episode_evaluation import PerEpisodeEvaluation  # noqa: E402
 from tests import helpers  # noqa: E402
 
@@ -41,9 +42,9 @@ A, S, WIDE = 3, 10, 9
 RNG_STEP = 3
 MODES = {"deterministic": native.MODE_DETERMINISTIC, "stochastic": native.MODE_STOCHASTIC, "sparse": native.MODE_SPARSE}
 PLANS = {"uct_plan": "uct", "uct_plan_stochastic": "uct", "opd_plan": "opd", "ropd_plan": "opd", "olop_plan": "olop",
-         "olop_plan_stochastic": "olop", "brue_plan": "brue"}
+         "olop_plan_stochastic": "olop", "brue_plan": "brue", "gape_plan": "gape", "gape_plan_stochastic": "gape"}
 OTHERS = ("uct_reset_tree", "uct_step_tree", "uct_step_tree_select", "load_policy", "load_joint", "load_table_batch",
-          "load_joint_batch", "vi_solve_batch", "synchronize")
+          "load_joint_batch", "vi_solve_batch", "synchronize", "gape_tree", "gape_stoch_tree")
 
 
 def _content(a):
@@ -137,14 +138,19 @@ class Ctx(object):
         length = kw.get("max_plan_len")
         if length is None:
             length = max(int(kw["horizon"]), 1) * (2 if kw.get("closed_loop") else 1) if "horizon" in kw else 1
+        if family == "gape":
+            length = 1                                                  # (an MDP-GapE plan is one action)
         out = {}
         for key, dtype, tail, _ in native.RESULTS[family]:
-            out[key] = np.zeros((n,) + tuple({"L": int(length), "A": model.A}[d] for d in tail), dtype)
+            out[key] = np.zeros((n,) + tuple({"L": int(length), "A": model.A, "P": 2}[d] for d in tail), dtype)
         if "plan_len" in out:
             out["plan_len"][:] = 1
         out["env_steps"][:] = np.arange(n) + 1
         if "root_child_count" in out:
             out["root_child_count"][:] = np.arange(model.A) + 1         # (a relabelled result shows the permutation)
+        if family == "gape":
+            out["episodes_run"][:], out["best_challenger"][:], out["child_count"][:] = 3, (1, 2), np.arange(model.A) + 1
+            out["child_lower"][:], out["child_upper"][:] = np.arange(model.A) / 10.0, np.arange(model.A) / 10.0 + 0.5
         fail = self.fail if self.fail and self.fail["call"] == self.plan_calls else None
         self.plan_calls += 1
         if fail and "status" in fail:
@@ -154,6 +160,18 @@ class Ctx(object):
         assert isinstance(rng_state, np.ndarray) and rng_state.dtype == np.uint64 and rng_state.size == 6 * n
         rng_state += np.uint64(RNG_STEP)
         return out
+
+    def _gape_tree(self, root, cap, keys=(-1, 0, 2, 5, 4), parent=(-1, 0, 0, 1, 2)):
+        """A root with the arms 0 and 2 and a decision node under each."""
+        n = len(keys)
+        return dict(kind=np.asarray([0, 1, 1, 0, 0], np.uint8), parent=np.asarray(parent, np.int32), action=np.asarray(keys, np.int32),
+                    depth=np.asarray([0, 0, 0, 1, 1], np.int32), count=np.arange(n, dtype=np.int64)[::-1] + 1,
+                    cum=np.arange(n) / 4.0, mu_ucb=np.arange(n) / 8.0 + 0.5, mu_lcb=np.arange(n) / 8.0, vu=np.arange(n) + 0.5,
+                    vl=np.arange(n) + 0.25, done=np.asarray([0, 0, 0, 0, 1], np.uint8), state=np.asarray([1, 1, 1, 5, 4], np.int32))
+
+    def _gape_stoch_tree(self, root, cap):
+        """A root with the arms 0 and 2; under arm 0 the placeholder left and the one observed state."""
+        return self._gape_tree(root, cap, keys=(-1, 0, 2, -2, 4), parent=(-1, 0, 0, 1, 1))
 
     def _load_policy(self, model, prior, rollout, listed, rollout_slots):
         return Policy(self)
@@ -224,10 +242,15 @@ def masked_env(n_actions=A, **kw):
     return MaskedFiniteMDPEnv(dict(table(n_actions, **kw), available=mask(n_actions)))
 
 
-def stochastic_env():
-    env = FiniteMDPEnv({k: v for k, v in helpers.stochastic_model("stochastic", S, A, False).items() if v is not None})
+def stochastic_env(kind="stochastic", ordered=False):
+    config = {k: v for k, v in helpers.stochastic_model(kind, S, A, False).items() if v is not None}
+    env = OrderedMaskedFiniteMDPEnv(dict(config, available=mask(), listing_order=[2, 0, 1])) if ordered else FiniteMDPEnv(config)
     env.seed(3)
     return env
+
+
+def ordered_env(**kw):
+    return OrderedMaskedFiniteMDPEnv(dict(table(**kw), available=mask(), listing_order=[2, 0, 1]))
 
 
 def rng_records(n):
@@ -244,6 +267,13 @@ OLOP_KL = dict(budget=8, episodes=4, horizon=2, gamma=0.8, upper_bound=dict(type
                                                                             threshold="2*np.log(time)"))
 OLOP_HOEFFDING = dict(budget=8, episodes=4, horizon=2, gamma=0.8)
 BRUE_CFG = dict(budget=6, horizon=2, gamma=0.8)
+GAPE_CFG = dict(budget=8, episodes=4, horizon=2, gamma=0.8, accuracy=0.1)
+GAPE_STOCH_CFG = dict(GAPE_CFG, max_next_states_count=2)
+
+
+def gape_bound(**strings):
+    return dict(upper_bound=dict(dict(type="kullback-leibler", time="global", threshold="2*np.log(time) + count",
+                                      transition_threshold="0.1*np.log(time) + count"), **strings))
 
 
 def with_stand_in(agent, ctx):
@@ -299,7 +329,7 @@ def construction_case(make_agent, make_env):
     return case
 
 
-def per_episode_case(make_agent, make_envs, fail=None):
+def per_episode_case(make_agent, make_envs, fail=None, **evaluation_kw):
     """Two lock-steps of three environments through PerEpisodeEvaluation.run(): every ``_plan`` and what it returns."""
     def case():
         ctx = Ctx(fail)
@@ -307,7 +337,7 @@ def per_episode_case(make_agent, make_envs, fail=None):
         agent = make_agent(envs[0])
         if hasattr(agent, "planner"):
             with_stand_in(agent, ctx)
-        ev = PerEpisodeEvaluation(envs, agent, sim_seed=5, max_steps=2)
+        ev = PerEpisodeEvaluation(envs, agent, sim_seed=5, max_steps=2, **evaluation_kw)
         assert ev.ctx is ctx
         steps, inner = [], ev._plan
 
@@ -366,6 +396,30 @@ def step_subtree(ctx, planner, k):
 def step_subtree_then_lose(ctx, planner, k):
     planner.step_by_subtree(1)
     ctx._tree_owner = None
+
+
+def describe_tree(root):
+    """Breadth first: every node's class, its key among its parent's children and what build_gape_tree gave it."""
+    out, queue = [], [(None, root)]
+    while queue:
+        key, node = queue.pop(0)
+        out.append([type(node).__name__, describe(key)] + [describe(getattr(node, k, "-")) for k in (
+            "count", "value_upper", "value_lower", "depth", "state", "observation", "done", "cumulative_reward", "mu_ucb", "mu_lcb")]
+            + [node.parent is None or node.parent.children[key] is node, node.planner is not None])
+        queue.extend(node.children.items())
+    return out
+
+
+def export_tree(ctx, planner, k):
+    ctx.calls.append(["export_tree", describe_tree(planner.export_tree(0))])
+
+
+def nan_initial_value(make_agent):
+    def make(env):
+        agent = make_agent(env)
+        agent.planner._value_init[1] = np.nan
+        return agent
+    return make
 
 
 def policy_source_agent(env):
@@ -474,6 +528,89 @@ CASES.update({
     "each_olop_other_status": per_episode_case(agent_of(OLOPAgent, OLOP_KL), three(plain_env), dict(call=0, root=1, status=OTHER)),
     "each_brue_negative_plan": per_episode_case(agent_of(BRUEAgent, BRUE_CFG), three(plain_env), dict(call=1, root=1, negative=True)),
 })
+
+
+def gape_cases():
+    """MDPGapEAgent on deterministic tables and StochasticMDPGapEAgent on a dense and a sparse model: what reaches the binding,
+    every status either maps to an exception, every refusal that comes after the generator records were made."""
+    cases = {}
+    no_arm, holders = native.ERR_GAPE_NO_CHALLENGER, native.ERR_GAPE_PLACEHOLDERS
+    for tag, cls, cfg, envs in (
+            ("gape", MDPGapEAgent, GAPE_CFG, dict(plain=plain_env, masked=masked_env, ordered=ordered_env)),
+            ("gape_stoch", StochasticMDPGapEAgent, GAPE_STOCH_CFG, dict(
+                plain=stochastic_env, sparse=functools.partial(stochastic_env, "sparse"), table=plain_env,
+                ordered=functools.partial(stochastic_env, ordered=True),
+                sparse_ordered=functools.partial(stochastic_env, "sparse", ordered=True)))):
+        agent = agent_of(cls, cfg)
+        first = envs["plain"]
+
+        def with_config(_cls=cls, _cfg=cfg, **kw):
+            return agent_of(_cls, dict(_cfg, **kw))
+        for n in (1, 3):
+            cases["{}_{}".format(tag, n)] = batch_case(agent, first, n)
+        for name, make_env in envs.items():
+            if name != "plain":
+                cases["{}_{}".format(tag, name)] = batch_case(agent, make_env, 3)
+        for name, status in (("no_challenger", no_arm), ("empty_choice", OTHER), ("reward_range", RANGE), ("placeholders", holders)):
+            if tag == "gape_stoch" or status != holders:
+                cases["{}_{}".format(tag, name)] = batch_case(agent, first, 3, dict(call=1, root=1, status=status), calls=2)
+        cases[tag + "_status_ordered"] = batch_case(agent, envs["ordered"], 3, dict(call=0, root=2, status=no_arm))
+        cases[tag + "_fixed_continuation"] = batch_case(with_config(continuation_type="zero"), first, 3)
+        cases[tag + "_threshold_raises"] = batch_case(with_config(**gape_bound(threshold="1/(count - 2)")), first, 3, calls=2)
+        cases[tag + "_threshold_not_finite"] = batch_case(with_config(**gape_bound(threshold="np.inf if count == 3 else 1.0")), first, 3)
+        cases[tag + "_initial_value_not_finite"] = batch_case(nan_initial_value(agent), first, 3)
+        cases[tag + "_accuracy_not_finite"] = batch_case(with_config(accuracy=float("nan")), first, 3)
+        cases[tag + "_other_bound"] = batch_case(with_config(**gape_bound(type="hoeffding")), first, 3)
+        cases[tag + "_subtree"] = batch_case(with_config(step_strategy="subtree"), first, 3)
+        cases[tag + "_export_tree"] = batch_case(agent, first, 3, calls=2, between=export_tree)
+        cases[tag + "_export_tree_ordered"] = batch_case(agent, envs["ordered"], 3, calls=2, between=export_tree)
+        cases[tag + "_own_records"] = batch_case_without_records(agent, first, 3)
+    cases.update({
+        "gape_two_next_states": batch_case(agent_of(MDPGapEAgent, GAPE_STOCH_CFG), plain_env, 3),
+        "gape_stochastic_env": batch_case(agent_of(MDPGapEAgent, GAPE_CFG), stochastic_env, 3),
+        "gape_stoch_transition_raises": batch_case(agent_of(StochasticMDPGapEAgent, dict(
+            GAPE_STOCH_CFG, **gape_bound(transition_threshold="1/(count - 2)"))), stochastic_env, 3, calls=2),
+        "gape_stoch_both_raise": batch_case(agent_of(StochasticMDPGapEAgent, dict(
+            GAPE_STOCH_CFG, **gape_bound(threshold="1/(count - 2)", transition_threshold="1/(count - 2)"))), stochastic_env, 3),
+        "gape_stoch_transition_not_finite": batch_case(agent_of(StochasticMDPGapEAgent, dict(
+            GAPE_STOCH_CFG, **gape_bound(transition_threshold="-np.inf if count == 2 else 1.0"))), stochastic_env, 3),
+        "gape_stoch_env_rng": batch_case(agent_of(StochasticMDPGapEAgent, GAPE_STOCH_CFG), stochastic_env, 3,
+                                         env_rng_states=rng_records(3) + np.uint64(9)),
+        "gape_stoch_33_next_states": batch_case(agent_of(StochasticMDPGapEAgent, dict(GAPE_CFG, max_next_states_count=33)),
+                                                stochastic_env, 3),
+        "gape_stoch_no_next_state": batch_case(agent_of(StochasticMDPGapEAgent, dict(GAPE_CFG, max_next_states_count=0)),
+                                               stochastic_env, 3),
+        "gape_stoch_half_a_next_state": batch_case(agent_of(StochasticMDPGapEAgent, dict(GAPE_CFG, max_next_states_count=1.5)),
+                                                   stochastic_env, 3),
+        "gape_stoch_32_next_states": batch_case(agent_of(StochasticMDPGapEAgent, dict(GAPE_CFG, max_next_states_count=32.0)),
+                                                stochastic_env, 1),
+        "each_gape": per_episode_case(agent_of(MDPGapEAgent, GAPE_CFG), three(plain_env), kind="gape"),
+        "each_gape_masked": per_episode_case(agent_of(MDPGapEAgent, GAPE_CFG), three(masked_env), kind="gape"),
+        "each_gape_ordered": per_episode_case(agent_of(MDPGapEAgent, GAPE_CFG), three(ordered_env), kind="gape"),
+        "each_gape_unasked": per_episode_case(agent_of(MDPGapEAgent, GAPE_CFG), three(plain_env)),
+        "each_gape_no_challenger": per_episode_case(agent_of(MDPGapEAgent, GAPE_CFG), three(plain_env),
+                                                    dict(call=1, root=1, status=no_arm), kind="gape"),
+        "each_gape_reward_range": per_episode_case(agent_of(MDPGapEAgent, GAPE_CFG), three(plain_env),
+                                                   dict(call=1, root=2, status=RANGE), kind="gape"),
+        "each_gape_threshold_raises": per_episode_case(agent_of(MDPGapEAgent, dict(GAPE_CFG, **gape_bound(threshold="1/(count - 2)"))),
+                                                       three(plain_env), kind="gape"),
+        "each_gape_stoch_refused": per_episode_case(agent_of(StochasticMDPGapEAgent, GAPE_STOCH_CFG), three(plain_env), kind="gape"),
+    })
+    return cases
+
+
+def batch_case_without_records(make_agent, make_env, n):
+    """One plan_batch that is handed no generator records: the planner makes its own (and they come back in the result)."""
+    def case():
+        ctx = Ctx()
+        env = make_env()
+        planner = with_stand_in(make_agent(env), ctx)
+        rng = np.zeros(0, np.uint64)
+        return dict(plans=[plan_record(ctx, planner, lambda: planner.plan_batch(env, list(range(1, n + 1))), rng)]), ctx
+    return case
+
+
+CASES.update(gape_cases())
 
 
 def run_case(name, mp):
