@@ -1207,6 +1207,11 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
  *   UCT           records of that many successors, 1 compact 16-byte records), bits of a path entry, the unrolled |A|
  * The host picks by model, batch size and the MP_* test hooks; reports and tests name what ran.  Results do not depend on the form. */
 const char *mp_last_kernel_variant(mp_ctx *ctx);
+/* 1 if the last mp_uct_plan / mp_uct_plan_models / mp_uct_plan_policy call on ctx launched its form with the rollout's action
+ * table in LDS ("uct_ldsr", |A| <= 6, a state-independent policy, 4 096 bytes of LDS to spare, MP_UCT_ACTION_TABLE not 0), 0 if
+ * it launched the form with the exact compares in every rollout step, or if no such call was made.  The form's name is the same
+ * either way, and so are the results: tests that force an arm assert it with this. */
+int mp_uct_last_action_table(mp_ctx *ctx);
 /* Every name mp_last_kernel_variant can return, one per line, built by the functions that name the launches (host only, no
  * device): a test table that is to cover every form is compared with this list.  (Sparse Sampling's two names are listed by
  * its own mp_ss_form_names, single-model value iteration's by mp_vi_form_names, the one-MDP-per-root forms of OLOP and BRUE by

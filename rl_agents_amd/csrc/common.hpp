@@ -88,6 +88,9 @@ struct mp_ctx {
     bool timed = false;
     int n_launches = 0;
     char last_variant[mp::kFormNameBytes] = ""; // which kernel form the last plan / batched VI call launched (mp_last_kernel_variant)
+    int uct_action_table = 0; // whether the last mp_uct_plan* call launched its form with the action table (mp_uct_last_action_table)
+    // UCT's action table (uct_action_table.hpp) as last built, and the thresholds it was built from
+    struct UctActionTable { int nth = 0, thr_valid = 0; uint64_t thr[8] = {}; std::vector<uint8_t> bytes; } uct_act;
     hipDeviceProp_t prop;
     mp::DevBuf ws[mp::WS_COUNT];
     mp::TreeMeta tree;

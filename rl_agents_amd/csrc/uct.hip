@@ -53,6 +53,7 @@
 #include "common.hpp"
 #include "libm_sincos.hpp"
 #include "pcg64.hpp"
+#include "uct_action_table.hpp"
 #include "uct_balance.hpp"
 #include "uct_host.hpp"
 #include "uct_virgin.hpp"
@@ -122,6 +123,8 @@ struct UctArgs {
                      // 0 (MP_UCT_TREE_STORES=lane, an A/B knob): every store per lane, first_child of an expanded node on its own
     int balance; // host side only: 1 launches the BAL instantiation of the one-lane LDS-resident form (WAVE BALANCE in uct_kernel) with
                  // 64 more bytes of LDS; 0: MP_UCT_BALANCE=0, any other form, or a model that leaves no room for them
+    int action_table; // host side only: 1 launches the ATAB instantiation of that form (ACTION TABLE in uct_kernel) with kUctActBytes
+                      // more of LDS; 0: MP_UCT_ACTION_TABLE=0, any other form or policy, or a model that leaves no room for them
     int Sb;    // batch models: states per MDP (root r plans on MDP root_state[r] / Sb); = S for any other model
 #ifdef MP_WAVE_STAMPS
     unsigned long long *wave_stamps; // diagnostic build: [waves of the launch][kWaveStampWords], or nullptr (WAVE STAMPS in uct_kernel)
@@ -143,6 +146,7 @@ struct UctArgs {
     const double *tab; // gpow[H+1] | thr[A] (uint64 bits) | tp[A] | rcp[TE+1] | tpdiv[A][TE+2]
     uint64_t thr_arg[8]; // the same thresholds by value (|A| <= 8), SHIFTED UP by 11 bits (compared with the raw 64-bit draw; 2^53 -> ~0): kernel arguments live in SGPRs
     int thr_valid;       // how many of the first |A| - 1 thresholds are below 2^53 (the others can never be reached)
+    const uint8_t *act_tab; // action_table: the kUctActBytes entries of uct_action_table_fill for thr_arg / thr_valid, else nullptr
     // per-state policies (mp_policy): nullptr / 0 for the state-independent ones
     const double *pol_prior; // [S][pol_stride]
     const uint64_t *pol_thr; // [S][pol_stride]
@@ -284,7 +288,9 @@ constexpr bool uct_pcg_words_form(int AT, int ENV, bool SP, bool MK, int IL, boo
 // BAL (the one-lane LDS-resident form): WAVE BALANCE below -- a template argument, not a kernel argument, because the form has no
 // scalar register left for a flag that lives over the whole plan (a run-time flag spilled in five of its seven instantiations).
 // VM (the forms of uct_mask_form, fresh trees): VISITED MASK below -- a template argument for the same reason.
-template <int AT, int ENV, bool SP = false, bool MK = false, int IL = 0, bool QD = false, bool BAL = false, bool VM = false>
+// ATAB (the forms of uct_action_table_form): ACTION TABLE below -- a template argument for the same reason.
+template <int AT, int ENV, bool SP = false, bool MK = false, int IL = 0, bool QD = false, bool BAL = false, bool VM = false,
+          bool ATAB = false>
 // Per-state-policy kernels with |A| <= 5 are held to the registers of 4 waves per SIMD (they would take 134-140 VGPRs = 3
 // waves; TA 52 %, VALU 45 %, L1 28 % busy: latency-bound -- 2.14 -> 1.91 ms at 262 144 roots with the fourth wave).
 __global__ __launch_bounds__(ENV == ENV_TABLE_LDSR ? 1024 : (ENV == ENV_CARTPOLE ? 256 : 64),
@@ -311,7 +317,11 @@ void uct_kernel(UctArgs p)
     // BAL: the sixteen progress words come FIRST, at an address known at compile time, and everything else moves up by their 64
     // bytes (the launch adds them to the form's LDS size): behind the model their address would be one more value to keep
     extern __shared__ __attribute__((aligned(16))) uint32_t lds_bal[];   // (the same bytes as lds_raw: every dynamic array starts there)
-    double *lds_d = lds_raw + (BAL ? kUctBalBytes / sizeof(double) : 0);
+    // ATAB: the action table directly behind them, at a compile-time address as well, and everything else moves up by it too
+    static_assert(!ATAB || uct_action_table_form(AT, ENV, SP, MK, IL, QD), "the action table: the forms of uct_action_table_form");
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_bytes[];  // (the same bytes again)
+    const uint8_t *lds_act = lds_bytes + (BAL ? kUctBalBytes : 0);       // [kUctActBytes]
+    double *lds_d = lds_raw + ((BAL ? kUctBalBytes : 0) + (ATAB ? kUctActBytes : 0)) / sizeof(double);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int A = AT > 0 ? AT : p.A, H = p.horizon, E = p.episodes;
     const int nthreads = p.waves * 64;
@@ -386,6 +396,17 @@ void uct_kernel(UctArgs p)
         uint4 *dst = reinterpret_cast<uint4 *>(t16);
         for (int i = tid; i < n8; i += nthreads) dst[i] = src[i];
         for (int i = (n8 << 3) + tid; i < n; i += nthreads) t16[i] = p.t16[i];
+    }
+    // ACTION TABLE (profiles/uct_action_table.md; the table: uct_action_table.hpp).  The rollout's policy is state-independent, so
+    // a step's action is a function of its draw alone, and for all but at most |A| - 1 of the 4 096 values of the draw's top twelve
+    // bits a function of those bits: one byte read from LDS instead of |A| - 1 compares of 64 bits and their adds.  A step in
+    // which some lane of the wave draws into a bucket that holds a threshold (kUctActExact) takes the compares for the whole
+    // wave, behind a wave-uniform branch.  The read sits one step AHEAD, beside the speculative draw it belongs to and off the
+    // state chain: a step is handed its action, not its draw.
+    if constexpr (ATAB) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(p.act_tab);
+        uint4 *dst = reinterpret_cast<uint4 *>(lds_bytes + (BAL ? kUctBalBytes : 0));
+        for (int i = tid; i < kUctActBytes / 16; i += nthreads) dst[i] = src[i];
     }
     // WAVE BALANCE (profiles/uct_wave_balance.md; the rule: uct_balance.hpp).  The saturated form runs four waves per SIMD for the
     // whole kernel, in one round, and with equal priorities the SIMD serves the oldest first: the oldest runs its rollouts near the
@@ -1296,6 +1317,20 @@ void uct_kernel(UctArgs p)
             const int hmax = p.max_steps > 0 ? min(H, depth + p.max_steps - st) : H;
             RollGen ga = roll_gen(g), gb = ga;
             uint64_t u = ga.next64() >> USH; // the 53 random bits of Generator.random() (RAWU: all 64, see thr_arg)
+            // ATAB: the action of a draw from its bucket's byte; the exact compares, clamp included, for every lane of the wave in
+            // a step where any of them reads kUctActExact (a scalar branch: a per-lane test is if-converted and both paths run)
+            [[maybe_unused]] auto table_action = [&](uint64_t draw) -> uint32_t {
+                uint32_t t = lds_act[(uint32_t)(draw >> (64 - kUctActBits))];
+                if (any64(t > (uint32_t)NTH)) {
+                    int act = 0;
+#pragma unroll
+                    for (int a = 0; a < NTH; ++a) act += p.thr_arg[a] <= draw ? 1 : 0; // scalar operands
+                    t = (uint32_t)min(act, p.thr_valid);
+                }
+                return t;
+            };
+            uint32_t act_next = 0;           // ATAB: the action of the step to come (that of the draw in `u`)
+            if constexpr (ATAB) act_next = table_action(u);
             bool stopped_in_a = true;
             double r_a = 0.0, r_b = 0.0, g_a = 0.0, g_b = 0.0;
             bool have_b = false;
@@ -1320,6 +1355,9 @@ void uct_kernel(UctArgs p)
                             const RollGen &gcur, RollGen &gspec, uint64_t &unext) -> bool {
                 // searchsorted(cdf, u, 'right') = #{a : cdf[a] <= u} = #{a : thr[a] <= k}
                 int act = 0;
+                if constexpr (ATAB) {
+                    act = (int)act_next;
+                } else
                 if (SP) {
                     // thr <= k is decided by the top bits unless they are equal: th < kh => thr < (th+1) << shift
                     // <= k;  th > kh => thr >= th << shift > k (also for the saturated th of thr = 2^53)
@@ -1362,6 +1400,7 @@ void uct_kernel(UctArgs p)
                     r_mine = rdict[r8[idx]];
                     gspec = gcur;
                     unext = gspec.next64() >> USH;
+                    if constexpr (ATAB) act_next = table_action(unext);
                     // (the first step of a rollout has no previous reward: r_prev = g_prev = 0.0 then, and adding +0.0 changes no bit
                     // of a return that is never -0 -- no select on `add_prev`)
                     total += g_prev * r_prev;
@@ -2693,6 +2732,8 @@ struct UctKnobs {
                       // mask of uct_virgin.hpp; a form or a tree that cannot keep it runs as 2)
     int balance;      // MP_UCT_BALANCE: 0 runs the LDS-resident form without its wave balance (every rollout at priority 0, for A/B
                       // runs and tests), any other value or unset with it
+    int action_table; // MP_UCT_ACTION_TABLE: 0 runs the LDS-resident form with the exact compares in every rollout step (for A/B
+                      // runs and tests), any other value or unset with the action table where it has room
 };
 static int uct_knob(const char *name)
 {
@@ -2715,6 +2756,7 @@ static UctKnobs uct_knobs_read()
     const char *tree_stores = getenv("MP_UCT_TREE_STORES");
     k.tree_stores = !tree_stores ? 3 : (!strcmp(tree_stores, "lane") ? 0 : (!strcmp(tree_stores, "group") ? 1 : (!strcmp(tree_stores, "virgin") ? 2 : 3)));
     k.balance = uct_knob("MP_UCT_BALANCE") != 0;
+    k.action_table = uct_knob("MP_UCT_ACTION_TABLE") != 0;
     return k;
 }
 
@@ -2910,12 +2952,29 @@ static int uct_choose(const UctCall &c, const UctKnobs &k, UctChoice *out)
 template <typename Kernel>
 static int uct_go(Kernel kernel, const UctChoice &ch, const UctArgs &a, hipStream_t st)
 {
-    const size_t lds = ch.lds + (a.balance ? (size_t)kUctBalBytes : 0);   // (the progress words of the wave balance, in front of the tables)
+    // (the progress words of the wave balance and the action table, in front of the tables)
+    const size_t lds = ch.lds + (a.balance ? (size_t)kUctBalBytes : 0) + (a.action_table ? (size_t)kUctActBytes : 0);
     if (lds > 64 * 1024)
         MP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kernel, dim3((unsigned)((a.n_roots + ch.roots_per_wg - 1) / ch.roots_per_wg)), dim3((unsigned)ch.threads), lds,
                        st, a);
     return MP_OK;
+}
+
+// the one-lane LDS-resident form with (ATAB) or without its action table: the instantiation for the call's visited mask and
+// wave balance
+template <int AT, bool ATAB>
+static int uct_launch_ldsr(const UctChoice &ch, bool vm, const UctArgs &a, hipStream_t st)
+{
+    if constexpr (uct_mask_form(AT, ENV_TABLE_LDSR, false, false, 2, false))
+        if (vm) {
+            if constexpr (uct_balance_form(AT))
+                if (a.balance) return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, true, true, ATAB>, ch, a, st);
+            return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, false, true, ATAB>, ch, a, st);
+        }
+    if constexpr (uct_balance_form(AT))
+        if (a.balance) return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, true, false, ATAB>, ch, a, st);
+    return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, false, false, ATAB>, ch, a, st);
 }
 
 // the kernel of a form for |A| = AT (0: any |A|), in the tree layout a.tree_il
@@ -2927,15 +2986,9 @@ static int uct_launch(const UctChoice &ch, bool listed, const UctArgs &a, hipStr
     if constexpr (AT > 0) {
         switch (ch.form) {
         case UF_LDSR:
-            if constexpr (uct_mask_form(AT, ENV_TABLE_LDSR, false, false, 2, false))
-                if (vm) {
-                    if constexpr (uct_balance_form(AT))
-                        if (a.balance) return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, true, true>, ch, a, st);
-                    return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, false, true>, ch, a, st);
-                }
-            if constexpr (uct_balance_form(AT))
-                if (a.balance) return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, false, true>, ch, a, st);
-            return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2>, ch, a, st);
+            if constexpr (uct_action_table_form(AT, ENV_TABLE_LDSR, false, false, 2, false))
+                if (a.action_table) return uct_launch_ldsr<AT, true>(ch, vm, a, st);
+            return uct_launch_ldsr<AT, false>(ch, vm, a, st);
         case UF_QUAD: return uct_go(uct_kernel<AT, ENV_TABLE_LDSR, false, false, 2, true>, ch, a, st);
         case UF_LONE: return uct_go(uct_lone_kernel<AT>, ch, a, st);
         case UF_LONE_MW: return uct_go(uct_lone_kernel<AT, false, true>, ch, a, st);
@@ -3017,8 +3070,9 @@ static bool cart_fastdiv(const mp_cartpole_params &cq, double *inv_tm)
     return true;
 }
 
-// the kernel arguments that the model, the policy and the tables decide; `thr`: the A thresholds of the tables
-static void uct_args_model(const UctPlan &c, int TE, const double *d_tab, const double *thr, UctArgs *out)
+// the kernel arguments that the model, the policy and the tables decide; `thr`: the A thresholds of the tables (the tables'
+// device addresses follow their upload)
+static void uct_args_model(const UctPlan &c, int TE, const double *thr, UctArgs *out)
 {
     const mp_model *model = c.model;
     const mp_policy *pol = c.pol;
@@ -3027,7 +3081,7 @@ static void uct_args_model(const UctPlan &c, int TE, const double *d_tab, const 
     a.n_roots = c.n_roots; a.S = model->S; a.A = A; a.episodes = c.episodes; a.horizon = c.horizon;
     a.table_n = TE;
     a.done_on_next = model->done_on_next; a.max_steps = model->max_steps; a.max_plan_len = c.max_plan_len;
-    a.rec = model->rec; a.t16 = model->t16; a.tab = d_tab;
+    a.rec = model->rec; a.t16 = model->t16; a.tab = nullptr; a.act_tab = nullptr;
     a.r8 = model->r8; a.rdict = model->rdict; a.n_rdict = model->n_rdict;
     a.Sb = model->NB > 1 && model->Sb > 0 ? model->Sb : model->S;
     a.thr_valid = 0;
@@ -3088,6 +3142,20 @@ static int uct_jump_table(mp_ctx *ctx, int H, const uint32_t **jump)
     return MP_OK;
 }
 
+// the action table of the call's thresholds (uct_action_table.hpp), kept in the context and rebuilt only when they change
+static const std::vector<uint8_t> &uct_action_table_bytes(mp_ctx *ctx, const UctArgs &a)
+{
+    mp_ctx::UctActionTable &t = ctx->uct_act;
+    const int nth = a.A - 1;
+    if (t.bytes.size() != (size_t)kUctActBytes || t.nth != nth || t.thr_valid != a.thr_valid || memcmp(t.thr, a.thr_arg, sizeof(t.thr)) != 0) {
+        t.bytes.resize(kUctActBytes);
+        uct_action_table_fill(a.thr_arg, nth, a.thr_valid, t.bytes.data());
+        t.nth = nth; t.thr_valid = a.thr_valid;
+        memcpy(t.thr, a.thr_arg, sizeof(t.thr));
+    }
+    return t.bytes;
+}
+
 // the kernel form and its geometry (uct_choose), the kernel arguments they decide, the jump table of the forms that jump ahead
 static int uct_form(mp_ctx *ctx, const UctPlan &c, bool cont, UctChoice *ch, UctArgs *a)
 {
@@ -3105,6 +3173,11 @@ static int uct_form(mp_ctx *ctx, const UctPlan &c, bool cont, UctChoice *ch, Uct
     // the wave balance of the one-lane LDS-resident form: where the model leaves its 64 bytes, else the form runs unbalanced
     a->balance = knobs.balance && ch->form == UF_LDSR && ch->lanes == 64 && ch->lds + kUctBalBytes <= kLdsBytes &&
                  model->A >= 2 && model->A <= 8 && uct_balance_form(model->A) ? 1 : 0;
+    // its action table: the same form with a state-independent policy (the form plans no other), where the model leaves the
+    // table's bytes as well; else today's instantiation
+    a->action_table = knobs.action_table && ch->form == UF_LDSR && ch->lanes == 64 && !c.pol &&
+                      ch->lds + kUctBalBytes + kUctActBytes <= kLdsBytes &&
+                      uct_action_table_form(model->A, ENV_TABLE_LDSR, false, false, ch->tree_il, false) ? 1 : 0;
     a->lanes = ch->lanes; a->waves = ch->waves; a->rep_shift = ch->rep_shift;
     a->jump = nullptr;
     const UctForm form = ch->form;
@@ -3294,17 +3367,28 @@ static int uct_plan_impl(mp_ctx *ctx, const UctPlan &c)
     const int TE = E < te_max ? E : te_max;
     std::vector<double> tab;
     const UctTables to = uct_tables(H, A, TE, c.gamma, c.temperature, c.prior_p, c.rollout_p, tab);
-    double *d_tab = nullptr;
-    MP_TRY(upload_tables(ctx, 1, tab, &d_tab));
 
     UctArgs a;
-    uct_args_model(c, TE, d_tab, tab.data() + to.cdf, &a);
+    uct_args_model(c, TE, tab.data() + to.cdf, &a);
     // the kernel form and its geometry: nothing below changes them
     const bool cont = ctx->tree.armed && ctx->tree.kind == 1 && ctx->tree.n_roots == n_roots && ctx->tree.A == A;
     UctChoice ch;
     MP_TRY(uct_form(ctx, c, cont, &ch, &a));
+    // the tables go up in one block, the action table of a launch that takes it behind the others (16-byte aligned): one copy on
+    // the planner's stream, and none while the block is what the last call uploaded
+    const size_t act_at = (to.n + 1) & ~(size_t)1;
+    if (a.action_table) {
+        const std::vector<uint8_t> &bytes = uct_action_table_bytes(ctx, a);
+        tab.resize(act_at + kUctActBytes / sizeof(double), 0.0);
+        memcpy(tab.data() + act_at, bytes.data(), kUctActBytes);
+    }
+    double *d_tab = nullptr;
+    MP_TRY(upload_tables(ctx, 1, tab, &d_tab));
+    a.tab = d_tab;
+    a.act_tab = a.action_table ? reinterpret_cast<const uint8_t *>(d_tab + act_at) : nullptr;
     MP_TRY(uct_trees(ctx, c, cont, ch, &a));
     form_record(ctx->last_variant, uct_form_name(ch.form));
+    ctx->uct_action_table = a.action_table;
 
     // the caller's arrays: root states, steps and generator records in, the records and the results out
     const bool host_call = mem_arrays(c.mem) == MP_MEM_HOST;       // the call synchronises before it returns
@@ -3368,6 +3452,8 @@ int mp_uct_plan_policy(mp_ctx *ctx, mp_model *model, mp_policy *policy, int32_t 
                                nullptr, 0, rng_state, nullptr, max_plan_len, plans, plan_len, root_value, root_child_count,
                                root_child_value, env_steps, mem});
 }
+
+int mp_uct_last_action_table(mp_ctx *ctx) { return ctx ? ctx->uct_action_table : 0; }
 
 // mcts_with_prior.py:47-62 as tables: per state, the prior row and the integer sampling thresholds of the rollout row
 // (computed exactly as mp_uct_plan computes them for one distribution), plus one fused record per (s, a).

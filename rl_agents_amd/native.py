@@ -168,6 +168,7 @@ SIGNATURES = {
     "mp_saopd_choose_form": (C.c_int, [_vp, _vp, P(C.c_char_p), P(C.c_char_p)]),
     "mp_last_kernel_ms": (C.c_int, [_vp, P(c_f64), P(c_i32)]),
     "mp_last_kernel_variant": (C.c_char_p, [_vp]),
+    "mp_uct_last_action_table": (C.c_int, [_vp]),
     "mp_kernel_form_names": (C.c_char_p, []),
     "mp_selftest_lds_atomic_order": (C.c_int, [_vp, C.c_int32, C.POINTER(C.c_int64)]),
     "mp_env_step": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, _vp, _vp, c_i32, c_i32, _vp, _vp, _vp, _vp, c_i32, _vp, c_i32]),
@@ -688,6 +689,12 @@ class Context(object):
         value-iteration call (vi_solve, vi_solve_v, vi_sweeps, vi_backup) one of vi_form_names() -- the launch that produced the
         returned values -- neither of which that list holds)."""
         return self._lib.mp_last_kernel_variant(self._h).decode()
+
+    def uct_last_action_table(self):
+        """Whether the last uct_plan* call launched its form ("uct_ldsr") with the rollout's action table in LDS
+        (mp_uct_last_action_table): False with MP_UCT_ACTION_TABLE=0, for any other form, for |A| > 6 and for a model that leaves
+        the table no room.  The form's name and the results are the same either way."""
+        return bool(self._lib.mp_uct_last_action_table(self._h))
 
     def vi_graph_captures(self):
         """How many times this context has captured a chain of deterministic value-iteration sweeps into a graph
