@@ -120,32 +120,56 @@ class GraphBasedPlanner(AbstractPlanner):
             self._device = None
         self._nodes = self._listing = None
 
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, keep_actions=None):
-        """``root_steps`` and ``keep_actions`` are accepted for the common interface: the ``done`` flag of a step is
-        discarded (:47) and "subtree" equals "reset"."""
+    # what the stochastic planner (rl_agents_amd/gbop.py), which plans through the same plan_batch, says differently
+    kept_with_graph = "bounds and counters"     # what of a kept graph was built on the previous tables
+    queue_knob = "MP_GBOPD_QUEUE"               # the environment knob its mp_*_create reads
+    steps_count_when_raising = False            # GBOP: the reference's steps up to a failing step are taken before it raises
+
+    def on_kept_graph(self, plan):
+        """``plan()``, the one call of the kept planners; the library's refusal of tables that changed under them as the
+        planner's own."""
+        try:
+            return plan()
+        except native.NativeError as e:
+            if "kept graph" in str(e):
+                raise NotImplementedError("graph-based planner: the environment's tables changed; the graph, {} kept from earlier "
+                                          "plans were built on the previous tables (call planner.forget() to start a new planner "
+                                          "on the new ones)".format(self.kept_with_graph)) from e
+            raise
+
+    def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None):
+        """The one ``mp_gbopd_plan`` call.  ``root_steps`` is accepted for the common interface (the ``done`` flag of a step is
+        discarded, :47); a batch model of one MDP per root is refused."""
+        if model_index is not None:
+            raise NotImplementedError("GBOP-D keeps its graph from plan to plan: one MDP per root is not planned")
+        cfg = self.config
+        planners = self.device_planners(model, len(root_states))
+        self._nodes = self._listing = None
+        return self.on_kept_graph(lambda: planners.plan(root_states, int(cfg["budget"]), cfg["gamma"], 1 / (1 - cfg["gamma"]),
+                                                        cfg["accuracy"], int(cfg["sampling_timeout"]), rng_states))
+
+    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, keep_actions=None, env_rng_states=None):
+        """``root_steps`` and ``keep_actions`` are accepted for the common interface ("subtree" equals "reset"), and so is
+        ``env_rng_states``: GBOP-D plans on a deterministic table, and GBOP re-seeds every episode's clone with a draw of the
+        planner's generator (graph_based_stochastic.py:239), so the environment's own generator is never read."""
         model = self.model_for(state)
         n = len(root_states)
         if rng_states is None:
             rng_states = self.batch_rng_states(n)
-        cfg = self.config
-        planners = self.device_planners(model, n)
-        self._nodes = self._listing = None
-        try:
-            out = planners.plan(root_states, int(cfg["budget"]), cfg["gamma"], 1 / (1 - cfg["gamma"]), cfg["accuracy"],
-                                int(cfg["sampling_timeout"]), rng_states)
-        except native.NativeError as e:
-            if "kept graph" in str(e):
-                raise NotImplementedError("graph-based planner: the environment's tables changed; the graph, bounds and "
-                                          "counters kept from earlier plans were built on the previous tables (call "
-                                          "planner.forget() to start a new planner on the new ones)") from e
-            raise
+        out = self.plan_on(model, root_states, root_steps, rng_states)
+        steps = int(out["env_steps"].sum())
+        if self.steps_count_when_raising:
+            self.env_steps += steps
         if not getattr(self, "defer_errors", False):               # (a batched caller checks its live slots only)
-            self.raise_for_status(out["status"])
+            self.raise_for_result(out)
         out["rng_states"] = rng_states
         out["root_lower"], out["root_upper"] = out["value_lower"], out["value_upper"]
+        if out["plans"].ndim == 1:                                 # (GBOP: one action a root is a plan of length one)
+            out["plans"] = out["plans"].reshape(n, 1)
         self.relabel(out, model)
         self.last, self._root, self._last_model = out, None, model
-        self.env_steps += int(out["env_steps"].sum())
+        if not self.steps_count_when_raising:
+            self.env_steps += steps
         return out
 
     def plan(self, state, observation):
@@ -159,13 +183,13 @@ class GraphBasedPlanner(AbstractPlanner):
         n = int(out["plan_len"][0])
         return [int(a) for a in out["plans"][0, :n]]
 
-    @staticmethod
-    def raise_for_status(status):
+    @classmethod
+    def raise_for_status(cls, status):
         status = np.asarray(status)
         if (status == native.MP_ERR_ALLOC).any():
             raise RuntimeError("graph-based planner: backup queue overflow on the device; raise the queue capacity "
-                               "(GraphBasedPlanner.queue_capacity, or MP_GBOPD_QUEUE in the environment) and start again: "
-                               "the planner's graph is half updated and stays failed")
+                               "({}.queue_capacity, or {} in the environment) and start again: the planner's graph is half "
+                               "updated and stays failed".format(cls.__name__, cls.queue_knob))
         if (status == native.MP_ERR_GBOPD_NO_ACTION).any():         # np.amax([]) in partial_value_iteration (:74)
             raise ValueError("zero-size array to reduction operation maximum which has no identity")
         if (status == native.MP_ERR_GBOPD_DIVERGED).any():

@@ -103,6 +103,23 @@ inline FormName gbopd_form_name(bool use_lds)
     snprintf(n.s, sizeof(n.s), "gbopd_wave_%s", use_lds ? "lds" : "global");
     return n;
 }
+// GBOP (gbop.hip): named by the model's rows (its MP_MODE_* of mi355plan.h, which common.hpp includes before this header) and
+// the placement of the bounds.  Listed by mp_gbop_form_names -- NOT by all_form_names below, as for Sparse Sampling.
+inline FormName gbop_form_name(int mode, bool use_lds)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "gbop_%s_%s", mode == MP_MODE_DETERMINISTIC ? "table" : mode == MP_MODE_SPARSE ? "sparse" : "dense",
+             use_lds ? "lds" : "global");
+    return n;
+}
+inline std::string gbop_form_names()
+{
+    std::string out;
+    for (int mode : {MP_MODE_DETERMINISTIC, MP_MODE_STOCHASTIC, MP_MODE_SPARSE})
+        for (int l = 1; l >= 0; --l) { out += gbop_form_name(mode, l != 0).s; out += '\n'; }
+    out.pop_back();
+    return out;
+}
 
 // Sparse Sampling (sparse_sampling.hip): the frames in LDS or in a global workspace.  Reported by mp_last_kernel_variant after a
 // call and listed by the planner's own mp_ss_form_names -- NOT by all_form_names below, whose list is pinned name for name

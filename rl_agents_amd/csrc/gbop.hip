@@ -40,38 +40,26 @@
 // gbopd_kernel; the chance records, which a backup streams through once, stay in global memory.
 #include <math.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <new>
 #include <string>
 #include <vector>
 
 #include "common.hpp"
+#include "graph_shared.hpp"
 #include "kl_transition.hpp"
 #include "opd_closing.hpp"
 #include "pcg64.hpp"
 #include "seed_sequence.hpp"
 #include "wave.hpp"
-#include "wave_host.hpp"
 
-struct mp_gbop {
-    mp_ctx *ctx = nullptr;
-    mp_model *model = nullptr;
-    uint64_t model_serial = 0;
-    int n = 0, S = 0, A = 0, K = 0, qcap = 0;
-    long E = 0;                 // parent entries per planner: in_ptr[S]
+struct mp_gbop : mp::GraphHandle {
+    int K = 0;
     int64_t steps_bound = 0;    // no count of any planner exceeds it: the steps of every plan call so far
-    double *lower = nullptr, *upper = nullptr, *c_val = nullptr, *k_cum = nullptr, *k_mu = nullptr, *k_lcb = nullptr, *pp = nullptr,
-           *pm = nullptr;
-    int32_t *index = nullptr, *npar = nullptr, *created = nullptr, *par = nullptr, *queue = nullptr, *uq = nullptr;
-    int32_t *c_count = nullptr, *c_m = nullptr, *c_backed = nullptr, *k_state = nullptr, *k_count = nullptr;
-    uint8_t *expanded = nullptr;
-    int64_t *count = nullptr, *visits = nullptr, *n_obs = nullptr;
-    int32_t *n_created = nullptr, *failed = nullptr, *root_of = nullptr;
-    int32_t *in_ptr = nullptr;  // [S + 1], shared
+    double *c_val = nullptr, *k_cum = nullptr, *k_mu = nullptr, *k_lcb = nullptr, *pp = nullptr, *pm = nullptr;
+    int32_t *uq = nullptr, *c_count = nullptr, *c_m = nullptr, *c_backed = nullptr, *k_state = nullptr, *k_count = nullptr;
+    int64_t *count = nullptr;
     std::vector<uint8_t> h_listed;  // [S * A] the actions a state lists (slot = listing order)
-    std::vector<int32_t> h_in_ptr;
-    std::vector<mp_ctx::Block> blocks;
 };
 
 namespace mp {
@@ -99,8 +87,6 @@ struct GbopArgs {
     int64_t *env_steps, *pops;
 };
 
-constexpr long kGbopMaxPops = 1L << 22; // pops one PLAN may make (see kGbMaxPops in gbopd.hip); MP_GBOP_MAX_POPS lowers it (tests)
-
 template <bool LDSV>
 __global__ __launch_bounds__(64) void gbop_kernel(GbopArgs p)
 {
@@ -121,12 +107,7 @@ __global__ __launch_bounds__(64) void gbop_kernel(GbopArgs p)
             if (l0) {
                 if (p.action) p.action[r] = -1;
                 if (p.key) p.key[r] = 0;
-                if (p.plan_len) p.plan_len[r] = 0;
-                if (p.status) p.status[r] = status;
-                if (p.root_lower) p.root_lower[r] = 0.0;
-                if (p.root_upper) p.root_upper[r] = 0.0;
-                if (p.env_steps) p.env_steps[r] = 0;
-                if (p.pops) p.pops[r] = 0;
+                graph_refuse(r, status, p.plan_len, p.status, p.root_lower, p.root_upper, p.env_steps, p.pops);
             }
             continue;
         }
@@ -145,14 +126,7 @@ __global__ __launch_bounds__(64) void gbop_kernel(GbopArgs p)
                       *const pm = p.pm + kb;
 
         int n_created = p.n_created[r];
-        if (LDSV) { // stage in the bounds of the nodes that exist
-            for (int i = lane; i < n_created; i += 64) {
-                const int s = created[i];
-                lower[s] = p.lower[sb + s];
-                upper[s] = p.upper[sb + s];
-            }
-            __syncthreads();
-        }
+        if (LDSV) graph_stage_in(p.lower, p.upper, sb, created, n_created, lower, upper, lane); // the bounds of the nodes that exist
         // graph_based.py:110-116 (every caller of it is uniform)
         auto get_node = [&](int s) {
             if (index[s] < 0) {
@@ -415,14 +389,7 @@ __global__ __launch_bounds__(64) void gbop_kernel(GbopArgs p)
             if (status != MP_OK) { len = 0; action = -1; key = 0; }
         }
         const double root_l = lower[s0], root_u = upper[s0];
-        if (LDSV) { // write the bounds back
-            __syncthreads();
-            for (int i = lane; i < n_created; i += 64) {
-                const int s = created[i];
-                p.lower[sb + s] = lower[s];
-                p.upper[sb + s] = upper[s];
-            }
-        }
+        if (LDSV) graph_write_back(p.lower, p.upper, sb, created, n_created, lower, upper, lane);
         if (l0) {
             gen.store(p.rng + (long)r * 6);
             p.n_created[r] = n_created;
@@ -440,40 +407,13 @@ __global__ __launch_bounds__(64) void gbop_kernel(GbopArgs p)
     }
 }
 
-inline FormName gbop_form_name(int mode, bool use_lds)
-{
-    FormName n;
-    snprintf(n.s, sizeof(n.s), "gbop_%s_%s", mode == MP_MODE_DETERMINISTIC ? "table" : mode == MP_MODE_SPARSE ? "sparse" : "dense",
-             use_lds ? "lds" : "global");
-    return n;
-}
-
-template <typename T>
-static hipError_t gbop_alloc(mp_gbop *pl, T **out, size_t bytes)
-{
-    void *p = nullptr;
-    size_t got = bytes;
-    const hipError_t e = ctx_block_alloc(pl->ctx, &p, bytes ? bytes : 16, &got);
-    if (e != hipSuccess) return e;
-    pl->blocks.push_back({p, got});
-    *out = static_cast<T *>(p);
-    return hipSuccess;
-}
-
 } // namespace mp
 
 using namespace mp;
 
 extern "C" {
 
-int mp_gbop_free(mp_gbop *pl)
-{
-    if (!pl) return MP_OK;
-    for (const auto &b : pl->blocks) ctx_block_release(pl->ctx, b.p, b.bytes);
-    pl->blocks.clear();
-    delete pl;
-    return MP_OK;
-}
+int mp_gbop_free(mp_gbop *pl) { return graph_free(pl); }
 
 int mp_gbop_create(mp_ctx *ctx, mp_model *model, int32_t n_planners, int32_t max_next_states, int32_t queue_cap, mp_gbop **out)
 {
@@ -492,18 +432,8 @@ int mp_gbop_create(mp_ctx *ctx, mp_model *model, int32_t n_planners, int32_t max
     pl->ctx = ctx; pl->model = model; pl->model_serial = model->serial; pl->n = n_planners; pl->S = model->S; pl->A = model->A; pl->K = K;
     const int S = pl->S, A = pl->A;
     const size_t SA = (size_t)S * A;
-    // queue capacity: a power of two, at least S (an episode's update_queue holds distinct states); the default of mp_gbopd_create
-    long want = queue_cap;
-    if (want <= 0) {
-        if (const char *e = getenv("MP_GBOP_QUEUE")) want = atol(e);
-    }
-    if (want <= 0) {
-        want = 65536;
-        while (want > 1024 && (size_t)want * 4 * (size_t)n_planners > ((size_t)4 << 30)) want >>= 1;
-    }
-    int q = 2;
-    while (q < want && q < (1 << 28)) q <<= 1;
-    pl->qcap = q;
+    // (an episode's update_queue holds distinct states: a ring of fewer than S entries can fail on its first episode)
+    const int q = pl->qcap = graph_queue_capacity(queue_cap, "MP_GBOP_QUEUE", n_planners);
     // the listed actions and the in-degrees on the host: the distinct states with a listed action that may lead to c
     const int W = model->mode == MP_MODE_DETERMINISTIC ? 1 : model->mode == MP_MODE_STOCHASTIC ? S : model->B;
     std::vector<Rec> hrec;
@@ -531,66 +461,44 @@ int mp_gbop_create(mp_ctx *ctx, mp_model *model, int32_t n_planners, int32_t max
         return fail(MP_ERR_HIP, "%s: reading the model's tables failed", who);
     }
     pl->h_listed.assign(SA, 0);
-    pl->h_in_ptr.assign((size_t)S + 1, 0);
-    {
-        std::vector<int32_t> last((size_t)S, -1);
-        for (int s = 0; s < S; ++s)
-            for (int a = 0; a < A; ++a) {
-                const size_t sa = (size_t)s * A + a;
-                const bool is_listed = model->mode == MP_MODE_DETERMINISTIC ? (hrec[sa].flags & 4u) != 0 : (havail.empty() || havail[sa] != 0);
-                pl->h_listed[sa] = is_listed ? 1 : 0;
-                if (!is_listed) continue;
-                for (int j = 0; j < W; ++j) {
-                    int c;
-                    if (model->mode == MP_MODE_DETERMINISTIC) c = hrec[sa].next;
-                    else {
-                        // the row search can return column j only where its threshold exceeds the one before; the last
-                        // column also takes a draw past every threshold
-                        const uint64_t before = j ? hthr[sa * W + j - 1] : 0;
-                        if (!(hthr[sa * W + j] > before) && j != W - 1) continue;
-                        c = model->mode == MP_MODE_SPARSE ? hnxt[sa * W + j] : j;
-                    }
-                    if (c < 0 || c >= S) {
-                        delete pl;
-                        return fail(MP_ERR_ARG, "%s: a next state of (%d, %d) is %d: out of range", who, s, a, c);
-                    }
-                    if (last[c] != s) { last[c] = s; ++pl->h_in_ptr[(size_t)c + 1]; }
-                }
-            }
-        for (int s = 0; s < S; ++s) pl->h_in_ptr[(size_t)s + 1] += pl->h_in_ptr[s];
+    const int counted = graph_count_parents(pl, who, [&](int s, int a, auto visit) {
+        const size_t sa = (size_t)s * A + a;
+        const bool is_listed = model->mode == MP_MODE_DETERMINISTIC ? (hrec[sa].flags & 4u) != 0 : (havail.empty() || havail[sa] != 0);
+        pl->h_listed[sa] = is_listed ? 1 : 0;
+        if (!is_listed) return (int)MP_OK;
+        if (model->mode == MP_MODE_DETERMINISTIC) return visit(hrec[sa].next);
+        for (int j = 0; j < W; ++j) {
+            // the row search can return column j only where its threshold exceeds the one before; the last column also
+            // takes a draw past every threshold
+            const uint64_t before = j ? hthr[sa * W + j - 1] : 0;
+            if (!(hthr[sa * W + j] > before) && j != W - 1) continue;
+            MP_TRY(visit(model->mode == MP_MODE_SPARSE ? hnxt[sa * W + j] : j));
+        }
+        return (int)MP_OK;
+    });
+    if (counted != MP_OK) {
+        delete pl;
+        return counted;
     }
-    pl->E = pl->h_in_ptr[S];
-    const size_t sn = (size_t)S * pl->n, n = (size_t)pl->n, cn = sn * A, kn = cn * K;
-    if (gbop_alloc(pl, &pl->lower, sn * 8) != hipSuccess || gbop_alloc(pl, &pl->upper, sn * 8) != hipSuccess ||
-        gbop_alloc(pl, &pl->index, sn * 4) != hipSuccess || gbop_alloc(pl, &pl->npar, sn * 4) != hipSuccess ||
-        gbop_alloc(pl, &pl->created, sn * 4) != hipSuccess || gbop_alloc(pl, &pl->uq, sn * 4) != hipSuccess ||
-        gbop_alloc(pl, &pl->expanded, sn) != hipSuccess || gbop_alloc(pl, &pl->count, sn * 8) != hipSuccess ||
-        gbop_alloc(pl, &pl->visits, sn * 8) != hipSuccess || gbop_alloc(pl, &pl->par, n * (size_t)pl->E * 4) != hipSuccess ||
-        gbop_alloc(pl, &pl->queue, n * (size_t)pl->qcap * 4) != hipSuccess || gbop_alloc(pl, &pl->c_count, cn * 4) != hipSuccess ||
-        gbop_alloc(pl, &pl->c_m, cn * 4) != hipSuccess || gbop_alloc(pl, &pl->c_backed, cn * 4) != hipSuccess ||
-        gbop_alloc(pl, &pl->c_val, cn * 16) != hipSuccess || gbop_alloc(pl, &pl->k_state, kn * 4) != hipSuccess ||
-        gbop_alloc(pl, &pl->k_count, kn * 4) != hipSuccess || gbop_alloc(pl, &pl->k_cum, kn * 8) != hipSuccess ||
-        gbop_alloc(pl, &pl->k_mu, kn * 8) != hipSuccess || gbop_alloc(pl, &pl->k_lcb, kn * 8) != hipSuccess ||
-        gbop_alloc(pl, &pl->pp, kn * 8) != hipSuccess || gbop_alloc(pl, &pl->pm, kn * 8) != hipSuccess ||
-        gbop_alloc(pl, &pl->n_obs, n * 8) != hipSuccess || gbop_alloc(pl, &pl->n_created, n * 4) != hipSuccess ||
-        gbop_alloc(pl, &pl->failed, n * 4) != hipSuccess || gbop_alloc(pl, &pl->root_of, n * 4) != hipSuccess ||
-        gbop_alloc(pl, &pl->in_ptr, ((size_t)S + 1) * 4) != hipSuccess) {
+    const size_t sn = (size_t)S * pl->n, cn = sn * A, kn = cn * K;
+    int made = graph_create_shared(pl);
+    if (made == MP_OK &&
+        (graph_alloc(pl, &pl->uq, sn * 4) != hipSuccess || graph_alloc(pl, &pl->count, sn * 8) != hipSuccess ||
+         graph_alloc(pl, &pl->c_count, cn * 4) != hipSuccess || graph_alloc(pl, &pl->c_m, cn * 4) != hipSuccess ||
+         graph_alloc(pl, &pl->c_backed, cn * 4) != hipSuccess || graph_alloc(pl, &pl->c_val, cn * 16) != hipSuccess ||
+         graph_alloc(pl, &pl->k_state, kn * 4) != hipSuccess || graph_alloc(pl, &pl->k_count, kn * 4) != hipSuccess ||
+         graph_alloc(pl, &pl->k_cum, kn * 8) != hipSuccess || graph_alloc(pl, &pl->k_mu, kn * 8) != hipSuccess ||
+         graph_alloc(pl, &pl->k_lcb, kn * 8) != hipSuccess || graph_alloc(pl, &pl->pp, kn * 8) != hipSuccess ||
+         graph_alloc(pl, &pl->pm, kn * 8) != hipSuccess))
+        made = MP_ERR_ALLOC;
+    // (the chance records of a state are initialised when it is expanded)
+    if (made == MP_OK && (hipMemsetAsync(pl->count, 0, sn * 8, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) made = MP_ERR_HIP;
+    if (made != MP_OK) {
         (void)hipGetLastError();
         mp_gbop_free(pl);
+        if (made == MP_ERR_HIP) return fail(MP_ERR_HIP, "%s: initialising the planners failed", who);
         return fail(MP_ERR_ALLOC, "%s: device allocation failed (%d planners x %d states x %d actions x %d next states, queue of %d "
                                   "entries each)", who, n_planners, S, A, K, q);
-    }
-    // (stream order: the blocks may be recycled ones; the chance records of a state are initialised when it is expanded)
-    if (hipMemsetAsync(pl->index, 0xff, sn * 4, st) != hipSuccess || hipMemsetAsync(pl->npar, 0, sn * 4, st) != hipSuccess ||
-        hipMemsetAsync(pl->created, 0, sn * 4, st) != hipSuccess || hipMemsetAsync(pl->expanded, 0, sn, st) != hipSuccess ||
-        hipMemsetAsync(pl->count, 0, sn * 8, st) != hipSuccess || hipMemsetAsync(pl->visits, 0, sn * 8, st) != hipSuccess ||
-        hipMemsetAsync(pl->lower, 0, sn * 8, st) != hipSuccess || hipMemsetAsync(pl->upper, 0, sn * 8, st) != hipSuccess ||
-        hipMemsetAsync(pl->n_obs, 0, n * 8, st) != hipSuccess || hipMemsetAsync(pl->n_created, 0, n * 4, st) != hipSuccess ||
-        hipMemsetAsync(pl->failed, 0, n * 4, st) != hipSuccess || hipMemsetAsync(pl->root_of, 0xff, n * 4, st) != hipSuccess ||
-        hipMemcpyAsync(pl->in_ptr, pl->h_in_ptr.data(), ((size_t)S + 1) * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        mp_gbop_free(pl);
-        return fail(MP_ERR_HIP, "%s: initialising the planners failed", who);
     }
     *out = pl;
     return MP_OK;
@@ -607,10 +515,7 @@ int mp_gbop_plan(mp_ctx *ctx, mp_gbop *pl, const int32_t *root_state, int32_t ep
         return fail(MP_ERR_ARG, "%s: NULL argument", who);
     int rmem;
     MP_TRY(wave_mem(who, &mem, &rmem));
-    if (pl->ctx != ctx) return fail(MP_ERR_ARG, "%s: planners belong to another context", who);
-    if (pl->model->serial != pl->model_serial)
-        return fail(MP_ERR_ARG, "%s: the model's tables or action sets changed under a kept graph (bounds, parents, counts and "
-                                "chance records were built on the previous tables): free the planners and create new ones", who);
+    MP_TRY(graph_check_handle(ctx, pl, who, "bounds, parents, counts and chance records"));
     if (max_next_states < 1 || max_next_states > 32)
         return fail(MP_ERR_ARG, "%s: max_next_states_count %d is not in 1..32", who, max_next_states);
     if (max_next_states != pl->K)
@@ -618,8 +523,7 @@ int mp_gbop_plan(mp_ctx *ctx, mp_gbop *pl, const int32_t *root_state, int32_t ep
                     max_next_states, pl->K);
     if (episodes < 0 || horizon < 1 || sampling_timeout < 0) // (horizon 0: the reference's run() raises UnboundLocalError)
         return fail(MP_ERR_ARG, "%s: episodes = %d, horizon = %d, sampling_timeout = %d", who, episodes, horizon, sampling_timeout);
-    if (!(gamma > -1.0 && gamma < 1.0) || !(value_max == value_max) || !(accuracy >= 0.0))
-        return fail(MP_ERR_ARG, "%s: need -1 < gamma < 1, accuracy >= 0 and a number for 1 / (1 - gamma)", who);
+    MP_TRY(graph_check_numbers(who, gamma, value_max, accuracy));
     // counts are LIFETIME counts: none exceeds the steps made so far plus this call's
     const int64_t reach = pl->steps_bound + (int64_t)episodes * horizon;
     if (reach > 0x7fffffff) return fail(MP_ERR_ARG, "%s: %lld lifetime steps do not fit a 32-bit count", who, (long long)reach);
@@ -638,38 +542,22 @@ int mp_gbop_plan(mp_ctx *ctx, mp_gbop *pl, const int32_t *root_state, int32_t ep
     for (int64_t c = 0; c < reach; ++c) { tab[c] = reward_thr_by_count[c]; tab[reach + c] = transition_thr_by_count[c]; }
     double *d_tab = nullptr;
     MP_TRY(upload_tables(ctx, 44, tab, &d_tab));
-    a.n = n; a.S = S; a.A = pl->A; a.K = pl->K; a.M = episodes; a.H = horizon; a.qcap = pl->qcap; a.E = pl->E;
+    graph_args(pl, "MP_GBOP_MAX_POPS", gamma, value_max, accuracy, &a);
+    a.K = pl->K; a.M = episodes; a.H = horizon;
     a.plan_steps = sampling_timeout < 2 ? sampling_timeout : 2; a.n_counts = (int)reach;
-    a.max_pops = kGbopMaxPops;
-    if (const char *e = getenv("MP_GBOP_MAX_POPS")) { // test knob: a smaller limit (never a larger one)
-        const long v = atol(e);
-        if (v >= 1 && v < kGbopMaxPops) a.max_pops = v;
-    }
-    a.gamma = gamma; a.vmax = value_max; a.accuracy = accuracy;
     a.avail = pl->model->masked ? pl->model->avail : nullptr;
-    a.in_ptr = pl->in_ptr; a.rthr = d_tab; a.tthr = d_tab + reach;
-    a.lower = pl->lower; a.upper = pl->upper; a.c_val = pl->c_val; a.k_cum = pl->k_cum; a.k_mu = pl->k_mu; a.k_lcb = pl->k_lcb;
-    a.pp = pl->pp; a.pm = pl->pm; a.index = pl->index; a.npar = pl->npar; a.created = pl->created; a.par = pl->par;
-    a.queue = pl->queue; a.uq = pl->uq; a.n_created = pl->n_created; a.failed = pl->failed; a.root_of = pl->root_of;
-    a.c_count = pl->c_count; a.c_m = pl->c_m; a.c_backed = pl->c_backed; a.k_state = pl->k_state; a.k_count = pl->k_count;
-    a.expanded = pl->expanded; a.count = pl->count; a.visits = pl->visits; a.n_obs = pl->n_obs;
+    a.rthr = d_tab; a.tthr = d_tab + reach;
+    a.c_val = pl->c_val; a.k_cum = pl->k_cum; a.k_mu = pl->k_mu; a.k_lcb = pl->k_lcb; a.pp = pl->pp; a.pm = pl->pm;
+    a.uq = pl->uq; a.c_count = pl->c_count; a.c_m = pl->c_m; a.c_backed = pl->c_backed; a.k_state = pl->k_state; a.k_count = pl->k_count;
+    a.count = pl->count;
     WaveIo io(mem, rmem, n, root_state, &a.root_state, rng_state, &a.rng);
     io.add(WS_IO3, action, &a.action);
-    io.add(WS_IO4, plan_len, &a.plan_len);
-    io.add(WS_IO5, status, &a.status);
-    io.add(WS_IO6, env_steps, &a.env_steps);
-    io.add(WS_IO7, pops, &a.pops);
-    io.add(WS_IO8, value_lower, &a.root_lower);
-    io.add(WS_IO9, value_upper, &a.root_upper);
+    graph_results_io(io, plan_len, status, env_steps, pops, value_lower, value_upper, &a);
     io.add(WS_IO1, key, &a.key);
     MP_TRY(wave_stage(ctx, io));
 
-    // both bounds in LDS while they are small; MP_GBOP_LDS_BYTES moves the limit (0: never)
-    size_t lds_limit = 16 * 1024;
-    if (const char *e = getenv("MP_GBOP_LDS_BYTES")) lds_limit = (size_t)atol(e);
-    if (lds_limit > 64 * 1024) lds_limit = 64 * 1024;
-    const size_t lds = (size_t)S * 16;
-    const bool use_lds = lds <= lds_limit;
+    // both bounds in LDS while they are small; MP_GBOP_LDS_BYTES moves the limit
+    const bool use_lds = graph_use_lds("MP_GBOP_LDS_BYTES", S);
     // the workgroups stride over the planners: 16 wavefronts a compute unit; MP_GBOP_GRID lowers the grid (tests)
     long grid = (long)ctx->prop.multiProcessorCount * 16;
     if (const char *e = getenv("MP_GBOP_GRID")) {
@@ -678,20 +566,14 @@ int mp_gbop_plan(mp_ctx *ctx, mp_gbop *pl, const int32_t *root_state, int32_t ep
     }
     if (grid > n) grid = n;
     pl->steps_bound = reach;
-    MP_TRY(wave_launch(ctx, use_lds ? gbop_kernel<true> : gbop_kernel<false>, (int)grid, use_lds ? lds : 0,
+    MP_TRY(wave_launch(ctx, use_lds ? gbop_kernel<true> : gbop_kernel<false>, (int)grid, use_lds ? (size_t)S * 16 : 0,
                        gbop_form_name(pl->model->mode, use_lds), a));
     return wave_unstage(ctx, io);
 }
 
 const char *mp_gbop_form_names(void)
 {
-    static const std::string names = [] {
-        std::string out;
-        for (int mode : {MP_MODE_DETERMINISTIC, MP_MODE_STOCHASTIC, MP_MODE_SPARSE})
-            for (int l = 1; l >= 0; --l) { out += gbop_form_name(mode, l != 0).s; out += '\n'; }
-        out.pop_back();
-        return out;
-    }();
+    static const std::string names = gbop_form_names();
     return names.c_str();
 }
 
@@ -716,35 +598,13 @@ int mp_gbop_export(mp_gbop *pl, int32_t planner, int32_t cap, int32_t *n_nodes, 
                    int32_t *parent_ptr, int32_t *parent_idx, int64_t *visits, int64_t *n_observations, int32_t *root)
 {
     const char *const who = "mp_gbop_export";
-    if (!pl || !n_nodes) return fail(MP_ERR_ARG, "%s: NULL argument", who);
-    if (planner < 0 || planner >= pl->n) return fail(MP_ERR_ARG, "%s: planner %d out of range", who, planner);
-    if (pl->model->serial != pl->model_serial)
-        return fail(MP_ERR_ARG, "%s: the model's tables or action sets changed under a kept graph: the actions of its nodes are "
-                                "no longer the model's", who);
-    MP_HIP(hipSetDevice(pl->ctx->device));
-    MP_HIP(hipStreamSynchronize(pl->ctx->stream));
+    GraphExport x;
+    MP_TRY(graph_export_begin(pl, who, "actions", planner, cap, n_nodes, visits, n_observations, root, &x));
     const size_t S = (size_t)pl->S, A = (size_t)pl->A, K = (size_t)pl->K, r = (size_t)planner, SA = S * A, SAK = SA * K;
-    int32_t nc = 0, root_state = -1;
-    int64_t nobs = 0;
-    MP_HIP(hipMemcpy(&nc, pl->n_created + r, 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(&root_state, pl->root_of + r, 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(&nobs, pl->n_obs + r, 8, hipMemcpyDeviceToHost));
-    if (nc < 0 || (size_t)nc > S) return fail(MP_ERR_ARG, "%s: bad node count %d", who, nc);
-    *n_nodes = nc;
-    if (n_observations) *n_observations = nobs;
-    if (cap < nc) return fail(MP_ERR_ARG, "%s: capacity %d < %d nodes", who, cap, nc);
-    std::vector<double> hl(S), hu(S), hcv(2 * SA), hcum(SAK), hmu(SAK), hlcb(SAK), hpp(SAK), hpm(SAK);
-    std::vector<int32_t> hidx(S), hnp(S), hcr(S), hpar((size_t)pl->E), hcc(SA), hcm(SA), hcb(SA), hks(SAK), hkc(SAK);
+    std::vector<double> hcv(2 * SA), hcum(SAK), hmu(SAK), hlcb(SAK), hpp(SAK), hpm(SAK);
+    std::vector<int32_t> hcc(SA), hcm(SA), hcb(SA), hks(SAK), hkc(SAK);
     std::vector<int64_t> hcount(S);
-    std::vector<uint8_t> hex(S);
-    MP_HIP(hipMemcpy(hl.data(), pl->lower + r * S, S * 8, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hu.data(), pl->upper + r * S, S * 8, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hidx.data(), pl->index + r * S, S * 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hnp.data(), pl->npar + r * S, S * 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hcr.data(), pl->created + r * S, S * 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hex.data(), pl->expanded + r * S, S, hipMemcpyDeviceToHost));
     MP_HIP(hipMemcpy(hcount.data(), pl->count + r * S, S * 8, hipMemcpyDeviceToHost));
-    if (pl->E) MP_HIP(hipMemcpy(hpar.data(), pl->par + r * (size_t)pl->E, (size_t)pl->E * 4, hipMemcpyDeviceToHost));
     MP_HIP(hipMemcpy(hcc.data(), pl->c_count + r * SA, SA * 4, hipMemcpyDeviceToHost));
     MP_HIP(hipMemcpy(hcm.data(), pl->c_m + r * SA, SA * 4, hipMemcpyDeviceToHost));
     MP_HIP(hipMemcpy(hcb.data(), pl->c_backed + r * SA, SA * 4, hipMemcpyDeviceToHost));
@@ -756,21 +616,19 @@ int mp_gbop_export(mp_gbop *pl, int32_t planner, int32_t cap, int32_t *n_nodes, 
     MP_HIP(hipMemcpy(hlcb.data(), pl->k_lcb + r * SAK, SAK * 8, hipMemcpyDeviceToHost));
     MP_HIP(hipMemcpy(hpp.data(), pl->pp + r * SAK, SAK * 8, hipMemcpyDeviceToHost));
     MP_HIP(hipMemcpy(hpm.data(), pl->pm + r * SAK, SAK * 8, hipMemcpyDeviceToHost));
-    if (visits) MP_HIP(hipMemcpy(visits, pl->visits + r * S, S * 8, hipMemcpyDeviceToHost));
-    if (root) *root = root_state >= 0 && (size_t)root_state < S ? hidx[(size_t)root_state] : -1;
     int32_t np_total = 0;
     if (parent_ptr) parent_ptr[0] = 0;
-    for (int32_t i = 0; i < nc; ++i) {
-        const int32_t s = hcr[(size_t)i];
+    for (int32_t i = 0; i < x.n_nodes; ++i) {
+        const int32_t s = x.created[(size_t)i];
         if (s < 0 || (size_t)s >= S) return fail(MP_ERR_ARG, "%s: node %d holds state %d", who, i, s);
         if (state) state[i] = s;
-        if (lower) lower[i] = hl[(size_t)s];
-        if (upper) upper[i] = hu[(size_t)s];
-        if (expanded) expanded[i] = hex[(size_t)s];
+        if (lower) lower[i] = x.lower[(size_t)s];
+        if (upper) upper[i] = x.upper[(size_t)s];
+        if (expanded) expanded[i] = x.expanded[(size_t)s];
         if (count) count[i] = hcount[(size_t)s];
         for (size_t a = 0; a < A; ++a) { // the chance records by action slot (slot = listing order); zeros where there is none
             const size_t src = (size_t)s * A + a, dst = (size_t)i * A + a;
-            const bool has = hex[(size_t)s] && pl->h_listed[src];
+            const bool has = x.expanded[(size_t)s] && pl->h_listed[src];
             if (listed) listed[dst] = has ? 1 : 0;
             if (chance_count) chance_count[dst] = has ? hcc[src] : 0;
             if (chance_assigned) chance_assigned[dst] = has ? hcm[src] : 0;
@@ -787,14 +645,7 @@ int mp_gbop_export(mp_gbop *pl, int32_t planner, int32_t cap, int32_t *n_nodes, 
                 if (p_minus) p_minus[kd] = has ? hpm[ks] : 0.0;
             }
         }
-        const int32_t base = pl->h_in_ptr[(size_t)s], room = pl->h_in_ptr[(size_t)s + 1] - base;
-        const int32_t np = hnp[(size_t)s] < room ? hnp[(size_t)s] : room;
-        for (int32_t j = 0; j < np; ++j) {
-            const int32_t ps = hpar[(size_t)base + j];
-            if (parent_idx) parent_idx[np_total] = ps >= 0 && (size_t)ps < S ? hidx[(size_t)ps] : -1;
-            ++np_total;
-        }
-        if (parent_ptr) parent_ptr[i + 1] = np_total;
+        graph_export_parents(pl, x, i, s, parent_ptr, parent_idx, &np_total);
     }
     return MP_OK;
 }

@@ -34,33 +34,19 @@
 // reductions) -> compare with the old bounds -> store -> parents appended behind the tail.  Nothing of pop k + 1 can start
 // before pop k has stored: the next front may be the node just written, or read it as a child.
 #include <math.h>
-#include <stdlib.h>
-#include <string.h>
 
 #include <new>
 #include <vector>
 
 #include "common.hpp"
+#include "graph_shared.hpp"
 #include "opd_closing.hpp"
 #include "pcg64.hpp"
 #include "wave.hpp"
-#include "wave_host.hpp"
 
-struct mp_gbopd {
-    mp_ctx *ctx = nullptr;
-    mp_model *model = nullptr;
-    uint64_t model_serial = 0;
-    int n = 0, S = 0, A = 0, qcap = 0;
-    long E = 0;                 // parent entries per planner: in_ptr[S]
-    double *lower = nullptr, *upper = nullptr;
-    int32_t *index = nullptr, *npar = nullptr, *created = nullptr, *par = nullptr, *queue = nullptr;
-    uint8_t *expanded = nullptr;
-    int64_t *visits = nullptr, *updates = nullptr, *n_obs = nullptr;
-    int32_t *n_created = nullptr, *failed = nullptr, *root_of = nullptr;
-    int32_t *in_ptr = nullptr;  // [S + 1], shared
+struct mp_gbopd : mp::GraphHandle {
+    int64_t *updates = nullptr;
     std::vector<mp::Rec> hrec;  // host copy of the model's records (in-degrees at creation, children / rewards of the export)
-    std::vector<int32_t> h_in_ptr;
-    std::vector<mp_ctx::Block> blocks;
 };
 
 namespace mp {
@@ -79,14 +65,8 @@ struct GbArgs {
     int64_t *visits, *updates, *n_obs;
     int32_t *plans, *plan_len, *status;
     double *root_lower, *root_upper;
-    int64_t *env_steps, *n_updates;
+    int64_t *env_steps, *pops;
 };
-
-// Pops one PLAN may make.  With accuracy 0 and rewards outside [0, 1] the bounds need not move monotonically and can cycle
-// between neighbouring doubles for ever -- the reference then never returns; a device call must, and soon: the machine is
-// shared.  The reference's longest measured plan made 490 000 pops; the limit is eight times that: a plan is ended when its
-// NEXT pop would be pop number 2^22 + 1 (the outputs count the pops applied).  MP_GBOPD_MAX_POPS lowers it (tests).
-constexpr long kGbMaxPops = 1L << 22;
 
 template <bool LDSV>
 __global__ __launch_bounds__(64) void gbopd_kernel(GbArgs p)
@@ -105,14 +85,7 @@ __global__ __launch_bounds__(64) void gbopd_kernel(GbArgs p)
     if (status != MP_OK) {
         if (p.plans)
             for (int i = lane; i < T; i += 64) p.plans[(long)r * T + i] = -1;
-        if (l0) {
-            if (p.plan_len) p.plan_len[r] = 0;
-            if (p.status) p.status[r] = status;
-            if (p.root_lower) p.root_lower[r] = 0.0;
-            if (p.root_upper) p.root_upper[r] = 0.0;
-            if (p.env_steps) p.env_steps[r] = 0;
-            if (p.n_updates) p.n_updates[r] = 0;
-        }
+        if (l0) graph_refuse(r, status, p.plan_len, p.status, p.root_lower, p.root_upper, p.env_steps, p.pops);
         return;
     }
     double *const lower = LDSV ? lds_v : p.lower + sb;
@@ -127,14 +100,7 @@ __global__ __launch_bounds__(64) void gbopd_kernel(GbArgs p)
     const double gamma = p.gamma;
 
     int n_created = p.n_created[r];
-    if (LDSV) { // stage in the bounds of the nodes that exist
-        for (int i = lane; i < n_created; i += 64) {
-            const int s = created[i];
-            lower[s] = p.lower[sb + s];
-            upper[s] = p.upper[sb + s];
-        }
-        __syncthreads();
-    }
+    if (LDSV) graph_stage_in(p.lower, p.upper, sb, created, n_created, lower, upper, lane); // the bounds of the nodes that exist
     // plan(), :119: root = get_node(observation)
     if (index[s0] < 0) {
         if (l0) {
@@ -236,7 +202,7 @@ __global__ __launch_bounds__(64) void gbopd_kernel(GbArgs p)
             long pops = 0;
             while (qh != qt) {
                 const int v = __builtin_amdgcn_readfirstlane(queue[qh & qmask]);
-                if (pops_total + pops >= p.max_pops) { status = MP_ERR_GBOPD_DIVERGED; break; } // (see kGbMaxPops: the front stays unpopped)
+                if (pops_total + pops >= p.max_pops) { status = MP_ERR_GBOPD_DIVERGED; break; } // (see kGraphMaxPops: the front stays unpopped)
                 ++qh; ++pops;
                 const double old_l = lower[v], old_u = upper[v];
                 const int np = npar[v], base = p.in_ptr[v];
@@ -311,14 +277,7 @@ __global__ __launch_bounds__(64) void gbopd_kernel(GbArgs p)
     if (p.plans)
         for (int i = len + lane; i < T; i += 64) p.plans[(long)r * T + i] = -1;
     const double root_l = lower[s0], root_u = upper[s0];
-    if (LDSV) { // write the bounds back
-        __syncthreads();
-        for (int i = lane; i < n_created; i += 64) {
-            const int s = created[i];
-            p.lower[sb + s] = lower[s];
-            p.upper[sb + s] = upper[s];
-        }
-    }
+    if (LDSV) graph_write_back(p.lower, p.upper, sb, created, n_created, lower, upper, lane);
     if (l0) {
         gen.store(p.rng + (long)r * 6);
         p.n_created[r] = n_created;
@@ -329,20 +288,8 @@ __global__ __launch_bounds__(64) void gbopd_kernel(GbArgs p)
         if (p.root_lower) p.root_lower[r] = root_l;
         if (p.root_upper) p.root_upper[r] = root_u;
         if (p.env_steps) p.env_steps[r] = steps;
-        if (p.n_updates) p.n_updates[r] = pops_total;
+        if (p.pops) p.pops[r] = pops_total;
     }
-}
-
-template <typename T>
-static hipError_t gb_alloc(mp_gbopd *pl, T **out, size_t bytes)
-{
-    void *p = nullptr;
-    size_t got = bytes;
-    const hipError_t e = ctx_block_alloc(pl->ctx, &p, bytes ? bytes : 16, &got);
-    if (e != hipSuccess) return e;
-    pl->blocks.push_back({p, got});
-    *out = static_cast<T *>(p);
-    return hipSuccess;
 }
 
 } // namespace mp
@@ -351,92 +298,48 @@ using namespace mp;
 
 extern "C" {
 
-int mp_gbopd_free(mp_gbopd *pl)
-{
-    if (!pl) return MP_OK;
-    for (const auto &b : pl->blocks) ctx_block_release(pl->ctx, b.p, b.bytes);
-    pl->blocks.clear();
-    delete pl;
-    return MP_OK;
-}
+int mp_gbopd_free(mp_gbopd *pl) { return graph_free(pl); }
 
 int mp_gbopd_create(mp_ctx *ctx, mp_model *model, int32_t n_planners, int32_t queue_cap, mp_gbopd **out)
 {
-    if (!ctx || !model || !out) return fail(MP_ERR_ARG, "mp_gbopd_create: NULL argument");
+    const char *const who = "mp_gbopd_create";
+    if (!ctx || !model || !out) return fail(MP_ERR_ARG, "%s: NULL argument", who);
     if (model->mode != MP_MODE_DETERMINISTIC || !model->rec)
-        return fail(MP_ERR_MODE, "mp_gbopd_create: GBOP-D needs a deterministic table model (mode %d)", model->mode);
-    if (model->M != 1 || model->NB != 1)
-        return fail(MP_ERR_MODE, "mp_gbopd_create: one whole model expected (no joint or batch model)");
-    if (n_planners < 1 || model->S < 1 || model->A < 1) return fail(MP_ERR_ARG, "mp_gbopd_create: n_planners = %d", n_planners);
+        return fail(MP_ERR_MODE, "%s: GBOP-D needs a deterministic table model (mode %d)", who, model->mode);
+    if (model->M != 1 || model->NB != 1) return fail(MP_ERR_MODE, "%s: one whole model expected (no joint or batch model)", who);
+    if (n_planners < 1 || model->S < 1 || model->A < 1) return fail(MP_ERR_ARG, "%s: n_planners = %d", who, n_planners);
     MP_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     mp_gbopd *pl = new (std::nothrow) mp_gbopd;
-    if (!pl) return fail(MP_ERR_ALLOC, "mp_gbopd_create: out of memory");
+    if (!pl) return fail(MP_ERR_ALLOC, "%s: out of memory", who);
     pl->ctx = ctx; pl->model = model; pl->model_serial = model->serial; pl->n = n_planners; pl->S = model->S; pl->A = model->A;
     const int S = pl->S, A = pl->A;
-    // queue capacity: a power of two.  Default 65 536 entries: the reference's list peaked at 19 243 on the golden cases, and
-    // with gamma 0.99, accuracy 1e-4 on a 50-state, 8-action model at 53 084 on a first plan and 62 751 on a following one --
-    // within 4 % of the default.  While a batch's rings would exceed 4 GiB the default HALVES (16 384 at 65 536 planners) and
-    // no longer covers that configuration: such a batch names its queue_cap, or its hungry planners report MP_ERR_ALLOC.
-    long want = queue_cap;
-    if (want <= 0) {
-        if (const char *e = getenv("MP_GBOPD_QUEUE")) want = atol(e);
-    }
-    if (want <= 0) {
-        want = 65536;
-        while (want > 1024 && (size_t)want * 4 * (size_t)n_planners > ((size_t)4 << 30)) want >>= 1;
-    }
-    int q = 2;
-    while (q < want && q < (1 << 28)) q <<= 1;
-    pl->qcap = q;
-    // the model's records on the host; in-degrees: the distinct states with a listed action into c
+    pl->qcap = graph_queue_capacity(queue_cap, "MP_GBOPD_QUEUE", n_planners);
+    // the model's records on the host; a listed (s, a) leads to its one next state
     pl->hrec.resize((size_t)S * A);
     if (hipStreamSynchronize(st) != hipSuccess ||
         hipMemcpy(pl->hrec.data(), model->rec, (size_t)S * A * sizeof(Rec), hipMemcpyDeviceToHost) != hipSuccess) {
         delete pl;
-        return fail(MP_ERR_HIP, "mp_gbopd_create: reading the model's records failed");
+        return fail(MP_ERR_HIP, "%s: reading the model's records failed", who);
     }
-    pl->h_in_ptr.assign((size_t)S + 1, 0);
-    {
-        std::vector<int32_t> last((size_t)S, -1);
-        for (int s = 0; s < S; ++s)
-            for (int a = 0; a < A; ++a) {
-                const Rec &rc = pl->hrec[(size_t)s * A + a];
-                if (!(rc.flags & 4u)) continue;
-                if (rc.next < 0 || rc.next >= S) {
-                    delete pl;
-                    return fail(MP_ERR_ARG, "mp_gbopd_create: transition[%d, %d] = %d out of range", s, a, rc.next);
-                }
-                if (last[rc.next] != s) { last[rc.next] = s; ++pl->h_in_ptr[(size_t)rc.next + 1]; }
-            }
-        for (int s = 0; s < S; ++s) pl->h_in_ptr[(size_t)s + 1] += pl->h_in_ptr[s];
+    const int counted = graph_count_parents(pl, who, [&](int s, int a, auto visit) {
+        const Rec &rc = pl->hrec[(size_t)s * A + a];
+        return rc.flags & 4u ? visit(rc.next) : (int)MP_OK;
+    });
+    if (counted != MP_OK) {
+        delete pl;
+        return counted;
     }
-    pl->E = pl->h_in_ptr[S];
-    const size_t sn = (size_t)S * pl->n, n = (size_t)pl->n;
-    if (gb_alloc(pl, &pl->lower, sn * 8) != hipSuccess || gb_alloc(pl, &pl->upper, sn * 8) != hipSuccess ||
-        gb_alloc(pl, &pl->index, sn * 4) != hipSuccess || gb_alloc(pl, &pl->npar, sn * 4) != hipSuccess ||
-        gb_alloc(pl, &pl->created, sn * 4) != hipSuccess || gb_alloc(pl, &pl->expanded, sn) != hipSuccess ||
-        gb_alloc(pl, &pl->visits, sn * 8) != hipSuccess || gb_alloc(pl, &pl->updates, sn * 8) != hipSuccess ||
-        gb_alloc(pl, &pl->par, n * (size_t)pl->E * 4) != hipSuccess || gb_alloc(pl, &pl->queue, n * (size_t)pl->qcap * 4) != hipSuccess ||
-        gb_alloc(pl, &pl->n_obs, n * 8) != hipSuccess || gb_alloc(pl, &pl->n_created, n * 4) != hipSuccess ||
-        gb_alloc(pl, &pl->failed, n * 4) != hipSuccess || gb_alloc(pl, &pl->root_of, n * 4) != hipSuccess ||
-        gb_alloc(pl, &pl->in_ptr, ((size_t)S + 1) * 4) != hipSuccess) {
+    const size_t sn = (size_t)S * pl->n;
+    const int q = pl->qcap;
+    int made = graph_create_shared(pl);
+    if (made == MP_OK && graph_alloc(pl, &pl->updates, sn * 8) != hipSuccess) made = MP_ERR_ALLOC;
+    if (made == MP_OK && (hipMemsetAsync(pl->updates, 0, sn * 8, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) made = MP_ERR_HIP;
+    if (made != MP_OK) {
         (void)hipGetLastError();
         mp_gbopd_free(pl);
-        return fail(MP_ERR_ALLOC, "mp_gbopd_create: device allocation failed (%d planners x %d states, queue of %d entries each)",
-                    n_planners, S, q);
-    }
-    // (stream order: the blocks may be recycled ones)
-    if (hipMemsetAsync(pl->index, 0xff, sn * 4, st) != hipSuccess || hipMemsetAsync(pl->npar, 0, sn * 4, st) != hipSuccess ||
-        hipMemsetAsync(pl->created, 0, sn * 4, st) != hipSuccess || hipMemsetAsync(pl->expanded, 0, sn, st) != hipSuccess ||
-        hipMemsetAsync(pl->visits, 0, sn * 8, st) != hipSuccess || hipMemsetAsync(pl->updates, 0, sn * 8, st) != hipSuccess ||
-        hipMemsetAsync(pl->lower, 0, sn * 8, st) != hipSuccess || hipMemsetAsync(pl->upper, 0, sn * 8, st) != hipSuccess ||
-        hipMemsetAsync(pl->n_obs, 0, n * 8, st) != hipSuccess || hipMemsetAsync(pl->n_created, 0, n * 4, st) != hipSuccess ||
-        hipMemsetAsync(pl->failed, 0, n * 4, st) != hipSuccess || hipMemsetAsync(pl->root_of, 0xff, n * 4, st) != hipSuccess ||
-        hipMemcpyAsync(pl->in_ptr, pl->h_in_ptr.data(), ((size_t)S + 1) * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-        mp_gbopd_free(pl);
-        return fail(MP_ERR_HIP, "mp_gbopd_create: initialising the planners failed");
+        if (made == MP_ERR_HIP) return fail(MP_ERR_HIP, "%s: initialising the planners failed", who);
+        return fail(MP_ERR_ALLOC, "%s: device allocation failed (%d planners x %d states, queue of %d entries each)", who, n_planners, S, q);
     }
     *out = pl;
     return MP_OK;
@@ -446,51 +349,29 @@ int mp_gbopd_plan(mp_ctx *ctx, mp_gbopd *pl, const int32_t *root_state, int32_t 
                   double accuracy, int32_t sampling_timeout, uint64_t *rng_state, int32_t *plans, int32_t *plan_len,
                   double *value_lower, double *value_upper, int64_t *env_steps, int64_t *updates, int32_t *status, int32_t mem)
 {
-    if (!ctx || !pl || !root_state || !rng_state) return fail(MP_ERR_ARG, "mp_gbopd_plan: NULL argument");
+    const char *const who = "mp_gbopd_plan";
+    if (!ctx || !pl || !root_state || !rng_state) return fail(MP_ERR_ARG, "%s: NULL argument", who);
     int rmem;
-    MP_TRY(wave_mem("mp_gbopd_plan", &mem, &rmem));
-    if (pl->ctx != ctx) return fail(MP_ERR_ARG, "mp_gbopd_plan: planners belong to another context");
-    if (pl->model->serial != pl->model_serial)
-        return fail(MP_ERR_ARG, "mp_gbopd_plan: the model's tables or action sets changed under a kept graph (bounds, parents and "
-                                "counters were built on the previous tables): free the planners and create new ones");
-    if (sampling_timeout < 0) return fail(MP_ERR_ARG, "mp_gbopd_plan: sampling_timeout = %d", sampling_timeout);
-    // (the reference never ends with a negative accuracy -- every pop appends its parents -- or with |gamma| >= 1, where the
-    // bounds grow for ever: a device call must end)
-    if (!(gamma > -1.0 && gamma < 1.0) || !(value_max == value_max) || !(accuracy >= 0.0))
-        return fail(MP_ERR_ARG, "mp_gbopd_plan: need -1 < gamma < 1, accuracy >= 0 and a number for 1 / (1 - gamma)");
+    MP_TRY(wave_mem(who, &mem, &rmem));
+    MP_TRY(graph_check_handle(ctx, pl, who, "bounds, parents and counters"));
+    if (sampling_timeout < 0) return fail(MP_ERR_ARG, "%s: sampling_timeout = %d", who, sampling_timeout);
+    MP_TRY(graph_check_numbers(who, gamma, value_max, accuracy));
     const int n = pl->n, S = pl->S, A = pl->A;
-    MP_TRY(wave_roots(ctx, "mp_gbopd_plan", root_state, n, S, mem));
+    MP_TRY(wave_roots(ctx, who, root_state, n, S, mem));
 
     GbArgs a;
-    a.n = n; a.S = S; a.A = A; a.K = budget > 0 ? budget / A : 0; // :120: budget // state.action_space.n
-    a.timeout = sampling_timeout; a.qcap = pl->qcap; a.E = pl->E;
-    a.max_pops = kGbMaxPops;
-    if (const char *e = getenv("MP_GBOPD_MAX_POPS")) { // test knob: a smaller limit (never a larger one)
-        const long v = atol(e);
-        if (v >= 1 && v < kGbMaxPops) a.max_pops = v;
-    }
-    a.gamma = gamma; a.vmax = value_max; a.accuracy = accuracy;
-    a.rec = pl->model->rec; a.in_ptr = pl->in_ptr;
-    a.lower = pl->lower; a.upper = pl->upper; a.index = pl->index; a.npar = pl->npar; a.created = pl->created; a.par = pl->par;
-    a.queue = pl->queue; a.n_created = pl->n_created; a.failed = pl->failed; a.root_of = pl->root_of; a.expanded = pl->expanded;
-    a.visits = pl->visits; a.updates = pl->updates; a.n_obs = pl->n_obs;
+    graph_args(pl, "MP_GBOPD_MAX_POPS", gamma, value_max, accuracy, &a);
+    a.K = budget > 0 ? budget / A : 0; // :120: budget // state.action_space.n
+    a.timeout = sampling_timeout;
+    a.rec = pl->model->rec; a.updates = pl->updates;
     WaveIo io(mem, rmem, n, root_state, &a.root_state, rng_state, &a.rng);
     io.add(WS_IO3, plans, &a.plans, (size_t)sampling_timeout);
-    io.add(WS_IO4, plan_len, &a.plan_len);
-    io.add(WS_IO5, status, &a.status);
-    io.add(WS_IO6, env_steps, &a.env_steps);
-    io.add(WS_IO7, updates, &a.n_updates);
-    io.add(WS_IO8, value_lower, &a.root_lower);
-    io.add(WS_IO9, value_upper, &a.root_upper);
+    graph_results_io(io, plan_len, status, env_steps, updates, value_lower, value_upper, &a);
     MP_TRY(wave_stage(ctx, io));
 
-    // both bounds in LDS while they are small (16 KiB: ten planners per CU); MP_GBOPD_LDS_BYTES moves the limit (0: never)
-    size_t lds_limit = 16 * 1024;
-    if (const char *e = getenv("MP_GBOPD_LDS_BYTES")) lds_limit = (size_t)atol(e);
-    if (lds_limit > 64 * 1024) lds_limit = 64 * 1024;
-    const size_t lds = (size_t)S * 16;
-    const bool use_lds = lds <= lds_limit;
-    MP_TRY(wave_launch(ctx, use_lds ? gbopd_kernel<true> : gbopd_kernel<false>, n, use_lds ? lds : 0, gbopd_form_name(use_lds), a));
+    // both bounds in LDS while they are small; MP_GBOPD_LDS_BYTES moves the limit
+    const bool use_lds = graph_use_lds("MP_GBOPD_LDS_BYTES", S);
+    MP_TRY(wave_launch(ctx, use_lds ? gbopd_kernel<true> : gbopd_kernel<false>, n, use_lds ? (size_t)S * 16 : 0, gbopd_form_name(use_lds), a));
     return wave_unstage(ctx, io);
 }
 
@@ -509,59 +390,27 @@ int mp_gbopd_export(mp_gbopd *pl, int32_t planner, int32_t cap, int32_t *n_nodes
                     uint8_t *expanded, int32_t *child, double *reward, int32_t *parent_ptr, int32_t *parent_idx,
                     int64_t *visits, int64_t *updates, int64_t *n_observations, int32_t *root)
 {
-    if (!pl || !n_nodes) return fail(MP_ERR_ARG, "mp_gbopd_export: NULL argument");
-    if (planner < 0 || planner >= pl->n) return fail(MP_ERR_ARG, "mp_gbopd_export: planner %d out of range", planner);
-    if (pl->model->serial != pl->model_serial)
-        return fail(MP_ERR_ARG, "mp_gbopd_export: the model's tables or action sets changed under a kept graph: the children and "
-                                "rewards of its nodes are no longer the model's");
-    MP_HIP(hipSetDevice(pl->ctx->device));
-    MP_HIP(hipStreamSynchronize(pl->ctx->stream));
-    const size_t S = (size_t)pl->S, A = (size_t)pl->A, r = (size_t)planner;
-    int32_t nc = 0, root_state = -1;
-    int64_t nobs = 0;
-    MP_HIP(hipMemcpy(&nc, pl->n_created + r, 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(&root_state, pl->root_of + r, 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(&nobs, pl->n_obs + r, 8, hipMemcpyDeviceToHost));
-    if (nc < 0 || (size_t)nc > S) return fail(MP_ERR_ARG, "mp_gbopd_export: bad node count %d", nc);
-    *n_nodes = nc;
-    if (n_observations) *n_observations = nobs;
-    if (cap < nc) return fail(MP_ERR_ARG, "mp_gbopd_export: capacity %d < %d nodes", cap, nc);
-    std::vector<double> hl(S), hu(S);
-    std::vector<int32_t> hidx(S), hnp(S), hcr(S), hpar((size_t)pl->E);
-    std::vector<uint8_t> hex(S);
-    MP_HIP(hipMemcpy(hl.data(), pl->lower + r * S, S * 8, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hu.data(), pl->upper + r * S, S * 8, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hidx.data(), pl->index + r * S, S * 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hnp.data(), pl->npar + r * S, S * 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hcr.data(), pl->created + r * S, S * 4, hipMemcpyDeviceToHost));
-    MP_HIP(hipMemcpy(hex.data(), pl->expanded + r * S, S, hipMemcpyDeviceToHost));
-    if (pl->E) MP_HIP(hipMemcpy(hpar.data(), pl->par + r * (size_t)pl->E, (size_t)pl->E * 4, hipMemcpyDeviceToHost));
-    if (visits) MP_HIP(hipMemcpy(visits, pl->visits + r * S, S * 8, hipMemcpyDeviceToHost));
-    if (updates) MP_HIP(hipMemcpy(updates, pl->updates + r * S, S * 8, hipMemcpyDeviceToHost));
-    if (root) *root = root_state >= 0 && (size_t)root_state < S ? hidx[(size_t)root_state] : -1;
+    const char *const who = "mp_gbopd_export";
+    GraphExport x;
+    MP_TRY(graph_export_begin(pl, who, "children and rewards", planner, cap, n_nodes, visits, n_observations, root, &x));
+    const size_t S = (size_t)pl->S, A = (size_t)pl->A;
+    if (updates) MP_HIP(hipMemcpy(updates, pl->updates + (size_t)planner * S, S * 8, hipMemcpyDeviceToHost));
     int32_t np_total = 0;
     if (parent_ptr) parent_ptr[0] = 0;
-    for (int32_t i = 0; i < nc; ++i) {
-        const int32_t s = hcr[(size_t)i];
-        if (s < 0 || (size_t)s >= S) return fail(MP_ERR_ARG, "mp_gbopd_export: node %d holds state %d", i, s);
+    for (int32_t i = 0; i < x.n_nodes; ++i) {
+        const int32_t s = x.created[(size_t)i];
+        if (s < 0 || (size_t)s >= S) return fail(MP_ERR_ARG, "%s: node %d holds state %d", who, i, s);
         if (state) state[i] = s;
-        if (lower) lower[i] = hl[(size_t)s];
-        if (upper) upper[i] = hu[(size_t)s];
-        if (expanded) expanded[i] = hex[(size_t)s];
+        if (lower) lower[i] = x.lower[(size_t)s];
+        if (upper) upper[i] = x.upper[(size_t)s];
+        if (expanded) expanded[i] = x.expanded[(size_t)s];
         for (size_t a = 0; a < A; ++a) { // children and rewards per listed action (slot = listing order), -1 elsewhere
             const Rec &rc = pl->hrec[(size_t)s * A + a];
-            const bool has = hex[(size_t)s] && (rc.flags & 4u);
-            if (child) child[(size_t)i * A + a] = has ? hidx[(size_t)rc.next] : -1;
+            const bool has = x.expanded[(size_t)s] && (rc.flags & 4u);
+            if (child) child[(size_t)i * A + a] = has ? x.index[(size_t)rc.next] : -1;
             if (reward) reward[(size_t)i * A + a] = has ? rc.reward : 0.0;
         }
-        const int32_t base = pl->h_in_ptr[(size_t)s], room = pl->h_in_ptr[(size_t)s + 1] - base;
-        const int32_t np = hnp[(size_t)s] < room ? hnp[(size_t)s] : room;
-        for (int32_t j = 0; j < np; ++j) {
-            const int32_t ps = hpar[(size_t)base + j];
-            if (parent_idx) parent_idx[np_total] = ps >= 0 && (size_t)ps < S ? hidx[(size_t)ps] : -1;
-            ++np_total;
-        }
-        if (parent_ptr) parent_ptr[i + 1] = np_total;
+        graph_export_parents(pl, x, i, s, parent_ptr, parent_idx, &np_total);
     }
     return MP_OK;
 }

@@ -176,6 +176,9 @@ class StochasticGraphBasedPlanner(GraphBasedPlanner):
     carries_state = True
     supports_per_episode_tables = False
     per_episode_kind = None
+    kept_with_graph = "counts and chance records"
+    queue_knob = "MP_GBOP_QUEUE"                # (mp_gbop_create reads its own knob)
+    steps_count_when_raising = True             # the reference's steps and draws up to a failing step are taken before it raises
 
     def __init__(self, env, config=None):
         self.tables = ThresholdTables()
@@ -243,18 +246,12 @@ class StochasticGraphBasedPlanner(GraphBasedPlanner):
         self._nodes = self._listing = None
         reach = planners.info()["max_count"] + episodes * horizon
         reward, transition = self.tables.upto(bound, cfg["horizon"], self.env.action_space.n, cfg["episodes"], reach)
-        try:
-            return planners.plan(root_states, episodes, horizon, cfg["gamma"], 1 / (1 - cfg["gamma"]), cfg["accuracy"],
-                                 int(cfg["sampling_timeout"]), reward[:reach], transition[:reach], rng_states)
-        except native.NativeError as e:
-            if "kept graph" in str(e):
-                raise NotImplementedError("graph-based planner: the environment's tables changed; the graph, counts and chance "
-                                          "records kept from earlier plans were built on the previous tables (call "
-                                          "planner.forget() to start a new planner on the new ones)") from e
-            raise
+        return self.on_kept_graph(lambda: planners.plan(
+            root_states, episodes, horizon, cfg["gamma"], 1 / (1 - cfg["gamma"]), cfg["accuracy"], int(cfg["sampling_timeout"]),
+            reward[:reach], transition[:reach], rng_states))
 
-    @staticmethod
-    def raise_for_status(status):
+    @classmethod
+    def raise_for_status(cls, status):
         status = np.asarray(status)
         if (status == native.ERR_GBOP_PLACEHOLDERS).any():
             raise ValueError(PLACEHOLDERS_MESSAGE)
@@ -262,34 +259,7 @@ class StochasticGraphBasedPlanner(GraphBasedPlanner):
             raise TypeError(REWARD_THRESHOLD_MESSAGE)
         if (status == native.ERR_GBOP_CHOICE_P).any():
             raise ValueError("probabilities do not sum to 1")                       # Generator.choice in get_plan (:156)
-        if (status == native.MP_ERR_ALLOC).any():                                   # (mp_gbop_create reads its own knob)
-            raise RuntimeError("graph-based planner: backup queue overflow on the device; raise the queue capacity "
-                               "(StochasticGraphBasedPlanner.queue_capacity, or MP_GBOP_QUEUE in the environment) and start "
-                               "again: the planner's graph is half updated and stays failed")
-        GraphBasedPlanner.raise_for_status(status)
-
-    def raise_for_result(self, out):
-        self.raise_for_status(out["status"])
-
-    def plan_batch(self, state, root_states, root_steps=None, rng_states=None, keep_actions=None, env_rng_states=None):
-        """``root_steps`` and ``keep_actions`` are accepted for the common interface ("subtree" equals "reset"), and so is
-        ``env_rng_states``: every episode's clone is re-seeded with a draw of the planner's generator (:239), so the
-        environment's own generator is never read."""
-        model = self.model_for(state)
-        n = len(root_states)
-        if rng_states is None:
-            rng_states = self.batch_rng_states(n)
-        out = self.plan_on(model, root_states, root_steps, rng_states)
-        # the reference's steps and draws up to a failing step are taken before it raises
-        self.env_steps += int(out["env_steps"].sum())
-        if not getattr(self, "defer_errors", False):               # (a batched caller checks its live slots only)
-            self.raise_for_result(out)
-        out["rng_states"] = rng_states
-        out["root_lower"], out["root_upper"] = out["value_lower"], out["value_upper"]
-        out["plans"] = out["plans"].reshape(n, 1)
-        self.relabel(out, model)
-        self.last, self._root, self._last_model = out, None, model
-        return out
+        super(StochasticGraphBasedPlanner, cls).raise_for_status(status)        # (a full queue first, under this class's names)
 
     def _plan_of(self, out, i=0):
         n = int(out["plan_len"][i])

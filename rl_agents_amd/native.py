@@ -1728,7 +1728,31 @@ class StateAwarePlanners(_Handle):
 
 
 
-class GraphBasedPlanners(_Handle):
+class _GraphPlanners(_Handle):
+    """What the batches of mp_gbopd and of mp_gbop planners share: a host-array plan's checks and an export's reshaping."""
+
+    def _roots_and_rng(self, root_state, rng_state):
+        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
+        if rs.shape[0] != self.n:
+            raise ValueError("one root state per planner ({}), got {}".format(self.n, rs.shape[0]))
+        _check_rng(rng_state, self.n, "n_planners")
+        return rs
+
+    @staticmethod
+    def _listed_first(listed, A):
+        """-> n_children and ``take(x, fill)``: x [n, A, ...] with every node's listed slots first, in slot order, then ``fill``."""
+        rank = np.argsort(~listed, axis=1, kind="stable")
+        n_children = listed.sum(axis=1).astype(np.int32)
+        keep = np.arange(A)[None, :] < n_children[:, None]
+
+        def take(x, fill):
+            tail = (1,) * (x.ndim - 2)
+            idx = np.broadcast_to(rank.reshape(rank.shape + tail), x.shape)
+            return np.where(keep.reshape(keep.shape + tail), np.take_along_axis(x, idx, axis=1), fill)
+        return n_children, take
+
+
+class GraphBasedPlanners(_GraphPlanners):
     """A batch of device-resident GraphBasedPlanner objects (mp_gbopd): the graph of observed states with both bounds, the
     parents in insertion order and the lifetime visit / update counters persist across plan() calls, as in the reference
     (tree_search/graph_based.py:87-94).  ``queue_cap``: entries of a planner's backup queue (None: the library's default)."""
@@ -1741,10 +1765,7 @@ class GraphBasedPlanners(_Handle):
 
     def plan(self, root_state, budget, gamma, value_max, accuracy, sampling_timeout, rng_state):
         """GraphBasedPlanner.plan for every planner (host arrays).  ``value_max``: the host's ``1 / (1 - gamma)``."""
-        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
-        if rs.shape[0] != self.n:
-            raise ValueError("one root state per planner ({}), got {}".format(self.n, rs.shape[0]))
-        _check_rng(rng_state, self.n, "n_planners")
+        rs = self._roots_and_rng(root_state, rng_state)
         t = int(sampling_timeout)
         out = _results("gbopd", self.n, L=t)
         self._call(MP_MEM_HOST, _ptr(rs), budget, gamma, value_max, accuracy, t, _ptr(rng_state), _result_ptrs("gbopd", out))
@@ -1784,11 +1805,7 @@ class GraphBasedPlanners(_Handle):
                                              _ptr(updates), C.byref(nobs), C.byref(root)))
         n = nn.value
         child, reward = child[:n], reward[:n]
-        listed = child >= 0
-        rank = np.argsort(~listed, axis=1, kind="stable")                  # the listed slots first, in slot order
-        n_children = listed.sum(axis=1).astype(np.int32)
-        keep = np.arange(A)[None, :] < n_children[:, None]
-        take = lambda x, fill: np.where(keep, np.take_along_axis(x, rank, axis=1), fill)  # noqa: E731
+        n_children, take = self._listed_first(child >= 0, A)
         slots = np.broadcast_to(np.arange(A, dtype=np.int32), (n, A))
         return dict(state=state[:n].copy(), lower=lower[:n].copy(), upper=upper[:n].copy(), expanded=expanded[:n].copy(),
                     n_children=n_children, child_action=take(slots, -1).astype(np.int32),
@@ -1797,7 +1814,7 @@ class GraphBasedPlanners(_Handle):
                     n_observations=np.asarray(nobs.value), root=np.asarray(root.value))
 
 
-class StochasticGraphBasedPlanners(_Handle):
+class StochasticGraphBasedPlanners(_GraphPlanners):
     """A batch of device-resident StochasticGraphBasedPlanner objects (mp_gbop): the graph of observed states with both
     bounds, counts and parents in insertion order, and per (state, listed action) the chance record with its
     ``max_next_states`` transition children persist across plan() calls, as in the reference
@@ -1821,10 +1838,7 @@ class StochasticGraphBasedPlanners(_Handle):
         """StochasticGraphBasedPlanner.plan for every planner (host arrays).  ``value_max``: the host's ``1 / (1 - gamma)``;
         the two threshold tables by LIFETIME count, ``[count - 1]``, at least ``info()["max_count"] + episodes * horizon``
         entries each."""
-        rs = np.ascontiguousarray(root_state, dtype=np.int32).reshape(-1)
-        if rs.shape[0] != self.n:
-            raise ValueError("one root state per planner ({}), got {}".format(self.n, rs.shape[0]))
-        _check_rng(rng_state, self.n, "n_planners")
+        rs = self._roots_and_rng(root_state, rng_state)
         out = _results("gbop", self.n)
         self._call(MP_MEM_HOST, _ptr(rs), episodes, horizon, gamma, value_max, accuracy, sampling_timeout, reward_thr_by_count,
                    transition_thr_by_count, _ptr(rng_state), _result_ptrs("gbop", out))
@@ -1874,16 +1888,7 @@ class StochasticGraphBasedPlanners(_Handle):
                                             [_ptr(pptr), _ptr(pidx), _ptr(visits), C.byref(nobs), C.byref(root)])))
         n = nn.value
         t = {k: v[:n] for k, v in t.items()}
-        listed = t["listed"] != 0
-        rank = np.argsort(~listed, axis=1, kind="stable")                  # the listed slots first, in slot order
-        n_children = listed.sum(axis=1).astype(np.int32)
-        keep = np.arange(A)[None, :] < n_children[:, None]
-
-        def take(x, fill):
-            idx = rank.reshape(rank.shape + (1,) * (x.ndim - 2))
-            mask = keep.reshape(keep.shape + (1,) * (x.ndim - 2))
-            return np.where(mask, np.take_along_axis(x, np.broadcast_to(idx, x.shape), axis=1), fill)
-
+        n_children, take = self._listed_first(t["listed"] != 0, A)
         # the reference's dict order of a chance node's children: the slots m .. K - 1, then 0 .. m - 1
         rot = (np.arange(K)[None, None, :] + t["chance_assigned"][:, :, None]) % K
         children = lambda x, fill: take(np.take_along_axis(x, rot, axis=2), fill)  # noqa: E731

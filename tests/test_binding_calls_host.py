@@ -27,7 +27,8 @@ A, S, M, HORIZON = 3, 10, 2, 4
 SIZES = (1, 2, 65)
 CTX_H, MODEL_H, POLICY_H, RNG_H, PLANNERS_H, DEVICE_RNG_PTR, STREAM = 0xC0, 0xD0, 0xE0, 0xF0, 0x1A0, 0x7AB000, 0x5EED
 SCALARS = (C.c_int, C.c_int32, C.c_int64, C.c_double)
-BYREF_VALUES = {"mp_saopd_info": (2, 6, 2, S), "mp_gbopd_info": (2, S, A, 4, 6), "mp_uct_tree_capacity": (7,),
+BYREF_VALUES = {"mp_saopd_info": (2, 6, 2, S), "mp_gbopd_info": (2, S, A, 4, 6), "mp_gbop_info": (2, S, A, 2, 4, 6, 9),
+                "mp_uct_tree_capacity": (7,),
                 "mp_uct_stoch_tree_capacity": (7,), "mp_ctx_device_faults": (3,)}
 NAMES = b"form_a form_b"
 
@@ -202,6 +203,9 @@ class Harness(object):
     def gbopd(self, n):
         return self.new(native.GraphBasedPlanners, ctx=self.ctx, model=self.model(), n=n, _h=C.c_void_p(PLANNERS_H))
 
+    def gbop(self, n):
+        return self.new(native.StochasticGraphBasedPlanners, ctx=self.ctx, model=self.model(), n=n, K=2, _h=C.c_void_p(PLANNERS_H))
+
     def rng(self, n):
         self.rng_state = self.lib.remember(np.arange(n * 6, dtype=np.uint64).reshape(n, 6) + 7)
         return self.rng_state
@@ -310,8 +314,14 @@ def _gbopd(h, n, **kw):
     return h.gbopd(n).plan(kw.pop("root_state", _roots(n)), 6, 0.9, 10.0, 0.01, HORIZON, **kw)
 
 
+def _gbop(h, n, **kw):
+    kw.setdefault("rng_state", h.rng(n))
+    return h.gbop(n).plan(kw.pop("root_state", _roots(n)), 5, HORIZON, 0.9, 10.0, 0.01, 2, kw.pop("reward_thr", [0.0] * 5),
+                          kw.pop("transition_thr", THR), **kw)
+
+
 PLANS = dict(uct=_uct, uct_stoch=_uct_stoch, opd=_opd, ropd=_ropd, olop=_olop, olop_stoch=_olop_stoch, brue=_brue, ss=_ss,
-             gape=_gape, gape_stoch=_gape_stoch, saopd=_saopd, gbopd=_gbopd)
+             gape=_gape, gape_stoch=_gape_stoch, saopd=_saopd, gbopd=_gbopd, gbop=_gbop)
 WITH_MODELS = ("uct", "opd", "olop", "brue", "ss", "gape")
 
 
@@ -374,6 +384,23 @@ def _gbopd_device(h):
     return _device_plan(h, h.gbopd(2).plan_device, [_tensor([1, 2], "int32"), 6, 0.9, 10.0, 0.01, HORIZON, "rng"],
                         dict(value_lower=("float64", ()), value_upper=("float64", ()), updates=("int64", ()),
                              status=("int32", ())))
+
+
+def _gbop_device(h, rng_device_only):
+    t = {k: _torch().zeros(2, dtype=getattr(_torch(), dtype)) for k, dtype in (
+        ("action", "int32"), ("key", "int32"), ("plan_len", "int32"), ("value_lower", "float64"), ("value_upper", "float64"),
+        ("env_steps", "int64"), ("pops", "int64"), ("status", "int32"))}
+    rng = _tensor(np.arange(12).reshape(2, 6).tolist(), "int64")
+    out = h.gbop(2).plan_device(_tensor([1, 2], "int32"), 5, HORIZON, 0.9, 10.0, 0.01, 2, [0.0] * 5, THR, rng,
+                                rng_device_only=rng_device_only, **t)
+    return out, {k: _array(v.numpy()) for k, v in sorted(t.items())}
+
+
+def _gbop_graph(n, state, lower, upper, expanded, count, listed, chance_count, chance_assigned, *rest):
+    """Some slots unlisted (node i lists the slots other than i % 3, node 4 none) and 0, 1 or 2 states assigned: with the two
+    children mp_gbop_info reports, an odd number rotates the child order."""
+    listed[:] = (np.arange(A)[None, :] != (np.arange(S) % 3)[:, None]) & (np.arange(S) != 4)[:, None]
+    chance_assigned[:] = (np.arange(S)[:, None] + np.arange(A)[None, :]) % 3
 
 
 def _env_step(h, stochastic, log):
@@ -546,6 +573,9 @@ def _cases():
     c["saopd_plan options"] = lambda h: _saopd(h, 2, accuracy=0.5, backup_aggregated_nodes=False, max_plan_len=3)
     c["saopd_plan wrong roots"] = lambda h: _saopd(h, 2, root_state=[1, 2, 3])
     c["gbopd_plan wrong roots"] = lambda h: _gbopd(h, 2, root_state=[1])
+    c["gbop_plan wrong roots"] = lambda h: _gbop(h, 2, root_state=[1])
+    c["gbop_plan unequal thresholds"] = lambda h: _gbop(h, 2, reward_thr=[0.0] * 4)
+    c["gbop_plan threshold arrays"] = lambda h: _gbop(h, 2, reward_thr=h.arr([0.0] * 5, np.float64), transition_thr=h.arr(THR, np.float64))
 
     c["uct_plan_device"] = _uct_device
     c["uct_plan_device root_steps"] = lambda h: _uct_device(h, root_steps=_tensor([1, 2], "int32"))
@@ -559,6 +589,8 @@ def _cases():
         c[which + " model_index"] = lambda h, which=which: _opd_device(h, which, model_index=_tensor([3, 1], "int32"))
     c["saopd plan_device"] = _saopd_device
     c["gbopd plan_device"] = _gbopd_device
+    c["gbop plan_device"] = lambda h: _gbop_device(h, False)
+    c["gbop plan_device rng only"] = lambda h: _gbop_device(h, True)
 
     c["uct_tree"] = lambda h: h.ctx.uct_tree(1)
     c["uct_tree cap"] = lambda h: h.ctx.uct_tree(1, cap=9)
@@ -582,6 +614,9 @@ def _cases():
     c["saopd export whole arena"] = lambda h: h.saopd(2).export(0, current_tree_only=False)
     c["gbopd info"] = lambda h: h.gbopd(2).info()
     c["gbopd export"] = lambda h: h.gbopd(2).export(1)
+    c["gbop info"] = lambda h: h.gbop(2).info()
+    c["gbop export"] = lambda h: _hooked(h, "mp_gbop_export", _gbop_graph, lambda: h.gbop(2).export(1))
+    c["gbop export every slot listed"] = lambda h: h.gbop(2).export(0)
     c["uct_step_tree"] = lambda h: h.ctx.uct_step_tree([1, 2])
     c["uct_step_tree array"] = lambda h: h.ctx.uct_step_tree(h.arr([1, 2], np.int32))
     c["uct_step_tree tensor"] = lambda h: h.ctx.uct_step_tree(_tensor([1, 2], "int32"))
@@ -708,12 +743,16 @@ def _cases():
     c["pack_rows"] = lambda h: _rows(h, False)
     c["unpack_rows"] = lambda h: _rows(h, True)
     for name, owner in (("model", lambda h: h.model()), ("policy", lambda h: h.policy(None)), ("device rng", lambda h: h.device_rng(2)),
-                        ("saopd", lambda h: h.saopd(2)), ("gbopd", lambda h: h.gbopd(2))):
+                        ("saopd", lambda h: h.saopd(2)), ("gbopd", lambda h: h.gbopd(2)), ("gbop", lambda h: h.gbop(2))):
         c[name + " close"] = lambda h, owner=owner: _closed(h, owner(h))
         c[name + " close after context"] = lambda h, owner=owner: (lambda o: (setattr(h.ctx, "_h", None), _closed(h, o)))(owner(h))[1]
     c["saopd create"] = lambda h: (lambda p: (p.n, p._h.value, h.keep.append(p)))(native.StateAwarePlanners(h.ctx, h.model(), 2))[:2]
     c["gbopd create"] = lambda h: (lambda p: (p.n, p._h.value, h.keep.append(p)))(native.GraphBasedPlanners(h.ctx, h.model(), 2))[:2]
     c["gbopd create queue"] = lambda h: (lambda p: (p.n, h.keep.append(p)))(native.GraphBasedPlanners(h.ctx, h.model(), 2, 32))[:1]
+    c["gbop create"] = lambda h: (lambda p: (p.n, p.K, p._h.value, h.keep.append(p)))(
+        native.StochasticGraphBasedPlanners(h.ctx, h.model(native.MODE_SPARSE, b=2), 2, 3))[:3]
+    c["gbop create queue"] = lambda h: (lambda p: (p.n, p.K, h.keep.append(p)))(
+        native.StochasticGraphBasedPlanners(h.ctx, h.model(), 2, 3, 32))[:2]
 
     c["seed_sequence_states"] = lambda h: native.seed_sequence_states([1, 2 ** 40], 3, 2)
     c["seed_sequence_states no entropy"] = lambda h: native.seed_sequence_states((), 3, 2)

@@ -85,38 +85,76 @@ def test_every_golden_case_through_the_c_abi(z):
                 c.close()
             plans += int(case["n_plans"])
             continue
-        env = case_env(case)
-        planner = agent_factory(env, case_config(case)).planner
-        model = planner.model_for(env)
-        order = getattr(model, "action_order", None)
-        K, gamma = int(case["max_next_states_count"]), float(case["gamma"])
-        episodes, horizon, A = int(case["episodes"]), int(case["horizon"]), case["mdp/reward"].shape[1]
-        handle = native.StochasticGraphBasedPlanners(planner.models.ctx, model, 1, K)
-        tol = BOUND_TOL / (1 - gamma)
-        steps = 0
-        for i in range(int(case["n_plans"])):
-            reach = handle.info()["max_count"] + episodes * horizon
-            rthr, tthr = tables(str(case["threshold"]), str(case["transition_threshold"]), horizon, A, episodes, reach)
-            rng = case["plan{}/rng_before".format(i)].copy().reshape(1, 6)
-            out = handle.plan([int(case["roots"][i])], episodes, horizon, gamma, 1 / (1 - gamma), float(case["accuracy"]),
-                              int(case["sampling_timeout"]), rthr, tthr, rng)
-            tag = (name, i)
-            assert_form(planner.models.ctx, FORM[str(case["mdp/mode"])] + "_lds")
-            assert planner.models.ctx.last_kernel_variant() in native.gbop_form_names()
-            error = str(case["plan{}/error".format(i)])
-            assert int(out["status"][0]) == (STATUS[error + "/" + name] if error else native.MP_OK), tag
-            assert np.array_equal(rng[0], case["plan{}/rng_after".format(i)]), tag
-            assert device_plan(out, 0, order) == golden_plan(case, i), tag
-            steps += int(out["env_steps"][0])
-            assert steps == int(case["plan{}/env_steps".format(i)]), tag
-            ref = golden_graph(case, i)
-            assert gb.compare_listing(device_listing(handle, model), ref, tol) == [], tag
-            if not error:
-                r = int(ref["root"])
-                assert abs(out["value_lower"][0] - ref["lower"][r]) <= tol and abs(out["value_upper"][0] - ref["upper"][r]) <= tol, tag
-            plans += 1
-        handle.close()
+        plans += len(plan_golden_case(case, name)[1])
     assert plans == sum(int(z["gbop/{}/n_plans".format(n)]) for n in names(z))
+
+
+def plan_golden_case(case, name, n_plans=None, placement="lds"):
+    """Every plan of a golden case (or its first ``n_plans``) on one kept planner through the C ABI, each held to the golden:
+    kernel form, status, generator record, plan, steps, the exported graph and the root's bounds.
+    -> the handle's info and, per plan, (outputs, generator record, listing)."""
+    env = case_env(case)
+    planner = agent_factory(env, case_config(case)).planner
+    model = planner.model_for(env)
+    order = getattr(model, "action_order", None)
+    K, gamma = int(case["max_next_states_count"]), float(case["gamma"])
+    episodes, horizon, A = int(case["episodes"]), int(case["horizon"]), case["mdp/reward"].shape[1]
+    handle = native.StochasticGraphBasedPlanners(planner.models.ctx, model, 1, K)
+    tol = BOUND_TOL / (1 - gamma)
+    steps, records = 0, []
+    for i in range(int(case["n_plans"]) if n_plans is None else n_plans):
+        reach = handle.info()["max_count"] + episodes * horizon
+        rthr, tthr = tables(str(case["threshold"]), str(case["transition_threshold"]), horizon, A, episodes, reach)
+        rng = case["plan{}/rng_before".format(i)].copy().reshape(1, 6)
+        out = handle.plan([int(case["roots"][i])], episodes, horizon, gamma, 1 / (1 - gamma), float(case["accuracy"]),
+                          int(case["sampling_timeout"]), rthr, tthr, rng)
+        tag = (name, i)
+        assert_form(planner.models.ctx, FORM[str(case["mdp/mode"])] + "_" + placement)
+        assert planner.models.ctx.last_kernel_variant() in native.gbop_form_names()
+        error = str(case["plan{}/error".format(i)])
+        assert int(out["status"][0]) == (STATUS[error + "/" + name] if error else native.MP_OK), tag
+        assert np.array_equal(rng[0], case["plan{}/rng_after".format(i)]), tag
+        assert device_plan(out, 0, order) == golden_plan(case, i), tag
+        steps += int(out["env_steps"][0])
+        assert steps == int(case["plan{}/env_steps".format(i)]), tag
+        ref = golden_graph(case, i)
+        lst = device_listing(handle, model)
+        assert gb.compare_listing(lst, ref, tol) == [], tag
+        if not error:
+            r = int(ref["root"])
+            assert abs(out["value_lower"][0] - ref["lower"][r]) <= tol and abs(out["value_upper"][0] - ref["upper"][r]) <= tol, tag
+        records.append((out, rng, lst))
+    info = handle.info()
+    handle.close()
+    return info, records
+
+
+def test_each_knob_moves_only_its_own_planner(z, monkeypatch):
+    """The shared host helpers take the knob's name from their caller: GBOP-D's three leave a GBOP planner as it is -- the
+    default ring, both bounds in LDS, and no pop limit of 1: the golden's statuses and the unknobbed run's bits -- and GBOP's
+    own move it."""
+    for knob in ("MP_GBOPD_QUEUE", "MP_GBOPD_LDS_BYTES", "MP_GBOPD_MAX_POPS", "MP_GBOP_QUEUE", "MP_GBOP_LDS_BYTES", "MP_GBOP_MAX_POPS"):
+        monkeypatch.delenv(knob, raising=False)
+    name = next(n for n in names(z) if n != "no_listed_action" and int(z["gbop/{}/n_plans".format(n)]) >= 2 and not any(
+        str(z["gbop/{}/plan{}/error".format(n, i)]) for i in range(2)))
+    case = golden_case(z, name)
+    info, plain = plan_golden_case(case, name, 2)
+    assert info["queue_cap"] == 65536
+    assert all(int(out["status"][0]) == native.MP_OK for out, _, _ in plain)
+    assert max(int(out["pops"][0]) for out, _, _ in plain) > 1           # (a pop limit of 1 would end these plans)
+    monkeypatch.setenv("MP_GBOPD_QUEUE", "100")
+    monkeypatch.setenv("MP_GBOPD_LDS_BYTES", "0")
+    monkeypatch.setenv("MP_GBOPD_MAX_POPS", "1")
+    info, other = plan_golden_case(case, name, 2)                       # (the LDS form is asserted for every plan in there)
+    assert info["queue_cap"] == 65536
+    for (out, rng, lst), (out_o, rng_o, lst_o) in zip(plain, other):
+        assert all(out[k].tobytes() == out_o[k].tobytes() for k in out) and np.array_equal(rng, rng_o)
+        assert gb.compare_listing(lst_o, lst, 0.0) == []
+    monkeypatch.setenv("MP_GBOP_QUEUE", "100")
+    assert plan_golden_case(case, name, 0)[0]["queue_cap"] == 128       # (a new batch: nothing is planned on the small ring)
+    monkeypatch.delenv("MP_GBOP_QUEUE")
+    monkeypatch.setenv("MP_GBOP_LDS_BYTES", "0")
+    assert plan_golden_case(case, name, 2, placement="global")[0]["queue_cap"] == 65536
 
 
 def test_every_golden_case_through_the_agent(z):

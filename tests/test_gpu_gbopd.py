@@ -81,41 +81,107 @@ def object_listing(planner):
     return out
 
 
+def plan_golden_case(case, name, n_plans=None):
+    """Every plan of a golden case (or its first ``n_plans``) on one kept planner through the C ABI, each held to the golden:
+    status, generator record, plan, the exported graph by bits, the root's bounds, len(observations).
+    -> the handle's info and, per plan, (outputs, generator record, listing, kernel form)."""
+    env = golden_env(case)
+    planner = agent_factory(env, golden_config(case)).planner
+    model = planner.model_for(env)
+    order = getattr(model, "action_order", None)
+    handle = native.GraphBasedPlanners(planner.models.ctx, model, 1)
+    gamma = float(case["gamma"])
+    observations, records = 0, []
+    for i in range(int(case["n_plans"]) if n_plans is None else n_plans):
+        rng = case["plan{}/rng_before".format(i)].copy().reshape(1, 6)
+        out = handle.plan([int(case["roots"][i])], int(case["budget"]), gamma, 1 / (1 - gamma), float(case["accuracy"]),
+                          int(case["sampling_timeout"]), rng)
+        form = planner.models.ctx.last_kernel_variant()
+        tag = (name, i)
+        assert out["status"][0] == 0, tag
+        assert np.array_equal(rng[0], case["plan{}/rng_after".format(i)]), tag
+        plan = out["plans"][0, :out["plan_len"][0]]
+        plan = plan if order is None else np.asarray(order)[plan]
+        assert plan.tolist() == case["plan{}/plan".format(i)].tolist(), tag
+        assert (out["plans"][0, out["plan_len"][0]:] == -1).all(), tag
+        ref = golden_graph(case, i)
+        lst = device_listing(handle, model)
+        assert gr.same_listing(lst, ref) == [], tag
+        r = int(ref["root"])
+        assert np.array_equal(out["value_lower"], ref["lower"][r:r + 1]) and np.array_equal(out["value_upper"], ref["upper"][r:r + 1]), tag
+        observations += int(out["env_steps"][0])
+        assert observations == int(ref["n_observations"]), tag
+        records.append((out, rng, lst, form))
+    info = handle.info()
+    assert info["n_planners"] == 1
+    handle.close()
+    return info, records
+
+
+def cases_that_construct(z):
+    return [(name, case) for name, case in ((n, golden_case(z, n)) for n in names(z)) if not str(case["construct_error"])]
+
+
 def test_every_golden_case_through_the_c_abi(z):
-    plans = 0
-    for name in names(z):
-        case = golden_case(z, name)
-        if str(case["construct_error"]):
-            continue
-        env = golden_env(case)
-        planner = agent_factory(env, golden_config(case)).planner
-        model = planner.model_for(env)
-        order = getattr(model, "action_order", None)
-        handle = native.GraphBasedPlanners(planner.models.ctx, model, 1)
-        gamma = float(case["gamma"])
-        observations = 0
-        for i in range(int(case["n_plans"])):
-            rng = case["plan{}/rng_before".format(i)].copy().reshape(1, 6)
-            out = handle.plan([int(case["roots"][i])], int(case["budget"]), gamma, 1 / (1 - gamma), float(case["accuracy"]),
-                              int(case["sampling_timeout"]), rng)
-            tag = (name, i)
-            assert out["status"][0] == 0, tag
-            assert np.array_equal(rng[0], case["plan{}/rng_after".format(i)]), tag
-            plan = out["plans"][0, :out["plan_len"][0]]
-            plan = plan if order is None else np.asarray(order)[plan]
-            assert plan.tolist() == case["plan{}/plan".format(i)].tolist(), tag
-            assert (out["plans"][0, out["plan_len"][0]:] == -1).all(), tag
-            ref = golden_graph(case, i)
-            lst = device_listing(handle, model)
-            assert gr.same_listing(lst, ref) == [], tag
-            r = int(ref["root"])
-            assert np.array_equal(out["value_lower"], ref["lower"][r:r + 1]) and np.array_equal(out["value_upper"], ref["upper"][r:r + 1]), tag
-            observations += int(out["env_steps"][0])
-            assert observations == int(ref["n_observations"]), tag
-            plans += 1
-        assert handle.info()["n_planners"] == 1
-        handle.close()
+    plans = sum(len(plan_golden_case(case, name)[1]) for name, case in cases_that_construct(z))
     assert plans >= 60
+
+
+def test_both_placements_of_every_golden_case_by_bits(z, monkeypatch):
+    """Every golden case over all its plans on the kept graph with both bounds in LDS and, by MP_GBOPD_LDS_BYTES=0, in global
+    memory: each is held to the golden inside plan_golden_case, and to the other here -- every output, the generator records and
+    the export."""
+    monkeypatch.delenv("MP_GBOPD_LDS_BYTES", raising=False)
+    for name, case in cases_that_construct(z):
+        _, lds = plan_golden_case(case, name)
+        monkeypatch.setenv("MP_GBOPD_LDS_BYTES", "0")
+        _, glob = plan_golden_case(case, name)
+        monkeypatch.delenv("MP_GBOPD_LDS_BYTES")
+        assert len(lds) == len(glob) == int(case["n_plans"])
+        for i, ((out, rng, lst, form), (out_g, rng_g, lst_g, form_g)) in enumerate(zip(lds, glob)):
+            assert (form, form_g) == ("gbopd_wave_lds", "gbopd_wave_global"), (name, i)
+            assert sorted(out) == sorted(out_g)
+            for k in out:
+                assert out[k].dtype == out_g[k].dtype and out[k].tobytes() == out_g[k].tobytes(), (name, i, k)
+            assert np.array_equal(rng, rng_g), (name, i)
+            assert gr.same_listing(lst_g, lst) == [], (name, i)
+
+
+def test_each_knob_moves_only_its_own_planner(z, monkeypatch):
+    """The shared host helpers take the knob's name from their caller: GBOP's three leave a GBOP-D planner as it is -- the
+    default ring, both bounds in LDS, and no pop limit of 1: status 0 and the golden's bits -- and GBOP-D's own move it."""
+    for knob in ("MP_GBOPD_QUEUE", "MP_GBOPD_LDS_BYTES", "MP_GBOPD_MAX_POPS", "MP_GBOP_QUEUE", "MP_GBOP_LDS_BYTES", "MP_GBOP_MAX_POPS"):
+        monkeypatch.delenv(knob, raising=False)
+    name, case = next((n, c) for n, c in cases_that_construct(z) if int(c["n_plans"]) >= 2)
+    info, plain = plan_golden_case(case, name, 2)
+    assert info["queue_cap"] == 65536 and [r[3] for r in plain] == ["gbopd_wave_lds"] * 2
+    assert max(int(r[0]["updates"][0]) for r in plain) > 1              # (a pop limit of 1 would end these plans)
+    monkeypatch.setenv("MP_GBOP_QUEUE", "100")
+    monkeypatch.setenv("MP_GBOP_LDS_BYTES", "0")
+    monkeypatch.setenv("MP_GBOP_MAX_POPS", "1")
+    info, other = plan_golden_case(case, name, 2)
+    assert info["queue_cap"] == 65536 and [r[3] for r in other] == ["gbopd_wave_lds"] * 2
+    for (out, rng, lst, _), (out_o, rng_o, lst_o, _) in zip(plain, other):
+        assert all(out[k].tobytes() == out_o[k].tobytes() for k in out) and np.array_equal(rng, rng_o)
+        assert gr.same_listing(lst_o, lst) == []
+    monkeypatch.setenv("MP_GBOPD_QUEUE", "100")
+    assert plan_golden_case(case, name, 0)[0]["queue_cap"] == 128       # (a new batch; its ring is too small to plan this case on)
+    monkeypatch.delenv("MP_GBOPD_QUEUE")
+    monkeypatch.setenv("MP_GBOPD_LDS_BYTES", "0")
+    info, own = plan_golden_case(case, name, 2)
+    assert info["queue_cap"] == 65536 and [r[3] for r in own] == ["gbopd_wave_global"] * 2
+
+
+@pytest.mark.parametrize("S,form", [(1024, "gbopd_wave_lds"), (1025, "gbopd_wave_global")])
+def test_the_natural_lds_limit_without_a_knob(S, form, monkeypatch):
+    """16 * S bytes against the 16 KiB limit with no knob set: the last size whose bounds live in LDS and the first whose do
+    not, both against the restatement."""
+    monkeypatch.delenv("MP_GBOPD_LDS_BYTES", raising=False)
+    tab = generators.random_deterministic(S, 3, seed=76)
+    cfg = dict(budget=90, gamma=0.9, accuracy=1e-3, sampling_timeout=20)
+    roots = [np.asarray([0, S - 1], np.int32), np.asarray([S - 1, 7], np.int32)]
+    planner, _ = check_against_restatement(tab, None, None, cfg, roots)
+    assert planner.models.ctx.last_kernel_variant() == form
 
 
 def test_every_golden_case_and_the_episodes_through_the_agent(z):

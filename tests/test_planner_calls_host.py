@@ -5,6 +5,8 @@ A recording stand-in takes the place of ``planner.models`` (a ``.ctx`` and a ``.
 planners call.  Each call is bound against the real method's signature and recorded in order -- method name, scalars, arrays
 as dtype / shape / content -- and answered with a fixed pattern: plans of zeros, ``plan_len`` 1, ``env_steps`` = root index + 1,
 every generator record advanced by 3.  A case may ask for a status code or negative BRUE plans on one root of one plan call.
+The two graph-based planners construct ``native.GraphBasedPlanners`` / ``native.StochasticGraphBasedPlanners`` themselves, so
+these classes have a recording stand-in of their own (GraphPlanners), whose calls are recorded with the context's.
 What the planner returns, the generator records, ``planner.env_steps``, whether ``planner.last`` is the result, the tree claim,
 the log lines and any exception are recorded with the calls.  The record of every case must equal tests/planner_calls.json, which
 ``python tests/test_planner_calls_host.py --write`` writes (the package first on PYTHONPATH is the one recorded).
@@ -191,6 +193,61 @@ class Ctx(object):
     def _vi_solve_batch(self, model, gamma, iterations, rtol, atol):
         i, s, a = np.meshgrid(np.arange(model.n_models), np.arange(model.S_each), np.arange(model.A), indexing="ij")
         return ((i * 7 + s * 3 + a * 5) % 11) / 10.0, np.full(model.n_models, 2, np.int32)
+
+
+class GraphPlanners(object):
+    """The recording stand-in of native.GraphBasedPlanners, which the graph-based planner constructs itself: ``create``, every
+    ``plan``, ``info`` and ``close`` are bound against the real class and recorded with the context's calls.  A plan is answered
+    as Ctx._plan answers one (``plans`` shows a relabelling); the context's ``fail`` may also name ``error`` (a NativeError's
+    message) or ``set`` (result name -> the failing root's value)."""
+    real, family, label = native.GraphBasedPlanners, "gbopd", "gbopd"
+
+    def __init__(self, ctx, *args, **kwargs):
+        self.ctx, self.max_count = ctx, 0
+        named = self._record("create", self.real.__init__, (ctx,) + args, kwargs)
+        self.model, self.n, self.K = named["model"], int(named["n_planners"]), int(named.get("max_next_states", 0))
+
+    def _record(self, name, method, args, kwargs):
+        bound = inspect.signature(method).bind(self, *args, **kwargs)       # (TypeError as the binding's)
+        bound.apply_defaults()
+        named = dict(bound.arguments)
+        named.pop("self")
+        named.pop("ctx", None)
+        self.ctx.calls.append([self.label + "." + name, {k: describe(v) for k, v in named.items()}])
+        return named
+
+    def plan(self, *args, **kwargs):
+        named = self._record("plan", self.real.plan, args, kwargs)
+        ctx, n, rng = self.ctx, self.n, named["rng_state"]
+        fail = ctx.fail if ctx.fail and ctx.fail["call"] == ctx.plan_calls else None
+        ctx.plan_calls += 1
+        if fail and "error" in fail:
+            raise native.NativeError(native.MP_ERR_ARG, fail["error"])
+        out = {}
+        for key, dtype, tail, _ in native.RESULTS[self.family]:
+            out[key] = np.zeros((n,) + tuple(int(named["sampling_timeout"]) for _ in tail), dtype)
+        out["plans"][:] = (np.arange(out["plans"].size).reshape(out["plans"].shape) + 1) % self.model.A
+        out["plan_len"][:] = 1
+        out["env_steps"][:] = np.arange(n) + 1
+        out["value_lower"][:], out["value_upper"][:] = np.arange(n) / 4.0, np.arange(n) / 4.0 + 0.5
+        for key, value in (fail or {}).get("set", {}).items():
+            out[key][fail["root"]] = value
+        self.max_count += int(named.get("episodes", 0)) * int(named.get("horizon", 0))
+        assert isinstance(rng, np.ndarray) and rng.dtype == np.uint64 and rng.size == 6 * n
+        rng += np.uint64(RNG_STEP)
+        return out
+
+    def info(self):
+        self.ctx.calls.append([self.label + ".info", {}])
+        return dict(n_planners=self.n, n_states=self.model.S, n_actions=self.model.A, max_next_states=self.K, queue_cap=4,
+                    n_edges=6, max_count=self.max_count)
+
+    def close(self):
+        self.ctx.calls.append([self.label + ".close", {}])
+
+
+class StochasticGraphPlanners(GraphPlanners):
+    real, family, label = native.StochasticGraphBasedPlanners, "gbop", "gbop"
 
 
 class Models(object):
@@ -612,10 +669,111 @@ def batch_case_without_records(make_agent, make_env, n):
 
 CASES.update(gape_cases())
 
+GBOPD_CFG = dict(budget=7, gamma=0.8, accuracy=0.1, sampling_timeout=3)
+GBOP_CFG = dict(budget=8, episodes=2, horizon=3, gamma=0.8, accuracy=0.1, sampling_timeout=2, max_next_states_count=2,
+                upper_bound=dict(type="kullback-leibler", time="global", threshold="0*np.log(time)",
+                                 transition_threshold="0.1*np.log(time) + count"))
+KEPT_GRAPH = "mp_plan: the model's tables or action sets changed under a kept graph (built on the previous tables)"
+
+
+def graph_case(make_agent, make_env, sizes=(3,), fail=None, between=None, defer=False):
+    """One plan_batch per entry of ``sizes`` (that many roots) on one graph-based planner; ``between(ctx, planner, k)`` runs
+    before call k > 0.  Recorded beside plan_record's: the reference's plan of every root where the planner reads one out of a
+    result (``_plan_of``) and the counts the threshold strings were evaluated for."""
+    def case():
+        ctx = Ctx(fail)
+        env = make_env()
+        planner = with_stand_in(make_agent(env), ctx)
+        if defer:
+            planner.defer_errors = True
+        records = []
+        for k, n in enumerate(sizes):
+            if k > 0 and between is not None:
+                between(ctx, planner, k)
+            rng = rng_records(n)
+            rec = plan_record(ctx, planner, lambda: planner.plan_batch(env, list(range(1, n + 1)), [k] * n, rng_states=rng), rng)
+            if "result" in rec and hasattr(planner, "_plan_of"):
+                rec["plan_of"] = [planner._plan_of(planner.last, i) for i in range(n)]
+            if hasattr(planner, "tables"):
+                rec["evaluations"] = planner.tables.evaluations
+            records.append(rec)
+        return dict(plans=records), ctx
+    return case
+
+
+def forget(ctx, planner, k):
+    planner.forget()
+
+
+def plan_on_one_mdp_per_root(make_agent, make_env):
+    def case():
+        ctx = Ctx()
+        env = make_env()
+        planner = with_stand_in(make_agent(env), ctx)
+        rng = rng_records(2)
+        return dict(plans=[plan_record(ctx, planner, lambda: planner.plan_on(planner.model_for(env), [1, 2], None, rng,
+                                                                             model_index=[0, 1]), rng)]), ctx
+    return case
+
+
+def graph_cases():
+    """GraphBasedPlanner (GBOP-D) and StochasticGraphBasedPlanner (GBOP): the handle they keep, what reaches the binding, every
+    status with the exception it maps to and ``planner.env_steps`` afterwards (GBOP adds the steps before it raises, GBOP-D only
+    when it does not raise)."""
+    from rl_agents_amd.agents.tree_search.graph_based import GraphBasedPlannerAgent
+    from rl_agents_amd.gbop import StochasticGraphBasedPlannerAgent
+    cases = {}
+    statuses = dict(alloc=native.MP_ERR_ALLOC, no_action=native.MP_ERR_GBOPD_NO_ACTION, diverged=native.MP_ERR_GBOPD_DIVERGED,
+                    other=OTHER)
+    for tag, cls, cfg, first, ordered, more in (
+            ("gbopd", GraphBasedPlannerAgent, GBOPD_CFG, plain_env, ordered_env, {}),
+            ("gbop", StochasticGraphBasedPlannerAgent, GBOP_CFG, stochastic_env, functools.partial(stochastic_env, ordered=True),
+             dict(placeholders=native.ERR_GBOP_PLACEHOLDERS, reward_threshold=native.ERR_GBOP_REWARD_THRESHOLD,
+                  choice_p=native.ERR_GBOP_CHOICE_P))):
+        agent = agent_of(cls, cfg)
+        cases[tag + "_kept_handle"] = graph_case(agent, first, sizes=(3, 3, 2, 2), between=lambda ctx, planner, k: (
+            planner.forget() if k == 3 else None))
+        cases[tag + "_one_root"] = graph_case(agent, first, sizes=(1,))
+        cases[tag + "_ordered"] = graph_case(agent, ordered, sizes=(3,))
+        cases[tag + "_masked_table"] = graph_case(agent, masked_env, sizes=(3,))
+        cases[tag + "_defer_errors"] = graph_case(agent, first, sizes=(3, 3), fail=dict(call=1, root=1, set=dict(status=OTHER)),
+                                                  defer=True)
+        for name, status in dict(statuses, **more).items():
+            cases["{}_status_{}".format(tag, name)] = graph_case(agent, first, sizes=(3, 3),
+                                                                 fail=dict(call=1, root=1, set=dict(status=status)))
+        cases[tag + "_tables_changed"] = graph_case(agent, first, sizes=(3, 3), fail=dict(call=1, error=KEPT_GRAPH))
+        cases[tag + "_other_native_error"] = graph_case(agent, first, sizes=(3,), fail=dict(call=0, error="mp_plan: out of memory"))
+        cases["each_" + tag] = per_episode_case(agent, three(plain_env))
+    gbop = functools.partial(agent_of, StochasticGraphBasedPlannerAgent)
+    cases.update({
+        "gbop_table": graph_case(gbop(GBOP_CFG), plain_env, sizes=(3,)),
+        "gbop_sparse": graph_case(gbop(GBOP_CFG), functools.partial(stochastic_env, "sparse"), sizes=(3,)),
+        "gbop_one_mdp_per_root": plan_on_one_mdp_per_root(gbop(GBOP_CFG), stochastic_env),
+        "gbop_other_bound": graph_case(gbop(dict(GBOP_CFG, upper_bound=dict(GBOP_CFG["upper_bound"], type="hoeffding"))),
+                                       stochastic_env),
+        "gbop_no_next_state": graph_case(gbop(dict(GBOP_CFG, max_next_states_count=0)), stochastic_env),
+        "gbop_33_next_states": graph_case(gbop(dict(GBOP_CFG, max_next_states_count=33)), stochastic_env),
+        "gbop_half_a_next_state": graph_case(gbop(dict(GBOP_CFG, max_next_states_count=1.5)), stochastic_env),
+        "gbop_next_states_changed": graph_case(gbop(GBOP_CFG), stochastic_env, sizes=(3, 3), between=lambda ctx, planner, k: (
+            planner.config.update(max_next_states_count=3))),
+        "gbop_threshold_raises": graph_case(gbop(dict(GBOP_CFG, upper_bound=dict(
+            GBOP_CFG["upper_bound"], transition_threshold="1/(count - 8)"))), stochastic_env, sizes=(3, 3)),
+        "gbop_plan_len_0": graph_case(gbop(GBOP_CFG), stochastic_env, fail=dict(call=0, root=1, set=dict(plan_len=0, plans=-1))),
+        "gbop_plan_len_2": graph_case(gbop(GBOP_CFG), stochastic_env, fail=dict(call=0, root=1, set=dict(plan_len=2, key=7))),
+        "gbop_plan_len_2_placeholder": graph_case(gbop(GBOP_CFG), stochastic_env,
+                                                  fail=dict(call=0, root=2, set=dict(plan_len=2, key=-2))),
+    })
+    return cases
+
+
+CASES.update(graph_cases())
+
 
 def run_case(name, mp):
     mp.setattr(runtime, "get_context", lambda *a, **k: Ctx.current)
     mp.setattr(native, "seed_sequence_states", lambda entropy, first_key, count: rng_records(count) + np.uint64(first_key))
+    mp.setattr(native, "GraphBasedPlanners", GraphPlanners)
+    mp.setattr(native, "StochasticGraphBasedPlanners", StochasticGraphPlanners)
     log = Log()
     root = logging.getLogger("rl_agents_amd")
     level = root.level
