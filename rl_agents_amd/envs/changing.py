@@ -7,7 +7,7 @@ import copy
 import numpy as np
 
 from . import generators
-from .finite_mdp import _TABLE_TOKENS, FiniteMDPEnv, MaskedFiniteMDPEnv
+from .finite_mdp import _TABLE_TOKENS, FiniteMDPEnv, MaskedFiniteMDPEnv, OrderedMaskedFiniteMDPEnv
 from .highway_like import HighwayLikeEnv
 
 
@@ -46,6 +46,11 @@ class ScheduledTableEnv(_ScheduledTables, FiniteMDPEnv):
 class MaskedScheduledTableEnv(_ScheduledTables, MaskedFiniteMDPEnv):
     """The same over a :class:`MaskedFiniteMDPEnv`: ``tables[0]["available"]`` ([S][A] flags) restricts the action sets of
     every step (``get_available_actions``), as a grid of one shape does."""
+
+
+class OrderedMaskedScheduledTableEnv(_ScheduledTables, OrderedMaskedFiniteMDPEnv):
+    """The same over an :class:`OrderedMaskedFiniteMDPEnv`: ``tables[0]["available"]`` and ``tables[0]["listing_order"]`` (a
+    permutation of the action ids) hold for every step; the restriction and the order live on the env object, as on highway."""
 
 
 class ScheduledModelsEnv(ScheduledTableEnv):

@@ -71,6 +71,29 @@ def restrict_and_renormalise(tables, available):
     return masked / den[..., None]
 
 
+def boltzmann_prior_rows(q, order, temperature, available):
+    """The rows the loop uploads for a ``ValueIterationAgent`` prior: ``q`` [..., S, A] in DEVICE columns (column j = action
+    ``order[j]``; ``order`` None: ascending) -> softmax(Q / temperature) [..., S, A] in device columns, restricted to
+    ``available`` (bool [S, A], device columns, or None) and renormalised.  The sequential agent computes ``exp`` and the row
+    sum over the actions in ACTION-ID order (``ValueIterationAgent.policy_table``) and permutes afterwards
+    (``MCTSWithPriorPolicyAgent.policy_tables``): a sum over permuted columns differs in the last bits for any order but a swap
+    of the first two, so ``q`` goes back to action-id order first -- as a contiguous array, since numpy's ``exp`` and its
+    8-accumulator row sum are what they are on contiguous rows only."""
+    q = np.asarray(q, dtype=np.float64)
+    if order is not None:
+        order = np.asarray(order, dtype=np.int64)
+        inverse = np.empty_like(order)
+        inverse[order] = np.arange(len(order))
+        q = np.ascontiguousarray(q[..., inverse])
+    z = np.exp((q - q.max(axis=-1, keepdims=True)) / temperature)
+    tables = z / z.sum(axis=-1, keepdims=True)
+    if order is not None:
+        tables = tables[..., order]
+    if available is not None:
+        tables = restrict_and_renormalise(tables, available)
+    return tables
+
+
 class PerEpisodeEvaluation(object):
     def __init__(self, envs, agent, sim_seed=0, max_steps=None, kind=None):
         """``envs``: N environments exposing a deterministic finite MDP (``.mdp`` or ``to_finite_mdp()``) of one shape;
@@ -358,10 +381,10 @@ class PerEpisodeEvaluation(object):
         if type(pa) is ValueIterationAgent:
             # its act() re-converts and re-solves (value_iteration.py:29-35) and its distribution is Boltzmann over that Q table
             # (ValueIterationAgent.policy_table): N solves in one launch, the softmax rows in one numpy expression -- numpy's own
-            # exp and its own summation order over the |A| entries of a row, exactly as the single agent computes them
+            # exp and its own summation order over the |A| entries of a row IN ACTION-ID ORDER, exactly as the single agent
+            # computes them (boltzmann_prior_rows)
             q, _ = self.ctx.vi_solve_batch(model, pa.config["gamma"], pa.config["iterations"])
-            z = np.exp((q - q.max(axis=2, keepdims=True)) / pa.config.get("temperature", 1.0))
-            tables = z / z.sum(axis=2, keepdims=True)
+            return boltzmann_prior_rows(q, getattr(model, "action_order", None), pa.config.get("temperature", 1.0), self._available)
         else:
             if getattr(self, "_prior_cache", None) is None:
                 self._prior_cache = np.zeros((n, s, a))
