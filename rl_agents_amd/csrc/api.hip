@@ -15,6 +15,7 @@
 #include "each_host.hpp"
 #include "libm_sincos.hpp"
 #include "seed_sequence.hpp"
+#include "uct_term_table.hpp"
 
 namespace mp {
 
@@ -171,7 +172,7 @@ __global__ void pack_records(int S, int A, const int32_t *__restrict__ T, const 
 // model's whole arrays)
 __global__ void pack_records_range(int s0, int ns, int A, const int32_t *__restrict__ T, const double *__restrict__ R,
                                    const uint8_t *__restrict__ term, const uint8_t *__restrict__ avail, Rec *__restrict__ rec,
-                                   uint16_t *__restrict__ t16)
+                                   uint16_t *__restrict__ t16, uint16_t *__restrict__ t16s)
 {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= (long)ns * A) return;
@@ -183,6 +184,7 @@ __global__ void pack_records_range(int s0, int ns, int A, const int32_t *__restr
     r.reward = R[i];
     rec[i] = r;
     if (t16) t16[i] = (uint16_t)((uint32_t)r.next | (term && term[r.next] ? 0x8000u : 0u));
+    if (t16s) t16s[i] = uct_term_word(r.next, term && term[s], term && term[r.next], true);   // (uct_term_table.hpp)
 }
 
 // joint batch models (mp_model_load_joint_batch / mp_model_update_joint_tables): `count` sets of M tables, staged as the caller
@@ -234,7 +236,7 @@ __global__ void scatter_rows(int n_rows, int A, const int32_t *__restrict__ rows
 // ... and the records of exactly those rows (terminal flags unchanged)
 __global__ void pack_records_rows(int n_rows, int A, const int32_t *__restrict__ rows, const int32_t *__restrict__ T,
                                   const double *__restrict__ R, const uint8_t *__restrict__ term, const uint8_t *__restrict__ avail,
-                                  Rec *__restrict__ rec, uint16_t *__restrict__ t16)
+                                  Rec *__restrict__ rec, uint16_t *__restrict__ t16, uint16_t *__restrict__ t16s)
 {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= (long)n_rows * A) return;
@@ -247,6 +249,7 @@ __global__ void pack_records_rows(int n_rows, int A, const int32_t *__restrict__
     r.reward = R[i];
     rec[i] = r;
     if (t16) t16[i] = (uint16_t)((uint32_t)r.next | (term && term[r.next] ? 0x8000u : 0u));
+    if (t16s) t16s[i] = uct_term_word(r.next, term && term[s], term && term[r.next], true);   // (uct_term_table.hpp)
 }
 
 // root i of a batch model: global state = model_index[i] * Sb + local state (mp_uct_plan_models / mp_opd_plan_models)
@@ -975,6 +978,16 @@ int load_table_common(mp_ctx *ctx, int32_t M, int32_t S, int32_t A, const std::v
             return bail(fail(MP_ERR_ALLOC, "mp_model_load_table: hipMalloc failed"));
         hipLaunchKernelGGL(pack_t16, dim3((unsigned)((sa + 255) / 256)), dim3(256), 0, ctx->stream, S, A, m->T, m->term,
                            m->t16);
+        // ... and the copy whose bit 15 is terminal[s] of the state a record leaves (uct_term_table.hpp), built here
+        {
+            const size_t t16s_bytes = (((size_t)sa * 2 + 15) & ~(size_t)15) + 16;
+            std::vector<uint16_t> src_tab(t16s_bytes / 2, 0);
+            uct_term_table_fill(S, A, t32.data(), terminal, true, src_tab.data());
+            if (hipMalloc(&m->t16s, t16s_bytes) != hipSuccess)
+                return bail(fail(MP_ERR_ALLOC, "mp_model_load_table: hipMalloc failed"));
+            if (hipMemcpy(m->t16s, src_tab.data(), t16s_bytes, hipMemcpyHostToDevice) != hipSuccess)
+                return bail(fail(MP_ERR_HIP, "mp_model_load_table: upload failed"));
+        }
         // the LDS-resident form of model 0 (uct.hip ENV_TABLE_LDSR): rewards as 8-bit indices into the table of their
         // distinct values (by bit pattern: -0.0 and 0.0, or two NaNs, stay what they are) -- when there are at most 256
         m->rmap = new std::unordered_map<uint64_t, int>();
@@ -1182,7 +1195,7 @@ int mp_model_update_tables(mp_model *m, int32_t first, int32_t count, const int6
         drop_compact_rewards(m);
     }
     hipLaunchKernelGGL(pack_records_range, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (int)g0, (int)ns, A, m->T, m->R,
-                       m->term, (const uint8_t *)m->avail, m->rec, m->t16);
+                       m->term, (const uint8_t *)m->avail, m->rec, m->t16, m->t16s);
     MP_HIP(hipGetLastError());
     MP_HIP(hipEventRecord(m->upd_done, s));
     m->upd_pending = true;
@@ -1254,7 +1267,7 @@ int mp_model_update_rows(mp_model *m, int32_t n_rows, const int32_t *rows, const
                        m->term, compact && keep_compact ? m->r8 : (uint8_t *)nullptr);
     if (!terminal) {
         hipLaunchKernelGGL(pack_records_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n_rows, A, drows, m->T, m->R, m->term,
-                           (const uint8_t *)m->avail, m->rec, m->t16);
+                           (const uint8_t *)m->avail, m->rec, m->t16, m->t16s);
     } else {
         // a record carries terminal[next]: every record of the owning MDPs follows (one launch per MDP; many owners: all)
         std::sort(owners.begin(), owners.end());
@@ -1262,12 +1275,12 @@ int mp_model_update_rows(mp_model *m, int32_t n_rows, const int32_t *rows, const
         if (owners.size() > 64) {
             const long sa = (long)m->S * A;
             hipLaunchKernelGGL(pack_records_range, dim3((unsigned)((sa + 255) / 256)), dim3(256), 0, s, 0, m->S, A, m->T, m->R, m->term,
-                               (const uint8_t *)m->avail, m->rec, m->t16);
+                               (const uint8_t *)m->avail, m->rec, m->t16, m->t16s);
         } else {
             const long sa = (long)Sb * A;
             for (int32_t b : owners)
                 hipLaunchKernelGGL(pack_records_range, dim3((unsigned)((sa + 255) / 256)), dim3(256), 0, s, b * Sb, Sb, A, m->T, m->R,
-                                   m->term, (const uint8_t *)m->avail, m->rec, m->t16);
+                                   m->term, (const uint8_t *)m->avail, m->rec, m->t16, m->t16s);
         }
     }
     MP_HIP(hipGetLastError());
@@ -1639,6 +1652,7 @@ int mp_model_free(mp_model *m)
     if (m->T) hipFree(m->T);
     if (m->rec && m->rec != m->rec_all) hipFree(m->rec);
     if (m->t16) hipFree(m->t16);
+    if (m->t16s) hipFree(m->t16s);
     if (m->r8) hipFree(m->r8);
     if (m->rdict) hipFree(m->rdict);
     if (m->sa_cost) hipFree(m->sa_cost);

@@ -238,6 +238,7 @@ struct mp_model {
     // rec_all and avail are [M][S][A], term_all [M][S]; rec and term ALIAS model 0's part of rec_all / term_all
     bool joint_batch = false;
     uint16_t *t16 = nullptr; // model 0 as {bit15 = terminal[next], next}, [S*A]; only when S < 32768
+    uint16_t *t16s = nullptr; // the same with bit15 = terminal[s] of the state left (uct_term_table.hpp); wherever t16 is
     uint8_t *r8 = nullptr;   // model 0's rewards as indices into rdict, [S*A] (padded to 16 B); only with t16 and <= 256 distinct rewards
     double *rdict = nullptr; // the distinct reward values (bit patterns), [256]
     int n_rdict = 0;

@@ -27,6 +27,11 @@
 #define MP_PCG_HAS_ADDC 1
 #endif
 #endif
+// -DMP_PCG_NO_C1=0 builds Pcg64W::advance with the column-1 carry compare that its multiplier never needs, for A/B runs
+// (profiles/uct_lean_trip.md)
+#ifndef MP_PCG_NO_C1
+#define MP_PCG_NO_C1 1
+#endif
 
 namespace mp {
 
@@ -344,8 +349,15 @@ struct Pcg64W {
         const uint32_t m0 = 0x9FCCF645u, m1 = 0x4385DF64u, m2 = 0x1FC65DA4u, m3 = 0x2360ED05u;
         const uint64_t A0 = mad64(w0, m0, 0);                        // column 0
         const uint64_t B = mad64(w0, m1, A0 >> 32);                  // column 1: w0 m1 + carry (no overflow)
-        const uint64_t A1 = mad64(w1, m0, B);                        //           + w1 m0 (65 bits: the carry is c1)
+        const uint64_t A1 = mad64(w1, m0, B);                        //           + w1 m0 (65 bits in general: the carry is c1)
+#if MP_PCG_NO_C1
+        // w0 m1 + (A0 >> 32) + w1 m0 <= (2^32 - 1)(m0 + m1 + 1) < 2^64 while m0 + m1 < 2^32: for this multiplier column 1 never
+        // carries (profiles/uct_pcg_words.md, section 2), and the compare that would find the carry is not made
+        static_assert((uint64_t)m0 + (uint64_t)m1 < (1ULL << 32), "Pcg64W: column 1 can carry for this multiplier, keep the compare");
+        const uint32_t c1 = 0u;
+#else
         const uint32_t c1 = A1 < B ? 1u : 0u;                        // (a compare the compiler sees: the hazard note of Pcg64::mul_add)
+#endif
         const uint64_t C = mad64(w0, m2, A1 >> 32);                  // column 2 without c1 (it lands in word 3, below)
         const uint64_t D = mad64(w1, m1, C);
         const uint64_t A2 = mad64(w2, m0, D);

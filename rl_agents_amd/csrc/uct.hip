@@ -263,6 +263,28 @@ constexpr bool uct_pcg_words_form(int AT, int ENV, bool SP, bool MK, int IL, boo
 {
     return ENV != ENV_CARTPOLE && !QD;
 }
+// THE LEAN TRIP (profiles/uct_lean_trip.md): vector instructions of that rollout's trip of two env steps which the result does
+// not need, each part behind a macro of its own (default on; =0 builds the part as it was, for A/B runs):
+//   MP_UCT_TERM_TABLE   the terminal rule is in the staged table, not in the kernel (uct_term_table.hpp): one compare of the
+//                       record's bit 15 per step, in the descent as well; no `cur_term`, no select by done_on_next.  The
+//                       one-lane LDS-resident form only (the four-lane form, uct_lone_kernel and uct_row_kernel stage the
+//                       next-state table and keep the rule); the host hands the form the table of the model's rule
+//   MP_UCT_LEAN_INDEX   the record word is a 32-bit value from its load on: no zero-extension of the 15-bit next state
+//   MP_UCT_LEAN_COUNT   one add to the step counter per trip, compared with the last step in both steps
+//   MP_PCG_NO_C1        pcg64.hpp: no compare for the column-1 carry of Pcg64W
+#ifndef MP_UCT_TERM_TABLE
+#define MP_UCT_TERM_TABLE 1
+#endif
+#ifndef MP_UCT_LEAN_INDEX
+#define MP_UCT_LEAN_INDEX 1
+#endif
+#ifndef MP_UCT_LEAN_COUNT
+#define MP_UCT_LEAN_COUNT 1
+#endif
+constexpr bool uct_term_table_form(int ENV, bool QD)
+{
+    return MP_UCT_TERM_TABLE != 0 && ENV == ENV_TABLE_LDSR && !QD;
+}
 // SP: the prior and the rollout distribution are rows of per-state tables (mcts_with_prior.py:47-62).  The env is
 // deterministic, so the state a node is reached in is a function of its action sequence and the prior stored in a
 // child at expansion (mcts.py:237-246) is prior[state of the parent][action]: it is looked up with the state the
@@ -494,6 +516,14 @@ void uct_kernel(UctArgs p)
     using RollGen = typename std::conditional<PCGW, Pcg64W, Pcg64>::type;
     auto roll_gen = [](const Pcg64 &x) { if constexpr (PCGW) return Pcg64W::from(x); else return x; };
     auto roll_gen_commit = [](Pcg64 &x, const RollGen &y) { if constexpr (PCGW) y.state_to(x); else x = y; };
+    // THE LEAN TRIP (above).  TERMTAB: bit 15 of a staged record is the terminal flag the model's rule stops on -- terminal[next]
+    // with done_on_next, terminal[s] of the state the step leaves without it (uct_term_table.hpp) -- so a step's test is that bit
+    // under either rule.  The flag is a function of the state (mp_model_load_table takes terminal[S] and nothing per action), so
+    // terminal[s] read off a record of s is what `cur_term` carried: root_term for the first step of a plan or of a kept tree's
+    // next plan, the previous record's bit 15 afterwards.
+    constexpr bool TERMTAB = uct_term_table_form(ENV, QD);
+    constexpr bool LEANI = MP_UCT_LEAN_INDEX != 0 && PCGW && LDSR;
+    constexpr bool LEANH = MP_UCT_LEAN_COUNT != 0 && PCGW;
     uint64_t g4_lo = 0, g4_hi = 0;          // QD: inc * G_4, the additive term of a four-step jump of this root's generator
     if (QD || (CART && p.rep_shift >= 2)) g.inc_g4(g4_lo, g4_hi);
     uint64_t g16_lo = 0, g16_hi = 0;        // CartPole, sixteen replicas: inc * G_16
@@ -610,7 +640,7 @@ void uct_kernel(UctArgs p)
         double x4[4] = {x0[0], x0[1], x0[2], x0[3]};
         int node = 0, depth = 0;
         bool terminal = false;
-        bool cur_term = root_term; // terminal[s] of the state the next action is taken from
+        [[maybe_unused]] bool cur_term = root_term; // terminal[s] of the state the next action is taken from (TERMTAB: in the table)
         double total = 0.0;
         uint32_t cur_mask = mask0; // MK: listed actions of the state the descent is in
         if (!RC) PATH_PUT(0, tree.root_handle());
@@ -780,8 +810,12 @@ void uct_kernel(UctArgs p)
                 const uint32_t e = t16[idx];
                 reward = rdict[r8[idx]];
                 const bool next_term = (e & 0x8000u) != 0;
-                terminal = p.done_on_next ? next_term : cur_term;
-                cur_term = next_term;
+                if constexpr (TERMTAB) {
+                    terminal = next_term;   // (bit 15 is the flag of the model's rule: the table staged is the rule's)
+                } else {
+                    terminal = p.done_on_next ? next_term : cur_term;
+                    cur_term = next_term;
+                }
                 s = (int32_t)(e & 0x7fffu);
             } else if (MK) {
                 const uint4 q0 = p.pol_frec[(size_t)idx * (1 + NQ32)]; // the (s, a) record with the policy's masks
@@ -1351,8 +1385,12 @@ void uct_kernel(UctArgs p)
                 }
             }
             // one rollout step; returns true when the rollout must stop after it
-            auto step = [&](double &r_mine, double &g_mine, const double r_prev, const double g_prev, bool add_prev,
+            // LEANH: `h` holds the step count BEHIND the trip, two more than before its first step, one add per trip; step "a"
+            // (second_tag false) is step h - 2 and stops at the limit if h - 1 >= hmax, step "b" is step h - 1 and stops if
+            // h >= hmax.  The loop below leaves h as the number of steps made, as the other forms do.
+            auto step = [&](auto second_tag, double &r_mine, double &g_mine, const double r_prev, const double g_prev, bool add_prev,
                             const RollGen &gcur, RollGen &gspec, uint64_t &unext) -> bool {
+                constexpr int SECOND = decltype(second_tag)::value ? 1 : 0;
                 // searchsorted(cdf, u, 'right') = #{a : cdf[a] <= u} = #{a : thr[a] <= k}
                 int act = 0;
                 if constexpr (ATAB) {
@@ -1384,7 +1422,7 @@ void uct_kernel(UctArgs p)
                 } else {
                     for (int a = 0; a < A; ++a) act += thr[a] <= u ? 1 : 0;
                 }
-                g_mine = gpow[h];
+                g_mine = LEANH ? gpow[h - 2 + SECOND] : gpow[h];
                 // 32-bit record index (S * |A| < 2^31): one multiply-add instead of a 64-bit address chain; a 24-bit one where the
                 // form bounds S * |A| below 2^24 (the LDS-resident model: three bytes per (s, a) in at most 160 KB)
                 const unsigned ridx = PCGW && LDSR ? __umul24((unsigned)s, (unsigned)A) + (unsigned)act : (unsigned)(s * A + act);
@@ -1396,7 +1434,11 @@ void uct_kernel(UctArgs p)
                     total += g_mine * 1.0;
                 } else if (LDSR) {
                     const unsigned idx = ridx;
-                    const uint32_t e = t16[idx];
+                    uint32_t e = t16[idx];
+                    // LEANI: the word as the load leaves it, 32 bits with the upper half clear.  (What the compiler sees as a
+                    // 16-bit value it masks in 16 bits and then extends for the index: an `and` with 0xffff behind the `and` with
+                    // 0x7fff.  No instruction here.)
+                    if constexpr (LEANI) asm("" : "+v"(e));
                     r_mine = rdict[r8[idx]];
                     gspec = gcur;
                     unext = gspec.next64() >> USH;
@@ -1404,9 +1446,14 @@ void uct_kernel(UctArgs p)
                     // (the first step of a rollout has no previous reward: r_prev = g_prev = 0.0 then, and adding +0.0 changes no bit
                     // of a return that is never -0 -- no select on `add_prev`)
                     total += g_prev * r_prev;
-                    const bool next_term = (e & 0x8000u) != 0;
-                    term_h = p.done_on_next ? next_term : cur_term;
-                    cur_term = next_term;
+                    // (LEANI: the word is below 2^16, so bit 15 is one unsigned compare; a test of the bit is an `and` and a compare)
+                    const bool next_term = LEANI ? e > 0x7fffu : (e & 0x8000u) != 0;
+                    if constexpr (TERMTAB) {
+                        term_h = next_term;
+                    } else {
+                        term_h = p.done_on_next ? next_term : cur_term;
+                        cur_term = next_term;
+                    }
                     s = (int32_t)(e & 0x7fffu);
                 } else if (SP && NTH <= 4 && p.pol_packed) {
                     // one 16-byte record: the 10 top bits of each threshold ride in the spare bits of next / flags
@@ -1449,20 +1496,26 @@ void uct_kernel(UctArgs p)
                 }
                 // (st and steps_taken advance with h: added once after the rollout; the env's step limit is folded into hmax --
                 // three vector instructions fewer in a step that issues ~50)
-                ++h;
 #ifdef MP_PROFILE
                 ++n_roll;
 #endif
-                return term_h || h >= hmax;
+                if constexpr (LEANH) {
+                    return term_h || (SECOND ? h >= hmax : h > hmax);
+                } else {
+                    ++h;
+                    return term_h || h >= hmax;
+                }
             };
             while (true) {
                 uint64_t un;
-                if (step(r_a, g_a, r_b, g_b, have_b, ga, gb, un)) { stopped_in_a = true; break; }
+                if constexpr (LEANH) h += 2;
+                if (step(std::false_type{}, r_a, g_a, r_b, g_b, have_b, ga, gb, un)) { stopped_in_a = true; break; }
                 u = un;
                 have_b = true;
-                if (step(r_b, g_b, r_a, g_a, true, gb, ga, un)) { stopped_in_a = false; break; }
+                if (step(std::true_type{}, r_b, g_b, r_a, g_a, true, gb, ga, un)) { stopped_in_a = false; break; }
                 u = un;
             }
+            if constexpr (LEANH) h -= stopped_in_a ? 1 : 0;
             if (LDSR) total += stopped_in_a ? g_a * r_a : g_b * r_b;
             roll_gen_commit(g, stopped_in_a ? ga : gb); // the generator whose draw was consumed last
             st += h - depth; steps_taken += h - depth;
@@ -3178,6 +3231,12 @@ static int uct_form(mp_ctx *ctx, const UctPlan &c, bool cont, UctChoice *ch, Uct
     a->action_table = knobs.action_table && ch->form == UF_LDSR && ch->lanes == 64 && !c.pol &&
                       ch->lds + kUctBalBytes + kUctActBytes <= kLdsBytes &&
                       uct_action_table_form(model->A, ENV_TABLE_LDSR, false, false, ch->tree_il, false) ? 1 : 0;
+    // the one-lane LDS-resident form tests bit 15 of a record under either terminal rule (THE LEAN TRIP): the table whose bit is
+    // the model's rule.  Every other LDS form stages the next-state table and applies the rule itself.
+    if (uct_term_table_form(ENV_TABLE_LDSR, false) && ch->form == UF_LDSR && !model->done_on_next) {
+        if (!model->t16s) return fail(MP_ERR_ARG, "mp_uct_plan: the model has no source-rule transition table");
+        a->t16 = model->t16s;
+    }
     a->lanes = ch->lanes; a->waves = ch->waves; a->rep_shift = ch->rep_shift;
     a->jump = nullptr;
     const UctForm form = ch->form;
