@@ -720,6 +720,35 @@ int mp_gape_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const
                             int32_t *status, double *child_lower, double *child_upper, int64_t *child_count,
                             int32_t *best_challenger, int32_t mem);
 const char *mp_gape_stoch_form_names(void);
+/* mp_gape_plan_stochastic on a batch model of deterministic tables (mp_model_load_table_batch) with one MDP per root (see
+ * mp_gape_plan_models): model_index int32 [n_roots], root_state LOCAL; several roots may share an MDP.  After model_index the
+ * arguments and the results are mp_gape_plan_stochastic's.  Equal to MDPGapE.plan (tree_search/mdp_gape.py:94-110 with
+ * max_next_states_count = max_next_states in 1..32) of one agent per MDP, and to mp_gape_plan_stochastic on that table alone, bit
+ * for bit: every result, the generator records and every array of the exported tree; at max_next_states 1 also to
+ * mp_gape_plan_models.  The availability table is read per GLOBAL state (mp_model_set_available), so every MDP may list other
+ * actions; the done rule is the model's.  MP_ERR_MODE for a single table, a dense, sparse, joint, joint-batch or row-block model
+ * (mp_gape_plan_stochastic itself keeps refusing batch models); MP_ERR_ARG for a model_index outside [0, N) or a local state
+ * outside [0, S_each) in host arrays (device arrays: the clamp-and-count of mp_opd_plan_models), and under the conditions of
+ * mp_gape_plan_stochastic.  Nodes hold GLOBAL states: mp_gape_stoch_tree_export serves the trees afterwards, its `state` column
+ * (and a decision node's `action`) global.  mp_last_kernel_variant records one of mp_gape_stoch_each_form_names:
+ * "gape_stoch_each_lds" (the root's S_each * |A| records in LDS behind path[2 * horizon + 1]) / "gape_stoch_each_global", each
+ * also with "_slots" (part of no other list). */
+int mp_gape_plan_stochastic_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index,
+                                   const int32_t *root_state, int32_t episodes, int32_t horizon, int32_t max_next_states,
+                                   double gamma, double accuracy, int32_t continuation, int32_t n_actions_env,
+                                   const int32_t *action_column, const double *thr_by_count, const double *transition_thr_by_count,
+                                   const double *value_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans,
+                                   int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps, int32_t *status,
+                                   double *child_lower, double *child_upper, int64_t *child_count, int32_t *best_challenger,
+                                   int32_t mem);
+const char *mp_gape_stoch_each_form_names(void);
+/* The form mp_gape_plan_stochastic_models chooses for a call of this description, on the host alone (no device, no ctx; the
+ * function the launch code calls), with the six outputs of mp_gape_each_form_info: the kernel's own LDS array is
+ * path[2 * horizon + 1] int32, 16-byte rounded.  The LDS form is the default where it was measured faster beyond the spread of
+ * repeated medians (each_host.hpp), which is where mp_gape_plan_models has it: a workgroup of at most 160 KiB / 16 bytes, from
+ * 256 roots on, while all the roots' workgroups are resident at once; else the global form.  MP_EACH_MODEL=lds takes the LDS
+ * form for any table that fits the 160 KiB of a CU, MP_EACH_MODEL=global the global one. */
+int mp_gape_stoch_each_form_info(int32_t S_each, int32_t A, int32_t horizon, int32_t n_roots, int32_t cus, int64_t *out);
 /* Tree of root `root` after the last mp_gape_plan_stochastic, BREADTH FIRST over decision and chance nodes, a node's children in
  * the reference's dict order (a chance node's: the placeholders left in number order, then the observed states by first
  * observation, mdp_gape.py:281).  The fields of mp_gape_tree_export; `parent` is a position of this listing; the action of a
@@ -1193,7 +1222,9 @@ int mp_last_kernel_ms(mp_ctx *ctx, double *ms, int32_t *n_launches);
  *   Sparse        "ss_wave_lds", "ss_wave_global" (the frames of the recursion in LDS / in a global workspace); one MDP per root
  *   Sampling      (mp_ss_plan_models): "ss_each_lds" / "ss_each_global"
  *   MDP-GapE      "gape_global", then "_slots"; one MDP per root (mp_gape_plan_models): "gape_each_lds" / "gape_each_global", then
- *                 "_slots" (listed by mp_gape_form_names / mp_gape_each_form_names, not by mp_kernel_form_names)
+ *                 "_slots" (listed by mp_gape_form_names / mp_gape_each_form_names, not by mp_kernel_form_names); with transition
+ *                 bounds "gape_stoch_{table,dense,sparse}", one MDP per root "gape_stoch_each_lds" / "gape_stoch_each_global",
+ *                 then "_slots" (mp_gape_stoch_form_names / mp_gape_stoch_each_form_names)
  *   OPD           "opd_any" (more than 64 actions); "opd_lds" / "opd_ldsx" (bounds in LDS / the parent map in HBM), then "_gen"
  *                 (the main loop for arbitrary bounds), then "_chain" (the closing pass on the node array);
  *                 "opd_wide_sib" / "opd_wide_cls" (bounds in HBM, sibling / residue-class layout), then "_small" (at most two

@@ -20,12 +20,15 @@ dict order and ``max_expectation_under_constraint`` with its Newton iteration ru
 
 Refused by both: ``step_strategy: "subtree"`` (NotImplementedError at ``reset``); a bound type other than
 ``"kullback-leibler"`` (ValueError: the reference only logs an error and plans on infinite bounds).  By the stochastic planner
-also ``max_next_states_count`` above 32 (NotImplementedError) and one model per episode.
+also ``max_next_states_count`` above 32 (NotImplementedError).
 
 One model per episode: ``MDPGapE.plan_on(..., model_index=...)`` plans every root on its own deterministic table of a batch model
 (``mp_gape_plan_models``).  ``PerEpisodeEvaluation`` refuses ``MDPGapEAgent`` unasked, as it always has
 (``per_episode_kind = None``), and runs it on request: ``PerEpisodeEvaluation(envs, agent, kind="gape")``
-(``per_episode_kind_on_request``).  Out of scope: ``mp_gape_plan_stochastic`` on batch models, kept subtrees, K > 32.
+(``per_episode_kind_on_request``).  ``StochasticMDPGapE.plan_on(..., model_index=...)`` does the same with
+``max_next_states_count`` 1..32 (``mp_gape_plan_stochastic_models``); the loop runs it under the names
+``PerEpisodeStochasticMDPGapE`` / ``PerEpisodeStochasticMDPGapEAgent`` with ``kind="gape_stoch"``, and refuses
+``StochasticMDPGapEAgent`` itself under any kind, as it always has.  Out of scope: kept subtrees, K > 32.
 """
 import logging
 
@@ -334,9 +337,11 @@ class MDPGapEAgent(OLOPAgent):
 
 build_gape_stoch_tree = build_gape_tree       # (the name the stochastic planner's trees were built under)
 
-# StochasticMDPGapE, StochasticMDPGapEAgent and PLACEHOLDERS_MESSAGE live in rl_agents_amd/gape_stochastic.py (which imports this
-# module) and are served from here by name, so that an agent config names them beside MDPGapEAgent.
-_STOCHASTIC_NAMES = ("StochasticMDPGapE", "StochasticMDPGapEAgent", "PLACEHOLDERS_MESSAGE")
+# StochasticMDPGapE, StochasticMDPGapEAgent, their per-episode names and PLACEHOLDERS_MESSAGE live in
+# rl_agents_amd/gape_stochastic.py (which imports this module) and are served from here by name, so that an agent config names
+# them beside MDPGapEAgent.
+_STOCHASTIC_NAMES = ("StochasticMDPGapE", "StochasticMDPGapEAgent", "PLACEHOLDERS_MESSAGE", "PerEpisodeStochasticMDPGapE",
+                     "PerEpisodeStochasticMDPGapEAgent")
 
 
 def __getattr__(name):

@@ -70,18 +70,46 @@ struct GapeStochArgs {
     double *val;             // [slots][cap][2] value_upper, value_lower of every node
     int32_t *n_nodes_out;
     GapeResults out;
+    int Sb;                  // states of one MDP of a batch model (mp_gape_plan_stochastic_models); the other entry leaves it 0
 };
 
+// EACH (mp_gape_plan_stochastic_models: a batch model of deterministic tables, one MDP per root, the roots' states GLOBAL -- nodes
+// keep global states, and the availability flag and the done bits are those of the global state's records).  GS_WHOLE is the
+// kernel of mp_gape_plan_stochastic; GS_EACH_GLOBAL is its table branch alone on the batch model's records (a batch model has no
+// dense or sparse rows); GS_EACH_LDS copies the root's own Sb * |A| records into LDS behind path[] -- before its first episode,
+// and again only when a workgroup's next root sits on another MDP -- and serves both table reads, the flags of an expansion and
+// the step's record, from there: a record's `next` lies inside the root's MDP (mp_model_load_table_batch checks it), so its index
+// is (state - base) * |A| + a.  Everything the each forms add sits under `if constexpr`
+// (profiles/gape_stoch_each_kernel_resources.txt).
+enum { GS_WHOLE = 0, GS_EACH_GLOBAL = 1, GS_EACH_LDS = 2 };
+
+template <int EACH>
 __global__ __launch_bounds__(64) void gape_stoch_kernel(GapeStochArgs p)
 {
     extern __shared__ int32_t path[]; // [2 * H + 1] records of the episode's walk: decision, chance, decision, ...
     const int lane = threadIdx.x, A = p.A, H = p.H, K = p.K, W = p.W;
-    const bool table = p.mode == MP_MODE_DETERMINISTIC;
+    constexpr bool lds_model = EACH == GS_EACH_LDS;
+    const bool table = EACH != GS_WHOLE || p.mode == MP_MODE_DETERMINISTIC;
+    Rec *lrec = nullptr;              // [Sb * A] GS_EACH_LDS: the root's table, 16-byte aligned behind path[]
+    if constexpr (lds_model) lrec = static_cast<Rec *>(__builtin_assume_aligned(path + ((2 * H + 1 + 3) & ~3), 16));
+    int base = 0, loaded = -1;        // GS_EACH_LDS: first global state of the root's MDP / index of the MDP in LDS
+    // the record of (GLOBAL state, action) index `sa` = state * |A| + a
+    auto rec_at = [&](long sa) -> const Rec & { return lds_model ? lrec[sa - (long)base * A] : p.rec[sa]; };
     const uint32_t done_bit = p.done_on_next ? 2u : 1u;
     for (int root = blockIdx.x; root < p.n_roots; root += p.grid) {
         const long slot = p.keep ? root : (root == 0 ? p.grid : blockIdx.x);
         GsNode *N = p.nodes + slot * p.cap;
         double *V = p.val + slot * p.cap * 2;
+        // GS_EACH_LDS: the root's table into LDS (the previous root's reads ended at the barrier that closes its iteration; this
+        // root's begin after the one below)
+        if constexpr (lds_model) {
+            const int mi = p.root_state[root] / p.Sb;
+            if (mi != loaded) {
+                base = mi * p.Sb;
+                wave_lds_records(lrec, p.rec, base, A, p.Sb, lane);
+                loaded = mi;
+            }
+        }
         if (lane == 0) {
             GsNode r;
             r.cum = 0.0; r.mu_ucb = 1.0; r.mu_lcb = 0.0; r.count = 0; r.key = p.root_state[root]; r.parent = -1; r.first_child = -1;
@@ -105,7 +133,7 @@ __global__ __launch_bounds__(64) void gape_stoch_kernel(GapeStochArgs p)
             for (int a0 = 0; a0 < A; a0 += 64) {
                 const int a = a0 + lane;
                 bool av = false;
-                if (a < A) av = table ? (p.rec[(long)state * A + a].flags & 4u) != 0 : (!p.avail || p.avail[(long)state * A + a] != 0);
+                if (a < A) av = table ? (rec_at((long)state * A + a).flags & 4u) != 0 : (!p.avail || p.avail[(long)state * A + a] != 0);
                 const unsigned long long bal = __ballot(av);
                 const int pos = pos0 + __popcll(bal & ((1ull << lane) - 1ull));
                 if (av) {
@@ -171,7 +199,7 @@ __global__ __launch_bounds__(64) void gape_stoch_kernel(GapeStochArgs p)
                 double r;
                 bool step_done;
                 if (table) {
-                    const Rec rc = p.rec[sa];
+                    const Rec rc = rec_at(sa);
                     sn = rc.next; r = rc.reward; step_done = (rc.flags & done_bit) != 0;
                 } else {
                     const uint64_t u = eg.next64() >> 11;          // Generator.random() of the clone's generator
@@ -309,6 +337,14 @@ inline FormName gape_stoch_form_name(int mode, bool keep)
              keep ? "" : "_slots");
     return n;
 }
+// mp_gape_plan_stochastic_models: the root's table in LDS or read from global memory, with the `_slots` suffix.  Listed by
+// mp_gape_stoch_each_form_names, part of no other list of names.
+inline FormName gape_stoch_each_form_name(bool lds, bool keep)
+{
+    FormName n;
+    snprintf(n.s, sizeof(n.s), "gape_stoch_each_%s%s", lds ? "lds" : "global", keep ? "" : "_slots");
+    return n;
+}
 
 } // namespace mp
 
@@ -316,25 +352,39 @@ using namespace mp;
 
 extern "C" {
 
-int mp_gape_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes,
-                            int32_t horizon, int32_t max_next_states, double gamma, double accuracy, int32_t continuation,
-                            int32_t n_actions_env, const int32_t *action_column, const double *thr_by_count,
-                            const double *transition_thr_by_count, const double *value_init, uint64_t *rng_state,
-                            int32_t max_plan_len, int32_t *plans, int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps,
-                            int32_t *status, double *child_lower, double *child_upper, int64_t *child_count,
-                            int32_t *best_challenger, int32_t mem)
+extern "C++" {
+namespace {
+// mp_gape_plan_stochastic (model_index NULL: `root_state` holds states of the one model) and mp_gape_plan_stochastic_models (a
+// batch model of deterministic tables, `root_state` LOCAL to the MDP model_index names: globalize_roots_arg makes the GLOBAL
+// states the kernel plans from, and the form is each_form's)
+int gape_stoch_plan_impl(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index, const int32_t *root_state,
+                         int32_t episodes, int32_t horizon, int32_t max_next_states, double gamma, double accuracy,
+                         int32_t continuation, int32_t n_actions_env, const int32_t *action_column, const double *thr_by_count,
+                         const double *transition_thr_by_count, const double *value_init, uint64_t *rng_state,
+                         int32_t max_plan_len, int32_t *plans, int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps,
+                         int32_t *status, double *child_lower, double *child_upper, int64_t *child_count,
+                         int32_t *best_challenger, int32_t mem, bool each)
 {
-    const char *const who = "mp_gape_plan_stochastic";
-    if (!ctx || !model || !root_state || !rng_state || !thr_by_count || !transition_thr_by_count || !value_init)
+    const char *const who = each ? "mp_gape_plan_stochastic_models" : "mp_gape_plan_stochastic";
+    if (!ctx || !model || !root_state || !rng_state || !thr_by_count || !transition_thr_by_count || !value_init ||
+        (each && !model_index))
         return fail(MP_ERR_ARG, "%s: NULL argument", who);
+    const int32_t mem_flags = mem;
     int rmem;
     MP_TRY(wave_mem(who, &mem, &rmem));
-    MP_TRY(wave_mdp_check(who, model, false)); // (a CartPole model is no finite MDP: MP_ERR_MODE)
+    if (each && model->mode != MP_MODE_DETERMINISTIC)
+        return fail(MP_ERR_MODE, "%s: model mode %d is not a deterministic table (a batch model has no dense or sparse rows)", who,
+                    model->mode);
+    MP_TRY(wave_mdp_check(who, model, each)); // (a CartPole model is no finite MDP: MP_ERR_MODE)
+    if (each && !model->table_batch)
+        return fail(MP_ERR_MODE, "%s: a batch model of deterministic tables (mp_model_load_table_batch) expected", who);
     const int A = model->A, K = max_next_states;
     if (K < 1 || K > 32) return fail(MP_ERR_ARG, "%s: max_next_states_count %d is not in 1..32 (a chance node's children fill half a wavefront)", who, K);
     const GapeTables host_tab{thr_by_count, transition_thr_by_count, value_init, nullptr};
     MP_TRY(gape_check_args(who, n_roots, episodes, horizon, 8192, max_plan_len, A, n_actions_env, gamma, accuracy, host_tab,
                            continuation, action_column));
+    std::vector<int32_t> global_tmp;
+    if (each) MP_TRY(globalize_roots_arg(ctx, model, n_roots, model_index, root_state, mem_flags, global_tmp, &root_state));
     MP_TRY(wave_roots(ctx, who, root_state, n_roots, model->S, mem));
     // every step of every episode may give a chance node its K placeholders and expand one decision node; the root expands once
     const long long per = ((long long)episodes + 2) * horizon;
@@ -346,7 +396,10 @@ int mp_gape_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const
     MP_TRY(gape_upload_tables(ctx, 43, episodes, horizon, n_actions_env, action_column, host_tab, &tab));
 
     // the launch of mp_gape_plan with a path of 2 * horizon + 1 records in LDS
-    const EachForm form = each_form_global(EACH_OLOP, 2 * horizon, n_roots, ctx->prop.multiProcessorCount);
+    a.Sb = each ? (model->Sb > 0 ? model->Sb : model->S) : 0;
+    const int cus = ctx->prop.multiProcessorCount;
+    const EachForm form = each ? each_form(EACH_GAPE_STOCH, a.Sb, A, horizon, n_roots, cus)
+                               : each_form_global(EACH_GAPE_STOCH, horizon, n_roots, cus);
     a.n_roots = n_roots; a.A = A; a.M = episodes; a.H = horizon; a.K = K; a.cap = (int)cap; a.done_on_next = model->done_on_next;
     a.uniform = continuation; a.n_env = n_actions_env; a.max_plan_len = max_plan_len; a.gamma = gamma; a.accuracy = accuracy;
     a.grid = form.grid; a.term = model->term; a.avail = model->masked ? model->avail : nullptr;
@@ -357,8 +410,65 @@ int mp_gape_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const
     gape_results_io(io, {plans, plan_len, episodes_run, status, best_challenger, env_steps, child_count, child_lower, child_upper},
                     &a.out, max_plan_len, A);
     MP_TRY(wave_stage(ctx, io));
-    MP_TRY(wave_launch(ctx, gape_stoch_kernel, a.grid, form.lds_bytes(), gape_stoch_form_name(model->mode, a.keep), a));
+    if (each)
+        MP_TRY(wave_launch(ctx, form.lds ? gape_stoch_kernel<GS_EACH_LDS> : gape_stoch_kernel<GS_EACH_GLOBAL>, a.grid,
+                           form.lds_bytes(), gape_stoch_each_form_name(form.lds, a.keep), a));
+    else
+        MP_TRY(wave_launch(ctx, gape_stoch_kernel<GS_WHOLE>, a.grid, form.lds_bytes(), gape_stoch_form_name(model->mode, a.keep), a));
     return wave_unstage(ctx, io);
+}
+} // namespace
+} // extern "C++"
+
+int mp_gape_plan_stochastic(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *root_state, int32_t episodes,
+                            int32_t horizon, int32_t max_next_states, double gamma, double accuracy, int32_t continuation,
+                            int32_t n_actions_env, const int32_t *action_column, const double *thr_by_count,
+                            const double *transition_thr_by_count, const double *value_init, uint64_t *rng_state,
+                            int32_t max_plan_len, int32_t *plans, int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps,
+                            int32_t *status, double *child_lower, double *child_upper, int64_t *child_count,
+                            int32_t *best_challenger, int32_t mem)
+{
+    return gape_stoch_plan_impl(ctx, model, n_roots, nullptr, root_state, episodes, horizon, max_next_states, gamma, accuracy,
+                                continuation, n_actions_env, action_column, thr_by_count, transition_thr_by_count, value_init,
+                                rng_state, max_plan_len, plans, plan_len, episodes_run, env_steps, status, child_lower, child_upper,
+                                child_count, best_challenger, mem, false);
+}
+
+int mp_gape_plan_stochastic_models(mp_ctx *ctx, mp_model *model, int32_t n_roots, const int32_t *model_index,
+                                   const int32_t *root_state, int32_t episodes, int32_t horizon, int32_t max_next_states,
+                                   double gamma, double accuracy, int32_t continuation, int32_t n_actions_env,
+                                   const int32_t *action_column, const double *thr_by_count, const double *transition_thr_by_count,
+                                   const double *value_init, uint64_t *rng_state, int32_t max_plan_len, int32_t *plans,
+                                   int32_t *plan_len, int32_t *episodes_run, int64_t *env_steps, int32_t *status,
+                                   double *child_lower, double *child_upper, int64_t *child_count, int32_t *best_challenger,
+                                   int32_t mem)
+{
+    return gape_stoch_plan_impl(ctx, model, n_roots, model_index, root_state, episodes, horizon, max_next_states, gamma, accuracy,
+                                continuation, n_actions_env, action_column, thr_by_count, transition_thr_by_count, value_init,
+                                rng_state, max_plan_len, plans, plan_len, episodes_run, env_steps, status, child_lower, child_upper,
+                                child_count, best_challenger, mem, true);
+}
+
+const char *mp_gape_stoch_each_form_names(void)
+{
+    static const std::string names = [] {
+        std::string out;
+        for (int lds = 1; lds >= 0; --lds)
+            for (int keep = 1; keep >= 0; --keep) { out += gape_stoch_each_form_name(lds != 0, keep != 0).s; out += '\n'; }
+        return out;
+    }();
+    return names.c_str();
+}
+
+int mp_gape_stoch_each_form_info(int32_t S_each, int32_t A, int32_t horizon, int32_t n_roots, int32_t cus, int64_t *out)
+{
+    if (!out) return fail(MP_ERR_ARG, "mp_gape_stoch_each_form_info: NULL output");
+    if (S_each < 1 || A < 1 || horizon < 1 || n_roots < 1 || cus < 1)
+        return fail(MP_ERR_ARG, "mp_gape_stoch_each_form_info: bad arguments");
+    const EachForm f = each_form(EACH_GAPE_STOCH, S_each, A, horizon, n_roots, cus);
+    out[0] = (int64_t)f.lds_need; out[1] = f.lds ? 1 : 0; out[2] = f.grid; out[3] = (int64_t)f.lds_bytes();
+    out[4] = (int64_t)kEachLdsDefaultBytes; out[5] = (int64_t)kLdsBytes;
+    return MP_OK;
 }
 
 const char *mp_gape_stoch_form_names(void)

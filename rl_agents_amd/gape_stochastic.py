@@ -11,6 +11,12 @@ Both are served by name from ``rl_agents_amd.agents.tree_search.mdp_gape``, whic
 They are defined in this module rather than in that one because the planner classes that modules of ``rl_agents_amd/agents``
 define form a closed table with what ``PerEpisodeEvaluation`` does with each; this planner inherits ``per_episode_kind = None``
 from ``MDPGapE`` and is refused there as ``MDPGapE`` is.
+
+One model per episode: the planner runs under two further names, defined here and served from that module in the same way.
+``PerEpisodeStochasticMDPGapE.plan_on(..., model_index=...)`` plans every root on its own deterministic table of a batch model
+(``mp_gape_plan_stochastic_models``) and offers ``PerEpisodeEvaluation`` the kind ``"gape_stoch"`` on request
+(``PerEpisodeEvaluation(envs, agent, kind="gape_stoch")``); ``PerEpisodeStochasticMDPGapEAgent`` plans with it.
+``StochasticMDPGapE`` itself keeps offering no kind and keeps refusing a ``model_index``, which earlier code relies on.
 """
 import numpy as np
 
@@ -28,9 +34,11 @@ class StochasticMDPGapE(MDPGapE):
     :class:`MDPGapE` keeps its name and its refusals, which earlier code may rely on.
 
     Refused: ``max_next_states_count`` above 32 (NotImplementedError) or below 1 (ValueError), ``step_strategy: "subtree"``,
-    a bound type other than ``"kullback-leibler"``, one model per episode (``per_episode_kind`` None), CartPole models."""
+    a bound type other than ``"kullback-leibler"``, CartPole models; by ``PerEpisodeEvaluation`` this class under any kind
+    (:class:`PerEpisodeStochasticMDPGapE` is the name the loop runs it under)."""
 
-    per_episode_kind_on_request = None        # mp_gape_plan_stochastic takes no batch model: refused also when asked for
+    per_episode_kind_on_request = None        # the loop refuses this name also when asked: PerEpisodeStochasticMDPGapE is run
+    plans_on_batch_models = False             # plan_on refuses a model_index under this name, as it always has
     accepts_stochastic_models = True          # OLOP.model_for: availability in listing order, the env's done rule
     MAX_NEXT_STATES = 32                      # a chance node's children fill half a wavefront
 
@@ -68,9 +76,12 @@ class StochasticMDPGapE(MDPGapE):
 
     def plan_on(self, model, root_states, root_steps, rng_states, model_index=None, max_plan_len=None, n_env=None):
         """Both tables by count, the initial values and the column map, and the one ``ctx.gape_plan_stochastic`` call.  The
-        transition thresholds are evaluated before the plan: what they raise is raised with the generator not advanced."""
-        if model_index is not None:
-            raise NotImplementedError("one model per episode: mp_gape_plan_stochastic takes no batch model")
+        transition thresholds are evaluated before the plan: what they raise is raised with the generator not advanced.
+        ``model_index``: a batch model of deterministic tables, one MDP per root (mp_gape_plan_stochastic_models), for a class
+        that ``plans_on_batch_models``."""
+        if model_index is not None and not self.plans_on_batch_models:
+            raise NotImplementedError("one model per episode: {} takes no batch model; PerEpisodeStochasticMDPGapE "
+                                      "does".format(type(self).__name__))
         cfg = self.config
         episodes, horizon = int(cfg["episodes"]), self.refuse_unbuilt_configs()
         thresholds = self.thresholds_or_first_step(len(root_states), rng_states)
@@ -83,9 +94,11 @@ class StochasticMDPGapE(MDPGapE):
         if not (np.isfinite(cfg["gamma"]) and np.isfinite(cfg["accuracy"])):
             raise ValueError("MDP-GapE: gamma and accuracy must be finite")
         n_env, column = self.action_columns(model, n_env)
-        return self.models.ctx.gape_plan_stochastic(model, root_states, episodes, horizon, int(cfg["max_next_states_count"]),
-                                                    cfg["gamma"], cfg["accuracy"], cfg["continuation_type"] == "uniform", n_env,
-                                                    column, thresholds, transition, self._value_init, rng_states)
+        run = (episodes, horizon, int(cfg["max_next_states_count"]), cfg["gamma"], cfg["accuracy"],
+               cfg["continuation_type"] == "uniform", n_env, column, thresholds, transition, self._value_init, rng_states)
+        if model_index is not None:
+            return self.models.ctx.gape_plan_stochastic_models(model, model_index, root_states, *run)
+        return self.models.ctx.gape_plan_stochastic(model, root_states, *run)
 
     def raise_for_result(self, out):
         failed = np.flatnonzero(out["status"] != native.MP_OK)
@@ -105,3 +118,18 @@ class StochasticMDPGapEAgent(MDPGapEAgent):
     ``max_next_states_count: 2`` (``FiniteMDPEnv``, ``SailingEnv``, ``DummyEnv``) run on deterministic, ``stochastic`` and
     ``sparse`` finite-MDP envs with only the ``__class__`` line changed.  :class:`MDPGapEAgent` keeps its name and its refusals."""
     PLANNER_TYPE = StochasticMDPGapE
+
+
+class PerEpisodeStochasticMDPGapE(StochasticMDPGapE):
+    """:class:`StochasticMDPGapE` under the name ``PerEpisodeEvaluation`` runs on request, ``kind="gape_stoch"``: one
+    ``plan_on(..., model_index=...)`` per lock-step on the episodes' own tables (``mp_gape_plan_stochastic_models``).  Unasked the loop refuses it as it refuses
+    :class:`MDPGapE`.  Everything else is inherited unchanged."""
+    per_episode_kind = None
+    per_episode_kind_on_request = "gape_stoch"
+    plans_on_batch_models = True
+
+
+class PerEpisodeStochasticMDPGapEAgent(StochasticMDPGapEAgent):
+    """:class:`StochasticMDPGapEAgent` planning with :class:`PerEpisodeStochasticMDPGapE`: the agent
+    ``PerEpisodeEvaluation(envs, agent, kind="gape_stoch")`` takes."""
+    PLANNER_TYPE = PerEpisodeStochasticMDPGapE

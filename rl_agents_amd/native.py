@@ -142,6 +142,10 @@ SIGNATURES = {
     "mp_gape_plan_stochastic": (C.c_int, [_vp, _vp, c_i32, _vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp,
                                           _vp, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
     "mp_gape_stoch_form_names": (C.c_char_p, []),
+    "mp_gape_plan_stochastic_models": (C.c_int, [_vp, _vp, c_i32, _vp, _vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_i32, c_i32, _vp, _vp,
+                                                 _vp, _vp, _vp, c_i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, c_i32]),
+    "mp_gape_stoch_each_form_names": (C.c_char_p, []),
+    "mp_gape_stoch_each_form_info": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, _vp]),
     "mp_gbop_create": (C.c_int, [_vp, _vp, c_i32, c_i32, c_i32, P(_vp)]),
     "mp_gbop_free": (C.c_int, [_vp]),
     "mp_gbop_plan": (C.c_int, [_vp, _vp, _vp, c_i32, c_i32, c_i32, c_f64, c_f64, c_f64, c_i32, c_i32, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -525,6 +529,21 @@ def gape_stoch_form_names():
     """The names an MDP-GapE plan with transition bounds (``gape_plan_stochastic``) records for Context.last_kernel_variant()
     (mp_gape_stoch_form_names; host only).  They are part of no other list of names."""
     return load().mp_gape_stoch_form_names().decode().split()
+
+
+def gape_stoch_each_form_names():
+    """The names an MDP-GapE plan with transition bounds on one MDP per root (``gape_plan_stochastic_models``)
+    records for Context.last_kernel_variant() (mp_gape_stoch_each_form_names; host only).  They are part of no other list."""
+    return load().mp_gape_stoch_each_form_names().decode().split()
+
+
+def gape_stoch_each_form_info(s_each, n_actions, horizon, n_roots, cus=256):
+    """The form ``gape_plan_stochastic_models`` takes for a call of this description
+    (mp_gape_stoch_each_form_info; host only, MP_EACH_MODEL is read): the dict of :func:`each_form_info`."""
+    out = np.zeros(6, np.int64)
+    _check(load().mp_gape_stoch_each_form_info(int(s_each), int(n_actions), int(horizon), int(n_roots), int(cus), _ptr(out)))
+    return dict(lds_bytes=int(out[0]), lds=bool(out[1]), grid=int(out[2]), launch_lds_bytes=int(out[3]), default_limit=int(out[4]),
+                fit_limit=int(out[5]))
 
 
 def gbop_form_names():
@@ -1446,10 +1465,24 @@ class Context(object):
         sparse model, for a batch of roots (host arrays): mp_gape_plan_stochastic.  Arguments and results as :meth:`gape_plan`,
         and ``transition_thr_by_count`` float64 [episodes + 2]: ``transition_threshold()`` by a chance node's count.
         ``status`` ERR_GAPE_PLACEHOLDERS where more next states were observed than placeholders.  :meth:`gape_stoch_tree`
-        serves the trees afterwards."""
+        serves the trees afterwards.  (One MDP per root: :meth:`gape_plan_stochastic_models`.)"""
         return self._gape_plan(self._lib.mp_gape_plan_stochastic, None, "gape_plan_stochastic", model, root_state, episodes, horizon,
                                gamma, accuracy, uniform, n_actions_env, action_column, thr_by_count, value_init, rng_state,
                                transition_thr_by_count=transition_thr_by_count, max_next_states=max_next_states)
+
+    def gape_plan_stochastic_models(self, model, model_index, root_state, episodes, horizon, max_next_states, gamma, accuracy, uniform,
+                                    n_actions_env, action_column, thr_by_count, transition_thr_by_count, value_init, rng_state):
+        """:meth:`gape_plan_stochastic` on a batch model of deterministic tables with one MDP per root
+        (mp_gape_plan_stochastic_models): ``model_index`` int [n], ``root_state`` local to the MDP it names; the remaining
+        arguments and the results are those of :meth:`gape_plan_stochastic`.  :meth:`gape_stoch_tree` serves the trees
+        afterwards, with global states.  (A method of its own, not a keyword of :meth:`gape_plan_stochastic`: that method's
+        signature is part of what the recorded planner calls pin.)"""
+        if model_index is None:
+            raise ValueError("gape_plan_stochastic_models: model_index [n] expected")
+        return self._gape_plan(None, self._lib.mp_gape_plan_stochastic_models, "gape_plan_stochastic_models", model, root_state,
+                               episodes, horizon, gamma, accuracy, uniform, n_actions_env, action_column, thr_by_count, value_init,
+                               rng_state, transition_thr_by_count=transition_thr_by_count, max_next_states=max_next_states,
+                               model_index=model_index)
 
     def gape_stoch_tree(self, root, cap=None):
         """BREADTH-FIRST arrays of root ``root``'s tree after the last gape_plan_stochastic, children in the reference's dict

@@ -15,7 +15,8 @@ Here N environments advance in lock-step and share ONE launch per step:
                                                                                       mp_uct_plan_models / mp_opd_plan_models /
                                                                                       mp_olop_plan_models / mp_brue_plan_models /
                                                                                       mp_ropd_plan_models; on request
-                                                                                      mp_gape_plan_models / mp_ss_plan_models)
+                                                                                      mp_gape_plan_models / mp_ss_plan_models /
+                                                                                      mp_gape_plan_stochastic_models)
                                        env_i.step(action_i)                          (host: the environments are host objects)
 
 Episode i draws from the generator a sequential ``Evaluation`` would give agent i (``np_random(sim_seed + i)``,
@@ -38,6 +39,8 @@ SET of M tables per step, held as one joint batch model -- ``mp_model_load_joint
 and planned on by ``mp_ropd_plan_models``; see :meth:`PerEpisodeEvaluation._sync_joint`); on request, by name --
 ``PerEpisodeEvaluation(..., kind="gape")`` / ``kind="ss"`` -- ``MDPGapEAgent`` (``mp_gape_plan_models``) and ``SparseSamplingAgent``
 (``mp_ss_plan_models``): the loop has always refused the two and still does unasked, since earlier code may rely on the refusal;
+``kind="gape_stoch"`` -- ``PerEpisodeStochasticMDPGapEAgent`` (MDP-GapE with ``max_next_states_count`` 1..32,
+``mp_gape_plan_stochastic_models``; ``StochasticMDPGapEAgent`` itself stays refused under any kind);
 their batch model carries the availability table in listing order, as OLOP's, and the one call per lock-step is the planner's own
 ``plan_on`` with its exceptions; environments: deterministic finite MDPs of one (S, A) shape, with or without restricted /
 re-ordered action sets (``get_available_actions``: the restriction must be the same table for every episode, as it is for
@@ -102,7 +105,7 @@ class PerEpisodeEvaluation(object):
         per episode.  ``max_steps``: episode length cap (default: the env's ``max_steps``, else 100).  ``kind``: what the loop does
         with the planner, by name -- the planner class's ``per_episode_kind`` (the default, None: that kind, or the refusal of
         a planner that declares none) or its ``per_episode_kind_on_request`` ("gape" for ``MDPGapEAgent``, "ss" for
-        ``SparseSamplingAgent``: planners this loop has always refused and still refuses unasked)."""
+        ``SparseSamplingAgent``, "gape_stoch" for ``PerEpisodeStochasticMDPGapEAgent``: planners this loop refuses unasked)."""
         self.envs, self.agent = list(envs), agent
         if not self.envs:
             raise ValueError("at least one environment")
@@ -318,7 +321,7 @@ class PerEpisodeEvaluation(object):
                                                    done_rule=first_spec.done_rule, max_steps=first_spec.max_steps)
             self.model.action_order = first_spec.action_order
             self._available = None if first_spec.available is None else first_spec.available.astype(bool)
-            if self._available is not None and self.kind in ("opd", "olop", "gape", "ss"):
+            if self._available is not None and self.kind in ("opd", "olop", "gape", "ss", "gape_stoch"):
                 # (MCTS reads availability through its policies, mcts.py:59-97: see _uct_policy)
                 self.model.set_available(np.tile(self._available, (n, 1)))
             self.uploads += len(live)

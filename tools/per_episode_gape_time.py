@@ -2,12 +2,16 @@
 """Plan time per lock-step of PerEpisodeEvaluation with MDPGapEAgent on request (kind="gape"), from ONE run on one machine.
 
     python tools/per_episode_gape_time.py [--episodes 4096] [--steps 6] [--out profiles/per_episode_gape.json]
+    python tools/per_episode_gape_time.py --kind gape_stoch [--out profiles/per_episode_gape_stoch.json]
 
 ChangingHighwayEnv: a (3, 4, 10) grid re-drawn after every step, restricted action sets listed IDLE first; the reference's
 HighwayEnv/agents/MDPGapEAgent/baseline.json (budget 100 -> 14 episodes of horizon 6, gamma 0.8, accuracy 0.1,
 "1*np.log(time)").  `plan_ms` is the loop's own call per lock-step -- thresholds, the one mp_gape_plan_models launch, results and
 the synchronisation; the first lock-step (model built, workspaces allocated) is reported apart from the mean of the others.  The
 entry "device_lock_step" of the output file is replaced; its other entries (the reference's CPU time) are kept.
+
+``--kind gape_stoch``: PerEpisodeStochasticMDPGapEAgent (mp_gape_plan_stochastic_models) with the "k2" config of
+tests/golden/per_episode_gape_stoch.npz -- horizon 3, 20 episodes, gamma 0.8, accuracy 0, max_next_states_count 2.
 """
 import argparse
 import json
@@ -20,16 +24,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 
 CONFIG = dict(budget=100, gamma=0.8, accuracy=0.1, upper_bound={"type": "kullback-leibler", "threshold": "1*np.log(time)"})
+CONFIG_STOCH = dict(horizon=3, episodes=20, gamma=0.8, accuracy=0.0, max_next_states_count=2,
+                    upper_bound={"type": "kullback-leibler", "threshold": "1*np.log(time)"})
 
 
-def timed_run(n, steps):
-    from rl_agents_amd.agents.tree_search.mdp_gape import MDPGapEAgent
+def timed_run(n, steps, kind="gape"):
+    from rl_agents_amd.agents.tree_search.mdp_gape import MDPGapEAgent, PerEpisodeStochasticMDPGapEAgent
     from rl_agents_amd.envs import ChangingHighwayEnv
     from rl_agents_amd.trainer.per_episode_evaluation import PerEpisodeEvaluation
     envs = [ChangingHighwayEnv(3, 4, 10, table_seed=20 * i, state=((i % 3) * 4 + (i % 4)) * 10, collision_rate=0.03 + 0.02 * (i % 4))
             for i in range(n)]
-    agent = MDPGapEAgent(envs[0], dict(CONFIG))
-    ev = PerEpisodeEvaluation(envs, agent, sim_seed=1, max_steps=steps, kind="gape")
+    agent = MDPGapEAgent(envs[0], dict(CONFIG)) if kind == "gape" else PerEpisodeStochasticMDPGapEAgent(envs[0], dict(CONFIG_STOCH))
+    ev = PerEpisodeEvaluation(envs, agent, sim_seed=1, max_steps=steps, kind=kind)
     plan_s, forms, live = [], [], []
     real = ev._plan
 
@@ -49,8 +55,11 @@ def timed_run(n, steps):
     ev.close()
     lock_steps = len(plan_s)
     pc = agent.planner.config
-    return dict(what="one run on one machine: PerEpisodeEvaluation(kind='gape') on ChangingHighwayEnv, MDPGapEAgent baseline config",
-                episodes=n, steps=steps, planner_episodes=int(pc["episodes"]), horizon=int(pc["horizon"]), lock_steps=lock_steps,
+    what = "one run on one machine: PerEpisodeEvaluation(kind='gape') on ChangingHighwayEnv, MDPGapEAgent baseline config"
+    if kind != "gape":
+        what = "one run on one machine: PerEpisodeEvaluation(kind='gape_stoch') on ChangingHighwayEnv, " \
+               "PerEpisodeStochasticMDPGapEAgent, the 'k2' config (max_next_states_count 2)"
+    return dict(what=what, episodes=n, steps=steps, planner_episodes=int(pc["episodes"]), horizon=int(pc["horizon"]), lock_steps=lock_steps,
                 live_per_lock_step=live, kernel_forms=forms, plan_ms_per_lock_step=[1e3 * s for s in plan_s],
                 plan_ms_first=1e3 * plan_s[0],
                 plan_ms_mean_after_first=1e3 * float(np.mean(plan_s[1:])) if lock_steps > 1 else None,
@@ -64,8 +73,9 @@ def main():
     ap.add_argument("--episodes", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kind", choices=("gape", "gape_stoch"), default="gape")
     args = ap.parse_args()
-    entry = timed_run(args.episodes, args.steps)
+    entry = timed_run(args.episodes, args.steps, args.kind)
     print(json.dumps(entry))
     if args.out:
         doc = {}
